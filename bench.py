@@ -29,11 +29,18 @@ Multi-GPU (`--shard`):
                   ranks (strong scaling: 16384 candidates in total), value = plan steps of 16384 candidates per second.
   `--config c5`   BASELINE configs[4]: zero-shot goal reaching, 8192 windows (64 environments x 1024 / 8 GPUs) per GPU and call
                   through the pruned many-window path, environment-sharded (no collective), value = windows/s.
-With --shard env at N > 1 GPUs (the default multi-GPU run) the line also carries `c4` (BASELINE configs[3], candidate-sharded
+With --full and --shard env at N > 1 GPUs the line also carries `c4` (BASELINE configs[3], candidate-sharded
 through RCCL's all-gather on the same ranks, strong scaling), `c2_candidates_strong` (the headline shape with its 1024 candidates
 sharded, `replicated_ms` beside it) and `rccl_ranks_seen`; these legs run behind the headline measurement under a wall-clock
 watchdog (`--collective-timeout`): a leg that hangs costs its own entry ({"error": "timeout"}), never the headline.
-At 1 GPU the line carries the legs `c5`, `c3` (walker2d critic N=4096) and `c4_shard` (2048 halfcheetah candidates at H=32/T=64).
+At 1 GPU with --full the line carries the legs `c5`, `c3` (walker2d critic N=4096) and `c4_shard` (2048 halfcheetah candidates at H=32/T=64).
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the headline: `metric`, `value`, `unit`, `ms_per_step`
+(wall time of the K timed steps / K), `higher_is_better`, `dtype`, the workload's `config` and the re-score statistics.  `--full`
+adds the side measurements behind it: `latency_ms` / `serial_steps_per_s`, `roofline` (instrumented passes), the 1-GPU extras and
+legs, `cpu_baseline` and `parity` (the oracle), the multi-GPU collective legs.  `--dump-outputs DIR` writes what the timed path
+returned in its last step (PLAN_OUTPUTS; config c5: mu / std) as DIR/<name>.npy; with the same arguments every run has the same
+inputs (seeded weights, window and generators).
 
 Prints ONE JSON line on rank 0.
 """
@@ -101,6 +108,33 @@ class _NoGcPause:
         return False
 
 
+# --dump-outputs of a plan step: what the caller of the timed path receives -- the pair (sample_action (1, A), eval_action (A,))
+# and the step's record (planner.last): selection probabilities, expected returns (re-scored, and the bf16 candidate pass), the
+# chosen indices, the policy's loc / std and the sampled candidate actions
+PLAN_OUTPUTS = ("sample_action", "eval_action", "p", "expect_return", "expect_return_bf16", "argmax", "sample_idx", "loc", "std",
+                "sample_actions")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy: float32 (float64 for float64 and integer tensors).  Past DUMP_LIMIT_BYTES in all,
+    every array beyond its even share keeps a fixed (seed 0) sample of its rows, and the row indices go to <name>.rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in arrays.items() if v is not None}
+    arrays = {k: v.double() if (v.dtype == torch.float64 or not v.is_floating_point()) else v.float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    share = DUMP_LIMIT_BYTES // (2 * max(len(arrays), 1))  # (room for the row indices)
+    for k, v in arrays.items():
+        a = v.numpy()
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share and a.ndim > 0:
+            per_row = max(a.nbytes // a.shape[0], 1)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(1, min(a.shape[0], share // per_row)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, f"{k}.rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
 def alg_flops(N, T, H, S, A, d=512, n_enc=2, mode="rtg"):
     """Algorithmic (exactly pruned) FLOPs of one plan step, SURVEY.md section 8(d)."""
     idx = T - H
@@ -137,10 +171,12 @@ def alg_flops_goal(E, T, H, S, A, d=512, n_enc=2):
     return E * (pass_a + pass_b)
 
 
-def goal_leg(local_rank, E, T=8, H=4, S=11, A=3, steps=20, warm=3, precisions=("bf16", "fp32"), world=1, fp32_steps=None):
+def goal_leg(local_rank, E, T=8, H=4, S=11, A=3, steps=20, warm=3, precisions=("bf16", "fp32"), world=1, fp32_steps=None,
+             outputs=None):
     """BASELINE configs[4] on this GPU: E zero-shot goal-reaching windows (config_hopper: T=8, H=4; 64 environments x 1024 over
     8 GPUs = 8192 windows per GPU) per call through the pruned many-window path (m3pc_goal_step_batch), windows resident in
-    HBM.  Per precision: ms per call (event-bracketed, the calls back to back), windows/s, the F_alg-based MFMA fraction."""
+    HBM.  Per precision: ms per call (event-bracketed, the calls back to back), windows/s, the F_alg-based MFMA fraction.
+    `outputs` (a dict): receives per precision what the last timed call returned, {"mu": (E, A), "std": (E, A)}."""
     import types
 
     from m3pc_amd import capi, synth
@@ -180,6 +216,8 @@ def goal_leg(local_rank, E, T=8, H=4, S=11, A=3, steps=20, warm=3, precisions=("
             dt = float(tt.item())
         dt /= n
         mus[prec] = out_buf[0].clone()
+        if outputs is not None:
+            outputs[prec] = {"mu": mus[prec], "std": out_buf[1].clone()}
         res[prec] = {"ms_per_call": round(1e3 * dt, 4), "windows_per_s": round(E / dt, 1), "calls": n,
                      "mfma_frac": round(alg_flops_goal(E, T, H, S, A) / dt / 1e12 / MFMA_PEAK_TFLOPS[prec], 4)}
     if "bf16" in mus and "fp32" in mus:
@@ -322,7 +360,16 @@ def main():
     ap.add_argument("--calibration-factor", type=float, default=0.0, help="delta = this x the calibration passes' largest deviation (0: the planner's default, 1.6)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU (tests/test_bench_launch_cpu.py): the ranks meet over gloo and rank 0 prints a stub line")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the headline, the side measurements as well: latency distribution, instrumented roofline passes, fp32 / "
+                         "closed-loop / shipped-config / other-config legs, CPU baseline, oracle parity, the collective legs of a "
+                         "multi-GPU run and config 5's fp32 leg.  Off: the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, "
+                         "float64 for indices; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn(args)
@@ -347,7 +394,7 @@ def main():
             assert float(t) == world * (world + 1) / 2
         if os.environ.get("M3PC_BENCH_FAIL_RANK") == str(rank):
             raise SystemExit(3)
-        if world > 1 and not args.no_collective_legs:
+        if world > 1 and args.full and not args.no_collective_legs:
             finish_with_collective_legs(args, out, rank, local_rank, world)
             return
         if rank == 0:
@@ -451,94 +498,98 @@ def main():
     else:
         units = args.steps * world                                # every rank completed K plan steps of N candidates
     value = units / elapsed
-
-    # per-step latency distribution: one step alone, serial, one event pair per step, outside the timed region
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 200))]
-    for e0, e1 in pairs:
-        e0.record()
-        step()
-        e1.record()
-    torch.cuda.synchronize()
-    lat = sorted(e0.elapsed_time(e1) for e0, e1 in pairs)
-    latency = {"p50": round(lat[len(lat) // 2], 4), "p99": round(lat[min(len(lat) - 1, int(0.99 * len(lat)))], 4),
-               "min": round(lat[0], 4), "steps": len(lat), "what": "one plan step alone (serial order), device time"}
+    if args.dump_outputs and rank == 0:  # (planner.last: the record of the last step resolved, i.e. the last timed step)
+        dump_outputs(args.dump_outputs, {k: planner.last.get(k) for k in PLAN_OUTPUTS})
 
     n_local = mdist_count(n_global, rank, world) if shard_cand else n_global
     prec = capi.PREC_BF16 if args.precision == "bf16" else capi.PREC_FP32
 
-    # roofline of the dominant kernel: a further, instrumented pass of the same K steps with hipEvents around every MFMA launch
-    # on the stream it runs on (events perturb the step time, so they are kept out of the timed region above)
-    def instrumented(pmode):
-        planner.handle.profile_enable(pmode)
-        planner.handle.profile_read(reset=True)
-        run(args.steps)
+    latency = roofline = None
+    if args.full:
+        # per-step latency distribution: one step alone, serial, one event pair per step, outside the timed region
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 200))]
+        for e0, e1 in pairs:
+            e0.record()
+            step()
+            e1.record()
         torch.cuda.synchronize()
-        cls_ = planner.handle.profile_read(prec, reset=False)
-        tail_ = planner.handle.profile_read(capi.PROF_LAYER_TAIL, reset=False)
-        all_ = planner.handle.profile_read(-1, reset=True)
-        planner.handle.profile_enable(3 if args.serial_halves else False)
-        return cls_, tail_, all_
+        lat = sorted(e0.elapsed_time(e1) for e0, e1 in pairs)
+        latency = {"p50": round(lat[len(lat) // 2], 4), "p99": round(lat[min(len(lat) - 1, int(0.99 * len(lat)))], 4),
+                   "min": round(lat[0], 4), "steps": len(lat), "what": "one plan step alone (serial order), device time"}
 
-    # as run: the steps pipelined and the two candidate halves on two streams exactly as in the timed region (a bracket also
-    # holds what the other streams do on the chip meanwhile) ...
-    (launches, gemm_ms, gemm_flops), (t_launches, t_ms, t_flops), (all_launches, all_ms, all_flops) = instrumented(True)
-    # ... and serial with the halves one after the other on one stream: the same launches, each alone on the chip
-    if args.no_alone_pass:
-        (a_launches, a_ms, a_flops), (at_launches, at_ms, at_flops) = (0, 0.0, 0.0), (0, 0.0, 0.0)
-    else:
-        d_keep, depth = depth, 0
-        (a_launches, a_ms, a_flops), (at_launches, at_ms, at_flops), _ = instrumented(2)
-        depth = d_keep
-    peak = MFMA_PEAK_TFLOPS[args.precision]
-    f_step = alg_flops(n_local, T, H, S, A, mode="critic" if critic_mode else "rtg")
-    cls = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    if t_launches:   # the dominant kernel: the fused layer tail (block_fused.hip)
-        achieved, dom_l, dom_ms, dom_fl = t_flops / (t_ms * 1e-3) / 1e12, t_launches, t_ms, t_flops
-        al_l, al_ms, al_fl = at_launches, at_ms, at_flops
-        kname = ("m3pc::block_fused_kernel (layer tail: out-proj + residual + LayerNorm + Linear/GELU/Linear + residual + LayerNorm "
-                 "[+ the next encoder layer's Q|K|V projection | + the two scalar output heads], one launch per layer and "
-                 "candidate half)")
-    else:            # fp32 mode / shapes the fused kernel does not cover: the GEMM class
-        achieved, dom_l, dom_ms, dom_fl = cls, launches, gemm_ms, gemm_flops
-        al_l, al_ms, al_fl = a_launches, a_ms, a_flops
-        kname = f"the {args.precision} MFMA GEMM launches (gemm_line_kernel / gemm_glds_ring3_kernel / gemm_kernel)"
-    alone = al_fl / (al_ms * 1e-3) / 1e12 if al_ms > 0 else None
-    step_s = elapsed / args.steps
-    # `frac` is the kernel's own efficiency: every launch ALONE on the chip (serial order, the halves one after the other on one
-    # stream, m3pc_profile_enable(h, 2)) -- the figure whose launches-per-step x duration fits inside ms_per_step and that
-    # profiles/r05_kernel_stats_alone.csv reproduces.  `as_run` holds the brackets of the same launches as the timed region runs
-    # (steps pipelined, halves on two streams): concurrent brackets overlap, so their sum exceeds the step -- sharing, not efficiency.
-    as_run = {"avg_launch_us": 1e3 * dom_ms / max(dom_l, 1), "achieved": round(achieved, 2), "frac": round(achieved / peak, 4),
-              "kernel_ms_per_step": dom_ms / args.steps,
-              "note": "HIP-event brackets as the timed region runs: steps pipelined, the two candidate halves on two streams -- a bracket "
-                      "also holds what the other streams run on the chip meanwhile; brackets of concurrent launches overlap (their sum "
-                      "may exceed ms_per_step)"}
-    if alone is not None:
-        top = {"achieved": round(alone, 2), "frac": round(alone / peak, 4), "avg_launch_us": 1e3 * al_ms / max(al_l, 1),
-               "kernel_ms_per_step": al_ms / args.steps, "arrangement": "alone: serial order, candidate halves one after the other on one stream"}
-    else:
-        top = {"achieved": as_run["achieved"], "frac": as_run["frac"], "avg_launch_us": as_run["avg_launch_us"],
-               "kernel_ms_per_step": as_run["kernel_ms_per_step"], "arrangement": "as run (--no-alone-pass)"}
-    roofline = {"bound": "mfma", "achieved": top["achieved"], "peak": peak, "unit": "TFLOP/s",
-                "frac": top["frac"], "traffic": pmc_traffic(args.precision),
-                "peak_measured": 1800.0 if args.precision == "bf16" else None,  # register-resident v_mfma loop at the 1.75 GHz the chip holds
-                "kernel": kname,
-                "flops_per_launch": dom_fl / max(dom_l, 1), "avg_launch_us": top["avg_launch_us"],
-                "launches_per_step": dom_l / args.steps, "kernel_ms_per_step": top["kernel_ms_per_step"],
-                "arrangement": top["arrangement"],
-                "note": "HIP-event brackets on the stream of each launch in instrumented passes of the same K steps (outside the timed "
-                        "region): achieved = algorithmic flops per launch / average launch duration with every launch alone on the chip",
-                "as_run": as_run,
-                "alone": None if alone is None else {"avg_launch_us": 1e3 * al_ms / max(al_l, 1), "achieved": round(alone, 2),
-                                                      "frac": round(alone / peak, 4)},
-                # every MFMA launch of the compute dtype (fused tails, fused decoder input, Q|K|V / head GEMMs)
-                "mfma_class": {"achieved": round(cls, 2), "frac": round(cls / peak, 4), "launches_per_step": launches / args.steps,
-                               "ms_per_step": gemm_ms / args.steps},
-                "all_gemm_ms_per_step": all_ms / args.steps, "all_gemm_launches_per_step": all_launches / args.steps,
-                "step_alg_tflop": round(f_step / 1e12, 4),
-                "step_mfma_frac": round(f_step / step_s / 1e12 / peak, 4),  # per GPU: this rank's flops over this rank's step time
-                "step_alg_bytes": alg_bytes(n_local, T, S, A),
-                "step_hbm_frac_alg": round(alg_bytes(n_local, T, S, A) / step_s / 1e9 / HBM_PEAK_GBS, 5)}
+        # roofline of the dominant kernel: a further, instrumented pass of the same K steps with hipEvents around every MFMA launch
+        # on the stream it runs on (events perturb the step time, so they are kept out of the timed region above)
+        def instrumented(pmode):
+            planner.handle.profile_enable(pmode)
+            planner.handle.profile_read(reset=True)
+            run(args.steps)
+            torch.cuda.synchronize()
+            cls_ = planner.handle.profile_read(prec, reset=False)
+            tail_ = planner.handle.profile_read(capi.PROF_LAYER_TAIL, reset=False)
+            all_ = planner.handle.profile_read(-1, reset=True)
+            planner.handle.profile_enable(3 if args.serial_halves else False)
+            return cls_, tail_, all_
+
+        # as run: the steps pipelined and the two candidate halves on two streams exactly as in the timed region (a bracket also
+        # holds what the other streams do on the chip meanwhile) ...
+        (launches, gemm_ms, gemm_flops), (t_launches, t_ms, t_flops), (all_launches, all_ms, all_flops) = instrumented(True)
+        # ... and serial with the halves one after the other on one stream: the same launches, each alone on the chip
+        if args.no_alone_pass:
+            (a_launches, a_ms, a_flops), (at_launches, at_ms, at_flops) = (0, 0.0, 0.0), (0, 0.0, 0.0)
+        else:
+            d_keep, depth = depth, 0
+            (a_launches, a_ms, a_flops), (at_launches, at_ms, at_flops), _ = instrumented(2)
+            depth = d_keep
+        peak = MFMA_PEAK_TFLOPS[args.precision]
+        f_step = alg_flops(n_local, T, H, S, A, mode="critic" if critic_mode else "rtg")
+        cls = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        if t_launches:   # the dominant kernel: the fused layer tail (block_fused.hip)
+            achieved, dom_l, dom_ms, dom_fl = t_flops / (t_ms * 1e-3) / 1e12, t_launches, t_ms, t_flops
+            al_l, al_ms, al_fl = at_launches, at_ms, at_flops
+            kname = ("m3pc::block_fused_kernel (layer tail: out-proj + residual + LayerNorm + Linear/GELU/Linear + residual + LayerNorm "
+                     "[+ the next encoder layer's Q|K|V projection | + the two scalar output heads], one launch per layer and "
+                     "candidate half)")
+        else:            # fp32 mode / shapes the fused kernel does not cover: the GEMM class
+            achieved, dom_l, dom_ms, dom_fl = cls, launches, gemm_ms, gemm_flops
+            al_l, al_ms, al_fl = a_launches, a_ms, a_flops
+            kname = f"the {args.precision} MFMA GEMM launches (gemm_line_kernel / gemm_glds_ring3_kernel / gemm_kernel)"
+        alone = al_fl / (al_ms * 1e-3) / 1e12 if al_ms > 0 else None
+        step_s = elapsed / args.steps
+        # `frac` is the kernel's own efficiency: every launch ALONE on the chip (serial order, the halves one after the other on one
+        # stream, m3pc_profile_enable(h, 2)) -- the figure whose launches-per-step x duration fits inside ms_per_step and that
+        # profiles/r05_kernel_stats_alone.csv reproduces.  `as_run` holds the brackets of the same launches as the timed region runs
+        # (steps pipelined, halves on two streams): concurrent brackets overlap, so their sum exceeds the step -- sharing, not efficiency.
+        as_run = {"avg_launch_us": 1e3 * dom_ms / max(dom_l, 1), "achieved": round(achieved, 2), "frac": round(achieved / peak, 4),
+                  "kernel_ms_per_step": dom_ms / args.steps,
+                  "note": "HIP-event brackets as the timed region runs: steps pipelined, the two candidate halves on two streams -- a bracket "
+                          "also holds what the other streams run on the chip meanwhile; brackets of concurrent launches overlap (their sum "
+                          "may exceed ms_per_step)"}
+        if alone is not None:
+            top = {"achieved": round(alone, 2), "frac": round(alone / peak, 4), "avg_launch_us": 1e3 * al_ms / max(al_l, 1),
+                   "kernel_ms_per_step": al_ms / args.steps, "arrangement": "alone: serial order, candidate halves one after the other on one stream"}
+        else:
+            top = {"achieved": as_run["achieved"], "frac": as_run["frac"], "avg_launch_us": as_run["avg_launch_us"],
+                   "kernel_ms_per_step": as_run["kernel_ms_per_step"], "arrangement": "as run (--no-alone-pass)"}
+        roofline = {"bound": "mfma", "achieved": top["achieved"], "peak": peak, "unit": "TFLOP/s",
+                    "frac": top["frac"], "traffic": pmc_traffic(args.precision),
+                    "peak_measured": 1800.0 if args.precision == "bf16" else None,  # register-resident v_mfma loop at the 1.75 GHz the chip holds
+                    "kernel": kname,
+                    "flops_per_launch": dom_fl / max(dom_l, 1), "avg_launch_us": top["avg_launch_us"],
+                    "launches_per_step": dom_l / args.steps, "kernel_ms_per_step": top["kernel_ms_per_step"],
+                    "arrangement": top["arrangement"],
+                    "note": "HIP-event brackets on the stream of each launch in instrumented passes of the same K steps (outside the timed "
+                            "region): achieved = algorithmic flops per launch / average launch duration with every launch alone on the chip",
+                    "as_run": as_run,
+                    "alone": None if alone is None else {"avg_launch_us": 1e3 * al_ms / max(al_l, 1), "achieved": round(alone, 2),
+                                                          "frac": round(alone / peak, 4)},
+                    # every MFMA launch of the compute dtype (fused tails, fused decoder input, Q|K|V / head GEMMs)
+                    "mfma_class": {"achieved": round(cls, 2), "frac": round(cls / peak, 4), "launches_per_step": launches / args.steps,
+                                   "ms_per_step": gemm_ms / args.steps},
+                    "all_gemm_ms_per_step": all_ms / args.steps, "all_gemm_launches_per_step": all_launches / args.steps,
+                    "step_alg_tflop": round(f_step / 1e12, 4),
+                    "step_mfma_frac": round(f_step / step_s / 1e12 / peak, 4),  # per GPU: this rank's flops over this rank's step time
+                    "step_alg_bytes": alg_bytes(n_local, T, S, A),
+                    "step_hbm_frac_alg": round(alg_bytes(n_local, T, S, A) / step_s / 1e9 / HBM_PEAK_GBS, 5)}
 
     out = None
     if rank == 0:
@@ -568,21 +619,20 @@ def main():
                           "candidates_per_gpu": n_local, "global_candidates": n_global, "horizon": H, "traj_length": T,
                           "steps_in_flight": depth, "settle_steps": args.settle, "parallelism": par},
                # what `value` is and is not: the rate of INDEPENDENT plan steps with `steps_in_flight` of them in
-               # flight; one step alone -- what a single environment's loop can use -- is serial_steps_per_s
-               "serial_steps_per_s": round(1e3 / latency["p50"], 2),
-               "latency_ms": latency, "roofline": roofline,
+               # flight; one step alone -- what a single environment's loop can use -- is serial_steps_per_s (--full)
+               **({"serial_steps_per_s": round(1e3 / latency["p50"], 2), "latency_ms": latency, "roofline": roofline} if args.full else {}),
                "rescore": {"mode": args.rescore, "n_mean": round(sum(n_re) / max(len(n_re), 1), 2), "n_max": max(n_re) if n_re else None,
                            "delta": planner.last.get("delta"), "delta_grown": planner.delta_grown,
                            "min_margin_outside": planner.last.get("min_margin_outside")}}
-        if shard_cand and args.strong:
+        if shard_cand and args.strong and args.full:
             # what every rank repeats whatever the shard size: the policy pass and the re-score + select
             out["replicated_ms"] = round(latency["p50"] - candidate_only_ms(planner, mode, states, actions, rewards, h), 4)
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             try:
                 out.update(extras(args, dims, cfg, hist, planner, S, A))
             except Exception as e:  # the side measurements never take the headline down with them
                 out["extras_error"] = repr(e)[:300]
-        if world == 1 and not args.no_cpu_baseline and args.config == "c2":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.config == "c2":
             base, ref, eps = cpu_baseline(dims, dict(horizon=H, action_samples=args.candidates), hist, 3.0)
             out["cpu_baseline"] = base
             if not args.no_extras and args.guidance == "rtg_guiding":
@@ -590,7 +640,7 @@ def main():
                     out["parity"] = parity(args, dims, cfg, hist, ref, eps)
                 except Exception as e:
                     out["parity_error"] = repr(e)[:300]
-    if world > 1 and not shard_cand and args.config == "c2" and not args.no_collective_legs:
+    if world > 1 and not shard_cand and args.config == "c2" and args.full and not args.no_collective_legs:
         planner.handle.close()
         finish_with_collective_legs(args, out, rank, local_rank, world)
         return
@@ -658,9 +708,12 @@ def main_c5(args, rank, local_rank, world):
     value = windows planned per second over all ranks."""
     E = args.windows
     T, H, S, A = 8, 4, 11, 3   # zeroshot_omtm/config_hopper.yaml:6,78
-    precs = (args.precision,) if args.no_extras else (("bf16", "fp32") if args.precision == "bf16" else ("fp32",))
+    precs = (args.precision,) if args.no_extras or not args.full else (("bf16", "fp32") if args.precision == "bf16" else ("fp32",))
+    outputs = {}
     res = goal_leg(local_rank, E, T, H, S, A, steps=args.steps, warm=max(args.warmup, 1), precisions=precs, world=world,
-                   fp32_steps=max(3, args.steps // 8))
+                   fp32_steps=args.steps if args.precision == "fp32" else max(3, args.steps // 8), outputs=outputs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs[args.precision])
     if rank == 0:
         r = res[args.precision]
         out = {"metric": "zero-shot goal-reaching windows/sec (zeroshot_omtm config_hopper, 64 envs x N=1024)",

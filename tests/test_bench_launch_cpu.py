@@ -36,9 +36,9 @@ def test_bench_single_process_needs_no_launcher():
 
 
 def test_multi_gpu_default_runs_the_collective_legs():
-    """N > 1 without flags: behind the headline, the candidate-sharded legs run through the all-gather of the data path (gloo
-    here) and the line says how many ranks that collective saw."""
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1"])
+    """N > 1 with --full and no other flag: behind the headline, the candidate-sharded legs run through the all-gather of the data
+    path (gloo here) and the line says how many ranks that collective saw."""
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     assert d["rccl_ranks_seen"] == 2 and "c4" in d and "c2_candidates_strong" in d
@@ -50,7 +50,7 @@ def test_a_hung_collective_leg_costs_its_entry_not_the_headline():
     out and every rank exits with code 0."""
     import time
     t0 = time.time()
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--collective-timeout", "4"], {"M3PC_BENCH_HANG_LEG": "1"})
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--full", "--collective-timeout", "4"], {"M3PC_BENCH_HANG_LEG": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert time.time() - t0 < 120
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -65,7 +65,7 @@ def test_a_rank_that_fails_in_a_leg_is_reported_at_once_with_its_message():
     line carries the message and "collective_legs_ok": false."""
     import time
     t0 = time.time()
-    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--collective-timeout", "200"], {"M3PC_BENCH_FAIL_LEG_RANK": "1"})
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--full", "--collective-timeout", "200"], {"M3PC_BENCH_FAIL_LEG_RANK": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert time.time() - t0 < 90
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
@@ -73,7 +73,23 @@ def test_a_rank_that_fails_in_a_leg_is_reported_at_once_with_its_message():
 
 
 def test_no_collective_legs_flag():
-    r = _run(["--gpus", "2", "--no-collective-legs"])
+    r = _run(["--gpus", "2", "--full", "--no-collective-legs"])
     assert r.returncode == 0
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert "c4" not in d
+
+
+def test_plain_multi_gpu_run_is_the_headline_alone():
+    """Without --full a run measures its headline and nothing else: no collective legs behind it, and a leg that would hang is
+    never entered."""
+    r = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--collective-timeout", "4"], {"M3PC_BENCH_HANG_LEG": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 5 and not {"c4", "c4_pipelined", "c4_full", "c2_candidates_strong", "rccl_ranks_seen"} & set(d)
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr

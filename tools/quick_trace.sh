@@ -4,8 +4,9 @@ set -euo pipefail
 : "${GRAFT_REPO_ROOT:?run on the GPU box}"
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
-rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_trace -o kt --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-alone-pass --depth 0 "$@" > gpurun_out/${TAG}_trace.log 2>&1
-python3 tools/step_timeline.py gpurun_out/${TAG}_trace gpurun_out/${TAG}_step_timeline.txt > /dev/null
-find gpurun_out/${TAG}_trace -name "*kernel_stats.csv" -exec cp {} gpurun_out/${TAG}_kernel_stats.csv \;
-rm -rf gpurun_out/${TAG}_trace
+OUT=${OUT:-profile_out}  # where the traces, counters and logs go
+mkdir -p "$OUT"
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_trace -o kt --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-alone-pass --depth 0 "$@" > $OUT/${TAG}_trace.log 2>&1
+python3 tools/step_timeline.py $OUT/${TAG}_trace $OUT/${TAG}_step_timeline.txt > /dev/null
+find $OUT/${TAG}_trace -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_kernel_stats.csv \;
+rm -rf $OUT/${TAG}_trace
