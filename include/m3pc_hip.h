@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-/* ABI history.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
+/* ABI history.  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
+ * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
  * that passed the 5-float block of m3pc_topk_window must pass 8.  Inside the library: a bf16 candidate pass carries its residual
  * stream between the encoder layers in bf16 and runs the output heads' last Linear on bf16 hidden rows (scores move within the
@@ -50,7 +52,7 @@ extern "C" {
  * draw of the bf16 plan step); M3PC_PLAN_PRUNED_POLICY; m3pc_profile_enable(h, 3); the handle holds two chain workspaces per kind,
  * picked by the parity of m3pc_plan_args::slot.  v4: m3pc_goal_step_batch, m3pc_dims::max_goal_batch.  v3: M3PC_PLAN_DEFER_JOIN,
  * m3pc_candidate_join.  No structure changed layout in v5. */
-#define M3PC_ABI_VERSION 6
+#define M3PC_ABI_VERSION 7
 
 #define M3PC_OK 0
 #define M3PC_EINVAL (-1)   /* bad argument / shape mismatch            */
@@ -74,6 +76,10 @@ extern "C" {
 #define M3PC_PREC_FP32 0  /* fp32 operands, f32 MFMA (v_mfma_f32_32x32x2_f32), fp32 accumulate */
 #define M3PC_PREC_BF16 1  /* bf16 operands, bf16 MFMA (v_mfma_f32_32x32x16_bf16), fp32 accumulate,
                              fp32 residual stream / LayerNorm / softmax */
+#define M3PC_PREC_BF16X3 2 /* split bf16: the fp32 pass (fp32 activations, residual stream, attention, LayerNorm, heads) with its
+                              weight GEMMs (K >= 32) as x = hi + lo, hi = bf16(x), lo = bf16(x - hi) (round to nearest even) for both
+                              operands and a.w = a_hi.w_hi + a_hi.w_lo + a_lo.w_hi: three v_mfma_f32_32x32x16_bf16 per k-step into
+                              one fp32 accumulator (relative error ~2^-16 per product) */
 
 typedef struct m3pc_handle m3pc_handle;
 
@@ -211,7 +217,8 @@ int m3pc_goal_step(m3pc_handle* h, int batch, const float* states, const float* 
  *   idx        T - h; the masks are built inside (plan tables cached per idx)
  *   goal_mode  M3PC_GOAL_PIID: action_piid_sample (learner.py:151-261), both forwards;
  *              M3PC_GOAL_ID:   action_id_sample (learner.py:60-149), one forward under the gid mask (masks.py:50-69)
- *   precision  M3PC_PREC_BF16: bf16 MFMA kernels of the candidate pass (fused layer tails); M3PC_PREC_FP32: fp32 MFMA.
+ *   precision  M3PC_PREC_BF16: bf16 MFMA kernels of the candidate pass (fused layer tails); M3PC_PREC_FP32: fp32 MFMA;
+ *              M3PC_PREC_BF16X3: the fp32 pass with split-bf16 weight GEMMs (see M3PC_PREC_BF16X3).
  *              Either way a window's result does not depend on which other windows share the call, as long as the
  *              batch sizes fall in the same kernel regime (environment sharding: no collective).  fp32: bit-identical at any
  *              batch size.  bf16: bit-identical between calls of the same regime; the regime boundaries are >= 2048 windows

@@ -12,7 +12,8 @@
 extern "C" {
 #endif
 
-/* one GEMM launch of the library's dispatch on caller tensors (dtype 0 fp32 / 1 bf16 operands):
+/* one GEMM launch of the library's dispatch on caller tensors (dtype 0 fp32 / 1 bf16 operands / 2 split-bf16: A and W fp32,
+ * W split into hi / lo bf16 copies inside the call, gemm_x3.hip; variant 1 there: no split-K workspace):
  * C = epilogue(A (M,K) W (N,K)^T + bias [gelu] [+ res]); variant selects a kernel configuration (0: dispatch) */
 int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias, const float* res, void* C, int M, int N,
                     int K, int gelu, int f32out, int variant, void* stream);

@@ -19,11 +19,20 @@ LIB_PATH = os.environ.get("M3PC_LIB") or os.path.join(_HERE, "libm3pc_hip.so")  
 STATES, ACTIONS, REWARDS, RETURNS = 0, 1, 2, 3
 KEYS = ("states", "actions", "rewards", "returns")
 MODE_RTG, MODE_CRITIC, MODE_NOISE = 0, 1, 2
-PREC_FP32, PREC_BF16 = 0, 1
+PREC_FP32, PREC_BF16, PREC_BF16X3 = 0, 1, 2  # M3PC_PREC_*: BF16X3 is the fp32 pass with split-bf16 weight GEMMs (3 bf16 MFMAs)
+PRECISIONS = {"fp32": PREC_FP32, "bf16": PREC_BF16, "bf16x3": PREC_BF16X3}
+LOW_PRECISION = (PREC_BF16, PREC_BF16X3)  # candidate passes whose scores the certified fp32 re-score follows
 PROF_LAYER_TAIL = 16  # m3pc_profile_read: the fused layer-tail launches only
-ABI_VERSION = 6
+ABI_VERSION = 7
 GOAL_PIID, GOAL_ID = 0, 1  # m3pc_goal_step_batch goal_mode
 SLOTS = 4  # M3PC_SLOTS: plan steps in flight per handle
+
+
+def precision_code(name: str) -> int:
+    """M3PC_PREC_* of a precision name ("fp32", "bf16", "bf16x3"); ValueError for anything else."""
+    if name not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {name!r}")
+    return PRECISIONS[name]
 
 EXPORTS = (
     "m3pc_last_error", "m3pc_abi_version", "m3pc_create", "m3pc_destroy", "m3pc_load_weights", "m3pc_load_stats",

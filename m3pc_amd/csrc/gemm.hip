@@ -305,6 +305,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(GemmP p, int S, i
         }
 }
 
+int launch_splitk_reduce(const GemmP& p, int S, int exact_gelu, hipStream_t st) {
+    if (p.ln_g && p.ln_out && p.Cf && !p.Cb && p.cmap.rpg == 0 && p.N % 256 == 0 && p.N <= 1024 && p.ldc % 4 == 0 &&
+        (!p.res || p.ldr % 4 == 0)) {
+        hipLaunchKernelGGL(splitk_reduce_ln_kernel, dim3((p.M + 3) / 4), dim3(256), 0, st, p, S, exact_gelu);
+        return 1;
+    }
+    const long long n = (long long)p.M * p.N;
+    const int g = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p, S, exact_gelu);
+    return 0;
+}
+
 template <typename T, int BM, int BN, int EPI>
 static void launch_cfg(const GemmP& p, hipStream_t st) {
     const int grid = ((p.M + BM - 1) / BM) * (p.N / BN);
@@ -333,14 +345,7 @@ static int launch_epi(const GemmP& p, hipStream_t st) {
         }
         if (S > 1) {
             hipLaunchKernelGGL((gemm_kernel<T, 64, 64, EPI_SPLITK>), dim3((unsigned)tiles, S), dim3(256), 0, st, p);
-            if (p.ln_g && p.ln_out && p.Cf && !p.Cb && p.cmap.rpg == 0 && p.N % 256 == 0 && p.N <= 1024 && p.ldc % 4 == 0 &&
-                (!p.res || p.ldr % 4 == 0)) {
-                hipLaunchKernelGGL(splitk_reduce_ln_kernel, dim3((p.M + 3) / 4), dim3(256), 0, st, p, S, (int)(sizeof(T) == 4));
-                return 1;
-            }
-            const long long n = (long long)p.M * p.N;
-            const int g = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p, S, (int)(sizeof(T) == 4));
+            return launch_splitk_reduce(p, S, (int)(sizeof(T) == 4), st);
         } else {
             launch_cfg<T, 64, 64, EPI>(p, st);
         }

@@ -13,7 +13,7 @@
 
 namespace m3pc {
 
-enum { GE_GELU = 1, GE_RES = 2, GE_ROWTAB = 4, GE_F32OUT = 8 };
+enum { GE_GELU = 1, GE_RES = 2, GE_ROWTAB = 4, GE_F32OUT = 8, GE_GELU_EXACT = 16 };  // GE_GELU_EXACT (with GE_GELU): libm erff
 
 typedef float ge_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -31,6 +31,9 @@ __device__ __forceinline__ float ge_gelu(float x) {
     const float hx = 0.5f * x;
     return fmaf(fabsf(hx), erf_abs, hx);
 }
+
+// exact-erf GELU through libm erff: the fp32 arithmetic (gemm.hip gelu_exact), for the split-bf16 kernel (gemm_x3.hip)
+__device__ __forceinline__ float ge_gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // the same arithmetic on two values at once: the polynomial runs on v_pk_fma_f32 / v_pk_mul_f32 (two fp32 lanes per
 // instruction), which halves its VALU cost; every operation and its order match ge_gelu, so the results are identical
@@ -92,7 +95,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, ge_f32x16 (&acc)[T
                 float vj[TN];
 #pragma unroll
                 for (int j = 0; j < TN; ++j) vj[j] = acc[i][j][reg] + bj[j];
-                if constexpr ((EPI & GE_GELU) != 0) {
+                if constexpr ((EPI & GE_GELU) != 0 && (EPI & GE_GELU_EXACT) != 0) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) vj[j] = ge_gelu_erf(vj[j]);
+                } else if constexpr ((EPI & GE_GELU) != 0) {
                     if constexpr (TN % 2 == 0) {
 #pragma unroll
                         for (int j = 0; j < TN; j += 2) {
@@ -132,7 +138,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, ge_f32x16 (&acc)[T
                     const int c = cbase + j * 32 + l31;
                     float v = acc[i][j][reg] + bj[j];
                     if constexpr (EPI & GE_ROWTAB) v += p.rowtab[(long long)(r % p.rt_mod) * p.rt_ld + c];
-                    if constexpr (EPI & GE_GELU) v = ge_gelu(v);
+                    if constexpr (EPI & GE_GELU) v = (EPI & GE_GELU_EXACT) ? ge_gelu_erf(v) : ge_gelu(v);
                     if constexpr (EPI & GE_RES) v += p.res[pr * p.ldr + c];
                     if constexpr (EPI & GE_F32OUT)
                         p.Cf[pr * p.ldc + c] = v;

@@ -15,7 +15,8 @@ namespace m3pc {
 
 typedef __bf16 bf16_t;
 
-enum DType { DT_F32 = 0, DT_BF16 = 1 };
+// DT_X3: fp32 activations times split-bf16 weights (gemm_x3.hip) -- a GEMM arithmetic only, never the dtype of a pass's operands
+enum DType { DT_F32 = 0, DT_BF16 = 1, DT_X3 = 2 };
 
 static inline size_t dtype_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 
@@ -83,6 +84,8 @@ struct GemmP {
     // normalised on the fly while the operand is loaded (the arithmetic of layernorm_vec_kernel, bit for bit)
     const float* a_ln_g;
     const float* a_ln_b;
+    // split-bf16 kernel only (launch_gemm_x3): W points at the hi bf16 copy, the lo copy sits w_lo_off elements behind it
+    long long w_lo_off;
 };
 // The scalar output heads (D_k == 1) of a few-row fp32 pass in one launch (gemm_f32_direct.hip: head_f32_fused_kernel):
 // out[s][r] = w2[s] . gelu(W1[s] LN_B[s](LN_A(x)) + b1[s]) + b2[s] [* stdv + mean], x = row (r / grp) * row_mod + s * grp + r % grp of X
@@ -103,6 +106,12 @@ struct HeadFusedP {
 };
 bool launch_head_f32_fused(const HeadFusedP& p, hipStream_t st);  // false: not covered
 int launch_gemm(const GemmP& p, int dtype, hipStream_t st);
+// split-bf16 GEMM (gemm_x3.hip): A fp32, W = hi bf16 (lo at W + w_lo_off), three bf16 MFMAs per k-step, fp32 accumulate.  Returns as
+// launch_gemm, or -1 when the problem is not covered (K % 32, N % 64, no lo copy, not exactly one of Cf / Cb)
+int launch_gemm_x3(const GemmP& p, hipStream_t st);
+void launch_f32_split_bf16(const float* in, bf16_t* hi, bf16_t* lo, long long n, hipStream_t st);  // hi = bf16(x), lo = bf16(x - hi)
+// the second half of a split-K GEMM (gemm.hip): sum the S raw slabs of p.ws, epilogue; returns 1 when it applied p.ln_* too
+int launch_splitk_reduce(const GemmP& p, int S, int exact_gelu, hipStream_t st);
 bool gemm_f32_direct_covers(const GemmP& p);             // would launch_gemm_f32_direct take this problem (incl. a_ln_*)?
 bool launch_gemm_f32_direct_group(const GemmP* ps, int n, hipStream_t st);  // n <= 4 covered problems in ONE launch
 bool launch_gemm_ring(const GemmP& p, hipStream_t st);  // bf16, many rows: 256x256 tile, 4-slot LDS-DMA ring (gemm_ring.hip)

@@ -79,8 +79,12 @@ int m3pc_create(const m3pc_dims* dims, int device, m3pc_handle** out) {
     declare_weights(h.get());
     for (auto& kv : h->w) {
         CHK(dmalloc(&kv.second.f, (size_t)kv.second.numel));
-        if (kv.second.gemm) CHK(dmalloc(&kv.second.b, (size_t)kv.second.numel));
+        if (kv.second.gemm) {
+            CHK(dmalloc(&kv.second.b, 2 * (size_t)kv.second.numel));  // hi | lo (Tensor::b)
+            h->gemm_w.push_back({kv.second.f, &kv.second});
+        }
     }
+    std::sort(h->gemm_w.begin(), h->gemm_w.end());
     const int d = h->d, T = h->T;
     for (int k = 0; k < 4; ++k) {
         CHK(dmalloc(&h->WT[k], (size_t)h->feat[k] * d));
@@ -281,7 +285,7 @@ int m3pc_load_weights(m3pc_handle* h, const m3pc_named_tensor* tensors, int n, v
             return fail(M3PC_EINVAL, "'%s' has %lld elements, expected %lld", kv.first.c_str(), tensors[i].numel, kv.second.numel);
         HIPCHK(hipMemcpyAsync(kv.second.f, tensors[i].data, (size_t)kv.second.numel * sizeof(float),
                               tensors[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        if (kv.second.gemm) launch_f32_to_bf16(kv.second.f, kv.second.b, kv.second.numel, st);
+        if (kv.second.gemm) launch_f32_split_bf16(kv.second.f, kv.second.b, kv.second.b + kv.second.numel, kv.second.numel, st);
         kv.second.loaded = true;
         dirty.push_back(kv.first);
     }
@@ -458,7 +462,7 @@ int m3pc_forward(m3pc_handle* h, int batch, const float* const tokens[4], const 
     if (!h || !tokens || !masks) return fail(M3PC_EINVAL, "null argument");
     if (!h->weights_loaded) return fail(M3PC_ESTATE, "weights not loaded");
     if (batch < 1 || batch > h->dm.max_batch) return fail(M3PC_EINVAL, "batch %d outside [1, max_batch=%d]", batch, h->dm.max_batch);
-    if (precision != M3PC_PREC_FP32 && precision != M3PC_PREC_BF16) return fail(M3PC_EINVAL, "bad precision");
+    if (!precision_ok(precision)) return fail(M3PC_EINVAL, "bad precision %d", precision);
     if ((out_mu == nullptr) != (out_std == nullptr)) return fail(M3PC_EINVAL, "out_mu and out_std go together");
     HIPCHK(hipSetDevice(h->device));
     Plan* pl = nullptr;
@@ -472,8 +476,9 @@ int m3pc_forward(m3pc_handle* h, int batch, const float* const tokens[4], const 
     }
     h->allow_splitk = true;
     CHK(ws_sync(h, (hipStream_t)stream));
-    return forward_impl(h, pl, in, batch, out_states, out_rewards, out_returns, out_mu, out_std,
-                        precision == M3PC_PREC_BF16 ? DT_BF16 : DT_F32, (hipStream_t)stream);
+    X3Scope x3(h, precision == M3PC_PREC_BF16X3);
+    return forward_impl(h, pl, in, batch, out_states, out_rewards, out_returns, out_mu, out_std, pass_dt(precision),
+                        (hipStream_t)stream);
 }
 
 // Zero-shot goal reaching, both forwards of action_piid_sample (zeroshot_omtm/learner.py:151-261) in one call on RAW windows:
@@ -572,13 +577,14 @@ int m3pc_goal_step_batch(m3pc_handle* h, int batch, const float* states, const f
     for (int k = 0; k < 2; ++k)
         if (!h->tok_set[k]) return fail(M3PC_ESTATE, "tokenizer '%s' not set", KEYN[k]);
     if (batch < 1 || batch > h->dm.max_goal_batch) return fail(M3PC_EINVAL, "batch %d outside [1, max_goal_batch=%d]", batch, h->dm.max_goal_batch);
-    if (precision != M3PC_PREC_FP32 && precision != M3PC_PREC_BF16) return fail(M3PC_EINVAL, "bad precision");
+    if (!precision_ok(precision)) return fail(M3PC_EINVAL, "bad precision %d", precision);
     if (goal_mode != M3PC_GOAL_PIID && goal_mode != M3PC_GOAL_ID) return fail(M3PC_EINVAL, "bad goal_mode %d", goal_mode);
     const int T = h->T, d = h->d;
     if (idx < 0 || idx >= T) return fail(M3PC_EINVAL, "idx %d outside [0, T=%d)", idx, T);
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    const int dt = precision == M3PC_PREC_BF16 ? DT_BF16 : DT_F32;
+    const int dt = pass_dt(precision);
+    X3Scope x3(h, precision == M3PC_PREC_BF16X3);
     bind_ws(h, &h->base);
     CHK(ws_sync(h, st));
     // kernels chosen by the row count (split-K, the few-row fp32 kernels) stay off: a window's result must not depend on
@@ -672,7 +678,7 @@ static int plan_check(m3pc_handle* h, const m3pc_plan_args* a, bool need_critic)
     const int T = h->T;
     if (a->horizon < 1 || a->horizon > T) return fail(M3PC_EINVAL, "horizon %d outside [1, T=%d]", a->horizon, T);
     if (a->mode < 0 || a->mode > 2) return fail(M3PC_EINVAL, "bad mode %d", a->mode);
-    if (a->precision != M3PC_PREC_FP32 && a->precision != M3PC_PREC_BF16) return fail(M3PC_EINVAL, "bad precision");
+    if (!precision_ok(a->precision)) return fail(M3PC_EINVAL, "bad precision %d", a->precision);
     if (a->slot < 0 || a->slot >= M3PC_SLOTS) return fail(M3PC_EINVAL, "slot %d outside [0, %d)", a->slot, M3PC_SLOTS);
     if (a->flags & ~(M3PC_PLAN_DEFER_JOIN | M3PC_PLAN_PRUNED_POLICY))  // (also what a caller built against the shorter ABI v2 structure would hand over)
         return fail(M3PC_EINVAL, "unknown m3pc_plan_args::flags 0x%x (is the caller's structure the ABI v%d one?)", a->flags, M3PC_ABI_VERSION);
@@ -824,7 +830,8 @@ int m3pc_candidate_pass(m3pc_handle* h, const m3pc_plan_args* a, const float* st
     // 1024 candidates are 392 tiles = two rounds on 256 CUs with the second round half empty, a half is 196 tiles =
     // one round, and the other half's attention / projection kernels run on the CUs it leaves free.  Candidates are
     // independent, results are identical to the one-stream order.
-    const int dt = a->precision == M3PC_PREC_BF16 ? DT_BF16 : DT_F32;
+    const int dt = pass_dt(a->precision);
+    X3Scope x3(h, a->precision == M3PC_PREC_BF16X3);
     const int n = a->n_count;
     h->slot_join_n[a->slot] = 0;
     // (only when one half alone fills the chip with fused-tail tiles: more than 256 tiles of 128 rows in the whole pass)
@@ -935,16 +942,18 @@ int m3pc_score_actions(m3pc_handle* h, const m3pc_plan_args* a, int n_windows, c
     const int T = h->T, n = a->n_count;
     if (a->horizon < 1 || a->horizon > T) return fail(M3PC_EINVAL, "horizon %d outside [1, T=%d]", a->horizon, T);
     if (a->mode != M3PC_MODE_RTG && a->mode != M3PC_MODE_CRITIC) return fail(M3PC_EINVAL, "mode must be RTG or CRITIC scoring");
-    if (a->precision != M3PC_PREC_FP32 && a->precision != M3PC_PREC_BF16) return fail(M3PC_EINVAL, "bad precision");
+    if (!precision_ok(a->precision)) return fail(M3PC_EINVAL, "bad precision %d", a->precision);
     if (n < 1 || (n > h->dm.max_candidates && !(a->precision == M3PC_PREC_FP32 && n <= h->chain[0].max_cand)))
         return fail(M3PC_ENOMEM, "n_count %d outside [1, max_candidates=%d]", n, h->dm.max_candidates);
     if (n_windows < 1 || (n_windows > 1 && !window_index)) return fail(M3PC_EINVAL, "n_windows > 1 needs window_index");
     if (a->mode == M3PC_MODE_CRITIC && !h->critic_set) return fail(M3PC_ESTATE, "critic weights not set");
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    const int dt = a->precision == M3PC_PREC_BF16 ? DT_BF16 : DT_F32;
+    const int dt = pass_dt(a->precision);
+    const bool fp32 = a->precision == M3PC_PREC_FP32;
+    X3Scope x3(h, a->precision == M3PC_PREC_BF16X3);
     // few-row fp32 calls (the re-score of a batched plan) run in the chain workspace, like m3pc_rescore
-    WsScope ws(h, dt == DT_F32 && n <= h->chain[0].max_cand, false, a->slot);
+    WsScope ws(h, fp32 && n <= h->chain[0].max_cand, false, a->slot);
     if (h->cur == &h->base) CHK(ws_sync(h, st));
     SampleP sp;
     memset(&sp, 0, sizeof(sp));
@@ -960,7 +969,7 @@ int m3pc_score_actions(m3pc_handle* h, const m3pc_plan_args* a, int n_windows, c
     sp.cand = h->cand;
     launch_sample(sp, st);
     // (split-K is row-count dependent: only where the caller does not rely on sharding exactness, i.e. the fp32 re-scores)
-    h->allow_splitk = dt == DT_F32;
+    h->allow_splitk = fp32;
     const int rc = candidate_pass(h, a, states, rewards, n, cand, expect_return, pred_rewards, pred_boot, dt, st, window_index);
     h->allow_splitk = false;
     return rc;
@@ -1019,7 +1028,7 @@ int m3pc_plan_step_batch(m3pc_handle* h, const m3pc_plan_args* a, int n_windows,
     if (!h || !a || !states || !actions || !rewards || !rtg || !eps || !window_index || !sample_actions || !expect_return)
         return fail(M3PC_EINVAL, "null argument");
     const int T = h->T, E = n_windows, N = a->n_total;
-    if (a->precision != M3PC_PREC_FP32 && a->precision != M3PC_PREC_BF16) return fail(M3PC_EINVAL, "bad precision");
+    if (!precision_ok(a->precision)) return fail(M3PC_EINVAL, "bad precision %d", a->precision);
     if (E >= 1 && (N < 1 || (long long)E * N > h->dm.max_candidates))
         return fail(M3PC_ENOMEM, "n_windows * n_total = %lld > max_candidates %d", (long long)E * N, h->dm.max_candidates);
     if (a->mode >= 0 && a->mode <= 2 && a->mode != M3PC_MODE_RTG && !h->critic_set) return fail(M3PC_ESTATE, "critic weights not set");
@@ -1049,7 +1058,8 @@ int m3pc_plan_step_batch(m3pc_handle* h, const m3pc_plan_args* a, int n_windows,
         sp.sd_out = std_ ? std_ + (size_t)w * T * A : nullptr;
         launch_sample(sp, st);
     }
-    const int dt = a->precision == M3PC_PREC_BF16 ? DT_BF16 : DT_F32;
+    const int dt = pass_dt(a->precision);
+    X3Scope x3(h, a->precision == M3PC_PREC_BF16X3);
     return candidate_pass(h, a, states, rewards, E * N, sample_actions, expect_return, nullptr, nullptr, dt, st, window_index);
 }
 
@@ -1250,11 +1260,28 @@ int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias,
     else
         p.Cf = (float*)C;
     p.ldc = N;
-    if (dtype == DT_F32 && variant != 1) {  // split-K workspace as the handle provides it (variant 1: none)
+    if (dtype != DT_BF16 && variant != 1) {  // split-K workspace as the handle provides it (variant 1: none)
         static float* ws = nullptr;
         if (!ws) HIPCHK(hipMalloc((void**)&ws, 64 << 20));
         p.ws = ws;
         p.ws_bytes = 64 << 20;
+    }
+    if (dtype == DT_X3) {  // A fp32, Wt fp32: split into hi / lo bf16 copies here, as m3pc_load_weights splits the weights
+        static bf16_t* wsplit = nullptr;
+        static size_t cap = 0;
+        const size_t n = (size_t)N * (K + ldpad);
+        if (n > cap) {
+            if (wsplit) HIPCHK(hipFree(wsplit));
+            wsplit = nullptr;
+            cap = 0;
+            HIPCHK(hipMalloc((void**)&wsplit, 2 * n * sizeof(bf16_t)));
+            cap = n;
+        }
+        launch_f32_split_bf16((const float*)Wt, wsplit, wsplit + n, (long long)n, (hipStream_t)stream);
+        p.W = wsplit;
+        p.w_lo_off = (long long)n;
+        if (launch_gemm_x3(p, (hipStream_t)stream) < 0) return fail(M3PC_EINVAL, "debug_gemm: shape not covered by the x3 kernel");
+        return check_launch("debug_gemm");
     }
     launch_gemm(p, dtype, (hipStream_t)stream);
     return check_launch("debug_gemm");
@@ -1623,7 +1650,7 @@ int m3pc_profile_read(m3pc_handle* h, int precision, long long* launches, double
     for (size_t i = 0; i < h->ev_used; ++i) {
         if (precision == M3PC_PROF_LAYER_TAIL) {
             if (h->ev[i].kind != 1) continue;
-        } else if (precision >= 0 && h->ev[i].dt != (precision == M3PC_PREC_BF16 ? DT_BF16 : DT_F32)) {
+        } else if (precision >= 0 && h->ev[i].dt != gemm_dt(precision)) {
             continue;
         }
         float t = 0.f;

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <memory>
@@ -43,7 +44,7 @@ namespace m3pc {
 
 struct Tensor {
     float* f = nullptr;    // fp32 device
-    bf16_t* b = nullptr;   // bf16 copy (GEMM weights only)
+    bf16_t* b = nullptr;   // bf16 copy (GEMM weights only), 2 numel: hi = bf16(f) at [0, numel), lo = bf16(f - hi) at [numel, 2 numel)
     long long numel = 0;
     bool gemm = false;
     bool loaded = false;
@@ -172,6 +173,8 @@ struct m3pc_handle {
     Base* cur = nullptr;
     bool two_stream = true;       // candidate halves on two streams (M3PC_TWO_STREAM=0: one stream); measured -2.5 % step time on C2
     bool allow_splitk = true;     // see gemm(): off while sharded candidates are scored
+    bool x3 = false;              // a split-bf16 pass is being enqueued (X3Scope): gemm() runs the weight GEMMs on gemm_x3.hip
+    std::vector<std::pair<const float*, Tensor*>> gemm_w;  // the GEMM weights by fp32 address, ascending (x3_weight)
     double pass_scale = 1.0;      // candidates of the whole plan step / candidates of the launch being enqueued (>= 1; FUSED_MIN_ROWS)
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -258,6 +261,24 @@ struct WsScope {  // binds a chain workspace for the duration of a few-row fp32 
     }
     ~WsScope() { bind_ws(h, &h->base); }
 };
+// M3PC_PREC_BF16X3 (include/m3pc_hip.h): the pass keeps the fp32 structure (dt = DT_F32 everywhere: fp32 residual stream, fp32
+// attention, LayerNorm, heads); only gemm() looks at the scope, and runs the GEMMs whose W is a model weight with K >= 32 on the
+// split-bf16 kernel.  Host-side state only, like WsScope.  X3Scope(h, false) keeps a piece fp32 inside an x3 pass (the
+// candidate-independent decoder tables, which fp32 passes share).
+struct X3Scope {
+    m3pc_handle* h;
+    bool prev;
+    X3Scope(m3pc_handle* h_, bool on) : h(h_), prev(h_->x3) { h->x3 = on; }
+    ~X3Scope() { h->x3 = prev; }
+};
+inline int pass_dt(int precision) { return precision == M3PC_PREC_BF16 ? DT_BF16 : DT_F32; }
+inline int gemm_dt(int precision) {  // the GemmTimer dt of a precision's candidate-pass GEMMs (m3pc_profile_read)
+    return precision == M3PC_PREC_BF16 ? DT_BF16 : precision == M3PC_PREC_BF16X3 ? DT_X3 : DT_F32;
+}
+inline bool precision_ok(int precision) {
+    return precision == M3PC_PREC_FP32 || precision == M3PC_PREC_BF16 || precision == M3PC_PREC_BF16X3;
+}
+
 inline void bind_slot(m3pc_handle* h, int s) {
     h->cur_slot = s;
     h->loc = h->slot[s].loc;
@@ -396,6 +417,16 @@ struct GemmTimer {
     }
 };
 
+// the GEMM weight whose fp32 copy holds address w (a whole tensor or a view into it, such as the K|V rows of in_proj), or null
+inline Tensor* x3_weight(m3pc_handle* h, const void* w) {
+    const float* f = (const float*)w;
+    auto it = std::upper_bound(h->gemm_w.begin(), h->gemm_w.end(), f,
+                               [](const float* a, const std::pair<const float*, Tensor*>& e) { return a < e.first; });
+    if (it == h->gemm_w.begin()) return nullptr;
+    --it;
+    return f < it->first + it->second->numel ? it->second : nullptr;
+}
+
 // returns 1 when the LayerNorm named by p_in.ln_* was fused into the launch (GemmP::ln_g)
 inline int gemm(m3pc_handle* h, const GemmP& p_in, int dt, hipStream_t st) {
     GemmP p = p_in;
@@ -403,6 +434,18 @@ inline int gemm(m3pc_handle* h, const GemmP& p_in, int dt, hipStream_t st) {
     // same row count (policy pass, generic forward, top-k re-score): sharded candidate scores stay bit-identical
     p.ws = h->allow_splitk ? h->splitk_ws : nullptr;
     p.ws_bytes = h->splitk_ws_bytes;
+    if (h->x3 && dt == DT_F32 && p.K >= 32) {  // split-bf16 pass (X3Scope): W's hi / lo copies at the same element offset
+        if (Tensor* t = x3_weight(h, p.W)) {
+            p.W = t->b + ((const float*)p.W - t->f);
+            p.w_lo_off = t->numel;
+            GemmTimer t3(h, st, 2.0 * p.M * (double)p.N * p.K, DT_X3);
+            const int rc = launch_gemm_x3(p, st);
+            if (rc >= 0) return rc;
+            p = p_in;  // (a shape the kernel does not cover -- none of the passes' GEMMs: fp32 below)
+            p.ws = h->allow_splitk ? h->splitk_ws : nullptr;
+            p.ws_bytes = h->splitk_ws_bytes;
+        }
+    }
 #ifdef M3PC_LAB  // (the lab build only: an environment variable must not change which kernels the product runs)
     static const int env_variant = M3PC_ENV("M3PC_GEMM_VARIANT") ? atoi(M3PC_ENV("M3PC_GEMM_VARIANT")) : 0;  // A/B runs
     if (env_variant) p.variant = env_variant;

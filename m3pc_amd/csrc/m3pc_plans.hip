@@ -201,6 +201,7 @@ int build_tables(m3pc_handle* h, Plan* pl, int qi, int dt, hipStream_t st) {
     Plan::Query& q = pl->query[qi];
     SharedTables& tb = q.tab[dt];
     if (tb.valid) return 0;
+    X3Scope fp32_tables(h, false);  // (a split-bf16 pass uses the fp32 tables: built in fp32, whichever pass builds them first)
     const int T = h->T, d = h->d;
     const size_t es = dtype_size(dt);
     if (!tb.Yall) {

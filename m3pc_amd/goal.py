@@ -108,8 +108,8 @@ class GoalMixin:
         horizon for all of them (BASELINE config 5: thousands of goal-reaching windows per GPU).  Exactly pruned many-window path
         (m3pc_goal_step_batch): path inference reads the states head at the rows the overlay uses only, inverse dynamics reads
         ONE action token (zeroshot learner.py:240-256).  goal_mask "piid" (action_piid_sample) or "id" (action_id_sample).
-        precision: "bf16" / "fp32"; default the planner's.  Returns (E, A): tanh(loc) when eval, a sample else."""
-        prec = self.precision if precision is None else {"fp32": capi.PREC_FP32, "bf16": capi.PREC_BF16}[precision]
+        precision: "bf16" / "bf16x3" / "fp32"; default the planner's.  Returns (E, A): tanh(loc) when eval, a sample else."""
+        prec = self.precision if precision is None else capi.precision_code(precision)
         idx = self.T - int(horizon)
         self._drain()  # (m3pc_goal_step_batch runs in the candidate workspace)
         res = self.handle.goal_step_batch(states, actions, idx, capi.GOAL_PIID if goal_mask == "piid" else capi.GOAL_ID, prec,

@@ -137,7 +137,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                  max_windows: int = 1, pipeline_depth: int = 3, chain_priority: int = -1, tail_stream: bool = True,
                  defer_join: bool = True, goal_batch: int = 0, race_min: int = 2, calibration_windows: Optional[int] = None, certify_sample: bool = True,
                  chain_mode: str = "alternate", policy_head: str = "full", auto_fp32: bool = True,
-                 calibration_factor: float = 1.6, rescore_round: int = 4):
+                 calibration_factor: float = 1.6, rescore_round: int = 4, fallback: str = "fp32"):
         """cfg: any object with traj_length, action_samples, horizon, discount, temperature, lmbda,
         plan_guidance (finetune.py RunConfig fields read at learner.py:276,319,342).
         tokenizer_manager: a TokenizerManager (this package's) or {key: {"mean","std","min","max"}}.
@@ -164,6 +164,13 @@ class HipPlanner(GoalMixin, LockstepMixin):
           x 2 already re-scores a third of them) and the step is slower than a plain fp32 step.  With auto_fp32 the planner watches
           for that -- half of the candidates or more re-scored in fp32, on average over the last (up to 16, at least 4) steps -- and
           plans in fp32 from then on (one warning; ``planner.fp32_fallback``), until the next weight load gives bf16 another try.
+        precision="bf16x3": the fp32 candidate pass with its weight GEMMs in split bf16 (M3PC_PREC_BF16X3: x = hi + lo, three bf16
+          MFMAs per product, fp32 everywhere else), ~2e-5 of the scores' scale.  It goes through the same certified re-score as
+          bf16 (delta calibrated per weight load on full fp32 passes, rescore / certify_sample / auto_fp32 alike): the arg-max and
+          the drawn index are fp32's, and the merged vector puts eval_action within fp32 tolerance.
+        fallback: where a saturated bf16 certificate (auto_fp32) sends the planner: "fp32" (default) or "bf16x3" -- the split-bf16
+          pass, whose deviation is ~400 x smaller, with a fresh calibration.  ``planner.fallback_precision`` names the precision
+          fallen back to (None while there is none), ``planner.fp32_fallback`` is True while planning in fp32 because of it.
         pipeline_depth: how many plan steps ``action_sample_batch`` / ``rollout`` keep in flight (<= capi.SLOTS - 1).
         goal_batch: the largest number of zero-shot windows one ``action_piid_sample_batch`` / ``goal_actions`` call plans
         through the pruned many-window path (m3pc_goal_step_batch; BASELINE config 5: 8192 per GPU); 0 = that path is off."""
@@ -184,7 +191,10 @@ class HipPlanner(GoalMixin, LockstepMixin):
         # race entries a step lists (m3pc_topk_race_window); certify_sample=False: none -- the arg-max (hence eval_action) stays
         # certified, the multinomial index is then a near-winner of the reference's draw only (round-4 behaviour, A/B switch)
         self._R = max(min(RACE_MAX, N), 1) if certify_sample else 0
-        max_rescore = max((int(rescore_max) + self._R) * nw, int(rescore_topk), 1) if precision == "bf16" else 1
+        prec = capi.precision_code(precision)
+        if fallback not in ("fp32", "bf16x3"):
+            raise ValueError(f"fallback must be 'fp32' or 'bf16x3', got {fallback!r}")
+        max_rescore = max((int(rescore_max) + self._R) * nw, int(rescore_topk), 1) if prec in capi.LOW_PRECISION else 1
         self._max_batch = max(int(max_batch), nw, 1)
         self.handle = capi.Handle(S, A, T, n_embd, n_head, n_enc_layer, n_dec_layer,
                                   max_candidates=max(n_local * nw, 1), max_batch=self._max_batch,
@@ -192,13 +202,16 @@ class HipPlanner(GoalMixin, LockstepMixin):
         self._goal_batch = int(goal_batch)
         self.device = self.handle.device
         self.S, self.A, self.T = S, A, T
-        self.precision = {"fp32": capi.PREC_FP32, "bf16": capi.PREC_BF16}[precision]
-        self.rescore_topk = int(rescore_topk) if self.precision == capi.PREC_BF16 else 0
+        self.precision = prec
+        low = self.precision in capi.LOW_PRECISION
+        self.rescore_topk = int(rescore_topk) if low else 0
         assert rescore in ("bound", "topk")
-        self.rescore = rescore if self.precision == capi.PREC_BF16 else "none"
+        self.rescore = rescore if low else "none"
         self.rescore_min, self.rescore_max = int(rescore_min), int(rescore_max)
         self.race_min = max(1, int(race_min))  # race entries of a first pass (the winner of the bf16 race + one runner-up)
-        self._auto_fp32 = bool(auto_fp32) and self.precision == capi.PREC_BF16 and self.rescore == "bound"
+        self._auto_fp32 = bool(auto_fp32) and low and self.rescore == "bound"
+        self._fallback = capi.PRECISIONS[fallback]  # where a saturated bf16 certificate goes (a saturated bf16x3 one: fp32)
+        self.fallback_precision: Optional[str] = None
         self._configured = (self.precision, self.rescore)  # what the caller asked for (the fp32 fallback returns to it)
         self._sat_recent: list = []  # saturated flags of the last 16 resolved steps
         self._want_fp32 = False      # set by _finish, acted on by the next _issue (steps in flight are drained first)
@@ -291,9 +304,10 @@ class HipPlanner(GoalMixin, LockstepMixin):
         self._cal_left = getattr(self, "_cal_windows", 3)
         self._hist = {}
         self.delta_grown = 0
-        if getattr(self, "fp32_fallback", False):  # new weights: bf16 gets another try
+        if getattr(self, "fp32_fallback", False) or getattr(self, "fallback_precision", None):  # new weights: bf16 gets another try
             self.precision, self.rescore = self._configured
             self.fp32_fallback = False
+            self.fallback_precision = None
         self._sat_recent, self._want_fp32 = [], False
 
     # -- adaptive re-score state ------------------------------------------------------------------------
@@ -523,7 +537,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                                 precision=self.precision, slot=sl.i, defer_join=tk.deferred)
         er, a0 = res["expect_return"], res["sample_actions"][:, 0]
         er, a0 = mdist.gather_candidates(er, a0, N, self.group, force=self._force_collective)
-        if self._bf16_offset and self.precision == capi.PREC_BF16:
+        if self._bf16_offset and self.precision in capi.LOW_PRECISION:
             er = er + self._bf16_offset
         tk.res, tk.er_b, tk.a0 = res, er, a0
         if chain is not None:
@@ -547,11 +561,24 @@ class HipPlanner(GoalMixin, LockstepMixin):
         if len(seen) < 4 or sum(seen) < 0.5 * N * len(seen):  # (re-scoring k of N candidates costs ~k / N of an fp32 step on top of the bf16 one)
             return
         for tk in [sl.owner for sl in self._slots if sl.owner is not None]:
-            self._finish(tk)  # (issued as bf16 steps: resolved as such)
-        warnings.warn(f"m3pc_amd: the bf16 certificate re-scored {sum(seen) / len(seen):.0f} of {N} candidates in fp32 on average over "
-                      f"the last {len(seen)} plan steps (delta = {self._delta:.3g}): planning in fp32 until the next weight load "
-                      f"(HipPlanner(auto_fp32=False) keeps bf16)")
+            self._finish(tk)  # (issued as low-precision steps: resolved as such)
+        name = {capi.PREC_BF16: "bf16", capi.PREC_BF16X3: "bf16x3"}[self.precision]
+        to_x3 = self.precision == capi.PREC_BF16 and self._fallback == capi.PREC_BF16X3
+        warnings.warn(f"m3pc_amd: the {name} certificate re-scored {sum(seen) / len(seen):.0f} of {N} candidates in fp32 on average over "
+                      f"the last {len(seen)} plan steps (delta = {self._delta:.3g}): planning in {'bf16x3' if to_x3 else 'fp32'} until "
+                      f"the next weight load (HipPlanner(auto_fp32=False) keeps {name})")
+        if to_x3:
+            # the split-bf16 pass under the same certificate: its own delta, calibrated afresh on the next steps (the history of
+            # the bf16 steps says nothing about it).  Decided at the same step at any pipeline depth, like the fp32 fallback.
+            self.precision, self.fallback_precision = capi.PREC_BF16X3, "bf16x3"
+            self._delta0 = self._delta_fixed
+            self._cal_left = self._cal_windows
+            self._hist = {}
+            self.delta_grown = 0
+            self._sat_recent, self._want_fp32 = [], False
+            return
         self.precision, self.rescore, self.fp32_fallback = capi.PREC_FP32, "none", True
+        self.fallback_precision = "fp32"
 
     def _rescore_args(self, tk):
         return (tk.mode, tk.states, tk.actions, tk.rewards, tk.eps), (tk.h, tk.rtg, tk.lmbda, float(self.cfg.discount))
@@ -923,7 +950,9 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     precision: "bf16" (default since round 6: the configuration the headline is measured on) -- the bf16 candidate pass with the
     certified fp32 re-score: BOTH returned actions follow the fp32 path's decisions (the arg-max behind ``eval_action`` and
     the multinomial index behind ``sample_action`` are certified, ``certify_sample=True``; ``eval_action``'s weights p agree
-    to ~1e-4), and ``auto_fp32`` falls back to plain fp32 steps for weights on which the certificate is expensive.
+    to ~1e-4), and ``auto_fp32`` falls back to plain fp32 steps for weights on which the certificate is expensive
+    (``fallback="bf16x3"``: to split-bf16 steps instead).
+    "bf16x3": the fp32 pass with split-bf16 weight GEMMs under the same certificate: returned values within fp32 tolerance.
     "fp32": every tolerance of the reference's own fp32 arithmetic, ~8 x the time per step.
 
     Reads: learner.cfg, learner.mtm (state_dict + config), learner.tokenizer_manager.tokenizers[k]
@@ -934,6 +963,7 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     learner replica and passes a generator seeded identically); further keywords go to ``HipPlanner``.
     Weights are followed per tensor: before each call the version counters of ``mtm`` / ``iql.qf`` are compared with the
     ones uploaded last, and only the tensors that changed are sent (m3pc_load_weights re-packs what depends on them)."""
+    capi.precision_code(precision)  # (an unknown name fails here, before anything is built)
     mtm = learner.mtm
     mc = mtm.config
     toks = {}
