@@ -67,6 +67,29 @@ int m3pc_debug_attention_dec_le_bf16(const void* Qtab, const void* QKVm, const v
  * O (n, Lq + Lq2, 512), own rows first.  kernel as m3pc_debug_attention_bf16 */
 int m3pc_debug_attention_mix_bf16(const void* Qown, const void* Qsh, const void* KV, const void* QKVm, void* O, int n, int Lq, int Lq2, int kernel,
                                   void* stream);
+/* any attention of the library on caller tensors, through launch_attention's dispatch.  dtype 0: fp32 rows, 1: bf16 rows.
+ * Queries Q (row i of batch element b at Q + b q_bstride + i ldq; q_bstride 0: shared by the batch), Lq rows, output rows orow1 + i;
+ * optional batch-shared second query segment Q2 (Lq2 rows, output rows orow2 + i; bf16 only).  Keys / values: K1, V1 per batch
+ * element (L1 rows), optional batch-shared K2, V2 (L2 rows), optional batch-shared pre-reduced block Kp, Vp (Lp rows, bf16 only,
+ * batch-shared queries and no Q2) reduced by the prestats kernel into `pre` (n_head * Lq * (2 + hd) floats of scratch).  O row r of
+ * batch element b at O + b o_bstride + r ldo; head h owns columns [h hd, (h + 1) hd) of every row.  kernel: 0 = dispatch, 1 = never the
+ * pipelined kernels.  Shapes no kernel covers return M3PC_EINVAL before anything is launched: hd not 32 / 64 / 128, L1 < 1, Lq < 1,
+ * L1 + L2 > 256, Lp > 256, orow1 / Q2 / a pre block with fp32 rows, pointers not 16-byte aligned, strides not multiples of 16 bytes.
+ * picked (2 ints, optional): [0] the id of the attention kernel launched, [1] 50 if the prestats kernel ran, else 0.
+ * Kernel ids (tests/test_attention_gpu.py reaches every id of this list except the A/B-only ones):
+ *   fp32 (attn.hip):   1 attn_pair_kernel<4>;  2 / 3 / 4 attn_split_kernel hd 32 / 64 / 128;
+ *                      5 + 3 a + c: attn_kernel<HDT, NCH>, a = 0 / 1 / 2 for hd 32 / 64 / 128, c = 0 / 1 / 2 for NCH 1 / 2 / 4  (5..13)
+ *   bf16 (attn_bf16.hip): 20 pipe<49, 0>;  21 pipe<17, 32>;  22 pipe_dec<49>;  23 pipe_mix<49, 79>;  24 pipe_wide<97, 0, 97, 0, false>;
+ *                      25 pipe_wide<33, 64, 33, 64, false>;  26 pipe_wide<0, 64, 97, 0, true>;  27 / 28 / 29 pack2 hd 32 / 64 / 128;
+ *                      30 + 3 a + f: direct<HDT, ., .>, f = 0 / 1 / 2 for <1, 2> / <2, 2> / <2, 4>  (30..38);
+ *                      39 / 40 / 41 attn_bf16_kernel<HDT, 4> hd 32 / 64 / 128;
+ *                      A/B-only (M3PC_NO_ATTN_DIRECT): 42 + 2 a + c attn_bf16_kernel<HDT, NCH>, c = 0 / 1 for NCH 1 / 2  (42..47)
+ *   prestats:          50 attn_prestats_kernel */
+int m3pc_debug_attention(int dtype, const void* Q, long long q_bstride, int ldq, int Lq, int orow1, const void* Q2, int ldq2, int Lq2,
+                         int orow2, const void* K1, const void* V1, long long kv1_bstride, int ldkv1, int L1, const void* K2,
+                         const void* V2, int ldkv2, int L2, const void* Kp, const void* Vp, int ldp, int Lp, float* pre, void* O,
+                         long long o_bstride, int ldo, int batch, int n_head, int hd, float scale, int kernel, int* picked,
+                         void* stream);
 /* in-kernel phase stamps of workgroup 37 of every fused-tail launch as the step runs: cap > 0 starts a ring of cap entries
  * (64 int64 each), cap == 0 copies it to `out` (host), reports the number of launches logged and stops */
 int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged);

@@ -17,6 +17,10 @@
 
 namespace m3pc {
 
+#ifdef M3PC_LAB
+thread_local int g_attn_picked = 0;
+#endif
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -469,6 +473,7 @@ static void launch_split(const AttnP& p, hipStream_t st) {
         attr_set[dev] = true;
     }
     dim3 grid(p.batch, p.n_head, (p.Lq + 31) / 32), block(256);
+    M3PC_ATTN_PICK(HDT == 1 ? 2 : HDT == 2 ? 3 : 4);
     hipLaunchKernelGGL((attn_split_kernel<T, HDT>), grid, block, smem, st, p);
 }
 
@@ -481,6 +486,7 @@ static void launch_nch(const AttnP& p, dim3 grid, dim3 block, size_t smem, hipSt
         (void)hipFuncSetAttribute((const void*)attn_kernel<T, HDT, NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set[dev] = true;
     }
+    M3PC_ATTN_PICK(5 + 3 * (HDT == 1 ? 0 : HDT == 2 ? 1 : 2) + (NCH == 1 ? 0 : NCH == 2 ? 1 : 2));
     hipLaunchKernelGGL((attn_kernel<T, HDT, NCH>), grid, block, smem, st, p);
 }
 
@@ -494,6 +500,7 @@ static void launch_hd(const AttnP& p, hipStream_t st) {
         if constexpr (HDT == 4) {  // (each wave owns one 32-wide slice of the output: four waves = head dim 128)
             if (Lk <= 64 && !no_pair) {
                 dim3 grid(p.batch, p.n_head, (p.Lq + 31) / 32), block(256);
+                M3PC_ATTN_PICK(1);
                 hipLaunchKernelGGL((attn_pair_kernel<T, HDT>), grid, block, 0, st, p);
                 return;
             }

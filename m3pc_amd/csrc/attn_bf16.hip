@@ -1403,6 +1403,7 @@ static bool launch_pipe_mix(const AttnP& p, hipStream_t st) {
     constexpr int LDSB = 2 * ((N2 + 3) / 4) * 1024 + 4 * (2 * APIPE_IMG + 1024);
     static_assert(LDSB <= 160 * 1024, "LDS");
     if (!lds_opt_in(attn_bf16_pipe_mix_kernel<N1, N2>, LDSB)) return false;
+    M3PC_ATTN_PICK(23);
     hipLaunchKernelGGL((attn_bf16_pipe_mix_kernel<N1, N2>), dim3(grid), dim3(192), LDSB, st, p, n_items);
     return true;
 }
@@ -1411,6 +1412,7 @@ static bool launch_pipe_dec(const AttnP& p, hipStream_t st) {
     const int n_items = p.batch * p.n_head;
     const int grid = n_items < 256 ? n_items : 256;  // one workgroup per CU (4 x 26 KB of K|V buffers); a multiple of the 4 heads
     if (!lds_opt_in(attn_bf16_pipe_dec_kernel<N1>, 8 * APIPE_IMG)) return false;
+    M3PC_ATTN_PICK(22);
     hipLaunchKernelGGL((attn_bf16_pipe_dec_kernel<N1>), dim3(grid), dim3(192), 8 * APIPE_IMG, st, p, n_items);
     return true;
 }
@@ -1430,6 +1432,7 @@ static bool launch_pipe(const AttnP& p, hipStream_t st) {
     static const int env_lds = M3PC_ENV("M3PC_ATTN_PIPE_LDS") ? atoi(M3PC_ENV("M3PC_ATTN_PIPE_LDS")) : 0;
     if (env_lds > 0) lds_bytes = env_lds;
 #endif
+    M3PC_ATTN_PICK(SH == 0 ? 20 : 21);
     hipLaunchKernelGGL((attn_bf16_pipe_kernel<N1, SH>), dim3(grid), dim3(192), lds_bytes, st, p, n_items);
     return true;
 }
@@ -1443,6 +1446,7 @@ static bool launch_pipe_wide(const AttnP& p, hipStream_t st) {
     const int grid = n_items < 256 ? n_items : 256;  // one workgroup per CU (150 KB of row images); a multiple of the 4 heads
     if (!lds_opt_in(attn_bf16_pipe_wide_kernel<NQ1, SHQ, NK1, SHK, PRE>, WPIPE_LDS)) return false;
     constexpr int NTHR = ((NQ1 + SHQ + 31) / 32 + 1) * 64;
+    M3PC_ATTN_PICK(PRE ? 26 : SHQ == 0 ? 24 : 25);
     hipLaunchKernelGGL((attn_bf16_pipe_wide_kernel<NQ1, SHQ, NK1, SHK, PRE>), dim3(grid), dim3(NTHR), WPIPE_LDS, st, p, n_items);
     return true;
 }
@@ -1595,11 +1599,14 @@ template <int HDT, int NW, int NKT>
 static void launch_direct(const AttnP& p, int slots, hipStream_t st) {
     const size_t smem = (size_t)NKT * 32 * (HDT * 64 + 16) + NW * 32 * sizeof(float);
     const int qgroups = (slots + NW * 32 - 1) / (NW * 32);
+    M3PC_ATTN_PICK(30 + 3 * (HDT == 1 ? 0 : HDT == 2 ? 1 : 2) + (NW == 1 ? 0 : NKT == 2 ? 1 : 2));
     hipLaunchKernelGGL((attn_bf16_direct_kernel<HDT, NW, NKT>), dim3(p.batch, p.n_head, qgroups), dim3(NW * 64), smem, st, p);
 }
 
 template <int HDT, int NCH>
 static void launch_nch(const AttnP& p, dim3 grid, dim3 block, size_t smem, hipStream_t st) {
+    // (NCH = 4: ids 39..41; NCH = 1, 2 run only behind the M3PC_NO_ATTN_DIRECT switch: ids 42..47)
+    M3PC_ATTN_PICK(NCH == 4 ? 39 + (HDT == 1 ? 0 : HDT == 2 ? 1 : 2) : 42 + 2 * (HDT == 1 ? 0 : HDT == 2 ? 1 : 2) + (NCH == 1 ? 0 : 1));
     hipLaunchKernelGGL((attn_bf16_kernel<HDT, NCH>), grid, block, smem, st, p);
 }
 
@@ -1618,6 +1625,7 @@ static void launch_hd(const AttnP& p, hipStream_t st) {
     static const bool no_pack = M3PC_ENV("M3PC_NO_ATTN_PACK") != nullptr;  // A/B switch
     if (!no_direct && !no_pack && p.no_pipe != 1 && !p.Q2 && !p.K2 && !p.pre_m && p.L2 == 0 && p.Lq >= 1 && p.Lq <= 16 && p.L1 >= 1 && p.L1 <= 16 &&
         p.batch >= 64) {  // two windows per tile (the zero-shot passes)
+        M3PC_ATTN_PICK(27 + (HDT == 1 ? 0 : HDT == 2 ? 1 : 2));
         hipLaunchKernelGGL((attn_bf16_pack2_kernel<HDT>), dim3((p.batch + 1) / 2, p.n_head), dim3(64), 0, st, p);
         return;
     }

@@ -281,6 +281,14 @@ struct AttnP {
 // n_head, hd, scale of `p` (bf16 operands) and writes the three arrays
 void launch_attention_prestats(const AttnP& p, float* pre_m, float* pre_l, float* pre_O, hipStream_t st);
 void launch_attention(const AttnP& p, int dtype, hipStream_t st);
+// lab build: the id of the attention kernel the calling thread launched last (the list is in include/m3pc_hip_debug.h,
+// m3pc_debug_attention); the product build records nothing
+#ifdef M3PC_LAB
+extern thread_local int g_attn_picked;
+#define M3PC_ATTN_PICK(id) (::m3pc::g_attn_picked = (id))
+#else
+#define M3PC_ATTN_PICK(id) ((void)0)
+#endif
 void launch_attention_bf16(const AttnP& p, hipStream_t st);
 
 // Encoder token embedding (mtm_model.py:546-557) with the tokenizer affine folded in and the

@@ -1574,6 +1574,84 @@ int m3pc_debug_attention_mix_bf16(const void* Qown, const void* Qsh, const void*
     return check_launch("debug_attention_mix_bf16");
 }
 
+// any attention the library launches, on caller tensors (tests/test_attention_gpu.py): fills an AttnP and goes through
+// launch_attention's dispatch; shapes the kernels do not cover are refused before anything is launched
+int m3pc_debug_attention(int dtype, const void* Q, long long q_bstride, int ldq, int Lq, int orow1, const void* Q2, int ldq2, int Lq2,
+                         int orow2, const void* K1, const void* V1, long long kv1_bstride, int ldkv1, int L1, const void* K2,
+                         const void* V2, int ldkv2, int L2, const void* Kp, const void* Vp, int ldp, int Lp, float* pre, void* O,
+                         long long o_bstride, int ldo, int batch, int n_head, int hd, float scale, int kernel, int* picked,
+                         void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (picked) picked[0] = picked[1] = 0;
+    if (dtype != DT_F32 && dtype != DT_BF16) return fail(M3PC_EINVAL, "debug_attention: dtype %d", dtype);
+    if (hd != 32 && hd != 64 && hd != 128) return fail(M3PC_EINVAL, "debug_attention: head dim %d", hd);
+    if (!Q || !K1 || !V1 || !O || batch < 1 || n_head < 1 || Lq < 1 || L1 < 1 || L2 < 0 || Lp < 0 || L1 + L2 > 256 || Lp > 256)
+        return fail(M3PC_EINVAL, "debug_attention: shape");
+    if (kernel != 0 && kernel != 1) return fail(M3PC_EINVAL, "debug_attention: kernel %d", kernel);
+    const int w = n_head * hd, el = dtype == DT_BF16 ? 2 : 4, al = 16 / el;  // (16-byte row fragments)
+    if (q_bstride < 0 || kv1_bstride < 0 || o_bstride < 0 || orow1 < 0 || (Q2 && orow2 < 0)) return fail(M3PC_EINVAL, "debug_attention: negative stride / row");
+    if (ldq < w || ldkv1 < w || ldo < w || (K2 && ldkv2 < w) || (Q2 && ldq2 < w) || (Lp && ldp < w))
+        return fail(M3PC_EINVAL, "debug_attention: leading dimension below n_head * hd");
+    if ((ldq | ldkv1 | ldo | (K2 ? ldkv2 : 0) | (Q2 ? ldq2 : 0) | (Lp ? ldp : 0)) % al || (q_bstride | kv1_bstride | o_bstride) % al)
+        return fail(M3PC_EINVAL, "debug_attention: strides must be multiples of %d elements", al);
+    if (((uintptr_t)Q | (uintptr_t)K1 | (uintptr_t)V1 | (uintptr_t)O | (uintptr_t)Q2 | (uintptr_t)K2 | (uintptr_t)V2 | (uintptr_t)Kp |
+         (uintptr_t)Vp | (uintptr_t)pre) & 15)
+        return fail(M3PC_EINVAL, "debug_attention: pointers must be 16-byte aligned");
+    if ((K2 == nullptr) != (V2 == nullptr) || (L2 > 0) != (K2 != nullptr) || (Lp > 0) != (Kp && Vp && pre) || (Q2 != nullptr) != (Lq2 > 0))
+        return fail(M3PC_EINVAL, "debug_attention: optional segments need their pointers and a length");
+    // the fp32 kernels know one query segment, no pre-reduced block and no output row offset
+    if (dtype == DT_F32 && (Q2 || Lp || orow1)) return fail(M3PC_EINVAL, "debug_attention: Q2 / pre block / orow1 need bf16 rows");
+    // the pre-reduced block is per query, shared by the batch, and indexed by the first segment's query slots
+    if (Lp && (q_bstride != 0 || Q2)) return fail(M3PC_EINVAL, "debug_attention: a pre block needs batch-shared queries and no Q2");
+    AttnP a;
+    memset(&a, 0, sizeof(a));
+    a.Q = Q;
+    a.q_bstride = q_bstride;
+    a.ldq = ldq;
+    a.Lq = Lq;
+    a.orow1 = orow1;
+    a.Q2 = Q2;
+    a.ldq2 = ldq2;
+    a.Lq2 = Q2 ? Lq2 : 0;
+    a.orow2 = orow2;
+    a.n_head = n_head;
+    a.hd = hd;
+    a.scale = scale;
+    float* pre_m = pre;
+    float* pre_l = pre ? pre + (size_t)n_head * Lq : nullptr;
+    float* pre_O = pre ? pre + (size_t)2 * n_head * Lq : nullptr;
+    if (Lp) {  // (pre: n_head * Lq * (2 + hd) floats; pre_O 16-byte aligned as the pipelined kernels read it)
+        if ((2 * n_head * Lq) % 4) return fail(M3PC_EINVAL, "debug_attention: 2 * n_head * Lq must be a multiple of 4");
+        a.K2 = Kp;
+        a.V2 = Vp;
+        a.ldkv2 = ldp;
+        a.L2 = Lp;
+        launch_attention_prestats(a, pre_m, pre_l, pre_O, st);
+        if (picked) picked[1] = 50;
+        a.pre_m = pre_m;
+        a.pre_l = pre_l;
+        a.pre_O = pre_O;
+    }
+    a.K1 = K1;
+    a.V1 = V1;
+    a.kv1_bstride = kv1_bstride;
+    a.ldkv1 = ldkv1;
+    a.L1 = L1;
+    a.K2 = K2;
+    a.V2 = V2;
+    a.ldkv2 = ldkv2;
+    a.L2 = L2;
+    a.O = O;
+    a.o_bstride = o_bstride;
+    a.ldo = ldo;
+    a.batch = batch;
+    a.no_pipe = kernel;
+    g_attn_picked = 0;
+    launch_attention(a, dtype, st);
+    if (picked) picked[0] = g_attn_picked;
+    return check_launch("debug_attention");
+}
+
 int m3pc_debug_kv_fused(const void* Z, int n, int Le, int kept0, int off0, int kept1, int off1, const void* We0, const void* We1,
                         const void* Wkv, void* stream_buf, const float* rowtab0, const float* rowtab1, const float* ln_g,
                         const float* ln_b, const float* bkv, void* KV, void* stream, long long* stamps) {

@@ -88,7 +88,7 @@ def test_x3_gemm_against_fp64(K, N, epi):
 MASKS = {"rcbc": O.rcbc_mask, "fd": O.fd_mask, "pi": O.pi_mask, "fid": O.fid_mask}
 
 
-@pytest.mark.parametrize("d,nh,T,B", [(64, 2, 8, 3), (512, 4, 8, 2), (512, 4, 16, 1)])
+@pytest.mark.parametrize("d,nh,T,B", [(64, 2, 8, 3), (512, 4, 8, 2), (512, 4, 16, 1), (128, 2, 8, 3), (512, 8, 8, 2)])  # (head width 64: 128 / 2, 512 / 8)
 @pytest.mark.parametrize("mask_name,idx_frac", [("rcbc", 0.5), ("fd", 0.5), ("pi", 0.5), ("fid", 0.25), ("rcbc", 0.0)])
 def test_forward_x3_matches_oracle(d, nh, T, B, mask_name, idx_frac):
     """test_hip_parity.py::test_forward_matches_oracle's grid in x3: 2e-4 of scale (fp32 is held to 2e-5, bf16 to 5e-2)."""

@@ -36,7 +36,7 @@ def _assert_close(got, ref, tol, what):
 MASKS = {"rcbc": O.rcbc_mask, "fd": O.fd_mask, "pi": O.pi_mask, "fid": O.fid_mask}
 
 
-@pytest.mark.parametrize("d,nh,T,B", [(64, 2, 8, 3), (512, 4, 8, 2), (512, 4, 16, 1)])
+@pytest.mark.parametrize("d,nh,T,B", [(64, 2, 8, 3), (512, 4, 8, 2), (512, 4, 16, 1), (128, 2, 8, 3), (512, 8, 8, 2)])  # (head width 64: 128 / 2, 512 / 8)
 @pytest.mark.parametrize("mask_name,idx_frac", [("rcbc", 0.5), ("fd", 0.5), ("pi", 0.5), ("fid", 0.25), ("rcbc", 0.0)])
 def test_forward_matches_oracle(d, nh, T, B, mask_name, idx_frac):
     dims = synth.Dims(11, 3, T, n_embd=d, n_head=nh)
@@ -58,12 +58,22 @@ def test_forward_matches_oracle(d, nh, T, B, mask_name, idx_frac):
 def test_forward_bf16_close_to_oracle():
     """bf16 operands: 8-bit mantissas through 3 transformer layers; head outputs (O(1) values) agree with
     the fp32 oracle to 5e-2 of scale."""
-    dims = synth.Dims(11, 3, 8)
+    _forward_bf16_close(512, 4)
+
+
+@pytest.mark.parametrize("d,nh", [(128, 2), (512, 8)])
+def test_forward_bf16_head_width_64_close_to_oracle(d, nh):
+    """The same at head width 64: n_embd 128 / n_head 2 (the default omtmConfig, m3pc_amd/mtm.py) and 512 / 8."""
+    _forward_bf16_close(d, nh)
+
+
+def _forward_bf16_close(d, nh):
+    dims = synth.Dims(11, 3, 8, n_embd=d, n_head=nh)
     h, sd, stats, _ = make_handle(dims, max_candidates=8, max_batch=4)
     masks = O.fd_mask(8, 4)
     g = torch.Generator().manual_seed(3)
     toks = {k: torch.randn(2, 8, 1, f, generator=g) for k, f in dims.feat.items()}
-    ref = O.mtm_forward(sd, toks, masks, 4)
+    ref = O.mtm_forward(sd, toks, masks, nh)
     out = h.forward([toks[k][:, :, 0].cuda() for k in synth.KEYS], [masks[k] for k in synth.KEYS],
                     precision=capi.PREC_BF16)
     for k in ("states", "rewards", "returns"):
@@ -316,6 +326,29 @@ def test_odd_shapes_match_oracle(T, H, N, mode):
     ref = O.guiding(sd, stats, cfg, win, H, 0.6, eps, mode, critic=critic)
     s, a, r = window_dev(win)
     res = h.plan_step(MODES[mode], s, a, r, dev_eps, H, 2.0, 0.6, 0.99, N)
+    _assert_close(res["sample_actions"], ref["sample_actions"], 2e-5, "sample_actions")
+    scale = max(float(ref["expect_return"].abs().max()), 1.0)
+    assert float((res["expect_return"].cpu() - ref["expect_return"]).abs().max()) <= 5e-5 * scale
+    p, ev, am = h.select(res["expect_return"], res["sample_actions"][:, 0], cfg.temperature)
+    assert int(am.item()) == ref["argmax"]
+    _assert_close(ev, ref["eval_action"], 1e-4, "eval_action")
+    h.close()
+
+
+@pytest.mark.parametrize("mode", ["rtg", "critic"])
+def test_head_width_64_plan_step_matches_oracle(mode):
+    """n_embd 128 / n_head 2 (head width 64: the default omtmConfig, m3pc_amd/mtm.py): one fp32 plan step per mode against the
+    oracle, at test_odd_shapes_match_oracle's bars.  (The GEMM chains, not the fused layer tail, which needs n_embd 512.)"""
+    T, H, N = 8, 4, 130
+    dims = synth.Dims(11, 3, T, n_embd=128, n_head=2)
+    h, sd, stats, critic = make_handle(dims, max_candidates=N, max_batch=1)
+    cfg = O.PlanCfg(T, H, N, 0.99, 1.0 if mode != "rtg" else 0.01, 0.6, n_head=2)
+    win, hh = O.assemble_window(cfg, synth.make_history(dims, 3), 300, 2.0)
+    assert hh == H
+    eps = synth.make_eps(N, dims, 9)
+    ref = O.guiding(sd, stats, cfg, win, H, 0.6, eps, mode, critic=critic)
+    s, a, r = window_dev(win)
+    res = h.plan_step(MODES[mode], s, a, r, eps[:, 0, :, 0, :].cuda(), H, 2.0, 0.6, 0.99, N)
     _assert_close(res["sample_actions"], ref["sample_actions"], 2e-5, "sample_actions")
     scale = max(float(ref["expect_return"].abs().max()), 1.0)
     assert float((res["expect_return"].cpu() - ref["expect_return"]).abs().max()) <= 5e-5 * scale
