@@ -3,7 +3,8 @@
  * `python -m m3pc_amd.build --lab`, compiled with -DM3PC_LAB).  The product library libm3pc_hip.so
  * exports none of these and reads no environment variable; the lab build additionally honours the
  * A/B switches M3PC_NO_* / M3PC_GEMM_VARIANT / M3PC_TWO_STREAM / ... listed in DESIGN.md section 7.
- * Users: tests/test_gemm_kernels_gpu.py, tests/test_block_fused_gpu.py, tools/*.py.
+ * Users: tests/test_gemm_kernels_gpu.py, tests/test_gemm_edges_gpu.py, tests/test_bf16x3_gpu.py, tests/test_attention_gpu.py,
+ * tests/test_block_fused_gpu.py, tools/*.py.
  */
 #ifndef M3PC_HIP_DEBUG_H
 #define M3PC_HIP_DEBUG_H
@@ -17,6 +18,74 @@ extern "C" {
  * C = epilogue(A (M,K) W (N,K)^T + bias [gelu] [+ res]); variant selects a kernel configuration (0: dispatch) */
 int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias, const float* res, void* C, int M, int N,
                     int K, int gelu, int f32out, int variant, void* stream);
+/* one GEMM of the library on caller tensors with everything a production call can pass (GemmP, csrc/kernels.h), through
+ * launch_gemm's / launch_gemm_x3's dispatch:
+ *     C[cmap(r)] = [res[cmap(r)] +] [gelu](A[amap(r)] (K) . W (N, K)^T + bias + rowtab[(r % rt_mod) rt_ld ..])      r < M
+ * a row map {rpg, gstride, off} sends logical row r to physical row (r / rpg) gstride + r % rpg + off (rpg 0: identity); cmap
+ * applies to C and res alike, and res may be C itself.  dtype 0: fp32 operands, 1: bf16 operands, 2: split-bf16 (A and W fp32, W is
+ * split into its hi / lo bf16 copies inside the call).  f32out: C is fp32 (always for dtype 0), else bf16.  ws / ws_bytes: the
+ * split-K slab workspace (null: K is never split, and the few-row fp32 kernel of gemm_f32_direct.hip is not used).  a_padded: 127
+ * readable rows follow A's last row.  ln_g / ln_b / ln_out: the LayerNorm that consumes C (N columns, contiguous rows); bit 2 of
+ * picked[3] says whether the launch applied it -- when not, ln_out is untouched and the caller runs the LayerNorm itself.
+ * a_ln_g / a_ln_b: A is LayerNorm(A rows) (K columns), normalised on the operand load.  variant: 0 = dispatch; bf16 operands: 2 /
+ * 26 / 37 / 43 / 44 force launch_tile<128, 128, 2, 2, 64> (the double buffer on 64-byte LDS rows) / the ring without peeling / gemm_big / gemm_line 128 / gemm_line 256;
+ * fp32 operands: 2 = never the few-row kernel.
+ * Refused with M3PC_EINVAL before anything is launched (the register-staged kernel every shape can fall back to sets the shape
+ * rules): N % 64 (N % 32 where the few-row fp32 kernel, id 5 / 6, takes the problem), K * sizeof(operand) % 128 (x3: K % 32), a pointer not on 16 bytes, a leading dimension below its row length or
+ * whose rows leave 16 bytes, rowtab with rt_mod < 1, a row map that is neither rpg == 0 nor rpg >= 1 with gstride >= rpg (off >= 0),
+ * bf16 output of fp32 operands, an epilogue no launcher of the dispatch instantiates (id 0), ln_out without fp32 C / ln_g / ln_b,
+ * a_ln_* on a problem gemm_f32_direct_covers rejects (or without ws, or with
+ * variant 2: the fold would be dropped silently), any other variant, a forced variant whose launcher does not take the problem, and
+ * variant 44 with a_padded where the ragged 256-row tile would read more than the 127 rows a_padded vouches for.
+ * picked (4 ints, optional): [0] kernel id, [1] split count S (1: K not split), [2] the peel row (0: off), [3] bits: 1 persistent
+ * form (gemm_line.hip: look-alike tiles, tile origin in the scalar offset), 2 the split-K reduce applied the LayerNorm, 4 grouped.
+ * GEMM kernel ids (tests/test_gemm_edges_gpu.py reaches every id of this list):
+ *   gemm.hip:            1 gemm_kernel<float, 64, 64>;  2 gemm_kernel<float, 128, 128>;  3 gemm_kernel<bf16, 64, 64>;
+ *                        4 gemm_kernel<bf16, 128, 128>   (S > 1: followed by splitk_reduce_kernel / splitk_reduce_ln_kernel)
+ *   gemm_f32_direct.hip: 5 gemm_f32_direct_kernel<1, 16>;  6 gemm_f32_direct_group_kernel
+ *   gemm_glds.hip:       7 gemm_glds_ring3_kernel;  8 gemm_glds_kernel via launch_tile<128, 128, 2, 2, 64> (variant 2)
+ *   gemm_big.hip:        9 gemm_big_kernel
+ *   gemm_line.hip:       10 gemm_line_kernel<128>;  11 gemm_line_kernel<256>
+ *   gemm_x3.hip:         12 gemm_x3_kernel<64, 64>;  13 gemm_x3_kernel<128, 128>
+ *   not listed, not reachable through this hook: the lab-only experimental tilings gemm_ring.hip (variants 7-19), gemm_persist.hip (9),
+ *   gemm_rs.hip (36), gemm_glds_ring3w_kernel (31), launch_tile's 128-byte-row instance (3, 20-24, 27) and the timing variants of gemm_big.hip / gemm_line.hip (38-42, 45, 46) */
+typedef struct m3pc_debug_gemm_args {
+    int dtype;
+    const void* A;
+    int lda;
+    int amap[3]; /* rpg, gstride, off */
+    const void* W;
+    int ldw;
+    int M, N, K;
+    const float* bias; /* optional */
+    const float* rowtab; /* optional */
+    int rt_mod, rt_ld;
+    int gelu;
+    const float* res; /* optional; may be C */
+    int ldr;
+    void* C;
+    int f32out;
+    int ldc;
+    int cmap[3];
+    float* ws; /* optional */
+    long long ws_bytes;
+    int a_padded;
+    const float* ln_g;
+    const float* ln_b;
+    float* ln_out;
+    const float* a_ln_g;
+    const float* a_ln_b;
+    int variant;
+    void* stream;
+    int* picked; /* optional: 4 ints */
+} m3pc_debug_gemm_args;
+int m3pc_debug_gemm_ex(const m3pc_debug_gemm_args* a);
+/* the same checks and the same walk of the dispatch without launching anything (no GPU needed): the refusals, and `picked` as
+ * m3pc_debug_gemm_ex would report it */
+int m3pc_debug_gemm_plan(const m3pc_debug_gemm_args* a);
+/* n <= 4 fp32 problems in ONE launch (launch_gemm_f32_direct_group, kernel id 6): every problem must be one the few-row kernel
+ * covers, with ws set; stream and picked are those of a[0] */
+int m3pc_debug_gemm_group(const m3pc_debug_gemm_args* a, int n);
 /* clock probes of the last probed GEMM workgroup: {shader clocks, 100-MHz ticks} / gemm_big phase timers */
 int m3pc_debug_clock(long long* out2);
 int m3pc_debug_clock_big(long long* out4);

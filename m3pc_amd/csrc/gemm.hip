@@ -15,6 +15,11 @@
 
 namespace m3pc {
 
+#ifdef M3PC_LAB
+thread_local int g_gemm_picked[4] = {0, 0, 0, 0};
+thread_local int g_gemm_dry = 0;
+#endif
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -308,19 +313,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(GemmP p, int S, i
 int launch_splitk_reduce(const GemmP& p, int S, int exact_gelu, hipStream_t st) {
     if (p.ln_g && p.ln_out && p.Cf && !p.Cb && p.cmap.rpg == 0 && p.N % 256 == 0 && p.N <= 1024 && p.ldc % 4 == 0 &&
         (!p.res || p.ldr % 4 == 0)) {
-        hipLaunchKernelGGL(splitk_reduce_ln_kernel, dim3((p.M + 3) / 4), dim3(256), 0, st, p, S, exact_gelu);
+        M3PC_GEMM_LAUNCH(splitk_reduce_ln_kernel, dim3((p.M + 3) / 4), dim3(256), 0, st, p, S, exact_gelu);
+        M3PC_GEMM_PICK_FLAG(2);
         return 1;
     }
     const long long n = (long long)p.M * p.N;
     const int g = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p, S, exact_gelu);
+    M3PC_GEMM_LAUNCH(splitk_reduce_kernel, dim3(g), dim3(256), 0, st, p, S, exact_gelu);
     return 0;
 }
 
 template <typename T, int BM, int BN, int EPI>
 static void launch_cfg(const GemmP& p, hipStream_t st) {
     const int grid = ((p.M + BM - 1) / BM) * (p.N / BN);
-    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, EPI>), dim3(grid), dim3(256), 0, st, p);
+    M3PC_GEMM_LAUNCH((gemm_kernel<T, BM, BN, EPI>), dim3(grid), dim3(256), 0, st, p);
 }
 
 template <typename T, int EPI>
@@ -343,13 +349,15 @@ static int launch_epi(const GemmP& p, hipStream_t st) {
             if (S > 16) S = 16;
             while (S > 1 && (long long)S * p.M * p.N * 4 > p.ws_bytes) --S;
         }
+        M3PC_GEMM_PICK(sizeof(T) == 4 ? 1 : 3, S, 0, 0);
         if (S > 1) {
-            hipLaunchKernelGGL((gemm_kernel<T, 64, 64, EPI_SPLITK>), dim3((unsigned)tiles, S), dim3(256), 0, st, p);
+            M3PC_GEMM_LAUNCH((gemm_kernel<T, 64, 64, EPI_SPLITK>), dim3((unsigned)tiles, S), dim3(256), 0, st, p);
             return launch_splitk_reduce(p, S, (int)(sizeof(T) == 4), st);
         } else {
             launch_cfg<T, 64, 64, EPI>(p, st);
         }
     } else {
+        M3PC_GEMM_PICK(sizeof(T) == 4 ? 2 : 4, 1, 0, 0);
         launch_cfg<T, 128, 128, EPI>(p, st);
     }
     return 0;
@@ -369,7 +377,7 @@ static int launch_t(const GemmP& p, hipStream_t st) {
         case EPI_RES | EPI_F32OUT: return launch_epi<T, EPI_RES | EPI_F32OUT>(p, st);
         case EPI_ROWTAB: return launch_epi<T, EPI_ROWTAB>(p, st);
         case EPI_ROWTAB | EPI_F32OUT: return launch_epi<T, EPI_ROWTAB | EPI_F32OUT>(p, st);
-        default: return 0;  // no caller combines the remaining flags
+        default: M3PC_GEMM_PICK(0, 0, 0, 0); return 0;  // no caller combines the remaining flags (the lab hook refuses them: id 0)
     }
 }
 

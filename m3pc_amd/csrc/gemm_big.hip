@@ -276,18 +276,19 @@ bool launch_gemm_big(const GemmP& p, hipStream_t st) {
     const bool f32out = p.Cf != nullptr;
     const int epi = (p.gelu ? GE_GELU : 0) | (p.res ? GE_RES : 0) | (p.rowtab ? GE_ROWTAB : 0) | (f32out ? GE_F32OUT : 0);
     const dim3 grid(((p.M + 255) / 256) * (p.N / 256)), block(256);
+    M3PC_GEMM_PICK(9, 1, 0, 0);  // (a `default:` below leaves the pick behind: the caller's next launcher overwrites it)
     switch (epi) {
-        case 0: hipLaunchKernelGGL(gemm_big_kernel<0>, grid, block, 0, st, p); return true;
-        case GE_F32OUT: hipLaunchKernelGGL(gemm_big_kernel<GE_F32OUT>, grid, block, 0, st, p); return true;
-        case GE_GELU: hipLaunchKernelGGL(gemm_big_kernel<GE_GELU>, grid, block, 0, st, p); return true;
-        case GE_GELU | GE_F32OUT: hipLaunchKernelGGL((gemm_big_kernel<GE_GELU | GE_F32OUT>), grid, block, 0, st, p); return true;
+        case 0: M3PC_GEMM_LAUNCH(gemm_big_kernel<0>, grid, block, 0, st, p); return true;
+        case GE_F32OUT: M3PC_GEMM_LAUNCH(gemm_big_kernel<GE_F32OUT>, grid, block, 0, st, p); return true;
+        case GE_GELU: M3PC_GEMM_LAUNCH(gemm_big_kernel<GE_GELU>, grid, block, 0, st, p); return true;
+        case GE_GELU | GE_F32OUT: M3PC_GEMM_LAUNCH((gemm_big_kernel<GE_GELU | GE_F32OUT>), grid, block, 0, st, p); return true;
         case GE_RES | GE_F32OUT:
-            if (p.variant == 38) hipLaunchKernelGGL((gemm_big_kernel<GE_RES | GE_F32OUT, 1>), grid, block, 0, st, p);
-            else if (p.variant == 39) hipLaunchKernelGGL((gemm_big_kernel<GE_RES | GE_F32OUT, 2>), grid, block, 0, st, p);
-            else if (p.variant == 40) hipLaunchKernelGGL((gemm_big_kernel<GE_RES | GE_F32OUT, 3>), grid, block, 0, st, p);
-            else if (p.variant == 41) hipLaunchKernelGGL((gemm_big_kernel<GE_RES | GE_F32OUT, 5>), grid, block, 0, st, p);
-            else if (p.variant == 42) hipLaunchKernelGGL((gemm_big_kernel<GE_RES | GE_F32OUT, 6>), grid, block, 0, st, p);
-            else hipLaunchKernelGGL((gemm_big_kernel<GE_RES | GE_F32OUT, 0>), grid, block, 0, st, p);
+            if (p.variant == 38) M3PC_GEMM_LAUNCH((gemm_big_kernel<GE_RES | GE_F32OUT, 1>), grid, block, 0, st, p);
+            else if (p.variant == 39) M3PC_GEMM_LAUNCH((gemm_big_kernel<GE_RES | GE_F32OUT, 2>), grid, block, 0, st, p);
+            else if (p.variant == 40) M3PC_GEMM_LAUNCH((gemm_big_kernel<GE_RES | GE_F32OUT, 3>), grid, block, 0, st, p);
+            else if (p.variant == 41) M3PC_GEMM_LAUNCH((gemm_big_kernel<GE_RES | GE_F32OUT, 5>), grid, block, 0, st, p);
+            else if (p.variant == 42) M3PC_GEMM_LAUNCH((gemm_big_kernel<GE_RES | GE_F32OUT, 6>), grid, block, 0, st, p);
+            else M3PC_GEMM_LAUNCH((gemm_big_kernel<GE_RES | GE_F32OUT, 0>), grid, block, 0, st, p);
             return true;
         default: return false;
     }

@@ -365,7 +365,8 @@ bool gemm_f32_direct_covers(const GemmP& p) {
 bool launch_gemm_f32_direct(const GemmP& p, hipStream_t st) {
     if (!gemm_f32_direct_covers(p)) return false;
     const int grid = ((p.M + 31) / 32) * (p.N / 32);
-    hipLaunchKernelGGL((gemm_f32_direct_kernel<1, 16>), dim3(grid), dim3(1024), 0, st, p);
+    M3PC_GEMM_PICK(5, 1, 0, 0);
+    M3PC_GEMM_LAUNCH((gemm_f32_direct_kernel<1, 16>), dim3(grid), dim3(1024), 0, st, p);
     return true;
 }
 
@@ -380,7 +381,8 @@ bool launch_gemm_f32_direct_group(const GemmP* ps, int n, hipStream_t st) {
         tiles = t > tiles ? t : tiles;
     }
     for (int i = n; i < 4; ++i) g.p[i] = ps[0];
-    hipLaunchKernelGGL(gemm_f32_direct_group_kernel, dim3(tiles, n), dim3(1024), 0, st, g);
+    M3PC_GEMM_PICK(6, 1, 0, 4);
+    M3PC_GEMM_LAUNCH(gemm_f32_direct_group_kernel, dim3(tiles, n), dim3(1024), 0, st, g);
     return true;
 }
 

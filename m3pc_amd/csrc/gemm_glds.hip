@@ -566,8 +566,8 @@ static bool launch_ring3w(const GemmP& p, hipStream_t st) {
     const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) | (f32out ? EPI_F32OUT : 0);
     const dim3 grid(((p.M + 255) / 256) * (p.N / 128)), block(256);
     switch (epi) {
-        case 0: hipLaunchKernelGGL(gemm_glds_ring3w_kernel<0>, grid, block, 0, st, p); return true;
-        case EPI_GELU: hipLaunchKernelGGL(gemm_glds_ring3w_kernel<EPI_GELU>, grid, block, 0, st, p); return true;
+        case 0: M3PC_GEMM_LAUNCH(gemm_glds_ring3w_kernel<0>, grid, block, 0, st, p); return true;
+        case EPI_GELU: M3PC_GEMM_LAUNCH(gemm_glds_ring3w_kernel<EPI_GELU>, grid, block, 0, st, p); return true;
         default: return false;
     }
 }
@@ -578,13 +578,14 @@ static bool launch_ring3(const GemmP& p, hipStream_t st) {
     const int tiles = p.peel > 0 ? (p.peel / 128) * (p.N / 128) + ((p.M - p.peel + 63) / 64) * (p.N / 64)
                                  : ((p.M + 127) / 128) * (p.N / 128);
     const dim3 grid(tiles), block(256);
+    M3PC_GEMM_PICK(7, 1, p.peel > 0 ? p.peel : 0, 0);
     switch (epi) {
-        case 0: hipLaunchKernelGGL(gemm_glds_ring3_kernel<0>, grid, block, 0, st, p); return true;
-        case EPI_F32OUT: hipLaunchKernelGGL(gemm_glds_ring3_kernel<EPI_F32OUT>, grid, block, 0, st, p); return true;
-        case EPI_GELU: hipLaunchKernelGGL(gemm_glds_ring3_kernel<EPI_GELU>, grid, block, 0, st, p); return true;
-        case EPI_GELU | EPI_F32OUT: hipLaunchKernelGGL(gemm_glds_ring3_kernel<EPI_GELU | EPI_F32OUT>, grid, block, 0, st, p); return true;
-        case EPI_RES | EPI_F32OUT: hipLaunchKernelGGL(gemm_glds_ring3_kernel<EPI_RES | EPI_F32OUT>, grid, block, 0, st, p); return true;
-        case EPI_ROWTAB | EPI_F32OUT: hipLaunchKernelGGL(gemm_glds_ring3_kernel<EPI_ROWTAB | EPI_F32OUT>, grid, block, 0, st, p); return true;
+        case 0: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<0>, grid, block, 0, st, p); return true;
+        case EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_F32OUT>, grid, block, 0, st, p); return true;
+        case EPI_GELU: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_GELU>, grid, block, 0, st, p); return true;
+        case EPI_GELU | EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_GELU | EPI_F32OUT>, grid, block, 0, st, p); return true;
+        case EPI_RES | EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_RES | EPI_F32OUT>, grid, block, 0, st, p); return true;
+        case EPI_ROWTAB | EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_ROWTAB | EPI_F32OUT>, grid, block, 0, st, p); return true;
         default: return false;
     }
 }
@@ -610,18 +611,19 @@ static void launch_cfg(const GemmP& p, hipStream_t st) {
     if (p.peel > 0) {
         if constexpr (BM == 128 && BN == 128 && WM == 2 && WN == 2) {
             const int grid = (p.peel / BM) * (p.N / BN) + ((p.M - p.peel + 63) / 64) * (p.N / 64);
-            hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, EPI, WM, WN, ROWB, true>), dim3(grid), dim3(256), 0, st, p);
+            M3PC_GEMM_LAUNCH((gemm_glds_kernel<BM, BN, EPI, WM, WN, ROWB, true>), dim3(grid), dim3(256), 0, st, p);
             return;
         }
     }
     const int grid = ((p.M + BM - 1) / BM) * (p.N / BN);
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, EPI, WM, WN, ROWB, false>), dim3(grid), dim3(WM * WN * 64), 0, st, p);
+    M3PC_GEMM_LAUNCH((gemm_glds_kernel<BM, BN, EPI, WM, WN, ROWB, false>), dim3(grid), dim3(WM * WN * 64), 0, st, p);
 }
 
 template <int BM, int BN, int WM, int WN, int ROWB = 128>
 static bool launch_tile(const GemmP& p, hipStream_t st) {
     const bool f32out = p.Cf != nullptr;
     const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) | (f32out ? EPI_F32OUT : 0);
+    M3PC_GEMM_PICK(BM == 128 && BN == 128 && WM == 2 && WN == 2 ? 8 : 0, 1, BM == 128 && BN == 128 && p.peel > 0 ? p.peel : 0, 0);
     switch (epi) {
         case 0: launch_cfg<BM, BN, 0, WM, WN, ROWB>(p, st); return true;
         case EPI_F32OUT: launch_cfg<BM, BN, EPI_F32OUT, WM, WN, ROWB>(p, st); return true;

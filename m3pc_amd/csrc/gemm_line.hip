@@ -316,16 +316,17 @@ static bool launch_line(const GemmP& p, hipStream_t st) {
     const int tiles = ((p.M + BT - 1) / BT) * (p.N / BT), slots = (BT == 128 ? 2 : 1) * 256;  // resident workgroups on 256 CUs
     const bool uniform = p.amap.rpg == 0 && (p.M % BT == 0 || p.a_padded);  // (see the kernel: persistent workgroups need look-alike tiles)
     const dim3 grid(uniform && tiles > slots ? slots : tiles), block(256);
+    M3PC_GEMM_PICK(BT == 128 ? 10 : 11, 1, 0, uniform ? 1 : 0);
     switch (epi) {
         case 0:
-            if (p.variant == 45) hipLaunchKernelGGL((gemm_line_kernel<BT, 0, 1>), grid, block, 0, st, p);
-            else if (p.variant == 46) hipLaunchKernelGGL((gemm_line_kernel<BT, 0, 2>), grid, block, 0, st, p);
-            else hipLaunchKernelGGL((gemm_line_kernel<BT, 0, 0>), grid, block, 0, st, p);
+            if (p.variant == 45) M3PC_GEMM_LAUNCH((gemm_line_kernel<BT, 0, 1>), grid, block, 0, st, p);
+            else if (p.variant == 46) M3PC_GEMM_LAUNCH((gemm_line_kernel<BT, 0, 2>), grid, block, 0, st, p);
+            else M3PC_GEMM_LAUNCH((gemm_line_kernel<BT, 0, 0>), grid, block, 0, st, p);
             return true;
-        case GE_F32OUT: hipLaunchKernelGGL((gemm_line_kernel<BT, GE_F32OUT>), grid, block, 0, st, p); return true;
-        case GE_GELU: hipLaunchKernelGGL((gemm_line_kernel<BT, GE_GELU>), grid, block, 0, st, p); return true;
-        case GE_GELU | GE_F32OUT: hipLaunchKernelGGL((gemm_line_kernel<BT, GE_GELU | GE_F32OUT>), grid, block, 0, st, p); return true;
-        case GE_RES | GE_F32OUT: hipLaunchKernelGGL((gemm_line_kernel<BT, GE_RES | GE_F32OUT>), grid, block, 0, st, p); return true;
+        case GE_F32OUT: M3PC_GEMM_LAUNCH((gemm_line_kernel<BT, GE_F32OUT>), grid, block, 0, st, p); return true;
+        case GE_GELU: M3PC_GEMM_LAUNCH((gemm_line_kernel<BT, GE_GELU>), grid, block, 0, st, p); return true;
+        case GE_GELU | GE_F32OUT: M3PC_GEMM_LAUNCH((gemm_line_kernel<BT, GE_GELU | GE_F32OUT>), grid, block, 0, st, p); return true;
+        case GE_RES | GE_F32OUT: M3PC_GEMM_LAUNCH((gemm_line_kernel<BT, GE_RES | GE_F32OUT>), grid, block, 0, st, p); return true;
         default: return false;
     }
 }

@@ -213,7 +213,7 @@ void launch_f32_split_bf16(const float* in, bf16_t* hi, bf16_t* lo, long long n,
 template <int BM, int BN, int EPI>
 static void x3_launch(const GemmP& p, int S, hipStream_t st) {
     const int grid = ((p.M + BM - 1) / BM) * (p.N / BN);
-    hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, EPI>), dim3(grid, S), dim3(256), 0, st, p);
+    M3PC_GEMM_LAUNCH((gemm_x3_kernel<BM, BN, EPI>), dim3(grid, S), dim3(256), 0, st, p);
 }
 
 template <int EPI>
@@ -222,6 +222,7 @@ static int x3_launch_epi(const GemmP& p, hipStream_t st) {
     // else 64x64; split K over blocks only where the caller allows it (p.ws) and the tiles alone do not fill the chip
     const long long big_tiles = (long long)((p.M + 127) / 128) * (p.N / 128);
     if ((p.N % 128) == 0 && big_tiles >= 512) {
+        M3PC_GEMM_PICK(13, 1, 0, 0);
         x3_launch<128, 128, EPI>(p, 1, st);
         return 0;
     }
@@ -234,6 +235,7 @@ static int x3_launch_epi(const GemmP& p, hipStream_t st) {
         if (S > 16) S = 16;
         while (S > 1 && (long long)S * p.M * p.N * 4 > p.ws_bytes) --S;
     }
+    M3PC_GEMM_PICK(12, S, 0, 0);
     if (S > 1) {
         x3_launch<64, 64, X3_SPLITK>(p, S, st);
         return launch_splitk_reduce(p, S, 1, st);

@@ -290,6 +290,28 @@ extern thread_local int g_attn_picked;
 #define M3PC_ATTN_PICK(id) ((void)0)
 #endif
 void launch_attention_bf16(const AttnP& p, hipStream_t st);
+// lab build: what the GEMM dispatch launched last on the calling thread -- {kernel id, split count S (1: K not split), peel row
+// (0: off), flags: 1 persistent form, 2 the split-K reduce applied the LayerNorm, 4 grouped launch}; the ids are listed in
+// include/m3pc_hip_debug.h (m3pc_debug_gemm_ex).  With g_gemm_dry set the launchers of gemm.hip, gemm_x3.hip, gemm_glds.hip,
+// gemm_big.hip, gemm_line.hip and gemm_f32_direct.hip walk their dispatch and record the pick WITHOUT launching anything: the
+// hook learns what would run (and whether anything would) before it touches the GPU.  The product build records nothing and
+// M3PC_GEMM_LAUNCH is hipLaunchKernelGGL.
+#ifdef M3PC_LAB
+extern thread_local int g_gemm_picked[4];
+extern thread_local int g_gemm_dry;
+#define M3PC_GEMM_PICK(id, S, peel, flags)                                                          \
+    (::m3pc::g_gemm_picked[0] = (id), ::m3pc::g_gemm_picked[1] = (S), ::m3pc::g_gemm_picked[2] = (peel), \
+     ::m3pc::g_gemm_picked[3] = (flags))
+#define M3PC_GEMM_PICK_FLAG(f) (::m3pc::g_gemm_picked[3] |= (f))
+#define M3PC_GEMM_LAUNCH(...)                                     \
+    do {                                                          \
+        if (!::m3pc::g_gemm_dry) hipLaunchKernelGGL(__VA_ARGS__); \
+    } while (0)
+#else
+#define M3PC_GEMM_PICK(id, S, peel, flags) ((void)0)
+#define M3PC_GEMM_PICK_FLAG(f) ((void)0)
+#define M3PC_GEMM_LAUNCH(...) hipLaunchKernelGGL(__VA_ARGS__)
+#endif
 
 // Encoder token embedding (mtm_model.py:546-557) with the tokenizer affine folded in and the
 // mask-drop gather (mtm_model.py:534-544) applied: X[b, j, :] for the kept tokens only.

@@ -1287,6 +1287,149 @@ int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias,
     return check_launch("debug_gemm");
 }
 
+// Every GEMM the library launches, on caller tensors, with everything a GemmP can carry (tests/test_gemm_edges_gpu.py).  The
+// checks below are the shape rules of the register-staged kernel every problem can fall back to; what the dispatch would launch is
+// learnt from a dry walk of the launchers (g_gemm_dry, csrc/kernels.h), so nothing reaches the GPU before the call is known to be
+// covered.  Fills `p` (and, for dtype 2, nothing yet of W's split) or returns the error.
+static int debug_gemm_fill(const m3pc_debug_gemm_args* a, GemmP& p) {
+    if (!a) return fail(M3PC_EINVAL, "debug_gemm_ex: null argument");
+    const int dt = a->dtype;
+    if (dt != DT_F32 && dt != DT_BF16 && dt != DT_X3) return fail(M3PC_EINVAL, "debug_gemm_ex: dtype %d", dt);
+    if (!a->A || !a->W || !a->C) return fail(M3PC_EINVAL, "debug_gemm_ex: null operand");
+    if (a->M < 1 || a->M > (1 << 20) || a->N < 32 || a->N > (1 << 16) || a->K < 1 || a->K > (1 << 16)) return fail(M3PC_EINVAL, "debug_gemm_ex: M / N / K out of range");
+    const int es = dt == DT_BF16 ? 2 : 4;  // bytes per element of A (x3: fp32 activations; its W copies are bf16)
+    if (a->N % 32) return fail(M3PC_EINVAL, "debug_gemm_ex: N %d is not a multiple of 32 (columns would be dropped)", a->N);
+    if (((long long)a->K * es) % 128) return fail(M3PC_EINVAL, "debug_gemm_ex: K %d is not a whole number of 128-byte k-tiles (k terms would be dropped)", a->K);
+    if (dt == DT_F32 && !a->f32out) return fail(M3PC_EINVAL, "debug_gemm_ex: fp32 operands have fp32 output only");
+    const int f32out = dt == DT_F32 || a->f32out;
+    const int os = f32out ? 4 : 2;
+    const uintptr_t ptrs = (uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->C | (uintptr_t)a->bias | (uintptr_t)a->rowtab | (uintptr_t)a->res |
+                           (uintptr_t)a->ws | (uintptr_t)a->ln_g | (uintptr_t)a->ln_b | (uintptr_t)a->ln_out | (uintptr_t)a->a_ln_g |
+                           (uintptr_t)a->a_ln_b;
+    if (ptrs & 15) return fail(M3PC_EINVAL, "debug_gemm_ex: pointers must be 16-byte aligned");
+    if (a->lda < a->K || a->ldw < a->K || a->ldc < a->N || (a->res && a->ldr < a->N) || (a->rowtab && a->rt_ld < a->N))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: a leading dimension is below its row length");
+    // (x3: W's bf16 copies keep ldw, so their rows need ldw % 8 as well)
+    if (((long long)a->lda * es) % 16 || ((long long)a->ldw * (dt == DT_F32 ? 4 : 2)) % 16 || (dt == DT_X3 && a->ldw % 4) || ((long long)a->ldc * os) % 16 ||
+        (a->res && a->ldr % 4) || (a->rowtab && a->rt_ld % 4))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: rows of a leading dimension leave 16-byte alignment");
+    if (a->rowtab && a->rt_mod < 1) return fail(M3PC_EINVAL, "debug_gemm_ex: rowtab with rt_mod %d", a->rt_mod);
+    for (const int* m : {a->amap, a->cmap})
+        if (m[0] < 0 || m[2] < 0 || (m[0] >= 1 && m[1] < m[0])) return fail(M3PC_EINVAL, "debug_gemm_ex: row map {%d, %d, %d}", m[0], m[1], m[2]);
+    if (a->ws && a->ws_bytes < 0) return fail(M3PC_EINVAL, "debug_gemm_ex: negative ws_bytes");
+    if (a->ln_out && (!f32out || !a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_gemm_ex: ln_out needs fp32 C, ln_g and ln_b");
+    if ((a->a_ln_g != nullptr) != (a->a_ln_b != nullptr)) return fail(M3PC_EINVAL, "debug_gemm_ex: a_ln_g and a_ln_b go together");
+    const int v = a->variant;
+    if (!(v == 0 || (dt == DT_BF16 && (v == 2 || v == 26 || v == 37 || v == 43 || v == 44)) || (dt == DT_F32 && v == 2)))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: variant %d of dtype %d is not one this hook drives", v, dt);
+    // (a_padded vouches for 127 rows behind A: a ragged 256-row tile of gemm_line_kernel<256>'s persistent form may need up to 255)
+    if (v == 44 && a->a_padded && a->M % 256 && 256 - a->M % 256 > 127)
+        return fail(M3PC_EINVAL, "debug_gemm_ex: variant 44 with a_padded would read %d rows behind A", 256 - a->M % 256);
+    p = gemm_basic(a->A, a->lda, a->W, a->ldw, a->M, a->N, a->K, a->bias);
+    p.amap = RowMap{a->amap[0], a->amap[1], a->amap[2]};
+    p.cmap = RowMap{a->cmap[0], a->cmap[1], a->cmap[2]};
+    p.rowtab = a->rowtab;
+    if (a->rowtab) {
+        p.rt_mod = a->rt_mod;
+        p.rt_ld = a->rt_ld;
+    }
+    p.gelu = a->gelu ? 1 : 0;
+    p.res = a->res;
+    p.ldr = a->ldr;
+    if (f32out)
+        p.Cf = (float*)a->C;
+    else
+        p.Cb = (bf16_t*)a->C;
+    p.ldc = a->ldc;
+    p.ws = a->ws;
+    p.ws_bytes = a->ws ? a->ws_bytes : 0;
+    p.a_padded = a->a_padded ? 1 : 0;
+    p.ln_g = a->ln_out ? a->ln_g : nullptr;
+    p.ln_b = a->ln_out ? a->ln_b : nullptr;
+    p.ln_out = a->ln_out;
+    p.a_ln_g = a->a_ln_g;
+    p.a_ln_b = a->a_ln_b;
+    p.variant = v;
+    if (a->a_ln_g && (dt != DT_F32 || !a->ws || v == 2 || !gemm_f32_direct_covers(p)))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: a_ln_* on a problem the few-row fp32 kernel does not take (the fold would be dropped)");
+    return 0;
+}
+
+// the checks and the dry walk: fills p (x3: W still the caller's fp32 tensor) and plan[4] = what the dispatch would launch
+static int debug_gemm_plan(const m3pc_debug_gemm_args* a, GemmP& p, int* plan) {
+    if (a && a->picked) a->picked[0] = a->picked[1] = a->picked[2] = a->picked[3] = 0;
+    if (int rc = debug_gemm_fill(a, p)) return rc;
+    const int dt = a->dtype;
+    if (dt == DT_X3) p.w_lo_off = (long long)a->N * a->ldw;  // (the hi / lo copies keep W's layout)
+    M3PC_GEMM_PICK(0, 0, 0, 0);
+    g_gemm_dry = 1;
+    const int dry = dt == DT_X3 ? launch_gemm_x3(p, nullptr) : launch_gemm(p, dt, nullptr);
+    g_gemm_dry = 0;
+    for (int i = 0; i < 4; ++i) plan[i] = g_gemm_picked[i];
+    if (dry < 0 || plan[0] == 0) return fail(M3PC_EINVAL, "debug_gemm_ex: no kernel of the dispatch covers this problem (epilogue flags / shape)");
+    if (a->N % 64 && plan[0] != 5)  // (only the few-row fp32 kernel has 32-column tiles)
+        return fail(M3PC_EINVAL, "debug_gemm_ex: N %d is not a multiple of 64 (kernel %d would drop columns)", a->N, plan[0]);
+    const int v = a->variant;
+    const int want = dt != DT_BF16 ? 0 : v == 2 ? 8 : v == 26 ? 7 : v == 37 ? 9 : v == 43 ? 10 : v == 44 ? 11 : 0;
+    if (want && plan[0] != want) return fail(M3PC_EINVAL, "debug_gemm_ex: variant %d does not take this problem (kernel %d would run)", v, plan[0]);
+    return 0;
+}
+
+int m3pc_debug_gemm_plan(const m3pc_debug_gemm_args* a) {
+    GemmP p;
+    int plan[4];
+    if (int rc = debug_gemm_plan(a, p, plan)) return rc;
+    if (a->picked)
+        for (int i = 0; i < 4; ++i) a->picked[i] = plan[i];
+    return 0;
+}
+
+int m3pc_debug_gemm_ex(const m3pc_debug_gemm_args* a) {
+    GemmP p;
+    int plan[4];
+    if (int rc = debug_gemm_plan(a, p, plan)) return rc;
+    hipStream_t st = (hipStream_t)a->stream;
+    if (a->dtype == DT_X3) {  // hi / lo copies of W, as m3pc_load_weights keeps them.  (A lab hook's shortcut: the buffer is a
+        // function-static that grows and is never freed, W is split again on every call, and calls from two threads would share it)
+        static bf16_t* wsplit = nullptr;
+        static size_t cap = 0;
+        const size_t nw = (size_t)a->N * a->ldw;
+        if (nw > cap) {
+            if (wsplit) HIPCHK(hipFree(wsplit));
+            wsplit = nullptr;
+            cap = 0;
+            HIPCHK(hipMalloc((void**)&wsplit, 2 * nw * sizeof(bf16_t)));
+            cap = nw;
+        }
+        launch_f32_split_bf16((const float*)a->W, wsplit, wsplit + nw, (long long)nw, st);
+        p.W = wsplit;
+    }
+    M3PC_GEMM_PICK(0, 0, 0, 0);
+    if (a->dtype == DT_X3)
+        launch_gemm_x3(p, st);
+    else
+        launch_gemm(p, a->dtype, st);
+    if (a->picked)
+        for (int i = 0; i < 4; ++i) a->picked[i] = g_gemm_picked[i];
+    return check_launch("debug_gemm_ex");
+}
+
+int m3pc_debug_gemm_group(const m3pc_debug_gemm_args* a, int n) {
+    if (!a || n < 1 || n > 4) return fail(M3PC_EINVAL, "debug_gemm_group: 1..4 problems");
+    if (a[0].picked) a[0].picked[0] = a[0].picked[1] = a[0].picked[2] = a[0].picked[3] = 0;
+    GemmP ps[4];
+    for (int i = 0; i < n; ++i) {
+        if (int rc = debug_gemm_fill(a + i, ps[i])) return rc;
+        if (a[i].dtype != DT_F32 || !a[i].ws || a[i].variant != 0 || a[i].ln_out || !gemm_f32_direct_covers(ps[i]))
+            return fail(M3PC_EINVAL, "debug_gemm_group: problem %d is not one the few-row fp32 kernel covers", i);
+    }
+    M3PC_GEMM_PICK(0, 0, 0, 0);
+    if (!launch_gemm_f32_direct_group(ps, n, (hipStream_t)a[0].stream)) return fail(M3PC_EINVAL, "debug_gemm_group: not covered");
+    if (a[0].picked)
+        for (int i = 0; i < 4; ++i) a[0].picked[i] = g_gemm_picked[i];
+    return check_launch("debug_gemm_group");
+}
+
 // Not part of the public header (tools/gemm_bench.py): clock counters of the last probed GEMM workgroup.
 // cap > 0: from now on every fused-tail launch of the handle logs the phase stamps of its workgroup 37 into a ring of `cap`
 // entries (64 int64 each: wave w at [16 w ..]); cap == 0: copy the ring to out (host, cap_prev * 64 int64), return how many

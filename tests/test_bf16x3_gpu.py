@@ -54,7 +54,7 @@ def _ref(A, W, bias, R, gelu):
 @pytest.mark.parametrize("K,N", [(512, 512), (512, 1536), (512, 2048), (2048, 512)])
 @pytest.mark.parametrize("epi", ["bias", "gelu", "res", "none"])
 def test_x3_gemm_against_fp64(K, N, epi):
-    """|C - C_fp64| <= 3e-5 sum_k |a_k w_k| elementwise at the step's shapes, ragged M, every epilogue; split-K (variant 0 on few
+    """|C - C_fp64| <= 3e-5 sum_k |a_k w_k| elementwise, on every row, at the step's shapes, ragged M, every epilogue; split-K (variant 0 on few
     rows) included.  And the result of a row does not depend on the row count (128x128 against 64x64 tiles, no split)."""
     lib = lab_library()
     dev = torch.device("cuda")
@@ -67,11 +67,12 @@ def test_x3_gemm_against_fp64(K, N, epi):
     gelu = int(epi == "gelu")
     out = torch.full((M, N), float("nan"), device=dev)
     _gemm_x3(lib, A, W, bias, R, out, gelu, 1)
-    sel = torch.cat([torch.arange(256), torch.arange(M // 2, M // 2 + 128), torch.arange(M - 256, M)]).to(dev)
-    ref, bound = _ref(A[sel], W, bias, R[sel] if R is not None else None, gelu)
-    err = (out[sel].double() - ref).abs()
     assert bool(torch.isfinite(out).all())
-    assert bool((err <= 3e-5 * bound + 1e-30).all()), float((err / bound).max())
+    for r0 in range(0, M, 4096):  # every row
+        r1 = min(M, r0 + 4096)
+        ref, bound = _ref(A[r0:r1], W, bias, R[r0:r1] if R is not None else None, gelu)
+        err = (out[r0:r1].double() - ref).abs()
+        assert bool((err <= 3e-5 * bound + 1e-30).all()), (r0, float((err / bound).max()))
     # a shard's row count: 300 + 5 rows take 64x64 tiles (the full problem took 128x128 where N allows): identical bits
     Ms = 305
     small = torch.full((Ms, N), float("nan"), device=dev)
