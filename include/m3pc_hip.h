@@ -42,7 +42,8 @@
 extern "C" {
 #endif
 
-/* ABI history.  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+/* ABI history.  Added within v7 (new symbols and structures only; nothing existing changed): m3pc_plan_step_certified,
+ * m3pc_calibrate_delta, m3pc_cert_args, m3pc_cert_record.  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -403,6 +404,64 @@ int m3pc_rescore_listed(m3pc_handle* h, const m3pc_plan_args* args, const float*
 int m3pc_select(m3pc_handle* h, const float* expect_return, const float* a0, long long a0_stride, int n,
                 float temperature, const float* expo, float* p, float* eval_action, int* argmax,
                 int* sample_idx, float* sample_action, void* stream);
+
+/* The CERTIFIED plan step as one call: learner.py:278-325 with the candidate pass in bf16 / split bf16 and both returned actions
+ * -- the arg-max behind eval_action (learner.py:318-323) and the multinomial draw behind sample_action (learner.py:324-325) --
+ * following the fp32 path's decisions.  It is the protocol of m3pc_amd/certificate.py (resolve) for a serial step, made of the
+ * calls above in the same order, all on `stream`:
+ *   m3pc_policy_pass (honours M3PC_PLAN_PRUNED_POLICY) -> m3pc_candidate_pass in args->precision -> m3pc_topk_race_window
+ *   (m3pc_topk_window when rmax == 0) -> m3pc_rescore of list[rmax - rfirst .. rmax + kmin) -> m3pc_merge_race_select -> read the
+ *   certificates (need, need_race) -> while one asks for more: raise delta (grow_delta), m3pc_rescore of the score entries up to
+ *   `need` (<= kmax) / of the race entries up to `need_race` (<= rmax), merge + select again.
+ *   Window set (need > kmax, need <= 1024 - 32): the `need` best candidates by low-precision score (descending, ties to the lower
+ *   index: m3pc_topk_window's order) are listed in place of the score entries and re-scored in chunks of max_rescore.
+ *   Everything (a larger window set, an exhausted race list, or a window set whose certificate still asks for more): one fp32
+ *   m3pc_candidate_pass in the candidate workspace, stream-ordered, no device-wide synchronisation; the select then runs on fp32
+ *   scores alone (record: everything = 1, n_rescored = n_total).
+ * args->precision == M3PC_PREC_FP32: m3pc_plan_step + m3pc_select, record {certified = 1, everything = 1, n_rescored = n_total};
+ * m3pc_cert_args is then read for its temperature only.  One rank: n_begin == 0 and n_count == n_total (<= 16384), else
+ * M3PC_EINVAL.  Bad kmin / kmax / rfirst / rmax and null required pointers return M3PC_EINVAL before any HIP call.
+ *   expo            device (n_total,) the Exp(1) variates of the draw (m3pc_select)
+ *   loc, std        device out (T,A), optional;  sample_actions device out (n_total,h,A)
+ *   scores_low      device out (n_total,): the candidate pass's scores
+ *   merged          device out (n_total,): the vector the select ran on (m3pc_rescore_merge)
+ *   list            device out (rmax + 1024,) int32, optional: the final lists -- the n_race re-scored race entries in front of
+ *                   list[rmax], the n_rescored re-scored score entries from list[rmax] on (not after `everything`)
+ *   p, eval_action, argmax, sample_idx, sample_action   device out, each optional, as m3pc_select
+ *   record          host out, valid on return; every device output is complete in stream order
+ * The certificates are read from a pinned host-mapped block the handle owns per step slot (the host_stats / seq mechanism of
+ * m3pc_rescore_merge): the host spins on the sequence number for at most 10 s, then synchronises `stream` once and reads the
+ * device copy; M3PC_EHIP if that fails too.  The host blocks until the LAST certificate of the step has been read. */
+typedef struct m3pc_cert_args {
+    float temperature;   /* cfg.temperature (learner.py:319) */
+    float delta;         /* bound on |(low - fp32) - shift| going in (m3pc_calibrate_delta) */
+    int grow_delta;      /* 1: raise delta to 1.5 x the deviation this step's re-scored set shows; 0: delta is fixed */
+    int kmin, kmax;      /* first-pass / listed score entries; 1 <= kmin <= min(kmax, n_total), kmax + rmax <= 1023 */
+    int rfirst, rmax;    /* first-pass / listed race entries; 1 <= rfirst <= rmax <= min(64, n_total), or rmax == rfirst == 0:
+                            the arg-max certificate only (the draw is then a near-winner of the fp32 draw) */
+} m3pc_cert_args;
+
+typedef struct m3pc_cert_record {
+    int n_rescored, n_race;            /* score / race entries re-scored in fp32 at the end */
+    int need_first, need_race_first;   /* what the FIRST certificates asked for */
+    int saturated, everything, certified, rounds;  /* window set taken / fp32 scores for every candidate / the step ended on
+                                                      satisfied certificates (it cannot end otherwise) / merges issued */
+    float delta, shift, deviation, margin;  /* delta coming out (>= going in); the LAST merge's common shift, largest deviation
+                                               from it, and margin of the arg-max threshold over the best un-listed score */
+} m3pc_cert_record;
+
+int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_cert_args* cert, const float* states,
+                             const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std,
+                             float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
+                             int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* record, void* stream);
+
+/* delta of the certified step from ONE full fp32 candidate pass over the candidates of the step that owns args->slot (its
+ * policy pass is reused; the pass runs in the candidate workspace): d = scores_low - fp32, c = the lower median of d (the
+ * element torch.median returns), *delta_out = max(factor * max|d - c|, 1e-6 * max|fp32|, 1e-30).  A caller keeps the maximum
+ * over the first steps behind a weight load (m3pc_amd/planner.py: 16 windows, factor 1.6).  n_total <= 16384, one rank;
+ * stream-ordered, with one bounded read of the host-mapped statistics at the end (as above). */
+int m3pc_calibrate_delta(m3pc_handle* h, const m3pc_plan_args* args, const float* states, const float* actions, const float* rewards,
+                         const float* eps, const float* scores_low, float factor, float* delta_out, void* stream);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

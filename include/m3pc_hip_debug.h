@@ -91,6 +91,11 @@ int m3pc_debug_clock(long long* out2);
 int m3pc_debug_clock_big(long long* out4);
 /* the top-k kernels on their own: indices of the k largest of v (n), descending, ties to the lower index */
 int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream);
+/* the statistics kernel of m3pc_calibrate_delta on caller vectors: stats (device, 8 floats) = {lower median c of scores_low - f32,
+ * max |scores_low - f32 - c|, max |f32|, 0 ...}; *delta_out (host) = max(factor * stats[1], 1e-6 * stats[2], 1e-30).  n <= 16384.
+ * Synchronises the stream. */
+int m3pc_debug_calibrate_stats(const float* scores_low, const float* f32, int n, float factor, float* stats, float* delta_out,
+                               void* stream);
 /* the fused layer tail (block_fused.hip) on caller tensors; see csrc/m3pc.hip for the argument layout */
 long long m3pc_debug_block_stream_bytes(void);
 int m3pc_debug_block_fused(const void* O, int M, const float* res, const float* rowtab, int rt_mod, const void* Wo, const void* W1,

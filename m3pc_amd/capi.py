@@ -43,6 +43,7 @@ EXPORTS = (
     "m3pc_rescore_listed", "m3pc_rescore_merge", "m3pc_topk_race_window", "m3pc_rescore_merge_race", "m3pc_merge_race_select", "m3pc_select",
     "m3pc_profile_enable",
     "m3pc_profile_read",
+    "m3pc_plan_step_certified", "m3pc_calibrate_delta",
 )
 
 
@@ -61,6 +62,19 @@ class PlanArgs(C.Structure):
                 ("n_begin", C.c_int), ("n_count", C.c_int), ("lmbda", C.c_double), ("discount", C.c_double),
                 ("rtg", C.c_double), ("slot", C.c_int), ("returns_f64", C.c_int), ("returns", C.c_void_p),
                 ("flags", C.c_int), ("window", C.c_int)]
+
+
+class CertArgs(C.Structure):
+    """m3pc_cert_args: what ``m3pc_plan_step_certified`` takes of the certified re-score's state."""
+    _fields_ = [("temperature", C.c_float), ("delta", C.c_float), ("grow_delta", C.c_int), ("kmin", C.c_int), ("kmax", C.c_int),
+                ("rfirst", C.c_int), ("rmax", C.c_int)]
+
+
+class CertRecord(C.Structure):
+    """m3pc_cert_record: what the certified step re-scored and what its certificates said."""
+    _fields_ = [("n_rescored", C.c_int), ("n_race", C.c_int), ("need_first", C.c_int), ("need_race_first", C.c_int),
+                ("saturated", C.c_int), ("everything", C.c_int), ("certified", C.c_int), ("rounds", C.c_int),
+                ("delta", C.c_float), ("shift", C.c_float), ("deviation", C.c_float), ("margin", C.c_float)]
 
 
 PLAN_DEFER_JOIN = 1
@@ -116,6 +130,9 @@ def load_library(path: Optional[str] = None):
         "m3pc_merge_race_select": [vp, vp, vp, f, i, vp, i, i, vp, vp, f, vp, vp, vp, f, vp, ll, vp, vp, vp, vp, vp, vp],
         "m3pc_rescore_listed": [vp, C.POINTER(PlanArgs), vp, vp, vp, vp, vp, i, vp, vp],
         "m3pc_select": [vp, vp, vp, ll, i, f, vp, vp, vp, vp, vp, vp, vp],
+        "m3pc_plan_step_certified": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, vp, C.POINTER(CertRecord), vp],
+        "m3pc_calibrate_delta": [vp, C.POINTER(PlanArgs), vp, vp, vp, vp, vp, f, C.POINTER(f), vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }
@@ -431,6 +448,49 @@ class Handle:
         if want_debug:
             res["pred_rewards"], res["pred_boot"] = pr, pb
         return res
+
+    def plan_step_certified(self, mode: int, states, actions, rewards, eps, expo, horizon: int, rtg: float, lmbda: float,
+                            discount: float, n_total: int, temperature: float, delta: float = 0.0, grow_delta: bool = False,
+                            kmin: int = 8, kmax: int = 128, rfirst: int = 2, rmax: int = 32, precision: int = PREC_BF16,
+                            slot: int = 0, returns=None, pruned: bool = False):
+        """One certified plan step in ONE library call (m3pc_plan_step_certified): policy pass, candidate pass in ``precision``,
+        lists, fp32 re-scores, certificates and select on the current stream.  Returns (res, record): ``res`` holds loc, std,
+        sample_actions, expect_return_low, expect_return (the merged vector), list (rmax + 1024 int32: race entries in front of
+        ``rmax``, score entries behind) and sel = (p, eval_action, argmax, sample_idx, sample_action); ``record`` is the
+        ``CertRecord`` of the step.  The host has read the step's last certificate when the call returns; the tensors are
+        complete in stream order."""
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        loc = torch.empty((self.T, self.A), **f32)
+        std = torch.empty((self.T, self.A), **f32)
+        acts = torch.empty((n_total, horizon, self.A), **f32)
+        low = torch.empty((n_total,), **f32)
+        merged = torch.empty((n_total,), **f32)
+        lst = torch.empty((int(rmax) + 1024,), dtype=torch.int32, device=dev)
+        sel = self.select_buffers(n_total)
+        args = self._args(mode, precision, horizon, n_total, 0, n_total, lmbda, discount, rtg, slot, returns)
+        args.flags = PLAN_PRUNED_POLICY if pruned else 0
+        cert = CertArgs(float(temperature), float(delta), int(bool(grow_delta)), int(kmin), int(kmax), int(rfirst), int(rmax))
+        rec = CertRecord()
+        ins = [self._f32(t) for t in (states, actions, rewards, eps)]
+        assert expo.numel() == n_total and expo.dtype == torch.float32 and expo.is_contiguous()
+        check(self.lib.m3pc_plan_step_certified(self._h, C.byref(args), C.byref(cert), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
+                                                _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low), _ptr(merged),
+                                                _ptr(lst), *[_ptr(t) for t in sel], C.byref(rec), _stream(dev)))
+        return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel), rec
+
+    def calibrate_delta(self, mode: int, states, actions, rewards, eps, scores_low: torch.Tensor, horizon: int, lmbda: float,
+                        discount: float, n_total: int, factor: float = 1.6, slot: int = 0) -> float:
+        """delta of the certified step from one full fp32 candidate pass over the candidates of the step that owns ``slot``
+        (m3pc_calibrate_delta): max(factor x the largest deviation of (scores_low - fp32) from its lower median, 1e-6 x the
+        largest |fp32 score|, 1e-30).  Blocks until the statistics are on the host."""
+        assert scores_low.numel() == n_total and scores_low.dtype == torch.float32 and scores_low.is_contiguous()
+        args = self._args(mode, PREC_FP32, horizon, n_total, 0, n_total, lmbda, discount, 0.0, slot)
+        ins = [self._f32(t) for t in (states, actions, rewards, eps)]
+        out = C.c_float()
+        check(self.lib.m3pc_calibrate_delta(self._h, C.byref(args), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]),
+                                            _ptr(scores_low), float(factor), C.byref(out), _stream(self.device)))
+        return float(out.value)
 
     def plan_step_batch(self, mode: int, states, actions, rewards, rtg, eps, horizon: int, lmbda: float, discount: float,
                         n_total: int, precision: int = PREC_FP32, slot: int = 0):

@@ -482,6 +482,9 @@ void launch_rescore_merge(const float* b, int n_total, const int* list, int r, i
 void launch_merge_select(const float* b, int n_total, const int* list, int r, int n, const float* list_scores, const float* f,
                          float delta, const float* expo, float tau, float* out, float* stats, float* host_stats, float seq,
                          const SelectP& sp, hipStream_t st);
+// calibration statistics over all n <= 16384 candidates (one workgroup): d = b - f, c = lower median of d (value, then index);
+// stats (8 floats) = {c, max |d - c|, max |f|, 0, -, 0, 0, 0}; host_stats / seq as launch_rescore_merge
+void launch_deviation_stats(const float* b, const float* f, int n, float* stats, float* host_stats, float seq, hipStream_t st);
 // dst[index[i]] = src[i]
 void launch_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, hipStream_t st);  // + index_copy[i] = index[i]
 

@@ -11,6 +11,9 @@
 // Candidate pass ("pass 2", learner.py:288-293) is exactly pruned: decoder rows of masked tokens do not
 // depend on the candidate, so only the 2h scored tokens are pushed through out-proj/FFN/heads and only the
 // un-masked tokens through the K/V projection.
+#include <atomic>
+#include <chrono>
+
 #include "m3pc_internal.h"
 
 namespace m3pc {
@@ -125,6 +128,14 @@ int m3pc_create(const m3pc_dims* dims, int device, m3pc_handle** out) {
     CHK(dmalloc(&h->sa_buf, (size_t)(D.max_candidates > h->chain[0].max_cand ? D.max_candidates : h->chain[0].max_cand) * T * h->A));
     CHK(dmalloc(&h->sa_chain[0], (size_t)h->chain[0].max_cand * T * h->A));
     CHK(dmalloc(&h->sa_chain[1], (size_t)h->chain[0].max_cand * T * h->A));
+    CHK(dmalloc(&h->cert_list, 64 + 1024));
+    CHK(dmalloc(&h->cert_b, 64 + 1024));
+    CHK(dmalloc(&h->cert_f, 64 + 1024));
+    CHK(dmalloc(&h->cert_stats, 16));
+    CHK(dmalloc(&h->cert_f32, (size_t)D.max_candidates));
+    HIPCHK(hipHostMalloc((void**)&h->cert_host, (size_t)M3PC_SLOTS * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(h->cert_host, 0, (size_t)M3PC_SLOTS * 8 * sizeof(float));
+    HIPCHK(hipHostGetDevicePointer((void**)&h->cert_host_dev, h->cert_host, 0));
     bind_ws(h.get(), &h->base);
     bind_slot(h.get(), 0);
     // ONE extra stream per device for all handles of the process: a process has four hardware queues, and with more
@@ -221,7 +232,9 @@ int m3pc_destroy(m3pc_handle* h) {
         hipFree(h->slot[s].sd);
         hipFree(h->slot[s].rtok);
     }
-    void* bufs[] = {h->sel_scratch, h->d_topk, h->er_top, h->sa_buf, h->sa_chain[0], h->sa_chain[1], h->c_om, h->c_os, h->goal_ws};
+    void* bufs[] = {h->sel_scratch, h->d_topk, h->er_top, h->sa_buf, h->sa_chain[0], h->sa_chain[1], h->c_om, h->c_os, h->goal_ws,
+                    h->cert_list, h->cert_b, h->cert_f, h->cert_stats, h->cert_f32};
+    if (h->cert_host) hipHostFree(h->cert_host);
     for (size_t i = 1; i < h->auxs.size(); ++i) {
         hipStreamDestroy(h->auxs[i]);
         hipEventDestroy(h->ev_joins[i]);
@@ -1244,6 +1257,243 @@ int m3pc_select(m3pc_handle* h, const float* expect_return, const float* a0, lon
     return check_launch("select");
 }
 
+// ---- the certified plan step as one call (learner.py:318-325 on low-precision scores that fp32 re-scores certify)
+// The statistics of the kernel that carried `seq`, read from the slot's host-mapped block: a BOUNDED spin on the sequence number
+// (10 s, the bound of the Python binding's HostStats.wait); on expiry one synchronisation of the stream and the device copy.
+static int cert_wait(m3pc_handle* h, int slot, float seq, int n_device, hipStream_t st, float out[8]) {
+    const volatile float* hs = h->cert_host + 8 * slot;
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (hs[4] != seq) {
+        if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
+            if (hipStreamSynchronize(st) != hipSuccess ||
+                hipMemcpy(out, h->cert_stats, 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(M3PC_EHIP, "the statistics of the certified step reached neither host-mapped memory within 10 s nor the host by a copy");
+            for (int i = n_device; i < 8; ++i) out[i] = 0.f;  // (a four-statistics merge leaves the device slots 4..7 alone)
+            return 0;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int i = 0; i < 8; ++i) out[i] = hs[i];
+    return 0;
+}
+static float cert_next_seq(m3pc_handle* h, int slot) {
+    h->cert_seq[slot] = h->cert_seq[slot] % 1000000 + 1;
+    return (float)h->cert_seq[slot];
+}
+// max(factor x the largest deviation from the median, 1e-6 x the scores' scale, 1e-30): the host arithmetic of
+// HipPlanner._calibrate (doubles of the device's floats), rounded once to the float the ABI carries
+static float cert_delta(float factor, float deviation, float f_max) {
+    double d = (double)factor * (double)deviation;
+    if (1e-6 * (double)f_max > d) d = 1e-6 * (double)f_max;
+    if (1e-30 > d) d = 1e-30;
+    return (float)d;
+}
+// one rank, every candidate: what both calls need of m3pc_plan_args before any HIP call
+static int cert_check_args(const m3pc_plan_args* a, const char* who) {
+    if (a->n_total < 1 || a->n_total > 16384) return fail(M3PC_EINVAL, "%s: n_total %d outside [1, 16384]", who, a->n_total);
+    if (a->n_begin != 0 || a->n_count != a->n_total)
+        return fail(M3PC_EINVAL, "%s plans on one rank: candidates [%d,+%d) are not all n_total=%d", who, a->n_begin, a->n_count, a->n_total);
+    if (!precision_ok(a->precision)) return fail(M3PC_EINVAL, "bad precision %d", a->precision);
+    if (a->slot < 0 || a->slot >= M3PC_SLOTS) return fail(M3PC_EINVAL, "slot %d outside [0, %d)", a->slot, M3PC_SLOTS);
+    return 0;
+}
+
+int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
+                             const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
+                             float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
+                             float* sample_action, m3pc_cert_record* rec, void* stream) {
+    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged || !rec)
+        return fail(M3PC_EINVAL, "null argument");
+    CHK(cert_check_args(a, "m3pc_plan_step_certified"));
+    const int N = a->n_total, hh = a->horizon;
+    const bool low = a->precision != M3PC_PREC_FP32;
+    const int kmin = c->kmin, kmax = c->kmax, R = c->rmax, rfirst = c->rfirst;
+    if (low) {
+        if (kmax < 1 || kmax > 1023 || kmin < 1 || kmin > kmax || kmin > N)
+            return fail(M3PC_EINVAL, "kmin %d / kmax %d outside 1 <= kmin <= min(kmax, n_total=%d), kmax <= 1023", kmin, kmax, N);
+        if (R < 0 || R > 64 || R > N) return fail(M3PC_EINVAL, "rmax %d outside [0, min(64, n_total=%d)]", R, N);
+        if (kmax + R > 1023) return fail(M3PC_EINVAL, "kmax %d + rmax %d > 1023 (the merge lists 1024 entries)", kmax, R);
+        if (R == 0 ? rfirst != 0 : (rfirst < 1 || rfirst > R)) return fail(M3PC_EINVAL, "rfirst %d outside [1, rmax=%d] (0 with rmax == 0)", rfirst, R);
+        if (!(c->delta >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
+    }
+    if (!(c->temperature == c->temperature)) return fail(M3PC_EINVAL, "temperature is not a number");
+    memset(rec, 0, sizeof(*rec));
+    hipStream_t st = (hipStream_t)stream;
+    const float temp = c->temperature;
+    const long long a0_stride = (long long)hh * h->A;
+
+    // learner.py:278-316: policy pass (fp32), candidates, candidate pass in args->precision
+    m3pc_plan_args pa = *a;
+    pa.flags = a->flags & M3PC_PLAN_PRUNED_POLICY;
+    pa.window = 0;
+    CHK(m3pc_policy_pass(h, &pa, states, actions, rewards, nullptr, nullptr, stream));
+    pa.flags = 0;
+    CHK(m3pc_candidate_pass(h, &pa, states, actions, rewards, eps, loc, std_, sample_actions, scores_low, nullptr, nullptr, stream));
+    if (!low) {  // fp32 scores for every candidate: the select alone
+        HIPCHK(hipMemcpyAsync(merged, scores_low, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, st));
+        CHK(m3pc_select(h, scores_low, sample_actions, a0_stride, N, temp, expo, p, eval_action, argmax, sample_idx, sample_action, stream));
+        rec->n_rescored = N;
+        rec->everything = rec->certified = 1;
+        return 0;
+    }
+
+    const int slot = a->slot;
+    int* L = list ? list : h->cert_list;  // race entries in front of R, score entries behind (m3pc_topk_race_window)
+    float *B = h->cert_b, *F = h->cert_f, *dstats = h->cert_stats;
+    float* hstats = h->cert_host_dev + 8 * slot;
+    const int n_device = R > 0 ? 8 : 4;
+    m3pc_plan_args ra = *a;  // the fp32 re-scores (m3pc_rescore) and the fp32 pass over every candidate
+    ra.precision = M3PC_PREC_FP32;
+    ra.flags = 0;
+    ra.window = 0;
+    double delta = (double)c->delta;  // (1.5 x a float deviation needs 25 bits: kept as the double the Python protocol keeps)
+    int rounds = 0;
+    float seq = 0.f;
+    auto rescore = [&](int lo, int hi) -> int {  // list positions [lo, hi)
+        ra.n_count = hi - lo;
+        return m3pc_rescore(h, &ra, states, actions, rewards, eps, L + lo, hi - lo, nullptr, F + lo, stream);
+    };
+    auto select = [&]() -> int {
+        return m3pc_select(h, merged, sample_actions, a0_stride, N, temp, expo, p, eval_action, argmax, sample_idx, sample_action, stream);
+    };
+    auto merge = [&](int n, int r, bool with_select) -> int {
+        seq = cert_next_seq(h, slot);
+        ++rounds;
+        const int o = R - r;
+        if (R > 0) {
+            if (with_select)
+                return m3pc_merge_race_select(h, scores_low, expo, temp, N, L + o, r, n, B + o, F + o, (float)delta, merged, dstats, hstats,
+                                              seq, sample_actions, a0_stride, p, eval_action, argmax, sample_idx, sample_action, stream);
+            return m3pc_rescore_merge_race(h, scores_low, expo, temp, N, L + o, r, n, B + o, F + o, (float)delta, merged, dstats, hstats, seq,
+                                           stream);
+        }
+        CHK(m3pc_rescore_merge(h, scores_low, N, L, n, B, F, (float)delta, merged, dstats, hstats, seq, stream));
+        return with_select ? select() : 0;
+    };
+    int n_done = kmin, r_done = rfirst;
+    // The lists are too short.  Window set: the `need` best candidates by low-precision score (descending, ties to the lower
+    // index) listed behind the race entries in place of the score entries, re-scored in chunks of the re-score workspace.
+    // Everything: one fp32 candidate pass in the candidate workspace (stream-ordered behind this step's own pass), the best
+    // entry merged with itself at delta = 0 -- the select then runs on fp32 scores alone.
+    auto window_set = [&](int need, bool everything) -> int {
+        const int cnt = need < N ? need : N;
+        if (cnt <= 1024 - 32 && !everything) {
+            if (!launch_topk_race(scores_low, nullptr, 0.f, N, cnt, 0, R, L, B, st))
+                launch_window_stats(scores_low, N, L + R, cnt, 1, cnt, 0.f, dstats + 8, nullptr, 0.f, B + R, st, 0);
+            CHK(check_launch("plan_step_certified (window set)"));
+            const int cap = h->chain[0].max_cand;
+            for (int c0 = 0; c0 < cnt; c0 += cap) CHK(rescore(R + c0, R + (cnt < c0 + cap ? cnt : c0 + cap)));
+            n_done = cnt;
+            CHK(merge(cnt, r_done, false));
+            return select();
+        }
+        ra.n_count = N;
+        CHK(m3pc_candidate_pass(h, &ra, states, actions, rewards, eps, nullptr, nullptr, h->sa_buf, h->cert_f32, nullptr, nullptr, stream));
+        if (!launch_topk_race(h->cert_f32, nullptr, 0.f, N, 1, 0, 0, h->d_topk, h->er_top, st))
+            launch_window_stats(h->cert_f32, N, h->d_topk, 1, 1, 1, 0.f, dstats + 8, nullptr, 0.f, h->er_top, st, 0);
+        CHK(check_launch("plan_step_certified (every candidate in fp32)"));
+        n_done = N;
+        seq = cert_next_seq(h, slot);
+        ++rounds;
+        CHK(m3pc_rescore_merge(h, h->cert_f32, N, h->d_topk, 1, h->er_top, h->er_top, 0.f, merged, dstats, hstats, seq, stream));
+        return select();
+    };
+
+    // first pass, enqueued before anything is read: lists, fp32 re-score of the kmin best by score and the rfirst best by race
+    // key, merge + certificates + select
+    if (R > 0) CHK(m3pc_topk_race_window(h, scores_low, expo, temp, N, kmax, kmin, R, L, nullptr, B, nullptr, 0.f, stream));
+    else CHK(m3pc_topk_window(h, scores_low, N, kmax, kmin, 0.f, L, dstats + 8, B, nullptr, 0.f, stream));
+    CHK(rescore(R - rfirst, R + kmin));
+    CHK(merge(kmin, rfirst, true));
+
+    // m3pc_amd/certificate.py:resolve -- read the certificates; raise delta when the re-scored set deviates by more than it
+    // allows; re-score what a certificate asks for; stop when both are satisfied or every candidate has been scored in fp32
+    bool saturated = false, everything = false;
+    int need = 0, need_race = 0;
+    float s8[8];
+    for (bool first = true;; first = false) {
+        CHK(cert_wait(h, slot, seq, everything || R == 0 ? 4 : n_device, st, s8));
+        need = (int)s8[2];
+        need_race = (int)s8[5];
+        if (first) {
+            rec->need_first = need;
+            rec->need_race_first = need_race;
+        }
+        bool redo = false;
+        if (c->grow_delta && 1.5 * (double)s8[1] > delta && !everything) {
+            delta = 1.5 * (double)s8[1];
+            redo = n_done < N;
+        }
+        if (everything || n_done >= N) break;
+        if (!redo) {
+            if (need > n_done && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
+                CHK(window_set(N, true));
+                everything = true;
+                continue;
+            }
+            if (need > n_done) {
+                if (need <= kmax) {
+                    CHK(rescore(R + n_done, R + need));
+                    n_done = need;
+                    redo = true;
+                } else {
+                    CHK(window_set(need, false));
+                    saturated = true;
+                    everything = n_done >= N;
+                    continue;
+                }
+            }
+            if (need_race > r_done) {
+                if (need_race <= R) {
+                    CHK(rescore(R - need_race, R - r_done));
+                    r_done = need_race;
+                    redo = true;
+                } else {  // more racers than the race list holds: every candidate in fp32
+                    CHK(window_set(N, true));
+                    saturated = everything = true;
+                    continue;
+                }
+            }
+        }
+        if (!redo) break;
+        CHK(merge(n_done, r_done, true));
+    }
+    rec->n_rescored = n_done;
+    rec->n_race = r_done;
+    rec->saturated = saturated;
+    rec->everything = everything;
+    rec->certified = everything || n_done >= N || (need <= n_done && need_race <= r_done);
+    rec->rounds = rounds;
+    rec->delta = (float)delta;
+    rec->shift = s8[0];
+    rec->deviation = s8[1];
+    rec->margin = s8[3];
+    return 0;
+}
+
+// HipPlanner._calibrate as a call: delta from ONE full fp32 candidate pass over the step's candidates
+int m3pc_calibrate_delta(m3pc_handle* h, const m3pc_plan_args* a, const float* states, const float* actions, const float* rewards,
+                         const float* eps, const float* scores_low, float factor, float* delta_out, void* stream) {
+    if (!h || !a || !states || !actions || !rewards || !eps || !scores_low || !delta_out) return fail(M3PC_EINVAL, "null argument");
+    CHK(cert_check_args(a, "m3pc_calibrate_delta"));
+    if (!(factor > 0.f)) return fail(M3PC_EINVAL, "factor must be > 0");
+    hipStream_t st = (hipStream_t)stream;
+    const int N = a->n_total;
+    m3pc_plan_args fa = *a;
+    fa.precision = M3PC_PREC_FP32;
+    fa.flags = 0;
+    fa.window = 0;
+    CHK(m3pc_candidate_pass(h, &fa, states, actions, rewards, eps, nullptr, nullptr, h->sa_buf, h->cert_f32, nullptr, nullptr, stream));
+    const float seq = cert_next_seq(h, a->slot);
+    launch_deviation_stats(scores_low, h->cert_f32, N, h->cert_stats, h->cert_host_dev + 8 * a->slot, seq, st);
+    CHK(check_launch("calibrate_delta"));
+    float s8[8];
+    CHK(cert_wait(h, a->slot, seq, 8, st, s8));
+    *delta_out = cert_delta(factor, s8[1], s8[2]);
+    return 0;
+}
+
 #ifdef M3PC_LAB  // ---- kernel-level test / bench hooks: libm3pc_hip_lab.so only, declared in include/m3pc_hip_debug.h
 // Lab build only (include/m3pc_hip_debug.h): lets tools/gemm_bench.py time the GEMM kernel on the plan step's shapes.
 int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias, const float* res, void* C, int M, int N,
@@ -1461,6 +1711,19 @@ int m3pc_debug_clock(long long* out2) {
 }
 
 // Not part of the public header (tests/test_gemm_kernels_gpu.py): the top-k kernels on their own.
+// the statistics kernel of m3pc_calibrate_delta on caller vectors (tests/test_certified_step_gpu.py): stats = {lower median of
+// scores_low - f32, largest deviation from it, largest |f32|, 0 ...} on the device, *delta_out as m3pc_calibrate_delta forms it
+int m3pc_debug_calibrate_stats(const float* scores_low, const float* f32, int n, float factor, float* stats, float* delta_out,
+                               void* stream) {
+    if (!scores_low || !f32 || !stats || !delta_out || n < 1 || n > 16384) return fail(M3PC_EINVAL, "bad argument");
+    launch_deviation_stats(scores_low, f32, n, stats, nullptr, 0.f, (hipStream_t)stream);
+    CHK(check_launch("debug_calibrate_stats"));
+    float s8[8];
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(s8, stats, sizeof(s8), hipMemcpyDeviceToHost));
+    *delta_out = cert_delta(factor, s8[1], s8[2]);
+    return 0;
+}
 int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream) {
     launch_topk(v, n, k, idx_out, (hipStream_t)stream);
     return check_launch("debug_topk");

@@ -142,6 +142,15 @@ struct m3pc_handle {
     float* sa_chain[2] = {nullptr, nullptr};  // the same for re-scores that run in the chain workspaces (one per slot parity)
     float* splitk_ws = nullptr;   // raw split-K slabs of the few-row fp32 GEMMs
     long long splitk_ws_bytes = 0;
+    // m3pc_plan_step_certified / m3pc_calibrate_delta: the step's lists (64 race entries at most in front of 1024 score entries:
+    // ids when the caller brings no list, low-precision scores, fp32 re-scores), the device copy of the statistics (8 floats of
+    // the merges + 4 of m3pc_topk_window), the fp32 scores of every candidate (max_candidates) and, per step slot, a pinned
+    // host-mapped 8-float statistics block the merge kernels write (payload, then the sequence number: cert_seq).
+    int* cert_list = nullptr;
+    float *cert_b = nullptr, *cert_f = nullptr, *cert_stats = nullptr, *cert_f32 = nullptr;
+    float* cert_host = nullptr;       // M3PC_SLOTS x 8 floats, host address
+    float* cert_host_dev = nullptr;   // the same block as the device sees it
+    int cert_seq[M3PC_SLOTS] = {};
     // Step slots: the per-step state a plan step leaves behind its policy pass (loc / sd of the policy head, the normalised
     // returns tokens).  A pipelined caller (m3pc_policy_pass of step t+1 on one stream beside m3pc_candidate_pass of step t on
     // another, the fp32 re-score of step t after it) gives every step in flight its own slot (m3pc_plan_args::slot);

@@ -572,6 +572,90 @@ void launch_merge_select(const float* b, int n_total, const int* list, int r, in
                        stats, host_stats, seq, expo ? 8 : 4, sp);
 }
 
+// Calibration statistics of the certified re-score (m3pc_calibrate_delta): d_i = b_i - f_i over ALL n <= 16384 candidates (b: the
+// low-precision scores, f: their fp32 values), c = the lower median of d -- the element of rank (n - 1) / 2 of the ascending
+// order (value, then index: what torch.median returns) --, then max_i |d_i - c| and max_i |f_i|.  One workgroup: every thread
+// keeps up to 16 elements in registers and ranks them by counting against all n, which pass through LDS in tiles of 2048
+// (broadcast reads, as in topk_rank_kernel; n^2 compares: ~0.3 ms at 16384, beside the ~10 ms fp32 pass that made f).
+//   stats (device, 8 floats) = {c, max |d - c|, max |f|, 0, -, 0, 0, 0}; host_stats: the same, payload first, then `seq` into slot 4
+//   with system scope (rescore_merge_body's protocol).
+__global__ __launch_bounds__(1024) void deviation_stats_kernel(const float* b, const float* f, int n, float* stats, float* host_stats,
+                                                               float seq) {
+    __shared__ float tile[2048];
+    __shared__ float c_sh;
+    __shared__ float sv[16], sf[16];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int ns = (n + 1023) >> 10;  // elements per thread (uniform)
+    float v[16];
+    int rank[16];
+    float fmx = 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int e = s * 1024 + tid;
+        rank[s] = 0;
+        v[s] = 0.f;
+        if (e < n) {
+            const float fe = f[e];
+            v[s] = __fsub_rn(b[e], fe);
+            fmx = fmaxf(fmx, fabsf(fe));
+        }
+    }
+    for (int base = 0; base < n; base += 2048) {
+        __syncthreads();
+        for (int j = tid; j < 2048; j += 1024) {
+            const int e = base + j;
+            tile[j] = e < n ? __fsub_rn(b[e], f[e]) : 0.f;
+        }
+        __syncthreads();
+        const int m = n - base < 2048 ? n - base : 2048;
+        for (int j = 0; j < m; ++j) {
+            const float o = tile[j];
+            const int je = base + j;
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if (s < ns) rank[s] += (o < v[s] || (o == v[s] && je < s * 1024 + tid)) ? 1 : 0;
+        }
+    }
+    const int mid = (n - 1) / 2;
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+        if (s * 1024 + tid < n && rank[s] == mid) c_sh = v[s];  // (ranks are a permutation: exactly one writer)
+    __syncthreads();
+    const float c = c_sh;
+    float dev = 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+        if (s * 1024 + tid < n) dev = fmaxf(dev, fabsf(__fsub_rn(v[s], c)));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        dev = fmaxf(dev, __shfl_xor(dev, o));
+        fmx = fmaxf(fmx, __shfl_xor(fmx, o));
+    }
+    if (lane == 0) {
+        sv[wid] = dev;
+        sf[wid] = fmx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) {
+            dev = fmaxf(dev, sv[w]);
+            fmx = fmaxf(fmx, sf[w]);
+        }
+        const float st8[8] = {c, dev, fmx, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < 8; ++i) stats[i] = st8[i];
+        if (host_stats) {
+            for (int i = 0; i < 8; ++i)
+                if (i != 4) host_stats[i] = st8[i];
+            __threadfence_system();
+            __hip_atomic_store(host_stats + 4, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+void launch_deviation_stats(const float* b, const float* f, int n, float* stats, float* host_stats, float seq, hipStream_t st) {
+    if (n <= 0 || n > 16384) return;
+    hipLaunchKernelGGL(deviation_stats_kernel, dim3(1), dim3(1024), 0, st, b, f, n, stats, host_stats, seq);
+}
+
 __global__ void scatter_kernel(const float* src, const int* index, int n, float* dst, int* index_copy) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {

@@ -137,7 +137,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                  max_windows: int = 1, pipeline_depth: int = 3, chain_priority: int = -1, tail_stream: bool = True,
                  defer_join: bool = True, goal_batch: int = 0, race_min: int = 2, calibration_windows: Optional[int] = None, certify_sample: bool = True,
                  chain_mode: str = "alternate", policy_head: str = "full", auto_fp32: bool = True,
-                 calibration_factor: float = 1.6, rescore_round: int = 4, fallback: str = "fp32"):
+                 calibration_factor: float = 1.6, rescore_round: int = 4, fallback: str = "fp32", native_step: bool = False):
         """cfg: any object with traj_length, action_samples, horizon, discount, temperature, lmbda,
         plan_guidance (finetune.py RunConfig fields read at learner.py:276,319,342).
         tokenizer_manager: a TokenizerManager (this package's) or {key: {"mean","std","min","max"}}.
@@ -171,6 +171,15 @@ class HipPlanner(GoalMixin, LockstepMixin):
         fallback: where a saturated bf16 certificate (auto_fp32) sends the planner: "fp32" (default) or "bf16x3" -- the split-bf16
           pass, whose deviation is ~400 x smaller, with a fresh calibration.  ``planner.fallback_precision`` names the precision
           fallen back to (None while there is none), ``planner.fp32_fallback`` is True while planning in fp32 because of it.
+        native_step (default False: everything as before): a SERIAL plan step on one rank (``_guide``: ``action_sample``,
+          ``rtg_guiding``, ``critic_lambda_guiding``, ``noise_adding_lambda``) runs as ONE library call, m3pc_plan_step_certified --
+          policy pass, candidate pass, lists, fp32 re-scores, certificates, window-set / every-candidate slow paths and select --
+          and the calibration passes run through m3pc_calibrate_delta: no torch.topk / argmax / median and no device-wide
+          synchronisation in the step.  The adaptive state stays here (``_adapt``, ``_hist``, ``_delta0``, ``delta_grown``,
+          ``auto_fp32``): the call takes delta, kmin and rfirst in and returns the step's record; ``planner.last`` carries the same
+          keys.  delta crosses the C ABI as a float (the Python protocol keeps doubles; the kernels see float(delta) either way), and
+          ``delta_grown`` counts the STEPS that raised delta (the Python protocol counts every raise).  ``plan_async``, batches,
+          lock-step groups, ``world > 1`` and rescore="topk" keep the Python protocol (certificate.py).
         pipeline_depth: how many plan steps ``action_sample_batch`` / ``rollout`` keep in flight (<= capi.SLOTS - 1).
         goal_batch: the largest number of zero-shot windows one ``action_piid_sample_batch`` / ``goal_actions`` call plans
         through the pruned many-window path (m3pc_goal_step_batch; BASELINE config 5: 8192 per GPU); 0 = that path is off."""
@@ -279,6 +288,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
         # pruned decoder has as many; kept as an option (tests/test_policy_pruned_gpu.py), not the default.
         assert policy_head in ("pruned", "full")
         self._policy_pruned = policy_head == "pruned"
+        self._native_step = bool(native_step)
         self._warned_saturated = False
         self.delta_grown = 0        # how often the per-step deviation check raised delta since the last weight load
         self.action_list = []       # zero-shot "piid_allout" (action_piid_list_sample)
@@ -481,6 +491,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
             self._maybe_fall_back_to_fp32()
         if not pipelined:
             self._drain()  # a serial step runs its fp32 chains on the current stream: nothing pipelined may still be using them
+        if (self._native_step and not pipelined and slot is None and self.world == 1 and not self._force_collective
+                and not self._bf16_offset and self.rescore in ("bound", "none")):
+            return self._issue_native(mode, states, actions, rewards, rtg, h, lmbda, eps, returns)
         sl = (slot if slot is not None else self._acquire_slot()).ready(self)
         tk = PlanTicket(self, sl, mode, states, actions, rewards, float(rtg), int(h), float(lmbda), returns)
         sl.owner = tk
@@ -550,6 +563,78 @@ class HipPlanner(GoalMixin, LockstepMixin):
         else:
             self._enqueue_tail(tk)
             self._mark_main()
+        return tk
+
+    def _issue_native(self, mode: int, states, actions, rewards, rtg: float, h: int, lmbda: float, eps=None, returns=None) -> "PlanTicket":
+        """A serial plan step as ONE library call (``native_step=True``): m3pc_plan_step_certified runs what ``_issue``,
+        ``_enqueue_tail`` and certificate.resolve drive from here; the ticket comes back resolved."""
+        cfg, hd = self.cfg, self.handle
+        N, A = int(cfg.action_samples), self.A
+        sl = self._acquire_slot().ready(self)
+        tk = PlanTicket(self, sl, mode, states, actions, rewards, float(rtg), int(h), float(lmbda), returns)
+        tk.index, self._step_index = self._step_index, self._step_index + 1
+        tk.grow_in, tk.kfirst_in, tk.rfirst_in = self._adapt(tk.index)
+        # the variates in the serial order of draws: eps, then the multinomial's exponentials
+        if eps is None:
+            eps = self._draw_eps(mode, h)
+        tk.eps = eps = eps.reshape(N, -1, A)
+        tk.expo = self._draw_expo()
+        disc, temp = float(cfg.discount), float(cfg.temperature)
+        bound = self.rescore == "bound"
+        R = self._R if bound else 0
+        kmin = kmax = rfirst = 1
+        delta = 0.0
+        if bound:
+            if self._delta_fixed is None and self._cal_left > 0:
+                # a calibration step: the candidate pass's scores first (the certified call below repeats the two passes -- same
+                # kernels, same bits), then one fp32 pass over every candidate inside m3pc_calibrate_delta
+                self._cal_left -= 1
+                hd.policy_pass(mode, states, actions, rewards, h, tk.rtg, slot=sl.i, returns=returns, pruned=self._policy_pruned)
+                low = hd.candidate_pass(mode, states, actions, rewards, eps, h, tk.lmbda, disc, N, precision=self.precision,
+                                        slot=sl.i)["expect_return"]
+                d = hd.calibrate_delta(mode, states, actions, rewards, eps, low, h, tk.lmbda, disc, N,
+                                       factor=self.calibration_factor, slot=sl.i)
+                self._delta0 = d if self._delta0 is None else max(self._delta0, d)
+            kmax = max(min(self.rescore_max, N - 1 if N > 1 else 1, 1024 - self._R - 1), 1)
+            kmin = max(min(tk.kfirst_in, N, kmax), 1)
+            rfirst = max(min(tk.rfirst_in, R), 1) if R > 0 else 0
+            delta = max(self._delta0, tk.grow_in)
+        res, rec = hd.plan_step_certified(mode, states, actions, rewards, eps, tk.expo, h, tk.rtg, tk.lmbda, disc, N, temp,
+                                          delta=delta, grow_delta=bound and self._delta_fixed is None, kmin=kmin, kmax=kmax,
+                                          rfirst=rfirst, rmax=R, precision=self.precision, slot=sl.i, returns=returns,
+                                          pruned=self._policy_pruned)
+        self._mark_main()
+        extra = {}
+        top = None
+        if bound:
+            lst = res["list"]
+            if rec.delta > float(np.float32(delta)):
+                self.delta_grown += 1
+            if rec.saturated and not self._warned_saturated:
+                self._warned_saturated = True
+                warnings.warn(f"m3pc_amd: the certificates asked for more candidates than the step lists (delta={rec.delta:.3g}, "
+                              f"rescore_max={self.rescore_max}); the whole window set or every candidate was re-scored in fp32 (slow path)")
+            # (every candidate has an fp32 score: the list no longer says which ones were re-scored)
+            top = torch.arange(N, dtype=torch.int32, device=self.device) if rec.everything else lst[R : R + rec.n_rescored]
+            extra = dict(n_rescored=int(rec.n_rescored), n_in_window=int(rec.need_first), min_margin_outside=float(rec.margin),
+                         delta=float(rec.delta), saturated=bool(rec.saturated), shift=float(rec.shift), deviation=float(rec.deviation),
+                         n_race=int(rec.n_race), need_race=int(rec.need_race_first), certified=bool(rec.certified),
+                         n_first=kmin, n_race_first=min(max(tk.rfirst_in, 1), R), race=lst[R - rec.n_race : R], rounds=int(rec.rounds))
+            tk.delta = extra["delta"]
+            self._hist[tk.index] = (float(rec.deviation), min(int(rec.need_first), kmax), min(int(rec.need_race_first), R),
+                                    int(rec.n_rescored) + int(rec.n_race))
+            for i in [i for i in self._hist if i < tk.index - 64]:
+                if self._delta_fixed is None:
+                    self._delta0 = max(self._delta0, 1.5 * self._hist[i][0])
+                del self._hist[i]
+        p, eval_action, argmax, sample_idx, sample_action = tk.sel = res["sel"]
+        self.last = dict(expect_return=res["expect_return"] if bound else res["expect_return_low"],
+                         expect_return_bf16=res["expect_return_low"] if bound else None, p=p, argmax=argmax, sample_idx=sample_idx,
+                         loc=res["loc"], std=res["std"], sample_actions=res["sample_actions"], eps=tk.eps, topk=top,
+                         eval_action=eval_action, sample_action=sample_action, horizon=tk.h, expo=tk.expo, **extra)
+        tk.tail_enqueued = True
+        tk.info = self.last
+        tk.out = (sample_action, eval_action)
         return tk
 
     def _maybe_fall_back_to_fp32(self):
@@ -944,7 +1029,7 @@ def _versions(module):
 
 
 def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None, generator: Optional[torch.Generator] = None,
-           **planner_kw):
+           native_step: bool = False, **planner_kw):
     """Rebind the plan path of a reference-style ``Learner`` onto the HIP library.
 
     precision: "bf16" (default since round 6: the configuration the headline is measured on) -- the bf16 candidate pass with the
@@ -959,6 +1044,7 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     (._data_mean, ._data_std, .normalize, .stats), learner.iql.qf (state_dict, obs_mean, obs_std).
     Afterwards learner.action_sample / rtg_guiding / critic_lambda_guiding / noise_adding_lambda /
     mtm_sampling (and the zero-shot calls) run on the GPU; everything else on the object is untouched.
+    native_step: serial plan steps as one library call each (``HipPlanner(native_step=True)``; default False).
     ``group`` + ``generator``: shard the candidates over the ranks of a process group (every rank attaches its own
     learner replica and passes a generator seeded identically); further keywords go to ``HipPlanner``.
     Weights are followed per tensor: before each call the version counters of ``mtm`` / ``iql.qf`` are compared with the
@@ -977,7 +1063,8 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
                          q_state_dict=None if qf is None else qf.state_dict(),
                          obs_mean=None if qf is None else qf.obs_mean, obs_std=None if qf is None else qf.obs_std,
                          n_embd=mc.n_embd, n_head=mc.n_head, n_enc_layer=mc.n_enc_layer, n_dec_layer=mc.n_dec_layer,
-                         precision=precision, rescore_topk=rescore_topk, group=group, generator=generator, **planner_kw)
+                         precision=precision, rescore_topk=rescore_topk, group=group, generator=generator, native_step=native_step,
+                         **planner_kw)
     state = {"mtm": _versions(mtm), "qf": None if qf is None else _versions(qf)}
 
     def _sync():
