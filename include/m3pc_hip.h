@@ -43,7 +43,8 @@ extern "C" {
 #endif
 
 /* ABI history.  Added within v7 (new symbols and structures only; nothing existing changed): m3pc_plan_step_certified,
- * m3pc_calibrate_delta, m3pc_cert_args, m3pc_cert_record.  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * m3pc_calibrate_delta, m3pc_cert_args, m3pc_cert_record; then m3pc_plan_step_certified_begin / _end, m3pc_set_step_streams and
+ * m3pc_draw_variates.  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -144,6 +145,13 @@ typedef struct m3pc_plan_args {
  * tables, the kept tokens alone through decoder-embed / K|V, out-proj / FFN / actor head on h rows instead of 4T).  Rows t < T - h of
  * the slot's loc / std (what m3pc_candidate_pass copies out) are zero.  Same arithmetic per computed row up to fp32 re-association. */
 #define M3PC_PLAN_PRUNED_POLICY 2
+/* M3PC_PLAN_INPUTS_READY (m3pc_plan_step_certified_begin only): the window -- states, actions, rewards, the returns row -- is
+ * complete already in the order of the slot's chain stream (written before the stream's earlier work was enqueued and since
+ * synchronised, or copied on that chain stream: m3pc_set_step_streams), so the policy pass does not wait for the caller's stream,
+ * that is for the candidate pass of the step before, and runs beside it.  eps and expo are read on the caller's stream and behind
+ * it: they need no more than stream order either way.  The caller then also orders the chain streams behind whatever other entry
+ * point used the handle last. */
+#define M3PC_PLAN_INPUTS_READY 4
 
 const char* m3pc_last_error(void);
 int m3pc_abi_version(void);
@@ -454,6 +462,49 @@ int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* args, const m
                              const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std,
                              float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
                              int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* record, void* stream);
+
+/* Pipelined certified steps: m3pc_plan_step_certified in two halves, so that a host keeps up to M3PC_SLOTS steps in flight (the
+ * rate of m3pc_amd/planner.py's plan_async, from the library alone).  _begin enqueues and returns: it reads nothing from the device
+ * and never waits on it.  _end resolves the step begun in `slot`.  For the same inputs the two calls produce exactly what
+ * m3pc_plan_step_certified produces -- every output buffer and every field of the record, bit for bit -- at any depth
+ * 1..M3PC_SLOTS, with the _ends in any order, in every regime of the certificate and for every precision.
+ *   Schedule (planner.py's default: alternate chain streams, tail stream, deferred join).  The policy pass of the step in slot s
+ *   goes to chain stream s & 1, behind `stream` as it stands at _begin (M3PC_PLAN_INPUTS_READY: without waiting for it).  The candidate pass goes to `stream` behind it, with
+ *   M3PC_PLAN_DEFER_JOIN; `stream` carries nothing else of the step, so consecutive steps' candidate passes run back to back.  The
+ *   step's tail -- m3pc_candidate_join, lists, first fp32 re-score, merge + certificates + select -- runs on the chain stream and is
+ *   enqueued behind the policy pass of the next _begin that uses that chain stream, or by _end if it is still pending then.
+ *   _end reads the certificates (the bounded wait of m3pc_plan_step_certified, the only host wait), enqueues on the chain stream
+ *   what they ask for, orders `stream` behind the step's last kernel and fills the record.  What a slow path runs in the
+ *   candidate workspace (a re-score of more than max_rescore candidates, the fp32 pass over every candidate) is ordered by events
+ *   behind every candidate pass enqueued so far, and later candidate passes behind it: no device-wide synchronisation.
+ *   Buffers.  The window, eps and expo must be complete in `stream` order at _begin; they and every output buffer must stay
+ *   untouched until _end of the slot has returned.  The outputs are complete in the order of _end's `stream`.
+ *   State.  _begin on a slot whose step has not been ended, _end on a slot with no begun step, and m3pc_plan_step_certified /
+ *   m3pc_calibrate_delta / m3pc_set_step_streams with any step begun return M3PC_ESTATE.  Bad arguments (the checks of
+ *   m3pc_plan_step_certified) return M3PC_EINVAL and leave the handle usable.  Every OTHER compute entry point of the handle is
+ *   called with no step begun, and on a stream that the next _begin's `stream` is ordered behind (what HipPlanner._drain /
+ *   _mark_main enforce in Python).  m3pc_destroy drains.
+ *   Adaptive state (delta going in, kmin, rfirst) stays the caller's, per _begin; the record of _end carries what it folds back.
+ * m3pc_set_step_streams (optional): the two chain streams (slot parity 0 / 1).  Not called, or NULLs: the handle creates two
+ * non-blocking streams of its own at the first _begin.  A process that already owns such a pair (m3pc_amd/planner.py) passes it,
+ * so that the process stays within the device's four hardware queues. */
+int m3pc_set_step_streams(m3pc_handle* h, void* chain0, void* chain1);
+int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_cert_args* cert, const float* states,
+                                   const float* actions, const float* rewards, const float* eps, const float* expo, float* loc,
+                                   float* std, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
+                                   float* eval_action, int* argmax, int* sample_idx, float* sample_action, void* stream);
+int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* record, void* stream);
+
+/* The variates of a plan step, for a host without a generator of its own: eps device out (n_count, row_elems) standard normals =
+ * rows [n_begin, n_begin + n_count) of the (n_total, row_elems) array of (seed, step); expo device out (n_count,) Exp(1) (never 0),
+ * the same rows of the (n_total,) array.  Either may be NULL.  row_elems = T * A (RTG / CRITIC) or h * A (NOISE).
+ * Counter-based: a value depends on (seed, step, element index) only -- not on n_begin / n_count, the launch geometry or earlier
+ * draws -- so a candidate-sharded rank draws its slice of the one-rank array.  Philox4x32-10, key = (seed lo, seed hi), counter =
+ * (block, step lo, step hi, array), array 0 = eps, 1 = expo; block b gives the flat elements 4b .. 4b+3.  Normals: words (w0, w1)
+ * and (w2, w3) through Box-Muller, u1 = ((wa >> 8) + 1) 2^-24, u2 = (wb >> 8) 2^-24, z = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2).
+ * Exponentials: -ln(((w >> 8) + 1) 2^-24), and 2^-25 where that is 0.  It is NOT torch's generator stream. */
+int m3pc_draw_variates(m3pc_handle* h, unsigned long long seed, unsigned long long step, int n_begin, int n_count, int row_elems,
+                       float* eps, float* expo, void* stream);
 
 /* delta of the certified step from ONE full fp32 candidate pass over the candidates of the step that owns args->slot (its
  * policy pass is reused; the pass runs in the candidate workspace): d = scores_low - fp32, c = the lower median of d (the

@@ -167,6 +167,8 @@ int m3pc_debug_attention(int dtype, const void* Q, long long q_bstride, int ldq,
 /* in-kernel phase stamps of workgroup 37 of every fused-tail launch as the step runs: cap > 0 starts a ring of cap entries
  * (64 int64 each), cap == 0 copies it to `out` (host), reports the number of launches logged and stops */
 int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged);
+/* how many streams the handle has created for m3pc_plan_step_certified_begin (0: the pair of m3pc_set_step_streams serves them) */
+int m3pc_debug_step_streams_created(m3pc_handle* h);
 /* XCD / CU of every workgroup of a launch on `stream`: out[2 i] = XCC_ID, out[2 i + 1] = HW_ID */
 int m3pc_debug_xcc_probe(int* out, int n_blocks, void* stream);
 

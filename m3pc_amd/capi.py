@@ -44,6 +44,7 @@ EXPORTS = (
     "m3pc_profile_enable",
     "m3pc_profile_read",
     "m3pc_plan_step_certified", "m3pc_calibrate_delta",
+    "m3pc_set_step_streams", "m3pc_plan_step_certified_begin", "m3pc_plan_step_certified_end", "m3pc_draw_variates",
 )
 
 
@@ -79,6 +80,7 @@ class CertRecord(C.Structure):
 
 PLAN_DEFER_JOIN = 1
 PLAN_PRUNED_POLICY = 2
+PLAN_INPUTS_READY = 4
 
 
 class M3pcError(RuntimeError):
@@ -133,6 +135,11 @@ def load_library(path: Optional[str] = None):
         "m3pc_plan_step_certified": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                      vp, vp, vp, C.POINTER(CertRecord), vp],
         "m3pc_calibrate_delta": [vp, C.POINTER(PlanArgs), vp, vp, vp, vp, vp, f, C.POINTER(f), vp],
+        "m3pc_set_step_streams": [vp, vp, vp],
+        "m3pc_plan_step_certified_begin": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp],
+        "m3pc_plan_step_certified_end": [vp, i, C.POINTER(CertRecord), vp],
+        "m3pc_draw_variates": [vp, C.c_ulonglong, C.c_ulonglong, i, i, i, vp, vp, vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }
@@ -478,6 +485,66 @@ class Handle:
                                                 _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low), _ptr(merged),
                                                 _ptr(lst), *[_ptr(t) for t in sel], C.byref(rec), _stream(dev)))
         return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel), rec
+
+    def set_step_streams(self, chain0: Optional["torch.cuda.Stream"], chain1: Optional["torch.cuda.Stream"]):
+        """The two chain streams of the pipelined certified steps (m3pc_set_step_streams); None, None: the handle's own."""
+        self._step_streams = (chain0, chain1)  # (kept alive as long as the handle uses them)
+        check(self.lib.m3pc_set_step_streams(self._h, C.c_void_p(chain0.cuda_stream) if chain0 is not None else None,
+                                             C.c_void_p(chain1.cuda_stream) if chain1 is not None else None))
+
+    def plan_step_certified_begin(self, mode: int, states, actions, rewards, eps, expo, horizon: int, rtg: float, lmbda: float,
+                                  discount: float, n_total: int, temperature: float, delta: float = 0.0, grow_delta: bool = False,
+                                  kmin: int = 8, kmax: int = 128, rfirst: int = 2, rmax: int = 32, precision: int = PREC_BF16,
+                                  slot: int = 0, returns=None, pruned: bool = False, inputs_ready: bool = False):
+        """The enqueueing half of ``plan_step_certified`` (m3pc_plan_step_certified_begin): arguments as there, on the current
+        stream; nothing is read from the device.  Returns the step's ``res`` dict -- the same tensors, complete only behind
+        ``plan_step_certified_end(slot)``; it also keeps the inputs alive.  states / actions / rewards / eps / expo must be fp32,
+        contiguous and left untouched until the step has been ended.  inputs_ready: the window (states, actions, rewards) is
+        complete already in the order of the slot's chain stream (M3PC_PLAN_INPUTS_READY): the policy pass does not wait for the
+        current stream."""
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        loc = torch.empty((self.T, self.A), **f32)
+        std = torch.empty((self.T, self.A), **f32)
+        acts = torch.empty((n_total, horizon, self.A), **f32)
+        low = torch.empty((n_total,), **f32)
+        merged = torch.empty((n_total,), **f32)
+        lst = torch.empty((int(rmax) + 1024,), dtype=torch.int32, device=dev)
+        sel = self.select_buffers(n_total)
+        args = self._args(mode, precision, horizon, n_total, 0, n_total, lmbda, discount, rtg, slot, returns)
+        args.flags = (PLAN_PRUNED_POLICY if pruned else 0) | (PLAN_INPUTS_READY if inputs_ready else 0)
+        cert = CertArgs(float(temperature), float(delta), int(bool(grow_delta)), int(kmin), int(kmax), int(rfirst), int(rmax))
+        ins = [self._f32(t) for t in (states, actions, rewards, eps)]
+        assert expo.numel() == n_total and expo.dtype == torch.float32 and expo.is_contiguous()
+        check(self.lib.m3pc_plan_step_certified_begin(self._h, C.byref(args), C.byref(cert), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
+                                                      _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low), _ptr(merged),
+                                                      _ptr(lst), *[_ptr(t) for t in sel], _stream(dev)))
+        return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel,
+                    keep=(ins, expo, returns))
+
+    def plan_step_certified_end(self, slot: int) -> "CertRecord":
+        """Resolve the step begun in ``slot`` (m3pc_plan_step_certified_end): its outputs are complete in the order of the current
+        stream when the call returns; -> the step's ``CertRecord``."""
+        rec = CertRecord()
+        check(self.lib.m3pc_plan_step_certified_end(self._h, int(slot), C.byref(rec), _stream(self.device)))
+        return rec
+
+    def draw_variates(self, seed: int, step: int, n_total: int, row_elems: int, n_begin: int = 0, n_count: Optional[int] = None,
+                      eps: Optional[torch.Tensor] = None, expo: Optional[torch.Tensor] = None, want_eps: bool = True,
+                      want_expo: bool = True):
+        """Rows [n_begin, n_begin + n_count) of the step's (n_total, row_elems) standard normals and (n_total,) Exp(1) variates
+        from the library's counter-based generator (m3pc_draw_variates), on the current stream.  ``eps`` / ``expo``: optional
+        contiguous fp32 device buffers of (at least) n_count * row_elems / n_count elements to draw into.  -> (eps, expo)."""
+        n_count = n_total - n_begin if n_count is None else n_count
+        if eps is None and want_eps:
+            eps = torch.empty((n_count, row_elems), dtype=torch.float32, device=self.device)
+        if expo is None and want_expo:
+            expo = torch.empty((n_count,), dtype=torch.float32, device=self.device)
+        for t, n in ((eps, n_count * row_elems), (expo, n_count)):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n)
+        check(self.lib.m3pc_draw_variates(self._h, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(n_begin), int(n_count),
+                                          int(row_elems), _ptr(eps), _ptr(expo), _stream(self.device)))
+        return eps, expo
 
     def calibrate_delta(self, mode: int, states, actions, rewards, eps, scores_low: torch.Tensor, horizon: int, lmbda: float,
                         discount: float, n_total: int, factor: float = 1.6, slot: int = 0) -> float:

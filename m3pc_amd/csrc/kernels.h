@@ -485,6 +485,9 @@ void launch_merge_select(const float* b, int n_total, const int* list, int r, in
 // calibration statistics over all n <= 16384 candidates (one workgroup): d = b - f, c = lower median of d (value, then index);
 // stats (8 floats) = {c, max |d - c|, max |f|, 0, -, 0, 0, 0}; host_stats / seq as launch_rescore_merge
 void launch_deviation_stats(const float* b, const float* f, int n, float* stats, float* host_stats, float seq, hipStream_t st);
+// counter-based variates (Philox4x32-10 of (seed, step, array, element / 4)): out[0 .. g1 - g0) = elements [g0, g1) of the flat array;
+// array 0 = standard normals (Box-Muller), 1 = Exp(1), never 0
+void launch_variates(unsigned long long seed, unsigned long long step, int array, long long g0, long long g1, float* out, hipStream_t st);
 // dst[index[i]] = src[i]
 void launch_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, hipStream_t st);  // + index_copy[i] = index[i]
 

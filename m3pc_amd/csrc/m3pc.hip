@@ -128,11 +128,14 @@ int m3pc_create(const m3pc_dims* dims, int device, m3pc_handle** out) {
     CHK(dmalloc(&h->sa_buf, (size_t)(D.max_candidates > h->chain[0].max_cand ? D.max_candidates : h->chain[0].max_cand) * T * h->A));
     CHK(dmalloc(&h->sa_chain[0], (size_t)h->chain[0].max_cand * T * h->A));
     CHK(dmalloc(&h->sa_chain[1], (size_t)h->chain[0].max_cand * T * h->A));
-    CHK(dmalloc(&h->cert_list, 64 + 1024));
-    CHK(dmalloc(&h->cert_b, 64 + 1024));
-    CHK(dmalloc(&h->cert_f, 64 + 1024));
-    CHK(dmalloc(&h->cert_stats, 16));
-    CHK(dmalloc(&h->cert_f32, (size_t)D.max_candidates));
+    for (int s = 0; s < M3PC_SLOTS; ++s) {
+        CHK(dmalloc(&h->cert_list[s], 64 + 1024));
+        CHK(dmalloc(&h->cert_b[s], 64 + 1024));
+        CHK(dmalloc(&h->cert_f[s], 64 + 1024));
+        CHK(dmalloc(&h->cert_stats[s], 32));
+        CHK(dmalloc(&h->cert_f32[s], (size_t)D.max_candidates));
+        CHK(dmalloc(&h->cert_top1[s], 4));
+    }
     HIPCHK(hipHostMalloc((void**)&h->cert_host, (size_t)M3PC_SLOTS * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
     memset(h->cert_host, 0, (size_t)M3PC_SLOTS * 8 * sizeof(float));
     HIPCHK(hipHostGetDevicePointer((void**)&h->cert_host_dev, h->cert_host, 0));
@@ -232,8 +235,18 @@ int m3pc_destroy(m3pc_handle* h) {
         hipFree(h->slot[s].sd);
         hipFree(h->slot[s].rtok);
     }
-    void* bufs[] = {h->sel_scratch, h->d_topk, h->er_top, h->sa_buf, h->sa_chain[0], h->sa_chain[1], h->c_om, h->c_os, h->goal_ws,
-                    h->cert_list, h->cert_b, h->cert_f, h->cert_stats, h->cert_f32};
+    void* bufs[] = {h->sel_scratch, h->d_topk, h->er_top, h->sa_buf, h->sa_chain[0], h->sa_chain[1], h->c_om, h->c_os, h->goal_ws};
+    for (int s = 0; s < M3PC_SLOTS; ++s) {
+        void* cb[] = {h->cert_list[s], h->cert_b[s], h->cert_f[s], h->cert_stats[s], h->cert_f32[s], h->cert_top1[s]};
+        for (void* b : cb)
+            if (b) hipFree(b);
+        for (int i = 0; i < 4; ++i)
+            if (h->step_ev[s][i]) hipEventDestroy(h->step_ev[s][i]);
+    }
+    if (h->ev_excl) hipEventDestroy(h->ev_excl);
+    if (h->step_chain_own)
+        for (int i = 0; i < 2; ++i)
+            if (h->step_chain[i]) hipStreamDestroy(h->step_chain[i]);
     if (h->cert_host) hipHostFree(h->cert_host);
     for (size_t i = 1; i < h->auxs.size(); ++i) {
         hipStreamDestroy(h->auxs[i]);
@@ -1267,7 +1280,7 @@ static int cert_wait(m3pc_handle* h, int slot, float seq, int n_device, hipStrea
     while (hs[4] != seq) {
         if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
             if (hipStreamSynchronize(st) != hipSuccess ||
-                hipMemcpy(out, h->cert_stats, 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                hipMemcpy(out, h->cert_stats[slot], 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(M3PC_EHIP, "the statistics of the certified step reached neither host-mapped memory within 10 s nor the host by a copy");
             for (int i = n_device; i < 8; ++i) out[i] = 0.f;  // (a four-statistics merge leaves the device slots 4..7 alone)
             return 0;
@@ -1298,18 +1311,11 @@ static int cert_check_args(const m3pc_plan_args* a, const char* who) {
     if (a->slot < 0 || a->slot >= M3PC_SLOTS) return fail(M3PC_EINVAL, "slot %d outside [0, %d)", a->slot, M3PC_SLOTS);
     return 0;
 }
-
-int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
-                             const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
-                             float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
-                             float* sample_action, m3pc_cert_record* rec, void* stream) {
-    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged || !rec)
-        return fail(M3PC_EINVAL, "null argument");
-    CHK(cert_check_args(a, "m3pc_plan_step_certified"));
-    const int N = a->n_total, hh = a->horizon;
-    const bool low = a->precision != M3PC_PREC_FP32;
-    const int kmin = c->kmin, kmax = c->kmax, R = c->rmax, rfirst = c->rfirst;
-    if (low) {
+// the checks of the certified step (serial call and _begin), before any HIP call
+static int cert_check_step(const m3pc_plan_args* a, const m3pc_cert_args* c, const char* who) {
+    CHK(cert_check_args(a, who));
+    const int N = a->n_total, kmin = c->kmin, kmax = c->kmax, R = c->rmax, rfirst = c->rfirst;
+    if (a->precision != M3PC_PREC_FP32) {
         if (kmax < 1 || kmax > 1023 || kmin < 1 || kmin > kmax || kmin > N)
             return fail(M3PC_EINVAL, "kmin %d / kmax %d outside 1 <= kmin <= min(kmax, n_total=%d), kmax <= 1023", kmin, kmax, N);
         if (R < 0 || R > 64 || R > N) return fail(M3PC_EINVAL, "rmax %d outside [0, min(64, n_total=%d)]", R, N);
@@ -1318,10 +1324,238 @@ int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc
         if (!(c->delta >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
     }
     if (!(c->temperature == c->temperature)) return fail(M3PC_EINVAL, "temperature is not a number");
+    return 0;
+}
+static bool cert_any_begun(const m3pc_handle* h) {
+    for (int s = 0; s < M3PC_SLOTS; ++s)
+        if (h->cstep[s].begun) return true;
+    return false;
+}
+
+// ---- the pieces of a certified step, on the step's tail stream (the caller's stream in the serial call)
+using CertStep = m3pc_handle::CertStep;
+static int* cert_L(m3pc_handle* h, const CertStep& S) { return S.list ? S.list : h->cert_list[S.a.slot]; }
+// A pipelined step's tail runs on a chain stream, beside the candidate passes of its neighbours on the callers' streams.  What
+// it runs in the chain workspace of its parity needs no order.  What overflows into the candidate workspace -- a re-score of more
+// than max_rescore candidates, the fp32 pass over every candidate (with sa_buf and the handle's top-1 scratch) -- is ordered by
+// events: behind every candidate pass enqueued so far (ev_cand of the slot begun last; m3pc_candidate_pass / m3pc_rescore order
+// the handle's own streams themselves: ws_sync) and behind the overflow before it, and every later _begin's candidate pass goes
+// behind ev_excl.
+static int cert_excl_enter(m3pc_handle* h, const CertStep& S) {
+    if (!S.async) return 0;
+    if (h->cand_last_slot >= 0) HIPCHK(hipStreamWaitEvent(S.tail, h->step_ev[h->cand_last_slot][2], 0));
+    if (h->excl_valid) HIPCHK(hipStreamWaitEvent(S.tail, h->ev_excl, 0));
+    return 0;
+}
+static int cert_excl_leave(m3pc_handle* h, const CertStep& S) {
+    if (!S.async) return 0;
+    HIPCHK(hipEventRecord(h->ev_excl, S.tail));
+    h->excl_valid = true;
+    return 0;
+}
+static int cert_rescore(m3pc_handle* h, CertStep& S, int lo, int hi) {  // list positions [lo, hi)
+    m3pc_plan_args ra = S.a;
+    ra.precision = M3PC_PREC_FP32;
+    ra.flags = 0;
+    ra.window = 0;
+    ra.n_count = hi - lo;
+    const bool excl = hi - lo > h->chain[0].max_cand;
+    if (excl) CHK(cert_excl_enter(h, S));
+    CHK(m3pc_rescore(h, &ra, S.states, S.actions, S.rewards, S.eps, cert_L(h, S) + lo, hi - lo, nullptr, h->cert_f[S.a.slot] + lo, S.tail));
+    if (excl) CHK(cert_excl_leave(h, S));
+    return 0;
+}
+static int cert_select(m3pc_handle* h, CertStep& S) {
+    return m3pc_select(h, S.merged, S.sample_actions, (long long)S.a.horizon * h->A, S.a.n_total, S.c.temperature, S.expo, S.p, S.eval_action,
+                       S.argmax, S.sample_idx, S.sample_action, S.tail);
+}
+static int cert_merge(m3pc_handle* h, CertStep& S, int n, int r, bool with_select) {
+    const int slot = S.a.slot, R = S.c.rmax, N = S.a.n_total, o = R - r;
+    int* L = cert_L(h, S);
+    float *B = h->cert_b[slot], *F = h->cert_f[slot], *dstats = h->cert_stats[slot], *hstats = h->cert_host_dev + 8 * slot;
+    const float temp = S.c.temperature;
+    S.seq = cert_next_seq(h, slot);
+    ++S.rounds;
+    if (R > 0) {
+        if (with_select)
+            return m3pc_merge_race_select(h, S.scores_low, S.expo, temp, N, L + o, r, n, B + o, F + o, (float)S.delta, S.merged, dstats, hstats,
+                                          S.seq, S.sample_actions, (long long)S.a.horizon * h->A, S.p, S.eval_action, S.argmax, S.sample_idx,
+                                          S.sample_action, S.tail);
+        return m3pc_rescore_merge_race(h, S.scores_low, S.expo, temp, N, L + o, r, n, B + o, F + o, (float)S.delta, S.merged, dstats, hstats,
+                                       S.seq, S.tail);
+    }
+    CHK(m3pc_rescore_merge(h, S.scores_low, N, L, n, B, F, (float)S.delta, S.merged, dstats, hstats, S.seq, S.tail));
+    return with_select ? cert_select(h, S) : 0;
+}
+// The lists are too short.  Window set: the `need` best candidates by low-precision score (descending, ties to the lower
+// index) listed behind the race entries in place of the score entries, re-scored in chunks of the re-score workspace.
+// Everything: one fp32 candidate pass in the candidate workspace (stream-ordered behind this step's own pass), the best
+// entry merged with itself at delta = 0 -- the select then runs on fp32 scores alone.
+static int cert_window_set(m3pc_handle* h, CertStep& S, int need, bool everything) {
+    const int slot = S.a.slot, R = S.c.rmax, N = S.a.n_total;
+    int* L = cert_L(h, S);
+    float *B = h->cert_b[slot], *dstats = h->cert_stats[slot], *hstats = h->cert_host_dev + 8 * slot;
+    hipStream_t st = S.tail;
+    const int cnt = need < N ? need : N;
+    if (cnt <= 1024 - 32 && !everything) {
+        if (!launch_topk_race(S.scores_low, nullptr, 0.f, N, cnt, 0, R, L, B, st))
+            launch_window_stats(S.scores_low, N, L + R, cnt, 1, cnt, 0.f, dstats + 8, nullptr, 0.f, B + R, st, 0);
+        CHK(check_launch("plan_step_certified (window set)"));
+        const int cap = h->chain[0].max_cand;
+        for (int c0 = 0; c0 < cnt; c0 += cap) CHK(cert_rescore(h, S, R + c0, R + (cnt < c0 + cap ? cnt : c0 + cap)));
+        S.n_done = cnt;
+        CHK(cert_merge(h, S, cnt, S.r_done, false));
+        return cert_select(h, S);
+    }
+    m3pc_plan_args ra = S.a;
+    ra.precision = M3PC_PREC_FP32;
+    ra.flags = 0;
+    ra.window = 0;
+    ra.n_count = N;
+    float* f32 = h->cert_f32[slot];
+    int* top1 = h->cert_top1[slot];
+    float* top1v = dstats + 16;
+    CHK(cert_excl_enter(h, S));
+    CHK(m3pc_candidate_pass(h, &ra, S.states, S.actions, S.rewards, S.eps, nullptr, nullptr, h->sa_buf, f32, nullptr, nullptr, st));
+    CHK(cert_excl_leave(h, S));
+    if (!launch_topk_race(f32, nullptr, 0.f, N, 1, 0, 0, top1, top1v, st))
+        launch_window_stats(f32, N, top1, 1, 1, 1, 0.f, dstats + 8, nullptr, 0.f, top1v, st, 0);
+    CHK(check_launch("plan_step_certified (every candidate in fp32)"));
+    S.n_done = N;
+    S.seq = cert_next_seq(h, slot);
+    ++S.rounds;
+    CHK(m3pc_rescore_merge(h, f32, N, top1, 1, top1v, top1v, 0.f, S.merged, dstats, hstats, S.seq, st));
+    return cert_select(h, S);
+}
+// first pass, enqueued before anything is read: lists, fp32 re-score of the kmin best by score and the rfirst best by race
+// key, merge + certificates + select.  fp32 scores for every candidate: the select alone.
+static int cert_first_pass(m3pc_handle* h, CertStep& S) {
+    const int slot = S.a.slot, N = S.a.n_total, R = S.c.rmax, kmin = S.c.kmin, kmax = S.c.kmax, rfirst = S.c.rfirst;
+    if (S.a.precision == M3PC_PREC_FP32) {
+        HIPCHK(hipMemcpyAsync(S.merged, S.scores_low, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, S.tail));
+        return m3pc_select(h, S.scores_low, S.sample_actions, (long long)S.a.horizon * h->A, N, S.c.temperature, S.expo, S.p, S.eval_action,
+                           S.argmax, S.sample_idx, S.sample_action, S.tail);
+    }
+    int* L = cert_L(h, S);
+    float *B = h->cert_b[slot], *dstats = h->cert_stats[slot];
+    S.delta = (double)S.c.delta;  // (1.5 x a float deviation needs 25 bits: kept as the double the Python protocol keeps)
+    S.rounds = 0;
+    S.n_done = kmin;
+    S.r_done = rfirst;
+    if (R > 0) CHK(m3pc_topk_race_window(h, S.scores_low, S.expo, S.c.temperature, N, kmax, kmin, R, L, nullptr, B, nullptr, 0.f, S.tail));
+    else CHK(m3pc_topk_window(h, S.scores_low, N, kmax, kmin, 0.f, L, dstats + 8, B, nullptr, 0.f, S.tail));
+    CHK(cert_rescore(h, S, R - rfirst, R + kmin));
+    return cert_merge(h, S, kmin, rfirst, true);
+}
+// m3pc_amd/certificate.py:resolve -- read the certificates; raise delta when the re-scored set deviates by more than it
+// allows; re-score what a certificate asks for; stop when both are satisfied or every candidate has been scored in fp32
+static int cert_resolve(m3pc_handle* h, CertStep& S, m3pc_cert_record* rec) {
+    const int slot = S.a.slot, N = S.a.n_total, R = S.c.rmax, kmax = S.c.kmax;
     memset(rec, 0, sizeof(*rec));
-    hipStream_t st = (hipStream_t)stream;
-    const float temp = c->temperature;
-    const long long a0_stride = (long long)hh * h->A;
+    if (S.a.precision == M3PC_PREC_FP32) {
+        rec->n_rescored = N;
+        rec->everything = rec->certified = 1;
+        return 0;
+    }
+    const int n_device = R > 0 ? 8 : 4;
+    bool saturated = false, everything = false;
+    int need = 0, need_race = 0;
+    float s8[8];
+    for (bool first = true;; first = false) {
+        CHK(cert_wait(h, slot, S.seq, everything || R == 0 ? 4 : n_device, S.tail, s8));
+        need = (int)s8[2];
+        need_race = (int)s8[5];
+        if (first) {
+            rec->need_first = need;
+            rec->need_race_first = need_race;
+        }
+        bool redo = false;
+        if (S.c.grow_delta && 1.5 * (double)s8[1] > S.delta && !everything) {
+            S.delta = 1.5 * (double)s8[1];
+            redo = S.n_done < N;
+        }
+        if (everything || S.n_done >= N) break;
+        if (!redo) {
+            if (need > S.n_done && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
+                CHK(cert_window_set(h, S, N, true));
+                everything = true;
+                continue;
+            }
+            if (need > S.n_done) {
+                if (need <= kmax) {
+                    CHK(cert_rescore(h, S, R + S.n_done, R + need));
+                    S.n_done = need;
+                    redo = true;
+                } else {
+                    CHK(cert_window_set(h, S, need, false));
+                    saturated = true;
+                    everything = S.n_done >= N;
+                    continue;
+                }
+            }
+            if (need_race > S.r_done) {
+                if (need_race <= R) {
+                    CHK(cert_rescore(h, S, R - need_race, R - S.r_done));
+                    S.r_done = need_race;
+                    redo = true;
+                } else {  // more racers than the race list holds: every candidate in fp32
+                    CHK(cert_window_set(h, S, N, true));
+                    saturated = everything = true;
+                    continue;
+                }
+            }
+        }
+        if (!redo) break;
+        CHK(cert_merge(h, S, S.n_done, S.r_done, true));
+    }
+    rec->n_rescored = S.n_done;
+    rec->n_race = S.r_done;
+    rec->saturated = saturated;
+    rec->everything = everything;
+    rec->certified = everything || S.n_done >= N || (need <= S.n_done && need_race <= S.r_done);
+    rec->rounds = S.rounds;
+    rec->delta = (float)S.delta;
+    rec->shift = s8[0];
+    rec->deviation = s8[1];
+    rec->margin = s8[3];
+    return 0;
+}
+static void cert_fill(CertStep& S, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
+                      const float* rewards, const float* eps, const float* expo, float* sample_actions, float* scores_low, float* merged,
+                      int* list, float* p, float* eval_action, int* argmax, int* sample_idx, float* sample_action, hipStream_t tail, bool async) {
+    S.a = *a;
+    S.c = *c;
+    S.states = states;
+    S.actions = actions;
+    S.rewards = rewards;
+    S.eps = eps;
+    S.expo = expo;
+    S.sample_actions = sample_actions;
+    S.scores_low = scores_low;
+    S.merged = merged;
+    S.list = list;
+    S.p = p;
+    S.eval_action = eval_action;
+    S.argmax = argmax;
+    S.sample_idx = sample_idx;
+    S.sample_action = sample_action;
+    S.tail = tail;
+    S.async = async;
+    S.tail_pending = false;
+}
+
+int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
+                             const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
+                             float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
+                             float* sample_action, m3pc_cert_record* rec, void* stream) {
+    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged || !rec)
+        return fail(M3PC_EINVAL, "null argument");
+    CHK(cert_check_step(a, c, "m3pc_plan_step_certified"));
+    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "m3pc_plan_step_certified with a pipelined step begun (m3pc_plan_step_certified_end first)");
+    memset(rec, 0, sizeof(*rec));
+    CertStep& S = h->cstep[a->slot];
+    cert_fill(S, a, c, states, actions, rewards, eps, expo, sample_actions, scores_low, merged, list, p, eval_action, argmax, sample_idx,
+              sample_action, (hipStream_t)stream, false);
 
     // learner.py:278-316: policy pass (fp32), candidates, candidate pass in args->precision
     m3pc_plan_args pa = *a;
@@ -1330,146 +1564,129 @@ int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc
     CHK(m3pc_policy_pass(h, &pa, states, actions, rewards, nullptr, nullptr, stream));
     pa.flags = 0;
     CHK(m3pc_candidate_pass(h, &pa, states, actions, rewards, eps, loc, std_, sample_actions, scores_low, nullptr, nullptr, stream));
-    if (!low) {  // fp32 scores for every candidate: the select alone
-        HIPCHK(hipMemcpyAsync(merged, scores_low, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, st));
-        CHK(m3pc_select(h, scores_low, sample_actions, a0_stride, N, temp, expo, p, eval_action, argmax, sample_idx, sample_action, stream));
-        rec->n_rescored = N;
-        rec->everything = rec->certified = 1;
-        return 0;
+    CHK(cert_first_pass(h, S));
+    return cert_resolve(h, S, rec);
+}
+
+// ---- the certified step in two halves: _begin enqueues, _end resolves (include/m3pc_hip.h: "Pipelined certified steps")
+int m3pc_set_step_streams(m3pc_handle* h, void* chain0, void* chain1) {
+    if (!h) return fail(M3PC_EINVAL, "null handle");
+    if ((chain0 == nullptr) != (chain1 == nullptr) || (chain0 && chain0 == chain1))
+        return fail(M3PC_EINVAL, "m3pc_set_step_streams takes two different streams, or two NULLs");
+    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "m3pc_set_step_streams with a step begun");
+    if (h->step_chain_own) {
+        HIPCHK(hipSetDevice(h->device));
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(hipStreamSynchronize(h->step_chain[i]));
+            HIPCHK(hipStreamDestroy(h->step_chain[i]));
+        }
     }
-
-    const int slot = a->slot;
-    int* L = list ? list : h->cert_list;  // race entries in front of R, score entries behind (m3pc_topk_race_window)
-    float *B = h->cert_b, *F = h->cert_f, *dstats = h->cert_stats;
-    float* hstats = h->cert_host_dev + 8 * slot;
-    const int n_device = R > 0 ? 8 : 4;
-    m3pc_plan_args ra = *a;  // the fp32 re-scores (m3pc_rescore) and the fp32 pass over every candidate
-    ra.precision = M3PC_PREC_FP32;
-    ra.flags = 0;
-    ra.window = 0;
-    double delta = (double)c->delta;  // (1.5 x a float deviation needs 25 bits: kept as the double the Python protocol keeps)
-    int rounds = 0;
-    float seq = 0.f;
-    auto rescore = [&](int lo, int hi) -> int {  // list positions [lo, hi)
-        ra.n_count = hi - lo;
-        return m3pc_rescore(h, &ra, states, actions, rewards, eps, L + lo, hi - lo, nullptr, F + lo, stream);
-    };
-    auto select = [&]() -> int {
-        return m3pc_select(h, merged, sample_actions, a0_stride, N, temp, expo, p, eval_action, argmax, sample_idx, sample_action, stream);
-    };
-    auto merge = [&](int n, int r, bool with_select) -> int {
-        seq = cert_next_seq(h, slot);
-        ++rounds;
-        const int o = R - r;
-        if (R > 0) {
-            if (with_select)
-                return m3pc_merge_race_select(h, scores_low, expo, temp, N, L + o, r, n, B + o, F + o, (float)delta, merged, dstats, hstats,
-                                              seq, sample_actions, a0_stride, p, eval_action, argmax, sample_idx, sample_action, stream);
-            return m3pc_rescore_merge_race(h, scores_low, expo, temp, N, L + o, r, n, B + o, F + o, (float)delta, merged, dstats, hstats, seq,
-                                           stream);
-        }
-        CHK(m3pc_rescore_merge(h, scores_low, N, L, n, B, F, (float)delta, merged, dstats, hstats, seq, stream));
-        return with_select ? select() : 0;
-    };
-    int n_done = kmin, r_done = rfirst;
-    // The lists are too short.  Window set: the `need` best candidates by low-precision score (descending, ties to the lower
-    // index) listed behind the race entries in place of the score entries, re-scored in chunks of the re-score workspace.
-    // Everything: one fp32 candidate pass in the candidate workspace (stream-ordered behind this step's own pass), the best
-    // entry merged with itself at delta = 0 -- the select then runs on fp32 scores alone.
-    auto window_set = [&](int need, bool everything) -> int {
-        const int cnt = need < N ? need : N;
-        if (cnt <= 1024 - 32 && !everything) {
-            if (!launch_topk_race(scores_low, nullptr, 0.f, N, cnt, 0, R, L, B, st))
-                launch_window_stats(scores_low, N, L + R, cnt, 1, cnt, 0.f, dstats + 8, nullptr, 0.f, B + R, st, 0);
-            CHK(check_launch("plan_step_certified (window set)"));
-            const int cap = h->chain[0].max_cand;
-            for (int c0 = 0; c0 < cnt; c0 += cap) CHK(rescore(R + c0, R + (cnt < c0 + cap ? cnt : c0 + cap)));
-            n_done = cnt;
-            CHK(merge(cnt, r_done, false));
-            return select();
-        }
-        ra.n_count = N;
-        CHK(m3pc_candidate_pass(h, &ra, states, actions, rewards, eps, nullptr, nullptr, h->sa_buf, h->cert_f32, nullptr, nullptr, stream));
-        if (!launch_topk_race(h->cert_f32, nullptr, 0.f, N, 1, 0, 0, h->d_topk, h->er_top, st))
-            launch_window_stats(h->cert_f32, N, h->d_topk, 1, 1, 1, 0.f, dstats + 8, nullptr, 0.f, h->er_top, st, 0);
-        CHK(check_launch("plan_step_certified (every candidate in fp32)"));
-        n_done = N;
-        seq = cert_next_seq(h, slot);
-        ++rounds;
-        CHK(m3pc_rescore_merge(h, h->cert_f32, N, h->d_topk, 1, h->er_top, h->er_top, 0.f, merged, dstats, hstats, seq, stream));
-        return select();
-    };
-
-    // first pass, enqueued before anything is read: lists, fp32 re-score of the kmin best by score and the rfirst best by race
-    // key, merge + certificates + select
-    if (R > 0) CHK(m3pc_topk_race_window(h, scores_low, expo, temp, N, kmax, kmin, R, L, nullptr, B, nullptr, 0.f, stream));
-    else CHK(m3pc_topk_window(h, scores_low, N, kmax, kmin, 0.f, L, dstats + 8, B, nullptr, 0.f, stream));
-    CHK(rescore(R - rfirst, R + kmin));
-    CHK(merge(kmin, rfirst, true));
-
-    // m3pc_amd/certificate.py:resolve -- read the certificates; raise delta when the re-scored set deviates by more than it
-    // allows; re-score what a certificate asks for; stop when both are satisfied or every candidate has been scored in fp32
-    bool saturated = false, everything = false;
-    int need = 0, need_race = 0;
-    float s8[8];
-    for (bool first = true;; first = false) {
-        CHK(cert_wait(h, slot, seq, everything || R == 0 ? 4 : n_device, st, s8));
-        need = (int)s8[2];
-        need_race = (int)s8[5];
-        if (first) {
-            rec->need_first = need;
-            rec->need_race_first = need_race;
-        }
-        bool redo = false;
-        if (c->grow_delta && 1.5 * (double)s8[1] > delta && !everything) {
-            delta = 1.5 * (double)s8[1];
-            redo = n_done < N;
-        }
-        if (everything || n_done >= N) break;
-        if (!redo) {
-            if (need > n_done && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
-                CHK(window_set(N, true));
-                everything = true;
-                continue;
-            }
-            if (need > n_done) {
-                if (need <= kmax) {
-                    CHK(rescore(R + n_done, R + need));
-                    n_done = need;
-                    redo = true;
-                } else {
-                    CHK(window_set(need, false));
-                    saturated = true;
-                    everything = n_done >= N;
-                    continue;
-                }
-            }
-            if (need_race > r_done) {
-                if (need_race <= R) {
-                    CHK(rescore(R - need_race, R - r_done));
-                    r_done = need_race;
-                    redo = true;
-                } else {  // more racers than the race list holds: every candidate in fp32
-                    CHK(window_set(N, true));
-                    saturated = everything = true;
-                    continue;
-                }
-            }
-        }
-        if (!redo) break;
-        CHK(merge(n_done, r_done, true));
-    }
-    rec->n_rescored = n_done;
-    rec->n_race = r_done;
-    rec->saturated = saturated;
-    rec->everything = everything;
-    rec->certified = everything || n_done >= N || (need <= n_done && need_race <= r_done);
-    rec->rounds = rounds;
-    rec->delta = (float)delta;
-    rec->shift = s8[0];
-    rec->deviation = s8[1];
-    rec->margin = s8[3];
+    h->step_chain_own = false;
+    h->step_chain[0] = (hipStream_t)chain0;
+    h->step_chain[1] = (hipStream_t)chain1;
     return 0;
+}
+static int step_setup(m3pc_handle* h) {
+    if (!h->step_chain[0]) {
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(hipStreamCreateWithFlags(&h->step_chain[i], hipStreamNonBlocking));
+            ++h->step_streams_created;
+        }
+        h->step_chain_own = true;
+    }
+    if (!h->ev_excl) {
+        for (int s = 0; s < M3PC_SLOTS; ++s)
+            for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreateWithFlags(&h->step_ev[s][i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&h->ev_excl, hipEventDisableTiming));
+    }
+    return 0;
+}
+// the tail of a begun step on its chain stream: behind its candidate pass (every part: m3pc_candidate_join), then the first pass
+static int step_enqueue_tail(m3pc_handle* h, int slot) {
+    CertStep& S = h->cstep[slot];
+    HIPCHK(hipStreamWaitEvent(S.tail, h->step_ev[slot][2], 0));
+    CHK(m3pc_candidate_join(h, slot, S.tail));
+    S.tail_pending = false;
+    CHK(cert_first_pass(h, S));
+    HIPCHK(hipEventRecord(h->step_ev[slot][3], S.tail));
+    return 0;
+}
+
+int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states,
+                                   const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std_,
+                                   float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
+                                   int* argmax, int* sample_idx, float* sample_action, void* stream) {
+    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged)
+        return fail(M3PC_EINVAL, "null argument");
+    CHK(cert_check_step(a, c, "m3pc_plan_step_certified_begin"));
+    const int slot = a->slot;
+    CertStep& S = h->cstep[slot];
+    if (S.begun) return fail(M3PC_ESTATE, "m3pc_plan_step_certified_begin: the step in slot %d has not been ended", slot);
+    HIPCHK(hipSetDevice(h->device));
+    CHK(step_setup(h));
+    hipStream_t st = (hipStream_t)stream, chain = h->step_chain[slot & 1];
+    hipEvent_t* ev = h->step_ev[slot];
+    // the window is complete in `stream` order: the chain stream reads it behind ev_in (M3PC_PLAN_INPUTS_READY: complete already)
+    if (!(a->flags & M3PC_PLAN_INPUTS_READY)) {
+        HIPCHK(hipEventRecord(ev[0], st));
+        HIPCHK(hipStreamWaitEvent(chain, ev[0], 0));
+    }
+    m3pc_plan_args pa = *a;
+    pa.flags = a->flags & M3PC_PLAN_PRUNED_POLICY;
+    pa.window = 0;
+    CHK(m3pc_policy_pass(h, &pa, states, actions, rewards, nullptr, nullptr, chain));
+    HIPCHK(hipEventRecord(ev[1], chain));
+    // the pending-tail rule: the tails of the earlier steps of this parity go behind this step's policy pass, oldest first
+    for (;;) {
+        int o = -1;
+        for (int s = 0; s < M3PC_SLOTS; ++s)
+            if ((s & 1) == (slot & 1) && h->cstep[s].begun && h->cstep[s].tail_pending && (o < 0 || h->cstep[s].order < h->cstep[o].order))
+                o = s;
+        if (o < 0) break;
+        CHK(step_enqueue_tail(h, o));
+    }
+    // the candidate pass on the caller's stream: behind the policy pass, behind what overflowed into the candidate workspace, and
+    // behind the candidate pass enqueued last (free when the caller plans on one stream)
+    HIPCHK(hipStreamWaitEvent(st, ev[1], 0));
+    if (h->excl_valid) HIPCHK(hipStreamWaitEvent(st, h->ev_excl, 0));
+    if (h->cand_last_slot >= 0) HIPCHK(hipStreamWaitEvent(st, h->step_ev[h->cand_last_slot][2], 0));
+    pa.flags = M3PC_PLAN_DEFER_JOIN;
+    CHK(m3pc_candidate_pass(h, &pa, states, actions, rewards, eps, loc, std_, sample_actions, scores_low, nullptr, nullptr, stream));
+    HIPCHK(hipEventRecord(ev[2], st));
+    h->cand_last_slot = slot;
+    cert_fill(S, a, c, states, actions, rewards, eps, expo, sample_actions, scores_low, merged, list, p, eval_action, argmax, sample_idx,
+              sample_action, chain, true);
+    S.tail_pending = true;
+    S.begun = true;
+    S.order = ++h->step_order;
+    return 0;
+}
+
+int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* rec, void* stream) {
+    if (!h || !rec) return fail(M3PC_EINVAL, "null argument");
+    if (slot < 0 || slot >= M3PC_SLOTS) return fail(M3PC_EINVAL, "slot %d outside [0, %d)", slot, M3PC_SLOTS);
+    CertStep& S = h->cstep[slot];
+    if (!S.begun) return fail(M3PC_ESTATE, "m3pc_plan_step_certified_end: no step begun in slot %d", slot);
+    HIPCHK(hipSetDevice(h->device));
+    S.begun = false;  // (whatever happens below, the slot is free again)
+    if (S.tail_pending) CHK(step_enqueue_tail(h, slot));
+    const int rounds = S.rounds;
+    CHK(cert_resolve(h, S, rec));
+    if (S.rounds != rounds) HIPCHK(hipEventRecord(h->step_ev[slot][3], S.tail));
+    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->step_ev[slot][3], 0));
+    return 0;
+}
+
+int m3pc_draw_variates(m3pc_handle* h, unsigned long long seed, unsigned long long step, int n_begin, int n_count, int row_elems,
+                       float* eps, float* expo, void* stream) {
+    if (!h) return fail(M3PC_EINVAL, "null handle");
+    if (n_begin < 0 || n_count < 1 || row_elems < 1 || (long long)n_begin + n_count > (1LL << 31) - 1 ||
+        ((long long)n_begin + n_count) * row_elems > (1LL << 33))
+        return fail(M3PC_EINVAL, "m3pc_draw_variates: rows [%d,+%d) of %d elements outside the generator's range", n_begin, n_count, row_elems);
+    HIPCHK(hipSetDevice(h->device));
+    launch_variates(seed, step, 0, (long long)n_begin * row_elems, ((long long)n_begin + n_count) * row_elems, eps, (hipStream_t)stream);
+    launch_variates(seed, step, 1, n_begin, (long long)n_begin + n_count, expo, (hipStream_t)stream);
+    return check_launch("draw_variates");
 }
 
 // HipPlanner._calibrate as a call: delta from ONE full fp32 candidate pass over the step's candidates
@@ -1478,15 +1695,17 @@ int m3pc_calibrate_delta(m3pc_handle* h, const m3pc_plan_args* a, const float* s
     if (!h || !a || !states || !actions || !rewards || !eps || !scores_low || !delta_out) return fail(M3PC_EINVAL, "null argument");
     CHK(cert_check_args(a, "m3pc_calibrate_delta"));
     if (!(factor > 0.f)) return fail(M3PC_EINVAL, "factor must be > 0");
+    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "m3pc_calibrate_delta with a pipelined step begun (m3pc_plan_step_certified_end first)");
     hipStream_t st = (hipStream_t)stream;
     const int N = a->n_total;
     m3pc_plan_args fa = *a;
     fa.precision = M3PC_PREC_FP32;
     fa.flags = 0;
     fa.window = 0;
-    CHK(m3pc_candidate_pass(h, &fa, states, actions, rewards, eps, nullptr, nullptr, h->sa_buf, h->cert_f32, nullptr, nullptr, stream));
+    float* f32 = h->cert_f32[a->slot];
+    CHK(m3pc_candidate_pass(h, &fa, states, actions, rewards, eps, nullptr, nullptr, h->sa_buf, f32, nullptr, nullptr, stream));
     const float seq = cert_next_seq(h, a->slot);
-    launch_deviation_stats(scores_low, h->cert_f32, N, h->cert_stats, h->cert_host_dev + 8 * a->slot, seq, st);
+    launch_deviation_stats(scores_low, f32, N, h->cert_stats[a->slot], h->cert_host_dev + 8 * a->slot, seq, st);
     CHK(check_launch("calibrate_delta"));
     float s8[8];
     CHK(cert_wait(h, a->slot, seq, 8, st, s8));
@@ -1495,6 +1714,8 @@ int m3pc_calibrate_delta(m3pc_handle* h, const m3pc_plan_args* a, const float* s
 }
 
 #ifdef M3PC_LAB  // ---- kernel-level test / bench hooks: libm3pc_hip_lab.so only, declared in include/m3pc_hip_debug.h
+// streams the handle created for its pipelined certified steps (0 while the caller's pair of m3pc_set_step_streams serves them)
+int m3pc_debug_step_streams_created(m3pc_handle* h) { return h ? h->step_streams_created : -1; }
 // Lab build only (include/m3pc_hip_debug.h): lets tools/gemm_bench.py time the GEMM kernel on the plan step's shapes.
 int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias, const float* res, void* C, int M, int N,
                     int K, int gelu, int f32out, int variant, void* stream) {

@@ -146,11 +146,43 @@ struct m3pc_handle {
     // ids when the caller brings no list, low-precision scores, fp32 re-scores), the device copy of the statistics (8 floats of
     // the merges + 4 of m3pc_topk_window), the fp32 scores of every candidate (max_candidates) and, per step slot, a pinned
     // host-mapped 8-float statistics block the merge kernels write (payload, then the sequence number: cert_seq).
-    int* cert_list = nullptr;
-    float *cert_b = nullptr, *cert_f = nullptr, *cert_stats = nullptr, *cert_f32 = nullptr;
+    // All of them per step slot: the steps of m3pc_plan_step_certified_begin / _end in flight each keep their own.
+    int* cert_list[M3PC_SLOTS] = {};
+    float *cert_b[M3PC_SLOTS] = {}, *cert_f[M3PC_SLOTS] = {}, *cert_stats[M3PC_SLOTS] = {}, *cert_f32[M3PC_SLOTS] = {};
+    int* cert_top1[M3PC_SLOTS] = {};     // the best fp32 candidate of the every-candidate pass and (cert_stats + 16) its score
     float* cert_host = nullptr;       // M3PC_SLOTS x 8 floats, host address
     float* cert_host_dev = nullptr;   // the same block as the device sees it
     int cert_seq[M3PC_SLOTS] = {};
+    // One certified step: its arguments and how far its re-score has come.  The serial call fills and resolves one within the
+    // call (tail == the caller's stream); _begin leaves it for _end (tail == the chain stream of the slot's parity).
+    struct CertStep {
+        bool begun = false;         // between _begin and _end
+        bool tail_pending = false;  // lists + first re-score + merge + select not enqueued yet (the pending-tail rule)
+        bool async = false;
+        unsigned long long order = 0;  // _begin count: pending tails go out oldest first
+        m3pc_plan_args a;
+        m3pc_cert_args c;
+        const float *states = nullptr, *actions = nullptr, *rewards = nullptr, *eps = nullptr, *expo = nullptr;
+        float *sample_actions = nullptr, *scores_low = nullptr, *merged = nullptr, *p = nullptr, *eval_action = nullptr,
+              *sample_action = nullptr;
+        int *list = nullptr, *argmax = nullptr, *sample_idx = nullptr;
+        hipStream_t tail = nullptr;
+        double delta = 0.0;
+        int rounds = 0, n_done = 0, r_done = 0;
+        float seq = 0.f;
+    } cstep[M3PC_SLOTS];
+    // Pipelined certified steps: the two chain streams (slot parity; the caller's pair of m3pc_set_step_streams or the handle's
+    // own, created at the first _begin), the events of a slot, and the order of the candidate workspace across steps:
+    // ev_cand_last behind the candidate pass enqueued last, ev_excl behind the last few-row-workspace overflow (a re-score of
+    // more than max_rescore candidates, the every-candidate fp32 pass) that ran in the candidate workspace on a chain stream.
+    hipStream_t step_chain[2] = {nullptr, nullptr};
+    bool step_chain_own = false;
+    int step_streams_created = 0;  // (lab: m3pc_debug_step_streams_created)
+    hipEvent_t step_ev[M3PC_SLOTS][4] = {};  // ev_in, ev_pol, ev_cand, ev_done
+    hipEvent_t ev_excl = nullptr;
+    bool excl_valid = false;
+    int cand_last_slot = -1;
+    unsigned long long step_order = 0;
     // Step slots: the per-step state a plan step leaves behind its policy pass (loc / sd of the policy head, the normalised
     // returns tokens).  A pipelined caller (m3pc_policy_pass of step t+1 on one stream beside m3pc_candidate_pass of step t on
     // another, the fp32 re-score of step t after it) gives every step in flight its own slot (m3pc_plan_args::slot);

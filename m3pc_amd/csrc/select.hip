@@ -668,4 +668,73 @@ void launch_scatter(const float* src, const int* index, int n, float* dst, int* 
     hipLaunchKernelGGL(scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, index, n, dst, index_copy);
 }
 
+// ---- the variates of a plan step from a counter-based generator (m3pc_draw_variates): a value depends on (seed, step, element
+// index) alone -- not on the launch geometry, the slice asked for or earlier draws -- so a candidate-sharded rank draws its rows
+// of the one-rank array.  Philox4x32-10 (Salmon et al., SC'11): key = (seed lo, seed hi), counter = (block, step lo, step hi,
+// array) with array 0 = eps, 1 = expo; block b gives the flat elements 4b .. 4b+3 of its array.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0;
+    w[1] = c1;
+    w[2] = c2;
+    w[3] = c3;
+}
+// Box-Muller on two words: u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], u2 = (wb >> 8) 2^-24; z = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2).
+// 2 u2 is exact in fp32, so the angle goes through sincospif unrounded; logf / sqrtf / sincospif are the precise library versions.
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, float& z1) {
+    const float u1 = (float)((wa >> 8) + 1u) * 0x1p-24f;
+    const float t2 = (float)(wb >> 8) * 0x1p-23f;
+    const float r = sqrtf(-2.f * logf(u1));
+    float s, c;
+    sincospif(t2, &s, &c);
+    z0 = r * c;
+    z1 = r * s;
+}
+// array 0: standard normals; array 1: Exp(1), -ln u with u in (0, 1], and 2^-25 where that is 0 (the select divides by it and the
+// race key takes its log).  One thread per Philox block.  g0 / g1: the slice [g0, g1) of the flat array that goes to out[0 .. g1 - g0);
+// a block wholly inside the slice is one 16-byte store when g0 and `out` allow it, everything else goes element by element.
+__global__ __launch_bounds__(256) void variates_kernel(uint32_t k0, uint32_t k1, uint32_t s0, uint32_t s1, uint32_t array, long long g0,
+                                                       long long g1, float* __restrict__ out, int vec_ok) {
+    const long long b = g0 / 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (4 * b >= g1) return;
+    uint32_t w[4];
+    philox4x32_10((uint32_t)b, s0, s1, array, k0, k1, w);
+    float v[4];
+    if (array == 0) {
+        box_muller(w[0], w[1], v[0], v[1]);
+        box_muller(w[2], w[3], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float q = -logf((float)((w[i] >> 8) + 1u) * 0x1p-24f);
+            v[i] = q > 0.f ? q : 0x1p-25f;
+        }
+    }
+    const long long e = 4 * b;
+    if (vec_ok && e >= g0 && e + 4 <= g1) {
+        *reinterpret_cast<float4*>(out + (e - g0)) = make_float4(v[0], v[1], v[2], v[3]);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (e + i >= g0 && e + i < g1) out[e + i - g0] = v[i];
+}
+void launch_variates(unsigned long long seed, unsigned long long step, int array, long long g0, long long g1, float* out, hipStream_t st) {
+    if (g1 <= g0 || !out) return;
+    const long long blocks = (g1 + 3) / 4 - g0 / 4;
+    const int vec_ok = g0 % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    hipLaunchKernelGGL(variates_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)array, g0, g1, out, vec_ok);
+}
+
 }  // namespace m3pc

@@ -105,6 +105,7 @@ class PlanTicket:
         self.eps = self.expo = self.res = self.er_b = self.er = self.a0 = self.sel = self.top = None
         self.tail_enqueued = False
         self.deferred = False
+        self.native = False  # issued through m3pc_plan_step_certified_begin: resolved by m3pc_plan_step_certified_end
         self.kmin = self.kmax = self.n_done = self.r_done = self.index = 0
         self.grow_in, self.kfirst_in, self.rfirst_in = 0.0, 0, 0
         self.lst, self.R, self.wset = None, 0, None
@@ -137,7 +138,8 @@ class HipPlanner(GoalMixin, LockstepMixin):
                  max_windows: int = 1, pipeline_depth: int = 3, chain_priority: int = -1, tail_stream: bool = True,
                  defer_join: bool = True, goal_batch: int = 0, race_min: int = 2, calibration_windows: Optional[int] = None, certify_sample: bool = True,
                  chain_mode: str = "alternate", policy_head: str = "full", auto_fp32: bool = True,
-                 calibration_factor: float = 1.6, rescore_round: int = 4, fallback: str = "fp32", native_step: bool = False):
+                 calibration_factor: float = 1.6, rescore_round: int = 4, fallback: str = "fp32", native_step: bool = False,
+                 variates: str = "torch", seed: int = 0):
         """cfg: any object with traj_length, action_samples, horizon, discount, temperature, lmbda,
         plan_guidance (finetune.py RunConfig fields read at learner.py:276,319,342).
         tokenizer_manager: a TokenizerManager (this package's) or {key: {"mean","std","min","max"}}.
@@ -178,8 +180,14 @@ class HipPlanner(GoalMixin, LockstepMixin):
           synchronisation in the step.  The adaptive state stays here (``_adapt``, ``_hist``, ``_delta0``, ``delta_grown``,
           ``auto_fp32``): the call takes delta, kmin and rfirst in and returns the step's record; ``planner.last`` carries the same
           keys.  delta crosses the C ABI as a float (the Python protocol keeps doubles; the kernels see float(delta) either way), and
-          ``delta_grown`` counts the STEPS that raised delta (the Python protocol counts every raise).  ``plan_async``, batches,
-          lock-step groups, ``world > 1`` and rescore="topk" keep the Python protocol (certificate.py).
+          ``delta_grown`` counts the STEPS that raised delta (the Python protocol counts every raise).  One-rank ``plan_async``
+          steps (under the default schedule: chain_mode="alternate", tail_stream, defer_join) go through
+          m3pc_plan_step_certified_begin / _end: the library runs the pipelined schedule of ``_issue`` / ``_enqueue_tail`` on this
+          planner's chain-stream pair (m3pc_set_step_streams), the ticket's result resolves the step; calibration steps run
+          serially.  Lock-step groups, ``world > 1`` and rescore="topk" keep the Python protocol (certificate.py).
+        variates: "torch" (default) draws a plan step's normals and exponentials from ``generator``; "library" draws them with
+          m3pc_draw_variates -- the library's counter-based generator on (``seed``, the planner's step index), what a host
+          without torch gets -- on the same stream.  Not torch's stream of numbers: goldens recorded on one do not hold on the other.
         pipeline_depth: how many plan steps ``action_sample_batch`` / ``rollout`` keep in flight (<= capi.SLOTS - 1).
         goal_batch: the largest number of zero-shot windows one ``action_piid_sample_batch`` / ``goal_actions`` call plans
         through the pruned many-window path (m3pc_goal_step_batch; BASELINE config 5: 8192 per GPU); 0 = that path is off."""
@@ -203,6 +211,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
         prec = capi.precision_code(precision)
         if fallback not in ("fp32", "bf16x3"):
             raise ValueError(f"fallback must be 'fp32' or 'bf16x3', got {fallback!r}")
+        if variates not in ("torch", "library"):
+            raise ValueError(f"variates must be 'torch' or 'library', got {variates!r}")
+        self._variates, self._seed = variates, int(seed)
         max_rescore = max((int(rescore_max) + self._R) * nw, int(rescore_topk), 1) if prec in capi.LOW_PRECISION else 1
         self._max_batch = max(int(max_batch), nw, 1)
         self.handle = capi.Handle(S, A, T, n_embd, n_head, n_enc_layer, n_dec_layer,
@@ -289,6 +300,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
         assert policy_head in ("pruned", "full")
         self._policy_pruned = policy_head == "pruned"
         self._native_step = bool(native_step)
+        self._step_streams_set = False  # the chain-stream pair has been handed to the library (m3pc_set_step_streams)
         self._warned_saturated = False
         self.delta_grown = 0        # how often the per-step deviation check raised delta since the last weight load
         self.action_list = []       # zero-shot "piid_allout" (action_piid_list_sample)
@@ -426,6 +438,27 @@ class HipPlanner(GoalMixin, LockstepMixin):
         """The multinomial's exponentials (ATen's own algorithm: argmax(p / q), q ~ Exp(1))."""
         return torch.empty((int(self.cfg.action_samples),), dtype=torch.float32, device=self.device).exponential_(1, generator=self.generator)
 
+    def _step_eps(self, step: int, mode, h, buf=None):
+        """The candidate variates of plan step ``step``: torch's generator (``_draw_eps``), or with variates="library" the rows of
+        (seed, step) from the library's counter-based generator (m3pc_draw_variates), on the current stream either way."""
+        if self._variates != "library":
+            return self._draw_eps(mode, h, buf)
+        N, T, A = int(self.cfg.action_samples), self.T, self.A
+        shape = (N, h, A) if mode == capi.MODE_NOISE else (N, 1, T, 1, A)
+        n = int(np.prod(shape))
+        out = buf[:n] if buf is not None else torch.empty((n,), dtype=torch.float32, device=self.device)
+        self.handle.draw_variates(self._seed, step, N, n // N, eps=out, want_expo=False)
+        return out.view(shape)
+
+    def _step_expo(self, step: int, buf=None):
+        """The multinomial's exponentials of plan step ``step`` (see ``_step_eps``)."""
+        if self._variates != "library":
+            return self._draw_expo() if buf is None else buf.exponential_(1, generator=self.generator)
+        N = int(self.cfg.action_samples)
+        out = buf if buf is not None else torch.empty((N,), dtype=torch.float32, device=self.device)
+        self.handle.draw_variates(self._seed, step, N, 1, expo=out, want_eps=False)
+        return out
+
     def _chain_streams(self):
         """(stream 0, stream 1) of this device and priority, shared by every planner of the process."""
         if self._chain is None:
@@ -494,6 +527,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
         if (self._native_step and not pipelined and slot is None and self.world == 1 and not self._force_collective
                 and not self._bf16_offset and self.rescore in ("bound", "none")):
             return self._issue_native(mode, states, actions, rewards, rtg, h, lmbda, eps, returns)
+        if (self._native_step and pipelined and self.world == 1 and not self._force_collective and not self._bf16_offset
+                and self.rescore in ("bound", "none") and self._alternate and self._tail_stream and self._defer_join):
+            return self._issue_native_async(mode, states, actions, rewards, rtg, h, lmbda, eps, returns, slot, inputs_ready)
         sl = (slot if slot is not None else self._acquire_slot()).ready(self)
         tk = PlanTicket(self, sl, mode, states, actions, rewards, float(rtg), int(h), float(lmbda), returns)
         sl.owner = tk
@@ -526,9 +562,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
             # the policy pass consumes no variate: its ~30 launches go out first, the draws are enqueued while the device runs them
             hd.policy_pass(mode, states, actions, rewards, h, tk.rtg, slot=sl.i, returns=returns, pruned=self._policy_pruned)
             if eps is None:
-                eps = self._draw_eps(mode, h, sl.eps_buf if chain is not None else None)
+                eps = self._step_eps(tk.index, mode, h, sl.eps_buf if chain is not None else None)
             tk.eps = eps = eps.reshape(N, -1, A)
-            tk.expo = sl.expo_buf.exponential_(1, generator=self.generator) if chain is not None else self._draw_expo()
+            tk.expo = self._step_expo(tk.index, sl.expo_buf if chain is not None else None)
             if chain is not None:
                 sl.ev_pol.record(chain)
         if chain is not None and self._alternate:
@@ -565,20 +601,21 @@ class HipPlanner(GoalMixin, LockstepMixin):
             self._mark_main()
         return tk
 
-    def _issue_native(self, mode: int, states, actions, rewards, rtg: float, h: int, lmbda: float, eps=None, returns=None) -> "PlanTicket":
+    def _issue_native(self, mode: int, states, actions, rewards, rtg: float, h: int, lmbda: float, eps=None, returns=None,
+                      slot=None) -> "PlanTicket":
         """A serial plan step as ONE library call (``native_step=True``): m3pc_plan_step_certified runs what ``_issue``,
         ``_enqueue_tail`` and certificate.resolve drive from here; the ticket comes back resolved."""
         cfg, hd = self.cfg, self.handle
         N, A = int(cfg.action_samples), self.A
-        sl = self._acquire_slot().ready(self)
+        sl = (slot if slot is not None else self._acquire_slot()).ready(self)
         tk = PlanTicket(self, sl, mode, states, actions, rewards, float(rtg), int(h), float(lmbda), returns)
         tk.index, self._step_index = self._step_index, self._step_index + 1
         tk.grow_in, tk.kfirst_in, tk.rfirst_in = self._adapt(tk.index)
         # the variates in the serial order of draws: eps, then the multinomial's exponentials
         if eps is None:
-            eps = self._draw_eps(mode, h)
+            eps = self._step_eps(tk.index, mode, h)
         tk.eps = eps = eps.reshape(N, -1, A)
-        tk.expo = self._draw_expo()
+        tk.expo = self._step_expo(tk.index)
         disc, temp = float(cfg.discount), float(cfg.temperature)
         bound = self.rescore == "bound"
         R = self._R if bound else 0
@@ -604,6 +641,14 @@ class HipPlanner(GoalMixin, LockstepMixin):
                                           rfirst=rfirst, rmax=R, precision=self.precision, slot=sl.i, returns=returns,
                                           pruned=self._policy_pruned)
         self._mark_main()
+        return self._native_result(tk, res, rec, delta, kmin, kmax)
+
+    def _native_result(self, tk, res, rec, delta, kmin, kmax) -> "PlanTicket":
+        """Fold the record of a certified step the library ran (serial call, or _begin + _end) into the adaptive state and
+        ``planner.last``; the ticket is resolved."""
+        N = int(self.cfg.action_samples)
+        bound = self.rescore == "bound"
+        R = self._R if bound else 0
         extra = {}
         top = None
         if bound:
@@ -636,6 +681,67 @@ class HipPlanner(GoalMixin, LockstepMixin):
         tk.info = self.last
         tk.out = (sample_action, eval_action)
         return tk
+
+    def _issue_native_async(self, mode: int, states, actions, rewards, rtg: float, h: int, lmbda: float, eps, returns, slot,
+                            inputs_ready: bool) -> "PlanTicket":
+        """A pipelined plan step through m3pc_plan_step_certified_begin (``native_step=True``): the library runs the schedule of
+        ``_issue`` / ``_enqueue_tail`` on this planner's chain-stream pair, ``_finish`` resolves the ticket with
+        m3pc_plan_step_certified_end.  The adaptive state stays here, as in ``_issue_native``; calibration steps run serially."""
+        cfg, hd = self.cfg, self.handle
+        N, A = int(cfg.action_samples), self.A
+        sl = (slot if slot is not None else self._acquire_slot()).ready(self)
+        bound = self.rescore == "bound"
+        main = torch.cuda.current_stream(self.device)
+        if bound and self._delta_fixed is None and self._cal_left > 0:
+            self._drain()
+            if inputs_ready:
+                main.wait_event(sl.ev_h2d)  # (plan_async copied the window on the chain stream)
+            tk = self._issue_native(mode, states, actions, rewards, rtg, h, lmbda, eps, returns, slot=sl)
+            sl.ev_done.record(main)  # (plan_async re-fills the slot's window buffer behind it)
+            return tk
+        chain, _ = self._streams_of(sl)
+        if not self._step_streams_set:
+            self._drain()
+            hd.set_step_streams(*self._chain_streams())  # the library's chain streams ARE this process's pair (four hardware queues)
+            self._step_streams_set = True
+        tk = PlanTicket(self, sl, mode, states, actions, rewards, float(rtg), int(h), float(lmbda), returns)
+        sl.owner = tk
+        tk.native = True
+        tk.chain = tk.tchain = chain
+        tk.index, self._step_index = self._step_index, self._step_index + 1
+        tk.grow_in, tk.kfirst_in, tk.rfirst_in = self._adapt(tk.index)
+        if inputs_ready and self._ev_main is not None:
+            chain.wait_event(self._ev_main)  # (_mark_main: the caller's stream was in the chain workspaces)
+        # the variates in the serial order of draws, on the current stream into the slot's buffers (free: the slot's previous owner
+        # has been ended, which ordered this stream behind its last kernel)
+        if eps is None:
+            eps = self._step_eps(tk.index, mode, h, sl.eps_buf)
+        tk.eps = eps = eps.reshape(N, -1, A)
+        tk.expo = self._step_expo(tk.index, sl.expo_buf)
+        R = self._R if bound else 0
+        kmin = kmax = rfirst = 1
+        delta = 0.0
+        if bound:
+            kmax = max(min(self.rescore_max, N - 1 if N > 1 else 1, 1024 - self._R - 1), 1)
+            kmin = max(min(tk.kfirst_in, N, kmax), 1)
+            rfirst = max(min(tk.rfirst_in, R), 1) if R > 0 else 0
+            delta = max(self._delta0, tk.grow_in)
+        tk.kmin, tk.kmax, tk.delta = kmin, kmax, delta
+        tk.res = hd.plan_step_certified_begin(mode, states, actions, rewards, eps, tk.expo, h, tk.rtg, tk.lmbda, float(cfg.discount), N,
+                                              float(cfg.temperature), delta=delta, grow_delta=bound and self._delta_fixed is None,
+                                              kmin=kmin, kmax=kmax, rfirst=rfirst, rmax=R, precision=self.precision, slot=sl.i,
+                                              returns=returns, pruned=self._policy_pruned, inputs_ready=inputs_ready)
+        tk.tail_enqueued = True  # (the library's business)
+        return tk
+
+    def _finish_native(self, tk):
+        sl = tk.slot
+        rec = self.handle.plan_step_certified_end(sl.i)
+        sl.ev_done.record(torch.cuda.current_stream(self.device))  # (plan_async re-fills the slot's buffers behind it)
+        self._native_result(tk, tk.res, rec, tk.delta, tk.kmin, tk.kmax)
+        if sl.owner is tk:
+            sl.owner = None
+        return tk.out
 
     def _maybe_fall_back_to_fp32(self):
         """auto_fp32: the certified bf16 step costs more than an fp32 step once its certificates keep asking for the whole window
@@ -753,6 +859,8 @@ class HipPlanner(GoalMixin, LockstepMixin):
         for more candidates, and order the current stream behind the step."""
         if tk.out is not None:
             return tk.out
+        if tk.native:
+            return self._finish_native(tk)
         cfg, hd, sl = self.cfg, self.handle, tk.slot
         if not tk.tail_enqueued:
             self._pending = [o for o in self._pending if o is not tk]
