@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI history.  Added within v7 (new symbols and structures only; nothing existing changed): m3pc_plan_step_certified,
  * m3pc_calibrate_delta, m3pc_cert_args, m3pc_cert_record; then m3pc_plan_step_certified_begin / _end, m3pc_set_step_streams and
- * m3pc_draw_variates.  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * m3pc_draw_variates; then m3pc_refit_resample, m3pc_refine_plan and m3pc_refine_args (CEM / MPPI refinement).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -513,6 +513,72 @@ int m3pc_draw_variates(m3pc_handle* h, unsigned long long seed, unsigned long lo
  * stream-ordered, with one bounded read of the host-mapped statistics at the end (as above). */
 int m3pc_calibrate_delta(m3pc_handle* h, const m3pc_plan_args* args, const float* states, const float* actions, const float* rewards,
                          const float* eps, const float* scores_low, float factor, float* delta_out, void* stream);
+
+/* Iterative refinement of a plan: cross-entropy (CEM) or softmax-weighted (MPPI) refits of a per-(step, action) Gaussian over the
+ * last h actions, warm-startable from the previous plan -- the algorithm of the legacy sample_action_cem
+ * (research/omtm/datasets/sequence_dataset.py:919-1000: noisy copies of the policy mean, score, keep top_k, refit, resample, clamp to
+ * [-1, 1]) on this model's plan step, as m3pc_amd/goal.py (cem_guiding) states it.
+ *
+ * The refit, per column c = (t, a) of the h * A columns, over the k elite rows x_i = cand[elite_i, c]:
+ *   weights  M3PC_REFINE_CEM:  w_i = 1 / k
+ *            M3PC_REFINE_MPPI: u_i = expf(temperature * (E[elite_i] - max_i E[elite_i])), w_i = u_i / sum u
+ *   mean_c = sum w_i x_i;  S_c = sum w_i (x_i - mean_c)^2 (a second pass over the values);  D = sum w_i (1 - w_i)
+ *   std_c  = max(D > 1e-6 ? sqrt(S_c / D) : 0, min_std)
+ * With equal weights that is torch.std's unbiased estimate (0 at k = 1); with MPPI weights the reliability-weighted unbiased
+ * variance.  A column whose elites are all equal has exactly that value as its mean and exactly 0 in front of the floor.
+ * The resample: out[j, c] = min(1, max(-1, mean_c + std_c * noise[j, c])), product and sum rounded separately in fp32 (bit for bit
+ * torch.clamp(mean + std * noise, -1, 1)).  Both kernels reduce in a fixed order without atomics: results are bit-identical from
+ * run to run. */
+#define M3PC_REFINE_CEM 0
+#define M3PC_REFINE_MPPI 1
+#define M3PC_REFINE_MAX_ITER 16
+typedef struct m3pc_refine_args {   /* 4-byte fields only, in this order */
+    int iterations;      /* 1 .. M3PC_REFINE_MAX_ITER */
+    int top_k;           /* elites per iteration, 1 .. n_total */
+    int weighting;       /* M3PC_REFINE_* */
+    float temperature;   /* MPPI only; finite, >= 0 */
+    float init_std;      /* finite, >= 0 */
+    float min_std;       /* floor of every refit std; finite, >= 0 */
+    unsigned int seed_lo, seed_hi, step_lo, step_hi;  /* generator coordinates, read when noise == NULL */
+} m3pc_refine_args;
+
+/* One refit (+ optional resample) as a call of its own, for a host that runs its own loop.  Needs a handle (for A and the device),
+ * no weights.
+ *   cand     device (n, horizon, A);  elites device (k,) int32: distinct ids in [0, n), any order (an id outside is clamped)
+ *   scores   device (n,): read for M3PC_REFINE_MPPI only (NULL allowed for M3PC_REFINE_CEM)
+ *   mean, std  device out (horizon, A)
+ *   noise    device (n, horizon, A) and cand_out device out (n, horizon, A): both given (refit, then resample) or both NULL
+ *            (refit only).  cand_out may alias cand.
+ * n <= 16384, 1 <= k <= n, 1 <= horizon <= T; bad arguments return M3PC_EINVAL before any HIP call. */
+int m3pc_refit_resample(m3pc_handle* h, const float* cand, int n, int horizon, const float* scores, const int* elites, int k,
+                        int weighting, float temperature, float min_std, const float* noise, float* mean, float* std,
+                        float* cand_out, void* stream);
+
+/* The whole refinement as one call, all on `stream`; nothing is read back to the host, the host never waits:
+ *   1. m3pc_policy_pass for `args` (honours M3PC_PLAN_PRUNED_POLICY, args->returns, rtg): the slot's policy head and returns tokens
+ *   2. mean[0] = init_mean if given (device (h, A): the warm start, e.g. the previous call's final mean), else tanh of the policy
+ *      loc over the last h steps;  std[0] = init_std
+ *   3. candidates = resample(mean[0], std[0], noise[0])
+ *   4. for it = 0 .. iterations-1: scores[it] = the candidates' TD(lambda) scores in args->precision (m3pc_score_actions: RTG or
+ *      CRITIC scoring, one window);  elites[it] = their top_k (descending, ties to the lower index);  refit into mean[it+1],
+ *      std[it+1];  candidates = resample(mean[it+1], std[it+1], noise[it+1])
+ *   5. sample_action = candidates[0, 0, :], eval_action = mean[iterations][0, :]
+ * One rank: n_begin == 0, n_count == n_total <= min(max_candidates, 16384).  args->flags: M3PC_PLAN_PRUNED_POLICY or 0 (anything else: M3PC_EINVAL).
+ *   mean, std    device out (iterations + 1, h, A)
+ *   candidates   device out (n_total, h, A): the live buffer of the loop; on return the candidates of the last resample
+ *   scores       device out (iterations, n_total), optional;  elites device out (iterations, top_k) int32, optional
+ *   noise        device (iterations + 1, n_total, h, A) standard normals, or NULL: the library draws them -- exactly what
+ *                m3pc_draw_variates(seed, step, 0, (iterations + 1) * n_total, h * A, eps, NULL) yields
+ *   sample_action, eval_action   device out (A,), each optional
+ * In M3PC_PREC_BF16 the elite set of an iteration is the bf16 ranking's; M3PC_PREC_BF16X3 and M3PC_PREC_FP32 are the modes whose
+ * elite sets follow fp32 scores (no certificate covers the elite boundary).
+ * Bad arguments (the one-rank checks of m3pc_plan_step_certified; iterations, top_k, weighting, temperature, init_std, min_std;
+ * a mode other than RTG / CRITIC; null required pointers) return M3PC_EINVAL before any HIP call.  M3PC_ESTATE while a pipelined
+ * certified step is begun, and for CRITIC scoring without critic weights, before anything is enqueued.  Runs in the workspaces of m3pc_policy_pass and m3pc_score_actions, under their ordering rules. */
+int m3pc_refine_plan(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_refine_args* refine, const float* states,
+                     const float* actions, const float* rewards, const float* init_mean, const float* noise,
+                     float* mean, float* std, float* candidates, float* scores, int* elites,
+                     float* sample_action, float* eval_action, void* stream);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

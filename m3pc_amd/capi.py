@@ -45,6 +45,7 @@ EXPORTS = (
     "m3pc_profile_read",
     "m3pc_plan_step_certified", "m3pc_calibrate_delta",
     "m3pc_set_step_streams", "m3pc_plan_step_certified_begin", "m3pc_plan_step_certified_end", "m3pc_draw_variates",
+    "m3pc_refit_resample", "m3pc_refine_plan",
 )
 
 
@@ -77,6 +78,17 @@ class CertRecord(C.Structure):
                 ("saturated", C.c_int), ("everything", C.c_int), ("certified", C.c_int), ("rounds", C.c_int),
                 ("delta", C.c_float), ("shift", C.c_float), ("deviation", C.c_float), ("margin", C.c_float)]
 
+
+class RefineArgs(C.Structure):
+    """m3pc_refine_args: the refinement loop of ``m3pc_refine_plan`` (seed / step: read when the library draws the noise)."""
+    _fields_ = [("iterations", C.c_int), ("top_k", C.c_int), ("weighting", C.c_int), ("temperature", C.c_float),
+                ("init_std", C.c_float), ("min_std", C.c_float), ("seed_lo", C.c_uint), ("seed_hi", C.c_uint),
+                ("step_lo", C.c_uint), ("step_hi", C.c_uint)]
+
+
+REFINE_CEM, REFINE_MPPI = 0, 1  # M3PC_REFINE_*
+REFINE_MAX_ITER = 16
+REFINE_WEIGHTINGS = {"cem": REFINE_CEM, "mppi": REFINE_MPPI}
 
 PLAN_DEFER_JOIN = 1
 PLAN_PRUNED_POLICY = 2
@@ -140,6 +152,8 @@ def load_library(path: Optional[str] = None):
                                            vp, vp, vp, vp, vp, vp],
         "m3pc_plan_step_certified_end": [vp, i, C.POINTER(CertRecord), vp],
         "m3pc_draw_variates": [vp, C.c_ulonglong, C.c_ulonglong, i, i, i, vp, vp, vp],
+        "m3pc_refit_resample": [vp, vp, i, i, vp, vp, i, i, f, f, vp, vp, vp, vp, vp],
+        "m3pc_refine_plan": [vp, C.POINTER(PlanArgs), C.POINTER(RefineArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }
@@ -545,6 +559,75 @@ class Handle:
         check(self.lib.m3pc_draw_variates(self._h, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(n_begin), int(n_count),
                                           int(row_elems), _ptr(eps), _ptr(expo), _stream(self.device)))
         return eps, expo
+
+    def refit_resample(self, cand: torch.Tensor, elites: torch.Tensor, scores: Optional[torch.Tensor] = None,
+                       weighting: int = REFINE_CEM, temperature: float = 0.0, min_std: float = 0.0,
+                       noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+        """One CEM / MPPI refit of cand (n,h,A) on the rows ``elites`` (k,) int32 (m3pc_refit_resample), on the current stream:
+        -> (mean (h,A), std (h,A)), and with ``noise`` (n,h,A) also the resampled candidates clamp(mean + std * noise, -1, 1)
+        (``out``: the buffer they go to; may be ``cand`` itself).  scores (n,): needed for REFINE_MPPI.  Needs no weights."""
+        assert cand.is_cuda and cand.dtype == torch.float32 and cand.is_contiguous() and cand.dim() == 3 and cand.shape[2] == self.A
+        assert elites.is_cuda and elites.dtype == torch.int32 and elites.is_contiguous()
+        n, hz = int(cand.shape[0]), int(cand.shape[1])
+        f32 = dict(dtype=torch.float32, device=self.device)
+        mean = torch.empty((hz, self.A), **f32)
+        std = torch.empty((hz, self.A), **f32)
+        if scores is not None:
+            assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == n
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == cand.numel()
+            out = torch.empty_like(cand) if out is None else out
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == cand.numel()
+        else:
+            out = None
+        check(self.lib.m3pc_refit_resample(self._h, _ptr(cand), n, hz, _ptr(scores), _ptr(elites), int(elites.numel()), int(weighting),
+                                           float(temperature), float(min_std), _ptr(noise), _ptr(mean), _ptr(std), _ptr(out),
+                                           _stream(self.device)))
+        return (mean, std) if noise is None else (mean, std, out)
+
+    def refine_plan(self, mode: int, states, actions, rewards, horizon: int, rtg: float, lmbda: float, discount: float, n_total: int,
+                    iterations: int = 2, top_k: int = 128, weighting: int = REFINE_CEM, temperature: float = 0.0,
+                    init_std: float = 0.1, min_std: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0,
+                    init_mean: Optional[torch.Tensor] = None, precision: int = PREC_FP32, slot: int = 0, returns=None,
+                    pruned: bool = False, out: Optional[Dict[str, torch.Tensor]] = None, want_trace: bool = True,
+                    want_actions: bool = True):
+        """The whole CEM / MPPI refinement of a plan in ONE library call on the current stream (m3pc_refine_plan): policy pass,
+        then ``iterations`` x (score the candidates in ``precision``, top_k, refit, resample).  noise: (iterations+1, n_total, h, A)
+        normals, or None: the library draws them from (seed, step) -- ``draw_variates(seed, step, (iterations+1) * n_total, h * A)``.
+        init_mean (h,A): the warm start (else tanh of the policy loc).  ``out``: optional preallocated outputs by name.
+        -> dict: mean, std (iterations+1,h,A), candidates (n_total,h,A), scores (iterations,n_total), elites (iterations,top_k)
+        int32, sample_action (1,A), eval_action (A,).  want_trace=False: no scores / elites (the call's optional outputs are
+        passed as NULL: scratch of the handle stands in); want_actions=False: no sample_action / eval_action."""
+        dev, A, it, n, hz, k = self.device, self.A, int(iterations), int(n_total), int(horizon), int(top_k)
+        shapes = dict(mean=(it + 1, hz, A), std=(it + 1, hz, A), candidates=(n, hz, A), scores=(it, n), elites=(it, k),
+                      sample_action=(1, A), eval_action=(A,))
+        res = {}
+        skip = (() if want_trace else ("scores", "elites")) + (() if want_actions else ("sample_action", "eval_action"))
+        for name, shape in shapes.items():
+            if name in skip:
+                continue
+            shape = tuple(max(v, 0) for v in shape)  # (a bad size is the library's to refuse)
+            dtype = torch.int32 if name == "elites" else torch.float32
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape, name
+            res[name] = t
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == (it + 1) * n * hz * A
+        if init_mean is not None:
+            init_mean = self._f32(init_mean)
+            assert init_mean.is_cuda and init_mean.numel() == hz * A
+        args = self._args(mode, precision, hz, n, 0, n, lmbda, discount, rtg, slot, returns)
+        args.flags = PLAN_PRUNED_POLICY if pruned else 0
+        seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        ref = RefineArgs(it, k, int(weighting), float(temperature), float(init_std), float(min_std), seed & 0xFFFFFFFF, seed >> 32,
+                         step & 0xFFFFFFFF, step >> 32)
+        ins = [self._f32(t) for t in (states, actions, rewards)]
+        check(self.lib.m3pc_refine_plan(self._h, C.byref(args), C.byref(ref), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(init_mean),
+                                        _ptr(noise), _ptr(res["mean"]), _ptr(res["std"]), _ptr(res["candidates"]), _ptr(res.get("scores")),
+                                        _ptr(res.get("elites")), _ptr(res.get("sample_action")), _ptr(res.get("eval_action")), _stream(dev)))
+        return res
 
     def calibrate_delta(self, mode: int, states, actions, rewards, eps, scores_low: torch.Tensor, horizon: int, lmbda: float,
                         discount: float, n_total: int, factor: float = 1.6, slot: int = 0) -> float:

@@ -488,6 +488,37 @@ void launch_deviation_stats(const float* b, const float* f, int n, float* stats,
 // counter-based variates (Philox4x32-10 of (seed, step, array, element / 4)): out[0 .. g1 - g0) = elements [g0, g1) of the flat array;
 // array 0 = standard normals (Box-Muller), 1 = Exp(1), never 0
 void launch_variates(unsigned long long seed, unsigned long long step, int array, long long g0, long long g1, float* out, hipStream_t st);
+// CEM / MPPI refit (refine.hip): per column c of the C = h * A columns, over the k elite rows cand[elite[i], c]:
+// w_i = 1 / k (weighting 0) or softmax_i(tau * scores[elite[i]]) (weighting 1); mean[c] = sum w_i x_i;
+// std[c] = max(sqrt(sum w_i (x_i - mean)^2 / sum w_i (1 - w_i)), min_std), 0 in front of the floor when sum w_i (1 - w_i) <= 1e-6.
+// One workgroup per column, fixed-order reductions: bit-identical from run to run.  n <= 16384, 1 <= k <= n.
+struct RefitP {
+    const float* cand;    // (n, C)
+    const int* elite;     // (k,) distinct ids in [0, n), any order
+    const float* scores;  // (n,), read for weighting 1 only
+    int n, k, C, weighting;
+    float tau, min_std;
+    float* mean;          // (C,)
+    float* std;           // (C,)
+};
+void launch_refit(const RefitP& p, hipStream_t st);
+// out[e] = min(1, max(-1, mean[e % C] + std[e % C] * noise[e])) over total = n * C elements, product and sum rounded separately.
+// mean == NULL: tanhf(loc[c]); std == NULL: std_const (the first distribution of a refinement).  16-byte loads and stores when
+// total % 4 == 0 and noise / out are 16-byte aligned.  out may alias the candidates an earlier launch_refit read.
+struct ResampleP {
+    const float* mean;    // (C,) or NULL
+    const float* std;     // (C,) or NULL
+    const float* loc;     // (C,) read when mean == NULL
+    float std_const;
+    const float* noise;   // (total,)
+    float* out;           // (total,)
+    int total, C, A;
+    float* mean_out;      // optional (C,): the mean / std the launch used
+    float* std_out;
+    float* sample_action; // optional (A,): out[0 .. A)
+    float* eval_action;   // optional (A,): mean[0 .. A)
+};
+void launch_resample(const ResampleP& p, hipStream_t st);
 // dst[index[i]] = src[i]
 void launch_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, hipStream_t st);  // + index_copy[i] = index[i]
 

@@ -128,6 +128,9 @@ int m3pc_create(const m3pc_dims* dims, int device, m3pc_handle** out) {
     CHK(dmalloc(&h->sa_buf, (size_t)(D.max_candidates > h->chain[0].max_cand ? D.max_candidates : h->chain[0].max_cand) * T * h->A));
     CHK(dmalloc(&h->sa_chain[0], (size_t)h->chain[0].max_cand * T * h->A));
     CHK(dmalloc(&h->sa_chain[1], (size_t)h->chain[0].max_cand * T * h->A));
+    CHK(dmalloc(&h->refine_noise, (size_t)D.max_candidates * T * h->A));
+    CHK(dmalloc(&h->refine_scores, (size_t)D.max_candidates));
+    CHK(dmalloc(&h->refine_elites, (size_t)D.max_candidates));
     for (int s = 0; s < M3PC_SLOTS; ++s) {
         CHK(dmalloc(&h->cert_list[s], 64 + 1024));
         CHK(dmalloc(&h->cert_b[s], 64 + 1024));
@@ -235,7 +238,8 @@ int m3pc_destroy(m3pc_handle* h) {
         hipFree(h->slot[s].sd);
         hipFree(h->slot[s].rtok);
     }
-    void* bufs[] = {h->sel_scratch, h->d_topk, h->er_top, h->sa_buf, h->sa_chain[0], h->sa_chain[1], h->c_om, h->c_os, h->goal_ws};
+    void* bufs[] = {h->sel_scratch, h->d_topk, h->er_top, h->sa_buf, h->sa_chain[0], h->sa_chain[1], h->c_om, h->c_os, h->goal_ws,
+                    h->refine_noise, h->refine_scores, h->refine_elites};
     for (int s = 0; s < M3PC_SLOTS; ++s) {
         void* cb[] = {h->cert_list[s], h->cert_b[s], h->cert_f[s], h->cert_stats[s], h->cert_f32[s], h->cert_top1[s]};
         for (void* b : cb)
@@ -1710,6 +1714,144 @@ int m3pc_calibrate_delta(m3pc_handle* h, const m3pc_plan_args* a, const float* s
     float s8[8];
     CHK(cert_wait(h, a->slot, seq, 8, st, s8));
     *delta_out = cert_delta(factor, s8[1], s8[2]);
+    return 0;
+}
+
+// ---- CEM / MPPI refinement of a plan (include/m3pc_hip.h: m3pc_refit_resample, m3pc_refine_plan; kernels: refine.hip)
+static bool finite_nonneg(float v) { return v >= 0.f && v <= 3.402823466e+38f; }
+// weighting / temperature / min_std of a refit, before any HIP call
+static int refine_check_refit(int weighting, float temperature, float min_std, const char* who) {
+    if (weighting != M3PC_REFINE_CEM && weighting != M3PC_REFINE_MPPI)
+        return fail(M3PC_EINVAL, "%s: weighting %d is neither M3PC_REFINE_CEM nor M3PC_REFINE_MPPI", who, weighting);
+    if (weighting == M3PC_REFINE_MPPI && !finite_nonneg(temperature)) return fail(M3PC_EINVAL, "%s: temperature must be finite and >= 0", who);
+    if (!finite_nonneg(min_std)) return fail(M3PC_EINVAL, "%s: min_std must be finite and >= 0", who);
+    return 0;
+}
+
+int m3pc_refit_resample(m3pc_handle* h, const float* cand, int n, int horizon, const float* scores, const int* elites, int k, int weighting,
+                        float temperature, float min_std, const float* noise, float* mean, float* std_, float* cand_out, void* stream) {
+    if (!h || !cand || !elites || !mean || !std_) return fail(M3PC_EINVAL, "null argument");
+    if (n < 1 || n > 16384) return fail(M3PC_EINVAL, "m3pc_refit_resample: n %d outside [1, 16384]", n);
+    if (k < 1 || k > n) return fail(M3PC_EINVAL, "m3pc_refit_resample: k %d outside [1, n=%d]", k, n);
+    if (horizon < 1) return fail(M3PC_EINVAL, "m3pc_refit_resample: horizon %d < 1", horizon);
+    CHK(refine_check_refit(weighting, temperature, min_std, "m3pc_refit_resample"));
+    if (weighting == M3PC_REFINE_MPPI && !scores) return fail(M3PC_EINVAL, "m3pc_refit_resample: M3PC_REFINE_MPPI needs scores");
+    if ((noise == nullptr) != (cand_out == nullptr)) return fail(M3PC_EINVAL, "m3pc_refit_resample: noise and cand_out are given together or not at all");
+    if (horizon > h->T) return fail(M3PC_EINVAL, "horizon %d outside [1, T=%d]", horizon, h->T);
+    const long long total = (long long)n * horizon * h->A;
+    if (total > (1LL << 30)) return fail(M3PC_EINVAL, "m3pc_refit_resample: %lld candidate elements > 2^30", total);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    RefitP rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.cand = cand;
+    rp.elite = elites;
+    rp.scores = scores;
+    rp.n = n;
+    rp.k = k;
+    rp.C = horizon * h->A;
+    rp.weighting = weighting;
+    rp.tau = temperature;
+    rp.min_std = min_std;
+    rp.mean = mean;
+    rp.std = std_;
+    launch_refit(rp, st);
+    if (noise) {
+        ResampleP sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.mean = mean;
+        sp.std = std_;
+        sp.noise = noise;
+        sp.out = cand_out;
+        sp.total = (int)total;
+        sp.C = rp.C;
+        sp.A = h->A;
+        launch_resample(sp, st);
+    }
+    return check_launch("refit_resample");
+}
+
+int m3pc_refine_plan(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_refine_args* r, const float* states, const float* actions,
+                     const float* rewards, const float* init_mean, const float* noise, float* mean, float* std_, float* candidates,
+                     float* scores, int* elites, float* sample_action, float* eval_action, void* stream) {
+    if (!h || !a || !r || !states || !actions || !rewards || !mean || !std_ || !candidates) return fail(M3PC_EINVAL, "null argument");
+    CHK(cert_check_args(a, "m3pc_refine_plan"));
+    if (a->mode != M3PC_MODE_RTG && a->mode != M3PC_MODE_CRITIC) return fail(M3PC_EINVAL, "m3pc_refine_plan: mode must be RTG or CRITIC scoring");
+    if (a->horizon < 1) return fail(M3PC_EINVAL, "m3pc_refine_plan: horizon %d < 1", a->horizon);
+    if (a->flags & ~M3PC_PLAN_PRUNED_POLICY)
+        return fail(M3PC_EINVAL, "m3pc_refine_plan: m3pc_plan_args::flags 0x%x holds more than M3PC_PLAN_PRUNED_POLICY", a->flags);
+    if (r->iterations < 1 || r->iterations > M3PC_REFINE_MAX_ITER)
+        return fail(M3PC_EINVAL, "m3pc_refine_plan: iterations %d outside [1, %d]", r->iterations, M3PC_REFINE_MAX_ITER);
+    if (r->top_k < 1 || r->top_k > a->n_total) return fail(M3PC_EINVAL, "m3pc_refine_plan: top_k %d outside [1, n_total=%d]", r->top_k, a->n_total);
+    CHK(refine_check_refit(r->weighting, r->temperature, r->min_std, "m3pc_refine_plan"));
+    if (!finite_nonneg(r->init_std)) return fail(M3PC_EINVAL, "m3pc_refine_plan: init_std must be finite and >= 0");
+    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "m3pc_refine_plan with a pipelined step begun (m3pc_plan_step_certified_end first)");
+    if (a->mode == M3PC_MODE_CRITIC && !h->critic_set) return fail(M3PC_ESTATE, "critic weights not set");
+    const int N = a->n_total, k = r->top_k, T = h->T, hh = a->horizon;
+    if (N > h->dm.max_candidates) return fail(M3PC_ENOMEM, "n_total %d > max_candidates %d", N, h->dm.max_candidates);
+    if (hh > T) return fail(M3PC_EINVAL, "horizon %d outside [1, T=%d]", hh, T);
+    hipStream_t st = (hipStream_t)stream;
+    const int C = hh * h->A;
+    const long long total = (long long)N * C;  // (<= max_candidates * T * A: what the workspace holds)
+
+    // learner.py:278-284: the policy pass; leaves the slot's policy head and returns tokens (the scoring reads the latter)
+    m3pc_plan_args pa = *a;
+    pa.window = 0;
+    CHK(m3pc_policy_pass(h, &pa, states, actions, rewards, nullptr, nullptr, stream));
+    pa.flags = 0;
+
+    const unsigned long long seed = ((unsigned long long)r->seed_hi << 32) | r->seed_lo, step = ((unsigned long long)r->step_hi << 32) | r->step_lo;
+    // the noise of iteration `it`: the caller's slice, or that slice of the (seed, step) array drawn into the handle's buffer
+    auto noise_of = [&](int it) -> const float* {
+        if (noise) return noise + (size_t)it * total;
+        launch_variates(seed, step, 0, (long long)it * total, (long long)(it + 1) * total, h->refine_noise, st);
+        return h->refine_noise;
+    };
+    ResampleP sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.out = candidates;
+    sp.total = (int)total;
+    sp.C = C;
+    sp.A = h->A;
+    // distribution 0: the caller's mean or tanh of the policy head over the last h steps, std = init_std; candidates from it
+    sp.mean = init_mean;
+    sp.loc = h->loc + (size_t)(T - hh) * h->A;
+    sp.std_const = r->init_std;
+    sp.noise = noise_of(0);
+    sp.mean_out = mean;
+    sp.std_out = std_;
+    launch_resample(sp, st);
+    CHK(check_launch("refine_plan"));
+    sp.mean_out = sp.std_out = nullptr;
+    for (int it = 0; it < r->iterations; ++it) {
+        float* er = scores ? scores + (size_t)it * N : h->refine_scores;
+        int* top = elites ? elites + (size_t)it * k : h->refine_elites;
+        CHK(m3pc_score_actions(h, &pa, 1, states, actions, rewards, candidates, nullptr, er, nullptr, nullptr, stream));
+        launch_topk(er, N, k, top, st);
+        RefitP rp;
+        memset(&rp, 0, sizeof(rp));
+        rp.cand = candidates;
+        rp.elite = top;
+        rp.scores = er;
+        rp.n = N;
+        rp.k = k;
+        rp.C = C;
+        rp.weighting = r->weighting;
+        rp.tau = r->temperature;
+        rp.min_std = r->min_std;
+        rp.mean = mean + (size_t)(it + 1) * C;
+        rp.std = std_ + (size_t)(it + 1) * C;
+        launch_refit(rp, st);
+        sp.mean = rp.mean;
+        sp.std = rp.std;
+        sp.noise = noise_of(it + 1);
+        if (it == r->iterations - 1) {  // what cem_guiding returns: candidate 0's first action, the final mean's first action
+            sp.sample_action = sample_action;
+            sp.eval_action = eval_action;
+        }
+        launch_resample(sp, st);
+        CHK(check_launch("refine_plan"));
+    }
     return 0;
 }
 

@@ -140,6 +140,11 @@ struct m3pc_handle {
     float* er_top = nullptr;      // (1024,) their fp32 re-scores
     float* sa_buf = nullptr;      // (max(max_candidates, max_rescore), h, A) scratch for m3pc_rescore
     float* sa_chain[2] = {nullptr, nullptr};  // the same for re-scores that run in the chain workspaces (one per slot parity)
+    // m3pc_refine_plan: one iteration's library-drawn noise (max_candidates, T, A), and what stands in for the caller's optional
+    // scores (max_candidates,) / elites (max_candidates,) -- allocated once, with the handle
+    float* refine_noise = nullptr;
+    float* refine_scores = nullptr;
+    int* refine_elites = nullptr;
     float* splitk_ws = nullptr;   // raw split-K slabs of the few-row fp32 GEMMs
     long long splitk_ws_bytes = 0;
     // m3pc_plan_step_certified / m3pc_calibrate_delta: the step's lists (64 race entries at most in front of 1024 score entries:

@@ -181,7 +181,8 @@ class GoalMixin:
     # ---------------------------------------------------------------------------------------- CEM refinement
     @torch.no_grad()
     def cem_guiding(self, trajectory: Dict[str, torch.Tensor], h: int, iterations: int = 2, top_k: int = 128, init_std: float = 0.1,
-                    noise=None):
+                    noise=None, native: bool = False, weighting: str = "cem", temperature: Optional[float] = None, min_std: float = 0.0,
+                    init_mean=None):
         """Cross-entropy refinement of the plan (the legacy ``sample_action_cem`` of
         research/omtm/datasets/sequence_dataset.py:919-1000 -- N=1024, top_k=128, 2 iterations -- restated on this model's
         plan step: that function predates the four-key omtm model and cannot run on it, so parity is pinned on the oracle's
@@ -190,7 +191,17 @@ class GoalMixin:
           repeat: score (TD(lambda) as rtg_guiding / critic_lambda_guiding) -> top_k -> mean / std per (t, a)
                   candidates = clamp(mean + std * noise_i, -1, 1)
         Returns (sample_action (1,A): first action of candidate 0 after the last refit, as the legacy code returns;
-                 eval_action (A,): first action of the final mean).  ``noise``: optional (iterations+1, N, h, A) normals."""
+                 eval_action (A,): first action of the final mean).  ``noise``: optional (iterations+1, N, h, A) normals.
+        native=True: the whole refinement as ONE library call (m3pc_refine_plan: refit and resample on the device, nothing but
+        the library's kernels), with what that call adds: weighting "cem" (equal weights on the top_k) or "mppi" (softmax of
+        ``temperature`` x score over the top_k; default cfg.temperature), ``min_std`` (floor of every refit std) and ``init_mean``
+        (h, A): the warm start, e.g. ``last["cem"][-1]["mean"]`` of the previous call, in place of tanh(policy loc).  Without
+        ``noise`` it is drawn from torch as in the loop below, or by the library from (seed, step index) when the planner was
+        built with variates="library".  native=False takes none of these options (ValueError)."""
+        if native:
+            return self._cem_native(trajectory, h, iterations, top_k, init_std, noise, weighting, temperature, min_std, init_mean)
+        if weighting != "cem" or temperature is not None or min_std != 0.0 or init_mean is not None:
+            raise ValueError("cem_guiding: weighting / temperature / min_std / init_mean need native=True")
         self._drain()
         s, a, r, rtg, ret = self._split(trajectory)
         cfg = self.cfg
@@ -219,3 +230,31 @@ class GoalMixin:
         self.last = dict(cem=trace, candidates=cand)
         return cand[0, 0][None], mean[0]
 
+    def _cem_native(self, trajectory, h, iterations, top_k, init_std, noise, weighting, temperature, min_std, init_mean):
+        """``cem_guiding(native=True)``: one m3pc_refine_plan call; fills ``self.last`` as the Python loop does."""
+        if weighting not in capi.REFINE_WEIGHTINGS:
+            raise ValueError(f"weighting must be one of {sorted(capi.REFINE_WEIGHTINGS)}, got {weighting!r}")
+        self._drain()
+        s, a, r, rtg, ret = self._split(trajectory)
+        cfg = self.cfg
+        N, A = int(cfg.action_samples), self.A
+        mode = capi.MODE_CRITIC if cfg.plan_guidance == "critic_lambda_guiding" else capi.MODE_RTG
+        lmbda = 0.6 if mode == capi.MODE_RTG else float(cfg.lmbda)
+        k = min(int(top_k), N)
+        seed = step = 0
+        if noise is None:
+            if self._variates == "library":
+                seed, step, self._step_index = self._seed, self._step_index, self._step_index + 1
+            else:
+                noise = self._eps((iterations + 1, N, h, A))
+        else:
+            noise = noise.to(self.device, torch.float32).contiguous()
+        tau = float(cfg.temperature) if temperature is None else float(temperature)
+        res = self.handle.refine_plan(mode, s, a, r, h, rtg, lmbda, float(cfg.discount), N, iterations=iterations, top_k=k,
+                                      weighting=capi.REFINE_WEIGHTINGS[weighting], temperature=tau, init_std=init_std, min_std=min_std,
+                                      noise=noise, seed=seed, step=step, init_mean=init_mean, precision=self.precision, returns=ret)
+        self._mark_main()
+        trace = [dict(expect_return=res["scores"][it], top=res["elites"][it], mean=res["mean"][it + 1], std=res["std"][it + 1])
+                 for it in range(iterations)]
+        self.last = dict(cem=trace, candidates=res["candidates"])
+        return res["sample_action"], res["eval_action"]
