@@ -4,7 +4,7 @@
  * exports none of these and reads no environment variable; the lab build additionally honours the
  * A/B switches M3PC_NO_* / M3PC_GEMM_VARIANT / M3PC_TWO_STREAM / ... listed in DESIGN.md section 7.
  * Users: tests/test_gemm_kernels_gpu.py, tests/test_gemm_edges_gpu.py, tests/test_bf16x3_gpu.py, tests/test_attention_gpu.py,
- * tests/test_block_fused_gpu.py, tools/*.py.
+ * tests/test_block_fused_gpu.py, tests/test_block_edges_gpu.py, tests/test_block_ref_cpu.py, tools/*.py.
  */
 #ifndef M3PC_HIP_DEBUG_H
 #define M3PC_HIP_DEBUG_H
@@ -116,11 +116,114 @@ int m3pc_debug_block_fused_heads(const void* O, int M, const float* rowtab, int 
                                  const float* lnB_g1, const float* lnB_b1, int out_mod, int out_grp, const float* hb1, const float* hw2,
                                  const float* hb2, const float* hmean, const float* hstd, float* out0, float* out1, void* stream,
                                  long long* stamps);
+/* one launch of the fused layer tail with everything a production call can pass (BlockP, csrc/kernels.h), through
+ * launch_block_fused's checks and dispatch; the weight stream is packed inside the call (Wo (512, 512), W1 (2048, 512), W2 (512, 2048),
+ * optional Wqkv (1536, 512) or Wh (2, 512, 512): bf16, torch Linear layout; stream_buf: m3pc_debug_block_stream_bytes() bytes on 1 KiB).
+ *     X'  = residual(r) + bo + O[r] Wo^T          residual(r): res[r] (ldr; bf16 rows when x_bf16); with res_L > 0 the rows come in
+ *                                                 sequences of res_L and row j < res_nshared of every sequence is read from sequence 0;
+ *                                                 with rowtab: rowtab[w], w = r % rt_mod, and for w < res_nu the row of its own stored
+ *                                                 behind the table, rowtab[rt_mod + (r / rt_mod) res_nu + w]
+ *     X'' = X' + b2 + gelu(LN2(X') W1^T + b1) W2^T     -> Xout (ldx; fp32, bf16 when x_bf16; may be res)
+ *     Hout[orow(r)] = bf16(LN_B[s]?(LN_A(X'')))   (ldh) out_mod > 0: s = (r % out_mod) / out_grp, orow = s (M / out_mod) out_grp +
+ *                                                 (r / out_mod) out_grp + r % out_grp; out_mod 0 with lnB_g[0]: LN_B[0] for every row
+ *     QKVout[r] = bf16(bf16(LN_A(X'')) Wqkv^T + bqkv)  (ldq >= 1536; qkv_bytes: the size of the buffer, stores behind it are dropped)
+ *     head_out[s][i] = detok(hw2_s . gelu(Wh_s bf16(LN_B[s](LN_A(X''))) + hb1_s) + hb2_s) for the i-th row of group s (hb1 / hw2
+ *                                                 (2, 512), hb2 / hmean / hstd (2) floats; hmean null: no de-tokenisation)
+ * split: four workgroups per tile write fp32 partials to the block_split_n() = 4 slabs of M rows behind Xout (ldx 512), and
+ * block_split_reduce_kernel follows: red_Xout (red_ldx) = their sum, red_Hout (red_ldh) = bf16(LN_B?(LN_A(sum))) with red_lnA_* /
+ * red_lnB_* / red_out_mod / red_out_grp as above.
+ * Refused with M3PC_EINVAL before anything is launched: whatever block_fused_accepts refuses (tests/test_block_ref_cpu.py lists the
+ * refusals), a missing weight the form needs, and reduce arguments block_split_reduce_kernel does not cover (red_ldx % 4, red_ldh % 8,
+ * red_Hout without red_lnA_*, red_out_mod != 2 red_out_grp or not dividing M, neither output).
+ * picked (1 int, optional): the instance launched.  Block forms (tests/test_block_edges_gpu.py reaches every value of this list):
+ *   0 block_fused_kernel<0, 0>;  1 block_fused_kernel<0, 1> (next Q|K|V);  2 block_fused_kernel<0, 2> (heads);
+ *   3 block_fused_kernel<0, 3> + block_split_reduce_kernel;  16 block_fused_kernel<0, 0, 1>;  17 block_fused_kernel<0, 1, 1>
+ * (the timing variants DBG 1..7 compute wrong results by design and are not reachable through this hook) */
+typedef struct m3pc_debug_block_args {
+    const void* O;
+    int ldo;
+    int M;
+    const void* res; /* fp32 rows, bf16 rows when x_bf16; or rowtab */
+    int ldr;
+    int res_L, res_nshared;
+    const float* rowtab;
+    int rt_mod, res_nu;
+    const void* Wo;
+    const void* W1;
+    const void* W2;
+    const void* Wqkv; /* optional: with QKVout */
+    const void* Wh;   /* optional: with head_out */
+    void* stream_buf;
+    const float* bo;
+    const float* b1;
+    const float* b2;
+    const float* ln2_g;
+    const float* ln2_b;
+    const float* lnA_g;
+    const float* lnA_b;
+    const float* lnB_g[2];
+    const float* lnB_b[2];
+    void* Xout; /* optional; with split: the slabs */
+    int ldx;
+    int x_bf16;
+    void* Hout; /* optional */
+    int ldh;
+    int out_mod, out_grp;
+    void* QKVout; /* optional */
+    int ldq;
+    long long qkv_bytes;
+    const float* bqkv;
+    const float* hb1;
+    const float* hw2;
+    const float* hb2;
+    const float* hmean; /* optional */
+    const float* hstd;
+    float* head_out[2]; /* optional */
+    int split;
+    float* red_Xout; /* optional */
+    int red_ldx;
+    void* red_Hout; /* optional */
+    int red_ldh;
+    const float* red_lnA_g;
+    const float* red_lnA_b;
+    const float* red_lnB_g[2];
+    const float* red_lnB_b[2];
+    int red_out_mod, red_out_grp;
+    void* stream;
+    int* picked; /* optional: 1 int */
+} m3pc_debug_block_args;
+int m3pc_debug_block_ex(const m3pc_debug_block_args* a);
+/* the same checks without packing or launching anything (no GPU needed): the refusals, and `picked` as m3pc_debug_block_ex reports it */
+int m3pc_debug_block_accepts(const m3pc_debug_block_args* a);
+int m3pc_debug_block_split_n(void);
 /* the fused decoder input (kv_fused_kernel) on caller tensors */
 long long m3pc_debug_kv_stream_bytes(void);
 int m3pc_debug_kv_fused(const void* Z, int n, int Le, int kept0, int off0, int kept1, int off1, const void* We0, const void* We1,
                         const void* Wkv, void* stream_buf, const float* rowtab0, const float* rowtab1, const float* ln_g,
                         const float* ln_b, const float* bkv, void* KV, void* stream, long long* stamps);
+/* the same with everything KvFusedP carries: group g holds M[g] rows (0: absent; group 1 only with group 0), its row r is row
+ * (r / rpg) gstride + r % rpg + off of Z (ldz) and of KV (ldkv) under map[g] = {rpg, gstride, off} (rpg 0: identity), embedded with
+ * We[g] (512, 512) bf16 + rowtab[g][r % rt_mod[g]]; Wkv (1024, 512) bf16; stream_buf: 2 * m3pc_debug_kv_stream_bytes() bytes.
+ * kv_bytes: the size of the KV buffer from its base (stores behind it are dropped).  Refusals: launch_kv_fused's. */
+typedef struct m3pc_debug_kv_args {
+    const void* Z;
+    int ldz;
+    int M[2];
+    int map[2][3];
+    const float* rowtab[2];
+    int rt_mod[2];
+    const void* We[2];
+    const void* Wkv;
+    void* stream_buf;
+    const float* ln_g;
+    const float* ln_b;
+    const float* bkv;
+    void* KV;
+    int ldkv;
+    long long kv_bytes;
+    void* stream;
+} m3pc_debug_kv_args;
+int m3pc_debug_kv_fused_ex(const m3pc_debug_kv_args* a);
 /* the bf16 attention of an encoder layer of the candidate pass on caller tensors: QKV (batch, n_own, 1536) per-candidate rows
  * [Q | K | V] and, when n_sh > 0, QKVs (n_sh, 1536) rows shared by the batch (first layer: history tokens); O (batch, n_own + n_sh, 512),
  * shared rows first.  4 heads of 128.  kernel: 0 = what the library picks, 1 = never the pipelined kernel, 2 / 3 = the pipelined kernel

@@ -1546,6 +1546,7 @@ bool block_fused_accepts(const BlockP& p) {
     }
     if (p.split) {  // four workgroups per tile, fp32 partials to four slabs of M rows behind Xout (block_split_reduce sums them)
         if (p.Hout || p.QKVout || p.head_out[0] || !p.Xout || p.Xout == p.res || p.res_L > 0) return false;
+        if (p.ldx != BD) return false;  // (block_split_reduce reads the slabs as rows of 512 floats)
     }
     if (p.x_bf16) {  // bf16 residual rows in, bf16 X'' rows out: whole 128-byte lines of 64 features
         if (p.rowtab || p.split || p.head_out[0] || p.res_L > 0 || p.variant || !p.res) return false;
@@ -1553,6 +1554,15 @@ bool block_fused_accepts(const BlockP& p) {
         if (p.Xout && ((p.ldx % 8) || (unsigned long long)p.M * p.ldx * 2 >= 0x80000000ull)) return false;
     }
     return true;
+}
+
+// The instance launch_block_fused launches for accepted arguments: 0 plain, 1 next-Q|K|V, 2 heads, 3 split; + 16: bf16 residual rows
+int block_fused_form(const BlockP& p) {
+    if (p.x_bf16) return p.QKVout ? 17 : 16;
+    if (p.split) return 3;
+    if (p.QKVout) return 1;
+    if (p.head_out[0]) return 2;
+    return 0;
 }
 
 bool launch_block_fused(const BlockP& p, hipStream_t st) {
@@ -1569,12 +1579,14 @@ bool launch_block_fused(const BlockP& p, hipStream_t st) {
     else if (p.variant == 7) hipLaunchKernelGGL((block_fused_kernel<7, 0>), grid, block, 0, st, p);
     else
 #endif
-    if (p.x_bf16 && p.QKVout) hipLaunchKernelGGL((block_fused_kernel<0, 1, 1>), grid, block, 0, st, p);
-    else if (p.x_bf16) hipLaunchKernelGGL((block_fused_kernel<0, 0, 1>), grid, block, 0, st, p);
-    else if (p.split) hipLaunchKernelGGL((block_fused_kernel<0, 3>), dim3((p.M + 127) / 128, SPLIT_N), block, 0, st, p);
-    else if (p.QKVout) hipLaunchKernelGGL((block_fused_kernel<0, 1>), grid, block, 0, st, p);
-    else if (p.head_out[0]) hipLaunchKernelGGL((block_fused_kernel<0, 2>), dim3(2 * ((p.M / 2 + 127) / 128)), block, 0, st, p);
-    else hipLaunchKernelGGL((block_fused_kernel<0, 0>), grid, block, 0, st, p);
+    switch (block_fused_form(p)) {
+        case 17: hipLaunchKernelGGL((block_fused_kernel<0, 1, 1>), grid, block, 0, st, p); break;
+        case 16: hipLaunchKernelGGL((block_fused_kernel<0, 0, 1>), grid, block, 0, st, p); break;
+        case 3: hipLaunchKernelGGL((block_fused_kernel<0, 3>), dim3((p.M + 127) / 128, SPLIT_N), block, 0, st, p); break;
+        case 1: hipLaunchKernelGGL((block_fused_kernel<0, 1>), grid, block, 0, st, p); break;
+        case 2: hipLaunchKernelGGL((block_fused_kernel<0, 2>), dim3(2 * ((p.M / 2 + 127) / 128)), block, 0, st, p); break;
+        default: hipLaunchKernelGGL((block_fused_kernel<0, 0>), grid, block, 0, st, p); break;
+    }
     return true;
 }
 

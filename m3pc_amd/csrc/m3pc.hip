@@ -2219,6 +2219,121 @@ int m3pc_debug_block_fused_heads(const void* O, int M, const float* rowtab, int 
     return check_launch("debug_block_fused_heads");
 }
 
+// the fused layer tail with everything BlockP carries (include/m3pc_hip_debug.h)
+static int debug_block_fill(const m3pc_debug_block_args* a, BlockP& b, SplitReduceP& r) {
+    if (!a) return fail(M3PC_EINVAL, "debug_block: null arguments");
+    memset(&b, 0, sizeof(b));
+    memset(&r, 0, sizeof(r));
+    if (a->picked) a->picked[0] = 0;
+    if (a->M <= 0) return fail(M3PC_EINVAL, "debug_block: M = %d", a->M);
+    if (!a->O || !a->Wo || !a->W1 || !a->W2 || !a->stream_buf || !a->bo || !a->b1 || !a->b2 || !a->ln2_g || !a->ln2_b)
+        return fail(M3PC_EINVAL, "debug_block: O, the layer's weights, biases, norm2 and the stream buffer are required");
+    if (!a->res && !a->rowtab) return fail(M3PC_EINVAL, "debug_block: neither res nor rowtab");
+    if (a->rowtab && a->rt_mod < 1) return fail(M3PC_EINVAL, "debug_block: rowtab with rt_mod %d", a->rt_mod);
+    if (a->res_L < 0 || a->res_nshared < 0) return fail(M3PC_EINVAL, "debug_block: res_L / res_nshared below 0");
+    if ((a->Hout || a->head_out[0]) && !a->lnA_g) return fail(M3PC_EINVAL, "debug_block: Hout / heads without lnA");
+    if (a->lnA_g && !a->lnA_b) return fail(M3PC_EINVAL, "debug_block: lnA_g without lnA_b");
+    for (int s = 0; s < 2; ++s)
+        if ((a->lnB_g[s] != nullptr) != (a->lnB_b[s] != nullptr)) return fail(M3PC_EINVAL, "debug_block: lnB_g / lnB_b come in pairs");
+    if (a->lnB_g[0] && !a->lnB_g[1]) return fail(M3PC_EINVAL, "debug_block: lnB is two pairs (the kernel's tables hold two)");
+    if (a->out_mod < 0 || (a->out_mod > 0 && (a->out_grp < 1 || !a->lnB_g[0]))) return fail(M3PC_EINVAL, "debug_block: out_mod / out_grp / lnB");
+    if (a->QKVout && !a->Wqkv) return fail(M3PC_EINVAL, "debug_block: QKVout without Wqkv");
+    if (a->head_out[0] && (!a->Wh || !a->hb1 || !a->hw2 || !a->hb2)) return fail(M3PC_EINVAL, "debug_block: heads without their weights");
+    if (a->Wqkv && a->Wh) return fail(M3PC_EINVAL, "debug_block: Wqkv and Wh share the stream's tail");
+    if (a->qkv_bytes < 0 || a->qkv_bytes > 0xffffffffll) return fail(M3PC_EINVAL, "debug_block: qkv_bytes");
+    b.O = (const bf16_t*)a->O;
+    b.ldo = a->ldo;
+    b.M = a->M;
+    b.res = (const float*)a->res;
+    b.ldr = a->ldr;
+    b.res_L = a->res_L;
+    b.res_nshared = a->res_nshared;
+    b.rowtab = a->rowtab;
+    b.rt_mod = a->rt_mod;
+    b.res_nu = a->res_nu;
+    b.wstream = (const bf16_t*)a->stream_buf;
+    b.bo = a->bo;
+    b.b1 = a->b1;
+    b.b2 = a->b2;
+    b.ln2_g = a->ln2_g;
+    b.ln2_b = a->ln2_b;
+    b.Xout = (float*)a->Xout;
+    b.ldx = a->ldx;
+    b.x_bf16 = a->x_bf16 ? 1 : 0;
+    b.lnA_g = a->lnA_g;
+    b.lnA_b = a->lnA_b;
+    for (int s = 0; s < 2; ++s) {
+        b.lnB_g[s] = a->lnB_g[s];
+        b.lnB_b[s] = a->lnB_b[s];
+    }
+    b.out_mod = a->out_mod;
+    b.out_grp = a->out_grp;
+    b.Hout = (bf16_t*)a->Hout;
+    b.ldh = a->ldh;
+    b.QKVout = (bf16_t*)a->QKVout;
+    b.ldq = a->ldq;
+    b.qkv_bytes = (unsigned)a->qkv_bytes;
+    b.bqkv = a->bqkv;
+    for (int s = 0; s < 2; ++s) {
+        b.head_out[s] = a->head_out[s];
+        if (!a->head_out[0]) continue;
+        b.hb1[s] = a->hb1 + 512 * s;
+        b.hw2[s] = a->hw2 + 512 * s;
+        b.hb2[s] = a->hb2 + s;
+        b.hmean[s] = a->hmean ? a->hmean + s : nullptr;
+        b.hstd[s] = a->hstd ? a->hstd + s : nullptr;
+    }
+    b.split = a->split ? 1 : 0;
+    if (!block_fused_accepts(b)) return fail(M3PC_EINVAL, "debug_block: arguments not covered (block_fused_accepts)");
+    if (b.split) {
+        r.slabs = (const float*)a->Xout;
+        r.M = a->M;
+        r.Xout = a->red_Xout;
+        r.ldx = a->red_ldx;
+        r.lnA_g = a->red_lnA_g;
+        r.lnA_b = a->red_lnA_b;
+        for (int s = 0; s < 2; ++s) {
+            r.lnB_g[s] = a->red_lnB_g[s];
+            r.lnB_b[s] = a->red_lnB_b[s];
+        }
+        r.out_mod = a->red_out_mod;
+        r.out_grp = a->red_out_grp;
+        r.Hout = (bf16_t*)a->red_Hout;
+        r.ldh = a->red_ldh;
+        if (!r.Xout && !r.Hout) return fail(M3PC_EINVAL, "debug_block: the reduce has no output");
+        if (r.Xout && (((uintptr_t)r.Xout & 15) || r.ldx < 512 || (r.ldx % 4))) return fail(M3PC_EINVAL, "debug_block: red_Xout / red_ldx");
+        if (r.Hout && (((uintptr_t)r.Hout & 15) || r.ldh < 512 || (r.ldh % 8) || !r.lnA_g || !r.lnA_b)) return fail(M3PC_EINVAL, "debug_block: red_Hout / red_ldh / red_lnA");
+        if ((r.lnB_g[0] != nullptr) != (r.lnB_b[0] != nullptr) || (r.lnB_g[0] && r.out_mod > 0 && (!r.lnB_g[1] || !r.lnB_b[1])))
+            return fail(M3PC_EINVAL, "debug_block: red_lnB");
+        if (r.out_mod < 0 || (r.out_mod > 0 && (!r.lnB_g[0] || r.out_mod != 2 * r.out_grp || a->M % r.out_mod != 0)))
+            return fail(M3PC_EINVAL, "debug_block: red_out_mod / red_out_grp");
+    }
+    if (a->picked) a->picked[0] = block_fused_form(b);
+    return 0;
+}
+int m3pc_debug_block_split_n(void) { return block_split_n(); }
+int m3pc_debug_block_accepts(const m3pc_debug_block_args* a) {
+    BlockP b;
+    SplitReduceP r;
+    return debug_block_fill(a, b, r);
+}
+int m3pc_debug_block_ex(const m3pc_debug_block_args* a) {
+    BlockP b;
+    SplitReduceP r;
+    const int rc = debug_block_fill(a, b, r);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)a->stream;
+    launch_pack_block_stream((const bf16_t*)a->Wo, (const bf16_t*)a->W1, (const bf16_t*)a->W2, (bf16_t*)a->stream_buf, st);
+    if (a->Wqkv) launch_pack_block_qkv((const bf16_t*)a->Wqkv, (bf16_t*)a->stream_buf, st);
+    if (a->Wh) launch_pack_block_heads((const bf16_t*)a->Wh, (const bf16_t*)a->Wh + 512 * 512, (bf16_t*)a->stream_buf, st);
+    if (!launch_block_fused(b, st)) {
+        if (a->picked) a->picked[0] = 0;
+        return fail(M3PC_EINVAL, "debug_block: arguments not covered");
+    }
+    if (b.split) launch_block_split_reduce(r, st);
+    return check_launch("debug_block_ex");
+}
+
 // kv_fused_kernel alone (tests/test_block_fused_gpu.py): n candidates of Le rows each in Z (n*Le, 512) bf16; group g holds
 // the kept[g] rows at offset off[g] of every candidate, embedded with We[g] (512, 512) bf16 + rowtab[g] (kept[g], 512);
 // stream_buf: 2 * m3pc_debug_kv_stream_bytes() bytes; KV (n*Le, 1024) bf16
@@ -2452,6 +2567,36 @@ int m3pc_debug_kv_fused(const void* Z, int n, int Le, int kept0, int off0, int k
     p.stamps = stamps;
     if (!launch_kv_fused(p, st)) return fail(M3PC_EINVAL, "kv_fused: arguments not covered");
     return check_launch("debug_kv_fused");
+}
+
+int m3pc_debug_kv_fused_ex(const m3pc_debug_kv_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_kv: null arguments");
+    if (!a->Z || !a->Wkv || !a->stream_buf || !a->ln_g || !a->ln_b || !a->bkv || !a->KV) return fail(M3PC_EINVAL, "debug_kv: a required pointer is null");
+    if (a->kv_bytes <= 0 || a->kv_bytes > 0xffffffffll) return fail(M3PC_EINVAL, "debug_kv: kv_bytes");
+    hipStream_t st = (hipStream_t)a->stream;
+    KvFusedP p;
+    memset(&p, 0, sizeof(p));
+    p.Z = (const bf16_t*)a->Z;
+    p.ldz = a->ldz;
+    for (int g = 0; g < 2; ++g) {
+        p.M[g] = a->M[g];
+        if (a->map[g][0] < 0 || a->map[g][2] < 0 || (a->map[g][0] > 0 && a->map[g][1] < a->map[g][0])) return fail(M3PC_EINVAL, "debug_kv: row map of group %d", g);
+        p.map[g] = RowMap{a->map[g][0], a->map[g][1], a->map[g][2]};
+        p.rowtab[g] = a->rowtab[g];
+        p.rt_mod[g] = a->rt_mod[g];
+        p.wstream[g] = (const bf16_t*)((char*)a->stream_buf + g * kv_stream_bytes());
+        if (a->M[g] > 0 && !a->We[g]) return fail(M3PC_EINVAL, "debug_kv: group %d without its embedding weights", g);
+    }
+    p.ln_g = a->ln_g;
+    p.ln_b = a->ln_b;
+    p.bkv = a->bkv;
+    p.KV = (bf16_t*)a->KV;
+    p.ldkv = a->ldkv;
+    p.kv_bytes = (unsigned)a->kv_bytes;
+    for (int g = 0; g < 2; ++g)
+        if (a->M[g] > 0) launch_pack_kv_stream((const bf16_t*)a->We[g], (const bf16_t*)a->Wkv, (bf16_t*)p.wstream[g], st);
+    if (!launch_kv_fused(p, st)) return fail(M3PC_EINVAL, "kv_fused: arguments not covered");
+    return check_launch("debug_kv_fused_ex");
 }
 
 // which XCD (and CU) every workgroup of a launch on `stream` lands on: out[2 i] = XCC_ID, out[2 i + 1] = HW_ID register
