@@ -4,7 +4,8 @@
  * exports none of these and reads no environment variable; the lab build additionally honours the
  * A/B switches M3PC_NO_* / M3PC_GEMM_VARIANT / M3PC_TWO_STREAM / ... listed in DESIGN.md section 7.
  * Users: tests/test_gemm_kernels_gpu.py, tests/test_gemm_edges_gpu.py, tests/test_bf16x3_gpu.py, tests/test_attention_gpu.py,
- * tests/test_block_fused_gpu.py, tests/test_block_edges_gpu.py, tests/test_block_ref_cpu.py, tools/*.py.
+ * tests/test_block_fused_gpu.py, tests/test_block_edges_gpu.py, tests/test_block_ref_cpu.py, tests/test_lockstep_kernels_gpu.py,
+ * tools/*.py.
  */
 #ifndef M3PC_HIP_DEBUG_H
 #define M3PC_HIP_DEBUG_H
@@ -96,6 +97,56 @@ int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream);
  * Synchronises the stream. */
 int m3pc_debug_calibrate_stats(const float* scores_low, const float* f32, int n, float factor, float* stats, float* delta_out,
                                void* stream);
+/* ---- the tail of a lock-step batch of certified plan steps (csrc/select.hip), each kernel alone on caller device arrays.  Every
+ * kernel takes its window from the grid and runs the device functions of the one-window kernels: window w's results are those of
+ * the one-window entry points on row w, bit for bit (tests/test_lockstep_kernels_gpu.py).
+ * The lists of n_windows windows in one launch: scores / expo (n_windows, n_total); per window the layout of m3pc_topk_race_window,
+ * list[w][rmax + i] = the i-th best by score (i < min(kmax + 1, n_total)), list[w][rmax - 1 - i] = the i-th best by race key (i < rmax),
+ * rows of rmax + kmax + 1 entries, list_scores (optional) in the same layout; rmax 0: m3pc_topk_window's list (expo unused).
+ * Descending, ties to the lower index.  n_total <= 16384, kmax <= 1023, rmax <= min(64, n_total). */
+int m3pc_debug_topk_race_batch(const float* scores, const float* expo, float temperature, int n_windows, int n_total, int kmax, int kmin,
+                               int rmax, int* list, float* list_scores, void* stream);
+/* what the lists name, for one m3pc_score_actions call: cand[w m + i] = sample_actions[w][list[w][lo + i]] (rows of row_floats = h A
+ * floats; sample_actions (n_windows, n_total, row_floats), list rows of list_stride entries) and window_index[w m + i] = w (int32,
+ * optional), m = hi - lo, window-major.  An entry outside [0, n_total) leaves its row of cand untouched. */
+int m3pc_debug_gather_listed(const float* sample_actions, const int* list, int n_windows, int n_total, int row_floats, int list_stride,
+                             int lo, int hi, float* cand, int* window_index, void* stream);
+/* merge + certificate statistics + select of n_windows windows in one launch: m3pc_merge_race_select per window (race != 0), or
+ * m3pc_rescore_merge followed by m3pc_select (race == 0: r[w] = 0, four statistics, expo optional and used by the select alone);
+ * select == 0: the merge alone.  Window w uses r[w] race and n[w] score entries, the slice [rmax - r[w], rmax + n[w]) of its list and
+ * list_scores (rows of list_stride), their fp32 re-scores list_rescored[w f_stride + j - f_lo] for list position j (f_stride =
+ * list_stride and f_lo = 0: the list's layout), and delta[w]; r / n / delta are HOST arrays.  scores / expo / merged / p
+ * (n_windows, n_total); stats (n_windows, 8) device; host_stats (optional): n_windows blocks of 8 floats a kernel can store to, each
+ * closed by seq in slot 4, written last at system scope; a0: window w's first actions at a0 + w a0_window_stride, candidate j's at
+ * + j a0_stride (A floats); eval_action / sample_action (n_windows, A), argmax / sample_idx (n_windows,) int32, each optional. */
+typedef struct m3pc_debug_tail_args {
+    const float* scores;
+    const float* expo;
+    int race, select;
+    float temperature;
+    int n_windows, n_total;
+    const int* list;
+    const float* list_scores;
+    const float* list_rescored;
+    int rmax, list_stride, f_stride, f_lo;
+    const int* r;       /* host */
+    const int* n;       /* host */
+    const float* delta; /* host */
+    float* merged;
+    float* stats;
+    float* host_stats;
+    float seq;
+    const float* a0;
+    long long a0_window_stride, a0_stride;
+    int A;
+    float* p;
+    float* eval_action;
+    int* argmax;
+    int* sample_idx;
+    float* sample_action;
+    void* stream;
+} m3pc_debug_tail_args;
+int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a);
 /* the fused layer tail (block_fused.hip) on caller tensors; see csrc/m3pc.hip for the argument layout */
 long long m3pc_debug_block_stream_bytes(void);
 int m3pc_debug_block_fused(const void* O, int M, const float* res, const float* rowtab, int rt_mod, const void* Wo, const void* W1,

@@ -483,6 +483,47 @@ void launch_rescore_merge(const float* b, int n_total, const int* list, int r, i
 void launch_merge_select(const float* b, int n_total, const int* list, int r, int n, const float* list_scores, const float* f,
                          float delta, const float* expo, float tau, float* out, float* stats, float* host_stats, float seq,
                          const SelectP& sp, hipStream_t st);
+// ---- the same tail for E lock-step windows, one launch each (select.hip; the one-window device functions, a window per grid index)
+// launch_topk_race over row w of v / expo (E, n) with row stride v_stride into list w / list_scores w (list_stride entries each);
+// false: n > 8192 and the device refused the LDS for the keys (nothing launched)
+bool launch_topk_race_batch(const float* v, const float* expo, float tau, int E, int n, long long v_stride, int kk, int rr, int rmax,
+                            int* list, float* list_scores, int list_stride, hipStream_t st);
+// cand (E m, row) = sample_actions (E, n_total, row)[w, list_w[lo + i]], window_index (E m,) = w (optional), window-major
+void launch_gather_listed(const float* sa, int E, int n_total, int row, const int* list, int list_stride, int lo, int m, float* cand,
+                          int* window_index, hipStream_t st);
+// launch_merge_select / launch_rescore_merge per window: window w takes r[w] race and n[w] score entries -- the slice
+// [rmax - r[w], rmax + n[w]) of its list and list_scores -- and their fp32 re-scores f[w f_stride + j - f_lo] for list position j
+// (f_stride = list_stride, f_lo = 0: f in the list's layout; f_stride = m, f_lo = the first listed position: the rows a
+// launch_gather_listed slice was scored into).  race: the merge takes expo (8 statistics), else 4; select: select_body on the merged
+// row (expo optional then).  stats / host_stats: 8 floats per window; every host block ends with seq in slot 4, written last.
+struct MergeSelectBatchP {
+    const float* b;        // (E, n_total) low-precision scores, row stride row_stride (also of expo, out, p)
+    const float* expo;     // (E, n_total), required with race
+    long long row_stride;
+    int n_total, race, select;
+    float tau;
+    const int* list;
+    const float* list_scores;
+    int list_stride, rmax;
+    const float* f;
+    int f_stride, f_lo;
+    float* out;            // (E, n_total) merged
+    float* stats;          // (E, 8) device
+    float* host_stats;     // optional (E, 8) host-mapped
+    float seq;
+    const float* a0;       // window w: a0 + w a0_wstride, candidate j: + j a0_stride
+    long long a0_wstride, a0_stride;
+    int A;
+    float* p;              // optional (E, n_total)
+    float* eval_action;    // optional (E, A)
+    int* argmax;           // optional (E,)
+    int* sample_idx;       // optional (E,)
+    float* sample_action;  // optional (E, A)
+    int w0;                // (set by the launcher)
+    int r[64], n[64];
+    float delta[64];
+};
+void launch_merge_select_batch(MergeSelectBatchP& P, int E, const int* r, const int* n, const float* delta, hipStream_t st);
 // calibration statistics over all n <= 16384 candidates (one workgroup): d = b - f, c = lower median of d (value, then index);
 // stats (8 floats) = {c, max |d - c|, max |f|, 0, -, 0, 0, 0}; host_stats / seq as launch_rescore_merge
 void launch_deviation_stats(const float* b, const float* f, int n, float* stats, float* host_stats, float seq, hipStream_t st);

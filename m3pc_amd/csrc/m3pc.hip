@@ -2092,6 +2092,80 @@ int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream) {
     return check_launch("debug_topk");
 }
 
+// Not part of the public header (tests/test_lockstep_kernels_gpu.py): the three kernels of a lock-step batch's tail, each alone on
+// caller arrays.  The checks are those of the one-window entry points, per window.
+int m3pc_debug_topk_race_batch(const float* scores, const float* expo, float temperature, int n_windows, int n_total, int kmax, int kmin,
+                               int rmax, int* list, float* list_scores, void* stream) {
+    if (!scores || !list || (rmax > 0 && !expo)) return fail(M3PC_EINVAL, "null argument");
+    if (n_windows < 1 || n_windows > 65535) return fail(M3PC_EINVAL, "n_windows %d outside [1, 65535]", n_windows);
+    if (n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "top-k supports n_total <= 16384");
+    if (kmax < 1 || kmax > 1023 || kmin < 1 || kmin > kmax) return fail(M3PC_EINVAL, "bad kmin/kmax");
+    if (rmax < 0 || rmax > 64 || rmax > n_total) return fail(M3PC_EINVAL, "rmax %d outside [0, min(64, n_total)]", rmax);
+    const int kk = kmax + 1 < n_total ? kmax + 1 : n_total;
+    if (!launch_topk_race_batch(scores, expo, temperature, n_windows, n_total, n_total, kk, rmax, rmax, list, list_scores,
+                                rmax + kmax + 1, (hipStream_t)stream))
+        return fail(M3PC_ENOMEM, "the device refused the LDS for the keys of %d candidates", n_total);
+    return check_launch("debug_topk_race_batch");
+}
+int m3pc_debug_gather_listed(const float* sample_actions, const int* list, int n_windows, int n_total, int row_floats, int list_stride,
+                             int lo, int hi, float* cand, int* window_index, void* stream) {
+    if (!sample_actions || !list || !cand) return fail(M3PC_EINVAL, "null argument");
+    if (n_windows < 1 || n_total < 1 || row_floats < 1) return fail(M3PC_EINVAL, "bad sizes");
+    if (lo < 0 || hi < lo || hi > list_stride) return fail(M3PC_EINVAL, "slice [%d, %d) outside the list of %d", lo, hi, list_stride);
+    if ((long long)n_windows * (hi - lo) > 0x7fffffffLL) return fail(M3PC_EINVAL, "too many rows");
+    launch_gather_listed(sample_actions, n_windows, n_total, row_floats, list, list_stride, lo, hi - lo, cand, window_index,
+                         (hipStream_t)stream);
+    return check_launch("debug_gather_listed");
+}
+int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a) {
+    if (!a || !a->scores || !a->list || !a->list_scores || !a->list_rescored || !a->merged || !a->stats || !a->r || !a->n || !a->delta)
+        return fail(M3PC_EINVAL, "null argument");
+    if (a->race && !a->expo) return fail(M3PC_EINVAL, "race needs expo");
+    if (a->n_windows < 1 || a->n_total < 1 || a->n_total > 16384) return fail(M3PC_EINVAL, "bad sizes");
+    if (a->rmax < 0 || a->rmax > 64 || a->list_stride < a->rmax + 1 || a->f_lo < 0 || a->f_stride < 1)
+        return fail(M3PC_EINVAL, "bad list layout");
+    if (a->select && (a->eval_action || a->sample_action) && (!a->a0 || a->A < 1 || a->A > 1024))
+        return fail(M3PC_EINVAL, "eval_action / sample_action need a0");
+    for (int w = 0; w < a->n_windows; ++w) {
+        const int r = a->r[w], n = a->n[w];
+        if (n < 1 || r < 0 || r + n > 1024 || n > a->n_total || r > a->n_total || r > a->rmax || (!a->race && r != 0) ||
+            n > a->list_stride - a->rmax || a->rmax - r < a->f_lo || a->rmax + n - a->f_lo > a->f_stride)
+            return fail(M3PC_EINVAL, "window %d: r %d + n %d outside the list / [1, 1024] / n_total %d", w, r, n, a->n_total);
+        if (!(a->delta[w] >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
+    }
+    MergeSelectBatchP P;
+    memset(&P, 0, sizeof(P));
+    P.b = a->scores;
+    P.expo = a->expo;
+    P.row_stride = a->n_total;
+    P.n_total = a->n_total;
+    P.race = a->race;
+    P.select = a->select;
+    P.tau = a->temperature;
+    P.list = a->list;
+    P.list_scores = a->list_scores;
+    P.list_stride = a->list_stride;
+    P.rmax = a->rmax;
+    P.f = a->list_rescored;
+    P.f_stride = a->f_stride;
+    P.f_lo = a->f_lo;
+    P.out = a->merged;
+    P.stats = a->stats;
+    P.host_stats = a->host_stats;
+    P.seq = a->seq;
+    P.a0 = a->a0;
+    P.a0_wstride = a->a0_window_stride;
+    P.a0_stride = a->a0_stride;
+    P.A = a->A;
+    P.p = a->p;
+    P.eval_action = a->eval_action;
+    P.argmax = a->argmax;
+    P.sample_idx = a->sample_idx;
+    P.sample_action = a->sample_action;
+    launch_merge_select_batch(P, a->n_windows, a->r, a->n, a->delta, (hipStream_t)a->stream);
+    return check_launch("debug_merge_select_batch");
+}
+
 // Not part of the public header (tests/test_block_fused_gpu.py, tools/block_bench.py): the fused layer tail on its own.
 //   O (M,512) bf16; res (M,512) fp32 or rowtab (rt_mod,512); Wo (512,512), W1 (2048,512), W2 (512,2048) bf16 in torch
 //   Linear layout; stream: scratch of m3pc_debug_block_stream_bytes() bytes (packed when pack != 0);

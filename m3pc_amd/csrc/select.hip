@@ -263,10 +263,7 @@ __global__ __launch_bounds__(256) void topk_rank_blocks2_kernel(TopSrc s0, TopSr
 // the keys of ALL n elements in dynamic LDS (8 n bytes: 32 KB at 4096, 128 KB at 16384), 64 elements per block ranked by 256
 // threads, a quarter of the keys each.  One launch of ~10-20 us where the selection kernel needs k rounds of butterflies in a
 // single workgroup (~60 us for the 32 racers) and the 129 best by score a whole bitonic sort.
-__global__ __launch_bounds__(256) void topk_rank_blocks2_dyn_kernel(TopSrc s0, TopSrc s1, int n, int n4) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long dkeys[];  // 4 * n4 entries
-    __shared__ int part[4][64];
-    const TopSrc s = blockIdx.y ? s1 : s0;
+__device__ __forceinline__ void rank_blocks_dyn_body(const TopSrc& s, int n, int n4, unsigned long long* dkeys, int (*part)[64]) {
     const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
     for (int e = tid; e < 4 * n4; e += 256) dkeys[e] = e < n ? ((unsigned long long)orderable(src_value(s, e)) << 32) | (unsigned int)(~e) : 0ull;
     __syncthreads();
@@ -289,6 +286,26 @@ __global__ __launch_bounds__(256) void topk_rank_blocks2_dyn_kernel(TopSrc s0, T
             if (s.scores_out) s.scores_out[rank * s.out_stride] = s.v[e];
         }
     }
+}
+__global__ __launch_bounds__(256) void topk_rank_blocks2_dyn_kernel(TopSrc s0, TopSrc s1, int n, int n4) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long dkeys[];  // 4 * n4 entries
+    __shared__ int part[4][64];
+    const TopSrc s = blockIdx.y ? s1 : s0;
+    rank_blocks_dyn_body(s, n, n4, dkeys, part);
+}
+// The two rankings of E windows in one launch (the lock-step batch): blockIdx.z picks the window -- row z of v / expo, list z of
+// out / scores_out --, everything else is the kernel above, for every n <= 16384 (keys in dynamic LDS on both sides of 2048: the
+// rank of an element is a count of integer key comparisons, so the lists are those of topk_rank_blocks2_kernel too).
+__global__ __launch_bounds__(256) void topk_rank_batch_kernel(TopSrc s0, TopSrc s1, int n, int n4, long long v_stride, int list_stride) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long dkeys[];  // 4 * n4 entries
+    __shared__ int part[4][64];
+    TopSrc s = blockIdx.y ? s1 : s0;
+    const long long w = blockIdx.z;
+    s.v += w * v_stride;
+    if (s.expo) s.expo += w * v_stride;
+    s.out += w * list_stride;
+    if (s.scores_out) s.scores_out += w * list_stride;
+    rank_blocks_dyn_body(s, n, n4, dkeys, part);
 }
 
 __global__ __launch_bounds__(1024) void topk_rank_kernel(const float* v, int n, int k, int* idx_out) {
@@ -347,6 +364,20 @@ void launch_topk(const float* v, int n, int k, int* idx_out, hipStream_t st) {
     hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), (size_t)np * 8, st, v, n, np, k, idx_out);
 }
 
+// > 64 KiB of dynamic LDS for a ranking kernel: state[device] = 0: not asked, 1: granted, 2: refused
+static bool rank_lds_fits(const void* kernel, std::atomic<int>* state, size_t lds) {
+    if (lds <= 64 * 1024) return true;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+    int stt = state[dev].load(std::memory_order_acquire);
+    if (stt == 0) {
+        stt = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024) == hipSuccess ? 1 : 2;
+        if (stt == 2) (void)hipGetLastError();
+        state[dev].store(stt, std::memory_order_release);
+    }
+    return stt == 1;
+}
+
 // The two candidate lists of the certified re-score in one buffer (m3pc_topk_race_window): list[rmax + i] = the i-th best
 // entry of v (i <= kk - 1), list[rmax - 1 - i] = the i-th best entry by race key (i < rr): the r best racers and the n best
 // scorers are the contiguous slice [rmax - r, rmax + n).
@@ -366,19 +397,8 @@ bool launch_topk_race(const float* v, const float* expo, float tau, int n, int k
         // > 64 KiB of dynamic LDS is a per-device opt-in, asked for ONCE per device and only when the launch needs it (n > 8192);
         // a refusal is remembered and its error cleared, so that the fallback below is not reported as a failed launch by the
         // caller's hipGetLastError (the same pattern as lds_opt_in in attn_bf16.hip)
-        static std::atomic<int> state[64] = {};  // 0: not asked, 1: granted, 2: refused
-        int dev = 0;
-        const bool dev_ok = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
-        bool fits = lds <= 64 * 1024;
-        if (!fits && dev_ok) {
-            int stt = state[dev].load(std::memory_order_acquire);
-            if (stt == 0) {
-                stt = hipFuncSetAttribute((const void*)topk_rank_blocks2_dyn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 132 * 1024) == hipSuccess ? 1 : 2;
-                if (stt == 2) (void)hipGetLastError();
-                state[dev].store(stt, std::memory_order_release);
-            }
-            fits = stt == 1;
-        }
+        static std::atomic<int> state[64] = {};
+        const bool fits = rank_lds_fits((const void*)topk_rank_blocks2_dyn_kernel, state, lds);
         if (fits) {
             hipLaunchKernelGGL(topk_rank_blocks2_dyn_kernel, dim3((n + 63) / 64, rr > 0 ? 2 : 1), dim3(256), lds, st, s0, s1, n, n4);
             return true;
@@ -389,6 +409,24 @@ bool launch_topk_race(const float* v, const float* expo, float tau, int n, int k
     launch_topk(v, n, kk, list + rmax, st);
     if (rr > 0) hipLaunchKernelGGL(topk_select_kernel, dim3(1), dim3(1024), 0, st, t1, n);  // (rr <= 64, n <= 16384)
     return false;     // (the caller still has to gather list_scores: launch_window_stats)
+}
+
+// launch_topk_race for E windows in one launch (n <= 16384): window w ranks row w of v / expo (row stride v_stride) into list w
+// (list_stride >= rmax + kk entries; list_scores in the same layout).  false: the device refused the LDS the keys of n > 8192
+// candidates need -- nothing is launched, the caller reports it.
+bool launch_topk_race_batch(const float* v, const float* expo, float tau, int E, int n, long long v_stride, int kk, int rr, int rmax,
+                            int* list, float* list_scores, int list_stride, hipStream_t st) {
+    if (E <= 0 || n <= 0 || kk <= 0) return true;
+    if (n > 16384) return false;
+    const TopSrc s0{v, nullptr, 0.f, kk, list + rmax, 1, list_scores ? list_scores + rmax : nullptr};
+    const TopSrc s1{v, expo, tau, rr, list + rmax - 1, -1, list_scores ? list_scores + rmax - 1 : nullptr};
+    const int n4 = (((n + 3) / 4) + 1) & ~1;
+    const size_t lds = (size_t)4 * n4 * sizeof(unsigned long long);
+    static std::atomic<int> state[64] = {};
+    if (!rank_lds_fits((const void*)topk_rank_batch_kernel, state, lds)) return false;
+    hipLaunchKernelGGL(topk_rank_batch_kernel, dim3((n + 63) / 64, rr > 0 ? 2 : 1, E), dim3(256), lds, st, s0, s1, n, n4, v_stride,
+                       list_stride);
+    return true;
 }
 
 // idx: the kk best entries of v, best first.  n = clamp(#{i < kk: v[idx[i]] >= v[idx[0]] - window}, kmin, kmax) and the
@@ -572,6 +610,51 @@ void launch_merge_select(const float* b, int n_total, const int* list, int r, in
                        stats, host_stats, seq, expo ? 8 : 4, sp);
 }
 
+// launch_merge_select (or, without `select`, launch_rescore_merge) for up to 64 windows in one launch: workgroup i is window
+// w0 + i with its own r / n / delta, its rows of the (E, n_total) arrays, the slice [rmax - r, rmax + n) of its list and its block of
+// 8 statistics -- the bodies are those of the one-window kernels, so the results are theirs bit for bit.
+__global__ __launch_bounds__(1024) void merge_select_batch_kernel(MergeSelectBatchP P) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    const int i = blockIdx.x;
+    const long long w = P.w0 + i;
+    const int r = P.r[i], n = P.n[i];
+    const long long row = w * P.row_stride, lo = w * P.list_stride + P.rmax - r;
+    const float* expo = P.expo ? P.expo + row : nullptr;
+    float* out = P.out + row;
+    rescore_merge_body(P.b + row, P.n_total, P.list + lo, r, n, P.list_scores + lo, P.f + w * P.f_stride + (P.rmax - r - P.f_lo), P.delta[i],
+                       P.race ? expo : nullptr, P.tau, out, P.stats + 8 * w, P.host_stats ? P.host_stats + 8 * w : nullptr, P.seq,
+                       P.race ? 8 : 4);
+    if (!P.select) return;
+    __syncthreads();
+    SelectP sp;
+    sp.er = out;
+    sp.a0 = P.a0 ? P.a0 + w * P.a0_wstride : nullptr;
+    sp.a0_stride = P.a0_stride;
+    sp.n = P.n_total;
+    sp.A = P.A;
+    sp.temperature = P.tau;
+    sp.expo = expo;
+    sp.p = P.p ? P.p + row : nullptr;
+    sp.eval_action = P.eval_action ? P.eval_action + w * P.A : nullptr;
+    sp.argmax = P.argmax ? P.argmax + w : nullptr;
+    sp.sample_idx = P.sample_idx ? P.sample_idx + w : nullptr;
+    sp.sample_action = P.sample_action ? P.sample_action + w * P.A : nullptr;
+    select_body(sp, sv, si);
+}
+void launch_merge_select_batch(MergeSelectBatchP& P, int E, const int* r, const int* n, const float* delta, hipStream_t st) {
+    for (int w0 = 0; w0 < E; w0 += 64) {  // (per-window scalars travel in the kernel arguments: 64 windows per launch)
+        const int e = E - w0 < 64 ? E - w0 : 64;
+        P.w0 = w0;
+        for (int i = 0; i < e; ++i) {
+            P.r[i] = r[w0 + i];
+            P.n[i] = n[w0 + i];
+            P.delta[i] = delta[w0 + i];
+        }
+        hipLaunchKernelGGL(merge_select_batch_kernel, dim3(e), dim3(1024), 0, st, P);
+    }
+}
+
 // Calibration statistics of the certified re-score (m3pc_calibrate_delta): d_i = b_i - f_i over ALL n <= 16384 candidates (b: the
 // low-precision scores, f: their fp32 values), c = the lower median of d -- the element of rank (n - 1) / 2 of the ascending
 // order (value, then index: what torch.median returns) --, then max_i |d_i - c| and max_i |f_i|.  One workgroup: every thread
@@ -666,6 +749,26 @@ __global__ void scatter_kernel(const float* src, const int* index, int n, float*
 void launch_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, hipStream_t st) {
     if (n <= 0) return;
     hipLaunchKernelGGL(scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, index, n, dst, index_copy);
+}
+
+// cand[w m + i] = sample_actions[w, list_w[lo + i]] (rows of `row` floats) and window_index[w m + i] = w for the slice [lo, lo + m)
+// of every window's list: the rows one m3pc_score_actions call re-scores, window-major.  One wave per row; an entry that names no
+// candidate (a list slot no ranking wrote) leaves its row untouched.
+__global__ __launch_bounds__(64) void gather_listed_kernel(const float* sa, int n_total, int row, const int* list, int list_stride, int lo,
+                                                           int m, float* cand, int* window_index) {
+    const int o = blockIdx.x, w = o / m, i = o - w * m;
+    const int id = list[(long long)w * list_stride + lo + i];
+    if (threadIdx.x == 0 && window_index) window_index[o] = w;
+    if ((unsigned int)id >= (unsigned int)n_total) return;
+    const float* src = sa + ((long long)w * n_total + id) * row;
+    float* dst = cand + (long long)o * row;
+    for (int c = threadIdx.x; c < row; c += 64) dst[c] = src[c];
+}
+void launch_gather_listed(const float* sa, int E, int n_total, int row, const int* list, int list_stride, int lo, int m, float* cand,
+                          int* window_index, hipStream_t st) {
+    if (E <= 0 || m <= 0 || row <= 0) return;
+    hipLaunchKernelGGL(gather_listed_kernel, dim3((unsigned)(E * m)), dim3(64), 0, st, sa, n_total, row, list, list_stride, lo, m, cand,
+                       window_index);
 }
 
 // ---- the variates of a plan step from a counter-based generator (m3pc_draw_variates): a value depends on (seed, step, element
