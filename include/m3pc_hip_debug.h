@@ -5,6 +5,7 @@
  * A/B switches M3PC_NO_* / M3PC_GEMM_VARIANT / M3PC_TWO_STREAM / ... listed in DESIGN.md section 7.
  * Users: tests/test_gemm_kernels_gpu.py, tests/test_gemm_edges_gpu.py, tests/test_bf16x3_gpu.py, tests/test_attention_gpu.py,
  * tests/test_block_fused_gpu.py, tests/test_block_edges_gpu.py, tests/test_block_ref_cpu.py, tests/test_lockstep_kernels_gpu.py,
+ * tests/test_block_shared_xb_gpu.py, tests/test_block_shared_xb_cpu.py, tests/test_embed_shared_xb_gpu.py,
  * tools/*.py.
  */
 #ifndef M3PC_HIP_DEBUG_H
@@ -171,7 +172,8 @@ int m3pc_debug_block_fused_heads(const void* O, int M, const float* rowtab, int 
  * launch_block_fused's checks and dispatch; the weight stream is packed inside the call (Wo (512, 512), W1 (2048, 512), W2 (512, 2048),
  * optional Wqkv (1536, 512) or Wh (2, 512, 512): bf16, torch Linear layout; stream_buf: m3pc_debug_block_stream_bytes() bytes on 1 KiB).
  *     X'  = residual(r) + bo + O[r] Wo^T          residual(r): res[r] (ldr; bf16 rows when x_bf16); with res_L > 0 the rows come in
- *                                                 sequences of res_L and row j < res_nshared of every sequence is read from sequence 0;
+ *                                                 sequences of res_L and row j < res_nshared of every sequence is read from sequence 0
+ *                                                 (x_bf16: res is the compact block of m3pc_debug_block_res_row, and Xout is not res);
  *                                                 with rowtab: rowtab[w], w = r % rt_mod, and for w < res_nu the row of its own stored
  *                                                 behind the table, rowtab[rt_mod + (r / rt_mod) res_nu + w]
  *     X'' = X' + b2 + gelu(LN2(X') W1^T + b1) W2^T     -> Xout (ldx; fp32, bf16 when x_bf16; may be res)
@@ -247,6 +249,34 @@ int m3pc_debug_block_ex(const m3pc_debug_block_args* a);
 /* the same checks without packing or launching anything (no GPU needed): the refusals, and `picked` as m3pc_debug_block_ex reports it */
 int m3pc_debug_block_accepts(const m3pc_debug_block_args* a);
 int m3pc_debug_block_split_n(void);
+/* x_bf16 with res_L > 0 (forms 16 / 17): `res` is the compact block -- the res_nshared shared rows once, then the res_L - res_nshared
+ * own rows of sequence 0, 1, ... -- and this is the row of it that token row r takes as its residual (-1: arguments out of range).
+ * Host only, no GPU needed (tests/test_block_shared_xb_cpu.py) */
+int m3pc_debug_block_res_row(int r, int res_L, int res_nshared);
+/* the embedding kernel (launch_embed; d = 256, 512, 768 or 1024: the wave-per-row kernel) on caller tensors: token j of batch element
+ * b is key tokmap[2 j] at step t = tokmap[2 j + 1], its row X[b L + j] = tok[key][b bstride[key] + t feat[key] ..] WT[key] + E[key][t]
+ * (WT (feat, d), E (T, d) fp32; no normalisation, no window index), stored as fp32 (X) or bf16 (Xb); with ln_g / ln_b also
+ * LayerNorm(row) as bf16 to Hb (n_sh > 0: tokens j < n_sh once to Hb_sh[j], the others to Hb[b (L - n_sh) + j - n_sh]).  The first
+ * n_indep tokens do not depend on b; x_first_only: their X rows are stored for b = 0 only; x_compact (with Xb, x_first_only,
+ * n_indep > 0): Xb holds those n_indep rows once and behind them the L - n_indep own rows of b = 0, 1, ... (m3pc_debug_block_res_row) */
+typedef struct m3pc_debug_embed_args {
+    const float* tok[4];
+    long long bstride[4];
+    const float* WT[4];
+    const float* E[4];
+    int feat[4];
+    const int* tokmap; /* (L, 2) int32 */
+    int batch, L, d, T;
+    float* X;
+    void* Xb;
+    const float* ln_g; /* optional */
+    const float* ln_b;
+    void* Hb;    /* optional */
+    void* Hb_sh; /* with n_sh > 0 */
+    int n_indep, n_sh, x_first_only, x_compact;
+    void* stream;
+} m3pc_debug_embed_args;
+int m3pc_debug_embed(const m3pc_debug_embed_args* a);
 /* the fused decoder input (kv_fused_kernel) on caller tensors */
 long long m3pc_debug_kv_stream_bytes(void);
 int m3pc_debug_kv_fused(const void* Z, int n, int Le, int kept0, int off0, int kept1, int off1, const void* We0, const void* We1,

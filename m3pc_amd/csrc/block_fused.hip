@@ -220,6 +220,7 @@ __device__ __forceinline__ void acc_touch(f32x16 (&c)[16]) {
 // XB (round 6): the residual rows p.res and the output rows p.Xout are bf16 (BlockP::x_bf16).  A 128-byte line then holds the 64
 // features of TWO feature tiles, so the residual arrives and X'' leaves a tile PAIR at a time: half the LDS-DMA pieces, half the
 // stores, half the bytes of both HBM bursts of a tile; everything between (X' in the accumulators, both LayerNorms) stays fp32.
+// With p.res_L > 0 the residual rows come from the compact block of block_res_row_xb (shared leading rows stored once).
 template <int DBG, int TAIL, int XB = 0>
 __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
     constexpr bool QKV = TAIL == 1, HEADS = TAIL == 2, SPLIT = TAIL == 3;
@@ -341,7 +342,11 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
             int rs = rt;
             if (p.res_L > 0) {  // shared leading rows of a sequence: read from sequence 0
                 const int jj = rt % p.res_L;
-                if (jj < p.res_nshared) rs = jj;
+                // (XB: the shared rows stored once, every sequence's own rows compactly behind them -- block_res_row_xb.  The 8 rows
+                // of a piece may then lie in both blocks and in two sequences: every lane carries the offset of its own row, as it
+                // always did, and the piece count of a phase -- the vmcnt bookkeeping below -- does not change)
+                if (XB) rs = block_res_row_xb(rt, p.res_L, p.res_nshared);
+                else if (jj < p.res_nshared) rs = jj;
             }
             size_t rowoff;
             if (p.rowtab) {
@@ -1549,9 +1554,22 @@ bool block_fused_accepts(const BlockP& p) {
         if (p.ldx != BD) return false;  // (block_split_reduce reads the slabs as rows of 512 floats)
     }
     if (p.x_bf16) {  // bf16 residual rows in, bf16 X'' rows out: whole 128-byte lines of 64 features
-        if (p.rowtab || p.split || p.head_out[0] || p.res_L > 0 || p.variant || !p.res) return false;
-        if ((p.ldr % 8) || (unsigned long long)p.M * p.ldr * 2 >= 0xfffffff0ull) return false;
+        if (p.rowtab || p.split || p.head_out[0] || p.variant || !p.res) return false;
+        // (res_L > 0: res is the shared block of res_nshared rows with the sequences' own rows behind it, block_res_row_xb; Xout is
+        // another buffer: the block has another shape than the full rows of X'', so any overlap would be read while written)
+        unsigned long long res_rows = (unsigned long long)p.M;  // rows of res that a token row < M names
+        if (p.res_L > 0) {
+            const unsigned long long own = (unsigned long long)(p.M / p.res_L) * (p.res_L - p.res_nshared) +
+                                           (p.M % p.res_L > p.res_nshared ? p.M % p.res_L - p.res_nshared : 0);
+            res_rows = own > 0 ? p.res_nshared + own : (unsigned long long)(p.M < p.res_nshared ? p.M : p.res_nshared);
+        }
+        if ((p.ldr % 8) || res_rows * p.ldr * 2 >= 0xfffffff0ull) return false;
         if (p.Xout && ((p.ldx % 8) || (unsigned long long)p.M * p.ldx * 2 >= 0x80000000ull)) return false;
+        if (p.Xout && p.res_L > 0) {
+            const uintptr_t r0 = (uintptr_t)p.res, r1 = r0 + (uintptr_t)(((res_rows - 1) * p.ldr + BD) * 2);
+            const uintptr_t x0 = (uintptr_t)p.Xout, x1 = x0 + (uintptr_t)((((unsigned long long)p.M - 1) * p.ldx + BD) * 2);
+            if (r0 < x1 && x0 < r1) return false;
+        }
     }
     return true;
 }

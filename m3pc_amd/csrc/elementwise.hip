@@ -167,6 +167,8 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(EmbedP p, int CB, int n
         const long long row = (long long)b * p.L + j;
         if (!(indep && p.x_first_only && b > 0)) {
             if (p.Xb) {
+                // (x_compact: the shared rows once, the own rows of every batch element behind them)
+                const long long xrow = p.x_compact ? block_res_row_xb((int)row, p.L, p.n_indep) : row;
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {
                     typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(EmbedP p, int CB, int n
                     o[1] = (bf16_t)x[i].y;
                     o[2] = (bf16_t)x[i].z;
                     o[3] = (bf16_t)x[i].w;
-                    stream_store(o, (bf16x4_t*)(p.Xb + row * d + (i * 64 + lane) * 4));
+                    stream_store(o, (bf16x4_t*)(p.Xb + xrow * d + (i * 64 + lane) * 4));
                 }
             } else {
 #pragma unroll

@@ -124,6 +124,14 @@ void read_big_probe(long long out[4]);                   // debug: gemm_big.hip 
 void read_clock_probe(long long out[2]);                // debug: {shader clocks, 100-MHz ticks} of one ring workgroup
 bool launch_gemm_f32_direct(const GemmP& p, hipStream_t st);  // fp32, few rows: in-workgroup K split (gemm_f32_direct.hip)
 
+// Where the bf16 residual row of token row r lives when the leading rows of the sequences are stored once (BlockP::x_bf16 with
+// res_L > 0, EmbedP::x_compact): rows of a block that starts with the nshared shared rows and goes on with the L - nshared own rows
+// of sequence 0, 1, ...
+__host__ __device__ inline int block_res_row_xb(int r, int L, int nshared) {
+    const int b = r / L, w = r % L;
+    return w < nshared ? w : nshared + b * (L - nshared) + (w - nshared);
+}
+
 // The tail of one pre-LN transformer layer after its attention, as one launch (block_fused.hip; d = 512, ff = 2048,
 // bf16 operands):  X' = res + bo + O Wo^T;  X'' = X' + b2 + gelu(LN2(X') W1^T + b1) W2^T;
 // Xout = X'' (fp32, optional);  Hout = bf16(LN_B[sel]?(LN_A(X''))).
@@ -150,7 +158,10 @@ struct BlockP {
     int x_bf16;             // round 6: res and Xout are bf16 rows (ldr / ldx in elements; res / Xout are bf16_t* behind the casts): the
                             // residual stream crosses HBM between the encoder layers in bf16 -- half of a tile's residual bytes in,
                             // half of its X'' bytes out (oracle/lowprec_study.py "bf16_res": delta x 0.95-1.25).  Plain and
-                            // next-Q|K|V forms only (no rowtab, no split, no heads, no shared leading rows)
+                            // next-Q|K|V forms only (no rowtab, no split, no heads).  With res_L > 0 the residual rows are stored
+                            // compactly: res holds the res_nshared shared rows ONCE, then every sequence's res_L - res_nshared own
+                            // rows, sequence by sequence (block_res_row_xb; the embedding kernel writes them so, EmbedP::x_compact);
+                            // Xout still takes full rows r and is another buffer -- in place is not a form of this layout
     const float* lnA_g;     // LayerNorm of the block output (next block's norm1 / the stack's final norm)
     const float* lnA_b;
     const float* lnB_g[2];  // optional second LayerNorm on top (an output head's norm), per row group
@@ -337,6 +348,8 @@ struct EmbedP {
     bf16_t* Hb;              // ... bf16 rows (batch*L, d)
     int n_indep;             // the first n_indep tokens do not depend on the batch index (computed once per wave)
     int x_first_only;        // != 0: the X rows of those tokens are stored for batch element 0 only (the consumer reads them there)
+    int x_compact;           // != 0 (with Xb, x_first_only and n_indep > 0): Xb holds the n_indep shared rows once, then the L - n_indep
+                             // own rows of batch element 0, 1, ... (block_res_row_xb) instead of rows b L + j with holes
     int n_sh;                // > 0: LayerNorm rows of tokens j < n_sh go once to Hb_sh[j], those of tokens j >= n_sh
     bf16_t* Hb_sh;           //      compactly to Hb[b * (L - n_sh) + j - n_sh]  (first-layer pruning, see run_block)
 };

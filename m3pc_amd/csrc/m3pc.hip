@@ -2407,6 +2407,48 @@ int m3pc_debug_block_ex(const m3pc_debug_block_args* a) {
     if (b.split) launch_block_split_reduce(r, st);
     return check_launch("debug_block_ex");
 }
+// where the bf16 residual row of token row r lives in the compact layout (block_res_row_xb; host only, no GPU needed)
+int m3pc_debug_block_res_row(int r, int res_L, int res_nshared) {
+    if (r < 0 || res_L < 1 || res_nshared < 0 || res_nshared > res_L) return -1;
+    return block_res_row_xb(r, res_L, res_nshared);
+}
+
+// the embedding kernel (launch_embed) on caller tensors (include/m3pc_hip_debug.h)
+int m3pc_debug_embed(const m3pc_debug_embed_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_embed: null arguments");
+    if (a->batch < 1 || a->L < 1 || a->d % 256 != 0 || a->d < 256 || a->d > 1024 || !a->tokmap) return fail(M3PC_EINVAL, "debug_embed: batch / L / d / tokmap");
+    if (a->n_indep < 0 || a->n_indep > a->L || a->n_sh < 0 || a->n_sh > a->n_indep) return fail(M3PC_EINVAL, "debug_embed: n_indep / n_sh");
+    if (!a->X == !a->Xb) return fail(M3PC_EINVAL, "debug_embed: exactly one of X / Xb");
+    if (a->x_compact && !(a->Xb && a->x_first_only && a->n_indep > 0)) return fail(M3PC_EINVAL, "debug_embed: x_compact needs Xb, x_first_only and n_indep > 0");
+    if ((a->Hb || a->n_sh) && (!a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_embed: Hb without ln_g / ln_b");
+    if (a->n_sh > 0 && (!a->Hb || !a->Hb_sh)) return fail(M3PC_EINVAL, "debug_embed: n_sh without Hb / Hb_sh");
+    EmbedP e;
+    memset(&e, 0, sizeof(e));
+    for (int k = 0; k < 4; ++k) {
+        e.tok[k] = a->tok[k];
+        e.bstride[k] = a->bstride[k];
+        e.WT[k] = a->WT[k];
+        e.E[k] = a->E[k];
+        e.feat[k] = a->feat[k];
+    }
+    e.tokmap = (const int2*)a->tokmap;
+    e.batch = a->batch;
+    e.L = a->L;
+    e.d = a->d;
+    e.T = a->T;
+    e.X = a->X;
+    e.Xb = (bf16_t*)a->Xb;
+    e.ln_g = a->ln_g;
+    e.ln_b = a->ln_b;
+    e.Hb = (bf16_t*)a->Hb;
+    e.Hb_sh = (bf16_t*)a->Hb_sh;
+    e.n_indep = a->n_indep;
+    e.n_sh = a->n_sh;
+    e.x_first_only = a->x_first_only ? 1 : 0;
+    e.x_compact = a->x_compact ? 1 : 0;
+    launch_embed(e, (hipStream_t)a->stream);
+    return check_launch("debug_embed");
+}
 
 // kv_fused_kernel alone (tests/test_block_fused_gpu.py): n candidates of Le rows each in Z (n*Le, 512) bf16; group g holds
 // the kept[g] rows at offset off[g] of every candidate, embedded with We[g] (512, 512) bf16 + rowtab[g] (kept[g], 512);

@@ -543,6 +543,7 @@ inline void gemm_out(GemmP& p, int dt_out, void* C, int ldc) {
 // x_dead: nothing reads X after this block except through next_ln (lets the fused tail skip the fp32 store).
 // Xnext / res_nshared (fused tail only): the block output goes to Xnext instead of X, and the first res_nshared rows of
 // every sequence of X are read from sequence 0 (the embedding kernel stored the history rows once, EmbedP::x_first_only).
+// With x_bf16, X is then the compact block of block_res_row_xb (EmbedP::x_compact): shared rows once, own rows behind them.
 // The fused layer tail (block_fused.hip) works in 128-row tiles, one per CU, and a tile takes its ~130-170 us whatever the row
 // count: below ~96 tiles most of the chip idles for that long and the GEMM chain, whose tiles spread over all CUs, is faster
 // (the reference's shipped N=625 / T=8 config, 64 + 40 tiles: 1.13 -> 1.00 ms per closed-loop call).

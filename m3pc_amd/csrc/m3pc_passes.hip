@@ -313,8 +313,20 @@ int run_encoder(m3pc_handle* h, Plan* pl, const TokIn& in, int batch, int dt, hi
                 (double)batch * pl->Le * h->pass_scale >= (double)FUSED_MIN_ROWS && (size_t)batch * pl->Le * 3 * h->d * 2 < 0x7fffffffull &&
                 (unsigned long long)batch * pl->Le * h->d * 2 < 0x80000000ull;
     for (int i = 0; i < h->dm.n_enc_layer && xb16; ++i) xb16 = h->wstream.count("encoder.layers." + std::to_string(i)) != 0;
-    e.x_first_only = shared_res ? 1 : 0;
-    if (xb16) e.Xb = (bf16_t*)h->X;
+    // The history rows of the bf16 residual stream stored once per pass (each half its own copy, in its own workspace rows) and
+    // the candidates' own rows compactly behind them (block_res_row_xb): the embedding writes n_indep + batch (Le - n_indep) rows
+    // instead of batch Le, and the first layer's tail reads those.  The block lives behind the full bf16 rows the first tail writes
+    // (X'' goes to h->X as before, so nothing changes from the second layer on): a candidate owns 2 T fp32 rows of X, i.e. 4 T bf16
+    // rows, of which the stream takes Le.  Decided from the pass's shape alone, like xb16.  M3PC_NO_SHARED_XB=1: the full rows.
+    static const bool no_shared_xb = M3PC_ENV("M3PC_NO_SHARED_XB") != nullptr;  // A/B switch
+    const long long xc_rows = (long long)n_indep + (long long)batch * (pl->Le - n_indep);  // rows of the compact block
+    const bool xb_shared = xb16 && n_sh > 0 && !no_shared_xb && n_indep < pl->Le &&
+                           (long long)batch * pl->Le + xc_rows <= (long long)batch * 4 * h->T &&
+                           (h->X - h->cur->X) / h->d + (long long)batch * 2 * h->T <= h->R;
+    bf16_t* const Xc = (bf16_t*)h->X + (size_t)batch * pl->Le * h->d;
+    e.x_first_only = shared_res || xb_shared ? 1 : 0;
+    e.x_compact = xb_shared ? 1 : 0;
+    if (xb16) e.Xb = xb_shared ? Xc : (bf16_t*)h->X;
     e.widx = in.widx;
     e.tokmap = pl->d_tokmap;
     e.batch = batch;
@@ -347,6 +359,10 @@ int run_encoder(m3pc_handle* h, Plan* pl, const TokIn& in, int batch, int dt, hi
     float* Xs = shared_res && layer_from > 0 ? h->Y : h->X;  // where the residual stream lives
     for (int i = layer_from > 0 ? layer_from : 0; i < nl && i < layer_to; ++i) {
         float* Xn = shared_res && i == 0 ? h->Y : nullptr;
+        if (xb_shared && i == 0) {  // the first tail reads the compact block and writes the full rows to X, where the stream stays
+            Xs = (float*)Xc;
+            Xn = h->X;
+        }
         LnP nxt = ln;  // what follows layer i on X: norm1 of layer i+1 (-> Hn) or encoder.norm (-> EncOut / Z)
         nxt.X = ln.X = Xn ? Xn : Xs;
         if (i + 1 < nl) {
