@@ -44,7 +44,8 @@ extern "C" {
 
 /* ABI history.  Added within v7 (new symbols and structures only; nothing existing changed): m3pc_plan_step_certified,
  * m3pc_calibrate_delta, m3pc_cert_args, m3pc_cert_record; then m3pc_plan_step_certified_begin / _end, m3pc_set_step_streams and
- * m3pc_draw_variates; then m3pc_refit_resample, m3pc_refine_plan and m3pc_refine_args (CEM / MPPI refinement).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * m3pc_draw_variates; then m3pc_refit_resample, m3pc_refine_plan and m3pc_refine_args (CEM / MPPI refinement); then
+ * m3pc_plan_steps_certified (a lock-step batch of certified steps).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -494,6 +495,49 @@ int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* args, c
                                    float* std, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
                                    float* eval_action, int* argmax, int* sample_idx, float* sample_action, void* stream);
 int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* record, void* stream);
+
+/* A LOCK-STEP BATCH of certified plan steps as one call: E = n_windows environments that step together (replay_buffer.py:204-232 per
+ * environment), all windows sharing one effective horizon.  It is the protocol of m3pc_amd/lockstep.py (action_sample_batch(lockstep=True))
+ * restated in C, everything on `stream`, in the serial form (there is no _begin / _end split of this call):
+ *   1. m3pc_policy_pass_batch into args->slot (args->flags, args->window and args->rtg are ignored; rtg comes per window)
+ *   2. E x m3pc_candidate_pass (window = w, that window's rows, M3PC_PLAN_DEFER_JOIN) in args->precision, one m3pc_candidate_join
+ *   3. the lists of m3pc_topk_race_window (m3pc_topk_window when rmax == 0) of all windows in ONE launch
+ *   4. list[rmax - rfirst .. rmax + kmin) of every window gathered window-major, with the window index beside it
+ *   5. ONE fp32 m3pc_score_actions over those E (rfirst + kmin) rows (RTG scoring for M3PC_MODE_RTG, else CRITIC scoring)
+ *   6. merge + certificates + select of all windows in ONE launch, each window's statistics to a host-mapped block of its own
+ *   7. ONE bounded wait for the E sequence numbers (at most 10 s, then one synchronisation of `stream` and the device copies)
+ *   8. per window, in ascending order, the loop of m3pc_plan_step_certified on the window's certificates.  Its fp32 re-scores are
+ *      m3pc_score_actions calls with n_windows = 1 on the window's own rows, over gathered slices of its list in chunks of max_rescore
+ *      (score entries up to `need`, race entries up to `need_race`, the window set); its merges are the one-window
+ *      m3pc_merge_race_select (m3pc_rescore_merge + m3pc_select when rmax == 0) on the window's rows and host block.  Everything: ONE
+ *      fp32 m3pc_score_actions over all n_total candidates of the window, the best entry merged with itself at delta 0, the select.
+ * delta across windows: every window's first merge runs under cert->delta.  With grow_delta a window that raises the bound raises it
+ * for every LATER window, and such a window is first merged and selected again under the raised bound, before its certificate is
+ * read.  records[w].delta is the bound coming out of window w -- records[E-1].delta is what the caller folds back -- and
+ * records[w].rounds counts the merges issued for window w (the batched launch counts as one).
+ * args->precision == M3PC_PREC_FP32: fp32 candidate passes, merged = a copy of scores_low, the selects of all windows in one launch
+ * (m3pc_select's results per window, bit for bit), records {certified = 1, everything = 1, n_rescored = n_total}; cert is read for
+ * its temperature only.
+ * A window's results are those of the lock-step Python path for the same inputs, bit for bit.  They are NOT the bits of
+ * m3pc_plan_step_certified on that window alone: the few-row fp32 kernels choose their tiling by the row count (see
+ * m3pc_policy_pass_batch), so the two agree to fp32 rounding.
+ *   states (E,T,S), actions (E,T,A), rewards (E,T,1) device;  rtg host (E,)
+ *   eps       device (E,n_total,T,A) for RTG / CRITIC, (E,n_total,h,A) for NOISE;  expo device (E,n_total)
+ *   loc, std  device out (E,T,A), optional;  sample_actions device out (E,n_total,h,A)
+ *   scores_low, merged   device out (E,n_total)
+ *   list      device out (E, rmax + 1024) int32, optional: per window the final lists, as m3pc_plan_step_certified's
+ *   p (E,n_total), eval_action (E,A), argmax (E,), sample_idx (E,), sample_action (E,A)   device out, each optional
+ *   records   host out (E,), valid on return; every device output is complete in stream order
+ * Refused before any HIP call: null required pointers, n_windows < 1, args->returns != NULL (the batched policy pass takes rtg only)
+ * and every check of m3pc_plan_step_certified (M3PC_EINVAL); then n_windows > max_batch (M3PC_EINVAL), a pipelined step begun
+ * (M3PC_ESTATE), CRITIC / NOISE without critic weights (M3PC_ESTATE), and a first pass of more than max(max_candidates, max_rescore)
+ * rows, E (rfirst + kmin) (M3PC_ENOMEM).  The per-window buffers (lists, statistics, host blocks, gathered rows) are sized by
+ * m3pc_dims::max_batch and allocated at the first call.  Between calls the handle is in the state m3pc_plan_step_certified leaves. */
+int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_cert_args* cert, int n_windows,
+                              const float* states, const float* actions, const float* rewards, const double* rtg,
+                              const float* eps, const float* expo, float* loc, float* std, float* sample_actions,
+                              float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax,
+                              int* sample_idx, float* sample_action, m3pc_cert_record* records, void* stream);
 
 /* The variates of a plan step, for a host without a generator of its own: eps device out (n_count, row_elems) standard normals =
  * rows [n_begin, n_begin + n_count) of the (n_total, row_elems) array of (seed, step); expo device out (n_count,) Exp(1) (never 0),

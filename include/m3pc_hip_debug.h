@@ -148,6 +148,12 @@ typedef struct m3pc_debug_tail_args {
     void* stream;
 } m3pc_debug_tail_args;
 int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a);
+/* m3pc_select of n_windows windows in one launch (select_batch_kernel, the fp32 form of m3pc_plan_steps_certified): scores / expo / p
+ * (n_windows, n_total); a0 as above; eval_action / sample_action (n_windows, A), argmax / sample_idx (n_windows,) int32; p, the four
+ * outputs and expo optional as in m3pc_select.  Window w's results are m3pc_select's on row w, bit for bit.  n_total <= 16384. */
+int m3pc_debug_select_batch(const float* scores, const float* a0, long long a0_window_stride, long long a0_stride, int n_windows,
+                            int n_total, int A, float temperature, const float* expo, float* p, float* eval_action, int* argmax,
+                            int* sample_idx, float* sample_action, void* stream);
 /* the fused layer tail (block_fused.hip) on caller tensors; see csrc/m3pc.hip for the argument layout */
 long long m3pc_debug_block_stream_bytes(void);
 int m3pc_debug_block_fused(const void* O, int M, const float* res, const float* rowtab, int rt_mod, const void* Wo, const void* W1,

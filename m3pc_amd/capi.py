@@ -46,6 +46,7 @@ EXPORTS = (
     "m3pc_plan_step_certified", "m3pc_calibrate_delta",
     "m3pc_set_step_streams", "m3pc_plan_step_certified_begin", "m3pc_plan_step_certified_end", "m3pc_draw_variates",
     "m3pc_refit_resample", "m3pc_refine_plan",
+    "m3pc_plan_steps_certified",
 )
 
 
@@ -146,6 +147,8 @@ def load_library(path: Optional[str] = None):
         "m3pc_select": [vp, vp, vp, ll, i, f, vp, vp, vp, vp, vp, vp, vp],
         "m3pc_plan_step_certified": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                      vp, vp, vp, C.POINTER(CertRecord), vp],
+        "m3pc_plan_steps_certified": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), i, vp, vp, vp, C.POINTER(d), vp, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp, vp, vp, vp, C.POINTER(CertRecord), vp],
         "m3pc_calibrate_delta": [vp, C.POINTER(PlanArgs), vp, vp, vp, vp, vp, f, C.POINTER(f), vp],
         "m3pc_set_step_streams": [vp, vp, vp],
         "m3pc_plan_step_certified_begin": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -499,6 +502,50 @@ class Handle:
                                                 _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low), _ptr(merged),
                                                 _ptr(lst), *[_ptr(t) for t in sel], C.byref(rec), _stream(dev)))
         return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel), rec
+
+    def plan_steps_certified(self, mode: int, states, actions, rewards, rtg, eps, expo, horizon: int, lmbda: float, discount: float,
+                             n_total: int, temperature: float, delta: float = 0.0, grow_delta: bool = False, kmin: int = 8,
+                             kmax: int = 128, rfirst: int = 2, rmax: int = 32, precision: int = PREC_BF16, slot: int = 0,
+                             want_policy: bool = True, want_list: bool = True, want_p: bool = True, out=None):
+        """A lock-step batch of certified plan steps in ONE library call (m3pc_plan_steps_certified) on the current stream: states
+        (E,T,S), actions (E,T,A), rewards (E,T,1), rtg (E,) floats, eps (E, n_total, T|h, A), expo (E, n_total).  Returns (res,
+        records): ``res`` holds loc / std (E,T,A), sample_actions (E,n_total,h,A), expect_return_low and expect_return (the merged
+        vectors, (E,n_total)), list (E, rmax + 1024) int32 and sel = (p (E,n_total), eval_action (E,A), argmax (E,), sample_idx (E,),
+        sample_action (E,A)); ``records`` is the list of the windows' ``CertRecord``.  want_policy / want_list / want_p = False: the
+        optional loc + std / list / p are passed as NULL (``None`` in ``res``).  ``out``: optional preallocated contiguous outputs
+        by name (loc, std, sample_actions, expect_return_low, expect_return, list, p, eval_action, argmax, sample_idx,
+        sample_action).  The host has read every window's last certificate when the call returns; the tensors are complete in
+        stream order."""
+        dev, T, A = self.device, self.T, self.A
+        ins = [self._f32(t) for t in (states, actions, rewards, eps, expo)]
+        E = int(ins[0].shape[0])
+        assert ins[0].shape == (E, T, self.S) and ins[1].shape == (E, T, A) and ins[2].numel() == E * T
+        assert ins[3].numel() == E * n_total * (horizon if mode == MODE_NOISE else T) * A and ins[4].numel() == E * n_total
+        rt = [float(v) for v in rtg]
+        assert len(rt) == E
+        shapes = dict(loc=(E, T, A), std=(E, T, A), sample_actions=(E, n_total, horizon, A), expect_return_low=(E, n_total),
+                      expect_return=(E, n_total), list=(E, int(rmax) + 1024), p=(E, n_total), eval_action=(E, A), argmax=(E,),
+                      sample_idx=(E,), sample_action=(E, A))
+        skip = (() if want_policy else ("loc", "std")) + (() if want_list else ("list",)) + (() if want_p else ("p",))
+        o = {}
+        for name, shape in shapes.items():
+            dtype = torch.int32 if name in ("list", "argmax", "sample_idx") else torch.float32
+            t = None
+            if name not in skip:
+                t = (out or {}).get(name)
+                if t is None:
+                    t = torch.empty(shape, dtype=dtype, device=dev)
+                assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape, name
+            o[name] = t
+        loc, std, acts, low, merged, lst = (o[k] for k in ("loc", "std", "sample_actions", "expect_return_low", "expect_return", "list"))
+        sel = tuple(o[k] for k in ("p", "eval_action", "argmax", "sample_idx", "sample_action"))
+        args = self._args(mode, precision, horizon, n_total, 0, n_total, lmbda, discount, 0.0, slot)
+        cert = CertArgs(float(temperature), float(delta), int(bool(grow_delta)), int(kmin), int(kmax), int(rfirst), int(rmax))
+        recs = (CertRecord * E)()
+        check(self.lib.m3pc_plan_steps_certified(self._h, C.byref(args), C.byref(cert), E, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
+                                                 (C.c_double * E)(*rt), _ptr(ins[3]), _ptr(ins[4]), _ptr(loc), _ptr(std), _ptr(acts),
+                                                 _ptr(low), _ptr(merged), _ptr(lst), *[_ptr(t) for t in sel], recs, _stream(dev)))
+        return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel), list(recs)
 
     def set_step_streams(self, chain0: Optional["torch.cuda.Stream"], chain1: Optional["torch.cuda.Stream"]):
         """The two chain streams of the pipelined certified steps (m3pc_set_step_streams); None, None: the handle's own."""

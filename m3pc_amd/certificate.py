@@ -89,7 +89,9 @@ class _WindowOps:
     def read(self):
         c, w = self.c, self.w
         if self.pending is not None:
-            c.stats_h[w], self.pending = self.pending.cpu(), None
+            st, self.pending = self.pending.cpu(), None
+            c.stats_h[w] = 0.0  # (a merge without race entries -- the every-candidate path -- writes four statistics: the rest read 0)
+            c.stats_h[w, : st.numel()] = st
         v = [float(x) for x in c.stats_h[w]]
         return v[:4] + (v[5:8] if len(v) >= 8 else [0.0, 0.0, 0.0])
 

@@ -474,6 +474,9 @@ struct SelectP {
     float* sample_action;  // (A,) = a0[sample_idx]
 };
 void launch_select(const SelectP& p, hipStream_t st);
+// launch_select for E windows in one launch (workgroup = window, select_body): p describes window 0; window w reads er / expo and
+// writes p at + w row_stride, reads a0 at + w a0_wstride, writes eval_action / sample_action at + w A, argmax / sample_idx at + w
+void launch_select_batch(const SelectP& p, int E, long long row_stride, long long a0_wstride, hipStream_t st);
 
 // indices of the k largest values (descending; ties -> lower index first), n <= 16384, k <= n
 void launch_topk(const float* v, int n, int k, int* idx_out, hipStream_t st);

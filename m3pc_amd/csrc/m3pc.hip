@@ -252,6 +252,12 @@ int m3pc_destroy(m3pc_handle* h) {
         for (int i = 0; i < 2; ++i)
             if (h->step_chain[i]) hipStreamDestroy(h->step_chain[i]);
     if (h->cert_host) hipHostFree(h->cert_host);
+    {
+        void* lb[] = {h->ls.list, h->ls.b, h->ls.f, h->ls.stats, h->ls.cand, h->ls.fs, h->ls.widx};
+        for (void* b : lb)
+            if (b) hipFree(b);
+        if (h->ls.host) hipHostFree(h->ls.host);
+    }
     for (size_t i = 1; i < h->auxs.size(); ++i) {
         hipStreamDestroy(h->auxs[i]);
         hipEventDestroy(h->ev_joins[i]);
@@ -1681,6 +1687,326 @@ int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* rec
     return 0;
 }
 
+// ---- a lock-step batch of certified plan steps as one call (include/m3pc_hip.h: m3pc_plan_steps_certified): the order of
+// m3pc_amd/lockstep.py with the batched kernels of select.hip around ONE fp32 scoring pass, then certificate.py:resolve per window
+using Lockstep = m3pc_handle::Lockstep;
+static const int LS_ROW = 64 + 1024;  // list entries a window can hold (rmax <= 64 in front of 1024)
+static int ls_setup(m3pc_handle* h) {
+    Lockstep& W = h->ls;
+    if (W.ready) return 0;
+    const size_t E = (size_t)(h->dm.max_batch > 0 ? h->dm.max_batch : 1);
+    W.cand_rows = h->dm.max_candidates > h->chain[0].max_cand ? h->dm.max_candidates : h->chain[0].max_cand;
+    if (!W.list) CHK(dmalloc(&W.list, E * LS_ROW));
+    if (!W.b) CHK(dmalloc(&W.b, E * LS_ROW));
+    if (!W.f) CHK(dmalloc(&W.f, E * LS_ROW));
+    if (!W.stats) CHK(dmalloc(&W.stats, E * 24));
+    if (!W.cand) CHK(dmalloc(&W.cand, (size_t)W.cand_rows * h->T * h->A));
+    if (!W.fs) CHK(dmalloc(&W.fs, (size_t)W.cand_rows));
+    if (!W.widx) CHK(dmalloc(&W.widx, (size_t)W.cand_rows));
+    if (!W.host) {
+        HIPCHK(hipHostMalloc((void**)&W.host, E * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+        memset(W.host, 0, E * 8 * sizeof(float));
+        HIPCHK(hipHostGetDevicePointer((void**)&W.host_dev, W.host, 0));
+    }
+    W.seq_w.assign(E, 0.f);
+    W.ready = true;
+    return 0;
+}
+static float ls_next_seq(Lockstep& W) {
+    W.seq = W.seq % 1000000 + 1;
+    return (float)W.seq;
+}
+// cert_wait for the windows [w0, w1): ONE bounded spin until block w holds the sequence number issued last for window w (seq_w),
+// for all of them; on expiry one synchronisation of the stream and the device copies.  out: 8 floats per window.
+static int ls_wait(m3pc_handle* h, int w0, int w1, int n_device, hipStream_t st, float* out) {
+    Lockstep& W = h->ls;
+    const volatile float* hs = W.host;
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    for (int w = w0; w < w1; ++w)
+        while (hs[8 * w + 4] != W.seq_w[w]) {
+            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
+                if (hipStreamSynchronize(st) != hipSuccess ||
+                    hipMemcpy(out, W.stats + 8 * w0, (size_t)(w1 - w0) * 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                    return fail(M3PC_EHIP, "the statistics of the lock-step batch reached neither host-mapped memory within 10 s nor the host by a copy");
+                for (int v = 0; v < w1 - w0; ++v)
+                    for (int i = n_device; i < 8; ++i) out[8 * v + i] = 0.f;
+                return 0;
+            }
+        }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int i = 8 * w0; i < 8 * w1; ++i) out[i - 8 * w0] = hs[i];
+    return 0;
+}
+
+int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, int n_windows, const float* states,
+                              const float* actions, const float* rewards, const double* rtg, const float* eps, const float* expo,
+                              float* loc, float* std_, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
+                              float* eval_action, int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* records,
+                              void* stream) {
+    static const char* who = "m3pc_plan_steps_certified";
+    if (!h || !a || !c || !states || !actions || !rewards || !rtg || !eps || !expo || !sample_actions || !scores_low || !merged || !records)
+        return fail(M3PC_EINVAL, "null argument");
+    if (n_windows < 1) return fail(M3PC_EINVAL, "%s: n_windows %d < 1", who, n_windows);
+    if (a->returns) return fail(M3PC_EINVAL, "%s takes rtg per window, not a returns row (args->returns must be NULL)", who);
+    CHK(cert_check_step(a, c, who));
+    if (a->mode < 0 || a->mode > 2) return fail(M3PC_EINVAL, "bad mode %d", a->mode);
+    // from here on the handle is read
+    const int E = n_windows;
+    if (E > h->dm.max_batch) return fail(M3PC_EINVAL, "%s: n_windows %d > max_batch=%d", who, E, h->dm.max_batch);
+    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "%s with a pipelined step begun (m3pc_plan_step_certified_end first)", who);
+    if (a->mode != M3PC_MODE_RTG && !h->critic_set) return fail(M3PC_ESTATE, "critic weights not set");
+    if (a->precision != M3PC_PREC_FP32) {  // (the rows one scoring call can take: what ls_setup sizes the gathered rows by)
+        const long long rows = h->dm.max_candidates > h->chain[0].max_cand ? h->dm.max_candidates : h->chain[0].max_cand;
+        if ((long long)n_windows * (c->rfirst + c->kmin) > rows)
+            return fail(M3PC_ENOMEM, "%s: the first pass re-scores %d x %d candidates, more than max(max_candidates, max_rescore)=%lld", who,
+                        n_windows, c->rfirst + c->kmin, rows);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    CHK(ls_setup(h));
+    Lockstep& W = h->ls;
+    hipStream_t st = (hipStream_t)stream;
+    const int N = a->n_total, T = h->T, S = h->S, A = h->A, hz = a->horizon, slot = a->slot;
+    const long long row = (long long)hz * A, eps_w = (long long)N * (a->mode == M3PC_MODE_NOISE ? hz : T) * A;
+    const float temp = c->temperature;
+    memset(records, 0, (size_t)E * sizeof(*records));
+
+    // lockstep.py:57-62: ONE policy pass at batch E, every window's own candidate pass back to back, one join
+    m3pc_plan_args pa = *a;
+    pa.flags = 0;
+    pa.window = 0;
+    CHK(m3pc_policy_pass_batch(h, &pa, E, states, actions, rewards, rtg, nullptr, nullptr, stream));
+    pa.flags = M3PC_PLAN_DEFER_JOIN;
+    for (int w = 0; w < E; ++w) {
+        pa.window = w;
+        CHK(m3pc_candidate_pass(h, &pa, states + (size_t)w * T * S, actions + (size_t)w * T * A, rewards + (size_t)w * T, eps + w * eps_w,
+                                loc ? loc + (size_t)w * T * A : nullptr, std_ ? std_ + (size_t)w * T * A : nullptr, sample_actions + w * N * row,
+                                scores_low + (size_t)w * N, nullptr, nullptr, stream));
+    }
+    CHK(m3pc_candidate_join(h, slot, stream));
+
+    SelectP sel;  // window 0's select; window w at + w of every array
+    memset(&sel, 0, sizeof(sel));
+    sel.a0 = sample_actions;
+    sel.a0_stride = row;
+    sel.n = N;
+    sel.A = A;
+    sel.temperature = temp;
+    sel.expo = expo;
+    sel.p = p;
+    sel.eval_action = eval_action;
+    sel.argmax = argmax;
+    sel.sample_idx = sample_idx;
+    sel.sample_action = sample_action;
+    if (a->precision == M3PC_PREC_FP32) {  // fp32 scores for every candidate: the select alone, all windows in one launch
+        HIPCHK(hipMemcpyAsync(merged, scores_low, (size_t)E * N * sizeof(float), hipMemcpyDeviceToDevice, st));
+        sel.er = scores_low;
+        launch_select_batch(sel, E, N, N * row, st);
+        for (int w = 0; w < E; ++w) {
+            records[w].n_rescored = N;
+            records[w].everything = records[w].certified = 1;
+        }
+        return check_launch(who);
+    }
+
+    const int R = c->rmax, kmin = c->kmin, kmax = c->kmax, rfirst = c->rfirst, LS = R + 1024, m0 = rfirst + kmin;
+    const int kk = kmax + 1 < N ? kmax + 1 : N, cap = h->chain[0].max_cand;
+    int* L = list ? list : W.list;  // rows of LS entries, as are B and F
+    float *B = W.b, *F = W.f;
+    auto Lw = [&](int w) { return L + (size_t)w * LS; };
+    auto Bw = [&](int w) { return B + (size_t)w * LS; };
+    auto Fw = [&](int w) { return F + (size_t)w * LS; };
+    auto low = [&](int w) { return scores_low + (size_t)w * N; };
+    auto scratch = [&](int w) { return W.stats + 8 * (size_t)h->dm.max_batch + 16 * (size_t)w; };
+    // lockstep.py:93-100: the lists of every window (the kmax + 1 best by score, the rmax best by race key) in one launch
+    if (!launch_topk_race_batch(scores_low, expo, temp, E, N, N, kk, R, R, L, B, LS, st)) {
+        for (int w = 0; w < E; ++w)  // (the device refused the LDS of the batched ranking: the one-window launches, same lists)
+            if (!launch_topk_race(low(w), R > 0 ? expo + (size_t)w * N : nullptr, temp, N, kk, R, R, Lw(w), Bw(w), st))
+                launch_window_stats(low(w), N, Lw(w) + R, kk, kmin, kmax, 0.f, scratch(w), nullptr, 0.f, Bw(w) + R, st, R);
+    }
+    // lockstep.py:106-110: list positions [rmax - rfirst, rmax + kmin) of every window, window-major, in ONE fp32 scoring pass
+    launch_gather_listed(sample_actions, E, N, (int)row, L, LS, R - rfirst, m0, W.cand, W.widx, st);
+    CHK(check_launch(who));
+    m3pc_plan_args sa = *a;
+    sa.mode = a->mode == M3PC_MODE_RTG ? M3PC_MODE_RTG : M3PC_MODE_CRITIC;
+    sa.precision = M3PC_PREC_FP32;
+    sa.flags = 0;
+    sa.window = 0;
+    sa.n_begin = 0;
+    sa.n_total = sa.n_count = E * m0;
+    CHK(m3pc_score_actions(h, &sa, E, states, actions, rewards, W.cand, W.widx, W.fs, nullptr, nullptr, stream));
+    // lockstep.py:111-123: merge + certificates + select of every window in one launch, the statistics to the windows' host blocks
+    std::vector<int> n_done(E, kmin), r_done(E, rfirst);
+    std::vector<float> d0(E, c->delta), s8((size_t)E * 8);
+    const float seq0 = ls_next_seq(W);
+    MergeSelectBatchP P;
+    memset(&P, 0, sizeof(P));
+    P.b = scores_low;
+    P.expo = expo;
+    P.row_stride = N;
+    P.n_total = N;
+    P.race = R > 0;
+    P.select = 1;
+    P.tau = temp;
+    P.list = L;
+    P.list_scores = B;
+    P.list_stride = LS;
+    P.rmax = R;
+    P.f = W.fs;
+    P.f_stride = m0;
+    P.f_lo = R - rfirst;
+    P.out = merged;
+    P.stats = W.stats;
+    P.host_stats = W.host_dev;
+    P.seq = seq0;
+    P.a0 = sample_actions;
+    P.a0_wstride = N * row;
+    P.a0_stride = row;
+    P.A = A;
+    P.p = p;
+    P.eval_action = eval_action;
+    P.argmax = argmax;
+    P.sample_idx = sample_idx;
+    P.sample_action = sample_action;
+    launch_merge_select_batch(P, E, r_done.data(), n_done.data(), d0.data(), st);
+    for (int w = 0; w < E; ++w) {
+        W.seq_w[w] = seq0;
+        records[w].rounds = 1;
+    }
+    // (the re-scores into the list's layout, where the one-window merges behind the certificates read them)
+    HIPCHK(hipMemcpy2DAsync(F + (R - rfirst), (size_t)LS * sizeof(float), W.fs, (size_t)m0 * sizeof(float), (size_t)m0 * sizeof(float), E,
+                            hipMemcpyDeviceToDevice, st));
+    CHK(check_launch(who));
+    CHK(ls_wait(h, 0, E, R > 0 ? 8 : 4, st, s8.data()));  // the ONE host wait of the first pass: E sequence numbers
+
+    // ---- per window, ascending: certificate.py:resolve with the device work of _WindowOps
+    auto select_w = [&](int w, const float* er) -> int {
+        return m3pc_select(h, er, sample_actions + w * N * row, row, N, temp, expo + (size_t)w * N, p ? p + (size_t)w * N : nullptr,
+                           eval_action ? eval_action + (size_t)w * A : nullptr, argmax ? argmax + w : nullptr,
+                           sample_idx ? sample_idx + w : nullptr, sample_action ? sample_action + (size_t)w * A : nullptr, stream);
+    };
+    auto merge_w = [&](int w, int n, int r, double delta) -> int {  // _WindowOps.merge_select
+        const int o = R - r;
+        float *mw = merged + (size_t)w * N, *dst = W.stats + 8 * (size_t)w, *hst = W.host_dev + 8 * (size_t)w;
+        W.seq_w[w] = ls_next_seq(W);
+        ++records[w].rounds;
+        if (R > 0)
+            return m3pc_merge_race_select(h, low(w), expo + (size_t)w * N, temp, N, Lw(w) + o, r, n, Bw(w) + o, Fw(w) + o, (float)delta, mw, dst,
+                                          hst, W.seq_w[w], sample_actions + w * N * row, row, p ? p + (size_t)w * N : nullptr,
+                                          eval_action ? eval_action + (size_t)w * A : nullptr, argmax ? argmax + w : nullptr,
+                                          sample_idx ? sample_idx + w : nullptr, sample_action ? sample_action + (size_t)w * A : nullptr, stream);
+        CHK(m3pc_rescore_merge(h, low(w), N, Lw(w), n, Bw(w), Fw(w), (float)delta, mw, dst, hst, W.seq_w[w], stream));
+        return select_w(w, mw);
+    };
+    auto rescore_w = [&](int w, int lo, int hi) -> int {  // _WindowOps._score: list positions [lo, hi), chunks of max_rescore
+        for (int c0 = lo; c0 < hi; c0 += cap) {
+            const int m = hi - c0 < cap ? hi - c0 : cap;
+            launch_gather_listed(sample_actions + w * N * row, 1, N, (int)row, Lw(w), LS, c0, m, W.cand, nullptr, st);
+            sa.n_total = sa.n_count = m;
+            CHK(m3pc_score_actions(h, &sa, 1, states + (size_t)w * T * S, actions + (size_t)w * T * A, rewards + (size_t)w * T, W.cand, nullptr,
+                                   Fw(w) + c0, nullptr, nullptr, stream));
+        }
+        return 0;
+    };
+    auto window_set_w = [&](int w, int need, bool everything, double delta) -> int {  // _WindowOps.window_set
+        const int cnt = need < N ? need : N;
+        if (cnt <= 1024 - 32 && !everything) {
+            if (!launch_topk_race(low(w), nullptr, 0.f, N, cnt, 0, R, Lw(w), Bw(w), st))
+                launch_window_stats(low(w), N, Lw(w) + R, cnt, 1, cnt, 0.f, scratch(w), nullptr, 0.f, Bw(w) + R, st, 0);
+            CHK(check_launch("plan_steps_certified (window set)"));
+            CHK(rescore_w(w, R, R + cnt));
+            n_done[w] = cnt;
+            return merge_w(w, cnt, r_done[w], delta);
+        }
+        float* f32 = h->cert_f32[slot];
+        int* top1 = h->cert_top1[slot];
+        float *top1v = scratch(w) + 8, *mw = merged + (size_t)w * N;
+        sa.n_total = sa.n_count = N;
+        CHK(m3pc_score_actions(h, &sa, 1, states + (size_t)w * T * S, actions + (size_t)w * T * A, rewards + (size_t)w * T,
+                               sample_actions + w * N * row, nullptr, f32, nullptr, nullptr, stream));
+        if (!launch_topk_race(f32, nullptr, 0.f, N, 1, 0, 0, top1, top1v, st))
+            launch_window_stats(f32, N, top1, 1, 1, 1, 0.f, scratch(w), nullptr, 0.f, top1v, st, 0);
+        CHK(check_launch("plan_steps_certified (every candidate in fp32)"));
+        n_done[w] = N;  // (r_done stays: the record's n_race is what resolve counted, as in the Python protocol)
+        W.seq_w[w] = ls_next_seq(W);
+        ++records[w].rounds;
+        CHK(m3pc_rescore_merge(h, f32, N, top1, 1, top1v, top1v, 0.f, mw, W.stats + 8 * (size_t)w, W.host_dev + 8 * (size_t)w, W.seq_w[w], stream));
+        return select_w(w, mw);
+    };
+
+    double delta = (double)c->delta;  // (1.5 x a float deviation needs 25 bits: the double the Python protocol keeps)
+    const double delta_first = delta;
+    for (int w = 0; w < E; ++w) {
+        m3pc_cert_record* rec = records + w;
+        float* s = s8.data() + 8 * (size_t)w;
+        bool have = true;  // the statistics of the window's last merge are on the host already
+        if (delta > delta_first) {  // an earlier window raised the bound: this window's certificate again, under it
+            CHK(merge_w(w, n_done[w], r_done[w], delta));
+            have = false;
+        }
+        bool saturated = false, everything = false;
+        int need = 0, need_race = 0;
+        for (bool first = true;; first = false) {
+            if (!have) CHK(ls_wait(h, w, w + 1, everything || R == 0 ? 4 : 8, st, s));
+            have = false;
+            need = (int)s[2];
+            need_race = (int)s[5];
+            if (first) {
+                rec->need_first = need;
+                rec->need_race_first = need_race;
+            }
+            bool redo = false;
+            if (c->grow_delta && 1.5 * (double)s[1] > delta && !everything) {
+                delta = 1.5 * (double)s[1];
+                redo = n_done[w] < N;
+            }
+            if (everything || n_done[w] >= N) break;
+            if (!redo) {
+                if (need > n_done[w] && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
+                    CHK(window_set_w(w, N, true, delta));
+                    everything = true;
+                    continue;
+                }
+                if (need > n_done[w]) {
+                    if (need <= kmax) {
+                        CHK(rescore_w(w, R + n_done[w], R + need));
+                        n_done[w] = need;
+                        redo = true;
+                    } else {
+                        CHK(window_set_w(w, need, false, delta));
+                        saturated = true;
+                        everything = n_done[w] >= N;
+                        continue;
+                    }
+                }
+                if (need_race > r_done[w]) {
+                    if (need_race <= R) {
+                        CHK(rescore_w(w, R - need_race, R - r_done[w]));
+                        r_done[w] = need_race;
+                        redo = true;
+                    } else {  // more racers than the race list holds: every candidate in fp32
+                        CHK(window_set_w(w, N, true, delta));
+                        saturated = everything = true;
+                        continue;
+                    }
+                }
+            }
+            if (!redo) break;
+            CHK(merge_w(w, n_done[w], r_done[w], delta));
+        }
+        rec->n_rescored = n_done[w];
+        rec->n_race = r_done[w];
+        rec->saturated = saturated;
+        rec->everything = everything;
+        rec->certified = everything || n_done[w] >= N || (need <= n_done[w] && need_race <= r_done[w]);
+        rec->delta = (float)delta;
+        rec->shift = s[0];
+        rec->deviation = s[1];
+        rec->margin = s[3];
+    }
+    return 0;
+}
+
 int m3pc_draw_variates(m3pc_handle* h, unsigned long long seed, unsigned long long step, int n_begin, int n_count, int row_elems,
                        float* eps, float* expo, void* stream) {
     if (!h) return fail(M3PC_EINVAL, "null handle");
@@ -2164,6 +2490,31 @@ int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a) {
     P.sample_action = a->sample_action;
     launch_merge_select_batch(P, a->n_windows, a->r, a->n, a->delta, (hipStream_t)a->stream);
     return check_launch("debug_merge_select_batch");
+}
+// the select of n_windows windows in one launch (the fp32 form of m3pc_plan_steps_certified): m3pc_select's checks, per window
+int m3pc_debug_select_batch(const float* scores, const float* a0, long long a0_window_stride, long long a0_stride, int n_windows,
+                            int n_total, int A, float temperature, const float* expo, float* p, float* eval_action, int* argmax,
+                            int* sample_idx, float* sample_action, void* stream) {
+    if (!scores || n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "bad argument");
+    if (n_windows < 1 || n_windows > 65535) return fail(M3PC_EINVAL, "n_windows %d outside [1, 65535]", n_windows);
+    if ((eval_action || sample_action) && (!a0 || A < 1 || A > 1024)) return fail(M3PC_EINVAL, "eval_action / sample_action need a0");
+    if ((sample_idx || sample_action) && !expo) return fail(M3PC_EINVAL, "the multinomial draw needs expo");
+    SelectP s;
+    memset(&s, 0, sizeof(s));
+    s.er = scores;
+    s.a0 = a0;
+    s.a0_stride = a0_stride;
+    s.n = n_total;
+    s.A = A;
+    s.temperature = temperature;
+    s.expo = expo;
+    s.p = p;
+    s.eval_action = eval_action;
+    s.argmax = argmax;
+    s.sample_idx = sample_idx;
+    s.sample_action = sample_action;
+    launch_select_batch(s, n_windows, n_total, a0_window_stride, (hipStream_t)stream);
+    return check_launch("debug_select_batch");
 }
 
 // Not part of the public header (tests/test_block_fused_gpu.py, tools/block_bench.py): the fused layer tail on its own.

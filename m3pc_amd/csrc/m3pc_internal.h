@@ -176,6 +176,23 @@ struct m3pc_handle {
         int rounds = 0, n_done = 0, r_done = 0;
         float seq = 0.f;
     } cstep[M3PC_SLOTS];
+    // m3pc_plan_steps_certified (a lock-step batch of certified steps): what a certified step keeps per slot, per WINDOW of the
+    // batch, sized by max_batch and allocated at the first call.  list / b / f: rows of rmax + 1024 entries (ids when the caller
+    // brings no list, low-precision scores, fp32 re-scores in the list's layout); stats: 8 floats per window of the merges, then
+    // 16 per window of scratch (the 4 of a window-statistics launch, the best fp32 score of the every-candidate pass at +8);
+    // host: one host-mapped 8-float block per window, closed by the sequence number the window's last merge carried (seq_w) --
+    // ONE counter (seq) serves the batched launch and the one-window merges behind it; cand / widx / fs: the gathered candidate
+    // rows of one scoring call (cand_rows of them), their window indices and their scores.
+    struct Lockstep {
+        bool ready = false;
+        int* list = nullptr;
+        float *b = nullptr, *f = nullptr, *stats = nullptr, *cand = nullptr, *fs = nullptr;
+        int* widx = nullptr;
+        float *host = nullptr, *host_dev = nullptr;
+        long long cand_rows = 0;
+        int seq = 0;
+        std::vector<float> seq_w;
+    } ls;
     // Pipelined certified steps: the two chain streams (slot parity; the caller's pair of m3pc_set_step_streams or the handle's
     // own, created at the first _begin), the events of a slot, and the order of the candidate workspace across steps:
     // ev_cand_last behind the candidate pass enqueued last, ev_excl behind the last few-row-workspace overflow (a re-score of

@@ -95,6 +95,26 @@ void launch_select(const SelectP& p, hipStream_t st) {
     if (p.n <= 0) return;
     hipLaunchKernelGGL(select_kernel, dim3(1), dim3(1024), 0, st, p);
 }
+// select_kernel for E lock-step windows (the fp32 form of m3pc_plan_steps_certified): workgroup w is window w on its rows of the
+// (E, n) arrays -- select_body itself, so a window's results are m3pc_select's on its row bit for bit.
+__global__ __launch_bounds__(1024) void select_batch_kernel(SelectP p, long long row_stride, long long a0_wstride) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    const long long w = blockIdx.x;
+    p.er += w * row_stride;
+    if (p.a0) p.a0 += w * a0_wstride;
+    if (p.expo) p.expo += w * row_stride;
+    if (p.p) p.p += w * row_stride;
+    if (p.eval_action) p.eval_action += w * p.A;
+    if (p.argmax) p.argmax += w;
+    if (p.sample_idx) p.sample_idx += w;
+    if (p.sample_action) p.sample_action += w * p.A;
+    select_body(p, sv, si);
+}
+void launch_select_batch(const SelectP& p, int E, long long row_stride, long long a0_wstride, hipStream_t st) {
+    if (p.n <= 0 || E <= 0) return;
+    hipLaunchKernelGGL(select_batch_kernel, dim3((unsigned)E), dim3(1024), 0, st, p, row_stride, a0_wstride);
+}
 
 // ---------------------------------------------------------------------------------------------- top-k
 // Bitonic sort of 64-bit keys {orderable(value), ~index} in LDS (descending), first k indices out.

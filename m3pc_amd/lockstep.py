@@ -1,10 +1,13 @@
 """Environments that step together (``HipPlanner.action_sample_batch(lockstep=True)``): ONE policy pass at batch E
 (m3pc_policy_pass_batch), every window's own candidate pass back to back, ONE fp32 re-score pass over all windows' re-score
 sets (m3pc_score_actions) and one host read of all certificates -- the fp32 chains are paid once per call instead of once
-per window.  A mixin of ``HipPlanner``; the certificate protocol itself is m3pc_amd/certificate.py."""
+per window.  ``lockstep="native"`` runs the same protocol as ONE library call per group of windows (m3pc_plan_steps_certified,
+``_native_group``): per window the bits of the Python path.  A mixin of ``HipPlanner``; the certificate protocol itself is
+m3pc_amd/certificate.py."""
 from __future__ import annotations
 
 import types
+import warnings
 
 import numpy as np
 import torch
@@ -16,7 +19,12 @@ _MODES = {"rtg_guiding": capi.MODE_RTG, "critic_lambda_guiding": capi.MODE_CRITI
 
 
 class LockstepMixin:
-    def _action_sample_lockstep(self, sequence_histories, percentage=1.0, eval=False, rtg=None, onepass: bool = False):
+    def _action_sample_lockstep(self, sequence_histories, percentage=1.0, eval=False, rtg=None, onepass: bool = False,
+                                native: bool = False):
+        if native and self.precision in capi.LOW_PRECISION and self.rescore != "bound":
+            # (the call runs the certificate protocol on a low-precision pass; rescore="topk" / "none" select differently)
+            raise ValueError(f"lockstep='native' runs the certified re-score (rescore='bound') behind a low-precision candidate pass; "
+                             f"rescore={self.rescore!r} is served by lockstep=True")
         self._drain()
         cfg = self.cfg
         guidance = cfg.plan_guidance
@@ -45,6 +53,11 @@ class LockstepMixin:
             r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
             Eg = len(ids)
             eps = self._eps((Eg, N, h, A)) if mode == capi.MODE_NOISE else self._eps((Eg, N, T, A))
+            # lockstep="native": the whole group in ONE library call (m3pc_plan_steps_certified).  While the weight load's
+            # calibration windows are not used up the group takes the Python path below -- that path is what calibrates
+            if native and not (self.rescore == "bound" and self._delta_fixed is None and (self._delta0 is None or self._cal_left > 0)):
+                self._native_group(mode, s, a, r, [meta[i][1] for i in ids], eps, h, lmbda, ids, eval, out, info)
+                continue
             if onepass:
                 res = self.handle.plan_step_batch(mode, s, a, r, [meta[i][1] for i in ids], eps, h, lmbda, float(cfg.discount), N,
                                                   precision=self.precision)
@@ -151,4 +164,54 @@ class LockstepMixin:
         self._mark_main()
         self.last = dict(windows=info, delta=self._delta)
         return out
+
+    def _native_group(self, mode, s, a, r, rtgs, eps, h, lmbda, ids, eval, out, info):
+        """One group of a lock-step batch through m3pc_plan_steps_certified: the draws, the first-pass sizes and the bound are
+        those of the Python path above; ``info`` and the bound are filled from the windows' records.  Two things are the
+        records' and not the Python path's: ``delta_grown`` counts the WINDOWS that came out with a larger bound (``resolve``
+        counts every raise, and a window may raise more than once), and the bound folded back into ``_delta0`` is
+        ``records[-1].delta``, the float the ABI carries, where the Python path keeps the double 1.5 x deviation -- the same
+        number after one rounding to float, which is what every kernel is given."""
+        cfg = self.cfg
+        Eg, N = len(ids), int(cfg.action_samples)
+        # the multinomial's exponentials, window by window: the generator is consumed exactly as by the Python path
+        expo = torch.empty((Eg, N), dtype=torch.float32, device=self.device)
+        for w in range(Eg):
+            expo[w].exponential_(1, generator=self.generator)
+        bound = self.rescore == "bound"
+        R = self._R if bound else 0
+        kmin = kmax = 1
+        rfirst, delta = 0, 0.0
+        if bound:
+            kmax = max(min(self.rescore_max, N - 1 if N > 1 else 1, 1024 - self._R - 1), 1)
+            rfirst = max(min(self.race_min, R), 1) if R > 0 else 0
+            kmin = max(min(self.rescore_min - rfirst, N, kmax), 1)
+            delta = float(self._delta)
+        res, recs = self.handle.plan_steps_certified(mode, s, a, r, rtgs, eps, expo, h, lmbda, float(cfg.discount), N,
+                                                     float(cfg.temperature), delta=delta,
+                                                     grow_delta=bound and self._delta_fixed is None, kmin=kmin, kmax=kmax,
+                                                     rfirst=rfirst, rmax=R, precision=self.precision, slot=0, want_policy=False,
+                                                     want_list=False, want_p=False)
+        if bound:
+            seen = float(np.float32(delta))
+            for rec in recs:  # (a window that raised the bound raised it for every later window of the group)
+                if rec.delta > seen:
+                    seen = float(rec.delta)
+                    self.delta_grown += 1
+            if seen > float(np.float32(delta)):
+                self._delta0 = max(self._delta0, float(recs[-1].delta))
+            if any(rec.saturated for rec in recs) and not self._warned_saturated:
+                self._warned_saturated = True
+                warnings.warn(f"m3pc_amd: the certificates of a lock-step window asked for more candidates than it lists "
+                              f"(delta={recs[-1].delta:.3g}, rescore_max={self.rescore_max}); the whole window set or every candidate "
+                              f"was re-scored in fp32 (slow path)")
+        _, ev, am, si, sa = res["sel"]
+        for j, i in enumerate(ids):
+            out[i] = ev[j] if eval else sa[j]
+            rec = recs[j] if bound else None
+            info[i] = dict(expect_return=res["expect_return"][j], argmax=am[j : j + 1], sample_idx=si[j : j + 1], eval_action=ev[j],
+                           sample_action=sa[j : j + 1], horizon=h,
+                           n_rescored=None if rec is None else int(rec.n_rescored), n_race=None if rec is None else int(rec.n_race),
+                           min_margin_outside=None if rec is None else float(rec.margin),
+                           saturated=None if rec is None else bool(rec.saturated), delta=self._delta)
 

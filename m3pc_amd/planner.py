@@ -1076,10 +1076,15 @@ class HipPlanner(GoalMixin, LockstepMixin):
         paid once per call instead of once per window (needs ``HipPlanner(..., max_batch=E, max_windows=E)``; windows grouped by
         effective horizon; the few-row fp32 kernels choose their tiling by the row count, so a window's result agrees with the
         single-window call to fp32 rounding, not bit for bit).  ``lockstep="onepass"``: the round-2 form, one candidate pass
-        over E x N rows with a per-candidate window index (no history sharing between windows).
+        over E x N rows with a per-candidate window index (no history sharing between windows).  ``lockstep="native"``: the
+        protocol of ``lockstep=True`` as ONE library call per group of windows (m3pc_plan_steps_certified: the lists, the gather and
+        the merge + select of all windows in one launch each); per window bit-identical to ``lockstep=True`` for the same
+        generator state and bound.  Groups that still calibrate the bound (the first windows behind a weight load) take the
+        ``lockstep=True`` path; ``rescore="topk"`` is not served (ValueError).
         ``rtg``: None, a float, or one value per window.  Returns (E, A)."""
         if lockstep:
-            return self._action_sample_lockstep(sequence_histories, percentage, eval, rtg, onepass=lockstep == "onepass")
+            return self._action_sample_lockstep(sequence_histories, percentage, eval, rtg, onepass=lockstep == "onepass",
+                                                native=lockstep == "native")
         E, A = len(sequence_histories), self.A
         rtgs = [rtg] * E if (rtg is None or np.isscalar(rtg)) else list(rtg)
         out = torch.empty((E, A), dtype=torch.float32, device=self.device)
