@@ -45,7 +45,8 @@ extern "C" {
 /* ABI history.  Added within v7 (new symbols and structures only; nothing existing changed): m3pc_plan_step_certified,
  * m3pc_calibrate_delta, m3pc_cert_args, m3pc_cert_record; then m3pc_plan_step_certified_begin / _end, m3pc_set_step_streams and
  * m3pc_draw_variates; then m3pc_refit_resample, m3pc_refine_plan and m3pc_refine_args (CEM / MPPI refinement); then
- * m3pc_plan_steps_certified (a lock-step batch of certified steps).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * m3pc_plan_steps_certified (a lock-step batch of certified steps); then m3pc_eval_bound, m3pc_plan_step_certified_eval and
+ * m3pc_eval_record (the eval_action certificate).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -463,6 +464,70 @@ int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* args, const m
                              const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std,
                              float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
                              int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* record, void* stream);
+
+/* The THIRD certificate: eval_action (learner.py:318-323), the softmax-weighted mean of the first actions over ALL candidates and
+ * what every eval=True call returns.  Candidates that were not re-scored enter it with shift-corrected low-precision scores; under
+ * the model the other two certificates rest on -- every un-re-scored merged score is within delta of its fp32 value -- the
+ * deviation of eval_action from the fp32 step's is bounded per step.  After the last merge, with m the merged vector, L the
+ * re-scored candidates (race and score entries: m_j = f_j there), U all others, tau the temperature, eps = tau delta,
+ * p = softmax(tau (m - max m)) and e = sum_j p_j a0_j the eval_action the select produced, for every action component k:
+ *     S_k = sum_{j in U} p_j |a0_jk - e_k|      P_U = sum_{j in U} p_j
+ *     B_k = expm1(eps) S_k / (1 - (1 - exp(-eps)) P_U)      eval_bound = max_k B_k
+ * Claim: if |m_j - f_j| <= delta on U, then |e_k - e32_k| <= B_k, e32 being the select on fp32 scores.  (The fp32 weights are
+ * w_j r_j with r_j in [exp(-eps), exp(eps)] on U and 1 on L; sum_j w_j (a_j - e) = 0 gives
+ * e32 - e = sum_U w_j (r_j - 1)(a_j - e) / sum_j w_j r_j; the numerator is at most expm1(eps) sum_U w_j |a_j - e|, the denominator
+ * at least W (1 - (1 - exp(-eps)) P_U).)  delta is calibrated, not proven (m3pc_calibrate_delta): the bound inherits the measured
+ * exceedance rate of the other two certificates.
+ * need_eval: the score list holds n_listed entries (best low-precision score first), the first n of them re-scored.  bound(n'),
+ * n <= n' <= n_listed, is the formula on the CURRENT m and e with the score entries n .. n'-1 moved from U to L (an entry that is a
+ * re-scored race entry too is in L either way and counts once); it does not increase with n'.  need_eval = the smallest n' with
+ * bound(n') <= eval_tol, or n_total when even bound(n_listed) exceeds it (the list cannot reach the tolerance).
+ *
+ * m3pc_eval_bound: the certificate as a call (one launch of one workgroup; fixed-order reductions: bit-identical from run to run).
+ *   merged     device (n_total,): the vector the select ran on;  a0 device (n_total, A) rows of stride a0_stride floats
+ *   list       device int32: r re-scored race entries, then n_listed score entries -- the layout m3pc_rescore_merge_race takes, with
+ *              the listed but un-re-scored score entries behind the n re-scored ones.  An id outside [0, n_total) is ignored.
+ *   eval_tol   > 0; +inf: report only (need_eval = n)
+ *   stats      device out float[8] = {eval_bound = bound(n), need_eval, P_U, the k that attains eval_bound, -, eps, bound(n_listed),
+ *              |U|};  host_stats / seq: optional host-mapped float[8] copy closed by `seq` in slot 4, as m3pc_rescore_merge
+ * M3PC_EINVAL before any HIP call: a null required pointer (h, merged, list, a0, stats), eval_tol <= 0 or NaN, delta < 0 or NaN,
+ * n_total outside [1, 16384], A outside [1, 1024], r < 0, r + n_listed > 1024, n outside [0, n_listed].  The temperature enters as
+ * |temperature|. */
+int m3pc_eval_bound(m3pc_handle* h, const float* merged, int n_total, const int* list, int r, int n, int n_listed, const float* a0,
+                    long long a0_stride, int A, float temperature, float delta, float eval_tol, float* stats, float* host_stats,
+                    float seq, void* stream);
+
+/* m3pc_plan_step_certified with the eval_action certificate as a third one beside `need` and `need_race`: the same step, and once
+ * the arg-max and race certificates are satisfied and nothing is to be redone, m3pc_eval_bound runs behind the last merge + select
+ * (list = the re-scored race entries and the kmax listed score entries, delta = the bound as it stands) and reports into a second
+ * host-mapped block of the step slot (allocated at the first such call; the bounded wait of m3pc_plan_step_certified).
+ *   need_eval > n_rescored, need_eval <= kmax: m3pc_rescore of the score entries up to need_eval, merge + select again, all three
+ *   certificates read again (grow_delta may raise delta and ask again); n_rescored strictly grows, so the loop ends.
+ *   need_eval = n_total (the list cannot reach eval_tol; also behind a window set, whose list is wholly re-scored): the existing
+ *   every-candidate-in-fp32 path; records: everything = 1, eval_bound = 0, eval_certified = 1.
+ *   args->precision == M3PC_PREC_FP32: erec = {0, 0, 0, 0, 1}.
+ *   eval_tol = +inf: ONE bound launch, no extension -- every output buffer and every field of `record` is bit for bit what
+ *   m3pc_plan_step_certified gives on the same inputs.
+ * Which tier reaches a tolerance: at a nearly flat softmax (rtg guidance, temperature 0.01) bf16's delta leaves a bound of ~3e-2
+ * that no list lowers to 1e-3 -- the tier that certifies eval_action there is M3PC_PREC_BF16X3 (bound ~6e-5 with nothing extra
+ * re-scored); where the list holds a good share of the softmax weight (few candidates, peaked scores) a few dozen fp32 rows
+ * tighten a bf16 step's bound.  DESIGN.md section 5 has the measured table.
+ * Refusals: those of m3pc_plan_step_certified, plus erec == NULL and eval_tol <= 0 or NaN (M3PC_EINVAL, before any HIP call), plus
+ * M3PC_ESTATE while a pipelined step is begun.
+ * Out of scope: a _begin / _end split and a lock-step (m3pc_plan_steps_certified) form of the eval certificate. */
+typedef struct m3pc_eval_record {
+    float eval_bound;      /* the LAST bound: |eval_action - fp32 eval_action| <= eval_bound under the delta model; 0 after `everything` */
+    int need_eval_first;   /* what the FIRST eval certificate asked for (n_total: the list could not reach eval_tol) */
+    int n_eval;            /* score entries re-scored because THIS certificate asked, beyond what the other two asked for */
+    int eval_rounds;       /* bound launches */
+    int eval_certified;    /* eval_bound <= eval_tol at the end */
+} m3pc_eval_record;
+
+int m3pc_plan_step_certified_eval(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_cert_args* cert, const float* states,
+                                  const float* actions, const float* rewards, const float* eps, const float* expo, float* loc,
+                                  float* std, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
+                                  float* eval_action, int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* record,
+                                  float eval_tol, m3pc_eval_record* erec, void* stream);
 
 /* Pipelined certified steps: m3pc_plan_step_certified in two halves, so that a host keeps up to M3PC_SLOTS steps in flight (the
  * rate of m3pc_amd/planner.py's plan_async, from the library alone).  _begin enqueues and returns: it reads nothing from the device

@@ -47,6 +47,7 @@ EXPORTS = (
     "m3pc_set_step_streams", "m3pc_plan_step_certified_begin", "m3pc_plan_step_certified_end", "m3pc_draw_variates",
     "m3pc_refit_resample", "m3pc_refine_plan",
     "m3pc_plan_steps_certified",
+    "m3pc_eval_bound", "m3pc_plan_step_certified_eval",
 )
 
 
@@ -78,6 +79,12 @@ class CertRecord(C.Structure):
     _fields_ = [("n_rescored", C.c_int), ("n_race", C.c_int), ("need_first", C.c_int), ("need_race_first", C.c_int),
                 ("saturated", C.c_int), ("everything", C.c_int), ("certified", C.c_int), ("rounds", C.c_int),
                 ("delta", C.c_float), ("shift", C.c_float), ("deviation", C.c_float), ("margin", C.c_float)]
+
+
+class EvalRecord(C.Structure):
+    """m3pc_eval_record: what the eval_action certificate of ``m3pc_plan_step_certified_eval`` bounded and asked for."""
+    _fields_ = [("eval_bound", C.c_float), ("need_eval_first", C.c_int), ("n_eval", C.c_int), ("eval_rounds", C.c_int),
+                ("eval_certified", C.c_int)]
 
 
 class RefineArgs(C.Structure):
@@ -149,6 +156,9 @@ def load_library(path: Optional[str] = None):
                                      vp, vp, vp, C.POINTER(CertRecord), vp],
         "m3pc_plan_steps_certified": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), i, vp, vp, vp, C.POINTER(d), vp, vp, vp, vp, vp, vp,
                                       vp, vp, vp, vp, vp, vp, vp, C.POINTER(CertRecord), vp],
+        "m3pc_eval_bound": [vp, vp, i, vp, i, i, i, vp, ll, i, f, f, f, vp, vp, f, vp],
+        "m3pc_plan_step_certified_eval": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, vp, vp, C.POINTER(CertRecord), f, C.POINTER(EvalRecord), vp],
         "m3pc_calibrate_delta": [vp, C.POINTER(PlanArgs), vp, vp, vp, vp, vp, f, C.POINTER(f), vp],
         "m3pc_set_step_streams": [vp, vp, vp],
         "m3pc_plan_step_certified_begin": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -476,13 +486,14 @@ class Handle:
     def plan_step_certified(self, mode: int, states, actions, rewards, eps, expo, horizon: int, rtg: float, lmbda: float,
                             discount: float, n_total: int, temperature: float, delta: float = 0.0, grow_delta: bool = False,
                             kmin: int = 8, kmax: int = 128, rfirst: int = 2, rmax: int = 32, precision: int = PREC_BF16,
-                            slot: int = 0, returns=None, pruned: bool = False):
+                            slot: int = 0, returns=None, pruned: bool = False, eval_tol: Optional[float] = None):
         """One certified plan step in ONE library call (m3pc_plan_step_certified): policy pass, candidate pass in ``precision``,
         lists, fp32 re-scores, certificates and select on the current stream.  Returns (res, record): ``res`` holds loc, std,
         sample_actions, expect_return_low, expect_return (the merged vector), list (rmax + 1024 int32: race entries in front of
         ``rmax``, score entries behind) and sel = (p, eval_action, argmax, sample_idx, sample_action); ``record`` is the
         ``CertRecord`` of the step.  The host has read the step's last certificate when the call returns; the tensors are
-        complete in stream order."""
+        complete in stream order.  eval_tol (``plan_step_certified_eval``): the call is m3pc_plan_step_certified_eval and the return
+        value (res, record, eval_record)."""
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         loc = torch.empty((self.T, self.A), **f32)
@@ -498,10 +509,43 @@ class Handle:
         rec = CertRecord()
         ins = [self._f32(t) for t in (states, actions, rewards, eps)]
         assert expo.numel() == n_total and expo.dtype == torch.float32 and expo.is_contiguous()
+        res = dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel)
+        if eval_tol is not None:
+            erec = EvalRecord()
+            check(self.lib.m3pc_plan_step_certified_eval(self._h, C.byref(args), C.byref(cert), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
+                                                         _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low),
+                                                         _ptr(merged), _ptr(lst), *[_ptr(t) for t in sel], C.byref(rec),
+                                                         float(eval_tol), C.byref(erec), _stream(dev)))
+            return res, rec, erec
         check(self.lib.m3pc_plan_step_certified(self._h, C.byref(args), C.byref(cert), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
                                                 _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low), _ptr(merged),
                                                 _ptr(lst), *[_ptr(t) for t in sel], C.byref(rec), _stream(dev)))
-        return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel), rec
+        return res, rec
+
+    def plan_step_certified_eval(self, mode: int, states, actions, rewards, eps, expo, horizon: int, rtg: float, lmbda: float,
+                                 discount: float, n_total: int, temperature: float, eval_tol: float = float("inf"), **kw):
+        """``plan_step_certified`` with the eval_action certificate (m3pc_plan_step_certified_eval): the step re-scores score entries
+        until |eval_action - the fp32 step's| <= eval_tol under the delta model, or scores every candidate in fp32 when its list
+        cannot reach that.  eval_tol = inf: report only.  Returns (res, record, eval_record); keywords as ``plan_step_certified``."""
+        return self.plan_step_certified(mode, states, actions, rewards, eps, expo, horizon, rtg, lmbda, discount, n_total, temperature,
+                                        eval_tol=float(eval_tol), **kw)
+
+    def eval_bound(self, merged: torch.Tensor, lst: torch.Tensor, r: int, n: int, n_listed: int, a0: torch.Tensor, temperature: float,
+                   delta: float, eval_tol: float = float("inf"), stats: Optional[torch.Tensor] = None, host_stats=None, seq: float = 0.0):
+        """The eval_action certificate on a merged vector (m3pc_eval_bound): lst = r re-scored race entries, then n_listed score
+        entries of which the first n are re-scored; a0: (N, A) view (may be strided).  Returns the device stats (8 floats) =
+        [eval_bound, need_eval, P_U, arg-max component, -, eps, bound(n_listed), |U|]."""
+        nt = merged.numel()
+        assert merged.is_contiguous() and merged.dtype == torch.float32 and lst.dtype == torch.int32 and lst.is_contiguous()
+        assert a0.shape[0] == nt and a0.stride(-1) == 1 and a0.dtype == torch.float32 and lst.numel() >= r + n_listed
+        if stats is None:
+            stats = torch.empty((8,), dtype=torch.float32, device=self.device)
+        assert stats.numel() >= 8
+        check(self.lib.m3pc_eval_bound(self._h, _ptr(merged), nt, _ptr(lst), int(r), int(n), int(n_listed), _ptr(a0), a0.stride(0),
+                                       a0.shape[1], float(temperature), float(delta), float(eval_tol), _ptr(stats),
+                                       None if host_stats is None else C.c_void_p(host_stats.data_ptr()), float(seq),
+                                       _stream(self.device)))
+        return stats
 
     def plan_steps_certified(self, mode: int, states, actions, rewards, rtg, eps, expo, horizon: int, lmbda: float, discount: float,
                              n_total: int, temperature: float, delta: float = 0.0, grow_delta: bool = False, kmin: int = 8,

@@ -543,6 +543,14 @@ void launch_merge_select_batch(MergeSelectBatchP& P, int E, const int* r, const 
 // calibration statistics over all n <= 16384 candidates (one workgroup): d = b - f, c = lower median of d (value, then index);
 // stats (8 floats) = {c, max |d - c|, max |f|, 0, -, 0, 0, 0}; host_stats / seq as launch_rescore_merge
 void launch_deviation_stats(const float* b, const float* f, int n, float* stats, float* host_stats, float seq, hipStream_t st);
+// the eval_action certificate (one workgroup, n_total <= 16384, A <= 1024, r + n_listed <= 1024): m = the merged vector the select
+// ran on, list = r re-scored race entries then n_listed score entries (best low-precision score first) of which the first n are
+// re-scored.  With p / e the select's weights and eval_action on m, U = the candidates that are not re-scored and eps = tau delta:
+//   B_k = expm1(eps) sum_U p_j |a0_jk - e_k| / (1 - (1 - exp(-eps)) sum_U p_j), bound(n') = max_k B_k with the score entries n .. n'-1
+//   taken out of U.  stats (8 floats) = {bound(n), need_eval = the smallest n' in [n, n_listed] with bound(n') <= eval_tol (n_total:
+//   none), P_U, arg-max k of B_k, -, eps, bound(n_listed), |U|}; host_stats / seq as launch_rescore_merge
+void launch_eval_bound(const float* m, int n_total, const int* list, int r, int n, int n_listed, const float* a0, long long a0_stride,
+                       int A, float tau, float delta, float eval_tol, float* stats, float* host_stats, float seq, hipStream_t st);
 // counter-based variates (Philox4x32-10 of (seed, step, array, element / 4)): out[0 .. g1 - g0) = elements [g0, g1) of the flat array;
 // array 0 = standard normals (Box-Muller), 1 = Exp(1), never 0
 void launch_variates(unsigned long long seed, unsigned long long step, int array, long long g0, long long g1, float* out, hipStream_t st);

@@ -252,6 +252,7 @@ int m3pc_destroy(m3pc_handle* h) {
         for (int i = 0; i < 2; ++i)
             if (h->step_chain[i]) hipStreamDestroy(h->step_chain[i]);
     if (h->cert_host) hipHostFree(h->cert_host);
+    if (h->eval_host) hipHostFree(h->eval_host);
     {
         void* lb[] = {h->ls.list, h->ls.b, h->ls.f, h->ls.stats, h->ls.cand, h->ls.fs, h->ls.widx};
         for (void* b : lb)
@@ -1280,17 +1281,33 @@ int m3pc_select(m3pc_handle* h, const float* expect_return, const float* a0, lon
     return check_launch("select");
 }
 
+int m3pc_eval_bound(m3pc_handle* h, const float* merged, int n_total, const int* list, int r, int n, int n_listed, const float* a0,
+                    long long a0_stride, int A, float temperature, float delta, float eval_tol, float* stats, float* host_stats,
+                    float seq, void* stream) {
+    if (!h || !merged || !list || !a0 || !stats) return fail(M3PC_EINVAL, "null argument");
+    if (!(eval_tol > 0.f)) return fail(M3PC_EINVAL, "eval_tol must be > 0 (+inf: report only)");
+    if (!(delta >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
+    if (n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "n_total %d outside [1, 16384]", n_total);
+    if (A < 1 || A > 1024) return fail(M3PC_EINVAL, "A %d outside [1, 1024]", A);
+    if (r < 0 || n_listed < 0 || r + n_listed > 1024) return fail(M3PC_EINVAL, "r %d + n_listed %d outside [0, 1024]", r, n_listed);
+    if (n < 0 || n > n_listed) return fail(M3PC_EINVAL, "n %d outside [0, n_listed=%d]", n, n_listed);
+    if (!(temperature == temperature)) return fail(M3PC_EINVAL, "temperature is not a number");
+    HIPCHK(hipSetDevice(h->device));
+    launch_eval_bound(merged, n_total, list, r, n, n_listed, a0, a0_stride, A, temperature, delta, eval_tol, stats, host_stats, seq,
+                      (hipStream_t)stream);
+    return check_launch("eval_bound");
+}
+
 // ---- the certified plan step as one call (learner.py:318-325 on low-precision scores that fp32 re-scores certify)
 // The statistics of the kernel that carried `seq`, read from the slot's host-mapped block: a BOUNDED spin on the sequence number
 // (10 s, the bound of the Python binding's HostStats.wait); on expiry one synchronisation of the stream and the device copy.
-static int cert_wait(m3pc_handle* h, int slot, float seq, int n_device, hipStream_t st, float out[8]) {
-    const volatile float* hs = h->cert_host + 8 * slot;
+static int cert_wait_block(const volatile float* hs, const float* dev, float seq, int n_device, hipStream_t st, float out[8]) {
     const auto t0 = std::chrono::steady_clock::now();
     unsigned spins = 0;
     while (hs[4] != seq) {
         if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
             if (hipStreamSynchronize(st) != hipSuccess ||
-                hipMemcpy(out, h->cert_stats[slot], 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                hipMemcpy(out, dev, 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(M3PC_EHIP, "the statistics of the certified step reached neither host-mapped memory within 10 s nor the host by a copy");
             for (int i = n_device; i < 8; ++i) out[i] = 0.f;  // (a four-statistics merge leaves the device slots 4..7 alone)
             return 0;
@@ -1299,6 +1316,9 @@ static int cert_wait(m3pc_handle* h, int slot, float seq, int n_device, hipStrea
     std::atomic_thread_fence(std::memory_order_acquire);
     for (int i = 0; i < 8; ++i) out[i] = hs[i];
     return 0;
+}
+static int cert_wait(m3pc_handle* h, int slot, float seq, int n_device, hipStream_t st, float out[8]) {
+    return cert_wait_block(h->cert_host + 8 * slot, h->cert_stats[slot], seq, n_device, st, out);
 }
 static float cert_next_seq(m3pc_handle* h, int slot) {
     h->cert_seq[slot] = h->cert_seq[slot] % 1000000 + 1;
@@ -1459,64 +1479,109 @@ static int cert_first_pass(m3pc_handle* h, CertStep& S) {
 }
 // m3pc_amd/certificate.py:resolve -- read the certificates; raise delta when the re-scored set deviates by more than it
 // allows; re-score what a certificate asks for; stop when both are satisfied or every candidate has been scored in fp32
-static int cert_resolve(m3pc_handle* h, CertStep& S, m3pc_cert_record* rec) {
+// The eval_action certificate of m3pc_plan_step_certified_eval behind the step's last merge + select: the re-scored race entries
+// and the listed score entries (kmax of them; behind a window set the list is wholly re-scored), under delta as it stands.
+static int cert_eval_bound(m3pc_handle* h, CertStep& S, int n_listed, float eval_tol, float e8[8]) {
+    const int slot = S.a.slot, R = S.c.rmax;
+    float* dstats = h->cert_stats[slot] + 24;
+    h->eval_seq[slot] = h->eval_seq[slot] % 1000000 + 1;
+    const float seq = (float)h->eval_seq[slot];
+    CHK(m3pc_eval_bound(h, S.merged, S.a.n_total, cert_L(h, S) + R - S.r_done, S.r_done, S.n_done, n_listed, S.sample_actions,
+                        (long long)S.a.horizon * h->A, h->A, S.c.temperature, (float)S.delta, eval_tol, dstats, h->eval_host_dev + 8 * slot,
+                        seq, S.tail));
+    return cert_wait_block(h->eval_host + 8 * slot, dstats, seq, 8, S.tail, e8);
+}
+// eval_tol / erec: the third certificate (m3pc_plan_step_certified_eval); erec == NULL: the two certificates alone, nothing else
+// launched, read or allocated
+static int cert_resolve(m3pc_handle* h, CertStep& S, m3pc_cert_record* rec, float eval_tol = 0.f, m3pc_eval_record* erec = nullptr) {
     const int slot = S.a.slot, N = S.a.n_total, R = S.c.rmax, kmax = S.c.kmax;
     memset(rec, 0, sizeof(*rec));
+    if (erec) memset(erec, 0, sizeof(*erec));
     if (S.a.precision == M3PC_PREC_FP32) {
         rec->n_rescored = N;
         rec->everything = rec->certified = 1;
+        if (erec) erec->eval_certified = 1;
         return 0;
     }
     const int n_device = R > 0 ? 8 : 4;
     bool saturated = false, everything = false;
     int need = 0, need_race = 0;
     float s8[8];
-    for (bool first = true;; first = false) {
-        CHK(cert_wait(h, slot, S.seq, everything || R == 0 ? 4 : n_device, S.tail, s8));
-        need = (int)s8[2];
-        need_race = (int)s8[5];
-        if (first) {
-            rec->need_first = need;
-            rec->need_race_first = need_race;
-        }
-        bool redo = false;
-        if (S.c.grow_delta && 1.5 * (double)s8[1] > S.delta && !everything) {
-            S.delta = 1.5 * (double)s8[1];
-            redo = S.n_done < N;
-        }
-        if (everything || S.n_done >= N) break;
-        if (!redo) {
-            if (need > S.n_done && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
-                CHK(cert_window_set(h, S, N, true));
-                everything = true;
-                continue;
+    bool first = true;
+    for (;;) {  // (one turn without erec; with it, a turn per extension the eval certificate asks for)
+        for (;; first = false) {
+            CHK(cert_wait(h, slot, S.seq, everything || R == 0 ? 4 : n_device, S.tail, s8));
+            need = (int)s8[2];
+            need_race = (int)s8[5];
+            if (first) {
+                rec->need_first = need;
+                rec->need_race_first = need_race;
             }
-            if (need > S.n_done) {
-                if (need <= kmax) {
-                    CHK(cert_rescore(h, S, R + S.n_done, R + need));
-                    S.n_done = need;
-                    redo = true;
-                } else {
-                    CHK(cert_window_set(h, S, need, false));
-                    saturated = true;
-                    everything = S.n_done >= N;
-                    continue;
-                }
+            bool redo = false;
+            if (S.c.grow_delta && 1.5 * (double)s8[1] > S.delta && !everything) {
+                S.delta = 1.5 * (double)s8[1];
+                redo = S.n_done < N;
             }
-            if (need_race > S.r_done) {
-                if (need_race <= R) {
-                    CHK(cert_rescore(h, S, R - need_race, R - S.r_done));
-                    S.r_done = need_race;
-                    redo = true;
-                } else {  // more racers than the race list holds: every candidate in fp32
+            if (everything || S.n_done >= N) break;
+            if (!redo) {
+                if (need > S.n_done && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
                     CHK(cert_window_set(h, S, N, true));
-                    saturated = everything = true;
+                    everything = true;
                     continue;
                 }
+                if (need > S.n_done) {
+                    if (need <= kmax) {
+                        CHK(cert_rescore(h, S, R + S.n_done, R + need));
+                        S.n_done = need;
+                        redo = true;
+                    } else {
+                        CHK(cert_window_set(h, S, need, false));
+                        saturated = true;
+                        everything = S.n_done >= N;
+                        continue;
+                    }
+                }
+                if (need_race > S.r_done) {
+                    if (need_race <= R) {
+                        CHK(cert_rescore(h, S, R - need_race, R - S.r_done));
+                        S.r_done = need_race;
+                        redo = true;
+                    } else {  // more racers than the race list holds: every candidate in fp32
+                        CHK(cert_window_set(h, S, N, true));
+                        saturated = everything = true;
+                        continue;
+                    }
+                }
             }
+            if (!redo) break;
+            CHK(cert_merge(h, S, S.n_done, S.r_done, true));
         }
-        if (!redo) break;
-        CHK(cert_merge(h, S, S.n_done, S.r_done, true));
+        first = false;
+        if (!erec) break;
+        if (everything || S.n_done >= N) {  // the select ran on fp32 scores alone
+            erec->eval_bound = 0.f;
+            erec->eval_certified = 1;
+            break;
+        }
+        float e8[8];
+        const int n_listed = saturated ? S.n_done : (kmax < N ? kmax : N);
+        CHK(cert_eval_bound(h, S, n_listed, eval_tol, e8));
+        const int need_eval = (int)e8[1];
+        if (++erec->eval_rounds == 1) erec->need_eval_first = need_eval;
+        erec->eval_bound = e8[0];
+        if (need_eval <= S.n_done) {
+            erec->eval_certified = 1;
+            break;
+        }
+        if (need_eval <= n_listed) {  // score entries [n_done, need_eval), merge + select again, every certificate read again
+            CHK(cert_rescore(h, S, R + S.n_done, R + need_eval));
+            erec->n_eval += need_eval - S.n_done;
+            S.n_done = need_eval;
+            CHK(cert_merge(h, S, S.n_done, S.r_done, true));
+        } else {  // the list cannot reach the tolerance: every candidate in fp32
+            CHK(cert_window_set(h, S, N, true));
+            everything = true;
+        }
     }
     rec->n_rescored = S.n_done;
     rec->n_race = S.r_done;
@@ -1554,15 +1619,28 @@ static void cert_fill(CertStep& S, const m3pc_plan_args* a, const m3pc_cert_args
     S.tail_pending = false;
 }
 
-int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
-                             const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
-                             float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
-                             float* sample_action, m3pc_cert_record* rec, void* stream) {
-    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged || !rec)
+// the serial certified step; with_eval: m3pc_plan_step_certified_eval (eval_tol, erec)
+static int cert_step_serial(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
+                            const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
+                            float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
+                            float* sample_action, m3pc_cert_record* rec, bool with_eval, float eval_tol, m3pc_eval_record* erec,
+                            void* stream, const char* who) {
+    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged || !rec ||
+        (with_eval && !erec))
         return fail(M3PC_EINVAL, "null argument");
-    CHK(cert_check_step(a, c, "m3pc_plan_step_certified"));
-    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "m3pc_plan_step_certified with a pipelined step begun (m3pc_plan_step_certified_end first)");
+    CHK(cert_check_step(a, c, who));
+    if (with_eval && !(eval_tol > 0.f)) return fail(M3PC_EINVAL, "%s: eval_tol must be > 0 (+inf: report only)", who);
+    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "%s with a pipelined step begun (m3pc_plan_step_certified_end first)", who);
     memset(rec, 0, sizeof(*rec));
+    if (with_eval) {
+        memset(erec, 0, sizeof(*erec));
+        if (!h->eval_host && a->precision != M3PC_PREC_FP32) {  // the second host-mapped block of every slot, at the first such call
+            HIPCHK(hipSetDevice(h->device));
+            HIPCHK(hipHostMalloc((void**)&h->eval_host, (size_t)M3PC_SLOTS * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+            memset(h->eval_host, 0, (size_t)M3PC_SLOTS * 8 * sizeof(float));
+            HIPCHK(hipHostGetDevicePointer((void**)&h->eval_host_dev, h->eval_host, 0));
+        }
+    }
     CertStep& S = h->cstep[a->slot];
     cert_fill(S, a, c, states, actions, rewards, eps, expo, sample_actions, scores_low, merged, list, p, eval_action, argmax, sample_idx,
               sample_action, (hipStream_t)stream, false);
@@ -1575,7 +1653,24 @@ int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc
     pa.flags = 0;
     CHK(m3pc_candidate_pass(h, &pa, states, actions, rewards, eps, loc, std_, sample_actions, scores_low, nullptr, nullptr, stream));
     CHK(cert_first_pass(h, S));
-    return cert_resolve(h, S, rec);
+    return cert_resolve(h, S, rec, eval_tol, with_eval ? erec : nullptr);
+}
+
+int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
+                             const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
+                             float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
+                             float* sample_action, m3pc_cert_record* rec, void* stream) {
+    return cert_step_serial(h, a, c, states, actions, rewards, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p, eval_action,
+                            argmax, sample_idx, sample_action, rec, false, 0.f, nullptr, stream, "m3pc_plan_step_certified");
+}
+
+int m3pc_plan_step_certified_eval(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states,
+                                  const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std_,
+                                  float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
+                                  int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* rec, float eval_tol,
+                                  m3pc_eval_record* erec, void* stream) {
+    return cert_step_serial(h, a, c, states, actions, rewards, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p, eval_action,
+                            argmax, sample_idx, sample_action, rec, true, eval_tol, erec, stream, "m3pc_plan_step_certified_eval");
 }
 
 // ---- the certified step in two halves: _begin enqueues, _end resolves (include/m3pc_hip.h: "Pipelined certified steps")

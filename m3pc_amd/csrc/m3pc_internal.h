@@ -158,6 +158,11 @@ struct m3pc_handle {
     float* cert_host = nullptr;       // M3PC_SLOTS x 8 floats, host address
     float* cert_host_dev = nullptr;   // the same block as the device sees it
     int cert_seq[M3PC_SLOTS] = {};
+    // m3pc_plan_step_certified_eval: a second host-mapped 8-float block per step slot for the eval_action certificate's statistics
+    // (launch_eval_bound; the device copy is cert_stats + 24), allocated at the first such call, with a sequence counter of its own
+    float* eval_host = nullptr;
+    float* eval_host_dev = nullptr;
+    int eval_seq[M3PC_SLOTS] = {};
     // One certified step: its arguments and how far its re-score has come.  The serial call fills and resolves one within the
     // call (tail == the caller's stream); _begin leaves it for _end (tail == the chain stream of the slot's parity).
     struct CertStep {

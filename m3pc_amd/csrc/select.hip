@@ -759,6 +759,175 @@ void launch_deviation_stats(const float* b, const float* f, int n, float* stats,
     hipLaunchKernelGGL(deviation_stats_kernel, dim3(1), dim3(1024), 0, st, b, f, n, stats, host_stats, seq);
 }
 
+// ---- the eval_action certificate (m3pc_eval_bound; include/m3pc_hip.h states the bound and its claim).  One workgroup over the
+// merged vector the select ran on.  p and e are recomputed with select_body's own expressions (same order, so e is its eval_action
+// bit for bit); every candidate's membership lives in LDS as 16 bits: not listed / re-scored / the list position of a listed score
+// entry that is not re-scored.  Thread t of [n, n_listed) stands for "the score entries up to t re-scored": U is then the un-listed
+// candidates (a block_sum over the vector) plus the listed entries t .. n_listed-1 (an inclusive SUFFIX sum over the threads -- sums
+// of non-negative terms only, no cancellation where the list holds nearly all the weight), so all bound(n') come out of one scan
+// per action component.  Fixed-order reductions: bit-identical from run to run.
+// v[t] -> sum_{u >= t} v[u] over the 1024 threads (64-lane shuffles + one LDS hop, fixed order)
+__device__ __forceinline__ float block_suffix_sum(float v, float* sv) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float u = __shfl_down(v, o);
+        if (lane + o < 64) v += u;
+    }
+    __syncthreads();
+    if (lane == 0) sv[wid] = v;
+    __syncthreads();
+    float behind = 0.f;
+    for (int w = (int)(blockDim.x >> 6) - 1; w > wid; --w) behind += sv[w];
+    return v + behind;
+}
+// v[t] -> sum_{u < t} v[u], the same way from the other end
+__device__ __forceinline__ float block_prefix_sum(float v, float* sv) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float u = __shfl_up(v, o);
+        if (lane >= o) v += u;
+    }
+    __syncthreads();
+    if (lane == 63) sv[wid] = v;
+    __syncthreads();
+    float before = 0.f;
+    for (int w = 0; w < wid; ++w) before += sv[w];
+    const float ex = __shfl_up(v, 1);
+    return (lane ? ex : 0.f) + before;
+}
+// expm1(eps) S / (1 - (1 - exp(-eps)) P_U) with the denominator as P_L + exp(-eps) P_U (P_L + P_U = 1: sums of non-negative terms,
+// where 1 - (1 - exp(-eps)) P_U cancels at a large eps); S, P_L, P_U already divided by the select's sum of p; exactly 0 where S is
+__device__ __forceinline__ float eval_bound_of(float em1, float emeps, float S, float PL, float PU) {
+    return S > 0.f ? em1 * S / (PL + emeps * PU) : 0.f;
+}
+__global__ __launch_bounds__(1024) void eval_bound_kernel(const float* m, int n_total, const int* list, int r, int n, int n_listed,
+                                                           const float* a0, long long a0_stride, int A, float tau, float delta,
+                                                           float eval_tol, float* stats, float* host_stats, float seq) {
+    __shared__ unsigned short pos[16384];
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ float at_n[2];
+    __shared__ int at_n_k;
+    constexpr unsigned short UNLISTED = 0xffffu, RESCORED = 0xfffeu;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    for (int j = tid; j < n_total; j += 1024) pos[j] = UNLISTED;
+    __syncthreads();
+    int my_id = -1;  // the listed, not re-scored score entry this thread stands for
+    if (tid >= n && tid < n_listed) {
+        const int id = list[r + tid];
+        if ((unsigned int)id < (unsigned int)n_total) {
+            my_id = id;
+            pos[id] = (unsigned short)tid;
+        }
+    }
+    __syncthreads();
+    if (tid < r + n) {  // (a candidate that sits in both parts, or twice, gets the same mark from every writer)
+        const int id = list[tid];
+        if ((unsigned int)id < (unsigned int)n_total) pos[id] = RESCORED;
+    }
+    __syncthreads();
+    if (my_id >= 0 && pos[my_id] != (unsigned short)tid) my_id = -1;  // re-scored as a race entry: in L either way, counted once
+
+    // select_body's p and its sums
+    ArgMax am{-INFINITY, 0x7fffffff};
+    for (int i = tid; i < n_total; i += 1024) am = better(am, ArgMax{m[i], i});
+    am = block_argmax(am, sv, si);
+    const float mx = am.v;
+    float s = 0.f;
+    for (int i = tid; i < n_total; i += 1024) s += expf(__fmul_rn(__fsub_rn(m[i], mx), tau));
+    const float tot = block_sum(s, sv);
+    float pj[16];
+    float ps = 0.f, prest = 0.f, pres = 0.f, nu = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int j = q * 1024 + tid;
+        pj[q] = 0.f;
+        if (j < n_total) {
+            pj[q] = expf(__fmul_rn(__fsub_rn(m[j], mx), tau)) / tot;
+            ps += pj[q];
+            if (pos[j] == UNLISTED) prest += pj[q];
+            if (pos[j] == RESCORED) pres += pj[q];
+            else nu += 1.f;
+        }
+    }
+    const float psum = block_sum(ps, sv);
+    prest = block_sum(prest, sv) / psum;
+    pres = block_sum(pres, sv) / psum;
+    nu = block_sum(nu, sv);  // (a count <= 16384: exact)
+    const float p_me = my_id >= 0 ? expf(__fmul_rn(__fsub_rn(m[my_id], mx), tau)) / tot : 0.f;
+    // P_U and P_L with the score entries up to tid re-scored; with all n_listed of them
+    const float PU_t = prest + block_suffix_sum(p_me, sv) / psum, PL_t = pres + block_prefix_sum(p_me, sv) / psum;
+    const float PL_l = pres + block_sum(p_me, sv) / psum;
+
+    const float eps = fabsf(tau) * delta;
+    const float em1 = expm1f(eps), emeps = expf(-eps);
+    float b_t = 0.f, b_l = 0.f;  // bound(tid); bound(n_listed)
+    int k_t = 0, k_l = 0;
+    for (int a = 0; a < A; ++a) {
+        float acc = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int j = q * 1024 + tid;
+            if (j < n_total) acc = fmaf(a0[(long long)j * a0_stride + a], pj[q], acc);
+        }
+        const float e = block_sum(acc, sv) / psum;
+        float rest = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int j = q * 1024 + tid;
+            if (j < n_total && pos[j] == UNLISTED) rest += pj[q] * fabsf(a0[(long long)j * a0_stride + a] - e);
+        }
+        rest = block_sum(rest, sv) / psum;
+        const float c_me = my_id >= 0 ? p_me * fabsf(a0[(long long)my_id * a0_stride + a] - e) : 0.f;
+        const float S_t = rest + block_suffix_sum(c_me, sv) / psum;
+        const float bt = eval_bound_of(em1, emeps, S_t, PL_t, PU_t), bl = eval_bound_of(em1, emeps, rest, PL_l, prest);
+        if (bt > b_t) {
+            b_t = bt;
+            k_t = a;
+        }
+        if (bl > b_l) {
+            b_l = bl;
+            k_l = a;
+        }
+    }
+    // need_eval: the smallest n' of [n, n_listed] whose bound is within the tolerance
+    int need = (tid >= n && tid < n_listed && b_t <= eval_tol) ? tid : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int u = __shfl_xor(need, o);
+        need = u < need ? u : need;
+    }
+    __syncthreads();
+    if (lane == 0) si[wid] = need;
+    if (tid == n && n < n_listed) {
+        at_n[0] = b_t;
+        at_n[1] = PU_t;
+        at_n_k = k_t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) need = si[w] < need ? si[w] : need;
+        if (need == 0x7fffffff) need = b_l <= eval_tol ? n_listed : n_total;
+        const bool all = n >= n_listed;  // nothing listed beyond the re-scored entries: bound(n) is bound(n_listed)
+        const float st8[8] = {all ? b_l : at_n[0], (float)need, all ? prest : at_n[1], (float)(all ? k_l : at_n_k), 0.f, eps, b_l, nu};
+        for (int i = 0; i < 8; ++i) stats[i] = st8[i];
+        if (host_stats) {
+            for (int i = 0; i < 8; ++i)
+                if (i != 4) host_stats[i] = st8[i];
+            __threadfence_system();
+            __hip_atomic_store(host_stats + 4, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+void launch_eval_bound(const float* m, int n_total, const int* list, int r, int n, int n_listed, const float* a0, long long a0_stride,
+                       int A, float tau, float delta, float eval_tol, float* stats, float* host_stats, float seq, hipStream_t st) {
+    if (n_total <= 0 || n_total > 16384 || r < 0 || n < 0 || n > n_listed || r + n_listed > 1024) return;
+    hipLaunchKernelGGL(eval_bound_kernel, dim3(1), dim3(1024), 0, st, m, n_total, list, r, n, n_listed, a0, a0_stride, A, tau, delta,
+                       eval_tol, stats, host_stats, seq);
+}
+
 __global__ void scatter_kernel(const float* src, const int* index, int n, float* dst, int* index_copy) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {

@@ -139,7 +139,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                  defer_join: bool = True, goal_batch: int = 0, race_min: int = 2, calibration_windows: Optional[int] = None, certify_sample: bool = True,
                  chain_mode: str = "alternate", policy_head: str = "full", auto_fp32: bool = True,
                  calibration_factor: float = 1.6, rescore_round: int = 4, fallback: str = "fp32", native_step: bool = False,
-                 variates: str = "torch", seed: int = 0):
+                 variates: str = "torch", seed: int = 0, eval_tol: Optional[float] = None):
         """cfg: any object with traj_length, action_samples, horizon, discount, temperature, lmbda,
         plan_guidance (finetune.py RunConfig fields read at learner.py:276,319,342).
         tokenizer_manager: a TokenizerManager (this package's) or {key: {"mean","std","min","max"}}.
@@ -185,6 +185,16 @@ class HipPlanner(GoalMixin, LockstepMixin):
           m3pc_plan_step_certified_begin / _end: the library runs the pipelined schedule of ``_issue`` / ``_enqueue_tail`` on this
           planner's chain-stream pair (m3pc_set_step_streams), the ticket's result resolves the step; calibration steps run
           serially.  Lock-step groups, ``world > 1`` and rescore="topk" keep the Python protocol (certificate.py).
+        eval_tol (default None: everything as before): a tolerance on ``eval_action`` -- the softmax-weighted mean over ALL candidates
+          that every ``eval=True`` call returns, which the other two certificates do not cover.  Serial steps run as
+          m3pc_plan_step_certified_eval: under the same delta model the step bounds |eval_action - the fp32 step's| (``last["eval_bound"]``)
+          and re-scores score entries until the bound is within eval_tol (``last["n_eval"]`` of them; ``last["need_eval_first"]``:
+          what the first bound asked for), or scores every candidate in fp32 when its list cannot reach that -- which the
+          ``auto_fp32`` statistic sees like a saturated certificate.  At a nearly flat softmax (rtg guidance, temperature 0.01)
+          bf16 cannot reach 1e-3 through its list, nor at config 3's N = 4096 critic shape: the tier to ask for is "bf16x3" (6e-5 /
+          3e-5 as it stands).  Needs native_step=True, one rank and rescore="bound" (ValueError otherwise).  ``plan_async``
+          on such a planner runs the serial call and returns a resolved ticket (the route of calibration steps);
+          ``action_sample_batch(lockstep=...)`` raises ValueError: there is no lock-step form of this certificate.
         variates: "torch" (default) draws a plan step's normals and exponentials from ``generator``; "library" draws them with
           m3pc_draw_variates -- the library's counter-based generator on (``seed``, the planner's step index), what a host
           without torch gets -- on the same stream.  Not torch's stream of numbers: goldens recorded on one do not hold on the other.
@@ -194,6 +204,13 @@ class HipPlanner(GoalMixin, LockstepMixin):
         self.cfg = cfg
         self.group = group
         self.rank, self.world = mdist.world_info(group)
+        if eval_tol is not None:
+            if not native_step or self.world != 1 or rescore != "bound":
+                raise ValueError("eval_tol needs native_step=True, one rank (no group) and rescore='bound': the eval_action certificate "
+                                 "is part of the serial one-call step (m3pc_plan_step_certified_eval)")
+            if not float(eval_tol) > 0.0:
+                raise ValueError(f"eval_tol must be > 0 (inf: report the bound only), got {eval_tol!r}")
+        self._eval_tol = None if eval_tol is None else float(eval_tol)
         if device is None:
             device = torch.cuda.current_device() if torch.cuda.is_available() else 0
         S = state_dict["encoder_embed_dict.states.weight"].shape[1]
@@ -524,6 +541,10 @@ class HipPlanner(GoalMixin, LockstepMixin):
             self._maybe_fall_back_to_fp32()
         if not pipelined:
             self._drain()  # a serial step runs its fp32 chains on the current stream: nothing pipelined may still be using them
+        if self._eval_tol is not None:  # the eval_action certificate exists in the serial one-call step only
+            if pipelined:
+                return self._issue_native_async(mode, states, actions, rewards, rtg, h, lmbda, eps, returns, slot, inputs_ready)
+            return self._issue_native(mode, states, actions, rewards, rtg, h, lmbda, eps, returns, slot=slot)
         if (self._native_step and not pipelined and slot is None and self.world == 1 and not self._force_collective
                 and not self._bf16_offset and self.rescore in ("bound", "none")):
             return self._issue_native(mode, states, actions, rewards, rtg, h, lmbda, eps, returns)
@@ -636,14 +657,14 @@ class HipPlanner(GoalMixin, LockstepMixin):
             kmin = max(min(tk.kfirst_in, N, kmax), 1)
             rfirst = max(min(tk.rfirst_in, R), 1) if R > 0 else 0
             delta = max(self._delta0, tk.grow_in)
-        res, rec = hd.plan_step_certified(mode, states, actions, rewards, eps, tk.expo, h, tk.rtg, tk.lmbda, disc, N, temp,
-                                          delta=delta, grow_delta=bound and self._delta_fixed is None, kmin=kmin, kmax=kmax,
-                                          rfirst=rfirst, rmax=R, precision=self.precision, slot=sl.i, returns=returns,
-                                          pruned=self._policy_pruned)
+        out = hd.plan_step_certified(mode, states, actions, rewards, eps, tk.expo, h, tk.rtg, tk.lmbda, disc, N, temp,
+                                     delta=delta, grow_delta=bound and self._delta_fixed is None, kmin=kmin, kmax=kmax,
+                                     rfirst=rfirst, rmax=R, precision=self.precision, slot=sl.i, returns=returns,
+                                     pruned=self._policy_pruned, eval_tol=self._eval_tol)
         self._mark_main()
-        return self._native_result(tk, res, rec, delta, kmin, kmax)
+        return self._native_result(tk, out[0], out[1], delta, kmin, kmax, erec=out[2] if len(out) > 2 else None)
 
-    def _native_result(self, tk, res, rec, delta, kmin, kmax) -> "PlanTicket":
+    def _native_result(self, tk, res, rec, delta, kmin, kmax, erec=None) -> "PlanTicket":
         """Fold the record of a certified step the library ran (serial call, or _begin + _end) into the adaptive state and
         ``planner.last``; the ticket is resolved."""
         N = int(self.cfg.action_samples)
@@ -672,6 +693,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
                 if self._delta_fixed is None:
                     self._delta0 = max(self._delta0, 1.5 * self._hist[i][0])
                 del self._hist[i]
+        if erec is not None:  # (m3pc_plan_step_certified_eval; an fp32 step: bound 0, certified)
+            extra.update(eval_bound=float(erec.eval_bound), need_eval_first=int(erec.need_eval_first), n_eval=int(erec.n_eval),
+                         eval_rounds=int(erec.eval_rounds), eval_certified=bool(erec.eval_certified))
         p, eval_action, argmax, sample_idx, sample_action = tk.sel = res["sel"]
         self.last = dict(expect_return=res["expect_return"] if bound else res["expect_return_low"],
                          expect_return_bf16=res["expect_return_low"] if bound else None, p=p, argmax=argmax, sample_idx=sample_idx,
@@ -692,7 +716,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
         sl = (slot if slot is not None else self._acquire_slot()).ready(self)
         bound = self.rescore == "bound"
         main = torch.cuda.current_stream(self.device)
-        if bound and self._delta_fixed is None and self._cal_left > 0:
+        if (bound and self._delta_fixed is None and self._cal_left > 0) or self._eval_tol is not None:
             self._drain()
             if inputs_ready:
                 main.wait_event(sl.ev_h2d)  # (plan_async copied the window on the chain stream)
@@ -1082,6 +1106,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
         generator state and bound.  Groups that still calibrate the bound (the first windows behind a weight load) take the
         ``lockstep=True`` path; ``rescore="topk"`` is not served (ValueError).
         ``rtg``: None, a float, or one value per window.  Returns (E, A)."""
+        if lockstep and self._eval_tol is not None:
+            raise ValueError("eval_tol: the eval_action certificate has no lock-step form (m3pc_plan_step_certified_eval is the serial "
+                             "one-call step); use action_sample_batch(lockstep=False) or a planner without eval_tol")
         if lockstep:
             return self._action_sample_lockstep(sequence_histories, percentage, eval, rtg, onepass=lockstep == "onepass",
                                                 native=lockstep == "native")
@@ -1142,7 +1169,7 @@ def _versions(module):
 
 
 def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None, generator: Optional[torch.Generator] = None,
-           native_step: bool = False, **planner_kw):
+           native_step: bool = False, eval_tol: Optional[float] = None, **planner_kw):
     """Rebind the plan path of a reference-style ``Learner`` onto the HIP library.
 
     precision: "bf16" (default since round 6: the configuration the headline is measured on) -- the bf16 candidate pass with the
@@ -1158,6 +1185,8 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     Afterwards learner.action_sample / rtg_guiding / critic_lambda_guiding / noise_adding_lambda /
     mtm_sampling (and the zero-shot calls) run on the GPU; everything else on the object is untouched.
     native_step: serial plan steps as one library call each (``HipPlanner(native_step=True)``; default False).
+    eval_tol: a per-step tolerance on ``eval_action`` (``HipPlanner(eval_tol=...)``: needs native_step=True; default None) -- with
+    it evaluation rollouts (eval=True) stay within eval_tol of the fp32 step under the certificate's delta model.
     ``group`` + ``generator``: shard the candidates over the ranks of a process group (every rank attaches its own
     learner replica and passes a generator seeded identically); further keywords go to ``HipPlanner``.
     Weights are followed per tensor: before each call the version counters of ``mtm`` / ``iql.qf`` are compared with the
@@ -1177,7 +1206,7 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
                          obs_mean=None if qf is None else qf.obs_mean, obs_std=None if qf is None else qf.obs_std,
                          n_embd=mc.n_embd, n_head=mc.n_head, n_enc_layer=mc.n_enc_layer, n_dec_layer=mc.n_dec_layer,
                          precision=precision, rescore_topk=rescore_topk, group=group, generator=generator, native_step=native_step,
-                         **planner_kw)
+                         eval_tol=eval_tol, **planner_kw)
     state = {"mtm": _versions(mtm), "qf": None if qf is None else _versions(qf)}
 
     def _sync():
