@@ -154,7 +154,7 @@ int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a);
 int m3pc_debug_select_batch(const float* scores, const float* a0, long long a0_window_stride, long long a0_stride, int n_windows,
                             int n_total, int A, float temperature, const float* expo, float* p, float* eval_action, int* argmax,
                             int* sample_idx, float* sample_action, void* stream);
-/* the fused layer tail (block_fused.hip) on caller tensors; see csrc/m3pc.hip for the argument layout */
+/* the fused layer tail (block_fused.hip) on caller tensors; see csrc/m3pc_debug.hip for the argument layout */
 long long m3pc_debug_block_stream_bytes(void);
 int m3pc_debug_block_fused(const void* O, int M, const float* res, const float* rowtab, int rt_mod, const void* Wo, const void* W1,
                            const void* W2, void* stream_buf, int pack, const float* bo, const float* b1, const float* b2,
@@ -167,7 +167,7 @@ int m3pc_debug_block_fused_qkv(const void* O, int M, const float* res, const voi
                                const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* bqkv, float* Xout, void* QKV,
                                void* stream, long long* stamps, int x_bf16);  /* x_bf16: res / Xout are (M, 512) bf16 rows (round 6);
                                                                                  m3pc_debug_block_fused: bit 16 of `variant` */
-/* the decoder form with the two scalar output heads inside the tail (see csrc/m3pc.hip for the argument layout) */
+/* the decoder form with the two scalar output heads inside the tail (see csrc/m3pc_debug.hip for the argument layout) */
 int m3pc_debug_block_fused_heads(const void* O, int M, const float* rowtab, int rt_mod, const void* Wo, const void* W1, const void* W2,
                                  const void* Wh, void* stream_buf, const float* bo, const float* b1, const float* b2, const float* ln2_g,
                                  const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* lnB_g0, const float* lnB_b0,

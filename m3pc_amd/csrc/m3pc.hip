@@ -11,9 +11,6 @@
 // Candidate pass ("pass 2", learner.py:288-293) is exactly pruned: decoder rows of masked tokens do not
 // depend on the candidate, so only the 2h scored tokens are pushed through out-proj/FFN/heads and only the
 // un-masked tokens through the K/V projection.
-#include <atomic>
-#include <chrono>
-
 #include "m3pc_internal.h"
 
 namespace m3pc {
@@ -1298,810 +1295,6 @@ int m3pc_eval_bound(m3pc_handle* h, const float* merged, int n_total, const int*
     return check_launch("eval_bound");
 }
 
-// ---- the certified plan step as one call (learner.py:318-325 on low-precision scores that fp32 re-scores certify)
-// The statistics of the kernel that carried `seq`, read from the slot's host-mapped block: a BOUNDED spin on the sequence number
-// (10 s, the bound of the Python binding's HostStats.wait); on expiry one synchronisation of the stream and the device copy.
-static int cert_wait_block(const volatile float* hs, const float* dev, float seq, int n_device, hipStream_t st, float out[8]) {
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (hs[4] != seq) {
-        if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
-            if (hipStreamSynchronize(st) != hipSuccess ||
-                hipMemcpy(out, dev, 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(M3PC_EHIP, "the statistics of the certified step reached neither host-mapped memory within 10 s nor the host by a copy");
-            for (int i = n_device; i < 8; ++i) out[i] = 0.f;  // (a four-statistics merge leaves the device slots 4..7 alone)
-            return 0;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    for (int i = 0; i < 8; ++i) out[i] = hs[i];
-    return 0;
-}
-static int cert_wait(m3pc_handle* h, int slot, float seq, int n_device, hipStream_t st, float out[8]) {
-    return cert_wait_block(h->cert_host + 8 * slot, h->cert_stats[slot], seq, n_device, st, out);
-}
-static float cert_next_seq(m3pc_handle* h, int slot) {
-    h->cert_seq[slot] = h->cert_seq[slot] % 1000000 + 1;
-    return (float)h->cert_seq[slot];
-}
-// max(factor x the largest deviation from the median, 1e-6 x the scores' scale, 1e-30): the host arithmetic of
-// HipPlanner._calibrate (doubles of the device's floats), rounded once to the float the ABI carries
-static float cert_delta(float factor, float deviation, float f_max) {
-    double d = (double)factor * (double)deviation;
-    if (1e-6 * (double)f_max > d) d = 1e-6 * (double)f_max;
-    if (1e-30 > d) d = 1e-30;
-    return (float)d;
-}
-// one rank, every candidate: what both calls need of m3pc_plan_args before any HIP call
-static int cert_check_args(const m3pc_plan_args* a, const char* who) {
-    if (a->n_total < 1 || a->n_total > 16384) return fail(M3PC_EINVAL, "%s: n_total %d outside [1, 16384]", who, a->n_total);
-    if (a->n_begin != 0 || a->n_count != a->n_total)
-        return fail(M3PC_EINVAL, "%s plans on one rank: candidates [%d,+%d) are not all n_total=%d", who, a->n_begin, a->n_count, a->n_total);
-    if (!precision_ok(a->precision)) return fail(M3PC_EINVAL, "bad precision %d", a->precision);
-    if (a->slot < 0 || a->slot >= M3PC_SLOTS) return fail(M3PC_EINVAL, "slot %d outside [0, %d)", a->slot, M3PC_SLOTS);
-    return 0;
-}
-// the checks of the certified step (serial call and _begin), before any HIP call
-static int cert_check_step(const m3pc_plan_args* a, const m3pc_cert_args* c, const char* who) {
-    CHK(cert_check_args(a, who));
-    const int N = a->n_total, kmin = c->kmin, kmax = c->kmax, R = c->rmax, rfirst = c->rfirst;
-    if (a->precision != M3PC_PREC_FP32) {
-        if (kmax < 1 || kmax > 1023 || kmin < 1 || kmin > kmax || kmin > N)
-            return fail(M3PC_EINVAL, "kmin %d / kmax %d outside 1 <= kmin <= min(kmax, n_total=%d), kmax <= 1023", kmin, kmax, N);
-        if (R < 0 || R > 64 || R > N) return fail(M3PC_EINVAL, "rmax %d outside [0, min(64, n_total=%d)]", R, N);
-        if (kmax + R > 1023) return fail(M3PC_EINVAL, "kmax %d + rmax %d > 1023 (the merge lists 1024 entries)", kmax, R);
-        if (R == 0 ? rfirst != 0 : (rfirst < 1 || rfirst > R)) return fail(M3PC_EINVAL, "rfirst %d outside [1, rmax=%d] (0 with rmax == 0)", rfirst, R);
-        if (!(c->delta >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
-    }
-    if (!(c->temperature == c->temperature)) return fail(M3PC_EINVAL, "temperature is not a number");
-    return 0;
-}
-static bool cert_any_begun(const m3pc_handle* h) {
-    for (int s = 0; s < M3PC_SLOTS; ++s)
-        if (h->cstep[s].begun) return true;
-    return false;
-}
-
-// ---- the pieces of a certified step, on the step's tail stream (the caller's stream in the serial call)
-using CertStep = m3pc_handle::CertStep;
-static int* cert_L(m3pc_handle* h, const CertStep& S) { return S.list ? S.list : h->cert_list[S.a.slot]; }
-// A pipelined step's tail runs on a chain stream, beside the candidate passes of its neighbours on the callers' streams.  What
-// it runs in the chain workspace of its parity needs no order.  What overflows into the candidate workspace -- a re-score of more
-// than max_rescore candidates, the fp32 pass over every candidate (with sa_buf and the handle's top-1 scratch) -- is ordered by
-// events: behind every candidate pass enqueued so far (ev_cand of the slot begun last; m3pc_candidate_pass / m3pc_rescore order
-// the handle's own streams themselves: ws_sync) and behind the overflow before it, and every later _begin's candidate pass goes
-// behind ev_excl.
-static int cert_excl_enter(m3pc_handle* h, const CertStep& S) {
-    if (!S.async) return 0;
-    if (h->cand_last_slot >= 0) HIPCHK(hipStreamWaitEvent(S.tail, h->step_ev[h->cand_last_slot][2], 0));
-    if (h->excl_valid) HIPCHK(hipStreamWaitEvent(S.tail, h->ev_excl, 0));
-    return 0;
-}
-static int cert_excl_leave(m3pc_handle* h, const CertStep& S) {
-    if (!S.async) return 0;
-    HIPCHK(hipEventRecord(h->ev_excl, S.tail));
-    h->excl_valid = true;
-    return 0;
-}
-static int cert_rescore(m3pc_handle* h, CertStep& S, int lo, int hi) {  // list positions [lo, hi)
-    m3pc_plan_args ra = S.a;
-    ra.precision = M3PC_PREC_FP32;
-    ra.flags = 0;
-    ra.window = 0;
-    ra.n_count = hi - lo;
-    const bool excl = hi - lo > h->chain[0].max_cand;
-    if (excl) CHK(cert_excl_enter(h, S));
-    CHK(m3pc_rescore(h, &ra, S.states, S.actions, S.rewards, S.eps, cert_L(h, S) + lo, hi - lo, nullptr, h->cert_f[S.a.slot] + lo, S.tail));
-    if (excl) CHK(cert_excl_leave(h, S));
-    return 0;
-}
-static int cert_select(m3pc_handle* h, CertStep& S) {
-    return m3pc_select(h, S.merged, S.sample_actions, (long long)S.a.horizon * h->A, S.a.n_total, S.c.temperature, S.expo, S.p, S.eval_action,
-                       S.argmax, S.sample_idx, S.sample_action, S.tail);
-}
-static int cert_merge(m3pc_handle* h, CertStep& S, int n, int r, bool with_select) {
-    const int slot = S.a.slot, R = S.c.rmax, N = S.a.n_total, o = R - r;
-    int* L = cert_L(h, S);
-    float *B = h->cert_b[slot], *F = h->cert_f[slot], *dstats = h->cert_stats[slot], *hstats = h->cert_host_dev + 8 * slot;
-    const float temp = S.c.temperature;
-    S.seq = cert_next_seq(h, slot);
-    ++S.rounds;
-    if (R > 0) {
-        if (with_select)
-            return m3pc_merge_race_select(h, S.scores_low, S.expo, temp, N, L + o, r, n, B + o, F + o, (float)S.delta, S.merged, dstats, hstats,
-                                          S.seq, S.sample_actions, (long long)S.a.horizon * h->A, S.p, S.eval_action, S.argmax, S.sample_idx,
-                                          S.sample_action, S.tail);
-        return m3pc_rescore_merge_race(h, S.scores_low, S.expo, temp, N, L + o, r, n, B + o, F + o, (float)S.delta, S.merged, dstats, hstats,
-                                       S.seq, S.tail);
-    }
-    CHK(m3pc_rescore_merge(h, S.scores_low, N, L, n, B, F, (float)S.delta, S.merged, dstats, hstats, S.seq, S.tail));
-    return with_select ? cert_select(h, S) : 0;
-}
-// The lists are too short.  Window set: the `need` best candidates by low-precision score (descending, ties to the lower
-// index) listed behind the race entries in place of the score entries, re-scored in chunks of the re-score workspace.
-// Everything: one fp32 candidate pass in the candidate workspace (stream-ordered behind this step's own pass), the best
-// entry merged with itself at delta = 0 -- the select then runs on fp32 scores alone.
-static int cert_window_set(m3pc_handle* h, CertStep& S, int need, bool everything) {
-    const int slot = S.a.slot, R = S.c.rmax, N = S.a.n_total;
-    int* L = cert_L(h, S);
-    float *B = h->cert_b[slot], *dstats = h->cert_stats[slot], *hstats = h->cert_host_dev + 8 * slot;
-    hipStream_t st = S.tail;
-    const int cnt = need < N ? need : N;
-    if (cnt <= 1024 - 32 && !everything) {
-        if (!launch_topk_race(S.scores_low, nullptr, 0.f, N, cnt, 0, R, L, B, st))
-            launch_window_stats(S.scores_low, N, L + R, cnt, 1, cnt, 0.f, dstats + 8, nullptr, 0.f, B + R, st, 0);
-        CHK(check_launch("plan_step_certified (window set)"));
-        const int cap = h->chain[0].max_cand;
-        for (int c0 = 0; c0 < cnt; c0 += cap) CHK(cert_rescore(h, S, R + c0, R + (cnt < c0 + cap ? cnt : c0 + cap)));
-        S.n_done = cnt;
-        CHK(cert_merge(h, S, cnt, S.r_done, false));
-        return cert_select(h, S);
-    }
-    m3pc_plan_args ra = S.a;
-    ra.precision = M3PC_PREC_FP32;
-    ra.flags = 0;
-    ra.window = 0;
-    ra.n_count = N;
-    float* f32 = h->cert_f32[slot];
-    int* top1 = h->cert_top1[slot];
-    float* top1v = dstats + 16;
-    CHK(cert_excl_enter(h, S));
-    CHK(m3pc_candidate_pass(h, &ra, S.states, S.actions, S.rewards, S.eps, nullptr, nullptr, h->sa_buf, f32, nullptr, nullptr, st));
-    CHK(cert_excl_leave(h, S));
-    if (!launch_topk_race(f32, nullptr, 0.f, N, 1, 0, 0, top1, top1v, st))
-        launch_window_stats(f32, N, top1, 1, 1, 1, 0.f, dstats + 8, nullptr, 0.f, top1v, st, 0);
-    CHK(check_launch("plan_step_certified (every candidate in fp32)"));
-    S.n_done = N;
-    S.seq = cert_next_seq(h, slot);
-    ++S.rounds;
-    CHK(m3pc_rescore_merge(h, f32, N, top1, 1, top1v, top1v, 0.f, S.merged, dstats, hstats, S.seq, st));
-    return cert_select(h, S);
-}
-// first pass, enqueued before anything is read: lists, fp32 re-score of the kmin best by score and the rfirst best by race
-// key, merge + certificates + select.  fp32 scores for every candidate: the select alone.
-static int cert_first_pass(m3pc_handle* h, CertStep& S) {
-    const int slot = S.a.slot, N = S.a.n_total, R = S.c.rmax, kmin = S.c.kmin, kmax = S.c.kmax, rfirst = S.c.rfirst;
-    if (S.a.precision == M3PC_PREC_FP32) {
-        HIPCHK(hipMemcpyAsync(S.merged, S.scores_low, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, S.tail));
-        return m3pc_select(h, S.scores_low, S.sample_actions, (long long)S.a.horizon * h->A, N, S.c.temperature, S.expo, S.p, S.eval_action,
-                           S.argmax, S.sample_idx, S.sample_action, S.tail);
-    }
-    int* L = cert_L(h, S);
-    float *B = h->cert_b[slot], *dstats = h->cert_stats[slot];
-    S.delta = (double)S.c.delta;  // (1.5 x a float deviation needs 25 bits: kept as the double the Python protocol keeps)
-    S.rounds = 0;
-    S.n_done = kmin;
-    S.r_done = rfirst;
-    if (R > 0) CHK(m3pc_topk_race_window(h, S.scores_low, S.expo, S.c.temperature, N, kmax, kmin, R, L, nullptr, B, nullptr, 0.f, S.tail));
-    else CHK(m3pc_topk_window(h, S.scores_low, N, kmax, kmin, 0.f, L, dstats + 8, B, nullptr, 0.f, S.tail));
-    CHK(cert_rescore(h, S, R - rfirst, R + kmin));
-    return cert_merge(h, S, kmin, rfirst, true);
-}
-// m3pc_amd/certificate.py:resolve -- read the certificates; raise delta when the re-scored set deviates by more than it
-// allows; re-score what a certificate asks for; stop when both are satisfied or every candidate has been scored in fp32
-// The eval_action certificate of m3pc_plan_step_certified_eval behind the step's last merge + select: the re-scored race entries
-// and the listed score entries (kmax of them; behind a window set the list is wholly re-scored), under delta as it stands.
-static int cert_eval_bound(m3pc_handle* h, CertStep& S, int n_listed, float eval_tol, float e8[8]) {
-    const int slot = S.a.slot, R = S.c.rmax;
-    float* dstats = h->cert_stats[slot] + 24;
-    h->eval_seq[slot] = h->eval_seq[slot] % 1000000 + 1;
-    const float seq = (float)h->eval_seq[slot];
-    CHK(m3pc_eval_bound(h, S.merged, S.a.n_total, cert_L(h, S) + R - S.r_done, S.r_done, S.n_done, n_listed, S.sample_actions,
-                        (long long)S.a.horizon * h->A, h->A, S.c.temperature, (float)S.delta, eval_tol, dstats, h->eval_host_dev + 8 * slot,
-                        seq, S.tail));
-    return cert_wait_block(h->eval_host + 8 * slot, dstats, seq, 8, S.tail, e8);
-}
-// eval_tol / erec: the third certificate (m3pc_plan_step_certified_eval); erec == NULL: the two certificates alone, nothing else
-// launched, read or allocated
-static int cert_resolve(m3pc_handle* h, CertStep& S, m3pc_cert_record* rec, float eval_tol = 0.f, m3pc_eval_record* erec = nullptr) {
-    const int slot = S.a.slot, N = S.a.n_total, R = S.c.rmax, kmax = S.c.kmax;
-    memset(rec, 0, sizeof(*rec));
-    if (erec) memset(erec, 0, sizeof(*erec));
-    if (S.a.precision == M3PC_PREC_FP32) {
-        rec->n_rescored = N;
-        rec->everything = rec->certified = 1;
-        if (erec) erec->eval_certified = 1;
-        return 0;
-    }
-    const int n_device = R > 0 ? 8 : 4;
-    bool saturated = false, everything = false;
-    int need = 0, need_race = 0;
-    float s8[8];
-    bool first = true;
-    for (;;) {  // (one turn without erec; with it, a turn per extension the eval certificate asks for)
-        for (;; first = false) {
-            CHK(cert_wait(h, slot, S.seq, everything || R == 0 ? 4 : n_device, S.tail, s8));
-            need = (int)s8[2];
-            need_race = (int)s8[5];
-            if (first) {
-                rec->need_first = need;
-                rec->need_race_first = need_race;
-            }
-            bool redo = false;
-            if (S.c.grow_delta && 1.5 * (double)s8[1] > S.delta && !everything) {
-                S.delta = 1.5 * (double)s8[1];
-                redo = S.n_done < N;
-            }
-            if (everything || S.n_done >= N) break;
-            if (!redo) {
-                if (need > S.n_done && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
-                    CHK(cert_window_set(h, S, N, true));
-                    everything = true;
-                    continue;
-                }
-                if (need > S.n_done) {
-                    if (need <= kmax) {
-                        CHK(cert_rescore(h, S, R + S.n_done, R + need));
-                        S.n_done = need;
-                        redo = true;
-                    } else {
-                        CHK(cert_window_set(h, S, need, false));
-                        saturated = true;
-                        everything = S.n_done >= N;
-                        continue;
-                    }
-                }
-                if (need_race > S.r_done) {
-                    if (need_race <= R) {
-                        CHK(cert_rescore(h, S, R - need_race, R - S.r_done));
-                        S.r_done = need_race;
-                        redo = true;
-                    } else {  // more racers than the race list holds: every candidate in fp32
-                        CHK(cert_window_set(h, S, N, true));
-                        saturated = everything = true;
-                        continue;
-                    }
-                }
-            }
-            if (!redo) break;
-            CHK(cert_merge(h, S, S.n_done, S.r_done, true));
-        }
-        first = false;
-        if (!erec) break;
-        if (everything || S.n_done >= N) {  // the select ran on fp32 scores alone
-            erec->eval_bound = 0.f;
-            erec->eval_certified = 1;
-            break;
-        }
-        float e8[8];
-        const int n_listed = saturated ? S.n_done : (kmax < N ? kmax : N);
-        CHK(cert_eval_bound(h, S, n_listed, eval_tol, e8));
-        const int need_eval = (int)e8[1];
-        if (++erec->eval_rounds == 1) erec->need_eval_first = need_eval;
-        erec->eval_bound = e8[0];
-        if (need_eval <= S.n_done) {
-            erec->eval_certified = 1;
-            break;
-        }
-        if (need_eval <= n_listed) {  // score entries [n_done, need_eval), merge + select again, every certificate read again
-            CHK(cert_rescore(h, S, R + S.n_done, R + need_eval));
-            erec->n_eval += need_eval - S.n_done;
-            S.n_done = need_eval;
-            CHK(cert_merge(h, S, S.n_done, S.r_done, true));
-        } else {  // the list cannot reach the tolerance: every candidate in fp32
-            CHK(cert_window_set(h, S, N, true));
-            everything = true;
-        }
-    }
-    rec->n_rescored = S.n_done;
-    rec->n_race = S.r_done;
-    rec->saturated = saturated;
-    rec->everything = everything;
-    rec->certified = everything || S.n_done >= N || (need <= S.n_done && need_race <= S.r_done);
-    rec->rounds = S.rounds;
-    rec->delta = (float)S.delta;
-    rec->shift = s8[0];
-    rec->deviation = s8[1];
-    rec->margin = s8[3];
-    return 0;
-}
-static void cert_fill(CertStep& S, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
-                      const float* rewards, const float* eps, const float* expo, float* sample_actions, float* scores_low, float* merged,
-                      int* list, float* p, float* eval_action, int* argmax, int* sample_idx, float* sample_action, hipStream_t tail, bool async) {
-    S.a = *a;
-    S.c = *c;
-    S.states = states;
-    S.actions = actions;
-    S.rewards = rewards;
-    S.eps = eps;
-    S.expo = expo;
-    S.sample_actions = sample_actions;
-    S.scores_low = scores_low;
-    S.merged = merged;
-    S.list = list;
-    S.p = p;
-    S.eval_action = eval_action;
-    S.argmax = argmax;
-    S.sample_idx = sample_idx;
-    S.sample_action = sample_action;
-    S.tail = tail;
-    S.async = async;
-    S.tail_pending = false;
-}
-
-// the serial certified step; with_eval: m3pc_plan_step_certified_eval (eval_tol, erec)
-static int cert_step_serial(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
-                            const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
-                            float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
-                            float* sample_action, m3pc_cert_record* rec, bool with_eval, float eval_tol, m3pc_eval_record* erec,
-                            void* stream, const char* who) {
-    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged || !rec ||
-        (with_eval && !erec))
-        return fail(M3PC_EINVAL, "null argument");
-    CHK(cert_check_step(a, c, who));
-    if (with_eval && !(eval_tol > 0.f)) return fail(M3PC_EINVAL, "%s: eval_tol must be > 0 (+inf: report only)", who);
-    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "%s with a pipelined step begun (m3pc_plan_step_certified_end first)", who);
-    memset(rec, 0, sizeof(*rec));
-    if (with_eval) {
-        memset(erec, 0, sizeof(*erec));
-        if (!h->eval_host && a->precision != M3PC_PREC_FP32) {  // the second host-mapped block of every slot, at the first such call
-            HIPCHK(hipSetDevice(h->device));
-            HIPCHK(hipHostMalloc((void**)&h->eval_host, (size_t)M3PC_SLOTS * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-            memset(h->eval_host, 0, (size_t)M3PC_SLOTS * 8 * sizeof(float));
-            HIPCHK(hipHostGetDevicePointer((void**)&h->eval_host_dev, h->eval_host, 0));
-        }
-    }
-    CertStep& S = h->cstep[a->slot];
-    cert_fill(S, a, c, states, actions, rewards, eps, expo, sample_actions, scores_low, merged, list, p, eval_action, argmax, sample_idx,
-              sample_action, (hipStream_t)stream, false);
-
-    // learner.py:278-316: policy pass (fp32), candidates, candidate pass in args->precision
-    m3pc_plan_args pa = *a;
-    pa.flags = a->flags & M3PC_PLAN_PRUNED_POLICY;
-    pa.window = 0;
-    CHK(m3pc_policy_pass(h, &pa, states, actions, rewards, nullptr, nullptr, stream));
-    pa.flags = 0;
-    CHK(m3pc_candidate_pass(h, &pa, states, actions, rewards, eps, loc, std_, sample_actions, scores_low, nullptr, nullptr, stream));
-    CHK(cert_first_pass(h, S));
-    return cert_resolve(h, S, rec, eval_tol, with_eval ? erec : nullptr);
-}
-
-int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
-                             const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
-                             float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
-                             float* sample_action, m3pc_cert_record* rec, void* stream) {
-    return cert_step_serial(h, a, c, states, actions, rewards, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p, eval_action,
-                            argmax, sample_idx, sample_action, rec, false, 0.f, nullptr, stream, "m3pc_plan_step_certified");
-}
-
-int m3pc_plan_step_certified_eval(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states,
-                                  const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std_,
-                                  float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
-                                  int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* rec, float eval_tol,
-                                  m3pc_eval_record* erec, void* stream) {
-    return cert_step_serial(h, a, c, states, actions, rewards, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p, eval_action,
-                            argmax, sample_idx, sample_action, rec, true, eval_tol, erec, stream, "m3pc_plan_step_certified_eval");
-}
-
-// ---- the certified step in two halves: _begin enqueues, _end resolves (include/m3pc_hip.h: "Pipelined certified steps")
-int m3pc_set_step_streams(m3pc_handle* h, void* chain0, void* chain1) {
-    if (!h) return fail(M3PC_EINVAL, "null handle");
-    if ((chain0 == nullptr) != (chain1 == nullptr) || (chain0 && chain0 == chain1))
-        return fail(M3PC_EINVAL, "m3pc_set_step_streams takes two different streams, or two NULLs");
-    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "m3pc_set_step_streams with a step begun");
-    if (h->step_chain_own) {
-        HIPCHK(hipSetDevice(h->device));
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipStreamSynchronize(h->step_chain[i]));
-            HIPCHK(hipStreamDestroy(h->step_chain[i]));
-        }
-    }
-    h->step_chain_own = false;
-    h->step_chain[0] = (hipStream_t)chain0;
-    h->step_chain[1] = (hipStream_t)chain1;
-    return 0;
-}
-static int step_setup(m3pc_handle* h) {
-    if (!h->step_chain[0]) {
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipStreamCreateWithFlags(&h->step_chain[i], hipStreamNonBlocking));
-            ++h->step_streams_created;
-        }
-        h->step_chain_own = true;
-    }
-    if (!h->ev_excl) {
-        for (int s = 0; s < M3PC_SLOTS; ++s)
-            for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreateWithFlags(&h->step_ev[s][i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_excl, hipEventDisableTiming));
-    }
-    return 0;
-}
-// the tail of a begun step on its chain stream: behind its candidate pass (every part: m3pc_candidate_join), then the first pass
-static int step_enqueue_tail(m3pc_handle* h, int slot) {
-    CertStep& S = h->cstep[slot];
-    HIPCHK(hipStreamWaitEvent(S.tail, h->step_ev[slot][2], 0));
-    CHK(m3pc_candidate_join(h, slot, S.tail));
-    S.tail_pending = false;
-    CHK(cert_first_pass(h, S));
-    HIPCHK(hipEventRecord(h->step_ev[slot][3], S.tail));
-    return 0;
-}
-
-int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states,
-                                   const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std_,
-                                   float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
-                                   int* argmax, int* sample_idx, float* sample_action, void* stream) {
-    if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged)
-        return fail(M3PC_EINVAL, "null argument");
-    CHK(cert_check_step(a, c, "m3pc_plan_step_certified_begin"));
-    const int slot = a->slot;
-    CertStep& S = h->cstep[slot];
-    if (S.begun) return fail(M3PC_ESTATE, "m3pc_plan_step_certified_begin: the step in slot %d has not been ended", slot);
-    HIPCHK(hipSetDevice(h->device));
-    CHK(step_setup(h));
-    hipStream_t st = (hipStream_t)stream, chain = h->step_chain[slot & 1];
-    hipEvent_t* ev = h->step_ev[slot];
-    // the window is complete in `stream` order: the chain stream reads it behind ev_in (M3PC_PLAN_INPUTS_READY: complete already)
-    if (!(a->flags & M3PC_PLAN_INPUTS_READY)) {
-        HIPCHK(hipEventRecord(ev[0], st));
-        HIPCHK(hipStreamWaitEvent(chain, ev[0], 0));
-    }
-    m3pc_plan_args pa = *a;
-    pa.flags = a->flags & M3PC_PLAN_PRUNED_POLICY;
-    pa.window = 0;
-    CHK(m3pc_policy_pass(h, &pa, states, actions, rewards, nullptr, nullptr, chain));
-    HIPCHK(hipEventRecord(ev[1], chain));
-    // the pending-tail rule: the tails of the earlier steps of this parity go behind this step's policy pass, oldest first
-    for (;;) {
-        int o = -1;
-        for (int s = 0; s < M3PC_SLOTS; ++s)
-            if ((s & 1) == (slot & 1) && h->cstep[s].begun && h->cstep[s].tail_pending && (o < 0 || h->cstep[s].order < h->cstep[o].order))
-                o = s;
-        if (o < 0) break;
-        CHK(step_enqueue_tail(h, o));
-    }
-    // the candidate pass on the caller's stream: behind the policy pass, behind what overflowed into the candidate workspace, and
-    // behind the candidate pass enqueued last (free when the caller plans on one stream)
-    HIPCHK(hipStreamWaitEvent(st, ev[1], 0));
-    if (h->excl_valid) HIPCHK(hipStreamWaitEvent(st, h->ev_excl, 0));
-    if (h->cand_last_slot >= 0) HIPCHK(hipStreamWaitEvent(st, h->step_ev[h->cand_last_slot][2], 0));
-    pa.flags = M3PC_PLAN_DEFER_JOIN;
-    CHK(m3pc_candidate_pass(h, &pa, states, actions, rewards, eps, loc, std_, sample_actions, scores_low, nullptr, nullptr, stream));
-    HIPCHK(hipEventRecord(ev[2], st));
-    h->cand_last_slot = slot;
-    cert_fill(S, a, c, states, actions, rewards, eps, expo, sample_actions, scores_low, merged, list, p, eval_action, argmax, sample_idx,
-              sample_action, chain, true);
-    S.tail_pending = true;
-    S.begun = true;
-    S.order = ++h->step_order;
-    return 0;
-}
-
-int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* rec, void* stream) {
-    if (!h || !rec) return fail(M3PC_EINVAL, "null argument");
-    if (slot < 0 || slot >= M3PC_SLOTS) return fail(M3PC_EINVAL, "slot %d outside [0, %d)", slot, M3PC_SLOTS);
-    CertStep& S = h->cstep[slot];
-    if (!S.begun) return fail(M3PC_ESTATE, "m3pc_plan_step_certified_end: no step begun in slot %d", slot);
-    HIPCHK(hipSetDevice(h->device));
-    S.begun = false;  // (whatever happens below, the slot is free again)
-    if (S.tail_pending) CHK(step_enqueue_tail(h, slot));
-    const int rounds = S.rounds;
-    CHK(cert_resolve(h, S, rec));
-    if (S.rounds != rounds) HIPCHK(hipEventRecord(h->step_ev[slot][3], S.tail));
-    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->step_ev[slot][3], 0));
-    return 0;
-}
-
-// ---- a lock-step batch of certified plan steps as one call (include/m3pc_hip.h: m3pc_plan_steps_certified): the order of
-// m3pc_amd/lockstep.py with the batched kernels of select.hip around ONE fp32 scoring pass, then certificate.py:resolve per window
-using Lockstep = m3pc_handle::Lockstep;
-static const int LS_ROW = 64 + 1024;  // list entries a window can hold (rmax <= 64 in front of 1024)
-static int ls_setup(m3pc_handle* h) {
-    Lockstep& W = h->ls;
-    if (W.ready) return 0;
-    const size_t E = (size_t)(h->dm.max_batch > 0 ? h->dm.max_batch : 1);
-    W.cand_rows = h->dm.max_candidates > h->chain[0].max_cand ? h->dm.max_candidates : h->chain[0].max_cand;
-    if (!W.list) CHK(dmalloc(&W.list, E * LS_ROW));
-    if (!W.b) CHK(dmalloc(&W.b, E * LS_ROW));
-    if (!W.f) CHK(dmalloc(&W.f, E * LS_ROW));
-    if (!W.stats) CHK(dmalloc(&W.stats, E * 24));
-    if (!W.cand) CHK(dmalloc(&W.cand, (size_t)W.cand_rows * h->T * h->A));
-    if (!W.fs) CHK(dmalloc(&W.fs, (size_t)W.cand_rows));
-    if (!W.widx) CHK(dmalloc(&W.widx, (size_t)W.cand_rows));
-    if (!W.host) {
-        HIPCHK(hipHostMalloc((void**)&W.host, E * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-        memset(W.host, 0, E * 8 * sizeof(float));
-        HIPCHK(hipHostGetDevicePointer((void**)&W.host_dev, W.host, 0));
-    }
-    W.seq_w.assign(E, 0.f);
-    W.ready = true;
-    return 0;
-}
-static float ls_next_seq(Lockstep& W) {
-    W.seq = W.seq % 1000000 + 1;
-    return (float)W.seq;
-}
-// cert_wait for the windows [w0, w1): ONE bounded spin until block w holds the sequence number issued last for window w (seq_w),
-// for all of them; on expiry one synchronisation of the stream and the device copies.  out: 8 floats per window.
-static int ls_wait(m3pc_handle* h, int w0, int w1, int n_device, hipStream_t st, float* out) {
-    Lockstep& W = h->ls;
-    const volatile float* hs = W.host;
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    for (int w = w0; w < w1; ++w)
-        while (hs[8 * w + 4] != W.seq_w[w]) {
-            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
-                if (hipStreamSynchronize(st) != hipSuccess ||
-                    hipMemcpy(out, W.stats + 8 * w0, (size_t)(w1 - w0) * 8 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-                    return fail(M3PC_EHIP, "the statistics of the lock-step batch reached neither host-mapped memory within 10 s nor the host by a copy");
-                for (int v = 0; v < w1 - w0; ++v)
-                    for (int i = n_device; i < 8; ++i) out[8 * v + i] = 0.f;
-                return 0;
-            }
-        }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    for (int i = 8 * w0; i < 8 * w1; ++i) out[i - 8 * w0] = hs[i];
-    return 0;
-}
-
-int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, int n_windows, const float* states,
-                              const float* actions, const float* rewards, const double* rtg, const float* eps, const float* expo,
-                              float* loc, float* std_, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
-                              float* eval_action, int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* records,
-                              void* stream) {
-    static const char* who = "m3pc_plan_steps_certified";
-    if (!h || !a || !c || !states || !actions || !rewards || !rtg || !eps || !expo || !sample_actions || !scores_low || !merged || !records)
-        return fail(M3PC_EINVAL, "null argument");
-    if (n_windows < 1) return fail(M3PC_EINVAL, "%s: n_windows %d < 1", who, n_windows);
-    if (a->returns) return fail(M3PC_EINVAL, "%s takes rtg per window, not a returns row (args->returns must be NULL)", who);
-    CHK(cert_check_step(a, c, who));
-    if (a->mode < 0 || a->mode > 2) return fail(M3PC_EINVAL, "bad mode %d", a->mode);
-    // from here on the handle is read
-    const int E = n_windows;
-    if (E > h->dm.max_batch) return fail(M3PC_EINVAL, "%s: n_windows %d > max_batch=%d", who, E, h->dm.max_batch);
-    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "%s with a pipelined step begun (m3pc_plan_step_certified_end first)", who);
-    if (a->mode != M3PC_MODE_RTG && !h->critic_set) return fail(M3PC_ESTATE, "critic weights not set");
-    if (a->precision != M3PC_PREC_FP32) {  // (the rows one scoring call can take: what ls_setup sizes the gathered rows by)
-        const long long rows = h->dm.max_candidates > h->chain[0].max_cand ? h->dm.max_candidates : h->chain[0].max_cand;
-        if ((long long)n_windows * (c->rfirst + c->kmin) > rows)
-            return fail(M3PC_ENOMEM, "%s: the first pass re-scores %d x %d candidates, more than max(max_candidates, max_rescore)=%lld", who,
-                        n_windows, c->rfirst + c->kmin, rows);
-    }
-    HIPCHK(hipSetDevice(h->device));
-    CHK(ls_setup(h));
-    Lockstep& W = h->ls;
-    hipStream_t st = (hipStream_t)stream;
-    const int N = a->n_total, T = h->T, S = h->S, A = h->A, hz = a->horizon, slot = a->slot;
-    const long long row = (long long)hz * A, eps_w = (long long)N * (a->mode == M3PC_MODE_NOISE ? hz : T) * A;
-    const float temp = c->temperature;
-    memset(records, 0, (size_t)E * sizeof(*records));
-
-    // lockstep.py:57-62: ONE policy pass at batch E, every window's own candidate pass back to back, one join
-    m3pc_plan_args pa = *a;
-    pa.flags = 0;
-    pa.window = 0;
-    CHK(m3pc_policy_pass_batch(h, &pa, E, states, actions, rewards, rtg, nullptr, nullptr, stream));
-    pa.flags = M3PC_PLAN_DEFER_JOIN;
-    for (int w = 0; w < E; ++w) {
-        pa.window = w;
-        CHK(m3pc_candidate_pass(h, &pa, states + (size_t)w * T * S, actions + (size_t)w * T * A, rewards + (size_t)w * T, eps + w * eps_w,
-                                loc ? loc + (size_t)w * T * A : nullptr, std_ ? std_ + (size_t)w * T * A : nullptr, sample_actions + w * N * row,
-                                scores_low + (size_t)w * N, nullptr, nullptr, stream));
-    }
-    CHK(m3pc_candidate_join(h, slot, stream));
-
-    SelectP sel;  // window 0's select; window w at + w of every array
-    memset(&sel, 0, sizeof(sel));
-    sel.a0 = sample_actions;
-    sel.a0_stride = row;
-    sel.n = N;
-    sel.A = A;
-    sel.temperature = temp;
-    sel.expo = expo;
-    sel.p = p;
-    sel.eval_action = eval_action;
-    sel.argmax = argmax;
-    sel.sample_idx = sample_idx;
-    sel.sample_action = sample_action;
-    if (a->precision == M3PC_PREC_FP32) {  // fp32 scores for every candidate: the select alone, all windows in one launch
-        HIPCHK(hipMemcpyAsync(merged, scores_low, (size_t)E * N * sizeof(float), hipMemcpyDeviceToDevice, st));
-        sel.er = scores_low;
-        launch_select_batch(sel, E, N, N * row, st);
-        for (int w = 0; w < E; ++w) {
-            records[w].n_rescored = N;
-            records[w].everything = records[w].certified = 1;
-        }
-        return check_launch(who);
-    }
-
-    const int R = c->rmax, kmin = c->kmin, kmax = c->kmax, rfirst = c->rfirst, LS = R + 1024, m0 = rfirst + kmin;
-    const int kk = kmax + 1 < N ? kmax + 1 : N, cap = h->chain[0].max_cand;
-    int* L = list ? list : W.list;  // rows of LS entries, as are B and F
-    float *B = W.b, *F = W.f;
-    auto Lw = [&](int w) { return L + (size_t)w * LS; };
-    auto Bw = [&](int w) { return B + (size_t)w * LS; };
-    auto Fw = [&](int w) { return F + (size_t)w * LS; };
-    auto low = [&](int w) { return scores_low + (size_t)w * N; };
-    auto scratch = [&](int w) { return W.stats + 8 * (size_t)h->dm.max_batch + 16 * (size_t)w; };
-    // lockstep.py:93-100: the lists of every window (the kmax + 1 best by score, the rmax best by race key) in one launch
-    if (!launch_topk_race_batch(scores_low, expo, temp, E, N, N, kk, R, R, L, B, LS, st)) {
-        for (int w = 0; w < E; ++w)  // (the device refused the LDS of the batched ranking: the one-window launches, same lists)
-            if (!launch_topk_race(low(w), R > 0 ? expo + (size_t)w * N : nullptr, temp, N, kk, R, R, Lw(w), Bw(w), st))
-                launch_window_stats(low(w), N, Lw(w) + R, kk, kmin, kmax, 0.f, scratch(w), nullptr, 0.f, Bw(w) + R, st, R);
-    }
-    // lockstep.py:106-110: list positions [rmax - rfirst, rmax + kmin) of every window, window-major, in ONE fp32 scoring pass
-    launch_gather_listed(sample_actions, E, N, (int)row, L, LS, R - rfirst, m0, W.cand, W.widx, st);
-    CHK(check_launch(who));
-    m3pc_plan_args sa = *a;
-    sa.mode = a->mode == M3PC_MODE_RTG ? M3PC_MODE_RTG : M3PC_MODE_CRITIC;
-    sa.precision = M3PC_PREC_FP32;
-    sa.flags = 0;
-    sa.window = 0;
-    sa.n_begin = 0;
-    sa.n_total = sa.n_count = E * m0;
-    CHK(m3pc_score_actions(h, &sa, E, states, actions, rewards, W.cand, W.widx, W.fs, nullptr, nullptr, stream));
-    // lockstep.py:111-123: merge + certificates + select of every window in one launch, the statistics to the windows' host blocks
-    std::vector<int> n_done(E, kmin), r_done(E, rfirst);
-    std::vector<float> d0(E, c->delta), s8((size_t)E * 8);
-    const float seq0 = ls_next_seq(W);
-    MergeSelectBatchP P;
-    memset(&P, 0, sizeof(P));
-    P.b = scores_low;
-    P.expo = expo;
-    P.row_stride = N;
-    P.n_total = N;
-    P.race = R > 0;
-    P.select = 1;
-    P.tau = temp;
-    P.list = L;
-    P.list_scores = B;
-    P.list_stride = LS;
-    P.rmax = R;
-    P.f = W.fs;
-    P.f_stride = m0;
-    P.f_lo = R - rfirst;
-    P.out = merged;
-    P.stats = W.stats;
-    P.host_stats = W.host_dev;
-    P.seq = seq0;
-    P.a0 = sample_actions;
-    P.a0_wstride = N * row;
-    P.a0_stride = row;
-    P.A = A;
-    P.p = p;
-    P.eval_action = eval_action;
-    P.argmax = argmax;
-    P.sample_idx = sample_idx;
-    P.sample_action = sample_action;
-    launch_merge_select_batch(P, E, r_done.data(), n_done.data(), d0.data(), st);
-    for (int w = 0; w < E; ++w) {
-        W.seq_w[w] = seq0;
-        records[w].rounds = 1;
-    }
-    // (the re-scores into the list's layout, where the one-window merges behind the certificates read them)
-    HIPCHK(hipMemcpy2DAsync(F + (R - rfirst), (size_t)LS * sizeof(float), W.fs, (size_t)m0 * sizeof(float), (size_t)m0 * sizeof(float), E,
-                            hipMemcpyDeviceToDevice, st));
-    CHK(check_launch(who));
-    CHK(ls_wait(h, 0, E, R > 0 ? 8 : 4, st, s8.data()));  // the ONE host wait of the first pass: E sequence numbers
-
-    // ---- per window, ascending: certificate.py:resolve with the device work of _WindowOps
-    auto select_w = [&](int w, const float* er) -> int {
-        return m3pc_select(h, er, sample_actions + w * N * row, row, N, temp, expo + (size_t)w * N, p ? p + (size_t)w * N : nullptr,
-                           eval_action ? eval_action + (size_t)w * A : nullptr, argmax ? argmax + w : nullptr,
-                           sample_idx ? sample_idx + w : nullptr, sample_action ? sample_action + (size_t)w * A : nullptr, stream);
-    };
-    auto merge_w = [&](int w, int n, int r, double delta) -> int {  // _WindowOps.merge_select
-        const int o = R - r;
-        float *mw = merged + (size_t)w * N, *dst = W.stats + 8 * (size_t)w, *hst = W.host_dev + 8 * (size_t)w;
-        W.seq_w[w] = ls_next_seq(W);
-        ++records[w].rounds;
-        if (R > 0)
-            return m3pc_merge_race_select(h, low(w), expo + (size_t)w * N, temp, N, Lw(w) + o, r, n, Bw(w) + o, Fw(w) + o, (float)delta, mw, dst,
-                                          hst, W.seq_w[w], sample_actions + w * N * row, row, p ? p + (size_t)w * N : nullptr,
-                                          eval_action ? eval_action + (size_t)w * A : nullptr, argmax ? argmax + w : nullptr,
-                                          sample_idx ? sample_idx + w : nullptr, sample_action ? sample_action + (size_t)w * A : nullptr, stream);
-        CHK(m3pc_rescore_merge(h, low(w), N, Lw(w), n, Bw(w), Fw(w), (float)delta, mw, dst, hst, W.seq_w[w], stream));
-        return select_w(w, mw);
-    };
-    auto rescore_w = [&](int w, int lo, int hi) -> int {  // _WindowOps._score: list positions [lo, hi), chunks of max_rescore
-        for (int c0 = lo; c0 < hi; c0 += cap) {
-            const int m = hi - c0 < cap ? hi - c0 : cap;
-            launch_gather_listed(sample_actions + w * N * row, 1, N, (int)row, Lw(w), LS, c0, m, W.cand, nullptr, st);
-            sa.n_total = sa.n_count = m;
-            CHK(m3pc_score_actions(h, &sa, 1, states + (size_t)w * T * S, actions + (size_t)w * T * A, rewards + (size_t)w * T, W.cand, nullptr,
-                                   Fw(w) + c0, nullptr, nullptr, stream));
-        }
-        return 0;
-    };
-    auto window_set_w = [&](int w, int need, bool everything, double delta) -> int {  // _WindowOps.window_set
-        const int cnt = need < N ? need : N;
-        if (cnt <= 1024 - 32 && !everything) {
-            if (!launch_topk_race(low(w), nullptr, 0.f, N, cnt, 0, R, Lw(w), Bw(w), st))
-                launch_window_stats(low(w), N, Lw(w) + R, cnt, 1, cnt, 0.f, scratch(w), nullptr, 0.f, Bw(w) + R, st, 0);
-            CHK(check_launch("plan_steps_certified (window set)"));
-            CHK(rescore_w(w, R, R + cnt));
-            n_done[w] = cnt;
-            return merge_w(w, cnt, r_done[w], delta);
-        }
-        float* f32 = h->cert_f32[slot];
-        int* top1 = h->cert_top1[slot];
-        float *top1v = scratch(w) + 8, *mw = merged + (size_t)w * N;
-        sa.n_total = sa.n_count = N;
-        CHK(m3pc_score_actions(h, &sa, 1, states + (size_t)w * T * S, actions + (size_t)w * T * A, rewards + (size_t)w * T,
-                               sample_actions + w * N * row, nullptr, f32, nullptr, nullptr, stream));
-        if (!launch_topk_race(f32, nullptr, 0.f, N, 1, 0, 0, top1, top1v, st))
-            launch_window_stats(f32, N, top1, 1, 1, 1, 0.f, scratch(w), nullptr, 0.f, top1v, st, 0);
-        CHK(check_launch("plan_steps_certified (every candidate in fp32)"));
-        n_done[w] = N;  // (r_done stays: the record's n_race is what resolve counted, as in the Python protocol)
-        W.seq_w[w] = ls_next_seq(W);
-        ++records[w].rounds;
-        CHK(m3pc_rescore_merge(h, f32, N, top1, 1, top1v, top1v, 0.f, mw, W.stats + 8 * (size_t)w, W.host_dev + 8 * (size_t)w, W.seq_w[w], stream));
-        return select_w(w, mw);
-    };
-
-    double delta = (double)c->delta;  // (1.5 x a float deviation needs 25 bits: the double the Python protocol keeps)
-    const double delta_first = delta;
-    for (int w = 0; w < E; ++w) {
-        m3pc_cert_record* rec = records + w;
-        float* s = s8.data() + 8 * (size_t)w;
-        bool have = true;  // the statistics of the window's last merge are on the host already
-        if (delta > delta_first) {  // an earlier window raised the bound: this window's certificate again, under it
-            CHK(merge_w(w, n_done[w], r_done[w], delta));
-            have = false;
-        }
-        bool saturated = false, everything = false;
-        int need = 0, need_race = 0;
-        for (bool first = true;; first = false) {
-            if (!have) CHK(ls_wait(h, w, w + 1, everything || R == 0 ? 4 : 8, st, s));
-            have = false;
-            need = (int)s[2];
-            need_race = (int)s[5];
-            if (first) {
-                rec->need_first = need;
-                rec->need_race_first = need_race;
-            }
-            bool redo = false;
-            if (c->grow_delta && 1.5 * (double)s[1] > delta && !everything) {
-                delta = 1.5 * (double)s[1];
-                redo = n_done[w] < N;
-            }
-            if (everything || n_done[w] >= N) break;
-            if (!redo) {
-                if (need > n_done[w] && saturated) {  // the window set's certificate still asks for more: every candidate in fp32
-                    CHK(window_set_w(w, N, true, delta));
-                    everything = true;
-                    continue;
-                }
-                if (need > n_done[w]) {
-                    if (need <= kmax) {
-                        CHK(rescore_w(w, R + n_done[w], R + need));
-                        n_done[w] = need;
-                        redo = true;
-                    } else {
-                        CHK(window_set_w(w, need, false, delta));
-                        saturated = true;
-                        everything = n_done[w] >= N;
-                        continue;
-                    }
-                }
-                if (need_race > r_done[w]) {
-                    if (need_race <= R) {
-                        CHK(rescore_w(w, R - need_race, R - r_done[w]));
-                        r_done[w] = need_race;
-                        redo = true;
-                    } else {  // more racers than the race list holds: every candidate in fp32
-                        CHK(window_set_w(w, N, true, delta));
-                        saturated = everything = true;
-                        continue;
-                    }
-                }
-            }
-            if (!redo) break;
-            CHK(merge_w(w, n_done[w], r_done[w], delta));
-        }
-        rec->n_rescored = n_done[w];
-        rec->n_race = r_done[w];
-        rec->saturated = saturated;
-        rec->everything = everything;
-        rec->certified = everything || n_done[w] >= N || (need <= n_done[w] && need_race <= r_done[w]);
-        rec->delta = (float)delta;
-        rec->shift = s[0];
-        rec->deviation = s[1];
-        rec->margin = s[3];
-    }
-    return 0;
-}
-
 int m3pc_draw_variates(m3pc_handle* h, unsigned long long seed, unsigned long long step, int n_begin, int n_count, int row_elems,
                        float* eps, float* expo, void* stream) {
     if (!h) return fail(M3PC_EINVAL, "null handle");
@@ -2112,30 +1305,6 @@ int m3pc_draw_variates(m3pc_handle* h, unsigned long long seed, unsigned long lo
     launch_variates(seed, step, 0, (long long)n_begin * row_elems, ((long long)n_begin + n_count) * row_elems, eps, (hipStream_t)stream);
     launch_variates(seed, step, 1, n_begin, (long long)n_begin + n_count, expo, (hipStream_t)stream);
     return check_launch("draw_variates");
-}
-
-// HipPlanner._calibrate as a call: delta from ONE full fp32 candidate pass over the step's candidates
-int m3pc_calibrate_delta(m3pc_handle* h, const m3pc_plan_args* a, const float* states, const float* actions, const float* rewards,
-                         const float* eps, const float* scores_low, float factor, float* delta_out, void* stream) {
-    if (!h || !a || !states || !actions || !rewards || !eps || !scores_low || !delta_out) return fail(M3PC_EINVAL, "null argument");
-    CHK(cert_check_args(a, "m3pc_calibrate_delta"));
-    if (!(factor > 0.f)) return fail(M3PC_EINVAL, "factor must be > 0");
-    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "m3pc_calibrate_delta with a pipelined step begun (m3pc_plan_step_certified_end first)");
-    hipStream_t st = (hipStream_t)stream;
-    const int N = a->n_total;
-    m3pc_plan_args fa = *a;
-    fa.precision = M3PC_PREC_FP32;
-    fa.flags = 0;
-    fa.window = 0;
-    float* f32 = h->cert_f32[a->slot];
-    CHK(m3pc_candidate_pass(h, &fa, states, actions, rewards, eps, nullptr, nullptr, h->sa_buf, f32, nullptr, nullptr, stream));
-    const float seq = cert_next_seq(h, a->slot);
-    launch_deviation_stats(scores_low, f32, N, h->cert_stats[a->slot], h->cert_host_dev + 8 * a->slot, seq, st);
-    CHK(check_launch("calibrate_delta"));
-    float s8[8];
-    CHK(cert_wait(h, a->slot, seq, 8, st, s8));
-    *delta_out = cert_delta(factor, s8[1], s8[2]);
-    return 0;
 }
 
 // ---- CEM / MPPI refinement of a plan (include/m3pc_hip.h: m3pc_refit_resample, m3pc_refine_plan; kernels: refine.hip)
@@ -2275,918 +1444,6 @@ int m3pc_refine_plan(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_refine_
     }
     return 0;
 }
-
-#ifdef M3PC_LAB  // ---- kernel-level test / bench hooks: libm3pc_hip_lab.so only, declared in include/m3pc_hip_debug.h
-// streams the handle created for its pipelined certified steps (0 while the caller's pair of m3pc_set_step_streams serves them)
-int m3pc_debug_step_streams_created(m3pc_handle* h) { return h ? h->step_streams_created : -1; }
-// Lab build only (include/m3pc_hip_debug.h): lets tools/gemm_bench.py time the GEMM kernel on the plan step's shapes.
-int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias, const float* res, void* C, int M, int N,
-                    int K, int gelu, int f32out, int variant, void* stream) {
-    static const int ldpad = M3PC_ENV("M3PC_DEBUG_LDPAD") ? atoi(M3PC_ENV("M3PC_DEBUG_LDPAD")) : 0;  // operand row padding (elements)
-    GemmP p = gemm_basic(A, K + ldpad, Wt, K + ldpad, M, N, K, bias);
-    p.a_padded = 0;  // (a caller's tensor: nothing is known about the memory behind it)
-    p.gelu = gelu;
-    p.res = res;
-    p.ldr = N;
-    p.variant = variant;
-    if (dtype == DT_BF16 && !f32out)
-        p.Cb = (bf16_t*)C;
-    else
-        p.Cf = (float*)C;
-    p.ldc = N;
-    if (dtype != DT_BF16 && variant != 1) {  // split-K workspace as the handle provides it (variant 1: none)
-        static float* ws = nullptr;
-        if (!ws) HIPCHK(hipMalloc((void**)&ws, 64 << 20));
-        p.ws = ws;
-        p.ws_bytes = 64 << 20;
-    }
-    if (dtype == DT_X3) {  // A fp32, Wt fp32: split into hi / lo bf16 copies here, as m3pc_load_weights splits the weights
-        static bf16_t* wsplit = nullptr;
-        static size_t cap = 0;
-        const size_t n = (size_t)N * (K + ldpad);
-        if (n > cap) {
-            if (wsplit) HIPCHK(hipFree(wsplit));
-            wsplit = nullptr;
-            cap = 0;
-            HIPCHK(hipMalloc((void**)&wsplit, 2 * n * sizeof(bf16_t)));
-            cap = n;
-        }
-        launch_f32_split_bf16((const float*)Wt, wsplit, wsplit + n, (long long)n, (hipStream_t)stream);
-        p.W = wsplit;
-        p.w_lo_off = (long long)n;
-        if (launch_gemm_x3(p, (hipStream_t)stream) < 0) return fail(M3PC_EINVAL, "debug_gemm: shape not covered by the x3 kernel");
-        return check_launch("debug_gemm");
-    }
-    launch_gemm(p, dtype, (hipStream_t)stream);
-    return check_launch("debug_gemm");
-}
-
-// Every GEMM the library launches, on caller tensors, with everything a GemmP can carry (tests/test_gemm_edges_gpu.py).  The
-// checks below are the shape rules of the register-staged kernel every problem can fall back to; what the dispatch would launch is
-// learnt from a dry walk of the launchers (g_gemm_dry, csrc/kernels.h), so nothing reaches the GPU before the call is known to be
-// covered.  Fills `p` (and, for dtype 2, nothing yet of W's split) or returns the error.
-static int debug_gemm_fill(const m3pc_debug_gemm_args* a, GemmP& p) {
-    if (!a) return fail(M3PC_EINVAL, "debug_gemm_ex: null argument");
-    const int dt = a->dtype;
-    if (dt != DT_F32 && dt != DT_BF16 && dt != DT_X3) return fail(M3PC_EINVAL, "debug_gemm_ex: dtype %d", dt);
-    if (!a->A || !a->W || !a->C) return fail(M3PC_EINVAL, "debug_gemm_ex: null operand");
-    if (a->M < 1 || a->M > (1 << 20) || a->N < 32 || a->N > (1 << 16) || a->K < 1 || a->K > (1 << 16)) return fail(M3PC_EINVAL, "debug_gemm_ex: M / N / K out of range");
-    const int es = dt == DT_BF16 ? 2 : 4;  // bytes per element of A (x3: fp32 activations; its W copies are bf16)
-    if (a->N % 32) return fail(M3PC_EINVAL, "debug_gemm_ex: N %d is not a multiple of 32 (columns would be dropped)", a->N);
-    if (((long long)a->K * es) % 128) return fail(M3PC_EINVAL, "debug_gemm_ex: K %d is not a whole number of 128-byte k-tiles (k terms would be dropped)", a->K);
-    if (dt == DT_F32 && !a->f32out) return fail(M3PC_EINVAL, "debug_gemm_ex: fp32 operands have fp32 output only");
-    const int f32out = dt == DT_F32 || a->f32out;
-    const int os = f32out ? 4 : 2;
-    const uintptr_t ptrs = (uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->C | (uintptr_t)a->bias | (uintptr_t)a->rowtab | (uintptr_t)a->res |
-                           (uintptr_t)a->ws | (uintptr_t)a->ln_g | (uintptr_t)a->ln_b | (uintptr_t)a->ln_out | (uintptr_t)a->a_ln_g |
-                           (uintptr_t)a->a_ln_b;
-    if (ptrs & 15) return fail(M3PC_EINVAL, "debug_gemm_ex: pointers must be 16-byte aligned");
-    if (a->lda < a->K || a->ldw < a->K || a->ldc < a->N || (a->res && a->ldr < a->N) || (a->rowtab && a->rt_ld < a->N))
-        return fail(M3PC_EINVAL, "debug_gemm_ex: a leading dimension is below its row length");
-    // (x3: W's bf16 copies keep ldw, so their rows need ldw % 8 as well)
-    if (((long long)a->lda * es) % 16 || ((long long)a->ldw * (dt == DT_F32 ? 4 : 2)) % 16 || (dt == DT_X3 && a->ldw % 4) || ((long long)a->ldc * os) % 16 ||
-        (a->res && a->ldr % 4) || (a->rowtab && a->rt_ld % 4))
-        return fail(M3PC_EINVAL, "debug_gemm_ex: rows of a leading dimension leave 16-byte alignment");
-    if (a->rowtab && a->rt_mod < 1) return fail(M3PC_EINVAL, "debug_gemm_ex: rowtab with rt_mod %d", a->rt_mod);
-    for (const int* m : {a->amap, a->cmap})
-        if (m[0] < 0 || m[2] < 0 || (m[0] >= 1 && m[1] < m[0])) return fail(M3PC_EINVAL, "debug_gemm_ex: row map {%d, %d, %d}", m[0], m[1], m[2]);
-    if (a->ws && a->ws_bytes < 0) return fail(M3PC_EINVAL, "debug_gemm_ex: negative ws_bytes");
-    if (a->ln_out && (!f32out || !a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_gemm_ex: ln_out needs fp32 C, ln_g and ln_b");
-    if ((a->a_ln_g != nullptr) != (a->a_ln_b != nullptr)) return fail(M3PC_EINVAL, "debug_gemm_ex: a_ln_g and a_ln_b go together");
-    const int v = a->variant;
-    if (!(v == 0 || (dt == DT_BF16 && (v == 2 || v == 26 || v == 37 || v == 43 || v == 44)) || (dt == DT_F32 && v == 2)))
-        return fail(M3PC_EINVAL, "debug_gemm_ex: variant %d of dtype %d is not one this hook drives", v, dt);
-    // (a_padded vouches for 127 rows behind A: a ragged 256-row tile of gemm_line_kernel<256>'s persistent form may need up to 255)
-    if (v == 44 && a->a_padded && a->M % 256 && 256 - a->M % 256 > 127)
-        return fail(M3PC_EINVAL, "debug_gemm_ex: variant 44 with a_padded would read %d rows behind A", 256 - a->M % 256);
-    p = gemm_basic(a->A, a->lda, a->W, a->ldw, a->M, a->N, a->K, a->bias);
-    p.amap = RowMap{a->amap[0], a->amap[1], a->amap[2]};
-    p.cmap = RowMap{a->cmap[0], a->cmap[1], a->cmap[2]};
-    p.rowtab = a->rowtab;
-    if (a->rowtab) {
-        p.rt_mod = a->rt_mod;
-        p.rt_ld = a->rt_ld;
-    }
-    p.gelu = a->gelu ? 1 : 0;
-    p.res = a->res;
-    p.ldr = a->ldr;
-    if (f32out)
-        p.Cf = (float*)a->C;
-    else
-        p.Cb = (bf16_t*)a->C;
-    p.ldc = a->ldc;
-    p.ws = a->ws;
-    p.ws_bytes = a->ws ? a->ws_bytes : 0;
-    p.a_padded = a->a_padded ? 1 : 0;
-    p.ln_g = a->ln_out ? a->ln_g : nullptr;
-    p.ln_b = a->ln_out ? a->ln_b : nullptr;
-    p.ln_out = a->ln_out;
-    p.a_ln_g = a->a_ln_g;
-    p.a_ln_b = a->a_ln_b;
-    p.variant = v;
-    if (a->a_ln_g && (dt != DT_F32 || !a->ws || v == 2 || !gemm_f32_direct_covers(p)))
-        return fail(M3PC_EINVAL, "debug_gemm_ex: a_ln_* on a problem the few-row fp32 kernel does not take (the fold would be dropped)");
-    return 0;
-}
-
-// the checks and the dry walk: fills p (x3: W still the caller's fp32 tensor) and plan[4] = what the dispatch would launch
-static int debug_gemm_plan(const m3pc_debug_gemm_args* a, GemmP& p, int* plan) {
-    if (a && a->picked) a->picked[0] = a->picked[1] = a->picked[2] = a->picked[3] = 0;
-    if (int rc = debug_gemm_fill(a, p)) return rc;
-    const int dt = a->dtype;
-    if (dt == DT_X3) p.w_lo_off = (long long)a->N * a->ldw;  // (the hi / lo copies keep W's layout)
-    M3PC_GEMM_PICK(0, 0, 0, 0);
-    g_gemm_dry = 1;
-    const int dry = dt == DT_X3 ? launch_gemm_x3(p, nullptr) : launch_gemm(p, dt, nullptr);
-    g_gemm_dry = 0;
-    for (int i = 0; i < 4; ++i) plan[i] = g_gemm_picked[i];
-    if (dry < 0 || plan[0] == 0) return fail(M3PC_EINVAL, "debug_gemm_ex: no kernel of the dispatch covers this problem (epilogue flags / shape)");
-    if (a->N % 64 && plan[0] != 5)  // (only the few-row fp32 kernel has 32-column tiles)
-        return fail(M3PC_EINVAL, "debug_gemm_ex: N %d is not a multiple of 64 (kernel %d would drop columns)", a->N, plan[0]);
-    const int v = a->variant;
-    const int want = dt != DT_BF16 ? 0 : v == 2 ? 8 : v == 26 ? 7 : v == 37 ? 9 : v == 43 ? 10 : v == 44 ? 11 : 0;
-    if (want && plan[0] != want) return fail(M3PC_EINVAL, "debug_gemm_ex: variant %d does not take this problem (kernel %d would run)", v, plan[0]);
-    return 0;
-}
-
-int m3pc_debug_gemm_plan(const m3pc_debug_gemm_args* a) {
-    GemmP p;
-    int plan[4];
-    if (int rc = debug_gemm_plan(a, p, plan)) return rc;
-    if (a->picked)
-        for (int i = 0; i < 4; ++i) a->picked[i] = plan[i];
-    return 0;
-}
-
-int m3pc_debug_gemm_ex(const m3pc_debug_gemm_args* a) {
-    GemmP p;
-    int plan[4];
-    if (int rc = debug_gemm_plan(a, p, plan)) return rc;
-    hipStream_t st = (hipStream_t)a->stream;
-    if (a->dtype == DT_X3) {  // hi / lo copies of W, as m3pc_load_weights keeps them.  (A lab hook's shortcut: the buffer is a
-        // function-static that grows and is never freed, W is split again on every call, and calls from two threads would share it)
-        static bf16_t* wsplit = nullptr;
-        static size_t cap = 0;
-        const size_t nw = (size_t)a->N * a->ldw;
-        if (nw > cap) {
-            if (wsplit) HIPCHK(hipFree(wsplit));
-            wsplit = nullptr;
-            cap = 0;
-            HIPCHK(hipMalloc((void**)&wsplit, 2 * nw * sizeof(bf16_t)));
-            cap = nw;
-        }
-        launch_f32_split_bf16((const float*)a->W, wsplit, wsplit + nw, (long long)nw, st);
-        p.W = wsplit;
-    }
-    M3PC_GEMM_PICK(0, 0, 0, 0);
-    if (a->dtype == DT_X3)
-        launch_gemm_x3(p, st);
-    else
-        launch_gemm(p, a->dtype, st);
-    if (a->picked)
-        for (int i = 0; i < 4; ++i) a->picked[i] = g_gemm_picked[i];
-    return check_launch("debug_gemm_ex");
-}
-
-int m3pc_debug_gemm_group(const m3pc_debug_gemm_args* a, int n) {
-    if (!a || n < 1 || n > 4) return fail(M3PC_EINVAL, "debug_gemm_group: 1..4 problems");
-    if (a[0].picked) a[0].picked[0] = a[0].picked[1] = a[0].picked[2] = a[0].picked[3] = 0;
-    GemmP ps[4];
-    for (int i = 0; i < n; ++i) {
-        if (int rc = debug_gemm_fill(a + i, ps[i])) return rc;
-        if (a[i].dtype != DT_F32 || !a[i].ws || a[i].variant != 0 || a[i].ln_out || !gemm_f32_direct_covers(ps[i]))
-            return fail(M3PC_EINVAL, "debug_gemm_group: problem %d is not one the few-row fp32 kernel covers", i);
-    }
-    M3PC_GEMM_PICK(0, 0, 0, 0);
-    if (!launch_gemm_f32_direct_group(ps, n, (hipStream_t)a[0].stream)) return fail(M3PC_EINVAL, "debug_gemm_group: not covered");
-    if (a[0].picked)
-        for (int i = 0; i < 4; ++i) a[0].picked[i] = g_gemm_picked[i];
-    return check_launch("debug_gemm_group");
-}
-
-// Not part of the public header (tools/gemm_bench.py): clock counters of the last probed GEMM workgroup.
-// cap > 0: from now on every fused-tail launch of the handle logs the phase stamps of its workgroup 37 into a ring of `cap`
-// entries (64 int64 each: wave w at [16 w ..]); cap == 0: copy the ring to out (host, cap_prev * 64 int64), return how many
-// launches were logged through *n_logged, and stop logging
-int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged) {
-    if (!h) return fail(M3PC_EINVAL, "null handle");
-    if (cap > 0) {
-        if (h->stamp_log) hipFree(h->stamp_log);
-        CHK(dmalloc(&h->stamp_log, (size_t)cap * 64));
-        HIPCHK(hipMemset(h->stamp_log, 0, (size_t)cap * 64 * sizeof(long long)));
-        h->stamp_cap = cap;
-        h->stamp_i = 0;
-        return 0;
-    }
-    if (!h->stamp_log) return fail(M3PC_ESTATE, "stamp log not enabled");
-    HIPCHK(hipDeviceSynchronize());
-    if (out) HIPCHK(hipMemcpy(out, h->stamp_log, (size_t)h->stamp_cap * 64 * sizeof(long long), hipMemcpyDeviceToHost));
-    if (n_logged) *n_logged = h->stamp_i;
-    hipFree(h->stamp_log);
-    h->stamp_log = nullptr;
-    h->stamp_cap = 0;
-    return 0;
-}
-
-int m3pc_debug_clock(long long* out2) {
-    HIPCHK(hipDeviceSynchronize());
-    read_clock_probe(out2);
-    return 0;
-}
-
-// Not part of the public header (tests/test_gemm_kernels_gpu.py): the top-k kernels on their own.
-// the statistics kernel of m3pc_calibrate_delta on caller vectors (tests/test_certified_step_gpu.py): stats = {lower median of
-// scores_low - f32, largest deviation from it, largest |f32|, 0 ...} on the device, *delta_out as m3pc_calibrate_delta forms it
-int m3pc_debug_calibrate_stats(const float* scores_low, const float* f32, int n, float factor, float* stats, float* delta_out,
-                               void* stream) {
-    if (!scores_low || !f32 || !stats || !delta_out || n < 1 || n > 16384) return fail(M3PC_EINVAL, "bad argument");
-    launch_deviation_stats(scores_low, f32, n, stats, nullptr, 0.f, (hipStream_t)stream);
-    CHK(check_launch("debug_calibrate_stats"));
-    float s8[8];
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipMemcpy(s8, stats, sizeof(s8), hipMemcpyDeviceToHost));
-    *delta_out = cert_delta(factor, s8[1], s8[2]);
-    return 0;
-}
-int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream) {
-    launch_topk(v, n, k, idx_out, (hipStream_t)stream);
-    return check_launch("debug_topk");
-}
-
-// Not part of the public header (tests/test_lockstep_kernels_gpu.py): the three kernels of a lock-step batch's tail, each alone on
-// caller arrays.  The checks are those of the one-window entry points, per window.
-int m3pc_debug_topk_race_batch(const float* scores, const float* expo, float temperature, int n_windows, int n_total, int kmax, int kmin,
-                               int rmax, int* list, float* list_scores, void* stream) {
-    if (!scores || !list || (rmax > 0 && !expo)) return fail(M3PC_EINVAL, "null argument");
-    if (n_windows < 1 || n_windows > 65535) return fail(M3PC_EINVAL, "n_windows %d outside [1, 65535]", n_windows);
-    if (n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "top-k supports n_total <= 16384");
-    if (kmax < 1 || kmax > 1023 || kmin < 1 || kmin > kmax) return fail(M3PC_EINVAL, "bad kmin/kmax");
-    if (rmax < 0 || rmax > 64 || rmax > n_total) return fail(M3PC_EINVAL, "rmax %d outside [0, min(64, n_total)]", rmax);
-    const int kk = kmax + 1 < n_total ? kmax + 1 : n_total;
-    if (!launch_topk_race_batch(scores, expo, temperature, n_windows, n_total, n_total, kk, rmax, rmax, list, list_scores,
-                                rmax + kmax + 1, (hipStream_t)stream))
-        return fail(M3PC_ENOMEM, "the device refused the LDS for the keys of %d candidates", n_total);
-    return check_launch("debug_topk_race_batch");
-}
-int m3pc_debug_gather_listed(const float* sample_actions, const int* list, int n_windows, int n_total, int row_floats, int list_stride,
-                             int lo, int hi, float* cand, int* window_index, void* stream) {
-    if (!sample_actions || !list || !cand) return fail(M3PC_EINVAL, "null argument");
-    if (n_windows < 1 || n_total < 1 || row_floats < 1) return fail(M3PC_EINVAL, "bad sizes");
-    if (lo < 0 || hi < lo || hi > list_stride) return fail(M3PC_EINVAL, "slice [%d, %d) outside the list of %d", lo, hi, list_stride);
-    if ((long long)n_windows * (hi - lo) > 0x7fffffffLL) return fail(M3PC_EINVAL, "too many rows");
-    launch_gather_listed(sample_actions, n_windows, n_total, row_floats, list, list_stride, lo, hi - lo, cand, window_index,
-                         (hipStream_t)stream);
-    return check_launch("debug_gather_listed");
-}
-int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a) {
-    if (!a || !a->scores || !a->list || !a->list_scores || !a->list_rescored || !a->merged || !a->stats || !a->r || !a->n || !a->delta)
-        return fail(M3PC_EINVAL, "null argument");
-    if (a->race && !a->expo) return fail(M3PC_EINVAL, "race needs expo");
-    if (a->n_windows < 1 || a->n_total < 1 || a->n_total > 16384) return fail(M3PC_EINVAL, "bad sizes");
-    if (a->rmax < 0 || a->rmax > 64 || a->list_stride < a->rmax + 1 || a->f_lo < 0 || a->f_stride < 1)
-        return fail(M3PC_EINVAL, "bad list layout");
-    if (a->select && (a->eval_action || a->sample_action) && (!a->a0 || a->A < 1 || a->A > 1024))
-        return fail(M3PC_EINVAL, "eval_action / sample_action need a0");
-    for (int w = 0; w < a->n_windows; ++w) {
-        const int r = a->r[w], n = a->n[w];
-        if (n < 1 || r < 0 || r + n > 1024 || n > a->n_total || r > a->n_total || r > a->rmax || (!a->race && r != 0) ||
-            n > a->list_stride - a->rmax || a->rmax - r < a->f_lo || a->rmax + n - a->f_lo > a->f_stride)
-            return fail(M3PC_EINVAL, "window %d: r %d + n %d outside the list / [1, 1024] / n_total %d", w, r, n, a->n_total);
-        if (!(a->delta[w] >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
-    }
-    MergeSelectBatchP P;
-    memset(&P, 0, sizeof(P));
-    P.b = a->scores;
-    P.expo = a->expo;
-    P.row_stride = a->n_total;
-    P.n_total = a->n_total;
-    P.race = a->race;
-    P.select = a->select;
-    P.tau = a->temperature;
-    P.list = a->list;
-    P.list_scores = a->list_scores;
-    P.list_stride = a->list_stride;
-    P.rmax = a->rmax;
-    P.f = a->list_rescored;
-    P.f_stride = a->f_stride;
-    P.f_lo = a->f_lo;
-    P.out = a->merged;
-    P.stats = a->stats;
-    P.host_stats = a->host_stats;
-    P.seq = a->seq;
-    P.a0 = a->a0;
-    P.a0_wstride = a->a0_window_stride;
-    P.a0_stride = a->a0_stride;
-    P.A = a->A;
-    P.p = a->p;
-    P.eval_action = a->eval_action;
-    P.argmax = a->argmax;
-    P.sample_idx = a->sample_idx;
-    P.sample_action = a->sample_action;
-    launch_merge_select_batch(P, a->n_windows, a->r, a->n, a->delta, (hipStream_t)a->stream);
-    return check_launch("debug_merge_select_batch");
-}
-// the select of n_windows windows in one launch (the fp32 form of m3pc_plan_steps_certified): m3pc_select's checks, per window
-int m3pc_debug_select_batch(const float* scores, const float* a0, long long a0_window_stride, long long a0_stride, int n_windows,
-                            int n_total, int A, float temperature, const float* expo, float* p, float* eval_action, int* argmax,
-                            int* sample_idx, float* sample_action, void* stream) {
-    if (!scores || n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "bad argument");
-    if (n_windows < 1 || n_windows > 65535) return fail(M3PC_EINVAL, "n_windows %d outside [1, 65535]", n_windows);
-    if ((eval_action || sample_action) && (!a0 || A < 1 || A > 1024)) return fail(M3PC_EINVAL, "eval_action / sample_action need a0");
-    if ((sample_idx || sample_action) && !expo) return fail(M3PC_EINVAL, "the multinomial draw needs expo");
-    SelectP s;
-    memset(&s, 0, sizeof(s));
-    s.er = scores;
-    s.a0 = a0;
-    s.a0_stride = a0_stride;
-    s.n = n_total;
-    s.A = A;
-    s.temperature = temperature;
-    s.expo = expo;
-    s.p = p;
-    s.eval_action = eval_action;
-    s.argmax = argmax;
-    s.sample_idx = sample_idx;
-    s.sample_action = sample_action;
-    launch_select_batch(s, n_windows, n_total, a0_window_stride, (hipStream_t)stream);
-    return check_launch("debug_select_batch");
-}
-
-// Not part of the public header (tests/test_block_fused_gpu.py, tools/block_bench.py): the fused layer tail on its own.
-//   O (M,512) bf16; res (M,512) fp32 or rowtab (rt_mod,512); Wo (512,512), W1 (2048,512), W2 (512,2048) bf16 in torch
-//   Linear layout; stream: scratch of m3pc_debug_block_stream_bytes() bytes (packed when pack != 0);
-//   lnB_g0 / lnB_g1 optional (with out_mod / out_grp); Xout (M,512) fp32 optional; Hout (M,512) bf16 optional
-long long m3pc_debug_block_stream_bytes(void) { return (long long)block_stream_bytes(); }
-int m3pc_debug_block_fused(const void* O, int M, const float* res, const float* rowtab, int rt_mod, const void* Wo, const void* W1,
-                           const void* W2, void* stream_buf, int pack, const float* bo, const float* b1, const float* b2,
-                           const float* ln2_g, const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* lnB_g0,
-                           const float* lnB_b0, const float* lnB_g1, const float* lnB_b1, int out_mod, int out_grp, float* Xout,
-                           void* Hout, int variant, void* stream, long long* stamps) {
-    hipStream_t st = (hipStream_t)stream;
-    if (pack) launch_pack_block_stream((const bf16_t*)Wo, (const bf16_t*)W1, (const bf16_t*)W2, (bf16_t*)stream_buf, st);
-    BlockP b;
-    memset(&b, 0, sizeof(b));
-    b.O = (const bf16_t*)O;
-    b.ldo = 512;
-    b.M = M;
-    b.res = res;
-    b.ldr = 512;
-    b.rowtab = rowtab;
-    b.rt_mod = rt_mod;
-    b.wstream = (const bf16_t*)stream_buf;
-    b.bo = bo;
-    b.b1 = b1;
-    b.b2 = b2;
-    b.ln2_g = ln2_g;
-    b.ln2_b = ln2_b;
-    b.Xout = Xout;
-    b.ldx = 512;
-    b.lnA_g = lnA_g;
-    b.lnA_b = lnA_b;
-    b.lnB_g[0] = lnB_g0;
-    b.lnB_b[0] = lnB_b0;
-    b.lnB_g[1] = lnB_g1;
-    b.lnB_b[1] = lnB_b1;
-    b.out_mod = out_mod;
-    b.out_grp = out_grp;
-    b.Hout = (bf16_t*)Hout;
-    b.ldh = 512;
-    b.variant = variant & 15;
-    b.x_bf16 = (variant & 16) ? 1 : 0;  // (res and Xout are then (M, 512) bf16 rows)
-    b.stamps = stamps;
-    if (!launch_block_fused(b, st)) return fail(M3PC_EINVAL, "block_fused: arguments not covered");
-    return check_launch("debug_block_fused");
-}
-
-// the fused layer tail with the next layer's Q|K|V projection behind it: QKV (M, 1536) bf16 = LN_A(X'') Wqkv^T + bqkv
-int m3pc_debug_block_fused_qkv(const void* O, int M, const float* res, const void* Wo, const void* W1, const void* W2, const void* Wqkv,
-                               void* stream_buf, const float* bo, const float* b1, const float* b2, const float* ln2_g,
-                               const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* bqkv, float* Xout, void* QKV,
-                               void* stream, long long* stamps, int x_bf16) {
-    hipStream_t st = (hipStream_t)stream;
-    launch_pack_block_stream((const bf16_t*)Wo, (const bf16_t*)W1, (const bf16_t*)W2, (bf16_t*)stream_buf, st);
-    launch_pack_block_qkv((const bf16_t*)Wqkv, (bf16_t*)stream_buf, st);
-    BlockP b;
-    memset(&b, 0, sizeof(b));
-    b.O = (const bf16_t*)O;
-    b.ldo = 512;
-    b.M = M;
-    b.res = res;
-    b.ldr = 512;
-    b.wstream = (const bf16_t*)stream_buf;
-    b.bo = bo;
-    b.b1 = b1;
-    b.b2 = b2;
-    b.ln2_g = ln2_g;
-    b.ln2_b = ln2_b;
-    b.Xout = Xout;
-    b.ldx = 512;
-    b.lnA_g = lnA_g;
-    b.lnA_b = lnA_b;
-    b.QKVout = (bf16_t*)QKV;
-    b.ldq = 1536;
-    b.qkv_bytes = (unsigned)((size_t)M * 1536 * 2);
-    b.bqkv = bqkv;
-    b.stamps = stamps;
-    b.x_bf16 = x_bf16 ? 1 : 0;  // (res and Xout are then (M, 512) bf16 rows)
-    if (!launch_block_fused(b, st)) return fail(M3PC_EINVAL, "block_fused (qkv): arguments not covered");
-    return check_launch("debug_block_fused_qkv");
-}
-
-// the decoder form of the fused tail with the two scalar output heads inside: rows of group s = (r % out_mod) / out_grp;
-// out0 / out1 (M / 2) floats; Wh (2, 512, 512) bf16, hb1 / hw2 (2, 512), hb2 / hmean / hstd (2) floats (hmean null: no detok)
-int m3pc_debug_block_fused_heads(const void* O, int M, const float* rowtab, int rt_mod, const void* Wo, const void* W1, const void* W2,
-                                 const void* Wh, void* stream_buf, const float* bo, const float* b1, const float* b2, const float* ln2_g,
-                                 const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* lnB_g0, const float* lnB_b0,
-                                 const float* lnB_g1, const float* lnB_b1, int out_mod, int out_grp, const float* hb1, const float* hw2,
-                                 const float* hb2, const float* hmean, const float* hstd, float* out0, float* out1, void* stream,
-                                 long long* stamps) {
-    hipStream_t st = (hipStream_t)stream;
-    launch_pack_block_stream((const bf16_t*)Wo, (const bf16_t*)W1, (const bf16_t*)W2, (bf16_t*)stream_buf, st);
-    launch_pack_block_heads((const bf16_t*)Wh, (const bf16_t*)Wh + 512 * 512, (bf16_t*)stream_buf, st);
-    BlockP b;
-    memset(&b, 0, sizeof(b));
-    b.O = (const bf16_t*)O;
-    b.ldo = 512;
-    b.M = M;
-    b.rowtab = rowtab;
-    b.rt_mod = rt_mod;
-    b.wstream = (const bf16_t*)stream_buf;
-    b.bo = bo;
-    b.b1 = b1;
-    b.b2 = b2;
-    b.ln2_g = ln2_g;
-    b.ln2_b = ln2_b;
-    b.lnA_g = lnA_g;
-    b.lnA_b = lnA_b;
-    b.lnB_g[0] = lnB_g0;
-    b.lnB_b[0] = lnB_b0;
-    b.lnB_g[1] = lnB_g1;
-    b.lnB_b[1] = lnB_b1;
-    b.out_mod = out_mod;
-    b.out_grp = out_grp;
-    b.head_out[0] = out0;
-    b.head_out[1] = out1;
-    for (int s = 0; s < 2; ++s) {
-        b.hb1[s] = hb1 + 512 * s;
-        b.hw2[s] = hw2 + 512 * s;
-        b.hb2[s] = hb2 + s;
-        b.hmean[s] = hmean ? hmean + s : nullptr;
-        b.hstd[s] = hstd ? hstd + s : nullptr;
-    }
-    b.stamps = stamps;
-    if (!launch_block_fused(b, st)) return fail(M3PC_EINVAL, "block_fused (heads): arguments not covered");
-    return check_launch("debug_block_fused_heads");
-}
-
-// the fused layer tail with everything BlockP carries (include/m3pc_hip_debug.h)
-static int debug_block_fill(const m3pc_debug_block_args* a, BlockP& b, SplitReduceP& r) {
-    if (!a) return fail(M3PC_EINVAL, "debug_block: null arguments");
-    memset(&b, 0, sizeof(b));
-    memset(&r, 0, sizeof(r));
-    if (a->picked) a->picked[0] = 0;
-    if (a->M <= 0) return fail(M3PC_EINVAL, "debug_block: M = %d", a->M);
-    if (!a->O || !a->Wo || !a->W1 || !a->W2 || !a->stream_buf || !a->bo || !a->b1 || !a->b2 || !a->ln2_g || !a->ln2_b)
-        return fail(M3PC_EINVAL, "debug_block: O, the layer's weights, biases, norm2 and the stream buffer are required");
-    if (!a->res && !a->rowtab) return fail(M3PC_EINVAL, "debug_block: neither res nor rowtab");
-    if (a->rowtab && a->rt_mod < 1) return fail(M3PC_EINVAL, "debug_block: rowtab with rt_mod %d", a->rt_mod);
-    if (a->res_L < 0 || a->res_nshared < 0) return fail(M3PC_EINVAL, "debug_block: res_L / res_nshared below 0");
-    if ((a->Hout || a->head_out[0]) && !a->lnA_g) return fail(M3PC_EINVAL, "debug_block: Hout / heads without lnA");
-    if (a->lnA_g && !a->lnA_b) return fail(M3PC_EINVAL, "debug_block: lnA_g without lnA_b");
-    for (int s = 0; s < 2; ++s)
-        if ((a->lnB_g[s] != nullptr) != (a->lnB_b[s] != nullptr)) return fail(M3PC_EINVAL, "debug_block: lnB_g / lnB_b come in pairs");
-    if (a->lnB_g[0] && !a->lnB_g[1]) return fail(M3PC_EINVAL, "debug_block: lnB is two pairs (the kernel's tables hold two)");
-    if (a->out_mod < 0 || (a->out_mod > 0 && (a->out_grp < 1 || !a->lnB_g[0]))) return fail(M3PC_EINVAL, "debug_block: out_mod / out_grp / lnB");
-    if (a->QKVout && !a->Wqkv) return fail(M3PC_EINVAL, "debug_block: QKVout without Wqkv");
-    if (a->head_out[0] && (!a->Wh || !a->hb1 || !a->hw2 || !a->hb2)) return fail(M3PC_EINVAL, "debug_block: heads without their weights");
-    if (a->Wqkv && a->Wh) return fail(M3PC_EINVAL, "debug_block: Wqkv and Wh share the stream's tail");
-    if (a->qkv_bytes < 0 || a->qkv_bytes > 0xffffffffll) return fail(M3PC_EINVAL, "debug_block: qkv_bytes");
-    b.O = (const bf16_t*)a->O;
-    b.ldo = a->ldo;
-    b.M = a->M;
-    b.res = (const float*)a->res;
-    b.ldr = a->ldr;
-    b.res_L = a->res_L;
-    b.res_nshared = a->res_nshared;
-    b.rowtab = a->rowtab;
-    b.rt_mod = a->rt_mod;
-    b.res_nu = a->res_nu;
-    b.wstream = (const bf16_t*)a->stream_buf;
-    b.bo = a->bo;
-    b.b1 = a->b1;
-    b.b2 = a->b2;
-    b.ln2_g = a->ln2_g;
-    b.ln2_b = a->ln2_b;
-    b.Xout = (float*)a->Xout;
-    b.ldx = a->ldx;
-    b.x_bf16 = a->x_bf16 ? 1 : 0;
-    b.lnA_g = a->lnA_g;
-    b.lnA_b = a->lnA_b;
-    for (int s = 0; s < 2; ++s) {
-        b.lnB_g[s] = a->lnB_g[s];
-        b.lnB_b[s] = a->lnB_b[s];
-    }
-    b.out_mod = a->out_mod;
-    b.out_grp = a->out_grp;
-    b.Hout = (bf16_t*)a->Hout;
-    b.ldh = a->ldh;
-    b.QKVout = (bf16_t*)a->QKVout;
-    b.ldq = a->ldq;
-    b.qkv_bytes = (unsigned)a->qkv_bytes;
-    b.bqkv = a->bqkv;
-    for (int s = 0; s < 2; ++s) {
-        b.head_out[s] = a->head_out[s];
-        if (!a->head_out[0]) continue;
-        b.hb1[s] = a->hb1 + 512 * s;
-        b.hw2[s] = a->hw2 + 512 * s;
-        b.hb2[s] = a->hb2 + s;
-        b.hmean[s] = a->hmean ? a->hmean + s : nullptr;
-        b.hstd[s] = a->hstd ? a->hstd + s : nullptr;
-    }
-    b.split = a->split ? 1 : 0;
-    if (!block_fused_accepts(b)) return fail(M3PC_EINVAL, "debug_block: arguments not covered (block_fused_accepts)");
-    if (b.split) {
-        r.slabs = (const float*)a->Xout;
-        r.M = a->M;
-        r.Xout = a->red_Xout;
-        r.ldx = a->red_ldx;
-        r.lnA_g = a->red_lnA_g;
-        r.lnA_b = a->red_lnA_b;
-        for (int s = 0; s < 2; ++s) {
-            r.lnB_g[s] = a->red_lnB_g[s];
-            r.lnB_b[s] = a->red_lnB_b[s];
-        }
-        r.out_mod = a->red_out_mod;
-        r.out_grp = a->red_out_grp;
-        r.Hout = (bf16_t*)a->red_Hout;
-        r.ldh = a->red_ldh;
-        if (!r.Xout && !r.Hout) return fail(M3PC_EINVAL, "debug_block: the reduce has no output");
-        if (r.Xout && (((uintptr_t)r.Xout & 15) || r.ldx < 512 || (r.ldx % 4))) return fail(M3PC_EINVAL, "debug_block: red_Xout / red_ldx");
-        if (r.Hout && (((uintptr_t)r.Hout & 15) || r.ldh < 512 || (r.ldh % 8) || !r.lnA_g || !r.lnA_b)) return fail(M3PC_EINVAL, "debug_block: red_Hout / red_ldh / red_lnA");
-        if ((r.lnB_g[0] != nullptr) != (r.lnB_b[0] != nullptr) || (r.lnB_g[0] && r.out_mod > 0 && (!r.lnB_g[1] || !r.lnB_b[1])))
-            return fail(M3PC_EINVAL, "debug_block: red_lnB");
-        if (r.out_mod < 0 || (r.out_mod > 0 && (!r.lnB_g[0] || r.out_mod != 2 * r.out_grp || a->M % r.out_mod != 0)))
-            return fail(M3PC_EINVAL, "debug_block: red_out_mod / red_out_grp");
-    }
-    if (a->picked) a->picked[0] = block_fused_form(b);
-    return 0;
-}
-int m3pc_debug_block_split_n(void) { return block_split_n(); }
-int m3pc_debug_block_accepts(const m3pc_debug_block_args* a) {
-    BlockP b;
-    SplitReduceP r;
-    return debug_block_fill(a, b, r);
-}
-int m3pc_debug_block_ex(const m3pc_debug_block_args* a) {
-    BlockP b;
-    SplitReduceP r;
-    const int rc = debug_block_fill(a, b, r);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)a->stream;
-    launch_pack_block_stream((const bf16_t*)a->Wo, (const bf16_t*)a->W1, (const bf16_t*)a->W2, (bf16_t*)a->stream_buf, st);
-    if (a->Wqkv) launch_pack_block_qkv((const bf16_t*)a->Wqkv, (bf16_t*)a->stream_buf, st);
-    if (a->Wh) launch_pack_block_heads((const bf16_t*)a->Wh, (const bf16_t*)a->Wh + 512 * 512, (bf16_t*)a->stream_buf, st);
-    if (!launch_block_fused(b, st)) {
-        if (a->picked) a->picked[0] = 0;
-        return fail(M3PC_EINVAL, "debug_block: arguments not covered");
-    }
-    if (b.split) launch_block_split_reduce(r, st);
-    return check_launch("debug_block_ex");
-}
-// where the bf16 residual row of token row r lives in the compact layout (block_res_row_xb; host only, no GPU needed)
-int m3pc_debug_block_res_row(int r, int res_L, int res_nshared) {
-    if (r < 0 || res_L < 1 || res_nshared < 0 || res_nshared > res_L) return -1;
-    return block_res_row_xb(r, res_L, res_nshared);
-}
-
-// the embedding kernel (launch_embed) on caller tensors (include/m3pc_hip_debug.h)
-int m3pc_debug_embed(const m3pc_debug_embed_args* a) {
-    if (!a) return fail(M3PC_EINVAL, "debug_embed: null arguments");
-    if (a->batch < 1 || a->L < 1 || a->d % 256 != 0 || a->d < 256 || a->d > 1024 || !a->tokmap) return fail(M3PC_EINVAL, "debug_embed: batch / L / d / tokmap");
-    if (a->n_indep < 0 || a->n_indep > a->L || a->n_sh < 0 || a->n_sh > a->n_indep) return fail(M3PC_EINVAL, "debug_embed: n_indep / n_sh");
-    if (!a->X == !a->Xb) return fail(M3PC_EINVAL, "debug_embed: exactly one of X / Xb");
-    if (a->x_compact && !(a->Xb && a->x_first_only && a->n_indep > 0)) return fail(M3PC_EINVAL, "debug_embed: x_compact needs Xb, x_first_only and n_indep > 0");
-    if ((a->Hb || a->n_sh) && (!a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_embed: Hb without ln_g / ln_b");
-    if (a->n_sh > 0 && (!a->Hb || !a->Hb_sh)) return fail(M3PC_EINVAL, "debug_embed: n_sh without Hb / Hb_sh");
-    EmbedP e;
-    memset(&e, 0, sizeof(e));
-    for (int k = 0; k < 4; ++k) {
-        e.tok[k] = a->tok[k];
-        e.bstride[k] = a->bstride[k];
-        e.WT[k] = a->WT[k];
-        e.E[k] = a->E[k];
-        e.feat[k] = a->feat[k];
-    }
-    e.tokmap = (const int2*)a->tokmap;
-    e.batch = a->batch;
-    e.L = a->L;
-    e.d = a->d;
-    e.T = a->T;
-    e.X = a->X;
-    e.Xb = (bf16_t*)a->Xb;
-    e.ln_g = a->ln_g;
-    e.ln_b = a->ln_b;
-    e.Hb = (bf16_t*)a->Hb;
-    e.Hb_sh = (bf16_t*)a->Hb_sh;
-    e.n_indep = a->n_indep;
-    e.n_sh = a->n_sh;
-    e.x_first_only = a->x_first_only ? 1 : 0;
-    e.x_compact = a->x_compact ? 1 : 0;
-    launch_embed(e, (hipStream_t)a->stream);
-    return check_launch("debug_embed");
-}
-
-// kv_fused_kernel alone (tests/test_block_fused_gpu.py): n candidates of Le rows each in Z (n*Le, 512) bf16; group g holds
-// the kept[g] rows at offset off[g] of every candidate, embedded with We[g] (512, 512) bf16 + rowtab[g] (kept[g], 512);
-// stream_buf: 2 * m3pc_debug_kv_stream_bytes() bytes; KV (n*Le, 1024) bf16
-long long m3pc_debug_kv_stream_bytes(void) { return (long long)kv_stream_bytes(); }
-int m3pc_debug_attention_bf16(const void* QKV, const void* QKVs, void* O, int batch, int n_own, int n_sh, int kernel, void* stream,
-                              long long* stamps) {
-    const int d = 512, L = n_own + n_sh;
-    AttnP a;
-    memset(&a, 0, sizeof(a));
-    const char* q = (const char*)QKV;
-    const char* qs = (const char*)QKVs;
-    a.Q = q;
-    a.q_bstride = (long long)n_own * 3 * d;
-    a.ldq = 3 * d;
-    a.Lq = n_own;
-    a.K1 = q + (size_t)d * 2;
-    a.V1 = q + (size_t)2 * d * 2;
-    a.kv1_bstride = (long long)n_own * 3 * d;
-    a.ldkv1 = 3 * d;
-    a.L1 = n_own;
-    if (n_sh > 0) {  // (run_block: own rows first in the slots, shared rows first in the output)
-        a.orow1 = n_sh;
-        a.Q2 = qs;
-        a.ldq2 = 3 * d;
-        a.Lq2 = n_sh;
-        a.orow2 = 0;
-        a.K2 = qs + (size_t)d * 2;
-        a.V2 = qs + (size_t)2 * d * 2;
-        a.ldkv2 = 3 * d;
-        a.L2 = n_sh;
-    }
-    a.O = O;
-    a.o_bstride = (long long)L * d;
-    a.ldo = d;
-    a.batch = batch;
-    a.n_head = 4;
-    a.hd = 128;
-    a.scale = 1.0f / sqrtf(128.0f);
-    a.stamps = stamps;
-    a.no_pipe = kernel;  // (2, 3: timing variants of the pipelined kernel that compute nothing / load nothing)
-    launch_attention(a, DT_BF16, (hipStream_t)stream);
-    return check_launch("debug_attention_bf16");
-}
-
-int m3pc_debug_attention_dec_bf16(const void* Qtab, const void* QKVm, const void* KV, void* O, float* pre, int n, int nq, int Lm, int kernel,
-                                  void* stream) {
-    return m3pc_debug_attention_dec_le_bf16(Qtab, QKVm, KV, O, pre, n, nq, Lm, 49, kernel, stream);
-}
-
-int m3pc_debug_attention_dec_le_bf16(const void* Qtab, const void* QKVm, const void* KV, void* O, float* pre, int n, int nq, int Lm, int Le, int kernel,
-                                     void* stream) {
-    const int d = 512, nh = 4, hd = 128;
-    hipStream_t st = (hipStream_t)stream;
-    float* pre_m = pre;
-    float* pre_l = pre + nh * nq;
-    float* pre_O = pre + 2 * nh * nq;
-    AttnP at;
-    memset(&at, 0, sizeof(at));
-    at.Q = Qtab;
-    at.ldq = 3 * d;
-    at.Lq = nq;
-    at.K2 = (const char*)QKVm + (size_t)d * 2;
-    at.V2 = (const char*)QKVm + (size_t)2 * d * 2;
-    at.ldkv2 = 3 * d;
-    at.L2 = Lm;
-    at.n_head = nh;
-    at.hd = hd;
-    at.scale = 1.0f / sqrtf((float)hd);
-    launch_attention_prestats(at, pre_m, pre_l, pre_O, st);
-    at.K2 = at.V2 = nullptr;
-    at.L2 = 0;
-    at.q_bstride = 0;
-    at.K1 = KV;
-    at.V1 = (const char*)KV + (size_t)d * 2;
-    at.kv1_bstride = (long long)Le * 2 * d;
-    at.ldkv1 = 2 * d;
-    at.L1 = Le;
-    at.O = O;
-    at.o_bstride = (long long)nq * d;
-    at.ldo = d;
-    at.batch = n;
-    at.pre_m = pre_m;
-    at.pre_l = pre_l;
-    at.pre_O = pre_O;
-    at.no_pipe = kernel;
-    launch_attention(at, DT_BF16, st);
-    return check_launch("debug_attention_dec_bf16");
-}
-
-int m3pc_debug_attention_mix_bf16(const void* Qown, const void* Qsh, const void* KV, const void* QKVm, void* O, int n, int Lq, int Lq2, int kernel,
-                                  void* stream) {
-    const int d = 512, Le = 49, Lm = 79;
-    AttnP at;
-    memset(&at, 0, sizeof(at));
-    at.Q = Qown;
-    at.q_bstride = (long long)Lq * d;
-    at.ldq = d;
-    at.Lq = Lq;
-    at.orow1 = 0;
-    at.Q2 = Qsh;
-    at.ldq2 = 3 * d;
-    at.Lq2 = Lq2;
-    at.orow2 = Lq;
-    at.K1 = KV;
-    at.V1 = (const char*)KV + (size_t)d * 2;
-    at.kv1_bstride = (long long)Le * 2 * d;
-    at.ldkv1 = 2 * d;
-    at.L1 = Le;
-    at.K2 = (const char*)QKVm + (size_t)d * 2;
-    at.V2 = (const char*)QKVm + (size_t)2 * d * 2;
-    at.ldkv2 = 3 * d;
-    at.L2 = Lm;
-    at.O = O;
-    at.o_bstride = (long long)(Lq + Lq2) * d;
-    at.ldo = d;
-    at.batch = n;
-    at.n_head = 4;
-    at.hd = 128;
-    at.scale = 1.0f / sqrtf(128.0f);
-    at.no_pipe = kernel;
-    launch_attention(at, DT_BF16, (hipStream_t)stream);
-    return check_launch("debug_attention_mix_bf16");
-}
-
-// any attention the library launches, on caller tensors (tests/test_attention_gpu.py): fills an AttnP and goes through
-// launch_attention's dispatch; shapes the kernels do not cover are refused before anything is launched
-int m3pc_debug_attention(int dtype, const void* Q, long long q_bstride, int ldq, int Lq, int orow1, const void* Q2, int ldq2, int Lq2,
-                         int orow2, const void* K1, const void* V1, long long kv1_bstride, int ldkv1, int L1, const void* K2,
-                         const void* V2, int ldkv2, int L2, const void* Kp, const void* Vp, int ldp, int Lp, float* pre, void* O,
-                         long long o_bstride, int ldo, int batch, int n_head, int hd, float scale, int kernel, int* picked,
-                         void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (picked) picked[0] = picked[1] = 0;
-    if (dtype != DT_F32 && dtype != DT_BF16) return fail(M3PC_EINVAL, "debug_attention: dtype %d", dtype);
-    if (hd != 32 && hd != 64 && hd != 128) return fail(M3PC_EINVAL, "debug_attention: head dim %d", hd);
-    if (!Q || !K1 || !V1 || !O || batch < 1 || n_head < 1 || Lq < 1 || L1 < 1 || L2 < 0 || Lp < 0 || L1 + L2 > 256 || Lp > 256)
-        return fail(M3PC_EINVAL, "debug_attention: shape");
-    if (kernel != 0 && kernel != 1) return fail(M3PC_EINVAL, "debug_attention: kernel %d", kernel);
-    const int w = n_head * hd, el = dtype == DT_BF16 ? 2 : 4, al = 16 / el;  // (16-byte row fragments)
-    if (q_bstride < 0 || kv1_bstride < 0 || o_bstride < 0 || orow1 < 0 || (Q2 && orow2 < 0)) return fail(M3PC_EINVAL, "debug_attention: negative stride / row");
-    if (ldq < w || ldkv1 < w || ldo < w || (K2 && ldkv2 < w) || (Q2 && ldq2 < w) || (Lp && ldp < w))
-        return fail(M3PC_EINVAL, "debug_attention: leading dimension below n_head * hd");
-    if ((ldq | ldkv1 | ldo | (K2 ? ldkv2 : 0) | (Q2 ? ldq2 : 0) | (Lp ? ldp : 0)) % al || (q_bstride | kv1_bstride | o_bstride) % al)
-        return fail(M3PC_EINVAL, "debug_attention: strides must be multiples of %d elements", al);
-    if (((uintptr_t)Q | (uintptr_t)K1 | (uintptr_t)V1 | (uintptr_t)O | (uintptr_t)Q2 | (uintptr_t)K2 | (uintptr_t)V2 | (uintptr_t)Kp |
-         (uintptr_t)Vp | (uintptr_t)pre) & 15)
-        return fail(M3PC_EINVAL, "debug_attention: pointers must be 16-byte aligned");
-    if ((K2 == nullptr) != (V2 == nullptr) || (L2 > 0) != (K2 != nullptr) || (Lp > 0) != (Kp && Vp && pre) || (Q2 != nullptr) != (Lq2 > 0))
-        return fail(M3PC_EINVAL, "debug_attention: optional segments need their pointers and a length");
-    // the fp32 kernels know one query segment, no pre-reduced block and no output row offset
-    if (dtype == DT_F32 && (Q2 || Lp || orow1)) return fail(M3PC_EINVAL, "debug_attention: Q2 / pre block / orow1 need bf16 rows");
-    // the pre-reduced block is per query, shared by the batch, and indexed by the first segment's query slots
-    if (Lp && (q_bstride != 0 || Q2)) return fail(M3PC_EINVAL, "debug_attention: a pre block needs batch-shared queries and no Q2");
-    AttnP a;
-    memset(&a, 0, sizeof(a));
-    a.Q = Q;
-    a.q_bstride = q_bstride;
-    a.ldq = ldq;
-    a.Lq = Lq;
-    a.orow1 = orow1;
-    a.Q2 = Q2;
-    a.ldq2 = ldq2;
-    a.Lq2 = Q2 ? Lq2 : 0;
-    a.orow2 = orow2;
-    a.n_head = n_head;
-    a.hd = hd;
-    a.scale = scale;
-    float* pre_m = pre;
-    float* pre_l = pre ? pre + (size_t)n_head * Lq : nullptr;
-    float* pre_O = pre ? pre + (size_t)2 * n_head * Lq : nullptr;
-    if (Lp) {  // (pre: n_head * Lq * (2 + hd) floats; pre_O 16-byte aligned as the pipelined kernels read it)
-        if ((2 * n_head * Lq) % 4) return fail(M3PC_EINVAL, "debug_attention: 2 * n_head * Lq must be a multiple of 4");
-        a.K2 = Kp;
-        a.V2 = Vp;
-        a.ldkv2 = ldp;
-        a.L2 = Lp;
-        launch_attention_prestats(a, pre_m, pre_l, pre_O, st);
-        if (picked) picked[1] = 50;
-        a.pre_m = pre_m;
-        a.pre_l = pre_l;
-        a.pre_O = pre_O;
-    }
-    a.K1 = K1;
-    a.V1 = V1;
-    a.kv1_bstride = kv1_bstride;
-    a.ldkv1 = ldkv1;
-    a.L1 = L1;
-    a.K2 = K2;
-    a.V2 = V2;
-    a.ldkv2 = ldkv2;
-    a.L2 = L2;
-    a.O = O;
-    a.o_bstride = o_bstride;
-    a.ldo = ldo;
-    a.batch = batch;
-    a.no_pipe = kernel;
-    g_attn_picked = 0;
-    launch_attention(a, dtype, st);
-    if (picked) picked[0] = g_attn_picked;
-    return check_launch("debug_attention");
-}
-
-int m3pc_debug_kv_fused(const void* Z, int n, int Le, int kept0, int off0, int kept1, int off1, const void* We0, const void* We1,
-                        const void* Wkv, void* stream_buf, const float* rowtab0, const float* rowtab1, const float* ln_g,
-                        const float* ln_b, const float* bkv, void* KV, void* stream, long long* stamps) {
-    hipStream_t st = (hipStream_t)stream;
-    bf16_t* s0 = (bf16_t*)stream_buf;
-    bf16_t* s1 = (bf16_t*)((char*)stream_buf + kv_stream_bytes());
-    launch_pack_kv_stream((const bf16_t*)We0, (const bf16_t*)Wkv, s0, st);
-    if (kept1) launch_pack_kv_stream((const bf16_t*)We1, (const bf16_t*)Wkv, s1, st);
-    KvFusedP p;
-    memset(&p, 0, sizeof(p));
-    p.Z = (const bf16_t*)Z;
-    p.ldz = 512;
-    p.M[0] = n * kept0;
-    p.map[0] = RowMap{kept0, Le, off0};
-    p.rowtab[0] = rowtab0;
-    p.rt_mod[0] = kept0;
-    p.wstream[0] = s0;
-    p.M[1] = n * kept1;
-    p.map[1] = RowMap{kept1 ? kept1 : 1, Le, off1};
-    p.rowtab[1] = rowtab1;
-    p.rt_mod[1] = kept1 ? kept1 : 1;
-    p.wstream[1] = s1;
-    p.ln_g = ln_g;
-    p.ln_b = ln_b;
-    p.bkv = bkv;
-    p.KV = (bf16_t*)KV;
-    p.ldkv = 1024;
-    p.kv_bytes = (unsigned)((size_t)n * Le * 1024 * 2);
-    p.stamps = stamps;
-    if (!launch_kv_fused(p, st)) return fail(M3PC_EINVAL, "kv_fused: arguments not covered");
-    return check_launch("debug_kv_fused");
-}
-
-int m3pc_debug_kv_fused_ex(const m3pc_debug_kv_args* a) {
-    if (!a) return fail(M3PC_EINVAL, "debug_kv: null arguments");
-    if (!a->Z || !a->Wkv || !a->stream_buf || !a->ln_g || !a->ln_b || !a->bkv || !a->KV) return fail(M3PC_EINVAL, "debug_kv: a required pointer is null");
-    if (a->kv_bytes <= 0 || a->kv_bytes > 0xffffffffll) return fail(M3PC_EINVAL, "debug_kv: kv_bytes");
-    hipStream_t st = (hipStream_t)a->stream;
-    KvFusedP p;
-    memset(&p, 0, sizeof(p));
-    p.Z = (const bf16_t*)a->Z;
-    p.ldz = a->ldz;
-    for (int g = 0; g < 2; ++g) {
-        p.M[g] = a->M[g];
-        if (a->map[g][0] < 0 || a->map[g][2] < 0 || (a->map[g][0] > 0 && a->map[g][1] < a->map[g][0])) return fail(M3PC_EINVAL, "debug_kv: row map of group %d", g);
-        p.map[g] = RowMap{a->map[g][0], a->map[g][1], a->map[g][2]};
-        p.rowtab[g] = a->rowtab[g];
-        p.rt_mod[g] = a->rt_mod[g];
-        p.wstream[g] = (const bf16_t*)((char*)a->stream_buf + g * kv_stream_bytes());
-        if (a->M[g] > 0 && !a->We[g]) return fail(M3PC_EINVAL, "debug_kv: group %d without its embedding weights", g);
-    }
-    p.ln_g = a->ln_g;
-    p.ln_b = a->ln_b;
-    p.bkv = a->bkv;
-    p.KV = (bf16_t*)a->KV;
-    p.ldkv = a->ldkv;
-    p.kv_bytes = (unsigned)a->kv_bytes;
-    for (int g = 0; g < 2; ++g)
-        if (a->M[g] > 0) launch_pack_kv_stream((const bf16_t*)a->We[g], (const bf16_t*)a->Wkv, (bf16_t*)p.wstream[g], st);
-    if (!launch_kv_fused(p, st)) return fail(M3PC_EINVAL, "kv_fused: arguments not covered");
-    return check_launch("debug_kv_fused_ex");
-}
-
-// which XCD (and CU) every workgroup of a launch on `stream` lands on: out[2 i] = XCC_ID, out[2 i + 1] = HW_ID register
-// (tools/xcd_probe.py: maps the bits of a hipExtStreamCreateWithCUMask mask to XCDs)
-__global__ void xcc_probe_kernel(int* out) {
-    if (threadIdx.x == 0) {
-        out[2 * blockIdx.x] = (int)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));   // HW_REG_XCC_ID[3:0]
-        out[2 * blockIdx.x + 1] = (int)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)); // HW_REG_HW_ID
-    }
-    // (long enough that the workgroups of the launch spread over everything the stream may use)
-    const long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (int i = 0; i < 1024; ++i) {
-        if (__builtin_amdgcn_s_memrealtime() - t0 >= 300) break;
-        __builtin_amdgcn_s_sleep(16);
-    }
-}
-int m3pc_debug_xcc_probe(int* out, int n_blocks, void* stream) {
-    hipLaunchKernelGGL(xcc_probe_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, out);
-    return check_launch("xcc_probe");
-}
-
-int m3pc_debug_clock_big(long long* out4) {
-    HIPCHK(hipDeviceSynchronize());
-    read_big_probe(out4);
-    return 0;
-}
-
-#endif  // M3PC_LAB
 
 int m3pc_profile_enable(m3pc_handle* h, int enable) {
     if (!h) return fail(M3PC_EINVAL, "null handle");

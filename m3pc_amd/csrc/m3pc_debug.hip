@@ -1,0 +1,919 @@
+// libm3pc_hip_lab.so only (m3pc_amd/build.py: LAB_SOURCES): the kernel-level test / bench hooks declared in
+// include/m3pc_hip_debug.h.  The product build does not compile this file.
+#include "m3pc_internal.h"
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+// streams the handle created for its pipelined certified steps (0 while the caller's pair of m3pc_set_step_streams serves them)
+int m3pc_debug_step_streams_created(m3pc_handle* h) { return h ? h->step_streams_created : -1; }
+// Lab build only (include/m3pc_hip_debug.h): lets tools/gemm_bench.py time the GEMM kernel on the plan step's shapes.
+int m3pc_debug_gemm(int dtype, const void* A, const void* Wt, const float* bias, const float* res, void* C, int M, int N,
+                    int K, int gelu, int f32out, int variant, void* stream) {
+    static const int ldpad = M3PC_ENV("M3PC_DEBUG_LDPAD") ? atoi(M3PC_ENV("M3PC_DEBUG_LDPAD")) : 0;  // operand row padding (elements)
+    GemmP p = gemm_basic(A, K + ldpad, Wt, K + ldpad, M, N, K, bias);
+    p.a_padded = 0;  // (a caller's tensor: nothing is known about the memory behind it)
+    p.gelu = gelu;
+    p.res = res;
+    p.ldr = N;
+    p.variant = variant;
+    if (dtype == DT_BF16 && !f32out)
+        p.Cb = (bf16_t*)C;
+    else
+        p.Cf = (float*)C;
+    p.ldc = N;
+    if (dtype != DT_BF16 && variant != 1) {  // split-K workspace as the handle provides it (variant 1: none)
+        static float* ws = nullptr;
+        if (!ws) HIPCHK(hipMalloc((void**)&ws, 64 << 20));
+        p.ws = ws;
+        p.ws_bytes = 64 << 20;
+    }
+    if (dtype == DT_X3) {  // A fp32, Wt fp32: split into hi / lo bf16 copies here, as m3pc_load_weights splits the weights
+        static bf16_t* wsplit = nullptr;
+        static size_t cap = 0;
+        const size_t n = (size_t)N * (K + ldpad);
+        if (n > cap) {
+            if (wsplit) HIPCHK(hipFree(wsplit));
+            wsplit = nullptr;
+            cap = 0;
+            HIPCHK(hipMalloc((void**)&wsplit, 2 * n * sizeof(bf16_t)));
+            cap = n;
+        }
+        launch_f32_split_bf16((const float*)Wt, wsplit, wsplit + n, (long long)n, (hipStream_t)stream);
+        p.W = wsplit;
+        p.w_lo_off = (long long)n;
+        if (launch_gemm_x3(p, (hipStream_t)stream) < 0) return fail(M3PC_EINVAL, "debug_gemm: shape not covered by the x3 kernel");
+        return check_launch("debug_gemm");
+    }
+    launch_gemm(p, dtype, (hipStream_t)stream);
+    return check_launch("debug_gemm");
+}
+
+// Every GEMM the library launches, on caller tensors, with everything a GemmP can carry (tests/test_gemm_edges_gpu.py).  The
+// checks below are the shape rules of the register-staged kernel every problem can fall back to; what the dispatch would launch is
+// learnt from a dry walk of the launchers (g_gemm_dry, csrc/kernels.h), so nothing reaches the GPU before the call is known to be
+// covered.  Fills `p` (and, for dtype 2, nothing yet of W's split) or returns the error.
+static int debug_gemm_fill(const m3pc_debug_gemm_args* a, GemmP& p) {
+    if (!a) return fail(M3PC_EINVAL, "debug_gemm_ex: null argument");
+    const int dt = a->dtype;
+    if (dt != DT_F32 && dt != DT_BF16 && dt != DT_X3) return fail(M3PC_EINVAL, "debug_gemm_ex: dtype %d", dt);
+    if (!a->A || !a->W || !a->C) return fail(M3PC_EINVAL, "debug_gemm_ex: null operand");
+    if (a->M < 1 || a->M > (1 << 20) || a->N < 32 || a->N > (1 << 16) || a->K < 1 || a->K > (1 << 16)) return fail(M3PC_EINVAL, "debug_gemm_ex: M / N / K out of range");
+    const int es = dt == DT_BF16 ? 2 : 4;  // bytes per element of A (x3: fp32 activations; its W copies are bf16)
+    if (a->N % 32) return fail(M3PC_EINVAL, "debug_gemm_ex: N %d is not a multiple of 32 (columns would be dropped)", a->N);
+    if (((long long)a->K * es) % 128) return fail(M3PC_EINVAL, "debug_gemm_ex: K %d is not a whole number of 128-byte k-tiles (k terms would be dropped)", a->K);
+    if (dt == DT_F32 && !a->f32out) return fail(M3PC_EINVAL, "debug_gemm_ex: fp32 operands have fp32 output only");
+    const int f32out = dt == DT_F32 || a->f32out;
+    const int os = f32out ? 4 : 2;
+    const uintptr_t ptrs = (uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->C | (uintptr_t)a->bias | (uintptr_t)a->rowtab | (uintptr_t)a->res |
+                           (uintptr_t)a->ws | (uintptr_t)a->ln_g | (uintptr_t)a->ln_b | (uintptr_t)a->ln_out | (uintptr_t)a->a_ln_g |
+                           (uintptr_t)a->a_ln_b;
+    if (ptrs & 15) return fail(M3PC_EINVAL, "debug_gemm_ex: pointers must be 16-byte aligned");
+    if (a->lda < a->K || a->ldw < a->K || a->ldc < a->N || (a->res && a->ldr < a->N) || (a->rowtab && a->rt_ld < a->N))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: a leading dimension is below its row length");
+    // (x3: W's bf16 copies keep ldw, so their rows need ldw % 8 as well)
+    if (((long long)a->lda * es) % 16 || ((long long)a->ldw * (dt == DT_F32 ? 4 : 2)) % 16 || (dt == DT_X3 && a->ldw % 4) || ((long long)a->ldc * os) % 16 ||
+        (a->res && a->ldr % 4) || (a->rowtab && a->rt_ld % 4))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: rows of a leading dimension leave 16-byte alignment");
+    if (a->rowtab && a->rt_mod < 1) return fail(M3PC_EINVAL, "debug_gemm_ex: rowtab with rt_mod %d", a->rt_mod);
+    for (const int* m : {a->amap, a->cmap})
+        if (m[0] < 0 || m[2] < 0 || (m[0] >= 1 && m[1] < m[0])) return fail(M3PC_EINVAL, "debug_gemm_ex: row map {%d, %d, %d}", m[0], m[1], m[2]);
+    if (a->ws && a->ws_bytes < 0) return fail(M3PC_EINVAL, "debug_gemm_ex: negative ws_bytes");
+    if (a->ln_out && (!f32out || !a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_gemm_ex: ln_out needs fp32 C, ln_g and ln_b");
+    if ((a->a_ln_g != nullptr) != (a->a_ln_b != nullptr)) return fail(M3PC_EINVAL, "debug_gemm_ex: a_ln_g and a_ln_b go together");
+    const int v = a->variant;
+    if (!(v == 0 || (dt == DT_BF16 && (v == 2 || v == 26 || v == 37 || v == 43 || v == 44)) || (dt == DT_F32 && v == 2)))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: variant %d of dtype %d is not one this hook drives", v, dt);
+    // (a_padded vouches for 127 rows behind A: a ragged 256-row tile of gemm_line_kernel<256>'s persistent form may need up to 255)
+    if (v == 44 && a->a_padded && a->M % 256 && 256 - a->M % 256 > 127)
+        return fail(M3PC_EINVAL, "debug_gemm_ex: variant 44 with a_padded would read %d rows behind A", 256 - a->M % 256);
+    p = gemm_basic(a->A, a->lda, a->W, a->ldw, a->M, a->N, a->K, a->bias);
+    p.amap = RowMap{a->amap[0], a->amap[1], a->amap[2]};
+    p.cmap = RowMap{a->cmap[0], a->cmap[1], a->cmap[2]};
+    p.rowtab = a->rowtab;
+    if (a->rowtab) {
+        p.rt_mod = a->rt_mod;
+        p.rt_ld = a->rt_ld;
+    }
+    p.gelu = a->gelu ? 1 : 0;
+    p.res = a->res;
+    p.ldr = a->ldr;
+    if (f32out)
+        p.Cf = (float*)a->C;
+    else
+        p.Cb = (bf16_t*)a->C;
+    p.ldc = a->ldc;
+    p.ws = a->ws;
+    p.ws_bytes = a->ws ? a->ws_bytes : 0;
+    p.a_padded = a->a_padded ? 1 : 0;
+    p.ln_g = a->ln_out ? a->ln_g : nullptr;
+    p.ln_b = a->ln_out ? a->ln_b : nullptr;
+    p.ln_out = a->ln_out;
+    p.a_ln_g = a->a_ln_g;
+    p.a_ln_b = a->a_ln_b;
+    p.variant = v;
+    if (a->a_ln_g && (dt != DT_F32 || !a->ws || v == 2 || !gemm_f32_direct_covers(p)))
+        return fail(M3PC_EINVAL, "debug_gemm_ex: a_ln_* on a problem the few-row fp32 kernel does not take (the fold would be dropped)");
+    return 0;
+}
+
+// the checks and the dry walk: fills p (x3: W still the caller's fp32 tensor) and plan[4] = what the dispatch would launch
+static int debug_gemm_plan(const m3pc_debug_gemm_args* a, GemmP& p, int* plan) {
+    if (a && a->picked) a->picked[0] = a->picked[1] = a->picked[2] = a->picked[3] = 0;
+    if (int rc = debug_gemm_fill(a, p)) return rc;
+    const int dt = a->dtype;
+    if (dt == DT_X3) p.w_lo_off = (long long)a->N * a->ldw;  // (the hi / lo copies keep W's layout)
+    M3PC_GEMM_PICK(0, 0, 0, 0);
+    g_gemm_dry = 1;
+    const int dry = dt == DT_X3 ? launch_gemm_x3(p, nullptr) : launch_gemm(p, dt, nullptr);
+    g_gemm_dry = 0;
+    for (int i = 0; i < 4; ++i) plan[i] = g_gemm_picked[i];
+    if (dry < 0 || plan[0] == 0) return fail(M3PC_EINVAL, "debug_gemm_ex: no kernel of the dispatch covers this problem (epilogue flags / shape)");
+    if (a->N % 64 && plan[0] != 5)  // (only the few-row fp32 kernel has 32-column tiles)
+        return fail(M3PC_EINVAL, "debug_gemm_ex: N %d is not a multiple of 64 (kernel %d would drop columns)", a->N, plan[0]);
+    const int v = a->variant;
+    const int want = dt != DT_BF16 ? 0 : v == 2 ? 8 : v == 26 ? 7 : v == 37 ? 9 : v == 43 ? 10 : v == 44 ? 11 : 0;
+    if (want && plan[0] != want) return fail(M3PC_EINVAL, "debug_gemm_ex: variant %d does not take this problem (kernel %d would run)", v, plan[0]);
+    return 0;
+}
+
+int m3pc_debug_gemm_plan(const m3pc_debug_gemm_args* a) {
+    GemmP p;
+    int plan[4];
+    if (int rc = debug_gemm_plan(a, p, plan)) return rc;
+    if (a->picked)
+        for (int i = 0; i < 4; ++i) a->picked[i] = plan[i];
+    return 0;
+}
+
+int m3pc_debug_gemm_ex(const m3pc_debug_gemm_args* a) {
+    GemmP p;
+    int plan[4];
+    if (int rc = debug_gemm_plan(a, p, plan)) return rc;
+    hipStream_t st = (hipStream_t)a->stream;
+    if (a->dtype == DT_X3) {  // hi / lo copies of W, as m3pc_load_weights keeps them.  (A lab hook's shortcut: the buffer is a
+        // function-static that grows and is never freed, W is split again on every call, and calls from two threads would share it)
+        static bf16_t* wsplit = nullptr;
+        static size_t cap = 0;
+        const size_t nw = (size_t)a->N * a->ldw;
+        if (nw > cap) {
+            if (wsplit) HIPCHK(hipFree(wsplit));
+            wsplit = nullptr;
+            cap = 0;
+            HIPCHK(hipMalloc((void**)&wsplit, 2 * nw * sizeof(bf16_t)));
+            cap = nw;
+        }
+        launch_f32_split_bf16((const float*)a->W, wsplit, wsplit + nw, (long long)nw, st);
+        p.W = wsplit;
+    }
+    M3PC_GEMM_PICK(0, 0, 0, 0);
+    if (a->dtype == DT_X3)
+        launch_gemm_x3(p, st);
+    else
+        launch_gemm(p, a->dtype, st);
+    if (a->picked)
+        for (int i = 0; i < 4; ++i) a->picked[i] = g_gemm_picked[i];
+    return check_launch("debug_gemm_ex");
+}
+
+int m3pc_debug_gemm_group(const m3pc_debug_gemm_args* a, int n) {
+    if (!a || n < 1 || n > 4) return fail(M3PC_EINVAL, "debug_gemm_group: 1..4 problems");
+    if (a[0].picked) a[0].picked[0] = a[0].picked[1] = a[0].picked[2] = a[0].picked[3] = 0;
+    GemmP ps[4];
+    for (int i = 0; i < n; ++i) {
+        if (int rc = debug_gemm_fill(a + i, ps[i])) return rc;
+        if (a[i].dtype != DT_F32 || !a[i].ws || a[i].variant != 0 || a[i].ln_out || !gemm_f32_direct_covers(ps[i]))
+            return fail(M3PC_EINVAL, "debug_gemm_group: problem %d is not one the few-row fp32 kernel covers", i);
+    }
+    M3PC_GEMM_PICK(0, 0, 0, 0);
+    if (!launch_gemm_f32_direct_group(ps, n, (hipStream_t)a[0].stream)) return fail(M3PC_EINVAL, "debug_gemm_group: not covered");
+    if (a[0].picked)
+        for (int i = 0; i < 4; ++i) a[0].picked[i] = g_gemm_picked[i];
+    return check_launch("debug_gemm_group");
+}
+
+// Not part of the public header (tools/gemm_bench.py): clock counters of the last probed GEMM workgroup.
+// cap > 0: from now on every fused-tail launch of the handle logs the phase stamps of its workgroup 37 into a ring of `cap`
+// entries (64 int64 each: wave w at [16 w ..]); cap == 0: copy the ring to out (host, cap_prev * 64 int64), return how many
+// launches were logged through *n_logged, and stop logging
+int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged) {
+    if (!h) return fail(M3PC_EINVAL, "null handle");
+    if (cap > 0) {
+        if (h->stamp_log) hipFree(h->stamp_log);
+        CHK(dmalloc(&h->stamp_log, (size_t)cap * 64));
+        HIPCHK(hipMemset(h->stamp_log, 0, (size_t)cap * 64 * sizeof(long long)));
+        h->stamp_cap = cap;
+        h->stamp_i = 0;
+        return 0;
+    }
+    if (!h->stamp_log) return fail(M3PC_ESTATE, "stamp log not enabled");
+    HIPCHK(hipDeviceSynchronize());
+    if (out) HIPCHK(hipMemcpy(out, h->stamp_log, (size_t)h->stamp_cap * 64 * sizeof(long long), hipMemcpyDeviceToHost));
+    if (n_logged) *n_logged = h->stamp_i;
+    hipFree(h->stamp_log);
+    h->stamp_log = nullptr;
+    h->stamp_cap = 0;
+    return 0;
+}
+
+int m3pc_debug_clock(long long* out2) {
+    HIPCHK(hipDeviceSynchronize());
+    read_clock_probe(out2);
+    return 0;
+}
+
+// Not part of the public header (tests/test_gemm_kernels_gpu.py): the top-k kernels on their own.
+// the statistics kernel of m3pc_calibrate_delta on caller vectors (tests/test_certified_step_gpu.py): stats = {lower median of
+// scores_low - f32, largest deviation from it, largest |f32|, 0 ...} on the device, *delta_out as m3pc_calibrate_delta forms it
+int m3pc_debug_calibrate_stats(const float* scores_low, const float* f32, int n, float factor, float* stats, float* delta_out,
+                               void* stream) {
+    if (!scores_low || !f32 || !stats || !delta_out || n < 1 || n > 16384) return fail(M3PC_EINVAL, "bad argument");
+    launch_deviation_stats(scores_low, f32, n, stats, nullptr, 0.f, (hipStream_t)stream);
+    CHK(check_launch("debug_calibrate_stats"));
+    float s8[8];
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(s8, stats, sizeof(s8), hipMemcpyDeviceToHost));
+    *delta_out = cert_delta(factor, s8[1], s8[2]);
+    return 0;
+}
+int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream) {
+    launch_topk(v, n, k, idx_out, (hipStream_t)stream);
+    return check_launch("debug_topk");
+}
+
+// Not part of the public header (tests/test_lockstep_kernels_gpu.py): the three kernels of a lock-step batch's tail, each alone on
+// caller arrays.  The checks are those of the one-window entry points, per window.
+int m3pc_debug_topk_race_batch(const float* scores, const float* expo, float temperature, int n_windows, int n_total, int kmax, int kmin,
+                               int rmax, int* list, float* list_scores, void* stream) {
+    if (!scores || !list || (rmax > 0 && !expo)) return fail(M3PC_EINVAL, "null argument");
+    if (n_windows < 1 || n_windows > 65535) return fail(M3PC_EINVAL, "n_windows %d outside [1, 65535]", n_windows);
+    if (n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "top-k supports n_total <= 16384");
+    if (kmax < 1 || kmax > 1023 || kmin < 1 || kmin > kmax) return fail(M3PC_EINVAL, "bad kmin/kmax");
+    if (rmax < 0 || rmax > 64 || rmax > n_total) return fail(M3PC_EINVAL, "rmax %d outside [0, min(64, n_total)]", rmax);
+    const int kk = kmax + 1 < n_total ? kmax + 1 : n_total;
+    if (!launch_topk_race_batch(scores, expo, temperature, n_windows, n_total, n_total, kk, rmax, rmax, list, list_scores,
+                                rmax + kmax + 1, (hipStream_t)stream))
+        return fail(M3PC_ENOMEM, "the device refused the LDS for the keys of %d candidates", n_total);
+    return check_launch("debug_topk_race_batch");
+}
+int m3pc_debug_gather_listed(const float* sample_actions, const int* list, int n_windows, int n_total, int row_floats, int list_stride,
+                             int lo, int hi, float* cand, int* window_index, void* stream) {
+    if (!sample_actions || !list || !cand) return fail(M3PC_EINVAL, "null argument");
+    if (n_windows < 1 || n_total < 1 || row_floats < 1) return fail(M3PC_EINVAL, "bad sizes");
+    if (lo < 0 || hi < lo || hi > list_stride) return fail(M3PC_EINVAL, "slice [%d, %d) outside the list of %d", lo, hi, list_stride);
+    if ((long long)n_windows * (hi - lo) > 0x7fffffffLL) return fail(M3PC_EINVAL, "too many rows");
+    launch_gather_listed(sample_actions, n_windows, n_total, row_floats, list, list_stride, lo, hi - lo, cand, window_index,
+                         (hipStream_t)stream);
+    return check_launch("debug_gather_listed");
+}
+int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a) {
+    if (!a || !a->scores || !a->list || !a->list_scores || !a->list_rescored || !a->merged || !a->stats || !a->r || !a->n || !a->delta)
+        return fail(M3PC_EINVAL, "null argument");
+    if (a->race && !a->expo) return fail(M3PC_EINVAL, "race needs expo");
+    if (a->n_windows < 1 || a->n_total < 1 || a->n_total > 16384) return fail(M3PC_EINVAL, "bad sizes");
+    if (a->rmax < 0 || a->rmax > 64 || a->list_stride < a->rmax + 1 || a->f_lo < 0 || a->f_stride < 1)
+        return fail(M3PC_EINVAL, "bad list layout");
+    if (a->select && (a->eval_action || a->sample_action) && (!a->a0 || a->A < 1 || a->A > 1024))
+        return fail(M3PC_EINVAL, "eval_action / sample_action need a0");
+    for (int w = 0; w < a->n_windows; ++w) {
+        const int r = a->r[w], n = a->n[w];
+        if (n < 1 || r < 0 || r + n > 1024 || n > a->n_total || r > a->n_total || r > a->rmax || (!a->race && r != 0) ||
+            n > a->list_stride - a->rmax || a->rmax - r < a->f_lo || a->rmax + n - a->f_lo > a->f_stride)
+            return fail(M3PC_EINVAL, "window %d: r %d + n %d outside the list / [1, 1024] / n_total %d", w, r, n, a->n_total);
+        if (!(a->delta[w] >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
+    }
+    MergeSelectBatchP P;
+    memset(&P, 0, sizeof(P));
+    P.b = a->scores;
+    P.expo = a->expo;
+    P.row_stride = a->n_total;
+    P.n_total = a->n_total;
+    P.race = a->race;
+    P.select = a->select;
+    P.tau = a->temperature;
+    P.list = a->list;
+    P.list_scores = a->list_scores;
+    P.list_stride = a->list_stride;
+    P.rmax = a->rmax;
+    P.f = a->list_rescored;
+    P.f_stride = a->f_stride;
+    P.f_lo = a->f_lo;
+    P.out = a->merged;
+    P.stats = a->stats;
+    P.host_stats = a->host_stats;
+    P.seq = a->seq;
+    P.a0 = a->a0;
+    P.a0_wstride = a->a0_window_stride;
+    P.a0_stride = a->a0_stride;
+    P.A = a->A;
+    P.p = a->p;
+    P.eval_action = a->eval_action;
+    P.argmax = a->argmax;
+    P.sample_idx = a->sample_idx;
+    P.sample_action = a->sample_action;
+    launch_merge_select_batch(P, a->n_windows, a->r, a->n, a->delta, (hipStream_t)a->stream);
+    return check_launch("debug_merge_select_batch");
+}
+// the select of n_windows windows in one launch (the fp32 form of m3pc_plan_steps_certified): m3pc_select's checks, per window
+int m3pc_debug_select_batch(const float* scores, const float* a0, long long a0_window_stride, long long a0_stride, int n_windows,
+                            int n_total, int A, float temperature, const float* expo, float* p, float* eval_action, int* argmax,
+                            int* sample_idx, float* sample_action, void* stream) {
+    if (!scores || n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "bad argument");
+    if (n_windows < 1 || n_windows > 65535) return fail(M3PC_EINVAL, "n_windows %d outside [1, 65535]", n_windows);
+    if ((eval_action || sample_action) && (!a0 || A < 1 || A > 1024)) return fail(M3PC_EINVAL, "eval_action / sample_action need a0");
+    if ((sample_idx || sample_action) && !expo) return fail(M3PC_EINVAL, "the multinomial draw needs expo");
+    SelectP s;
+    memset(&s, 0, sizeof(s));
+    s.er = scores;
+    s.a0 = a0;
+    s.a0_stride = a0_stride;
+    s.n = n_total;
+    s.A = A;
+    s.temperature = temperature;
+    s.expo = expo;
+    s.p = p;
+    s.eval_action = eval_action;
+    s.argmax = argmax;
+    s.sample_idx = sample_idx;
+    s.sample_action = sample_action;
+    launch_select_batch(s, n_windows, n_total, a0_window_stride, (hipStream_t)stream);
+    return check_launch("debug_select_batch");
+}
+
+// Not part of the public header (tests/test_block_fused_gpu.py, tools/block_bench.py): the fused layer tail on its own.
+//   O (M,512) bf16; res (M,512) fp32 or rowtab (rt_mod,512); Wo (512,512), W1 (2048,512), W2 (512,2048) bf16 in torch
+//   Linear layout; stream: scratch of m3pc_debug_block_stream_bytes() bytes (packed when pack != 0);
+//   lnB_g0 / lnB_g1 optional (with out_mod / out_grp); Xout (M,512) fp32 optional; Hout (M,512) bf16 optional
+long long m3pc_debug_block_stream_bytes(void) { return (long long)block_stream_bytes(); }
+int m3pc_debug_block_fused(const void* O, int M, const float* res, const float* rowtab, int rt_mod, const void* Wo, const void* W1,
+                           const void* W2, void* stream_buf, int pack, const float* bo, const float* b1, const float* b2,
+                           const float* ln2_g, const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* lnB_g0,
+                           const float* lnB_b0, const float* lnB_g1, const float* lnB_b1, int out_mod, int out_grp, float* Xout,
+                           void* Hout, int variant, void* stream, long long* stamps) {
+    hipStream_t st = (hipStream_t)stream;
+    if (pack) launch_pack_block_stream((const bf16_t*)Wo, (const bf16_t*)W1, (const bf16_t*)W2, (bf16_t*)stream_buf, st);
+    BlockP b;
+    memset(&b, 0, sizeof(b));
+    b.O = (const bf16_t*)O;
+    b.ldo = 512;
+    b.M = M;
+    b.res = res;
+    b.ldr = 512;
+    b.rowtab = rowtab;
+    b.rt_mod = rt_mod;
+    b.wstream = (const bf16_t*)stream_buf;
+    b.bo = bo;
+    b.b1 = b1;
+    b.b2 = b2;
+    b.ln2_g = ln2_g;
+    b.ln2_b = ln2_b;
+    b.Xout = Xout;
+    b.ldx = 512;
+    b.lnA_g = lnA_g;
+    b.lnA_b = lnA_b;
+    b.lnB_g[0] = lnB_g0;
+    b.lnB_b[0] = lnB_b0;
+    b.lnB_g[1] = lnB_g1;
+    b.lnB_b[1] = lnB_b1;
+    b.out_mod = out_mod;
+    b.out_grp = out_grp;
+    b.Hout = (bf16_t*)Hout;
+    b.ldh = 512;
+    b.variant = variant & 15;
+    b.x_bf16 = (variant & 16) ? 1 : 0;  // (res and Xout are then (M, 512) bf16 rows)
+    b.stamps = stamps;
+    if (!launch_block_fused(b, st)) return fail(M3PC_EINVAL, "block_fused: arguments not covered");
+    return check_launch("debug_block_fused");
+}
+
+// the fused layer tail with the next layer's Q|K|V projection behind it: QKV (M, 1536) bf16 = LN_A(X'') Wqkv^T + bqkv
+int m3pc_debug_block_fused_qkv(const void* O, int M, const float* res, const void* Wo, const void* W1, const void* W2, const void* Wqkv,
+                               void* stream_buf, const float* bo, const float* b1, const float* b2, const float* ln2_g,
+                               const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* bqkv, float* Xout, void* QKV,
+                               void* stream, long long* stamps, int x_bf16) {
+    hipStream_t st = (hipStream_t)stream;
+    launch_pack_block_stream((const bf16_t*)Wo, (const bf16_t*)W1, (const bf16_t*)W2, (bf16_t*)stream_buf, st);
+    launch_pack_block_qkv((const bf16_t*)Wqkv, (bf16_t*)stream_buf, st);
+    BlockP b;
+    memset(&b, 0, sizeof(b));
+    b.O = (const bf16_t*)O;
+    b.ldo = 512;
+    b.M = M;
+    b.res = res;
+    b.ldr = 512;
+    b.wstream = (const bf16_t*)stream_buf;
+    b.bo = bo;
+    b.b1 = b1;
+    b.b2 = b2;
+    b.ln2_g = ln2_g;
+    b.ln2_b = ln2_b;
+    b.Xout = Xout;
+    b.ldx = 512;
+    b.lnA_g = lnA_g;
+    b.lnA_b = lnA_b;
+    b.QKVout = (bf16_t*)QKV;
+    b.ldq = 1536;
+    b.qkv_bytes = (unsigned)((size_t)M * 1536 * 2);
+    b.bqkv = bqkv;
+    b.stamps = stamps;
+    b.x_bf16 = x_bf16 ? 1 : 0;  // (res and Xout are then (M, 512) bf16 rows)
+    if (!launch_block_fused(b, st)) return fail(M3PC_EINVAL, "block_fused (qkv): arguments not covered");
+    return check_launch("debug_block_fused_qkv");
+}
+
+// the decoder form of the fused tail with the two scalar output heads inside: rows of group s = (r % out_mod) / out_grp;
+// out0 / out1 (M / 2) floats; Wh (2, 512, 512) bf16, hb1 / hw2 (2, 512), hb2 / hmean / hstd (2) floats (hmean null: no detok)
+int m3pc_debug_block_fused_heads(const void* O, int M, const float* rowtab, int rt_mod, const void* Wo, const void* W1, const void* W2,
+                                 const void* Wh, void* stream_buf, const float* bo, const float* b1, const float* b2, const float* ln2_g,
+                                 const float* ln2_b, const float* lnA_g, const float* lnA_b, const float* lnB_g0, const float* lnB_b0,
+                                 const float* lnB_g1, const float* lnB_b1, int out_mod, int out_grp, const float* hb1, const float* hw2,
+                                 const float* hb2, const float* hmean, const float* hstd, float* out0, float* out1, void* stream,
+                                 long long* stamps) {
+    hipStream_t st = (hipStream_t)stream;
+    launch_pack_block_stream((const bf16_t*)Wo, (const bf16_t*)W1, (const bf16_t*)W2, (bf16_t*)stream_buf, st);
+    launch_pack_block_heads((const bf16_t*)Wh, (const bf16_t*)Wh + 512 * 512, (bf16_t*)stream_buf, st);
+    BlockP b;
+    memset(&b, 0, sizeof(b));
+    b.O = (const bf16_t*)O;
+    b.ldo = 512;
+    b.M = M;
+    b.rowtab = rowtab;
+    b.rt_mod = rt_mod;
+    b.wstream = (const bf16_t*)stream_buf;
+    b.bo = bo;
+    b.b1 = b1;
+    b.b2 = b2;
+    b.ln2_g = ln2_g;
+    b.ln2_b = ln2_b;
+    b.lnA_g = lnA_g;
+    b.lnA_b = lnA_b;
+    b.lnB_g[0] = lnB_g0;
+    b.lnB_b[0] = lnB_b0;
+    b.lnB_g[1] = lnB_g1;
+    b.lnB_b[1] = lnB_b1;
+    b.out_mod = out_mod;
+    b.out_grp = out_grp;
+    b.head_out[0] = out0;
+    b.head_out[1] = out1;
+    for (int s = 0; s < 2; ++s) {
+        b.hb1[s] = hb1 + 512 * s;
+        b.hw2[s] = hw2 + 512 * s;
+        b.hb2[s] = hb2 + s;
+        b.hmean[s] = hmean ? hmean + s : nullptr;
+        b.hstd[s] = hstd ? hstd + s : nullptr;
+    }
+    b.stamps = stamps;
+    if (!launch_block_fused(b, st)) return fail(M3PC_EINVAL, "block_fused (heads): arguments not covered");
+    return check_launch("debug_block_fused_heads");
+}
+
+// the fused layer tail with everything BlockP carries (include/m3pc_hip_debug.h)
+static int debug_block_fill(const m3pc_debug_block_args* a, BlockP& b, SplitReduceP& r) {
+    if (!a) return fail(M3PC_EINVAL, "debug_block: null arguments");
+    memset(&b, 0, sizeof(b));
+    memset(&r, 0, sizeof(r));
+    if (a->picked) a->picked[0] = 0;
+    if (a->M <= 0) return fail(M3PC_EINVAL, "debug_block: M = %d", a->M);
+    if (!a->O || !a->Wo || !a->W1 || !a->W2 || !a->stream_buf || !a->bo || !a->b1 || !a->b2 || !a->ln2_g || !a->ln2_b)
+        return fail(M3PC_EINVAL, "debug_block: O, the layer's weights, biases, norm2 and the stream buffer are required");
+    if (!a->res && !a->rowtab) return fail(M3PC_EINVAL, "debug_block: neither res nor rowtab");
+    if (a->rowtab && a->rt_mod < 1) return fail(M3PC_EINVAL, "debug_block: rowtab with rt_mod %d", a->rt_mod);
+    if (a->res_L < 0 || a->res_nshared < 0) return fail(M3PC_EINVAL, "debug_block: res_L / res_nshared below 0");
+    if ((a->Hout || a->head_out[0]) && !a->lnA_g) return fail(M3PC_EINVAL, "debug_block: Hout / heads without lnA");
+    if (a->lnA_g && !a->lnA_b) return fail(M3PC_EINVAL, "debug_block: lnA_g without lnA_b");
+    for (int s = 0; s < 2; ++s)
+        if ((a->lnB_g[s] != nullptr) != (a->lnB_b[s] != nullptr)) return fail(M3PC_EINVAL, "debug_block: lnB_g / lnB_b come in pairs");
+    if (a->lnB_g[0] && !a->lnB_g[1]) return fail(M3PC_EINVAL, "debug_block: lnB is two pairs (the kernel's tables hold two)");
+    if (a->out_mod < 0 || (a->out_mod > 0 && (a->out_grp < 1 || !a->lnB_g[0]))) return fail(M3PC_EINVAL, "debug_block: out_mod / out_grp / lnB");
+    if (a->QKVout && !a->Wqkv) return fail(M3PC_EINVAL, "debug_block: QKVout without Wqkv");
+    if (a->head_out[0] && (!a->Wh || !a->hb1 || !a->hw2 || !a->hb2)) return fail(M3PC_EINVAL, "debug_block: heads without their weights");
+    if (a->Wqkv && a->Wh) return fail(M3PC_EINVAL, "debug_block: Wqkv and Wh share the stream's tail");
+    if (a->qkv_bytes < 0 || a->qkv_bytes > 0xffffffffll) return fail(M3PC_EINVAL, "debug_block: qkv_bytes");
+    b.O = (const bf16_t*)a->O;
+    b.ldo = a->ldo;
+    b.M = a->M;
+    b.res = (const float*)a->res;
+    b.ldr = a->ldr;
+    b.res_L = a->res_L;
+    b.res_nshared = a->res_nshared;
+    b.rowtab = a->rowtab;
+    b.rt_mod = a->rt_mod;
+    b.res_nu = a->res_nu;
+    b.wstream = (const bf16_t*)a->stream_buf;
+    b.bo = a->bo;
+    b.b1 = a->b1;
+    b.b2 = a->b2;
+    b.ln2_g = a->ln2_g;
+    b.ln2_b = a->ln2_b;
+    b.Xout = (float*)a->Xout;
+    b.ldx = a->ldx;
+    b.x_bf16 = a->x_bf16 ? 1 : 0;
+    b.lnA_g = a->lnA_g;
+    b.lnA_b = a->lnA_b;
+    for (int s = 0; s < 2; ++s) {
+        b.lnB_g[s] = a->lnB_g[s];
+        b.lnB_b[s] = a->lnB_b[s];
+    }
+    b.out_mod = a->out_mod;
+    b.out_grp = a->out_grp;
+    b.Hout = (bf16_t*)a->Hout;
+    b.ldh = a->ldh;
+    b.QKVout = (bf16_t*)a->QKVout;
+    b.ldq = a->ldq;
+    b.qkv_bytes = (unsigned)a->qkv_bytes;
+    b.bqkv = a->bqkv;
+    for (int s = 0; s < 2; ++s) {
+        b.head_out[s] = a->head_out[s];
+        if (!a->head_out[0]) continue;
+        b.hb1[s] = a->hb1 + 512 * s;
+        b.hw2[s] = a->hw2 + 512 * s;
+        b.hb2[s] = a->hb2 + s;
+        b.hmean[s] = a->hmean ? a->hmean + s : nullptr;
+        b.hstd[s] = a->hstd ? a->hstd + s : nullptr;
+    }
+    b.split = a->split ? 1 : 0;
+    if (!block_fused_accepts(b)) return fail(M3PC_EINVAL, "debug_block: arguments not covered (block_fused_accepts)");
+    if (b.split) {
+        r.slabs = (const float*)a->Xout;
+        r.M = a->M;
+        r.Xout = a->red_Xout;
+        r.ldx = a->red_ldx;
+        r.lnA_g = a->red_lnA_g;
+        r.lnA_b = a->red_lnA_b;
+        for (int s = 0; s < 2; ++s) {
+            r.lnB_g[s] = a->red_lnB_g[s];
+            r.lnB_b[s] = a->red_lnB_b[s];
+        }
+        r.out_mod = a->red_out_mod;
+        r.out_grp = a->red_out_grp;
+        r.Hout = (bf16_t*)a->red_Hout;
+        r.ldh = a->red_ldh;
+        if (!r.Xout && !r.Hout) return fail(M3PC_EINVAL, "debug_block: the reduce has no output");
+        if (r.Xout && (((uintptr_t)r.Xout & 15) || r.ldx < 512 || (r.ldx % 4))) return fail(M3PC_EINVAL, "debug_block: red_Xout / red_ldx");
+        if (r.Hout && (((uintptr_t)r.Hout & 15) || r.ldh < 512 || (r.ldh % 8) || !r.lnA_g || !r.lnA_b)) return fail(M3PC_EINVAL, "debug_block: red_Hout / red_ldh / red_lnA");
+        if ((r.lnB_g[0] != nullptr) != (r.lnB_b[0] != nullptr) || (r.lnB_g[0] && r.out_mod > 0 && (!r.lnB_g[1] || !r.lnB_b[1])))
+            return fail(M3PC_EINVAL, "debug_block: red_lnB");
+        if (r.out_mod < 0 || (r.out_mod > 0 && (!r.lnB_g[0] || r.out_mod != 2 * r.out_grp || a->M % r.out_mod != 0)))
+            return fail(M3PC_EINVAL, "debug_block: red_out_mod / red_out_grp");
+    }
+    if (a->picked) a->picked[0] = block_fused_form(b);
+    return 0;
+}
+int m3pc_debug_block_split_n(void) { return block_split_n(); }
+int m3pc_debug_block_accepts(const m3pc_debug_block_args* a) {
+    BlockP b;
+    SplitReduceP r;
+    return debug_block_fill(a, b, r);
+}
+int m3pc_debug_block_ex(const m3pc_debug_block_args* a) {
+    BlockP b;
+    SplitReduceP r;
+    const int rc = debug_block_fill(a, b, r);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)a->stream;
+    launch_pack_block_stream((const bf16_t*)a->Wo, (const bf16_t*)a->W1, (const bf16_t*)a->W2, (bf16_t*)a->stream_buf, st);
+    if (a->Wqkv) launch_pack_block_qkv((const bf16_t*)a->Wqkv, (bf16_t*)a->stream_buf, st);
+    if (a->Wh) launch_pack_block_heads((const bf16_t*)a->Wh, (const bf16_t*)a->Wh + 512 * 512, (bf16_t*)a->stream_buf, st);
+    if (!launch_block_fused(b, st)) {
+        if (a->picked) a->picked[0] = 0;
+        return fail(M3PC_EINVAL, "debug_block: arguments not covered");
+    }
+    if (b.split) launch_block_split_reduce(r, st);
+    return check_launch("debug_block_ex");
+}
+// where the bf16 residual row of token row r lives in the compact layout (block_res_row_xb; host only, no GPU needed)
+int m3pc_debug_block_res_row(int r, int res_L, int res_nshared) {
+    if (r < 0 || res_L < 1 || res_nshared < 0 || res_nshared > res_L) return -1;
+    return block_res_row_xb(r, res_L, res_nshared);
+}
+
+// the embedding kernel (launch_embed) on caller tensors (include/m3pc_hip_debug.h)
+int m3pc_debug_embed(const m3pc_debug_embed_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_embed: null arguments");
+    if (a->batch < 1 || a->L < 1 || a->d % 256 != 0 || a->d < 256 || a->d > 1024 || !a->tokmap) return fail(M3PC_EINVAL, "debug_embed: batch / L / d / tokmap");
+    if (a->n_indep < 0 || a->n_indep > a->L || a->n_sh < 0 || a->n_sh > a->n_indep) return fail(M3PC_EINVAL, "debug_embed: n_indep / n_sh");
+    if (!a->X == !a->Xb) return fail(M3PC_EINVAL, "debug_embed: exactly one of X / Xb");
+    if (a->x_compact && !(a->Xb && a->x_first_only && a->n_indep > 0)) return fail(M3PC_EINVAL, "debug_embed: x_compact needs Xb, x_first_only and n_indep > 0");
+    if ((a->Hb || a->n_sh) && (!a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_embed: Hb without ln_g / ln_b");
+    if (a->n_sh > 0 && (!a->Hb || !a->Hb_sh)) return fail(M3PC_EINVAL, "debug_embed: n_sh without Hb / Hb_sh");
+    EmbedP e;
+    memset(&e, 0, sizeof(e));
+    for (int k = 0; k < 4; ++k) {
+        e.tok[k] = a->tok[k];
+        e.bstride[k] = a->bstride[k];
+        e.WT[k] = a->WT[k];
+        e.E[k] = a->E[k];
+        e.feat[k] = a->feat[k];
+    }
+    e.tokmap = (const int2*)a->tokmap;
+    e.batch = a->batch;
+    e.L = a->L;
+    e.d = a->d;
+    e.T = a->T;
+    e.X = a->X;
+    e.Xb = (bf16_t*)a->Xb;
+    e.ln_g = a->ln_g;
+    e.ln_b = a->ln_b;
+    e.Hb = (bf16_t*)a->Hb;
+    e.Hb_sh = (bf16_t*)a->Hb_sh;
+    e.n_indep = a->n_indep;
+    e.n_sh = a->n_sh;
+    e.x_first_only = a->x_first_only ? 1 : 0;
+    e.x_compact = a->x_compact ? 1 : 0;
+    launch_embed(e, (hipStream_t)a->stream);
+    return check_launch("debug_embed");
+}
+
+// kv_fused_kernel alone (tests/test_block_fused_gpu.py): n candidates of Le rows each in Z (n*Le, 512) bf16; group g holds
+// the kept[g] rows at offset off[g] of every candidate, embedded with We[g] (512, 512) bf16 + rowtab[g] (kept[g], 512);
+// stream_buf: 2 * m3pc_debug_kv_stream_bytes() bytes; KV (n*Le, 1024) bf16
+long long m3pc_debug_kv_stream_bytes(void) { return (long long)kv_stream_bytes(); }
+int m3pc_debug_attention_bf16(const void* QKV, const void* QKVs, void* O, int batch, int n_own, int n_sh, int kernel, void* stream,
+                              long long* stamps) {
+    const int d = 512, L = n_own + n_sh;
+    AttnP a;
+    memset(&a, 0, sizeof(a));
+    const char* q = (const char*)QKV;
+    const char* qs = (const char*)QKVs;
+    a.Q = q;
+    a.q_bstride = (long long)n_own * 3 * d;
+    a.ldq = 3 * d;
+    a.Lq = n_own;
+    a.K1 = q + (size_t)d * 2;
+    a.V1 = q + (size_t)2 * d * 2;
+    a.kv1_bstride = (long long)n_own * 3 * d;
+    a.ldkv1 = 3 * d;
+    a.L1 = n_own;
+    if (n_sh > 0) {  // (run_block: own rows first in the slots, shared rows first in the output)
+        a.orow1 = n_sh;
+        a.Q2 = qs;
+        a.ldq2 = 3 * d;
+        a.Lq2 = n_sh;
+        a.orow2 = 0;
+        a.K2 = qs + (size_t)d * 2;
+        a.V2 = qs + (size_t)2 * d * 2;
+        a.ldkv2 = 3 * d;
+        a.L2 = n_sh;
+    }
+    a.O = O;
+    a.o_bstride = (long long)L * d;
+    a.ldo = d;
+    a.batch = batch;
+    a.n_head = 4;
+    a.hd = 128;
+    a.scale = 1.0f / sqrtf(128.0f);
+    a.stamps = stamps;
+    a.no_pipe = kernel;  // (2, 3: timing variants of the pipelined kernel that compute nothing / load nothing)
+    launch_attention(a, DT_BF16, (hipStream_t)stream);
+    return check_launch("debug_attention_bf16");
+}
+
+int m3pc_debug_attention_dec_bf16(const void* Qtab, const void* QKVm, const void* KV, void* O, float* pre, int n, int nq, int Lm, int kernel,
+                                  void* stream) {
+    return m3pc_debug_attention_dec_le_bf16(Qtab, QKVm, KV, O, pre, n, nq, Lm, 49, kernel, stream);
+}
+
+int m3pc_debug_attention_dec_le_bf16(const void* Qtab, const void* QKVm, const void* KV, void* O, float* pre, int n, int nq, int Lm, int Le, int kernel,
+                                     void* stream) {
+    const int d = 512, nh = 4, hd = 128;
+    hipStream_t st = (hipStream_t)stream;
+    float* pre_m = pre;
+    float* pre_l = pre + nh * nq;
+    float* pre_O = pre + 2 * nh * nq;
+    AttnP at;
+    memset(&at, 0, sizeof(at));
+    at.Q = Qtab;
+    at.ldq = 3 * d;
+    at.Lq = nq;
+    at.K2 = (const char*)QKVm + (size_t)d * 2;
+    at.V2 = (const char*)QKVm + (size_t)2 * d * 2;
+    at.ldkv2 = 3 * d;
+    at.L2 = Lm;
+    at.n_head = nh;
+    at.hd = hd;
+    at.scale = 1.0f / sqrtf((float)hd);
+    launch_attention_prestats(at, pre_m, pre_l, pre_O, st);
+    at.K2 = at.V2 = nullptr;
+    at.L2 = 0;
+    at.q_bstride = 0;
+    at.K1 = KV;
+    at.V1 = (const char*)KV + (size_t)d * 2;
+    at.kv1_bstride = (long long)Le * 2 * d;
+    at.ldkv1 = 2 * d;
+    at.L1 = Le;
+    at.O = O;
+    at.o_bstride = (long long)nq * d;
+    at.ldo = d;
+    at.batch = n;
+    at.pre_m = pre_m;
+    at.pre_l = pre_l;
+    at.pre_O = pre_O;
+    at.no_pipe = kernel;
+    launch_attention(at, DT_BF16, st);
+    return check_launch("debug_attention_dec_bf16");
+}
+
+int m3pc_debug_attention_mix_bf16(const void* Qown, const void* Qsh, const void* KV, const void* QKVm, void* O, int n, int Lq, int Lq2, int kernel,
+                                  void* stream) {
+    const int d = 512, Le = 49, Lm = 79;
+    AttnP at;
+    memset(&at, 0, sizeof(at));
+    at.Q = Qown;
+    at.q_bstride = (long long)Lq * d;
+    at.ldq = d;
+    at.Lq = Lq;
+    at.orow1 = 0;
+    at.Q2 = Qsh;
+    at.ldq2 = 3 * d;
+    at.Lq2 = Lq2;
+    at.orow2 = Lq;
+    at.K1 = KV;
+    at.V1 = (const char*)KV + (size_t)d * 2;
+    at.kv1_bstride = (long long)Le * 2 * d;
+    at.ldkv1 = 2 * d;
+    at.L1 = Le;
+    at.K2 = (const char*)QKVm + (size_t)d * 2;
+    at.V2 = (const char*)QKVm + (size_t)2 * d * 2;
+    at.ldkv2 = 3 * d;
+    at.L2 = Lm;
+    at.O = O;
+    at.o_bstride = (long long)(Lq + Lq2) * d;
+    at.ldo = d;
+    at.batch = n;
+    at.n_head = 4;
+    at.hd = 128;
+    at.scale = 1.0f / sqrtf(128.0f);
+    at.no_pipe = kernel;
+    launch_attention(at, DT_BF16, (hipStream_t)stream);
+    return check_launch("debug_attention_mix_bf16");
+}
+
+// any attention the library launches, on caller tensors (tests/test_attention_gpu.py): fills an AttnP and goes through
+// launch_attention's dispatch; shapes the kernels do not cover are refused before anything is launched
+int m3pc_debug_attention(int dtype, const void* Q, long long q_bstride, int ldq, int Lq, int orow1, const void* Q2, int ldq2, int Lq2,
+                         int orow2, const void* K1, const void* V1, long long kv1_bstride, int ldkv1, int L1, const void* K2,
+                         const void* V2, int ldkv2, int L2, const void* Kp, const void* Vp, int ldp, int Lp, float* pre, void* O,
+                         long long o_bstride, int ldo, int batch, int n_head, int hd, float scale, int kernel, int* picked,
+                         void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (picked) picked[0] = picked[1] = 0;
+    if (dtype != DT_F32 && dtype != DT_BF16) return fail(M3PC_EINVAL, "debug_attention: dtype %d", dtype);
+    if (hd != 32 && hd != 64 && hd != 128) return fail(M3PC_EINVAL, "debug_attention: head dim %d", hd);
+    if (!Q || !K1 || !V1 || !O || batch < 1 || n_head < 1 || Lq < 1 || L1 < 1 || L2 < 0 || Lp < 0 || L1 + L2 > 256 || Lp > 256)
+        return fail(M3PC_EINVAL, "debug_attention: shape");
+    if (kernel != 0 && kernel != 1) return fail(M3PC_EINVAL, "debug_attention: kernel %d", kernel);
+    const int w = n_head * hd, el = dtype == DT_BF16 ? 2 : 4, al = 16 / el;  // (16-byte row fragments)
+    if (q_bstride < 0 || kv1_bstride < 0 || o_bstride < 0 || orow1 < 0 || (Q2 && orow2 < 0)) return fail(M3PC_EINVAL, "debug_attention: negative stride / row");
+    if (ldq < w || ldkv1 < w || ldo < w || (K2 && ldkv2 < w) || (Q2 && ldq2 < w) || (Lp && ldp < w))
+        return fail(M3PC_EINVAL, "debug_attention: leading dimension below n_head * hd");
+    if ((ldq | ldkv1 | ldo | (K2 ? ldkv2 : 0) | (Q2 ? ldq2 : 0) | (Lp ? ldp : 0)) % al || (q_bstride | kv1_bstride | o_bstride) % al)
+        return fail(M3PC_EINVAL, "debug_attention: strides must be multiples of %d elements", al);
+    if (((uintptr_t)Q | (uintptr_t)K1 | (uintptr_t)V1 | (uintptr_t)O | (uintptr_t)Q2 | (uintptr_t)K2 | (uintptr_t)V2 | (uintptr_t)Kp |
+         (uintptr_t)Vp | (uintptr_t)pre) & 15)
+        return fail(M3PC_EINVAL, "debug_attention: pointers must be 16-byte aligned");
+    if ((K2 == nullptr) != (V2 == nullptr) || (L2 > 0) != (K2 != nullptr) || (Lp > 0) != (Kp && Vp && pre) || (Q2 != nullptr) != (Lq2 > 0))
+        return fail(M3PC_EINVAL, "debug_attention: optional segments need their pointers and a length");
+    // the fp32 kernels know one query segment, no pre-reduced block and no output row offset
+    if (dtype == DT_F32 && (Q2 || Lp || orow1)) return fail(M3PC_EINVAL, "debug_attention: Q2 / pre block / orow1 need bf16 rows");
+    // the pre-reduced block is per query, shared by the batch, and indexed by the first segment's query slots
+    if (Lp && (q_bstride != 0 || Q2)) return fail(M3PC_EINVAL, "debug_attention: a pre block needs batch-shared queries and no Q2");
+    AttnP a;
+    memset(&a, 0, sizeof(a));
+    a.Q = Q;
+    a.q_bstride = q_bstride;
+    a.ldq = ldq;
+    a.Lq = Lq;
+    a.orow1 = orow1;
+    a.Q2 = Q2;
+    a.ldq2 = ldq2;
+    a.Lq2 = Q2 ? Lq2 : 0;
+    a.orow2 = orow2;
+    a.n_head = n_head;
+    a.hd = hd;
+    a.scale = scale;
+    float* pre_m = pre;
+    float* pre_l = pre ? pre + (size_t)n_head * Lq : nullptr;
+    float* pre_O = pre ? pre + (size_t)2 * n_head * Lq : nullptr;
+    if (Lp) {  // (pre: n_head * Lq * (2 + hd) floats; pre_O 16-byte aligned as the pipelined kernels read it)
+        if ((2 * n_head * Lq) % 4) return fail(M3PC_EINVAL, "debug_attention: 2 * n_head * Lq must be a multiple of 4");
+        a.K2 = Kp;
+        a.V2 = Vp;
+        a.ldkv2 = ldp;
+        a.L2 = Lp;
+        launch_attention_prestats(a, pre_m, pre_l, pre_O, st);
+        if (picked) picked[1] = 50;
+        a.pre_m = pre_m;
+        a.pre_l = pre_l;
+        a.pre_O = pre_O;
+    }
+    a.K1 = K1;
+    a.V1 = V1;
+    a.kv1_bstride = kv1_bstride;
+    a.ldkv1 = ldkv1;
+    a.L1 = L1;
+    a.K2 = K2;
+    a.V2 = V2;
+    a.ldkv2 = ldkv2;
+    a.L2 = L2;
+    a.O = O;
+    a.o_bstride = o_bstride;
+    a.ldo = ldo;
+    a.batch = batch;
+    a.no_pipe = kernel;
+    g_attn_picked = 0;
+    launch_attention(a, dtype, st);
+    if (picked) picked[0] = g_attn_picked;
+    return check_launch("debug_attention");
+}
+
+int m3pc_debug_kv_fused(const void* Z, int n, int Le, int kept0, int off0, int kept1, int off1, const void* We0, const void* We1,
+                        const void* Wkv, void* stream_buf, const float* rowtab0, const float* rowtab1, const float* ln_g,
+                        const float* ln_b, const float* bkv, void* KV, void* stream, long long* stamps) {
+    hipStream_t st = (hipStream_t)stream;
+    bf16_t* s0 = (bf16_t*)stream_buf;
+    bf16_t* s1 = (bf16_t*)((char*)stream_buf + kv_stream_bytes());
+    launch_pack_kv_stream((const bf16_t*)We0, (const bf16_t*)Wkv, s0, st);
+    if (kept1) launch_pack_kv_stream((const bf16_t*)We1, (const bf16_t*)Wkv, s1, st);
+    KvFusedP p;
+    memset(&p, 0, sizeof(p));
+    p.Z = (const bf16_t*)Z;
+    p.ldz = 512;
+    p.M[0] = n * kept0;
+    p.map[0] = RowMap{kept0, Le, off0};
+    p.rowtab[0] = rowtab0;
+    p.rt_mod[0] = kept0;
+    p.wstream[0] = s0;
+    p.M[1] = n * kept1;
+    p.map[1] = RowMap{kept1 ? kept1 : 1, Le, off1};
+    p.rowtab[1] = rowtab1;
+    p.rt_mod[1] = kept1 ? kept1 : 1;
+    p.wstream[1] = s1;
+    p.ln_g = ln_g;
+    p.ln_b = ln_b;
+    p.bkv = bkv;
+    p.KV = (bf16_t*)KV;
+    p.ldkv = 1024;
+    p.kv_bytes = (unsigned)((size_t)n * Le * 1024 * 2);
+    p.stamps = stamps;
+    if (!launch_kv_fused(p, st)) return fail(M3PC_EINVAL, "kv_fused: arguments not covered");
+    return check_launch("debug_kv_fused");
+}
+
+int m3pc_debug_kv_fused_ex(const m3pc_debug_kv_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_kv: null arguments");
+    if (!a->Z || !a->Wkv || !a->stream_buf || !a->ln_g || !a->ln_b || !a->bkv || !a->KV) return fail(M3PC_EINVAL, "debug_kv: a required pointer is null");
+    if (a->kv_bytes <= 0 || a->kv_bytes > 0xffffffffll) return fail(M3PC_EINVAL, "debug_kv: kv_bytes");
+    hipStream_t st = (hipStream_t)a->stream;
+    KvFusedP p;
+    memset(&p, 0, sizeof(p));
+    p.Z = (const bf16_t*)a->Z;
+    p.ldz = a->ldz;
+    for (int g = 0; g < 2; ++g) {
+        p.M[g] = a->M[g];
+        if (a->map[g][0] < 0 || a->map[g][2] < 0 || (a->map[g][0] > 0 && a->map[g][1] < a->map[g][0])) return fail(M3PC_EINVAL, "debug_kv: row map of group %d", g);
+        p.map[g] = RowMap{a->map[g][0], a->map[g][1], a->map[g][2]};
+        p.rowtab[g] = a->rowtab[g];
+        p.rt_mod[g] = a->rt_mod[g];
+        p.wstream[g] = (const bf16_t*)((char*)a->stream_buf + g * kv_stream_bytes());
+        if (a->M[g] > 0 && !a->We[g]) return fail(M3PC_EINVAL, "debug_kv: group %d without its embedding weights", g);
+    }
+    p.ln_g = a->ln_g;
+    p.ln_b = a->ln_b;
+    p.bkv = a->bkv;
+    p.KV = (bf16_t*)a->KV;
+    p.ldkv = a->ldkv;
+    p.kv_bytes = (unsigned)a->kv_bytes;
+    for (int g = 0; g < 2; ++g)
+        if (a->M[g] > 0) launch_pack_kv_stream((const bf16_t*)a->We[g], (const bf16_t*)a->Wkv, (bf16_t*)p.wstream[g], st);
+    if (!launch_kv_fused(p, st)) return fail(M3PC_EINVAL, "kv_fused: arguments not covered");
+    return check_launch("debug_kv_fused_ex");
+}
+
+// which XCD (and CU) every workgroup of a launch on `stream` lands on: out[2 i] = XCC_ID, out[2 i + 1] = HW_ID register
+// (tools/xcd_probe.py: maps the bits of a hipExtStreamCreateWithCUMask mask to XCDs)
+__global__ void xcc_probe_kernel(int* out) {
+    if (threadIdx.x == 0) {
+        out[2 * blockIdx.x] = (int)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));   // HW_REG_XCC_ID[3:0]
+        out[2 * blockIdx.x + 1] = (int)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)); // HW_REG_HW_ID
+    }
+    // (long enough that the workgroups of the launch spread over everything the stream may use)
+    const long long t0 = __builtin_amdgcn_s_memrealtime();
+    for (int i = 0; i < 1024; ++i) {
+        if (__builtin_amdgcn_s_memrealtime() - t0 >= 300) break;
+        __builtin_amdgcn_s_sleep(16);
+    }
+}
+int m3pc_debug_xcc_probe(int* out, int n_blocks, void* stream) {
+    hipLaunchKernelGGL(xcc_probe_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, out);
+    return check_launch("xcc_probe");
+}
+
+int m3pc_debug_clock_big(long long* out4) {
+    HIPCHK(hipDeviceSynchronize());
+    read_big_probe(out4);
+    return 0;
+}
+
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -1,5 +1,6 @@
-// Internals of libm3pc_hip.so shared by its host-side translation units (m3pc.hip: the C ABI; m3pc_plans.hip: mask plans and
-// the candidate-independent decoder tables; m3pc_passes.hip: the forward passes).  Not part of the C ABI.
+// Internals of libm3pc_hip.so shared by its host-side translation units (m3pc.hip, m3pc_certified.hip and, in the lab build,
+// m3pc_debug.hip: the C ABI; m3pc_plans.hip: mask plans and the candidate-independent decoder tables; m3pc_passes.hip: the
+// forward passes).  Not part of the C ABI.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -18,6 +19,7 @@
 #ifdef M3PC_LAB
 #include "../../include/m3pc_hip_debug.h"
 #endif
+#include "cert_resolve.h"
 #include "kernels.h"
 
 using namespace m3pc;
@@ -177,8 +179,8 @@ struct m3pc_handle {
               *sample_action = nullptr;
         int *list = nullptr, *argmax = nullptr, *sample_idx = nullptr;
         hipStream_t tail = nullptr;
-        double delta = 0.0;
-        int rounds = 0, n_done = 0, r_done = 0;
+        CertState cs;    // the protocol's state (cert_resolve.h): n_done, r_done, delta, ...
+        int rounds = 0;  // merges issued
         float seq = 0.f;
     } cstep[M3PC_SLOTS];
     // m3pc_plan_steps_certified (a lock-step batch of certified steps): what a certified step keeps per slot, per WINDOW of the
@@ -604,6 +606,9 @@ void invalidate_tables(m3pc_handle* h);
 int build_query_list(m3pc_handle* h, Plan* pl, int qi, int hh, const std::vector<int>& toks, int n_groups, int key0, int key1);
 int build_query(m3pc_handle* h, Plan* pl, int qi, int hh);
 int build_tables(m3pc_handle* h, Plan* pl, int qi, int dt, hipStream_t st);
+// m3pc_certified.hip
+int cert_check_args(const m3pc_plan_args* a, const char* who);  // one rank, every candidate, a valid precision and slot
+bool cert_any_begun(const m3pc_handle* h);                      // a pipelined certified step is between _begin and _end
 // m3pc_passes.hip
 int run_block(m3pc_handle* h, const std::string& pfx, float* X, int batch, int L, int dt, hipStream_t st, bool ln1_done = false,
               int n_sh = 0, const LnP* next_ln = nullptr, bool* next_ln_done = nullptr, bool x_dead = false,
