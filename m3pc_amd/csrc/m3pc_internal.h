@@ -536,8 +536,7 @@ inline bool can_fold_ln(m3pc_handle* h, const GemmP& p, int dt) {
 }
 
 inline GemmP gemm_basic(const void* A, int lda, const void* Wp, int ldw, int M, int N, int K, const float* bias) {
-    GemmP p;
-    memset(&p, 0, sizeof(p));
+    GemmP p{};
     p.A = A;
     p.lda = lda;
     p.W = Wp;
@@ -560,14 +559,89 @@ inline void gemm_out(GemmP& p, int dt_out, void* C, int ldc) {
     p.ldc = ldc;
 }
 
+// ---------------------------------------------------------------------------------- descriptor fillers
+// LayerNorm (g, b) of `rows` contiguous rows of X (ld = d) -> rows of `out` in dtype dt_out
+inline LnP ln_rows(m3pc_handle* h, const float* X, int rows, const float* g, const float* b, void* out, int dt_out) {
+    LnP p{};
+    p.X = X;
+    p.ldx = h->d;
+    p.rows = rows;
+    p.d = h->d;
+    p.g1 = g;
+    p.b1 = b;
+    if (dt_out == DT_BF16)
+        p.Yb = (bf16_t*)out;
+    else
+        p.Yf = (float*)out;
+    return p;
+}
+// what every attention of a pass shares: `batch` sequences of Lo output rows each in O, the model's heads
+inline AttnP attn_basic(m3pc_handle* h, int batch, int Lo) {
+    AttnP a{};
+    a.O = h->O;
+    a.o_bstride = (long long)Lo * h->d;
+    a.ldo = h->d;
+    a.batch = batch;
+    a.n_head = h->nh;
+    a.hd = h->hd;
+    a.scale = 1.0f / sqrtf((float)h->hd);
+    return a;
+}
+// rows_per_batch rows per sequence, each from the sequence's own rows of Xe or from `table`, as rowsrc says
+inline GatherP gather_basic(m3pc_handle* h, const float* Xe, int xe_rows, const float* table, const int* rowsrc, int rows_per_batch, int batch) {
+    GatherP g{};
+    g.Xe = Xe;
+    g.xe_bstride = (long long)xe_rows * h->d;
+    g.table = table;
+    g.rowsrc = rowsrc;
+    g.rows_per_batch = rows_per_batch;
+    g.batch = batch;
+    g.d = h->d;
+    return g;
+}
+
+// ---------------------------------------------------------------------------------- lab A/B switches of the pass code
+// Every environment switch m3pc_passes.hip reads (tools/ab_env.sh; the lab build only), read once.  M3PC_ENV is a constant null
+// pointer in the product build, where every field folds to false.
+struct PassSwitches {
+    bool no_block_fused;     // M3PC_NO_BLOCK_FUSED: no fused layer tail, and nothing that needs one
+    bool no_block_split;     // M3PC_NO_BLOCK_SPLIT: no split form of it
+    bool no_qkv_fused;       // M3PC_NO_QKV_FUSED: the next layer's Q|K|V never inside the tail
+    bool no_fused_anything;  // either of the two: the bf16 residual stream needs both
+    bool no_prune1;          // M3PC_NO_PRUNE1: no shared history rows in the first encoder layer
+    bool no_bf16_residual;   // M3PC_NO_BF16_RESIDUAL
+    bool no_shared_xb;       // M3PC_NO_SHARED_XB: the bf16 residual stream's history rows stored per candidate
+    bool no_kv_fused;        // M3PC_NO_KV_FUSED (or no fused tail): decoder embedding, norm1 and K|V as GEMMs
+    bool no_mix_prefix;      // M3PC_NO_MIX_PREFIX
+    bool no_head_fused;      // M3PC_NO_HEAD_FUSED: the scalar heads never inside the tail
+    bool no_head_out_mfma;   // M3PC_NO_HEAD_OUT_MFMA
+    bool no_head_f32_fused;  // M3PC_NO_HEAD_F32_FUSED (or M3PC_NO_F32_DIRECT): the re-score's scalar heads as launches
+    bool no_group;           // M3PC_NO_GEMM_GROUP, M3PC_NO_F32_DIRECT or M3PC_GEMM_VARIANT: the decoder embeddings one GEMM each
+};
+inline const PassSwitches& pass_switches() {
+    static const PassSwitches s = [] {
+        auto on = [](const char* v) { return v != nullptr; };
+        PassSwitches w{};
+        w.no_block_fused = on(M3PC_ENV("M3PC_NO_BLOCK_FUSED"));
+        w.no_block_split = on(M3PC_ENV("M3PC_NO_BLOCK_SPLIT"));
+        w.no_qkv_fused = on(M3PC_ENV("M3PC_NO_QKV_FUSED"));
+        w.no_fused_anything = w.no_block_fused || w.no_qkv_fused;
+        w.no_prune1 = on(M3PC_ENV("M3PC_NO_PRUNE1"));
+        w.no_bf16_residual = on(M3PC_ENV("M3PC_NO_BF16_RESIDUAL"));
+        w.no_shared_xb = on(M3PC_ENV("M3PC_NO_SHARED_XB"));
+        w.no_kv_fused = on(M3PC_ENV("M3PC_NO_KV_FUSED")) || w.no_block_fused;
+        w.no_mix_prefix = on(M3PC_ENV("M3PC_NO_MIX_PREFIX"));
+        w.no_head_fused = on(M3PC_ENV("M3PC_NO_HEAD_FUSED"));
+        w.no_head_out_mfma = on(M3PC_ENV("M3PC_NO_HEAD_OUT_MFMA"));
+        const bool no_f32_direct = on(M3PC_ENV("M3PC_NO_F32_DIRECT"));
+        w.no_head_f32_fused = on(M3PC_ENV("M3PC_NO_HEAD_F32_FUSED")) || no_f32_direct;
+        w.no_group = on(M3PC_ENV("M3PC_NO_GEMM_GROUP")) || no_f32_direct || on(M3PC_ENV("M3PC_GEMM_VARIANT"));
+        return w;
+    }();
+    return s;
+}
+
 // ---------------------------------------------------------------------------------- transformer block
-// One pre-LN layer (mtm_model.py:379-409) over `batch` sequences of L rows, in place on X (fp32).
-// next_ln: the LayerNorm that follows this block on X (next block's norm1 or the stack's final norm); when the
-// FFN2 GEMM can apply it in its split-K reduce, *next_ln_done is set and the caller skips that launch.
-// x_dead: nothing reads X after this block except through next_ln (lets the fused tail skip the fp32 store).
-// Xnext / res_nshared (fused tail only): the block output goes to Xnext instead of X, and the first res_nshared rows of
-// every sequence of X are read from sequence 0 (the embedding kernel stored the history rows once, EmbedP::x_first_only).
-// With x_bf16, X is then the compact block of block_res_row_xb (EmbedP::x_compact): shared rows once, own rows behind them.
 // The fused layer tail (block_fused.hip) works in 128-row tiles, one per CU, and a tile takes its ~130-170 us whatever the row
 // count: below ~96 tiles most of the chip idles for that long and the GEMM chain, whose tiles spread over all CUs, is faster
 // (the reference's shipped N=625 / T=8 config, 64 + 40 tiles: 1.13 -> 1.00 ms per closed-loop call).
@@ -578,21 +652,33 @@ constexpr long long FUSED_MIN_ROWS = 96 * 128;
 // partials to four slabs in the F buffer) with a row-wise reduce + LayerNorm launch behind it (block_fused_kernel<0, 3>).
 constexpr long long SPLIT_MIN_ROWS = 16 * 128;
 
+// "norm1 of the next layer is already in Hn" (ln) / "its Q|K|V rows are already in QKV" (qkv): what one layer leaves for the next,
+// and what one piece of an encoder pass enqueued in pieces leaves for the next (the embedding kernel writes norm1 of layer 0)
+struct PieceState {
+    bool ln = true, qkv = false;
+};
+
+// One pre-LN layer (mtm_model.py:379-409) over `batch` sequences of L rows of X (fp32), in place unless Xnext is given.
+struct BlockArgs {
+    const std::string& pfx;                // "encoder.layers.0", ...
+    float* X;
+    int batch, L;
+    int n_sh = 0;                          // first layer of a candidate pass: the first n_sh tokens are the same for every candidate
+    const LnP* next_ln = nullptr;          // the LayerNorm that follows this block on its output (next block's norm1 or the stack's final
+                                           // norm): the tail applies it when it can, and says so in PieceState::ln
+    bool x_dead = false;                   // nothing reads the block output except through next_ln (the fused tail skips the fp32 store)
+    const std::string* next_qkv = nullptr; // the layer whose Q|K|V projection the fused tail may compute (-> PieceState::qkv)
+    bool x_bf16 = false;                   // X holds bf16 rows: the residual stream of a bf16 pass all of whose layers take the fused tail
+    float* Xnext = nullptr;                // x_bf16 only: the block output goes to Xnext, and X is the compact block of block_res_row_xb
+    int res_nshared = 0;                   // (EmbedP::x_compact): its first res_nshared rows stored once, every sequence's own rows behind them
+};
+
 struct TokIn {
     const float* ptr[4];
     long long bstride[4];
     int normalize[4];
     const int* widx = nullptr;  // optional per-batch-element window index into ptr[k] (stride wstride[k])
     long long wstride[4] = {0, 0, 0, 0};
-};
-
-// embed + encoder stack + encoder.norm -> EncOut (fp32) [and bf16 copy in Z when dt == bf16 and want_b]
-// n_indep: number of leading encoder tokens that are identical for every batch element (candidate pass: history)
-// layer_from / layer_to / ln_state: the pass can be enqueued in pieces (the embedding goes with layer 0, encoder.norm with the
-// last layer); *ln_state carries "norm1 of the next layer is already in Hn" (ln) / "its Q|K|V rows are already in QKV" (qkv)
-// from one piece to the next
-struct PieceState {
-    bool ln = true, qkv = false;
 };
 
 enum { TAIL_HEADS = 0, TAIL_X = 1 };
@@ -610,10 +696,12 @@ int build_tables(m3pc_handle* h, Plan* pl, int qi, int dt, hipStream_t st);
 int cert_check_args(const m3pc_plan_args* a, const char* who);  // one rank, every candidate, a valid precision and slot
 bool cert_any_begun(const m3pc_handle* h);                      // a pipelined certified step is between _begin and _end
 // m3pc_passes.hip
-int run_block(m3pc_handle* h, const std::string& pfx, float* X, int batch, int L, int dt, hipStream_t st, bool ln1_done = false,
-              int n_sh = 0, const LnP* next_ln = nullptr, bool* next_ln_done = nullptr, bool x_dead = false,
-              float* Xnext = nullptr, int res_nshared = 0, bool qkv_done = false, const std::string* next_qkv = nullptr,
-              bool* next_qkv_done = nullptr, bool x_bf16 = false);
+// ps: in, what the previous layer (or the embedding) left for this one; out, what this layer leaves for the next
+int run_block(m3pc_handle* h, const BlockArgs& a, int dt, hipStream_t st, PieceState& ps);
+// embed + encoder stack + encoder.norm -> EncOut (fp32), or Z (bf16) alone with bf16_out_only
+// n_indep: number of leading encoder tokens that are identical for every batch element (candidate pass: history)
+// layer_from / layer_to / ln_state: the pass can be enqueued in pieces (the embedding goes with layer 0, encoder.norm with the
+// last layer); *ln_state carries the PieceState from one piece to the next
 int run_encoder(m3pc_handle* h, Plan* pl, const TokIn& in, int batch, int dt, hipStream_t st, bool bf16_out_only = false,
                 int n_indep = 0, int layer_from = 0, int layer_to = 1 << 30, PieceState* ln_state = nullptr);
 void dec_embed(m3pc_handle* h, int k, const void* Zop, RowMap amap, float* Yout, RowMap cmap, int M, int mod, int dt,
