@@ -46,7 +46,8 @@ extern "C" {
  * m3pc_calibrate_delta, m3pc_cert_args, m3pc_cert_record; then m3pc_plan_step_certified_begin / _end, m3pc_set_step_streams and
  * m3pc_draw_variates; then m3pc_refit_resample, m3pc_refine_plan and m3pc_refine_args (CEM / MPPI refinement); then
  * m3pc_plan_steps_certified (a lock-step batch of certified steps); then m3pc_eval_bound, m3pc_plan_step_certified_eval and
- * m3pc_eval_record (the eval_action certificate).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * m3pc_eval_record (the eval_action certificate); then m3pc_plan_step_certified_eval_begin / _eval_end and
+ * m3pc_plan_steps_certified_eval (that certificate in the pipelined and the lock-step step).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -514,7 +515,8 @@ int m3pc_eval_bound(m3pc_handle* h, const float* merged, int n_total, const int*
  * tighten a bf16 step's bound.  DESIGN.md section 5 has the measured table.
  * Refusals: those of m3pc_plan_step_certified, plus erec == NULL and eval_tol <= 0 or NaN (M3PC_EINVAL, before any HIP call), plus
  * M3PC_ESTATE while a pipelined step is begun.
- * Out of scope: a _begin / _end split and a lock-step (m3pc_plan_steps_certified) form of the eval certificate. */
+ * The same certificate in the pipelined step: m3pc_plan_step_certified_eval_begin / _eval_end below; in a lock-step batch:
+ * m3pc_plan_steps_certified_eval.  This call keeps its launch sequence. */
 typedef struct m3pc_eval_record {
     float eval_bound;      /* the LAST bound: |eval_action - fp32 eval_action| <= eval_bound under the delta model; 0 after `everything` */
     int need_eval_first;   /* what the FIRST eval certificate asked for (n_total: the list could not reach eval_tol) */
@@ -561,6 +563,29 @@ int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* args, c
                                    float* eval_action, int* argmax, int* sample_idx, float* sample_action, void* stream);
 int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* record, void* stream);
 
+/* m3pc_plan_step_certified_eval in two halves: schedule, buffers and state rules are those of _begin / _end above.  For the same
+ * inputs the pair produces exactly what m3pc_plan_step_certified_eval produces -- every output buffer, every field of `record` and
+ * every field of `erec`, bit for bit -- at any depth 1..M3PC_SLOTS, with the _ends in any order, with plain and eval steps mixed in
+ * flight, in every regime of the certificates and for every precision (M3PC_PREC_FP32: erec = {0, 0, 0, 0, 1}).
+ *   No second host wait in the common case.  When the step's tail is enqueued, m3pc_eval_bound goes out on the chain stream right
+ *   behind the first merge + select, for the state that pass assumes (r = rfirst, n = kmin, n_listed = min(kmax, n_total), delta as
+ *   it came in), into the slot's second host-mapped block.  _eval_end reads the two certificates; if they ask for nothing -- no
+ *   further merge was issued, delta is unchanged -- that launch IS the serial call's bound launch (same kernel, same inputs, same
+ *   bits) and its statistics are taken.  Otherwise it is dropped, and the bound is launched behind the last merge and waited for
+ *   as in the serial call.  What the bound asks for is re-scored in _eval_end on the chain stream, like every other extension.
+ *   erec->eval_rounds counts the bounds the loop read: a dropped launch is not one.
+ *   Mixing.  m3pc_plan_step_certified_end on a slot begun with _eval_begin resolves the two certificates only (the block written in
+ *   advance is ignored).  _eval_end on a slot begun with m3pc_plan_step_certified_begin returns M3PC_ESTATE and leaves the step
+ *   begun.  eval_tol <= 0 or NaN, and erec == NULL, return M3PC_EINVAL before any HIP call.  m3pc_plan_step_certified_eval with a
+ *   step begun returns M3PC_ESTATE.  No new streams, no device-wide synchronisation, the bounded wait of the other certificates.
+ * examples/pipelined_eval.c is a complete host. */
+int m3pc_plan_step_certified_eval_begin(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_cert_args* cert, const float* states,
+                                        const float* actions, const float* rewards, const float* eps, const float* expo, float* loc,
+                                        float* std, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
+                                        float* eval_action, int* argmax, int* sample_idx, float* sample_action, float eval_tol,
+                                        void* stream);
+int m3pc_plan_step_certified_eval_end(m3pc_handle* h, int slot, m3pc_cert_record* record, m3pc_eval_record* erec, void* stream);
+
 /* A LOCK-STEP BATCH of certified plan steps as one call: E = n_windows environments that step together (replay_buffer.py:204-232 per
  * environment), all windows sharing one effective horizon.  It is the protocol of m3pc_amd/lockstep.py (action_sample_batch(lockstep=True))
  * restated in C, everything on `stream`, in the serial form (there is no _begin / _end split of this call):
@@ -603,6 +628,24 @@ int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* args, const 
                               const float* eps, const float* expo, float* loc, float* std, float* sample_actions,
                               float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax,
                               int* sample_idx, float* sample_action, m3pc_cert_record* records, void* stream);
+
+/* m3pc_plan_steps_certified with the eval_action certificate per window (erecs: host out (E,)).  Steps 1-7 are unchanged; behind
+ * the batched merge of step 6 ONE launch bounds every window (m3pc_eval_bound per window: r = rfirst, n = kmin, delta = cert->delta)
+ * into a second host-mapped block per window; step 8 runs the loop of m3pc_plan_step_certified_eval per window.  A window that
+ * issued no merge beyond the batched one (records[w].rounds == 1, which also means no earlier window raised delta) takes its block;
+ * any other window launches m3pc_eval_bound behind its last merge and waits.  Extensions are the window's own re-scores and merges;
+ * a raised delta travels to later windows as in m3pc_plan_steps_certified.
+ *   eval_tol = +inf: every output buffer and every record is bit for bit m3pc_plan_steps_certified's.
+ *   erecs[w].eval_bound is bit for bit a stand-alone m3pc_eval_bound on the returned merged row, lists and records[w].
+ *   M3PC_PREC_FP32: erecs[w] = {0, 0, 0, 0, 1}.
+ * Refusals: those of m3pc_plan_steps_certified, plus erecs == NULL and eval_tol <= 0 or NaN (M3PC_EINVAL, before any HIP call).
+ * The Python lock-step protocol (m3pc_amd/lockstep.py) has no eval form. */
+int m3pc_plan_steps_certified_eval(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_cert_args* cert, int n_windows,
+                                   const float* states, const float* actions, const float* rewards, const double* rtg,
+                                   const float* eps, const float* expo, float* loc, float* std, float* sample_actions,
+                                   float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax,
+                                   int* sample_idx, float* sample_action, m3pc_cert_record* records, float eval_tol,
+                                   m3pc_eval_record* erecs, void* stream);
 
 /* The variates of a plan step, for a host without a generator of its own: eps device out (n_count, row_elems) standard normals =
  * rows [n_begin, n_begin + n_count) of the (n_total, row_elems) array of (seed, step); expo device out (n_count,) Exp(1) (never 0),

@@ -154,6 +154,31 @@ int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a);
 int m3pc_debug_select_batch(const float* scores, const float* a0, long long a0_window_stride, long long a0_stride, int n_windows,
                             int n_total, int A, float temperature, const float* expo, float* p, float* eval_action, int* argmax,
                             int* sample_idx, float* sample_action, void* stream);
+/* m3pc_eval_bound of n_windows windows in one launch (eval_bound_batch_kernel, behind the batched merge of
+ * m3pc_plan_steps_certified_eval): window w reads row w of merged (n_windows, n_total), the slice of its list row (rows of list_stride
+ * int32) from rmax - r[w] on -- r[w] re-scored race entries, then n_listed score entries of which the first n[w] are re-scored --,
+ * its first actions at a0 + w a0_window_stride (candidate j's at + j a0_stride, A floats) and delta[w]; r / n / delta are HOST arrays;
+ * n_listed, temperature and eval_tol are shared.  stats (n_windows, 8) device; host_stats (optional): n_windows blocks of 8 floats a
+ * kernel can store to, each closed by seq in slot 4, written last at system scope.  Window w's eight floats are m3pc_eval_bound's on
+ * that window's rows, bit for bit (tests/test_eval_bound_batch_gpu.py).  rmax + n_listed <= min(1024, list_stride). */
+typedef struct m3pc_debug_eval_batch_args {
+    const float* merged;
+    int n_windows, n_total;
+    const int* list;
+    int rmax, list_stride, n_listed;
+    const int* r;       /* host */
+    const int* n;       /* host */
+    const float* delta; /* host */
+    const float* a0;
+    long long a0_window_stride, a0_stride;
+    int A;
+    float temperature, eval_tol;
+    float* stats;
+    float* host_stats;
+    float seq;
+    void* stream;
+} m3pc_debug_eval_batch_args;
+int m3pc_debug_eval_bound_batch(const m3pc_debug_eval_batch_args* a);
 /* the fused layer tail (block_fused.hip) on caller tensors; see csrc/m3pc_debug.hip for the argument layout */
 long long m3pc_debug_block_stream_bytes(void);
 int m3pc_debug_block_fused(const void* O, int M, const float* res, const float* rowtab, int rt_mod, const void* Wo, const void* W1,

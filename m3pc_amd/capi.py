@@ -48,6 +48,7 @@ EXPORTS = (
     "m3pc_refit_resample", "m3pc_refine_plan",
     "m3pc_plan_steps_certified",
     "m3pc_eval_bound", "m3pc_plan_step_certified_eval",
+    "m3pc_plan_step_certified_eval_begin", "m3pc_plan_step_certified_eval_end", "m3pc_plan_steps_certified_eval",
 )
 
 
@@ -164,6 +165,11 @@ def load_library(path: Optional[str] = None):
         "m3pc_plan_step_certified_begin": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                            vp, vp, vp, vp, vp, vp],
         "m3pc_plan_step_certified_end": [vp, i, C.POINTER(CertRecord), vp],
+        "m3pc_plan_step_certified_eval_begin": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, vp, vp, f, vp],
+        "m3pc_plan_step_certified_eval_end": [vp, i, C.POINTER(CertRecord), C.POINTER(EvalRecord), vp],
+        "m3pc_plan_steps_certified_eval": [vp, C.POINTER(PlanArgs), C.POINTER(CertArgs), i, vp, vp, vp, C.POINTER(d), vp, vp, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CertRecord), f, C.POINTER(EvalRecord), vp],
         "m3pc_draw_variates": [vp, C.c_ulonglong, C.c_ulonglong, i, i, i, vp, vp, vp],
         "m3pc_refit_resample": [vp, vp, i, i, vp, vp, i, i, f, f, vp, vp, vp, vp, vp],
         "m3pc_refine_plan": [vp, C.POINTER(PlanArgs), C.POINTER(RefineArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -550,7 +556,8 @@ class Handle:
     def plan_steps_certified(self, mode: int, states, actions, rewards, rtg, eps, expo, horizon: int, lmbda: float, discount: float,
                              n_total: int, temperature: float, delta: float = 0.0, grow_delta: bool = False, kmin: int = 8,
                              kmax: int = 128, rfirst: int = 2, rmax: int = 32, precision: int = PREC_BF16, slot: int = 0,
-                             want_policy: bool = True, want_list: bool = True, want_p: bool = True, out=None):
+                             want_policy: bool = True, want_list: bool = True, want_p: bool = True, out=None,
+                             eval_tol: Optional[float] = None):
         """A lock-step batch of certified plan steps in ONE library call (m3pc_plan_steps_certified) on the current stream: states
         (E,T,S), actions (E,T,A), rewards (E,T,1), rtg (E,) floats, eps (E, n_total, T|h, A), expo (E, n_total).  Returns (res,
         records): ``res`` holds loc / std (E,T,A), sample_actions (E,n_total,h,A), expect_return_low and expect_return (the merged
@@ -559,7 +566,8 @@ class Handle:
         optional loc + std / list / p are passed as NULL (``None`` in ``res``).  ``out``: optional preallocated contiguous outputs
         by name (loc, std, sample_actions, expect_return_low, expect_return, list, p, eval_action, argmax, sample_idx,
         sample_action).  The host has read every window's last certificate when the call returns; the tensors are complete in
-        stream order."""
+        stream order.  eval_tol: the call is m3pc_plan_steps_certified_eval (the eval_action certificate per window) and the return
+        value (res, records, eval_records)."""
         dev, T, A = self.device, self.T, self.A
         ins = [self._f32(t) for t in (states, actions, rewards, eps, expo)]
         E = int(ins[0].shape[0])
@@ -586,10 +594,18 @@ class Handle:
         args = self._args(mode, precision, horizon, n_total, 0, n_total, lmbda, discount, 0.0, slot)
         cert = CertArgs(float(temperature), float(delta), int(bool(grow_delta)), int(kmin), int(kmax), int(rfirst), int(rmax))
         recs = (CertRecord * E)()
+        res = dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel)
+        if eval_tol is not None:
+            erecs = (EvalRecord * E)()
+            check(self.lib.m3pc_plan_steps_certified_eval(self._h, C.byref(args), C.byref(cert), E, _ptr(ins[0]), _ptr(ins[1]),
+                                                          _ptr(ins[2]), (C.c_double * E)(*rt), _ptr(ins[3]), _ptr(ins[4]), _ptr(loc),
+                                                          _ptr(std), _ptr(acts), _ptr(low), _ptr(merged), _ptr(lst),
+                                                          *[_ptr(t) for t in sel], recs, float(eval_tol), erecs, _stream(dev)))
+            return res, list(recs), list(erecs)
         check(self.lib.m3pc_plan_steps_certified(self._h, C.byref(args), C.byref(cert), E, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
                                                  (C.c_double * E)(*rt), _ptr(ins[3]), _ptr(ins[4]), _ptr(loc), _ptr(std), _ptr(acts),
                                                  _ptr(low), _ptr(merged), _ptr(lst), *[_ptr(t) for t in sel], recs, _stream(dev)))
-        return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel), list(recs)
+        return res, list(recs)
 
     def set_step_streams(self, chain0: Optional["torch.cuda.Stream"], chain1: Optional["torch.cuda.Stream"]):
         """The two chain streams of the pipelined certified steps (m3pc_set_step_streams); None, None: the handle's own."""
@@ -600,13 +616,15 @@ class Handle:
     def plan_step_certified_begin(self, mode: int, states, actions, rewards, eps, expo, horizon: int, rtg: float, lmbda: float,
                                   discount: float, n_total: int, temperature: float, delta: float = 0.0, grow_delta: bool = False,
                                   kmin: int = 8, kmax: int = 128, rfirst: int = 2, rmax: int = 32, precision: int = PREC_BF16,
-                                  slot: int = 0, returns=None, pruned: bool = False, inputs_ready: bool = False):
+                                  slot: int = 0, returns=None, pruned: bool = False, inputs_ready: bool = False,
+                                  eval_tol: Optional[float] = None):
         """The enqueueing half of ``plan_step_certified`` (m3pc_plan_step_certified_begin): arguments as there, on the current
         stream; nothing is read from the device.  Returns the step's ``res`` dict -- the same tensors, complete only behind
         ``plan_step_certified_end(slot)``; it also keeps the inputs alive.  states / actions / rewards / eps / expo must be fp32,
         contiguous and left untouched until the step has been ended.  inputs_ready: the window (states, actions, rewards) is
         complete already in the order of the slot's chain stream (M3PC_PLAN_INPUTS_READY): the policy pass does not wait for the
-        current stream."""
+        current stream.  eval_tol: the call is m3pc_plan_step_certified_eval_begin -- the step carries the eval_action certificate
+        and is resolved by ``plan_step_certified_end(slot, eval=True)``."""
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         loc = torch.empty((self.T, self.A), **f32)
@@ -621,16 +639,27 @@ class Handle:
         cert = CertArgs(float(temperature), float(delta), int(bool(grow_delta)), int(kmin), int(kmax), int(rfirst), int(rmax))
         ins = [self._f32(t) for t in (states, actions, rewards, eps)]
         assert expo.numel() == n_total and expo.dtype == torch.float32 and expo.is_contiguous()
-        check(self.lib.m3pc_plan_step_certified_begin(self._h, C.byref(args), C.byref(cert), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
-                                                      _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low), _ptr(merged),
-                                                      _ptr(lst), *[_ptr(t) for t in sel], _stream(dev)))
+        if eval_tol is not None:
+            check(self.lib.m3pc_plan_step_certified_eval_begin(self._h, C.byref(args), C.byref(cert), _ptr(ins[0]), _ptr(ins[1]),
+                                                               _ptr(ins[2]), _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts),
+                                                               _ptr(low), _ptr(merged), _ptr(lst), *[_ptr(t) for t in sel],
+                                                               float(eval_tol), _stream(dev)))
+        else:
+            check(self.lib.m3pc_plan_step_certified_begin(self._h, C.byref(args), C.byref(cert), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
+                                                          _ptr(ins[3]), _ptr(expo), _ptr(loc), _ptr(std), _ptr(acts), _ptr(low),
+                                                          _ptr(merged), _ptr(lst), *[_ptr(t) for t in sel], _stream(dev)))
         return dict(loc=loc, std=std, sample_actions=acts, expect_return_low=low, expect_return=merged, list=lst, sel=sel,
                     keep=(ins, expo, returns))
 
-    def plan_step_certified_end(self, slot: int) -> "CertRecord":
+    def plan_step_certified_end(self, slot: int, eval: bool = False):
         """Resolve the step begun in ``slot`` (m3pc_plan_step_certified_end): its outputs are complete in the order of the current
-        stream when the call returns; -> the step's ``CertRecord``."""
+        stream when the call returns; -> the step's ``CertRecord``.  eval: m3pc_plan_step_certified_eval_end, for a step begun with
+        an ``eval_tol``; -> (record, eval_record)."""
         rec = CertRecord()
+        if eval:
+            erec = EvalRecord()
+            check(self.lib.m3pc_plan_step_certified_eval_end(self._h, int(slot), C.byref(rec), C.byref(erec), _stream(self.device)))
+            return rec, erec
         check(self.lib.m3pc_plan_step_certified_end(self._h, int(slot), C.byref(rec), _stream(self.device)))
         return rec
 

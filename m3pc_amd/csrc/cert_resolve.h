@@ -1,7 +1,8 @@
 // The certified re-score's protocol (m3pc_amd/certificate.py:resolve) in plain C++: no HIP, standard headers only, so a host
 // compiler builds it alone (tests/cert_resolve_host.cpp drives it with scripted certificates).  The device work comes from an
-// ops object, as in certificate.py; m3pc_certified.hip has the two of the library: a single step (serial, eval, _begin / _end)
-// and a window of a lock-step batch.
+// ops object, as in certificate.py; m3pc_certified.hip has the two of the library: a single step (serial, eval, _begin / _end,
+// _eval_begin / _eval_end) and a window of a lock-step batch.  cert_resolve_eval is the same loop with the eval_action certificate
+// behind it (tests/cert_resolve_eval_host.cpp).
 #pragma once
 #include <string.h>
 
@@ -85,6 +86,66 @@ int cert_resolve(CertState& s, Ops& ops) {
         if (!redo) return 0;
         if (int rc = ops.merge_select()) return rc;
     }
+}
+
+// The third certificate's state (m3pc_eval_record's fields, and the tolerance the ops' bound kernel takes).
+struct EvalState {
+    EvalState() {}
+    explicit EvalState(float eval_tol_) : eval_tol(eval_tol_) {}
+    float eval_tol = 0.f;
+    float eval_bound = 0.f;   // the LAST bound read; 0 once every candidate has an fp32 score
+    int need_eval_first = 0;  // what the FIRST bound asked for
+    int n_eval = 0;           // score entries re-scored because this certificate asked
+    int eval_rounds = 0;      // bounds the loop READ (a speculative launch that is discarded is not one)
+    int eval_certified = 0;
+};
+
+// The loop with the eval_action certificate as a third one (m3pc_plan_step_certified_eval, _eval_end, a window of
+// m3pc_plan_steps_certified_eval): cert_resolve, then the bound; what the bound asks for is re-scored, merged and selected, and
+// every certificate is read again.  One more operation:
+//   eval_read(n_listed, out8)      the eight statistics of the bound kernel behind the LAST merge + select, over the r_done race
+//                                  entries and n_listed score entries of which n_done are re-scored, under delta as it stands
+//                                  (blocks the host until they are there; the ops may hand back a launch they made in advance
+//                                  when nothing it read has changed since)
+// n_done strictly grows from turn to turn, so the loop ends.
+template <class Ops>
+int cert_resolve_eval(CertState& s, Ops& ops, EvalState& e) {
+    for (;;) {
+        if (int rc = cert_resolve(s, ops)) return rc;
+        if (s.everything || s.n_done >= s.N) {  // the select ran on fp32 scores alone
+            e.eval_bound = 0.f;
+            e.eval_certified = 1;
+            return 0;
+        }
+        float e8[8];
+        const int n_listed = s.saturated ? s.n_done : (s.kmax < s.N ? s.kmax : s.N);  // (a window set's list is wholly re-scored)
+        if (int rc = ops.eval_read(n_listed, e8)) return rc;
+        const int need_eval = (int)e8[1];
+        if (++e.eval_rounds == 1) e.need_eval_first = need_eval;
+        e.eval_bound = e8[0];
+        if (need_eval <= s.n_done) {
+            e.eval_certified = 1;
+            return 0;
+        }
+        if (need_eval <= n_listed) {  // score entries [n_done, need_eval), merge + select again, every certificate read again
+            if (int rc = ops.extend(s.n_done, need_eval)) return rc;
+            e.n_eval += need_eval - s.n_done;
+            s.n_done = need_eval;
+            if (int rc = ops.merge_select()) return rc;
+        } else {  // the list cannot reach the tolerance: every candidate in fp32
+            if (int rc = ops.window_set(s.N, true)) return rc;
+            s.everything = true;
+        }
+    }
+}
+// m3pc_eval_record from the state the loop left (a template, as cert_record)
+template <class Rec>
+void cert_eval_record(const EvalState& e, Rec* erec) {
+    erec->eval_bound = e.eval_bound;
+    erec->need_eval_first = e.need_eval_first;
+    erec->n_eval = e.n_eval;
+    erec->eval_rounds = e.eval_rounds;
+    erec->eval_certified = e.eval_certified;
 }
 
 // The step's record (m3pc_cert_record; a template so that this header needs no other) from the state the loop left.  `rounds`

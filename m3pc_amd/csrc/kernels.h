@@ -551,6 +551,27 @@ void launch_deviation_stats(const float* b, const float* f, int n, float* stats,
 //   none), P_U, arg-max k of B_k, -, eps, bound(n_listed), |U|}; host_stats / seq as launch_rescore_merge
 void launch_eval_bound(const float* m, int n_total, const int* list, int r, int n, int n_listed, const float* a0, long long a0_stride,
                        int A, float tau, float delta, float eval_tol, float* stats, float* host_stats, float seq, hipStream_t st);
+// launch_eval_bound per window: window w reads row w of m (stride n_total), the slice of its list row (stride list_stride) from
+// rmax - r[w] on -- r[w] re-scored race entries, then n_listed score entries of which n[w] are re-scored --, its first actions at
+// a0 + w a0_wstride (candidate j: + j a0_stride) and delta[w]; n_listed, tau and eval_tol are shared.  stats / host_stats: 8 floats
+// per window, every host block closed by seq in slot 4, written last.  Window w's eight floats are launch_eval_bound's bit for bit.
+struct EvalBoundBatchP {
+    const float* m;        // (E, n_total) merged
+    int n_total;
+    const int* list;
+    int list_stride, rmax, n_listed;
+    const float* a0;
+    long long a0_wstride, a0_stride;
+    int A;
+    float tau, eval_tol;
+    float* stats;          // (E, 8) device
+    float* host_stats;     // optional (E, 8) host-mapped
+    float seq;
+    int w0;                // (set by the launcher)
+    int r[64], n[64];
+    float delta[64];
+};
+void launch_eval_bound_batch(EvalBoundBatchP& P, int E, const int* r, const int* n, const float* delta, hipStream_t st);
 // counter-based variates (Philox4x32-10 of (seed, step, array, element / 4)): out[0 .. g1 - g0) = elements [g0, g1) of the flat array;
 // array 0 = standard normals (Box-Muller), 1 = Exp(1), never 0
 void launch_variates(unsigned long long seed, unsigned long long step, int array, long long g0, long long g1, float* out, hipStream_t st);

@@ -251,10 +251,11 @@ int m3pc_destroy(m3pc_handle* h) {
     if (h->cert_host) hipHostFree(h->cert_host);
     if (h->eval_host) hipHostFree(h->eval_host);
     {
-        void* lb[] = {h->ls.list, h->ls.b, h->ls.f, h->ls.stats, h->ls.cand, h->ls.fs, h->ls.widx};
+        void* lb[] = {h->ls.list, h->ls.b, h->ls.f, h->ls.stats, h->ls.cand, h->ls.fs, h->ls.widx, h->ls.estats};
         for (void* b : lb)
             if (b) hipFree(b);
         if (h->ls.host) hipHostFree(h->ls.host);
+        if (h->ls.ehost) hipHostFree(h->ls.ehost);
     }
     for (size_t i = 1; i < h->auxs.size(); ++i) {
         hipStreamDestroy(h->auxs[i]);

@@ -1,6 +1,7 @@
-// libm3pc_hip.so -- the certified plan steps of the C ABI (include/m3pc_hip.h): the serial call, the eval certificate, the
-// pipelined _begin / _end pair, the lock-step batch, and m3pc_calibrate_delta.  The protocol itself is cert_resolve.h: ONE loop,
-// driven here by two ops -- a single step (StepOps) and a window of a lock-step batch (LsOps).
+// libm3pc_hip.so -- the certified plan steps of the C ABI (include/m3pc_hip.h): the serial call, the pipelined _begin / _end pair
+// and the lock-step batch, each with and without the eval_action certificate, and m3pc_calibrate_delta.  The protocol itself is
+// cert_resolve.h: ONE loop (cert_resolve; cert_resolve_eval with the third certificate behind it), driven here by two ops -- a
+// single step (StepOps) and a window of a lock-step batch (LsOps).
 #include <atomic>
 #include <chrono>
 
@@ -185,15 +186,26 @@ static int cert_first_pass(m3pc_handle* h, CertStep& S) {
 }
 // The eval_action certificate of m3pc_plan_step_certified_eval behind the step's last merge + select: the re-scored race entries
 // and the listed score entries (kmax of them; behind a window set the list is wholly re-scored), under delta as it stands.
-static int cert_eval_bound(m3pc_handle* h, CertStep& S, int n_listed, float eval_tol, float e8[8]) {
+// Launch and wait are two pieces: a pipelined step launches it in advance (step_enqueue_tail) for r / n / delta of the first pass.
+static int cert_eval_launch(m3pc_handle* h, CertStep& S, int r, int n, int n_listed, float delta, float* seq_out) {
     const int slot = S.a.slot, R = S.c.rmax;
-    float* dstats = h->cert_stats[slot] + 24;
     h->eval_seq[slot] = h->eval_seq[slot] % 1000000 + 1;
-    const float seq = (float)h->eval_seq[slot];
-    CHK(m3pc_eval_bound(h, S.merged, S.a.n_total, cert_L(h, S) + R - S.cs.r_done, S.cs.r_done, S.cs.n_done, n_listed, S.sample_actions,
-                        (long long)S.a.horizon * h->A, h->A, S.c.temperature, (float)S.cs.delta, eval_tol, dstats, h->eval_host_dev + 8 * slot,
-                        seq, S.tail));
-    return cert_wait_blocks(h->eval_host + 8 * slot, dstats, &seq, 1, 8, S.tail, e8);
+    *seq_out = (float)h->eval_seq[slot];
+    return m3pc_eval_bound(h, S.merged, S.a.n_total, cert_L(h, S) + R - r, r, n, n_listed, S.sample_actions, (long long)S.a.horizon * h->A,
+                           h->A, S.c.temperature, delta, S.eval_tol, h->cert_stats[slot] + 24, h->eval_host_dev + 8 * slot, *seq_out, S.tail);
+}
+static int cert_eval_wait(m3pc_handle* h, CertStep& S, float seq, float e8[8]) {
+    const int slot = S.a.slot;
+    return cert_wait_blocks(h->eval_host + 8 * slot, h->cert_stats[slot] + 24, &seq, 1, 8, S.tail, e8);
+}
+// the second host-mapped block of every slot, at the first call that asks for the eval certificate
+static int eval_host_setup(m3pc_handle* h) {
+    if (h->eval_host) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipHostMalloc((void**)&h->eval_host, (size_t)M3PC_SLOTS * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(h->eval_host, 0, (size_t)M3PC_SLOTS * 8 * sizeof(float));
+    HIPCHK(hipHostGetDevicePointer((void**)&h->eval_host_dev, h->eval_host, 0));
+    return 0;
 }
 // the device work of cert_resolve (cert_resolve.h) for one step: certificate.py's _TicketOps
 struct StepOps {
@@ -204,11 +216,24 @@ struct StepOps {
     int extend_race(int lo, int hi) { return cert_rescore(h, S, S.c.rmax - hi, S.c.rmax - lo); }
     int window_set(int need, bool everything) { return cert_window_set(h, S, need, everything); }
     int merge_select() { return cert_merge(h, S, S.cs.n_done, S.cs.r_done, true); }
+    // The bound behind the last merge + select.  A launch made in advance saw r = rfirst, n = kmin and delta as it came in behind the
+    // first merge: it is this launch -- same kernel, same inputs, same bits -- exactly when no further merge has been issued (an
+    // extension, a raised delta that is acted on and a window set all merge again).  Otherwise it is dropped: launch and wait.
+    int eval_read(int n_listed, float* out8) {
+        if (S.spec) {
+            S.spec = false;
+            if (S.rounds == S.spec_rounds && n_listed == S.spec_n_listed && (float)S.cs.delta == S.c.delta)
+                return cert_eval_wait(h, S, S.spec_seq, out8);
+        }
+        float seq;
+        CHK(cert_eval_launch(h, S, S.cs.r_done, S.cs.n_done, n_listed, (float)S.cs.delta, &seq));
+        return cert_eval_wait(h, S, seq, out8);
+    }
 };
-// The certificates of a step whose first pass is enqueued.  eval_tol / erec: the third certificate
-// (m3pc_plan_step_certified_eval); erec == NULL: the two certificates alone, nothing else launched, read or allocated
-static int cert_resolve_step(m3pc_handle* h, CertStep& S, m3pc_cert_record* rec, float eval_tol = 0.f, m3pc_eval_record* erec = nullptr) {
-    const int N = S.a.n_total, R = S.c.rmax, kmax = S.c.kmax;
+// The certificates of a step whose first pass is enqueued.  erec: the third certificate under S.eval_tol (cert_resolve_eval);
+// erec == NULL: the two certificates alone, nothing else launched, read or allocated
+static int cert_resolve_step(m3pc_handle* h, CertStep& S, m3pc_cert_record* rec, m3pc_eval_record* erec = nullptr) {
+    const int N = S.a.n_total;
     if (erec) memset(erec, 0, sizeof(*erec));
     if (S.a.precision == M3PC_PREC_FP32) {
         cert_record_fp32(N, rec);
@@ -216,43 +241,24 @@ static int cert_resolve_step(m3pc_handle* h, CertStep& S, m3pc_cert_record* rec,
         return 0;
     }
     memset(rec, 0, sizeof(*rec));
-    CertState& cs = S.cs;
     StepOps ops{h, S};
-    for (;;) {  // (one turn without erec; with it, a turn per extension the eval certificate asks for)
-        CHK(cert_resolve(cs, ops));
-        if (!erec) break;
-        if (cs.everything || cs.n_done >= N) {  // the select ran on fp32 scores alone
-            erec->eval_bound = 0.f;
-            erec->eval_certified = 1;
-            break;
-        }
-        float e8[8];
-        const int n_listed = cs.saturated ? cs.n_done : (kmax < N ? kmax : N);
-        CHK(cert_eval_bound(h, S, n_listed, eval_tol, e8));
-        const int need_eval = (int)e8[1];
-        if (++erec->eval_rounds == 1) erec->need_eval_first = need_eval;
-        erec->eval_bound = e8[0];
-        if (need_eval <= cs.n_done) {
-            erec->eval_certified = 1;
-            break;
-        }
-        if (need_eval <= n_listed) {  // score entries [n_done, need_eval), merge + select again, every certificate read again
-            CHK(cert_rescore(h, S, R + cs.n_done, R + need_eval));
-            erec->n_eval += need_eval - cs.n_done;
-            cs.n_done = need_eval;
-            CHK(ops.merge_select());
-        } else {  // the list cannot reach the tolerance: every candidate in fp32
-            CHK(cert_window_set(h, S, N, true));
-            cs.everything = true;
-        }
+    if (erec) {
+        EvalState es(S.eval_tol);
+        CHK(cert_resolve_eval(S.cs, ops, es));
+        cert_eval_record(es, erec);
+    } else {
+        CHK(cert_resolve(S.cs, ops));
     }
-    cert_record(cs, rec);
+    cert_record(S.cs, rec);
     rec->rounds = S.rounds;
     return 0;
 }
 static void cert_fill(CertStep& S, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
                       const float* rewards, const float* eps, const float* expo, float* sample_actions, float* scores_low, float* merged,
-                      int* list, float* p, float* eval_action, int* argmax, int* sample_idx, float* sample_action, hipStream_t tail, bool async) {
+                      int* list, float* p, float* eval_action, int* argmax, int* sample_idx, float* sample_action, hipStream_t tail, bool async,
+                      float eval_tol) {
+    S.eval_tol = eval_tol;
+    S.spec = false;
     S.a = *a;
     S.c = *c;
     S.states = states;
@@ -289,16 +295,11 @@ static int cert_step_serial(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_
     memset(rec, 0, sizeof(*rec));
     if (with_eval) {
         memset(erec, 0, sizeof(*erec));
-        if (!h->eval_host && a->precision != M3PC_PREC_FP32) {  // the second host-mapped block of every slot, at the first such call
-            HIPCHK(hipSetDevice(h->device));
-            HIPCHK(hipHostMalloc((void**)&h->eval_host, (size_t)M3PC_SLOTS * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-            memset(h->eval_host, 0, (size_t)M3PC_SLOTS * 8 * sizeof(float));
-            HIPCHK(hipHostGetDevicePointer((void**)&h->eval_host_dev, h->eval_host, 0));
-        }
+        if (a->precision != M3PC_PREC_FP32) CHK(eval_host_setup(h));
     }
     CertStep& S = h->cstep[a->slot];
     cert_fill(S, a, c, states, actions, rewards, eps, expo, sample_actions, scores_low, merged, list, p, eval_action, argmax, sample_idx,
-              sample_action, (hipStream_t)stream, false);
+              sample_action, (hipStream_t)stream, false, with_eval ? eval_tol : 0.f);
 
     // learner.py:278-316: policy pass (fp32), candidates, candidate pass in args->precision
     m3pc_plan_args pa = *a;
@@ -308,7 +309,7 @@ static int cert_step_serial(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_
     pa.flags = 0;
     CHK(m3pc_candidate_pass(h, &pa, states, actions, rewards, eps, loc, std_, sample_actions, scores_low, nullptr, nullptr, stream));
     CHK(cert_first_pass(h, S));
-    return cert_resolve_step(h, S, rec, eval_tol, with_eval ? erec : nullptr);
+    return cert_resolve_step(h, S, rec, with_eval ? erec : nullptr);
 }
 
 int m3pc_plan_step_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
@@ -368,22 +369,34 @@ static int step_enqueue_tail(m3pc_handle* h, int slot) {
     CHK(m3pc_candidate_join(h, slot, S.tail));
     S.tail_pending = false;
     CHK(cert_first_pass(h, S));
+    if (S.eval_tol > 0.f && S.a.precision != M3PC_PREC_FP32) {
+        // _eval_begin: the bound goes out right behind the first pass, for the state that pass assumes; _eval_end takes its
+        // statistics when the two certificates are satisfied at their first read (StepOps::eval_read), without a second wait
+        const int N = S.a.n_total;
+        S.spec_n_listed = S.c.kmax < N ? S.c.kmax : N;
+        CHK(cert_eval_launch(h, S, S.c.rfirst, S.c.kmin, S.spec_n_listed, S.c.delta, &S.spec_seq));
+        S.spec_rounds = S.rounds;
+        S.spec = true;
+    }
     HIPCHK(hipEventRecord(h->step_ev[slot][3], S.tail));
     return 0;
 }
 
-int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states,
-                                   const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std_,
-                                   float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
-                                   int* argmax, int* sample_idx, float* sample_action, void* stream) {
+// _begin; with_eval: m3pc_plan_step_certified_eval_begin (eval_tol)
+static int cert_step_begin(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states, const float* actions,
+                           const float* rewards, const float* eps, const float* expo, float* loc, float* std_, float* sample_actions,
+                           float* scores_low, float* merged, int* list, float* p, float* eval_action, int* argmax, int* sample_idx,
+                           float* sample_action, bool with_eval, float eval_tol, void* stream, const char* who) {
     if (!h || !a || !c || !states || !actions || !rewards || !eps || !expo || !sample_actions || !scores_low || !merged)
         return fail(M3PC_EINVAL, "null argument");
-    CHK(cert_check_step(a, c, "m3pc_plan_step_certified_begin"));
+    CHK(cert_check_step(a, c, who));
+    if (with_eval && !(eval_tol > 0.f)) return fail(M3PC_EINVAL, "%s: eval_tol must be > 0 (+inf: report only)", who);
     const int slot = a->slot;
     CertStep& S = h->cstep[slot];
-    if (S.begun) return fail(M3PC_ESTATE, "m3pc_plan_step_certified_begin: the step in slot %d has not been ended", slot);
+    if (S.begun) return fail(M3PC_ESTATE, "%s: the step in slot %d has not been ended", who, slot);
     HIPCHK(hipSetDevice(h->device));
     CHK(step_setup(h));
+    if (with_eval && a->precision != M3PC_PREC_FP32) CHK(eval_host_setup(h));
     hipStream_t st = (hipStream_t)stream, chain = h->step_chain[slot & 1];
     hipEvent_t* ev = h->step_ev[slot];
     // the window is complete in `stream` order: the chain stream reads it behind ev_in (M3PC_PLAN_INPUTS_READY: complete already)
@@ -415,26 +428,51 @@ int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* a, cons
     HIPCHK(hipEventRecord(ev[2], st));
     h->cand_last_slot = slot;
     cert_fill(S, a, c, states, actions, rewards, eps, expo, sample_actions, scores_low, merged, list, p, eval_action, argmax, sample_idx,
-              sample_action, chain, true);
+              sample_action, chain, true, with_eval ? eval_tol : 0.f);
     S.tail_pending = true;
     S.begun = true;
     S.order = ++h->step_order;
     return 0;
 }
+int m3pc_plan_step_certified_begin(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states,
+                                   const float* actions, const float* rewards, const float* eps, const float* expo, float* loc, float* std_,
+                                   float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
+                                   int* argmax, int* sample_idx, float* sample_action, void* stream) {
+    return cert_step_begin(h, a, c, states, actions, rewards, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p, eval_action,
+                           argmax, sample_idx, sample_action, false, 0.f, stream, "m3pc_plan_step_certified_begin");
+}
+int m3pc_plan_step_certified_eval_begin(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, const float* states,
+                                        const float* actions, const float* rewards, const float* eps, const float* expo, float* loc,
+                                        float* std_, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
+                                        float* eval_action, int* argmax, int* sample_idx, float* sample_action, float eval_tol,
+                                        void* stream) {
+    return cert_step_begin(h, a, c, states, actions, rewards, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p, eval_action,
+                           argmax, sample_idx, sample_action, true, eval_tol, stream, "m3pc_plan_step_certified_eval_begin");
+}
 
-int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* rec, void* stream) {
-    if (!h || !rec) return fail(M3PC_EINVAL, "null argument");
+// _end; erec: m3pc_plan_step_certified_eval_end -- the step must have been begun with _eval_begin (it carries the tolerance)
+static int cert_step_end(m3pc_handle* h, int slot, m3pc_cert_record* rec, bool with_eval, m3pc_eval_record* erec, void* stream,
+                         const char* who) {
+    if (!h || !rec || (with_eval && !erec)) return fail(M3PC_EINVAL, "null argument");
     if (slot < 0 || slot >= M3PC_SLOTS) return fail(M3PC_EINVAL, "slot %d outside [0, %d)", slot, M3PC_SLOTS);
     CertStep& S = h->cstep[slot];
-    if (!S.begun) return fail(M3PC_ESTATE, "m3pc_plan_step_certified_end: no step begun in slot %d", slot);
+    if (!S.begun) return fail(M3PC_ESTATE, "%s: no step begun in slot %d", who, slot);
+    if (with_eval && !(S.eval_tol > 0.f))
+        return fail(M3PC_ESTATE, "%s: the step in slot %d was begun without an eval_tol (m3pc_plan_step_certified_end resolves it)", who, slot);
     HIPCHK(hipSetDevice(h->device));
     S.begun = false;  // (whatever happens below, the slot is free again)
     if (S.tail_pending) CHK(step_enqueue_tail(h, slot));
     const int rounds = S.rounds;
-    CHK(cert_resolve_step(h, S, rec));
+    CHK(cert_resolve_step(h, S, rec, with_eval ? erec : nullptr));
     if (S.rounds != rounds) HIPCHK(hipEventRecord(h->step_ev[slot][3], S.tail));
     HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->step_ev[slot][3], 0));
     return 0;
+}
+int m3pc_plan_step_certified_end(m3pc_handle* h, int slot, m3pc_cert_record* rec, void* stream) {
+    return cert_step_end(h, slot, rec, false, nullptr, stream, "m3pc_plan_step_certified_end");
+}
+int m3pc_plan_step_certified_eval_end(m3pc_handle* h, int slot, m3pc_cert_record* rec, m3pc_eval_record* erec, void* stream) {
+    return cert_step_end(h, slot, rec, true, erec, stream, "m3pc_plan_step_certified_eval_end");
 }
 
 // ---- a lock-step batch of certified plan steps as one call (include/m3pc_hip.h: m3pc_plan_steps_certified): the order of
@@ -457,6 +495,13 @@ static int ls_setup(m3pc_handle* h) {
         HIPCHK(hipHostMalloc((void**)&W.host, E * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
         memset(W.host, 0, E * 8 * sizeof(float));
         HIPCHK(hipHostGetDevicePointer((void**)&W.host_dev, W.host, 0));
+    }
+    // (the eval_action certificate of m3pc_plan_steps_certified_eval: eight statistics per window, device and host-mapped)
+    if (!W.estats) CHK(dmalloc(&W.estats, E * 8));
+    if (!W.ehost) {
+        HIPCHK(hipHostMalloc((void**)&W.ehost, E * 8 * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+        memset(W.ehost, 0, E * 8 * sizeof(float));
+        HIPCHK(hipHostGetDevicePointer((void**)&W.ehost_dev, W.ehost, 0));
     }
     W.seq_w.assign(E, 0.f);
     W.ready = true;
@@ -483,6 +528,11 @@ struct LsOps {
     int w;
     bool have;  // first + 8 w are still the statistics of the window's last merge
     CertState cs;
+    // m3pc_plan_steps_certified_eval: the tolerance, and whether the window's block of the batched bound launch (r = rfirst,
+    // n = kmin, n_listed = spec_n_listed, delta = spec_delta, closed by spec_seq) may still stand for the window's bound
+    float eval_tol = 0.f, spec_delta = 0.f, spec_seq = 0.f;
+    int spec_n_listed = 0;
+    bool spec = false;
 
     int* Lw() const { return L + (size_t)w * LS; }
     float* Bw() const { return B + (size_t)w * LS; }
@@ -517,6 +567,23 @@ struct LsOps {
         }
         Lockstep& W = h->ls;
         return cert_wait_blocks(W.host + 8 * w, W.stats + 8 * w, &W.seq_w[w], 1, four_only ? 4 : 8, st, out8);
+    }
+    // The bound behind the window's last merge + select.  The batched launch behind the batched merge is that launch exactly when
+    // the window has issued no merge of its own (an earlier window's raised delta makes it merge again first); otherwise the
+    // one-window kernel behind its last merge, and a wait.
+    int eval_read(int n_listed, float* out8) {
+        Lockstep& W = h->ls;
+        float seq = spec_seq;
+        const bool take = spec && records[w].rounds == 1 && n_listed == spec_n_listed && (float)cs.delta == spec_delta;
+        spec = false;
+        if (!take) {
+            W.eseq = W.eseq % 1000000 + 1;
+            seq = (float)W.eseq;
+            const int r = cs.r_done;
+            CHK(m3pc_eval_bound(h, mw(), N, Lw() + R - r, r, cs.n_done, n_listed, sample_actions + w * N * row, row, h->A, temp, (float)cs.delta,
+                                eval_tol, W.estats + 8 * (size_t)w, W.ehost_dev + 8 * (size_t)w, seq, st));
+        }
+        return cert_wait_blocks(W.ehost + 8 * w, W.estats + 8 * w, &seq, 1, 8, st, out8);
     }
     int extend(int lo, int hi) { return rescore(R + lo, R + hi); }
     int extend_race(int lo, int hi) { return rescore(R - hi, R - lo); }
@@ -560,14 +627,16 @@ struct LsOps {
     }
 };
 
-int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, int n_windows, const float* states,
-                              const float* actions, const float* rewards, const double* rtg, const float* eps, const float* expo,
-                              float* loc, float* std_, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
-                              float* eval_action, int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* records,
-                              void* stream) {
-    static const char* who = "m3pc_plan_steps_certified";
-    if (!h || !a || !c || !states || !actions || !rewards || !rtg || !eps || !expo || !sample_actions || !scores_low || !merged || !records)
+// the lock-step batch; with_eval: m3pc_plan_steps_certified_eval (eval_tol, erecs)
+static int ls_steps(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, int n_windows, const float* states,
+                    const float* actions, const float* rewards, const double* rtg, const float* eps, const float* expo, float* loc,
+                    float* std_, float* sample_actions, float* scores_low, float* merged, int* list, float* p, float* eval_action,
+                    int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* records, bool with_eval, float eval_tol,
+                    m3pc_eval_record* erecs, void* stream, const char* who) {
+    if (!h || !a || !c || !states || !actions || !rewards || !rtg || !eps || !expo || !sample_actions || !scores_low || !merged || !records ||
+        (with_eval && !erecs))
         return fail(M3PC_EINVAL, "null argument");
+    if (with_eval && !(eval_tol > 0.f)) return fail(M3PC_EINVAL, "%s: eval_tol must be > 0 (+inf: report only)", who);
     if (n_windows < 1) return fail(M3PC_EINVAL, "%s: n_windows %d < 1", who, n_windows);
     if (a->returns) return fail(M3PC_EINVAL, "%s takes rtg per window, not a returns row (args->returns must be NULL)", who);
     CHK(cert_check_step(a, c, who));
@@ -591,6 +660,7 @@ int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3p
     const long long row = (long long)hz * A, eps_w = (long long)N * (a->mode == M3PC_MODE_NOISE ? hz : T) * A;
     const float temp = c->temperature;
     memset(records, 0, (size_t)E * sizeof(*records));
+    if (with_eval) memset(erecs, 0, (size_t)E * sizeof(*erecs));
 
     // lockstep.py:57-62: ONE policy pass at batch E, every window's own candidate pass back to back, one join
     m3pc_plan_args pa = *a;
@@ -623,7 +693,10 @@ int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3p
         HIPCHK(hipMemcpyAsync(merged, scores_low, (size_t)E * N * sizeof(float), hipMemcpyDeviceToDevice, st));
         sel.er = scores_low;
         launch_select_batch(sel, E, N, N * row, st);
-        for (int w = 0; w < E; ++w) cert_record_fp32(N, records + w);
+        for (int w = 0; w < E; ++w) {
+            cert_record_fp32(N, records + w);
+            if (with_eval) erecs[w].eval_certified = 1;
+        }
         return check_launch(who);
     }
 
@@ -706,6 +779,31 @@ int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3p
     P.sample_idx = sample_idx;
     P.sample_action = sample_action;
     launch_merge_select_batch(P, E, r_done.data(), n_done.data(), d0.data(), st);
+    O.eval_tol = eval_tol;
+    if (with_eval) {
+        // the bound of every window behind the batched merge, for the state it assumes: a window whose certificates are satisfied
+        // at their first read takes its block (LsOps::eval_read) -- no launch and, as a rule, no wait of its own
+        EvalBoundBatchP Q;
+        memset(&Q, 0, sizeof(Q));
+        Q.m = merged;
+        Q.n_total = N;
+        Q.list = L;
+        Q.list_stride = LS;
+        Q.rmax = R;
+        Q.n_listed = O.spec_n_listed = kmax < N ? kmax : N;
+        Q.a0 = sample_actions;
+        Q.a0_wstride = N * row;
+        Q.a0_stride = row;
+        Q.A = A;
+        Q.tau = temp;
+        Q.eval_tol = eval_tol;
+        Q.stats = W.estats;
+        Q.host_stats = W.ehost_dev;
+        W.eseq = W.eseq % 1000000 + 1;
+        Q.seq = O.spec_seq = (float)W.eseq;
+        O.spec_delta = c->delta;
+        launch_eval_bound_batch(Q, E, r_done.data(), n_done.data(), d0.data(), st);
+    }
     for (int w = 0; w < E; ++w) {
         W.seq_w[w] = seq0;
         records[w].rounds = 1;
@@ -728,11 +826,34 @@ int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3p
             CHK(O.merge_select());
             O.have = false;
         }
-        CHK(cert_resolve(O.cs, O));
+        if (with_eval) {
+            O.spec = true;
+            EvalState es(eval_tol);
+            CHK(cert_resolve_eval(O.cs, O, es));
+            cert_eval_record(es, erecs + w);
+        } else {
+            CHK(cert_resolve(O.cs, O));
+        }
         delta = O.cs.delta;
         cert_record(O.cs, records + w);
     }
     return 0;
+}
+int m3pc_plan_steps_certified(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, int n_windows, const float* states,
+                              const float* actions, const float* rewards, const double* rtg, const float* eps, const float* expo,
+                              float* loc, float* std_, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
+                              float* eval_action, int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* records,
+                              void* stream) {
+    return ls_steps(h, a, c, n_windows, states, actions, rewards, rtg, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p,
+                    eval_action, argmax, sample_idx, sample_action, records, false, 0.f, nullptr, stream, "m3pc_plan_steps_certified");
+}
+int m3pc_plan_steps_certified_eval(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_cert_args* c, int n_windows, const float* states,
+                                   const float* actions, const float* rewards, const double* rtg, const float* eps, const float* expo,
+                                   float* loc, float* std_, float* sample_actions, float* scores_low, float* merged, int* list, float* p,
+                                   float* eval_action, int* argmax, int* sample_idx, float* sample_action, m3pc_cert_record* records,
+                                   float eval_tol, m3pc_eval_record* erecs, void* stream) {
+    return ls_steps(h, a, c, n_windows, states, actions, rewards, rtg, eps, expo, loc, std_, sample_actions, scores_low, merged, list, p,
+                    eval_action, argmax, sample_idx, sample_action, records, true, eval_tol, erecs, stream, "m3pc_plan_steps_certified_eval");
 }
 
 // HipPlanner._calibrate as a call: delta from ONE full fp32 candidate pass over the step's candidates

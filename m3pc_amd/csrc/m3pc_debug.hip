@@ -314,6 +314,42 @@ int m3pc_debug_merge_select_batch(const m3pc_debug_tail_args* a) {
     launch_merge_select_batch(P, a->n_windows, a->r, a->n, a->delta, (hipStream_t)a->stream);
     return check_launch("debug_merge_select_batch");
 }
+// the eval_action certificate of n_windows windows in one launch (eval_bound_batch_kernel): m3pc_eval_bound's checks, per window
+int m3pc_debug_eval_bound_batch(const m3pc_debug_eval_batch_args* a) {
+    if (!a || !a->merged || !a->list || !a->a0 || !a->stats || !a->r || !a->n || !a->delta) return fail(M3PC_EINVAL, "null argument");
+    if (!(a->eval_tol > 0.f)) return fail(M3PC_EINVAL, "eval_tol must be > 0 (+inf: report only)");
+    if (a->n_windows < 1 || a->n_windows > 65535) return fail(M3PC_EINVAL, "n_windows %d outside [1, 65535]", a->n_windows);
+    if (a->n_total < 1 || a->n_total > 16384) return fail(M3PC_EINVAL, "n_total %d outside [1, 16384]", a->n_total);
+    if (a->A < 1 || a->A > 1024) return fail(M3PC_EINVAL, "A %d outside [1, 1024]", a->A);
+    if (a->rmax < 0 || a->rmax > 64 || a->n_listed < 0 || a->rmax + a->n_listed > 1024 || a->rmax + a->n_listed > a->list_stride)
+        return fail(M3PC_EINVAL, "rmax %d + n_listed %d outside [0, min(1024, list_stride=%d)]", a->rmax, a->n_listed, a->list_stride);
+    if (!(a->temperature == a->temperature)) return fail(M3PC_EINVAL, "temperature is not a number");
+    for (int w = 0; w < a->n_windows; ++w) {
+        if (a->r[w] < 0 || a->r[w] > a->rmax || a->n[w] < 0 || a->n[w] > a->n_listed)
+            return fail(M3PC_EINVAL, "window %d: r %d outside [0, rmax=%d] or n %d outside [0, n_listed=%d]", w, a->r[w], a->rmax, a->n[w],
+                        a->n_listed);
+        if (!(a->delta[w] >= 0.f)) return fail(M3PC_EINVAL, "delta must be >= 0");
+    }
+    EvalBoundBatchP P;
+    memset(&P, 0, sizeof(P));
+    P.m = a->merged;
+    P.n_total = a->n_total;
+    P.list = a->list;
+    P.list_stride = a->list_stride;
+    P.rmax = a->rmax;
+    P.n_listed = a->n_listed;
+    P.a0 = a->a0;
+    P.a0_wstride = a->a0_window_stride;
+    P.a0_stride = a->a0_stride;
+    P.A = a->A;
+    P.tau = a->temperature;
+    P.eval_tol = a->eval_tol;
+    P.stats = a->stats;
+    P.host_stats = a->host_stats;
+    P.seq = a->seq;
+    launch_eval_bound_batch(P, a->n_windows, a->r, a->n, a->delta, (hipStream_t)a->stream);
+    return check_launch("debug_eval_bound_batch");
+}
 // the select of n_windows windows in one launch (the fp32 form of m3pc_plan_steps_certified): m3pc_select's checks, per window
 int m3pc_debug_select_batch(const float* scores, const float* a0, long long a0_window_stride, long long a0_stride, int n_windows,
                             int n_total, int A, float temperature, const float* expo, float* p, float* eval_action, int* argmax,

@@ -182,6 +182,13 @@ struct m3pc_handle {
         CertState cs;    // the protocol's state (cert_resolve.h): n_done, r_done, delta, ...
         int rounds = 0;  // merges issued
         float seq = 0.f;
+        // the eval_action certificate: eval_tol > 0 for a step of m3pc_plan_step_certified_eval / _eval_begin.  spec: a bound kernel
+        // was enqueued behind the first pass for the state that pass assumes (r = rfirst, n = kmin, delta as it came in); its
+        // statistics are the step's bound as long as no further merge has been issued (rounds == spec_rounds)
+        float eval_tol = 0.f;
+        bool spec = false;
+        int spec_rounds = 0, spec_n_listed = 0;
+        float spec_seq = 0.f;
     } cstep[M3PC_SLOTS];
     // m3pc_plan_steps_certified (a lock-step batch of certified steps): what a certified step keeps per slot, per WINDOW of the
     // batch, sized by max_batch and allocated at the first call.  list / b / f: rows of rmax + 1024 entries (ids when the caller
@@ -199,6 +206,10 @@ struct m3pc_handle {
         long long cand_rows = 0;
         int seq = 0;
         std::vector<float> seq_w;
+        // m3pc_plan_steps_certified_eval: per window the eight statistics of the eval_action certificate (device copy, and a second
+        // host-mapped block closed by a sequence number of a counter of its own)
+        float *estats = nullptr, *ehost = nullptr, *ehost_dev = nullptr;
+        int eseq = 0;
     } ls;
     // Pipelined certified steps: the two chain streams (slot parity; the caller's pair of m3pc_set_step_streams or the handle's
     // own, created at the first _begin), the events of a slot, and the order of the candidate workspace across steps:

@@ -802,14 +802,13 @@ __device__ __forceinline__ float block_prefix_sum(float v, float* sv) {
 __device__ __forceinline__ float eval_bound_of(float em1, float emeps, float S, float PL, float PU) {
     return S > 0.f ? em1 * S / (PL + emeps * PU) : 0.f;
 }
-__global__ __launch_bounds__(1024) void eval_bound_kernel(const float* m, int n_total, const int* list, int r, int n, int n_listed,
-                                                           const float* a0, long long a0_stride, int A, float tau, float delta,
-                                                           float eval_tol, float* stats, float* host_stats, float seq) {
-    __shared__ unsigned short pos[16384];
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    __shared__ float at_n[2];
-    __shared__ int at_n_k;
+// (pos: 16384 entries, sv / si: 16, at_n: 2 floats, at_n_k: one int -- the LDS of the kernel that calls it, so that the one-window
+// and the batched kernel run the same expressions in the same order)
+__device__ __forceinline__ void eval_bound_body(const float* m, int n_total, const int* list, int r, int n, int n_listed, const float* a0,
+                                                long long a0_stride, int A, float tau, float delta, float eval_tol, float* stats,
+                                                float* host_stats, float seq, unsigned short* pos, float* sv, int* si, float* at_n,
+                                                int* at_n_k_p) {
+    int& at_n_k = *at_n_k_p;
     constexpr unsigned short UNLISTED = 0xffffu, RESCORED = 0xfffeu;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     for (int j = tid; j < n_total; j += 1024) pos[j] = UNLISTED;
@@ -921,11 +920,53 @@ __global__ __launch_bounds__(1024) void eval_bound_kernel(const float* m, int n_
         }
     }
 }
+__global__ __launch_bounds__(1024) void eval_bound_kernel(const float* m, int n_total, const int* list, int r, int n, int n_listed,
+                                                           const float* a0, long long a0_stride, int A, float tau, float delta,
+                                                           float eval_tol, float* stats, float* host_stats, float seq) {
+    __shared__ unsigned short pos[16384];
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ float at_n[2];
+    __shared__ int at_n_k;
+    eval_bound_body(m, n_total, list, r, n, n_listed, a0, a0_stride, A, tau, delta, eval_tol, stats, host_stats, seq, pos, sv, si, at_n,
+                    &at_n_k);
+}
 void launch_eval_bound(const float* m, int n_total, const int* list, int r, int n, int n_listed, const float* a0, long long a0_stride,
                        int A, float tau, float delta, float eval_tol, float* stats, float* host_stats, float seq, hipStream_t st) {
     if (n_total <= 0 || n_total > 16384 || r < 0 || n < 0 || n > n_listed || r + n_listed > 1024) return;
     hipLaunchKernelGGL(eval_bound_kernel, dim3(1), dim3(1024), 0, st, m, n_total, list, r, n, n_listed, a0, a0_stride, A, tau, delta,
                        eval_tol, stats, host_stats, seq);
+}
+// launch_eval_bound for up to 64 windows in one launch: workgroup i is window w0 + i with its own r / n / delta, row w of the merged
+// vectors, the slice of its list from rmax - r on, its first actions and its block of 8 statistics -- the body is the one-window
+// kernel's, so the eight floats are its bit for bit.  The pos table is per workgroup: the LDS of the one-window kernel.
+__global__ __launch_bounds__(1024) void eval_bound_batch_kernel(EvalBoundBatchP P) {
+    __shared__ unsigned short pos[16384];
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ float at_n[2];
+    __shared__ int at_n_k;
+    const int i = blockIdx.x;
+    const long long w = P.w0 + i;
+    const int r = P.r[i];
+    eval_bound_body(P.m + w * P.n_total, P.n_total, P.list + w * P.list_stride + (P.rmax - r), r, P.n[i], P.n_listed,
+                    P.a0 + w * P.a0_wstride, P.a0_stride, P.A, P.tau, P.delta[i], P.eval_tol, P.stats + 8 * w,
+                    P.host_stats ? P.host_stats + 8 * w : nullptr, P.seq, pos, sv, si, at_n, &at_n_k);
+}
+void launch_eval_bound_batch(EvalBoundBatchP& P, int E, const int* r, const int* n, const float* delta, hipStream_t st) {
+    if (P.n_total <= 0 || P.n_total > 16384) return;
+    for (int w = 0; w < E; ++w)  // (the one-window launcher's bounds, for every window, before anything is launched)
+        if (r[w] < 0 || r[w] > P.rmax || n[w] < 0 || n[w] > P.n_listed || r[w] + P.n_listed > 1024) return;
+    for (int w0 = 0; w0 < E; w0 += 64) {  // (per-window scalars travel in the kernel arguments: 64 windows per launch)
+        const int e = E - w0 < 64 ? E - w0 : 64;
+        P.w0 = w0;
+        for (int i = 0; i < e; ++i) {
+            P.r[i] = r[w0 + i];
+            P.n[i] = n[w0 + i];
+            P.delta[i] = delta[w0 + i];
+        }
+        hipLaunchKernelGGL(eval_bound_batch_kernel, dim3(e), dim3(1024), 0, st, P);
+    }
 }
 
 __global__ void scatter_kernel(const float* src, const int* index, int n, float* dst, int* index_copy) {

@@ -55,7 +55,12 @@ class LockstepMixin:
             eps = self._eps((Eg, N, h, A)) if mode == capi.MODE_NOISE else self._eps((Eg, N, T, A))
             # lockstep="native": the whole group in ONE library call (m3pc_plan_steps_certified).  While the weight load's
             # calibration windows are not used up the group takes the Python path below -- that path is what calibrates
-            if native and not (self.rescore == "bound" and self._delta_fixed is None and (self._delta0 is None or self._cal_left > 0)):
+            calibrating = self.rescore == "bound" and self._delta_fixed is None and (self._delta0 is None or self._cal_left > 0)
+            if native and calibrating and self._eval_tol is not None:
+                # (the eval_action certificate has no Python form to fall back to: calibrate on the group's own passes, then the call)
+                self._calibrate_group(mode, s, a, r, [meta[i][1] for i in ids], eps, h, lmbda)
+                calibrating = False
+            if native and not calibrating:
                 self._native_group(mode, s, a, r, [meta[i][1] for i in ids], eps, h, lmbda, ids, eval, out, info)
                 continue
             if onepass:
@@ -165,6 +170,30 @@ class LockstepMixin:
         self.last = dict(windows=info, delta=self._delta)
         return out
 
+    def _calibrate_group(self, mode, s, a, r, rtgs, eps, h, lmbda):
+        """The calibration of the Python path on a group's windows, alone: the group's policy pass and candidate passes in the
+        planner's precision, every candidate of the first windows in fp32, the bound folded into ``_delta0``.  No variate is drawn."""
+        cfg = self.cfg
+        Eg, N, T, A = s.shape[0], int(cfg.action_samples), self.T, self.A
+        f32 = dict(dtype=torch.float32, device=self.device)
+        res = dict(expect_return=torch.empty((Eg, N), **f32), sample_actions=torch.empty((Eg, N, h, A), **f32),
+                   loc=torch.empty((Eg, T, A), **f32), std=torch.empty((Eg, T, A), **f32))
+        self.handle.policy_pass_batch(mode, s, a, r, h, rtgs, slot=0)
+        n_cal = max(1, min(Eg, self._cal_left))
+        for w in range(n_cal):
+            self.handle.candidate_pass(mode, s[w], a[w], r[w], eps[w], h, lmbda, float(cfg.discount), N, precision=self.precision,
+                                       slot=0, window=w, defer_join=True, out={k: v[w] for k, v in res.items()})
+        self.handle.candidate_join(0)
+        smode = capi.MODE_RTG if mode == capi.MODE_RTG else capi.MODE_CRITIC
+        d0 = self._delta0 or 0.0
+        for w in range(n_cal):
+            er = res["expect_return"][w]
+            f = self.handle.score_actions(smode, s[w], a[w], r[w], res["sample_actions"][w], None, h, lmbda, float(cfg.discount))
+            d = er - f
+            d0 = max(d0, self.calibration_factor * float((d - d.median()).abs().max()), 1e-6 * float(f.abs().max()), 1e-30)
+        self._delta0 = d0
+        self._cal_left = max(0, self._cal_left - n_cal)
+
     def _native_group(self, mode, s, a, r, rtgs, eps, h, lmbda, ids, eval, out, info):
         """One group of a lock-step batch through m3pc_plan_steps_certified: the draws, the first-pass sizes and the bound are
         those of the Python path above; ``info`` and the bound are filled from the windows' records.  Two things are the
@@ -187,11 +216,13 @@ class LockstepMixin:
             rfirst = max(min(self.race_min, R), 1) if R > 0 else 0
             kmin = max(min(self.rescore_min - rfirst, N, kmax), 1)
             delta = float(self._delta)
-        res, recs = self.handle.plan_steps_certified(mode, s, a, r, rtgs, eps, expo, h, lmbda, float(cfg.discount), N,
-                                                     float(cfg.temperature), delta=delta,
-                                                     grow_delta=bound and self._delta_fixed is None, kmin=kmin, kmax=kmax,
-                                                     rfirst=rfirst, rmax=R, precision=self.precision, slot=0, want_policy=False,
-                                                     want_list=False, want_p=False)
+        got = self.handle.plan_steps_certified(mode, s, a, r, rtgs, eps, expo, h, lmbda, float(cfg.discount), N,
+                                               float(cfg.temperature), delta=delta,
+                                               grow_delta=bound and self._delta_fixed is None, kmin=kmin, kmax=kmax,
+                                               rfirst=rfirst, rmax=R, precision=self.precision, slot=0, want_policy=False,
+                                               want_list=False, want_p=False, eval_tol=self._eval_tol)
+        res, recs = got[0], got[1]
+        erecs = got[2] if len(got) > 2 else None  # (eval_tol: m3pc_plan_steps_certified_eval)
         if bound:
             seen = float(np.float32(delta))
             for rec in recs:  # (a window that raised the bound raised it for every later window of the group)
@@ -214,4 +245,9 @@ class LockstepMixin:
                            n_rescored=None if rec is None else int(rec.n_rescored), n_race=None if rec is None else int(rec.n_race),
                            min_margin_outside=None if rec is None else float(rec.margin),
                            saturated=None if rec is None else bool(rec.saturated), delta=self._delta)
+            if erecs is not None:
+                e = erecs[j]
+                info[i].update(eval_bound=float(e.eval_bound), need_eval_first=int(e.need_eval_first), n_eval=int(e.n_eval),
+                               eval_rounds=int(e.eval_rounds), eval_certified=bool(e.eval_certified),
+                               everything=bool(recs[j].everything))
 

@@ -106,6 +106,7 @@ class PlanTicket:
         self.tail_enqueued = False
         self.deferred = False
         self.native = False  # issued through m3pc_plan_step_certified_begin: resolved by m3pc_plan_step_certified_end
+        self.eval_tol = None  # issued through m3pc_plan_step_certified_eval_begin: resolved by m3pc_plan_step_certified_eval_end
         self.kmin = self.kmax = self.n_done = self.r_done = self.index = 0
         self.grow_in, self.kfirst_in, self.rfirst_in = 0.0, 0, 0
         self.lst, self.R, self.wset = None, 0, None
@@ -194,7 +195,8 @@ class HipPlanner(GoalMixin, LockstepMixin):
           bf16 cannot reach 1e-3 through its list, nor at config 3's N = 4096 critic shape: the tier to ask for is "bf16x3" (6e-5 /
           3e-5 as it stands).  Needs native_step=True, one rank and rescore="bound" (ValueError otherwise).  ``plan_async``
           on such a planner runs the serial call and returns a resolved ticket (the route of calibration steps);
-          ``action_sample_batch(lockstep=...)`` raises ValueError: there is no lock-step form of this certificate.
+          ``plan_async`` keeps its pipeline (m3pc_plan_step_certified_eval_begin / _eval_end); ``action_sample_batch(lockstep="native")``
+          runs m3pc_plan_steps_certified_eval; the Python lock-step forms (``lockstep=True`` / ``"onepass"``) raise ValueError.
         variates: "torch" (default) draws a plan step's normals and exponentials from ``generator``; "library" draws them with
           m3pc_draw_variates -- the library's counter-based generator on (``seed``, the planner's step index), what a host
           without torch gets -- on the same stream.  Not torch's stream of numbers: goldens recorded on one do not hold on the other.
@@ -541,7 +543,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
             self._maybe_fall_back_to_fp32()
         if not pipelined:
             self._drain()  # a serial step runs its fp32 chains on the current stream: nothing pipelined may still be using them
-        if self._eval_tol is not None:  # the eval_action certificate exists in the serial one-call step only
+        if self._eval_tol is not None:  # the eval_action certificate: a library step, serial (one call) or pipelined (_eval_begin / _eval_end)
             if pipelined:
                 return self._issue_native_async(mode, states, actions, rewards, rtg, h, lmbda, eps, returns, slot, inputs_ready)
             return self._issue_native(mode, states, actions, rewards, rtg, h, lmbda, eps, returns, slot=slot)
@@ -695,7 +697,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                 del self._hist[i]
         if erec is not None:  # (m3pc_plan_step_certified_eval; an fp32 step: bound 0, certified)
             extra.update(eval_bound=float(erec.eval_bound), need_eval_first=int(erec.need_eval_first), n_eval=int(erec.n_eval),
-                         eval_rounds=int(erec.eval_rounds), eval_certified=bool(erec.eval_certified))
+                         eval_rounds=int(erec.eval_rounds), eval_certified=bool(erec.eval_certified), everything=bool(rec.everything))
         p, eval_action, argmax, sample_idx, sample_action = tk.sel = res["sel"]
         self.last = dict(expect_return=res["expect_return"] if bound else res["expect_return_low"],
                          expect_return_bf16=res["expect_return_low"] if bound else None, p=p, argmax=argmax, sample_idx=sample_idx,
@@ -716,7 +718,10 @@ class HipPlanner(GoalMixin, LockstepMixin):
         sl = (slot if slot is not None else self._acquire_slot()).ready(self)
         bound = self.rescore == "bound"
         main = torch.cuda.current_stream(self.device)
-        if (bound and self._delta_fixed is None and self._cal_left > 0) or self._eval_tol is not None:
+        # (calibration steps run serially; so does an eval_tol planner whose schedule is not the library's: _begin runs alternate
+        # chain streams with a tail stream and a deferred join)
+        if (bound and self._delta_fixed is None and self._cal_left > 0) or (
+                self._eval_tol is not None and not (self._alternate and self._tail_stream and self._defer_join)):
             self._drain()
             if inputs_ready:
                 main.wait_event(sl.ev_h2d)  # (plan_async copied the window on the chain stream)
@@ -754,15 +759,21 @@ class HipPlanner(GoalMixin, LockstepMixin):
         tk.res = hd.plan_step_certified_begin(mode, states, actions, rewards, eps, tk.expo, h, tk.rtg, tk.lmbda, float(cfg.discount), N,
                                               float(cfg.temperature), delta=delta, grow_delta=bound and self._delta_fixed is None,
                                               kmin=kmin, kmax=kmax, rfirst=rfirst, rmax=R, precision=self.precision, slot=sl.i,
-                                              returns=returns, pruned=self._policy_pruned, inputs_ready=inputs_ready)
+                                              returns=returns, pruned=self._policy_pruned, inputs_ready=inputs_ready,
+                                              eval_tol=self._eval_tol)
+        tk.eval_tol = self._eval_tol
         tk.tail_enqueued = True  # (the library's business)
         return tk
 
     def _finish_native(self, tk):
         sl = tk.slot
-        rec = self.handle.plan_step_certified_end(sl.i)
+        erec = None
+        if tk.eval_tol is not None:  # begun with m3pc_plan_step_certified_eval_begin
+            rec, erec = self.handle.plan_step_certified_end(sl.i, eval=True)
+        else:
+            rec = self.handle.plan_step_certified_end(sl.i)
         sl.ev_done.record(torch.cuda.current_stream(self.device))  # (plan_async re-fills the slot's buffers behind it)
-        self._native_result(tk, tk.res, rec, tk.delta, tk.kmin, tk.kmax)
+        self._native_result(tk, tk.res, rec, tk.delta, tk.kmin, tk.kmax, erec=erec)
         if sl.owner is tk:
             sl.owner = None
         return tk.out
@@ -1104,11 +1115,14 @@ class HipPlanner(GoalMixin, LockstepMixin):
         protocol of ``lockstep=True`` as ONE library call per group of windows (m3pc_plan_steps_certified: the lists, the gather and
         the merge + select of all windows in one launch each); per window bit-identical to ``lockstep=True`` for the same
         generator state and bound.  Groups that still calibrate the bound (the first windows behind a weight load) take the
-        ``lockstep=True`` path; ``rescore="topk"`` is not served (ValueError).
+        ``lockstep=True`` path; ``rescore="topk"`` is not served (ValueError).  With ``eval_tol`` it is the only lock-step form
+        (m3pc_plan_steps_certified_eval): every window's ``info`` carries eval_bound, need_eval_first, n_eval, eval_rounds and
+        eval_certified, and a group that still calibrates is calibrated first and then runs the library call.
         ``rtg``: None, a float, or one value per window.  Returns (E, A)."""
-        if lockstep and self._eval_tol is not None:
-            raise ValueError("eval_tol: the eval_action certificate has no lock-step form (m3pc_plan_step_certified_eval is the serial "
-                             "one-call step); use action_sample_batch(lockstep=False) or a planner without eval_tol")
+        if lockstep and lockstep != "native" and self._eval_tol is not None:
+            raise ValueError("eval_tol: the eval_action certificate has no lock-step form in Python; its lock-step form is the library's "
+                             "(m3pc_plan_steps_certified_eval): use action_sample_batch(lockstep=\"native\"), lockstep=False, or a "
+                             "planner without eval_tol")
         if lockstep:
             return self._action_sample_lockstep(sequence_histories, percentage, eval, rtg, onepass=lockstep == "onepass",
                                                 native=lockstep == "native")

@@ -41,7 +41,7 @@ class _Episode:
 
 def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: float = 1.0, max_steps: int = 1000,
                   in_flight: Optional[int] = None, on_step: Optional[Callable] = None, eval: bool = True,
-                  percentage: float = 1.0, lockstep: bool = False) -> Dict[str, Any]:
+                  percentage: float = 1.0, lockstep=False) -> Dict[str, Any]:
     """One evaluation episode in each of ``envs`` (learner.py:645-741 with num_episodes = len(envs)), planned through the
     pipelined planner.  ``episode_rtg_ref[t] * ratio`` is the return-to-go handed to the planner at timestep t (learner.py:
     688); with ``eval=False`` the planner explores as ``online_rollout`` does (sampled action, return-to-go from the
@@ -52,8 +52,11 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
     of all live environments (one policy pass at batch E, the candidate passes back to back, one batched fp32 re-score: the
     short launches of the fp32 chains are paid once per round, not once per environment; needs a planner built with
     ``max_batch >= len(envs)``; per environment the actions agree with the pipelined loop to fp32 rounding of the policy
-    head, not bit for bit, and the draws are taken per round).  Returns {"return_mean", "return_std", "length_mean", "length_std", "returns",
-    "lengths", "trajectories", "plan_steps"} -- the statistics evaluate_plan logs (learner.py:715-731)."""
+    head, not bit for bit, and the draws are taken per round); ``lockstep="native"``: the same rounds as one library call each
+    (``action_sample_batch(lockstep="native")``), the lock-step form a planner with ``eval_tol`` takes.  Returns {"return_mean", "return_std", "length_mean", "length_std", "returns",
+    "lengths", "trajectories", "plan_steps"} -- the statistics evaluate_plan logs (learner.py:715-731); with a planner built with
+    ``eval_tol`` also "eval_bound_max" (the largest per-step bound on |eval_action - the fp32 step's|) and "eval_steps_everything"
+    (the steps that scored every candidate in fp32)."""
     from . import capi
 
     E = len(envs)
@@ -65,6 +68,14 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
     waiting: List[_Episode] = list(eps_)   # environments that need a plan step issued, in round-robin order
     flying: List[_Episode] = []            # environments whose plan step is on the device, oldest first
     steps = 0
+    with_eval = getattr(planner, "_eval_tol", None) is not None
+    bound_max, n_everything = 0.0, 0
+
+    def note(info):
+        nonlocal bound_max, n_everything
+        if with_eval and info is not None and "eval_bound" in info:
+            bound_max = max(bound_max, float(info["eval_bound"]))
+            n_everything += int(bool(info.get("everything", False)))
 
     def issue(ep: _Episode):
         ep.traj["observations"][ep.timestep] = ep.observation
@@ -76,6 +87,7 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
         nonlocal steps
         if action is None:
             action = ep.ticket.result().cpu().numpy()
+            note(ep.ticket.info)
             ep.ticket = None
         action = np.clip(action, -1, 1)  # learner.py:690 / replay_buffer.py:213-215
         obs, reward, done, info = ep.env.step(action)
@@ -97,7 +109,10 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
         for ep in live:
             ep.traj["observations"][ep.timestep] = ep.observation
         rtgs = [float(episode_rtg_ref[ep.timestep] * ratio) for ep in live] if eval else None
-        acts = planner.action_sample_batch([ep.traj for ep in live], percentage=percentage, eval=eval, rtg=rtgs, lockstep=True)
+        acts = planner.action_sample_batch([ep.traj for ep in live], percentage=percentage, eval=eval, rtg=rtgs,
+                                           lockstep="native" if lockstep == "native" else True)
+        for info in planner.last["windows"] if with_eval else ():
+            note(info)
         for ep, action in zip(live, acts.cpu().numpy()):  # one read-back per round
             land(ep, action)
     while waiting or flying:
@@ -119,4 +134,6 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
     out["returns"], out["lengths"] = stats.get("return", []), stats.get("length", [])
     out["trajectories"] = [ep.traj for ep in eps_]
     out["plan_steps"] = steps
+    if with_eval:
+        out["eval_bound_max"], out["eval_steps_everything"] = bound_max, n_everything
     return out
