@@ -47,7 +47,8 @@ extern "C" {
  * m3pc_draw_variates; then m3pc_refit_resample, m3pc_refine_plan and m3pc_refine_args (CEM / MPPI refinement); then
  * m3pc_plan_steps_certified (a lock-step batch of certified steps); then m3pc_eval_bound, m3pc_plan_step_certified_eval and
  * m3pc_eval_record (the eval_action certificate); then m3pc_plan_step_certified_eval_begin / _eval_end and
- * m3pc_plan_steps_certified_eval (that certificate in the pipelined and the lock-step step).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * m3pc_plan_steps_certified_eval (that certificate in the pipelined and the lock-step step); then m3pc_refine_plans (the
+ * refinement of a lock-step batch of windows, with a shifted warm start).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -731,6 +732,44 @@ int m3pc_refine_plan(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_refi
                      const float* actions, const float* rewards, const float* init_mean, const float* noise,
                      float* mean, float* std, float* candidates, float* scores, int* elites,
                      float* sample_action, float* eval_action, void* stream);
+
+/* m3pc_refine_plan for E windows that step together, as ONE call: every launch of the loop takes the batch as a grid dimension, so
+ * an iteration is one scoring pass over the E * n_total rows (window_index[c] = c / n_total, kept in the handle), one top-k, one refit
+ * and one resample, whatever E is.  All on `stream`; nothing is read back, the host never waits.
+ *   1. m3pc_policy_pass_batch into args->slot (rtg per window; args->rtg is ignored)
+ *   2. mean[0] of window w, row t (the receding-horizon warm start: the previous plan, shifted):
+ *        init_mean[w, t + init_offset]   when init_mean is given and t + init_offset < init_rows[w],
+ *        tanh(policy loc[w, T - h + t])  otherwise  (init_rows[w] = 0: a cold start)
+ *      std[0] = init_std.  A closed loop passes the last call's final mean with init_offset = 1: with the same horizon the last
+ *      row comes from the policy head; while the effective horizon shrinks by one per step (the first T steps of an episode)
+ *      init_rows[w] = h + 1 and nothing is filled.
+ *   3. candidates = resample(mean[0], std[0], noise[0]);  4. iterations x (score, top_k, refit, resample) as m3pc_refine_plan;
+ *   5. sample_action[w] = candidates[w, 0, 0, :], eval_action[w] = mean[iterations][w][0, :]
+ * For the same inputs a window's top-k, refit and resample are the one-window kernels' bit for bit; its policy head and scores agree
+ * with m3pc_refine_plan's to fp32 rounding (the few-row kernels tile by the row count), so the elite sets agree where the boundary
+ * is clear.
+ *   states (E,T,S), actions (E,T,A), rewards (E,T,1) device;  rtg host (E,)
+ *   init_mean   device (E, init_stride, A) or NULL (all cold);  init_rows host (E,), each in [0, init_stride], NULL = init_stride for
+ *               every window;  init_offset >= 0
+ *   noise       device (iterations + 1, E, n_total, h, A), or NULL: the library draws -- window w gets what m3pc_refine_plan uses for
+ *               (seed, steps[w]);  steps host (E,), NULL = refine step + w
+ *   mean, std   device out (iterations + 1, E, h, A);  candidates device out (E, n_total, h, A)
+ *   scores      device out (iterations, E, n_total), optional;  elites device out (iterations, E, top_k) int32, optional
+ *   sample_action, eval_action   device out (E, A), each optional
+ * Refused before any HIP call: every check of m3pc_refine_plan; n_windows < 1, args->returns != NULL, args->flags != 0, init_mean
+ * with init_stride < 1, an init_rows[w] outside [0, init_stride], init_offset < 0 (M3PC_EINVAL); n_windows > max_batch or
+ * n_windows * n_total > max_candidates (M3PC_ENOMEM); a pipelined step begun, CRITIC scoring without critic weights (M3PC_ESTATE).
+ * Where it pays: the batch call shares the policy chain and the short launches of an iteration among the windows, but its scoring
+ * pass gives up the first-layer sharing of history rows that a one-window m3pc_score_actions has.  Measured at E = 8 against eight
+ * m3pc_refine_plan calls (DESIGN.md section 5 "Refinement", tools/refine_batch_ab.py): 0.40 (bf16) / 0.81 (fp32) of their time at the
+ * shipped shape (N = 625, H = 4, T = 8), 0.92 at the headline shape (N = 1024, H = 16, T = 32) -- no crossover up to there; the gain
+ * shrinks as scoring takes over the call, so beyond the headline's rows per window measure before relying on either. */
+int m3pc_refine_plans(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_refine_args* refine, int n_windows,
+                      const float* states, const float* actions, const float* rewards, const double* rtg,
+                      const float* init_mean, int init_stride, const int* init_rows, int init_offset,
+                      const float* noise, const unsigned long long* steps,
+                      float* mean, float* std, float* candidates, float* scores, int* elites,
+                      float* sample_action, float* eval_action, void* stream);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

@@ -49,6 +49,7 @@ EXPORTS = (
     "m3pc_plan_steps_certified",
     "m3pc_eval_bound", "m3pc_plan_step_certified_eval",
     "m3pc_plan_step_certified_eval_begin", "m3pc_plan_step_certified_eval_end", "m3pc_plan_steps_certified_eval",
+    "m3pc_refine_plans",
 )
 
 
@@ -173,6 +174,8 @@ def load_library(path: Optional[str] = None):
         "m3pc_draw_variates": [vp, C.c_ulonglong, C.c_ulonglong, i, i, i, vp, vp, vp],
         "m3pc_refit_resample": [vp, vp, i, i, vp, vp, i, i, f, f, vp, vp, vp, vp, vp],
         "m3pc_refine_plan": [vp, C.POINTER(PlanArgs), C.POINTER(RefineArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "m3pc_refine_plans": [vp, C.POINTER(PlanArgs), C.POINTER(RefineArgs), i, vp, vp, vp, C.POINTER(d), vp, i, C.POINTER(i), i, vp,
+                              C.POINTER(C.c_ulonglong), vp, vp, vp, vp, vp, vp, vp, vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }
@@ -747,6 +750,64 @@ class Handle:
         check(self.lib.m3pc_refine_plan(self._h, C.byref(args), C.byref(ref), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(init_mean),
                                         _ptr(noise), _ptr(res["mean"]), _ptr(res["std"]), _ptr(res["candidates"]), _ptr(res.get("scores")),
                                         _ptr(res.get("elites")), _ptr(res.get("sample_action")), _ptr(res.get("eval_action")), _stream(dev)))
+        return res
+
+    def refine_plans(self, mode: int, states, actions, rewards, horizon: int, rtg, lmbda: float, discount: float, n_total: int,
+                     iterations: int = 2, top_k: int = 128, weighting: int = REFINE_CEM, temperature: float = 0.0,
+                     init_std: float = 0.1, min_std: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0,
+                     steps=None, init_mean: Optional[torch.Tensor] = None, init_rows=None, init_offset: int = 0,
+                     precision: int = PREC_FP32, slot: int = 0, out: Optional[Dict[str, torch.Tensor]] = None,
+                     want_trace: bool = True, want_actions: bool = True):
+        """``refine_plan`` for E windows that step together, in ONE library call on the current stream (m3pc_refine_plans): states
+        (E,T,S), actions (E,T,A), rewards (E,T,1), rtg (E,) floats.  noise: (iterations+1, E, n_total, h, A) normals, or None: the
+        library draws window w's from (seed, steps[w]) -- ``steps`` (E,) ints, default ``step + w``.  init_mean (E, init_stride, A):
+        the warm start; row t of window w's first mean is init_mean[w, t + init_offset] while t + init_offset < init_rows[w]
+        (default: init_stride), else tanh of the window's policy loc; init_rows[w] = 0: a cold start.
+        -> dict: mean, std (iterations+1,E,h,A), candidates (E,n_total,h,A), scores (iterations,E,n_total), elites
+        (iterations,E,top_k) int32, sample_action, eval_action (E,A).  want_trace / want_actions / out: as ``refine_plan``."""
+        dev, A, it, n, hz, k = self.device, self.A, int(iterations), int(n_total), int(horizon), int(top_k)
+        ins = [self._f32(t) for t in (states, actions, rewards)]
+        E = int(ins[0].shape[0]) if ins[0].dim() == 3 else 0
+        assert ins[0].shape == (E, self.T, self.S) and ins[1].shape == (E, self.T, A) and ins[2].numel() == E * self.T
+        rt = [float(v) for v in rtg]
+        assert len(rt) == E
+        shapes = dict(mean=(it + 1, E, hz, A), std=(it + 1, E, hz, A), candidates=(E, n, hz, A), scores=(it, E, n), elites=(it, E, k),
+                      sample_action=(E, A), eval_action=(E, A))
+        res = {}
+        skip = (() if want_trace else ("scores", "elites")) + (() if want_actions else ("sample_action", "eval_action"))
+        for name, shape in shapes.items():
+            if name in skip:
+                continue
+            shape = tuple(max(v, 0) for v in shape)  # (a bad size is the library's to refuse)
+            dtype = torch.int32 if name == "elites" else torch.float32
+            t = (out or {}).get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape, name
+            res[name] = t
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == (it + 1) * E * n * hz * A
+        stride, rows = 0, None
+        if init_mean is not None:
+            init_mean = self._f32(init_mean)
+            assert init_mean.is_cuda and init_mean.dim() == 3 and init_mean.shape[0] == E and init_mean.shape[2] == A
+            stride = int(init_mean.shape[1])
+            if init_rows is not None:
+                assert len(init_rows) == E
+                rows = (C.c_int * max(E, 1))(*[int(v) for v in init_rows])
+        stp = None
+        if steps is not None:
+            assert len(steps) == E
+            stp = (C.c_ulonglong * max(E, 1))(*[int(v) & (2 ** 64 - 1) for v in steps])
+        args = self._args(mode, precision, hz, n, 0, n, lmbda, discount, 0.0, slot)
+        seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        ref = RefineArgs(it, k, int(weighting), float(temperature), float(init_std), float(min_std), seed & 0xFFFFFFFF, seed >> 32,
+                         step & 0xFFFFFFFF, step >> 32)
+        check(self.lib.m3pc_refine_plans(self._h, C.byref(args), C.byref(ref), E, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]),
+                                         (C.c_double * max(E, 1))(*rt), _ptr(init_mean), stride, rows, int(init_offset), _ptr(noise), stp,
+                                         _ptr(res["mean"]), _ptr(res["std"]), _ptr(res["candidates"]), _ptr(res.get("scores")),
+                                         _ptr(res.get("elites")), _ptr(res.get("sample_action")), _ptr(res.get("eval_action")),
+                                         _stream(dev)))
         return res
 
     def calibrate_delta(self, mode: int, states, actions, rewards, eps, scores_low: torch.Tensor, horizon: int, lmbda: float,

@@ -606,6 +606,40 @@ struct ResampleP {
     float* eval_action;   // optional (A,): mean[0 .. A)
 };
 void launch_resample(const ResampleP& p, hipStream_t st);
+// ---- the same three steps for E windows, a window per grid index (m3pc_refine_plans); a window's output is the one-window
+// launch's bit for bit.
+// launch_refit over window w's cand + w n C, scores + w n, elite + w k into mean / std + w C
+void launch_refit_batch(const RefitP& p, int E, hipStream_t st);
+// launch_resample over window w's noise / out + w total from row w of mean / std (E, C).  mean == NULL: the first distribution,
+// per window and row t = c / A: init_mean[w, t + init_offset] while t + init_offset < init_rows[w], else tanhf of
+// loc[w loc_wstride + c]; std == NULL: std_const.  mean_out / std_out (E, C), sample_action / eval_action (E, A): optional.
+// 16-byte accesses only when total % 4 == 0 (every window's block aligned) and noise / out are 16-byte aligned.
+struct ResampleBatchP {
+    const float* mean;       // (E, C) or NULL
+    const float* std;        // (E, C) or NULL
+    const float* init_mean;  // (E, init_stride, A) or NULL, read when mean == NULL
+    int init_stride, init_offset;
+    const float* loc;        // window w: loc + w loc_wstride, (C,) from step T - h on
+    long long loc_wstride;
+    float std_const;
+    const float* noise;      // (E, total)
+    float* out;              // (E, total)
+    int total, C, A;
+    float* mean_out;
+    float* std_out;
+    float* sample_action;
+    float* eval_action;
+    int w0;                  // (set by the launcher, like init_rows: 64 windows per launch)
+    int init_rows[64];
+};
+void launch_resample_batch(ResampleBatchP& p, int E, const int* init_rows, hipStream_t st);  // init_rows host (E,), NULL = init_stride
+void launch_window_index(int* out, int total, int n, hipStream_t st);  // out[c] = c / n
+// launch_topk over E rows of n values into E lists of k indices, one launch (no environment switch: n <= 2048 ranks by blocks)
+void launch_topk_batch(const float* v, int E, int n, int k, int* idx_out, hipStream_t st);
+// launch_variates (array 0) for E windows: window w's elements [g0, g1) of the (seed, steps[w]) array to out + w (g1 - g0); steps
+// host (E,), 64 windows per launch
+void launch_variates_batch(unsigned long long seed, const unsigned long long* steps, int E, long long g0, long long g1, float* out,
+                           hipStream_t st);
 // dst[index[i]] = src[i]
 void launch_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, hipStream_t st);  // + index_copy[i] = index[i]
 

@@ -128,6 +128,7 @@ int m3pc_create(const m3pc_dims* dims, int device, m3pc_handle** out) {
     CHK(dmalloc(&h->refine_noise, (size_t)D.max_candidates * T * h->A));
     CHK(dmalloc(&h->refine_scores, (size_t)D.max_candidates));
     CHK(dmalloc(&h->refine_elites, (size_t)D.max_candidates));
+    CHK(dmalloc(&h->refine_widx, (size_t)D.max_candidates));
     for (int s = 0; s < M3PC_SLOTS; ++s) {
         CHK(dmalloc(&h->cert_list[s], 64 + 1024));
         CHK(dmalloc(&h->cert_b[s], 64 + 1024));
@@ -236,7 +237,7 @@ int m3pc_destroy(m3pc_handle* h) {
         hipFree(h->slot[s].rtok);
     }
     void* bufs[] = {h->sel_scratch, h->d_topk, h->er_top, h->sa_buf, h->sa_chain[0], h->sa_chain[1], h->c_om, h->c_os, h->goal_ws,
-                    h->refine_noise, h->refine_scores, h->refine_elites};
+                    h->refine_noise, h->refine_scores, h->refine_elites, h->refine_widx};
     for (int s = 0; s < M3PC_SLOTS; ++s) {
         void* cb[] = {h->cert_list[s], h->cert_b[s], h->cert_f[s], h->cert_stats[s], h->cert_f32[s], h->cert_top1[s]};
         for (void* b : cb)
@@ -1442,6 +1443,118 @@ int m3pc_refine_plan(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_refine_
         }
         launch_resample(sp, st);
         CHK(check_launch("refine_plan"));
+    }
+    return 0;
+}
+
+// The refinement of E lock-step windows: m3pc_refine_plan's sequence with the batch as a grid dimension of every launch -- one
+// policy pass at batch E, then per iteration one scoring pass over the E n_total rows, one top-k, one refit, one resample.
+int m3pc_refine_plans(m3pc_handle* h, const m3pc_plan_args* a, const m3pc_refine_args* r, int n_windows, const float* states,
+                      const float* actions, const float* rewards, const double* rtg, const float* init_mean, int init_stride,
+                      const int* init_rows, int init_offset, const float* noise, const unsigned long long* steps, float* mean, float* std_,
+                      float* candidates, float* scores, int* elites, float* sample_action, float* eval_action, void* stream) {
+    static const char* who = "m3pc_refine_plans";
+    if (!h || !a || !r) return fail(M3PC_EINVAL, "null argument");
+    if (n_windows < 1) return fail(M3PC_EINVAL, "%s: n_windows %d < 1", who, n_windows);
+    if (!states || !actions || !rewards || !rtg || !mean || !std_ || !candidates) return fail(M3PC_EINVAL, "null argument");
+    CHK(cert_check_args(a, who));
+    if (a->mode != M3PC_MODE_RTG && a->mode != M3PC_MODE_CRITIC) return fail(M3PC_EINVAL, "%s: mode must be RTG or CRITIC scoring", who);
+    if (a->horizon < 1) return fail(M3PC_EINVAL, "%s: horizon %d < 1", who, a->horizon);
+    if (a->flags != 0) return fail(M3PC_EINVAL, "%s: m3pc_plan_args::flags 0x%x must be 0", who, a->flags);
+    if (a->returns) return fail(M3PC_EINVAL, "%s takes rtg per window, not a returns row (args->returns must be NULL)", who);
+    if (r->iterations < 1 || r->iterations > M3PC_REFINE_MAX_ITER)
+        return fail(M3PC_EINVAL, "%s: iterations %d outside [1, %d]", who, r->iterations, M3PC_REFINE_MAX_ITER);
+    if (r->top_k < 1 || r->top_k > a->n_total) return fail(M3PC_EINVAL, "%s: top_k %d outside [1, n_total=%d]", who, r->top_k, a->n_total);
+    CHK(refine_check_refit(r->weighting, r->temperature, r->min_std, who));
+    if (!finite_nonneg(r->init_std)) return fail(M3PC_EINVAL, "%s: init_std must be finite and >= 0", who);
+    if (init_offset < 0) return fail(M3PC_EINVAL, "%s: init_offset %d < 0", who, init_offset);
+    if (init_mean) {
+        if (init_stride < 1) return fail(M3PC_EINVAL, "%s: init_stride %d < 1", who, init_stride);
+        if (init_rows)
+            for (int w = 0; w < n_windows; ++w)
+                if (init_rows[w] < 0 || init_rows[w] > init_stride)
+                    return fail(M3PC_EINVAL, "%s: init_rows[%d] = %d outside [0, init_stride=%d]", who, w, init_rows[w], init_stride);
+    }
+    const int E = n_windows, N = a->n_total, k = r->top_k, T = h->T, hh = a->horizon, A = h->A;
+    if (hh > T) return fail(M3PC_EINVAL, "horizon %d outside [1, T=%d]", hh, T);
+    if (E > h->dm.max_batch) return fail(M3PC_ENOMEM, "%s: n_windows %d > max_batch=%d", who, E, h->dm.max_batch);
+    if ((long long)E * N > h->dm.max_candidates)
+        return fail(M3PC_ENOMEM, "%s: n_windows * n_total = %lld > max_candidates %d", who, (long long)E * N, h->dm.max_candidates);
+    if (cert_any_begun(h)) return fail(M3PC_ESTATE, "%s with a pipelined step begun (m3pc_plan_step_certified_end first)", who);
+    if (a->mode == M3PC_MODE_CRITIC && !h->critic_set) return fail(M3PC_ESTATE, "critic weights not set");
+    hipStream_t st = (hipStream_t)stream;
+    const int C = hh * A;
+    const long long total = (long long)N * C;  // per window (E * total <= max_candidates * T * A: what the workspace holds)
+
+    m3pc_plan_args pa = *a;
+    pa.window = 0;
+    CHK(m3pc_policy_pass_batch(h, &pa, E, states, actions, rewards, rtg, nullptr, nullptr, stream));
+    if (h->refine_widx_n != N) {  // window_index[c] = c / N for every row one pass can take
+        launch_window_index(h->refine_widx, h->dm.max_candidates, N, st);
+        h->refine_widx_n = N;
+    }
+    pa.n_total = pa.n_count = E * N;
+
+    const unsigned long long seed = ((unsigned long long)r->seed_hi << 32) | r->seed_lo, step = ((unsigned long long)r->step_hi << 32) | r->step_lo;
+    std::vector<unsigned long long> stp;
+    if (!noise) {
+        stp.resize(E);
+        for (int w = 0; w < E; ++w) stp[w] = steps ? steps[w] : step + (unsigned long long)w;
+    }
+    // the noise of iteration `it`, (E, N, h, A): the caller's slice, or every window's slice of its (seed, steps[w]) array in one launch
+    auto noise_of = [&](int it) -> const float* {
+        if (noise) return noise + (size_t)it * E * total;
+        launch_variates_batch(seed, stp.data(), E, (long long)it * total, (long long)(it + 1) * total, h->refine_noise, st);
+        return h->refine_noise;
+    };
+    ResampleBatchP sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.out = candidates;
+    sp.total = (int)total;
+    sp.C = C;
+    sp.A = A;
+    // distribution 0 per window: the shifted rows of the caller's mean, then tanh of the policy head; std = init_std
+    sp.init_mean = init_mean;
+    sp.init_stride = init_mean ? init_stride : 0;
+    sp.init_offset = init_offset;
+    sp.loc = h->loc + (size_t)(T - hh) * A;
+    sp.loc_wstride = (long long)T * A;
+    sp.std_const = r->init_std;
+    sp.noise = noise_of(0);
+    sp.mean_out = mean;
+    sp.std_out = std_;
+    launch_resample_batch(sp, E, init_rows, st);
+    CHK(check_launch(who));
+    sp.mean_out = sp.std_out = nullptr;
+    sp.init_mean = nullptr;
+    for (int it = 0; it < r->iterations; ++it) {
+        float* er = scores ? scores + (size_t)it * E * N : h->refine_scores;
+        int* top = elites ? elites + (size_t)it * E * k : h->refine_elites;
+        CHK(m3pc_score_actions(h, &pa, E, states, actions, rewards, candidates, h->refine_widx, er, nullptr, nullptr, stream));
+        launch_topk_batch(er, E, N, k, top, st);
+        RefitP rp;
+        memset(&rp, 0, sizeof(rp));
+        rp.cand = candidates;
+        rp.elite = top;
+        rp.scores = er;
+        rp.n = N;
+        rp.k = k;
+        rp.C = C;
+        rp.weighting = r->weighting;
+        rp.tau = r->temperature;
+        rp.min_std = r->min_std;
+        rp.mean = mean + (size_t)(it + 1) * E * C;
+        rp.std = std_ + (size_t)(it + 1) * E * C;
+        launch_refit_batch(rp, E, st);
+        sp.mean = rp.mean;
+        sp.std = rp.std;
+        sp.noise = noise_of(it + 1);
+        if (it == r->iterations - 1) {
+            sp.sample_action = sample_action;
+            sp.eval_action = eval_action;
+        }
+        launch_resample_batch(sp, E, nullptr, st);
+        CHK(check_launch(who));
     }
     return 0;
 }

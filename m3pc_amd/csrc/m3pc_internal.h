@@ -147,6 +147,9 @@ struct m3pc_handle {
     float* refine_noise = nullptr;
     float* refine_scores = nullptr;
     int* refine_elites = nullptr;
+    // m3pc_refine_plans: window_index[c] = c / n_total of its one scoring pass, (max_candidates,), built once per n_total
+    int* refine_widx = nullptr;
+    int refine_widx_n = 0;
     float* splitk_ws = nullptr;   // raw split-K slabs of the few-row fp32 GEMMs
     long long splitk_ws_bytes = 0;
     // m3pc_plan_step_certified / m3pc_calibrate_delta: the step's lists (64 race entries at most in front of 1024 score entries:

@@ -3,6 +3,7 @@
 // shuffles + one LDS hop.
 #include <atomic>
 #include <stdlib.h>
+#include <string.h>
 
 #include "kernels.h"
 
@@ -141,8 +142,7 @@ struct TopSrc {
 };
 __device__ __forceinline__ float src_value(const TopSrc& s, int e) { return s.expo ? race_key(s.tau, s.v[e], s.expo[e]) : s.v[e]; }
 
-__global__ __launch_bounds__(1024) void topk_kernel(const float* v, int n, int npow2, int k, int* idx_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+__device__ __forceinline__ void topk_bitonic_body(const float* v, int n, int npow2, int k, int* idx_out, unsigned long long* keys) {
     const int tid = threadIdx.x;
     for (int i = tid; i < npow2; i += 1024)
         keys[i] = i < n ? ((unsigned long long)orderable(v[i]) << 32) | (unsigned int)(~i) : 0ull;
@@ -164,13 +164,20 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* v, int n, int n
     }
     for (int i = tid; i < k; i += 1024) idx_out[i] = (int)(~(unsigned int)(keys[i] & 0xffffffffull));
 }
+__global__ __launch_bounds__(1024) void topk_kernel(const float* v, int n, int npow2, int k, int* idx_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+    topk_bitonic_body(v, n, npow2, k, idx_out, keys);
+}
+// one workgroup per row of v (E, n): list blockIdx.x of k indices
+__global__ __launch_bounds__(1024) void topk_batch_kernel(const float* v, int n, int npow2, int k, int* idx_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
+    topk_bitonic_body(v + (size_t)blockIdx.x * n, n, npow2, k, idx_out + (size_t)blockIdx.x * k, keys);
+}
 // k <= 64 of n <= 16384 by selection instead of a full sort: every wave extracts the k best of its own 1/16 of the
 // values with k rounds of (register-local arg-max, 64-lane butterfly) -- no barrier --, then wave 0 does the same over
 // the 16 k survivors.  Same order as the bitonic kernel (descending value, ties to the lower index); ~3x faster
 // at n = 1024 and independent of n up to 16384 (the replicated top-k of an 8-GPU run sorts 8192 scores).
-__global__ __launch_bounds__(1024) void topk_select_kernel(TopSrc src, int n) {
-    __shared__ float cv[16 * 64];
-    __shared__ int ci[16 * 64];
+__device__ __forceinline__ void topk_select_body(const TopSrc& src, int n, float* cv, int* ci) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int k = src.k;
     float val[16];
@@ -215,6 +222,19 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(TopSrc src, int n) {
             if (mi[j] == a.i) mv[j] = -INFINITY;
     }
 }
+__global__ __launch_bounds__(1024) void topk_select_kernel(TopSrc src, int n) {
+    __shared__ float cv[16 * 64];
+    __shared__ int ci[16 * 64];
+    topk_select_body(src, n, cv, ci);
+}
+// one workgroup per row of src.v (E, n): list blockIdx.x of src.k entries (out_stride 1)
+__global__ __launch_bounds__(1024) void topk_select_batch_kernel(TopSrc src, int n) {
+    __shared__ float cv[16 * 64];
+    __shared__ int ci[16 * 64];
+    src.v += (size_t)blockIdx.x * n;
+    src.out += (size_t)blockIdx.x * src.k;
+    topk_select_body(src, n, cv, ci);
+}
 
 // n <= 2048: rank by counting.  Every element's 64-bit key {orderable(value), ~index} (the bitonic kernel's, so the order
 // is the same: descending value, ties to the lower index) is compared with all n keys, read as LDS broadcasts; keys are
@@ -224,9 +244,7 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(TopSrc src, int n) {
 // Many-block form of the same ranking (n <= 2048): 256 threads per block, thread t of block b ranks element 64 b + (t & 63)
 // against a quarter of the keys (t >> 6), the four partial ranks meet in LDS.  16 blocks at n = 1024 instead of one:
 // the n^2 / 2 key comparisons spread over 16 CUs (20 us -> a few).
-__global__ __launch_bounds__(256) void topk_rank_blocks_kernel(const float* v, int n, int k, int* idx_out) {
-    __shared__ __attribute__((aligned(16))) unsigned long long keys[2048];
-    __shared__ int part[4][64];
+__device__ __forceinline__ void topk_rank_blocks_body(const float* v, int n, int k, int* idx_out, unsigned long long* keys, int (*part)[64]) {
     const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
     for (int e = tid; e < 2048; e += 256) keys[e] = e < n ? ((unsigned long long)orderable(v[e]) << 32) | (unsigned int)(~e) : 0ull;
     __syncthreads();
@@ -247,6 +265,17 @@ __global__ __launch_bounds__(256) void topk_rank_blocks_kernel(const float* v, i
         rank = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
         if (rank < k) idx_out[rank] = e;
     }
+}
+__global__ __launch_bounds__(256) void topk_rank_blocks_kernel(const float* v, int n, int k, int* idx_out) {
+    __shared__ __attribute__((aligned(16))) unsigned long long keys[2048];
+    __shared__ int part[4][64];
+    topk_rank_blocks_body(v, n, k, idx_out, keys, part);
+}
+// the same ranking of row blockIdx.y of v (E, n) into list blockIdx.y
+__global__ __launch_bounds__(256) void topk_rank_blocks_batch_kernel(const float* v, int n, int k, int* idx_out) {
+    __shared__ __attribute__((aligned(16))) unsigned long long keys[2048];
+    __shared__ int part[4][64];
+    topk_rank_blocks_body(v + (size_t)blockIdx.y * n, n, k, idx_out + (size_t)blockIdx.y * k, keys, part);
 }
 
 // Two rankings in one launch (n <= 2048): blockIdx.y picks the source -- the scores themselves / the race keys.
@@ -382,6 +411,32 @@ void launch_topk(const float* v, int n, int k, int* idx_out, hipStream_t st) {
         attr[dev] = true;
     }
     hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), (size_t)np * 8, st, v, n, np, k, idx_out);
+}
+
+// launch_topk for E rows at once (m3pc_refine_plans): the same three regimes with the row as a grid index, so list w is
+// launch_topk's of row w (the keys are integers: the order does not depend on who compares them).  No environment switch.
+void launch_topk_batch(const float* v, int E, int n, int k, int* idx_out, hipStream_t st) {
+    if (E <= 0 || n <= 0 || k <= 0) return;
+    if (n <= 2048 && k <= n) {
+        for (int w0 = 0; w0 < E; w0 += 32768)
+            hipLaunchKernelGGL(topk_rank_blocks_batch_kernel, dim3((n + 63) / 64, E - w0 < 32768 ? E - w0 : 32768), dim3(256), 0, st,
+                               v + (size_t)w0 * n, n, k, idx_out + (size_t)w0 * k);
+        return;
+    }
+    if (k <= 64 && n <= 16384) {
+        hipLaunchKernelGGL(topk_select_batch_kernel, dim3(E), dim3(1024), 0, st, TopSrc{v, nullptr, 0.f, k, idx_out, 1, nullptr}, n);
+        return;
+    }
+    int np = 2;
+    while (np < n) np <<= 1;
+    static bool attr[64] = {};  // (a per-device opt-in)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev >= 0 && dev < 64 && !attr[dev]) {
+        (void)hipFuncSetAttribute((const void*)topk_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
+        attr[dev] = true;
+    }
+    hipLaunchKernelGGL(topk_batch_kernel, dim3(E), dim3(1024), (size_t)np * 8, st, v, n, np, k, idx_out);
 }
 
 // > 64 KiB of dynamic LDS for a ranking kernel: state[device] = 0: not asked, 1: granted, 2: refused
@@ -1036,8 +1091,8 @@ __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, 
 // array 0: standard normals; array 1: Exp(1), -ln u with u in (0, 1], and 2^-25 where that is 0 (the select divides by it and the
 // race key takes its log).  One thread per Philox block.  g0 / g1: the slice [g0, g1) of the flat array that goes to out[0 .. g1 - g0);
 // a block wholly inside the slice is one 16-byte store when g0 and `out` allow it, everything else goes element by element.
-__global__ __launch_bounds__(256) void variates_kernel(uint32_t k0, uint32_t k1, uint32_t s0, uint32_t s1, uint32_t array, long long g0,
-                                                       long long g1, float* __restrict__ out, int vec_ok) {
+__device__ __forceinline__ void variates_body(uint32_t k0, uint32_t k1, uint32_t s0, uint32_t s1, uint32_t array, long long g0,
+                                              long long g1, float* __restrict__ out, int vec_ok) {
     const long long b = g0 / 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (4 * b >= g1) return;
     uint32_t w[4];
@@ -1062,12 +1117,45 @@ __global__ __launch_bounds__(256) void variates_kernel(uint32_t k0, uint32_t k1,
     for (int i = 0; i < 4; ++i)
         if (e + i >= g0 && e + i < g1) out[e + i - g0] = v[i];
 }
+__global__ __launch_bounds__(256) void variates_kernel(uint32_t k0, uint32_t k1, uint32_t s0, uint32_t s1, uint32_t array, long long g0,
+                                                       long long g1, float* __restrict__ out, int vec_ok) {
+    variates_body(k0, k1, s0, s1, array, g0, g1, out, vec_ok);
+}
+// The normals of up to 64 windows in one launch: blockIdx.y picks the window -- its step (the generator's counter words) and its
+// block of g1 - g0 floats in out.  A value depends on (seed, step, element) alone, so window w gets launch_variates' for steps[w].
+struct VariatesBatchP {
+    uint32_t s0[64], s1[64];
+};
+__global__ __launch_bounds__(256) void variates_batch_kernel(uint32_t k0, uint32_t k1, VariatesBatchP sp, long long g0, long long g1,
+                                                             float* __restrict__ out, int vec_ok) {
+    const int y = blockIdx.y;
+    variates_body(k0, k1, sp.s0[y], sp.s1[y], 0u, g0, g1, out + (size_t)y * (size_t)(g1 - g0), vec_ok);
+}
 void launch_variates(unsigned long long seed, unsigned long long step, int array, long long g0, long long g1, float* out, hipStream_t st) {
     if (g1 <= g0 || !out) return;
     const long long blocks = (g1 + 3) / 4 - g0 / 4;
     const int vec_ok = g0 % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
     hipLaunchKernelGGL(variates_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, (uint32_t)seed, (uint32_t)(seed >> 32),
                        (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)array, g0, g1, out, vec_ok);
+}
+
+void launch_variates_batch(unsigned long long seed, const unsigned long long* steps, int E, long long g0, long long g1, float* out,
+                           hipStream_t st) {
+    if (g1 <= g0 || !out || E <= 0) return;
+    const long long blocks = (g1 + 3) / 4 - g0 / 4, len = g1 - g0;
+    // (a 16-byte store needs every window's block aligned: len % 4 == 0, or one window)
+    const int vec_ok = g0 % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 && (len % 4 == 0 || E == 1);
+    for (int w0 = 0; w0 < E; w0 += 64) {
+        const int m = E - w0 < 64 ? E - w0 : 64;
+        VariatesBatchP sp;
+        memset(&sp, 0, sizeof(sp));
+        for (int i = 0; i < m; ++i) {
+            sp.s0[i] = (uint32_t)steps[w0 + i];
+            sp.s1[i] = (uint32_t)(steps[w0 + i] >> 32);
+        }
+        hipLaunchKernelGGL(variates_batch_kernel, dim3((unsigned)((blocks + 255) / 256), m), dim3(256), 0, st, (uint32_t)seed,
+                           (uint32_t)(seed >> 32), sp, g0, g1, out + (size_t)w0 * len, vec_ok);
+    }
 }
 
 }  // namespace m3pc

@@ -258,3 +258,57 @@ class GoalMixin:
                  for it in range(iterations)]
         self.last = dict(cem=trace, candidates=res["candidates"])
         return res["sample_action"], res["eval_action"]
+
+    @torch.no_grad()
+    def cem_guiding_batch(self, trajectories, h: int, iterations: int = 2, top_k: int = 128, init_std: float = 0.1, noise=None,
+                          weighting: str = "cem", temperature: Optional[float] = None, min_std: float = 0.0, init_mean=None,
+                          init_rows=None, init_offset: int = 0):
+        """``cem_guiding(native=True)`` for E windows that step together, as ONE library call (m3pc_refine_plans: one policy pass
+        at batch E, per iteration one scoring pass over the E x N candidates, one top-k, one refit, one resample).  trajectories:
+        E reference-style dicts of (1,T,D) tensors with a constant return-to-go (``_rtg``), all of effective horizon ``h``; needs
+        ``HipPlanner(..., max_batch=E, max_windows=E)``.  noise: optional (iterations+1, E, N, h, A) normals; without it torch
+        draws them, or the library does from (seed, step index + w) when the planner was built with variates="library" (the index
+        advances by E).  init_mean (E, rows, A), init_rows (E,), init_offset: the shifted warm start -- row t of window w starts
+        from init_mean[w, t + init_offset] while t + init_offset < init_rows[w] (default: every row given), else from tanh of the
+        policy loc; ``init_rows[w] = 0``: a cold start.
+        Returns (sample_action (E,A), eval_action (E,A)); ``self.last["cem"][w]`` is the trace ``cem_guiding`` fills, per window."""
+        trajectories = list(trajectories)
+        parts = [self._split(t) for t in trajectories]
+        if any(ret is not None for *_, ret in parts):
+            raise ValueError("cem_guiding_batch takes a constant return-to-go per window (trajectory['_rtg']), not a returns row")
+        s, a, r = (torch.stack([q[i] for q in parts]).contiguous() for i in range(3))
+        return self._cem_batch(s, a, r.reshape(len(parts), self.T, 1), [q[3] for q in parts], h, iterations, top_k, init_std, noise,
+                               weighting, temperature, min_std, init_mean, init_rows, init_offset)
+
+    def _cem_batch(self, s, a, r, rtgs, h, iterations, top_k, init_std, noise, weighting, temperature, min_std, init_mean, init_rows,
+                   init_offset):
+        """``cem_guiding_batch`` on stacked windows s (E,T,S), a (E,T,A), r (E,T,1) and their return-to-go values."""
+        if weighting not in capi.REFINE_WEIGHTINGS:
+            raise ValueError(f"weighting must be one of {sorted(capi.REFINE_WEIGHTINGS)}, got {weighting!r}")
+        cfg = self.cfg
+        if cfg.plan_guidance == "noise_adding_lambda":
+            raise ValueError("refinement scores with rtg_guiding or critic_lambda_guiding; noise_adding_lambda has no scoring of its own")
+        self._drain()
+        E, N, A = int(s.shape[0]), int(cfg.action_samples), self.A
+        mode = capi.MODE_CRITIC if cfg.plan_guidance == "critic_lambda_guiding" else capi.MODE_RTG
+        lmbda = 0.6 if mode == capi.MODE_RTG else float(cfg.lmbda)
+        k = min(int(top_k), N)
+        seed, steps = 0, None
+        if noise is None:
+            if self._variates == "library":
+                seed, steps = self._seed, [self._step_index + w for w in range(E)]
+                self._step_index += E
+            else:
+                noise = self._eps((iterations + 1, E, N, h, A))
+        else:
+            noise = noise.to(self.device, torch.float32).contiguous()
+        tau = float(cfg.temperature) if temperature is None else float(temperature)
+        res = self.handle.refine_plans(mode, s, a, r, h, rtgs, lmbda, float(cfg.discount), N, iterations=iterations, top_k=k,
+                                       weighting=capi.REFINE_WEIGHTINGS[weighting], temperature=tau, init_std=init_std, min_std=min_std,
+                                       noise=noise, seed=seed, steps=steps, init_mean=init_mean, init_rows=init_rows,
+                                       init_offset=init_offset, precision=self.precision)
+        self._mark_main()
+        trace = [[dict(expect_return=res["scores"][it, w], top=res["elites"][it, w], mean=res["mean"][it + 1, w], std=res["std"][it + 1, w])
+                  for it in range(iterations)] for w in range(E)]
+        self.last = dict(cem=trace, candidates=res["candidates"], mean=res["mean"], std=res["std"])
+        return res["sample_action"], res["eval_action"]

@@ -140,7 +140,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                  defer_join: bool = True, goal_batch: int = 0, race_min: int = 2, calibration_windows: Optional[int] = None, certify_sample: bool = True,
                  chain_mode: str = "alternate", policy_head: str = "full", auto_fp32: bool = True,
                  calibration_factor: float = 1.6, rescore_round: int = 4, fallback: str = "fp32", native_step: bool = False,
-                 variates: str = "torch", seed: int = 0, eval_tol: Optional[float] = None):
+                 variates: str = "torch", seed: int = 0, eval_tol: Optional[float] = None, refine: Optional[dict] = None):
         """cfg: any object with traj_length, action_samples, horizon, discount, temperature, lmbda,
         plan_guidance (finetune.py RunConfig fields read at learner.py:276,319,342).
         tokenizer_manager: a TokenizerManager (this package's) or {key: {"mean","std","min","max"}}.
@@ -197,6 +197,18 @@ class HipPlanner(GoalMixin, LockstepMixin):
           on such a planner runs the serial call and returns a resolved ticket (the route of calibration steps);
           ``plan_async`` keeps its pipeline (m3pc_plan_step_certified_eval_begin / _eval_end); ``action_sample_batch(lockstep="native")``
           runs m3pc_plan_steps_certified_eval; the Python lock-step forms (``lockstep=True`` / ``"onepass"``) raise ValueError.
+        refine (default None: everything as before): a dict -- iterations (2), top_k (128), weighting ("cem" | "mppi"), temperature
+          (None: cfg.temperature), init_std (0.1), min_std (0.0), warm (True) -- that makes ``action_sample(plan=True)``,
+          ``action_sample_batch`` and ``rollout.evaluate_plan(lockstep=...)`` plan by CEM / MPPI refinement instead of the one-shot
+          sample -> score -> select step: the windows of a call are grouped by effective horizon and every group is ONE
+          m3pc_refine_plans call (``cem_guiding_batch``; needs max_batch = max_windows >= the windows of a call).  Scoring follows
+          cfg.plan_guidance as ``cem_guiding`` does (noise_adding_lambda: ValueError).  With ``warm`` the planner keeps every
+          caller key's final mean (``action_sample_batch(..., keys=...)``, default: the list position; ``action_sample``: one key)
+          and starts the key's next plan from it, shifted by the one step that passed: a window is warm only if its key's last
+          call was at path_length - 1 and its horizon is the last one (the last row comes from the policy head) or one shorter
+          (the shrinking horizon of an episode's first T steps: nothing to fill); a reset, a skipped step or a weight load is a
+          cold start.  ``planner.last["windows"][i]``: warm, init_rows, horizon, mean0 (the first distribution's mean), mean (the
+          final one) and the window's trace.  There is no ticket form: ``plan_async`` raises ValueError.
         variates: "torch" (default) draws a plan step's normals and exponentials from ``generator``; "library" draws them with
           m3pc_draw_variates -- the library's counter-based generator on (``seed``, the planner's step index), what a host
           without torch gets -- on the same stream.  Not torch's stream of numbers: goldens recorded on one do not hold on the other.
@@ -233,6 +245,20 @@ class HipPlanner(GoalMixin, LockstepMixin):
         if variates not in ("torch", "library"):
             raise ValueError(f"variates must be 'torch' or 'library', got {variates!r}")
         self._variates, self._seed = variates, int(seed)
+        self._refine = None
+        if refine is not None:
+            known = dict(iterations=2, top_k=128, weighting="cem", temperature=None, init_std=0.1, min_std=0.0, warm=True)
+            unknown = set(refine) - set(known)
+            if unknown:
+                raise ValueError(f"refine: unknown keys {sorted(unknown)} (known: {sorted(known)})")
+            self._refine = {**known, **refine}
+            if self._refine["weighting"] not in capi.REFINE_WEIGHTINGS:
+                raise ValueError(f"refine: weighting must be one of {sorted(capi.REFINE_WEIGHTINGS)}, got {self._refine['weighting']!r}")
+            if cfg.plan_guidance == "noise_adding_lambda":
+                raise ValueError("refine: scoring follows rtg_guiding or critic_lambda_guiding; noise_adding_lambda has none of its own")
+            if self.world != 1:
+                raise ValueError("refine plans on one rank")
+        self._warm: Dict[object, dict] = {}  # refine: per caller key, the last call's path_length, horizon and final mean (h, A)
         max_rescore = max((int(rescore_max) + self._R) * nw, int(rescore_topk), 1) if prec in capi.LOW_PRECISION else 1
         self._max_batch = max(int(max_batch), nw, 1)
         self.handle = capi.Handle(S, A, T, n_embd, n_head, n_enc_layer, n_dec_layer,
@@ -335,6 +361,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
         for tk in [sl.owner for sl in getattr(self, "_slots", []) if sl.owner is not None]:
             self._finish(tk)  # steps in flight were issued against the old weights: resolve them first
         self.handle.load_weights(state_dict)
+        self._warm = {}  # (a plan refined under the old weights is no warm start)
         self._reset_calibration()
 
     def _reset_calibration(self):
@@ -1068,6 +1095,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
         is bit-identical to the serial call; the draws (eps, multinomial) are taken from the generator in issue order."""
         if eval:
             assert rtg is not None
+        if self._refine is not None:
+            raise ValueError("a planner built with refine=... has no ticket form: plan with action_sample / action_sample_batch "
+                             "(rollout.evaluate_plan: lockstep=True)")
         guidance = self.cfg.plan_guidance
         assert guidance in _MODES, guidance
         lmbda = 0.6 if guidance == "rtg_guiding" else float(self.cfg.lmbda)  # learner.py:405-407
@@ -1099,7 +1129,66 @@ class HipPlanner(GoalMixin, LockstepMixin):
                 self._enqueue_tail(tk)
 
     @torch.no_grad()
-    def action_sample_batch(self, sequence_histories, percentage=1.0, eval=False, rtg=None, lockstep: bool = False):
+    def reset_warm_start(self, key=None):
+        """Forget the refinement's warm-start memory (``refine=...``): of one caller key, or (None) of all of them."""
+        if key is None:
+            self._warm = {}
+        else:
+            self._warm.pop(key, None)
+
+    def _refine_windows(self, sequence_histories, percentage, eval, rtg, keys):
+        """The plan of E windows by refinement (``refine=...``): one ``cem_guiding_batch`` per group of one effective horizon,
+        warm-started per caller key.  Returns (sample_action (E,A), eval_action (E,A))."""
+        rf = self._refine
+        self._drain()
+        E, T, S, A = len(sequence_histories), self.T, self.S, self.A
+        keys = list(range(E)) if keys is None else list(keys)
+        if len(keys) != E or len(set(keys)) != E:
+            raise ValueError("keys: one distinct key per window")
+        rtgs = [rtg] * E if (rtg is None or np.isscalar(rtg)) else list(rtg)
+        host = np.empty((E, T * (S + A + 1)), dtype=np.float32)
+        meta = [self._window_host(hst, rtgs[i], percentage, host[i]) for i, hst in enumerate(sequence_histories)]
+        dev = torch.from_numpy(host).to(self.device)  # one packed H2D copy for all windows
+        sa = torch.empty((E, A), dtype=torch.float32, device=self.device)
+        ev = torch.empty((E, A), dtype=torch.float32, device=self.device)
+        info = [None] * E
+        groups = []
+        for h in sorted({m[0] for m in meta}):  # windows of one effective horizon, at most max_batch of them per group
+            same = [i for i, m in enumerate(meta) if m[0] == h]
+            groups += [(h, same[c0 : c0 + self._max_batch]) for c0 in range(0, len(same), self._max_batch)]
+        for h, ids in groups:
+            sel = dev if len(ids) == E else dev[torch.tensor(ids, device=self.device)]
+            s = sel[:, : T * S].reshape(-1, T, S).contiguous()
+            a = sel[:, T * S : T * (S + A)].reshape(-1, T, A).contiguous()
+            r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
+            # the shifted warm start: the key's last final mean (h_prev rows) read from row 1 on
+            ends = [int(sequence_histories[i]["path_length"]) for i in ids]
+            rows = []
+            for i, end in zip(ids, ends):
+                prev = self._warm.get(keys[i]) if rf["warm"] else None
+                warm = prev is not None and prev["path_length"] == end - 1 and prev["horizon"] in (h, h + 1)
+                rows.append(prev["horizon"] if warm else 0)
+            init = None
+            if any(rows):
+                init = torch.zeros((len(ids), h + 1, A), dtype=torch.float32, device=self.device)
+                for j, i in enumerate(ids):
+                    if rows[j]:
+                        init[j, : rows[j]] = self._warm[keys[i]]["mean"]
+            gs, ge = self._cem_batch(s, a, r, [meta[i][1] for i in ids], h, int(rf["iterations"]), int(rf["top_k"]), float(rf["init_std"]),
+                                     None, rf["weighting"], rf["temperature"], float(rf["min_std"]), init, rows if init is not None else None,
+                                     1)
+            last = self.last
+            for j, i in enumerate(ids):
+                sa[i], ev[i] = gs[j], ge[j]
+                final = last["mean"][-1, j]
+                self._warm[keys[i]] = dict(path_length=ends[j], horizon=h, mean=final)
+                info[i] = dict(warm=bool(rows[j]), init_rows=rows[j], horizon=h, mean0=last["mean"][0, j], mean=final, cem=last["cem"][j],
+                               candidates=last["candidates"][j])
+        self.last = dict(windows=info)
+        return sa, ev
+
+    @torch.no_grad()
+    def action_sample_batch(self, sequence_histories, percentage=1.0, eval=False, rtg=None, lockstep: bool = False, keys=None):
         """``action_sample(history, plan=True)`` for E environments.  The reference steps one environment at a
         time (replay_buffer.py:204-232, learner.py:681-691: one action_sample per env step, the action read back each time).
         Default: the E windows are E plan steps issued back to back through ``plan_async`` -- ``pipeline_depth`` of them in
@@ -1118,7 +1207,15 @@ class HipPlanner(GoalMixin, LockstepMixin):
         ``lockstep=True`` path; ``rescore="topk"`` is not served (ValueError).  With ``eval_tol`` it is the only lock-step form
         (m3pc_plan_steps_certified_eval): every window's ``info`` carries eval_bound, need_eval_first, n_eval, eval_rounds and
         eval_certified, and a group that still calibrates is calibrated first and then runs the library call.
-        ``rtg``: None, a float, or one value per window.  Returns (E, A)."""
+        ``rtg``: None, a float, or one value per window.  Returns (E, A).
+        A planner built with ``refine=...`` plans every window by refinement instead, whatever ``lockstep`` says (one
+        m3pc_refine_plans call per group of one effective horizon); ``keys``: one hashable per window naming the caller (an
+        environment) whose warm-start memory the window continues -- default: the list position."""
+        if self._refine is not None:
+            if eval:
+                assert rtg is not None
+            sa, ev = self._refine_windows(sequence_histories, percentage, eval, rtg, keys)
+            return ev if eval else sa
         if lockstep and lockstep != "native" and self._eval_tol is not None:
             raise ValueError("eval_tol: the eval_action certificate has no lock-step form in Python; its lock-step form is the library's "
                              "(m3pc_plan_steps_certified_eval): use action_sample_batch(lockstep=\"native\"), lockstep=False, or a "
@@ -1152,6 +1249,9 @@ class HipPlanner(GoalMixin, LockstepMixin):
         """learner.py:329-417 (the ``horizon`` argument is ignored there too: cfg.horizon rules)."""
         if eval:
             assert rtg is not None
+        if plan and self._refine is not None:
+            sa, ev = self._refine_windows([sequence_history], percentage, eval, rtg, ["action_sample"])
+            return ev[0] if eval else sa
         if plan:
             guidance = self.cfg.plan_guidance
             assert guidance in _MODES, guidance

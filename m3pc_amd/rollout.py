@@ -109,8 +109,11 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
         for ep in live:
             ep.traj["observations"][ep.timestep] = ep.observation
         rtgs = [float(episode_rtg_ref[ep.timestep] * ratio) for ep in live] if eval else None
+        # (a planner that plans by refinement keeps a warm start per environment: `live` shrinks as episodes end, so the
+        # environments are named by their index, not by their position in this round)
+        named = dict(keys=[ep.index for ep in live]) if getattr(planner, "_refine", None) is not None else {}
         acts = planner.action_sample_batch([ep.traj for ep in live], percentage=percentage, eval=eval, rtg=rtgs,
-                                           lockstep="native" if lockstep == "native" else True)
+                                           lockstep="native" if lockstep == "native" else True, **named)
         for info in planner.last["windows"] if with_eval else ():
             note(info)
         for ep, action in zip(live, acts.cpu().numpy()):  # one read-back per round
