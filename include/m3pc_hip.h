@@ -48,7 +48,8 @@ extern "C" {
  * m3pc_plan_steps_certified (a lock-step batch of certified steps); then m3pc_eval_bound, m3pc_plan_step_certified_eval and
  * m3pc_eval_record (the eval_action certificate); then m3pc_plan_step_certified_eval_begin / _eval_end and
  * m3pc_plan_steps_certified_eval (that certificate in the pipelined and the lock-step step); then m3pc_refine_plans (the
- * refinement of a lock-step batch of windows, with a shifted warm start).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * refinement of a lock-step batch of windows, with a shifted warm start); then m3pc_episodes_create / _destroy / _reset / _observe /
+ * _record / _windows / _values / _export and the opaque m3pc_episodes (the episode store).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -770,6 +771,70 @@ int m3pc_refine_plans(m3pc_handle* h, const m3pc_plan_args* args, const m3pc_ref
                       const float* noise, const unsigned long long* steps,
                       float* mean, float* std, float* candidates, float* scores, int* elites,
                       float* sample_action, float* eval_action, void* stream);
+
+/* THE EPISODE STORE: the rollout histories of n_envs environments on the device, and their windows assembled there.  It replaces the
+ * episode buffer every caller of the reference keeps on the host -- current_trajectory of ReplayBuffer.online_rollout
+ * (finetune_omtm/replay_buffer.py:189-243) and of Learner.evaluate_plan (learner.py:660-700), and the way-point buffer of the zero-shot
+ * rollout (zeroshot_omtm/learner.py:515-603) -- together with the window rules of action_sample (finetune_omtm/learner.py:342-366) and
+ * action_piid_sample (zeroshot_omtm/learner.py:164-223), which a host would otherwise restate.
+ *   Storage, fp32, one array per key, so that a trajectory is three contiguous blocks: obs (n_envs, max_steps, S), act (n_envs,
+ *   max_steps, A), rew (n_envs, max_steps), and int32 path_length (n_envs) with a host mirror.  The host makes every call that changes a
+ *   path length, so the mirror is always what the calls made so far leave behind and no entry point reads the device.
+ *   A store is created on a handle, from which it takes S, A, T and the device; it needs no weights and does not refer to the handle
+ *   afterwards.  m3pc_episodes_create makes no HIP call: the storage is allocated, and zeroed in stream order, by the first call that
+ *   enqueues work.  A store is not re-entrant; its calls are ordered on the device by the caller (one stream, or events).
+ *   Everything is stream-ordered: no entry point waits for the device or synchronises it (m3pc_episodes_destroy drains).  Host
+ *   arguments -- env_ids always; observations, actions, rewards and tables when on_device == 0 -- are consumed before the call returns:
+ *   they are copied into pinned, device-visible blocks of the store that the kernels read directly.  A block is used again once the work
+ *   that read it has run; while none is free another is allocated, so the host never waits, however many ids a call brings.
+ *   env_ids: host int32 (n,), or NULL for the environments 0 .. n-1.
+ *   Kernels: gathers and scatters over a flat element index, coalesced across a row's features for any row width; no atomics; the one
+ *   reduction (values) runs in a fixed order: results are bit-identical from run to run.
+ * Refused with M3PC_EINVAL before any HIP call: null required pointers, n_envs < 1, max_steps < T, n outside [1, n_envs], an id outside
+ * [0, n_envs) or repeated within one call, a mode other than M3PC_WINDOW_*, horizon outside [1, T], clip_min > clip_max (or a NaN
+ * among them), a non-finite or negative discount, env outside [0, n_envs).  Refused with M3PC_ESTATE, with nothing written and no path
+ * length changed: observe, record or windows on an environment whose path_length == max_steps -- a full episode is a refusal, never an
+ * out-of-range access (the window of such an episode would take store row max_steps). */
+typedef struct m3pc_episodes m3pc_episodes;
+#define M3PC_WINDOW_PLAN 0  /* action_sample:      finetune_omtm/learner.py:342-366 */
+#define M3PC_WINDOW_GOAL 1  /* action_piid_sample: zeroshot_omtm/learner.py:164-223 */
+int m3pc_episodes_create(m3pc_handle* h, int n_envs, int max_steps, m3pc_episodes** out);
+int m3pc_episodes_destroy(m3pc_episodes* ep);
+/* The start of an episode (replay_buffer.py:189-203, learner.py:660-674: fresh zero arrays, path_length 0): the three blocks of every
+ * listed environment zeroed, its path length 0.  obs_table, optional: (n, max_steps, S), one table per listed environment, float32 or
+ * float64 (table_f64; rounded as NumPy's assignment into a float32 array rounds), host or device (on_device): the observation block
+ * starts out as this table -- the held way-points of the zero-shot rollout (zeroshot_omtm/learner.py:515-539). */
+int m3pc_episodes_reset(m3pc_episodes* ep, const int* env_ids, int n, const void* obs_table, int table_f64, int on_device, void* stream);
+/* current_trajectory["observations"][timestep] = observation (replay_buffer.py:206, learner.py:683): obs[e, path_length[e], :] = row i
+ * of obs (n, S), float32 or float64 (obs_f64), host or device (on_device).  The path length stays. */
+int m3pc_episodes_observe(m3pc_episodes* ep, const int* env_ids, int n, const void* obs, int obs_f64, int on_device, void* stream);
+/* action = np.clip(action, clip_min, clip_max); current_trajectory["actions"][timestep] = action; ["rewards"][timestep] = reward;
+ * path_length += 1 (replay_buffer.py:213-229, learner.py:690-697): act[e, path_length[e], :] = min(max(a, clip_min), clip_max) with the
+ * bits of np.clip (NaN stays, the sign of a zero is kept), rew[e, path_length[e]] = r, then path_length[e] += 1.
+ * actions (n, A), rewards (n,) float32, both host or both device (on_device). */
+int m3pc_episodes_record(m3pc_episodes* ep, const int* env_ids, int n, const float* actions, const float* rewards, float clip_min,
+                         float clip_max, int on_device, void* stream);
+/* The windows of n environments: states (n,T,S), actions (n,T,A), rewards (n,T,1) device out -- the layouts m3pc_plan_steps_certified,
+ * m3pc_refine_plans, m3pc_policy_pass_batch and m3pc_goal_step_batch take, so the output feeds them with no copy in between.
+ * With end = path_length[e] and H = horizon:  h = H if end + H >= T else T - end;  hl = T - h + 1;  lo = end - hl + 1.
+ *   M3PC_WINDOW_PLAN (finetune_omtm/learner.py:342-366): rows t < hl of all three keys are store rows lo + t -- row `end` of act / rew is
+ *   whatever the store holds there, zero after a reset; the reference copies it too --, rows t >= hl are zero.
+ *   M3PC_WINDOW_GOAL (zeroshot_omtm/learner.py:164-223): actions and rewards as above; states[t] = obs[lo + t] for t < smart =
+ *   T - max(0, end + h - max_steps) -- the future rows are way-points -- and zero behind; max_steps stands where the reference has the
+ *   literal 1000.
+ * horizons, optional: host out (n,), the effective h of every window, from the mirror -- valid on return; windows that go into one
+ * batched call share it. */
+int m3pc_episodes_windows(m3pc_episodes* ep, const int* env_ids, int n, int mode, int horizon, float* states, float* actions, float* rewards,
+                          int* horizons, void* stream);
+/* The discounted values ReplayBuffer.online_rollout hands to update_buffer (replay_buffer.py:234-243, discounts: :70), M = max_steps:
+ *   V[t] = sum_{j=0}^{M-t-2} rew[t+1+j] discount^j, formed in float64 by the reverse recurrence V[t] = rew[t+1] + discount V[t+1],
+ *   V[M-1] = 0, stored as float32;  use_avg != 0: the stored value is fp32(fp64(fp32(V[t])) / (M - t)).
+ * values: device out (n, max_steps).  One thread per environment. */
+int m3pc_episodes_values(m3pc_episodes* ep, const int* env_ids, int n, double discount, int use_avg, float* values, void* stream);
+/* One environment's blocks -- obs (max_steps, S), act (max_steps, A), rew (max_steps), each optional -- copied to caller buffers on the
+ * device (on_device != 0) or on the host (complete once the stream has been synchronised), and its path length (host out, optional,
+ * from the mirror: valid on return).  What new_trajectories carries out of online_rollout (replay_buffer.py:245-250). */
+int m3pc_episodes_export(m3pc_episodes* ep, int env, float* obs, float* act, float* rew, int* path_length, int on_device, void* stream);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

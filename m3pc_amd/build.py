@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libm3pc_hip.so")
 SOURCES = ["gemm.hip", "gemm_x3.hip", "gemm_glds.hip", "gemm_big.hip", "gemm_line.hip", "gemm_f32_direct.hip", "block_fused.hip", "attn.hip",
-           "attn_bf16.hip", "elementwise.hip", "select.hip", "refine.hip", "m3pc_plans.hip", "m3pc_passes.hip", "m3pc.hip", "m3pc_certified.hip"]
+           "attn_bf16.hip", "elementwise.hip", "select.hip", "refine.hip", "m3pc_plans.hip", "m3pc_passes.hip", "m3pc.hip", "m3pc_certified.hip",
+           "episodes.hip"]
 # the lab build (libm3pc_hip_lab.so, `python -m m3pc_amd.build --lab`, used by tools/ with M3PC_LIB=...): adds the experimental
 # GEMM tilings, the timing variants of block_fused.hip, the M3PC_GEMM_VARIANT environment override (-DM3PC_LAB) and the kernel-level
 # hooks of include/m3pc_hip_debug.h (m3pc_debug.hip)

@@ -50,6 +50,8 @@ EXPORTS = (
     "m3pc_eval_bound", "m3pc_plan_step_certified_eval",
     "m3pc_plan_step_certified_eval_begin", "m3pc_plan_step_certified_eval_end", "m3pc_plan_steps_certified_eval",
     "m3pc_refine_plans",
+    "m3pc_episodes_create", "m3pc_episodes_destroy", "m3pc_episodes_reset", "m3pc_episodes_observe", "m3pc_episodes_record",
+    "m3pc_episodes_windows", "m3pc_episodes_values", "m3pc_episodes_export",
 )
 
 
@@ -103,6 +105,7 @@ REFINE_WEIGHTINGS = {"cem": REFINE_CEM, "mppi": REFINE_MPPI}
 PLAN_DEFER_JOIN = 1
 PLAN_PRUNED_POLICY = 2
 PLAN_INPUTS_READY = 4
+WINDOW_PLAN, WINDOW_GOAL = 0, 1  # M3PC_WINDOW_*: the window rule of m3pc_episodes_windows
 
 
 class M3pcError(RuntimeError):
@@ -176,6 +179,14 @@ def load_library(path: Optional[str] = None):
         "m3pc_refine_plan": [vp, C.POINTER(PlanArgs), C.POINTER(RefineArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "m3pc_refine_plans": [vp, C.POINTER(PlanArgs), C.POINTER(RefineArgs), i, vp, vp, vp, C.POINTER(d), vp, i, C.POINTER(i), i, vp,
                               C.POINTER(C.c_ulonglong), vp, vp, vp, vp, vp, vp, vp, vp],
+        "m3pc_episodes_create": [vp, i, i, C.POINTER(vp)],
+        "m3pc_episodes_destroy": [vp],
+        "m3pc_episodes_reset": [vp, C.POINTER(i), i, vp, i, i, vp],
+        "m3pc_episodes_observe": [vp, C.POINTER(i), i, vp, i, i, vp],
+        "m3pc_episodes_record": [vp, C.POINTER(i), i, vp, vp, f, f, i, vp],
+        "m3pc_episodes_windows": [vp, C.POINTER(i), i, i, i, vp, vp, vp, C.POINTER(i), vp],
+        "m3pc_episodes_values": [vp, C.POINTER(i), i, d, i, vp, vp],
+        "m3pc_episodes_export": [vp, i, vp, vp, vp, C.POINTER(i), i, vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }

@@ -125,7 +125,8 @@ class GoalMixin:
         return torch.tanh(eps * sd + mu)
 
     @torch.no_grad()
-    def action_piid_sample_batch(self, sequence_histories, percentage=1.0, eval=True, rtg=None, pruned: Optional[bool] = None):
+    def action_piid_sample_batch(self, sequence_histories, percentage=1.0, eval=True, rtg=None, pruned: Optional[bool] = None,
+                                 store=None, env_ids=None):
         """E independent goal-reaching windows per launch (BASELINE config 5 / SURVEY §8 f1): the reference plans one
         env per call (zeroshot learner.py:151-261, unseen.py rollout loop); here the windows that share a horizon go
         through the pi and fid forwards as ONE batch of the same kernels.  Per window the arithmetic is that of
@@ -133,30 +134,44 @@ class GoalMixin:
         pruned=False (default up to 64 windows): the fp32 few-row kernels of ``action_piid_sample`` on the whole batch
         (``max_batch >= E``; ``last["state_inference"]`` holds every window's full states head).
         pruned=True (default beyond, needs ``goal_batch >= E``): the exactly pruned many-window path in the planner's
-        precision (``goal_actions``)."""
+        precision (``goal_actions``).
+        ``store``: an ``episodes.EpisodeStore`` holding the histories (way-points included) on the device: the windows of its
+        environments ``env_ids`` (None: all) are assembled there (m3pc_episodes_windows, M3PC_WINDOW_GOAL) -- no per-window host
+        loop and no H2D copy; ``sequence_histories`` is then ignored (pass None).  The windows are the bits of the host path's
+        (for a store of 1000 steps, the reference's buffer length), so the results are too."""
         if eval:
             assert rtg is not None
         from .masks import create_fid_mask, create_pi_mask, mask_rows
-        T, E = self.T, len(sequence_histories)
+        T = self.T
         S, A = self.S, self.A
+        win = None if store is None else store.windows(env_ids, horizon=int(self.cfg.horizon), mode="goal")
+        E = len(sequence_histories) if win is None else win[0].shape[0]
         if pruned is None:
             pruned = E > 64 or E > self._max_batch
         if pruned and E > self._goal_batch:
             raise ValueError(f"{E} windows through the pruned path need HipPlanner(..., goal_batch >= {E})"
                              + (f" (or, up to 64 windows, max_batch >= {E} for the un-pruned fp32 path: max_batch is {self._max_batch})"
                                 if E <= 64 else ""))
-        host = np.empty((E, T * (S + A + 1)), dtype=np.float32)
-        meta = [self._goal_window_host(hst, rtg, percentage, host[i]) for i, hst in enumerate(sequence_histories)]
-        dev = torch.from_numpy(host).to(self.device)  # one packed H2D copy for all windows
+        if win is None:
+            host = np.empty((E, T * (S + A + 1)), dtype=np.float32)
+            meta = [self._goal_window_host(hst, rtg, percentage, host[i]) for i, hst in enumerate(sequence_histories)]
+            dev = torch.from_numpy(host).to(self.device)  # one packed H2D copy for all windows
+        else:
+            rtg_v = self._rtg_value(rtg, percentage)
+            meta = [(int(h), rtg_v) for h in win[3]]
         out = torch.empty((E, self.A), dtype=torch.float32, device=self.device)
         infer = [None] * E
         self._drain()
         for h in sorted({m[0] for m in meta}):
             ids = [i for i, m in enumerate(meta) if m[0] == h]
             idx = T - h
-            sel = dev if len(ids) == E else dev[torch.tensor(ids, device=self.device)]
-            s = sel[:, : T * S].reshape(-1, T, S).contiguous()
-            a = sel[:, T * S : T * (S + A)].reshape(-1, T, A).contiguous()
+            if win is None:
+                sel = dev if len(ids) == E else dev[torch.tensor(ids, device=self.device)]
+                s = sel[:, : T * S].reshape(-1, T, S).contiguous()
+                a = sel[:, T * S : T * (S + A)].reshape(-1, T, A).contiguous()
+            else:
+                sel = None
+                s, a, r = win[:3] if len(ids) == E else [x[torch.tensor(ids, device=self.device)] for x in win[:3]]
             if pruned:
                 act = self.goal_actions(s, a, h, eval=eval)
                 if len(ids) == E:
@@ -164,7 +179,8 @@ class GoalMixin:
                 else:
                     out[torch.tensor(ids, device=self.device)] = act
                 continue
-            r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
+            if sel is not None:
+                r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
             mu, sd, inferred, _ = self.handle.goal_step(s, a, r, [meta[i][1] for i in ids], mask_rows(create_pi_mask(T, "cpu", idx)),
                                                         mask_rows(create_fid_mask(T, "cpu", idx)), idx)
             dist_ = SquashedNormal(mu.unsqueeze(2), sd.unsqueeze(2))

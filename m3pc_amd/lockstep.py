@@ -20,7 +20,7 @@ _MODES = {"rtg_guiding": capi.MODE_RTG, "critic_lambda_guiding": capi.MODE_CRITI
 
 class LockstepMixin:
     def _action_sample_lockstep(self, sequence_histories, percentage=1.0, eval=False, rtg=None, onepass: bool = False,
-                                native: bool = False):
+                                native: bool = False, store=None, env_ids=None):
         if native and self.precision in capi.LOW_PRECISION and self.rescore != "bound":
             # (the call runs the certificate protocol on a low-precision pass; rescore="topk" / "none" select differently)
             raise ValueError(f"lockstep='native' runs the certified re-score (rescore='bound') behind a low-precision candidate pass; "
@@ -31,15 +31,24 @@ class LockstepMixin:
         assert guidance in _MODES, guidance
         mode = _MODES[guidance]
         lmbda = 0.6 if guidance == "rtg_guiding" else float(cfg.lmbda)  # learner.py:405-407
-        E, T, S, A, N = len(sequence_histories), self.T, self.S, self.A, int(cfg.action_samples)
+        T, S, A, N = self.T, self.S, self.A, int(cfg.action_samples)
+        win = None
+        if store is not None:
+            # the windows come from the episode store (m3pc_episodes_windows: assembled on the device, the bits of _window_host),
+            # the horizons from its mirror of the path lengths
+            win = store.windows(env_ids, horizon=int(cfg.horizon), mode="plan")
+        E = len(sequence_histories) if win is None else win[0].shape[0]
         rtgs = [rtg] * E if (rtg is None or np.isscalar(rtg)) else list(rtg)
         if eval:
             assert all(r is not None for r in rtgs)
-        host = np.empty((E, T * (S + A + 1)), dtype=np.float32)
-        meta = []
-        for i, hst in enumerate(sequence_histories):
-            meta.append(self._window_host(hst, rtgs[i], percentage, host[i]))
-        dev = torch.from_numpy(host).to(self.device)  # one packed H2D copy for all windows
+        if win is None:
+            host = np.empty((E, T * (S + A + 1)), dtype=np.float32)
+            meta = []
+            for i, hst in enumerate(sequence_histories):
+                meta.append(self._window_host(hst, rtgs[i], percentage, host[i]))
+            dev = torch.from_numpy(host).to(self.device)  # one packed H2D copy for all windows
+        else:
+            meta = [(int(h), self._rtg_value(rtgs[i], percentage)) for i, h in enumerate(win[3])]
         out = torch.empty((E, A), dtype=torch.float32, device=self.device)
         info = [None] * E
         groups = []
@@ -47,10 +56,13 @@ class LockstepMixin:
             same = [i for i, m in enumerate(meta) if m[0] == h]
             groups += [(h, same[c0 : c0 + self._max_batch]) for c0 in range(0, len(same), self._max_batch)]
         for h, ids in groups:
-            sel = dev if len(ids) == E else dev[torch.tensor(ids, device=self.device)]
-            s = sel[:, : T * S].reshape(-1, T, S).contiguous()
-            a = sel[:, T * S : T * (S + A)].reshape(-1, T, A).contiguous()
-            r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
+            if win is None:
+                sel = dev if len(ids) == E else dev[torch.tensor(ids, device=self.device)]
+                s = sel[:, : T * S].reshape(-1, T, S).contiguous()
+                a = sel[:, T * S : T * (S + A)].reshape(-1, T, A).contiguous()
+                r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
+            else:
+                s, a, r = win[:3] if len(ids) == E else [x[torch.tensor(ids, device=self.device)] for x in win[:3]]
             Eg = len(ids)
             eps = self._eps((Eg, N, h, A)) if mode == capi.MODE_NOISE else self._eps((Eg, N, T, A))
             # lockstep="native": the whole group in ONE library call (m3pc_plan_steps_certified).  While the weight load's

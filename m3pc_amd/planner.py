@@ -1136,19 +1136,29 @@ class HipPlanner(GoalMixin, LockstepMixin):
         else:
             self._warm.pop(key, None)
 
-    def _refine_windows(self, sequence_histories, percentage, eval, rtg, keys):
+    def _refine_windows(self, sequence_histories, percentage, eval, rtg, keys, store=None, env_ids=None):
         """The plan of E windows by refinement (``refine=...``): one ``cem_guiding_batch`` per group of one effective horizon,
         warm-started per caller key.  Returns (sample_action (E,A), eval_action (E,A))."""
         rf = self._refine
         self._drain()
-        E, T, S, A = len(sequence_histories), self.T, self.S, self.A
+        T, S, A = self.T, self.S, self.A
+        win = None
+        if store is not None:  # (the windows of an episode store: assembled on the device, path lengths from its mirror)
+            win = store.windows(env_ids, horizon=int(self.cfg.horizon), mode="plan")
+            ends_all = [int(v) for v in (store.path_length if env_ids is None else store.path_length[np.asarray(env_ids, dtype=np.int64)])]
+        else:
+            ends_all = [int(hst["path_length"]) for hst in sequence_histories]
+        E = len(ends_all)
         keys = list(range(E)) if keys is None else list(keys)
         if len(keys) != E or len(set(keys)) != E:
             raise ValueError("keys: one distinct key per window")
         rtgs = [rtg] * E if (rtg is None or np.isscalar(rtg)) else list(rtg)
-        host = np.empty((E, T * (S + A + 1)), dtype=np.float32)
-        meta = [self._window_host(hst, rtgs[i], percentage, host[i]) for i, hst in enumerate(sequence_histories)]
-        dev = torch.from_numpy(host).to(self.device)  # one packed H2D copy for all windows
+        if win is None:
+            host = np.empty((E, T * (S + A + 1)), dtype=np.float32)
+            meta = [self._window_host(hst, rtgs[i], percentage, host[i]) for i, hst in enumerate(sequence_histories)]
+            dev = torch.from_numpy(host).to(self.device)  # one packed H2D copy for all windows
+        else:
+            meta = [(int(h), self._rtg_value(rtgs[i], percentage)) for i, h in enumerate(win[3])]
         sa = torch.empty((E, A), dtype=torch.float32, device=self.device)
         ev = torch.empty((E, A), dtype=torch.float32, device=self.device)
         info = [None] * E
@@ -1157,12 +1167,15 @@ class HipPlanner(GoalMixin, LockstepMixin):
             same = [i for i, m in enumerate(meta) if m[0] == h]
             groups += [(h, same[c0 : c0 + self._max_batch]) for c0 in range(0, len(same), self._max_batch)]
         for h, ids in groups:
-            sel = dev if len(ids) == E else dev[torch.tensor(ids, device=self.device)]
-            s = sel[:, : T * S].reshape(-1, T, S).contiguous()
-            a = sel[:, T * S : T * (S + A)].reshape(-1, T, A).contiguous()
-            r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
+            if win is None:
+                sel = dev if len(ids) == E else dev[torch.tensor(ids, device=self.device)]
+                s = sel[:, : T * S].reshape(-1, T, S).contiguous()
+                a = sel[:, T * S : T * (S + A)].reshape(-1, T, A).contiguous()
+                r = sel[:, T * (S + A) :].reshape(-1, T, 1).contiguous()
+            else:
+                s, a, r = win[:3] if len(ids) == E else [x[torch.tensor(ids, device=self.device)] for x in win[:3]]
             # the shifted warm start: the key's last final mean (h_prev rows) read from row 1 on
-            ends = [int(sequence_histories[i]["path_length"]) for i in ids]
+            ends = [ends_all[i] for i in ids]
             rows = []
             for i, end in zip(ids, ends):
                 prev = self._warm.get(keys[i]) if rf["warm"] else None
@@ -1188,7 +1201,8 @@ class HipPlanner(GoalMixin, LockstepMixin):
         return sa, ev
 
     @torch.no_grad()
-    def action_sample_batch(self, sequence_histories, percentage=1.0, eval=False, rtg=None, lockstep: bool = False, keys=None):
+    def action_sample_batch(self, sequence_histories, percentage=1.0, eval=False, rtg=None, lockstep: bool = False, keys=None,
+                            store=None, env_ids=None):
         """``action_sample(history, plan=True)`` for E environments.  The reference steps one environment at a
         time (replay_buffer.py:204-232, learner.py:681-691: one action_sample per env step, the action read back each time).
         Default: the E windows are E plan steps issued back to back through ``plan_async`` -- ``pipeline_depth`` of them in
@@ -1210,11 +1224,19 @@ class HipPlanner(GoalMixin, LockstepMixin):
         ``rtg``: None, a float, or one value per window.  Returns (E, A).
         A planner built with ``refine=...`` plans every window by refinement instead, whatever ``lockstep`` says (one
         m3pc_refine_plans call per group of one effective horizon); ``keys``: one hashable per window naming the caller (an
-        environment) whose warm-start memory the window continues -- default: the list position."""
+        environment) whose warm-start memory the window continues -- default: the list position.
+        ``store``: an ``episodes.EpisodeStore`` that holds the histories on the device -- the windows of its environments
+        ``env_ids`` (None: all of them, in order) are assembled there (m3pc_episodes_windows) instead of on the host from
+        ``sequence_histories`` (then ignored: pass None), the horizons come from its mirror of the path lengths.  The windows are
+        the bits of the host path's, and everything behind them is the same code: the same results, bit for bit.  Served by the
+        lock-step forms and by a ``refine=...`` planner."""
+        if store is not None and not lockstep and self._refine is None:
+            raise ValueError("store=: the windows of an episode store feed the lock-step forms (lockstep=True / 'onepass' / 'native') "
+                             "and a refine=... planner; the pipelined default plans host histories")
         if self._refine is not None:
             if eval:
                 assert rtg is not None
-            sa, ev = self._refine_windows(sequence_histories, percentage, eval, rtg, keys)
+            sa, ev = self._refine_windows(sequence_histories, percentage, eval, rtg, keys, store, env_ids)
             return ev if eval else sa
         if lockstep and lockstep != "native" and self._eval_tol is not None:
             raise ValueError("eval_tol: the eval_action certificate has no lock-step form in Python; its lock-step form is the library's "
@@ -1222,7 +1244,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                              "planner without eval_tol")
         if lockstep:
             return self._action_sample_lockstep(sequence_histories, percentage, eval, rtg, onepass=lockstep == "onepass",
-                                                native=lockstep == "native")
+                                                native=lockstep == "native", store=store, env_ids=env_ids)
         E, A = len(sequence_histories), self.A
         rtgs = [rtg] * E if (rtg is None or np.isscalar(rtg)) else list(rtg)
         out = torch.empty((E, A), dtype=torch.float32, device=self.device)

@@ -41,7 +41,8 @@ class _Episode:
 
 def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: float = 1.0, max_steps: int = 1000,
                   in_flight: Optional[int] = None, on_step: Optional[Callable] = None, eval: bool = True,
-                  percentage: float = 1.0, lockstep=False) -> Dict[str, Any]:
+                  percentage: float = 1.0, lockstep=False, store=False, discount: Optional[float] = None,
+                  use_avg: bool = False) -> Dict[str, Any]:
     """One evaluation episode in each of ``envs`` (learner.py:645-741 with num_episodes = len(envs)), planned through the
     pipelined planner.  ``episode_rtg_ref[t] * ratio`` is the return-to-go handed to the planner at timestep t (learner.py:
     688); with ``eval=False`` the planner explores as ``online_rollout`` does (sampled action, return-to-go from the
@@ -56,8 +57,17 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
     (``action_sample_batch(lockstep="native")``), the lock-step form a planner with ``eval_tol`` takes.  Returns {"return_mean", "return_std", "length_mean", "length_std", "returns",
     "lengths", "trajectories", "plan_steps"} -- the statistics evaluate_plan logs (learner.py:715-731); with a planner built with
     ``eval_tol`` also "eval_bound_max" (the largest per-step bound on |eval_action - the fp32 step's|) and "eval_steps_everything"
-    (the steps that scored every candidate in fp32)."""
+    (the steps that scored every candidate in fp32).
+    store: True (or an ``episodes.EpisodeStore`` of at least len(envs) environments and ``max_steps`` steps) keeps the episodes on
+    the device (lock-step forms only): per round ONE observe, one planning call fed by the store's windows, one record (which
+    clips as the host loop does); per environment the actions, rewards and lengths are those of the same call without the store,
+    bit for bit.  ``trajectories[i]`` is exported from the store at the end, with ``values`` filled as ReplayBuffer.online_rollout
+    fills them (replay_buffer.py:234-243) for ``discount`` (default: the planner's cfg.discount) and ``use_avg``; without a store
+    ``values`` stays zero, as before."""
     from . import capi
+
+    if store and not lockstep:
+        raise ValueError("store=: the episode store feeds the lock-step forms (lockstep=True / 'native')")
 
     E = len(envs)
     S, A = planner.S, planner.A
@@ -104,6 +114,47 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
         if not ep.done and ep.timestep < max_steps:
             waiting.append(ep)
 
+    st = None
+    if store:
+        from .episodes import EpisodeStore
+        st = EpisodeStore(planner, E, max_steps) if store is True else store
+        if st.n_envs < E or st.max_steps != max_steps:
+            raise ValueError(f"store: {st.n_envs} environments x {st.max_steps} steps, the rollout needs >= {E} x {max_steps}")
+        st.reset(list(range(E)))
+    while st is not None and waiting:
+        live, waiting = waiting, []
+        ids = [ep.index for ep in live]
+        st.observe(np.stack([np.asarray(ep.observation) for ep in live]), ids)
+        rtgs = [float(episode_rtg_ref[ep.timestep] * ratio) for ep in live] if eval else None
+        named = dict(keys=ids) if getattr(planner, "_refine", None) is not None else {}
+        acts = planner.action_sample_batch(None, percentage=percentage, eval=eval, rtg=rtgs,
+                                           lockstep="native" if lockstep == "native" else True, store=st, env_ids=ids, **named)
+        for info in planner.last["windows"] if with_eval else ():
+            note(info)
+        acts = acts.cpu().numpy()  # one read-back per round
+        rewards = np.empty((len(live),), dtype=np.float32)
+        for j, ep in enumerate(live):
+            obs, reward, done, info = ep.env.step(np.clip(acts[j], -1, 1))  # learner.py:690 / replay_buffer.py:213-215
+            rewards[j] = reward
+            ep.traj["total_return"] += reward
+            ep.observation = obs
+            ep.timestep += 1
+            ep.done, ep.info = bool(done), info
+            steps += 1
+            if on_step is not None:
+                on_step(ep.index, ep.timestep, np.clip(acts[j], -1, 1), reward, done)
+            if not ep.done and ep.timestep < max_steps:
+                waiting.append(ep)
+        st.record(acts, rewards, ids, clip_min=-1.0, clip_max=1.0)
+    if st is not None:
+        gamma = float(planner.cfg.discount) if discount is None else float(discount)
+        vals = st.values(gamma, use_avg, list(range(E)))
+        for ep in eps_:
+            total = ep.traj["total_return"]
+            ep.traj = st.trajectory(ep.index, vals[ep.index])
+            ep.traj["total_return"] = total
+        if store is True:
+            st.close()
     while lockstep and waiting:
         live, waiting = waiting, []
         for ep in live:

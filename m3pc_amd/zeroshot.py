@@ -81,10 +81,37 @@ class WaypointFollower:
         traj["path_length"] = timestep
         return np.clip(self._call(traj, rtg).cpu().numpy(), -1, 1)
 
+    def new_store(self, n_envs: int):
+        """An ``episodes.EpisodeStore`` of n_envs environments of 1000 steps whose observation blocks start out as the (held)
+        way-points: ``new_trajectory`` for every environment, on the device."""
+        from .episodes import EpisodeStore
+        store = EpisodeStore(self.planner, n_envs, self.waypoints.shape[0])
+        for e in range(n_envs):
+            store.reset([e], self.waypoints)
+        return store
+
     def act_batch(self, trajs: Sequence[dict], observations: Sequence[np.ndarray], timesteps: Sequence[int],
-                  rtgs: Sequence[float]) -> np.ndarray:
+                  rtgs: Sequence[float], store=None, env_ids=None) -> np.ndarray:
         """E environments per call (two-stage mode): rows of the returned (E, A) array are what ``act`` returns per env.
-        One rtg per call in the batched kernel path: windows are grouped by rtg value."""
+        One rtg per call in the batched kernel path: windows are grouped by rtg value.
+        store (two-stage mode; ``new_store``): the episodes live in an episode store -- ONE observe for the E observations, the
+        windows assembled on the device; ``trajs`` is ignored (pass None), ``env_ids`` names the store's environments (None:
+        0 .. E-1), and ``timesteps`` must be their path lengths (``store.record`` advances them).  Same actions as without it."""
+        if store is not None:
+            if self.mode != "two_stage":
+                raise ValueError("store=: the episode store serves the two-stage mode (goal_mask='piid')")
+            ids = np.arange(len(observations)) if env_ids is None else np.asarray(env_ids).reshape(-1)
+            if [int(t) for t in timesteps] != [int(v) for v in store.path_length[ids]]:
+                raise ValueError("store=: timesteps must equal the store's path lengths of env_ids")
+            store.observe(np.stack([np.asarray(o) for o in observations]), ids)
+            out = np.empty((len(ids), self.planner.A), dtype=np.float32)
+            groups: Dict[float, List[int]] = {}
+            for i, g in enumerate(rtgs):
+                groups.setdefault(float(g), []).append(i)
+            for g, sel in groups.items():
+                acts = self.planner.action_piid_sample_batch(None, percentage=1.0, eval=True, rtg=g, store=store, env_ids=ids[sel])
+                out[sel] = acts.cpu().numpy()
+            return np.clip(out, -1, 1)
         if self.mode != "two_stage":
             return np.stack([self.act(tr, o, t, g) for tr, o, t, g in zip(trajs, observations, timesteps, rtgs)])
         for tr, o, t in zip(trajs, observations, timesteps):
