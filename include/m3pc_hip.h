@@ -49,7 +49,9 @@ extern "C" {
  * m3pc_eval_record (the eval_action certificate); then m3pc_plan_step_certified_eval_begin / _eval_end and
  * m3pc_plan_steps_certified_eval (that certificate in the pipelined and the lock-step step); then m3pc_refine_plans (the
  * refinement of a lock-step batch of windows, with a shifted warm start); then m3pc_episodes_create / _destroy / _reset / _observe /
- * _record / _windows / _values / _export and the opaque m3pc_episodes (the episode store).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * _record / _windows / _values / _export and the opaque m3pc_episodes (the episode store); then m3pc_replay_create / _destroy / _append /
+ * _append_transitions / _push_episodes / _sample_segments / _sample_transitions / _values_up_bound / _counts / _path_lengths and the
+ * opaque m3pc_replay (the replay buffer).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -835,6 +837,103 @@ int m3pc_episodes_values(m3pc_episodes* ep, const int* env_ids, int n, double di
  * device (on_device != 0) or on the host (complete once the stream has been synchronised), and its path length (host out, optional,
  * from the mirror: valid on return).  What new_trajectories carries out of online_rollout (replay_buffer.py:245-250). */
 int m3pc_episodes_export(m3pc_episodes* ep, int env, float* obs, float* act, float* rew, int* path_length, int on_device, void* stream);
+
+/* THE REPLAY BUFFER: ReplayBuffer of finetune_omtm/replay_buffer.py on the device -- what the episodes of the store are handed to, and
+ * where the training batches of the fine-tuning loop (finetune_omtm/finetune.py:281-310) come from, as device arrays a training loop on
+ * the same GPU reads in place.
+ *   Storage.  A trajectory ring of traj_capacity slots: obs (C, max_steps, S), act (C, max_steps, A), rew (C, max_steps) float32, val (C,
+ *   max_steps) FLOAT64 (values_segmented is float64 in the reference, and traj_sample returns "returns" as float64), int32 path_length (C).
+ *   Two transition rings, M3PC_REPLAY_OFFLINE and M3PC_REPLAY_ONLINE, each of its own capacity: state (cap, S), action (cap, A), reward,
+ *   next_state (cap, S), done, float32 -- deque(maxlen=...) of :101-102.  A capacity of 0 leaves that part out.  In every ring logical
+ *   index 0 is the oldest entry and logical index i is physical slot (head + i) % capacity; every index of this interface is logical.
+ *   A buffer is created on a handle, from which it takes S, A and the device; it needs no weights and does not refer to the handle
+ *   afterwards.  m3pc_replay_create makes no HIP call: the storage is allocated by the first call that enqueues work.  A buffer is not
+ *   re-entrant; its calls are ordered on the device by the caller (one stream, or events).  Everything is stream-ordered: no entry point
+ *   waits for the device (m3pc_replay_destroy drains).  Host arguments are consumed before the call returns, through the pinned,
+ *   device-visible staging blocks the episode store uses.  The host mirrors counts, ring heads and path lengths -- it makes every call
+ *   that changes one -- so validation and the readers (m3pc_replay_counts, m3pc_replay_path_lengths) never read the device.
+ *   Kernels: gathers and scatters with consecutive lanes on consecutive features of a row; no atomics; every reduction in a fixed order:
+ *   results are bit-identical from run to run.
+ *   THE LIBRARY'S DRAWS come from the generator of m3pc_draw_variates, Philox4x32-10 with key = (seed lo, seed hi) and counter = (block,
+ *   step lo, step hi, array): a draw depends on (seed, step, row) alone.  All index arithmetic is exact integer arithmetic.
+ *     Segments, array 2: row j takes the words w0 .. w3 of block j.
+ *       M3PC_REPLAY_UNIFORM: trajectory i = (w0 * count) >> 32.
+ *       M3PC_REPLAY_LENGTH (in proportion to path length, np.random.choice(p = path_lengths / sum) of :330-332): r = (w0 * sum) >> 32 with
+ *       sum = the sum of the held path lengths, then the i with cum[i] <= r < cum[i+1], cum the int64 exclusive scan of the path lengths
+ *       in logical order (made on the device, in a fixed order, when the ring has changed since the last scan).
+ *       start = (w2 * (path_length[i] - segment_length + 1)) >> 32 (np.random.randint(0, len - L + 1) of :345-347).
+ *       A multiply-shift (w * n) >> 32 takes each of n values with probability within 2^-32 of 1/n: a relative bias of at most n / 2^32.
+ *     Transitions, distinct within a ring (random.sample of :371-381 draws without replacement): row j of a ring's rows takes logical
+ *     index pi(j), pi a keyed bijection of [0, n), n = the ring's count: for n = 1, pi(0) = 0; else with b = ceil(log2 n), half =
+ *     ceil(b / 2), mask = 2^half - 1 and the four round keys k0 .. k3 = the words of Philox block 0, array 3 (online ring) or 4 (offline
+ *     ring), x = j is taken through   (l, r) = (x >> half, x & mask);  four times, for k = k0 .. k3:  (l, r) = (r, l ^ ((((r + k) mod 2^32)
+ *     * 0x9E3779B1 mod 2^32) >> (32 - half)));  x = (l << half) | r   -- a balanced Feistel network, a bijection of [0, 2^(2 half)) --
+ *     again and again until x < n (cycle walking: a bijection of [0, n); the domain is smaller than 4 n).  O(1) per row, no scratch.
+ *     This does not reproduce NumPy's or Python's Mersenne streams, and nothing can: a caller who needs the reference's exact batches
+ *     passes its indices.  tests/replay_ref.py restates the draws bit for bit.
+ * Refused with M3PC_EINVAL before any HIP call: null required pointers; a capacity < 0; max_steps < 1; segment_length outside [1,
+ * max_steps]; n outside [1, capacity] (append, append_transitions) or [1, n_envs] (push_episodes); a path length < segment_length or >
+ * max_steps; a ring other than M3PC_REPLAY_OFFLINE / _ONLINE; a store of other sizes or another device; an id outside [0, n_envs) or
+ * repeated; a non-finite or negative discount; batch < 1; a mode other than M3PC_REPLAY_UNIFORM / _LENGTH; one of traj_index /
+ * start_index without the other; a host index out of range; n_online outside [0, batch]; more rows asked of a ring than it holds.
+ * Refused with M3PC_ESTATE: sampling, or values_up_bound, on a part that holds nothing. */
+typedef struct m3pc_replay m3pc_replay;
+#define M3PC_REPLAY_UNIFORM 0  /* select_mode "uniform": replay_buffer.py:320-326 */
+#define M3PC_REPLAY_LENGTH 1   /* select_mode "prob":    replay_buffer.py:328-332 */
+#define M3PC_REPLAY_OFFLINE 0  /* offline_trans_buffer,  replay_buffer.py:101 */
+#define M3PC_REPLAY_ONLINE 1   /* online_trans_buffer,   replay_buffer.py:102 */
+int m3pc_replay_create(m3pc_handle* h, int traj_capacity, int max_steps, int segment_length, int offline_capacity, int online_capacity,
+                       m3pc_replay** out);
+int m3pc_replay_destroy(m3pc_replay* rb);
+/* update_buffer (replay_buffer.py:272-310) on caller arrays, and the first fill (:129-160): n trajectories -- obs (n, max_steps, S), act
+ * (n, max_steps, A), rew (n, max_steps) float32, val (n, max_steps) float64, host or device (on_device, one flag for the four), lens (n,)
+ * int32 ALWAYS on the host (the mirror) -- are appended at the tail in order; when the ring is full the oldest leave (:288-304: drop the
+ * first n, append the n new).  All max_steps rows are copied.  The reference does not filter an episode shorter than traj_length, which
+ * later makes np.random.randint(0, <= 0) raise in traj_sample; here such an entry is refused, with nothing written. */
+int m3pc_replay_append(m3pc_replay* rb, int n, const float* obs, const float* act, const float* rew, const double* val, const int* lens,
+                       int on_device, void* stream);
+/* The offline fill (replay_buffer.py:108-125), or online_trans_buffer.append (:223-227) for a caller without a store: n transitions --
+ * state (n, S), action (n, A), reward (n,), next_state (n, S), done (n,) float32, host or device -- appended to ring `which`. */
+int m3pc_replay_append_transitions(m3pc_replay* rb, int which, int n, const float* state, const float* action, const float* reward,
+                                   const float* next_state, const float* done, int on_device, void* stream);
+/* The end of online_rollout (replay_buffer.py:223-251) for the episodes of a store, device to device, in one launch.  For the listed
+ * environments (env_ids host int32 (n,), or NULL for 0 .. n-1), in order:
+ *   an episode with path_length >= segment_length is appended to the trajectory ring as m3pc_replay_append would: the three blocks and
+ *   the path length as m3pc_episodes_export gives them, and the values of :234-243 computed in the same pass by the recurrence of
+ *   m3pc_episodes_values -- V[t] = rew[t+1] + discount V[t+1] in float64, rounded to float32 (the assignment of :238), then widened; with
+ *   use_avg the stored value is (double)(float)V[t] / (max_steps - t), NOT rounded again: a float32 array divided by an int64 array is a
+ *   float64 array in NumPy (:240-242; m3pc_episodes_values rounds this quotient to float32, the buffer must not).  A shorter episode
+ *   is skipped as a trajectory (online_rollout's "too short");
+ *   the transitions (obs[t], act[t], rew[t], obs[t+1], 0), t < path_length, of EVERY listed episode are appended to the online ring
+ *   (:223-227 appends them whatever becomes of the trajectory).  final_obs, optional, (n, S) float32, host or device (final_on_device):
+ *   row i is the next state of episode i's last transition; without it that transition is left out (the store never holds row
+ *   path_length of a full episode).
+ * taken, optional host out: the number of trajectories appended, from the mirrors -- valid on return.  The store is only read. */
+int m3pc_replay_push_episodes(m3pc_replay* rb, m3pc_episodes* ep, const int* env_ids, int n, double discount, int use_avg, const float* final_obs,
+                              int final_on_device, int* taken, void* stream);
+/* traj_sample (replay_buffer.py:312-366): states (batch, L, S), actions (batch, L, A), rewards (batch, L, 1) float32 and returns (batch,
+ * L, 1) float64 -- or float32, the float64 value rounded, when returns_f32 != 0 -- device out, L = segment_length; row j is rows start ..
+ * start + L - 1 of trajectory i.  (i, start) per row: traj_index / start_index, both (batch,) int32 on the host (checked) or the device
+ * (index_on_device; clamped into range, so that no index leads out of the storage), or, when both are NULL, drawn by the library from
+ * (seed, step) by `mode` (above); mode is checked either way.  out_traj / out_start, optional device out (batch,) int32: the pair of every
+ * row.  At most two launches: the gather, and the scan in front of it when M3PC_REPLAY_LENGTH draws from a ring that has changed. */
+int m3pc_replay_sample_segments(m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
+                                unsigned long long seed, unsigned long long step, float* states, float* actions, float* rewards, void* returns,
+                                int returns_f32, int* out_traj, int* out_start, void* stream);
+/* trans_sample (replay_buffer.py:368-420): state (batch, S), action (batch, A), reward (batch, 1), next_state (batch, S), done (batch, 1)
+ * float32 device out; rows [0, n_online) from the online ring, the other batch - n_online from the offline ring (the order of :375-382).
+ * index, (batch,) int32 host (checked) or device (clamped): the logical index of every row within its ring; NULL: drawn by the library,
+ * distinct within each ring (above).  out_index, optional device out (batch,).  One launch. */
+int m3pc_replay_sample_transitions(m3pc_replay* rb, int batch, int n_online, const int* index, int index_on_device, unsigned long long seed,
+                                   unsigned long long step, float* state, float* action, float* reward, float* next_state, float* done, int* out_index,
+                                   void* stream);
+/* values_up_bound (replay_buffer.py:161, :310): out (max_steps,) float64 device, the maximum over the held trajectories of every value
+ * column, all max_steps rows -- the episode_rtg_ref evaluate_plan is called with (finetune.py:373-377). */
+int m3pc_replay_values_up_bound(m3pc_replay* rb, double* out, void* stream);
+/* The mirrors (host out, each optional; no HIP call): the number of held trajectories, offline and online transitions. */
+int m3pc_replay_counts(m3pc_replay* rb, int* trajectories, int* offline, int* online);
+/* path_lengths (replay_buffer.py:133, :288) in logical order: host out, the first `count` of `capacity` entries; no HIP call. */
+int m3pc_replay_path_lengths(m3pc_replay* rb, int* path_lengths, int capacity);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

@@ -52,6 +52,9 @@ EXPORTS = (
     "m3pc_refine_plans",
     "m3pc_episodes_create", "m3pc_episodes_destroy", "m3pc_episodes_reset", "m3pc_episodes_observe", "m3pc_episodes_record",
     "m3pc_episodes_windows", "m3pc_episodes_values", "m3pc_episodes_export",
+    "m3pc_replay_create", "m3pc_replay_destroy", "m3pc_replay_append", "m3pc_replay_append_transitions", "m3pc_replay_push_episodes",
+    "m3pc_replay_sample_segments", "m3pc_replay_sample_transitions", "m3pc_replay_values_up_bound", "m3pc_replay_counts",
+    "m3pc_replay_path_lengths",
 )
 
 
@@ -106,6 +109,8 @@ PLAN_DEFER_JOIN = 1
 PLAN_PRUNED_POLICY = 2
 PLAN_INPUTS_READY = 4
 WINDOW_PLAN, WINDOW_GOAL = 0, 1  # M3PC_WINDOW_*: the window rule of m3pc_episodes_windows
+REPLAY_UNIFORM, REPLAY_LENGTH = 0, 1  # M3PC_REPLAY_*: how m3pc_replay_sample_segments draws a trajectory
+REPLAY_OFFLINE, REPLAY_ONLINE = 0, 1  # M3PC_REPLAY_*: the two transition rings
 
 
 class M3pcError(RuntimeError):
@@ -187,6 +192,16 @@ def load_library(path: Optional[str] = None):
         "m3pc_episodes_windows": [vp, C.POINTER(i), i, i, i, vp, vp, vp, C.POINTER(i), vp],
         "m3pc_episodes_values": [vp, C.POINTER(i), i, d, i, vp, vp],
         "m3pc_episodes_export": [vp, i, vp, vp, vp, C.POINTER(i), i, vp],
+        "m3pc_replay_create": [vp, i, i, i, i, i, C.POINTER(vp)],
+        "m3pc_replay_destroy": [vp],
+        "m3pc_replay_append": [vp, i, vp, vp, vp, vp, C.POINTER(i), i, vp],
+        "m3pc_replay_append_transitions": [vp, i, i, vp, vp, vp, vp, vp, i, vp],
+        "m3pc_replay_push_episodes": [vp, vp, C.POINTER(i), i, d, i, vp, i, C.POINTER(i), vp],
+        "m3pc_replay_sample_segments": [vp, i, i, vp, vp, i, C.c_ulonglong, C.c_ulonglong, vp, vp, vp, vp, i, vp, vp, vp],
+        "m3pc_replay_sample_transitions": [vp, i, i, vp, i, C.c_ulonglong, C.c_ulonglong, vp, vp, vp, vp, vp, vp, vp],
+        "m3pc_replay_values_up_bound": [vp, vp, vp],
+        "m3pc_replay_counts": [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)],
+        "m3pc_replay_path_lengths": [vp, C.POINTER(i), i],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }

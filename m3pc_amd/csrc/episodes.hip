@@ -4,7 +4,7 @@
 // (consecutive lanes take consecutive features of a row: coalesced for any row width, no alignment assumed), without atomics;
 // the one reduction (values) is a serial fp64 recurrence per environment: every result is bit-identical from run to run.
 // The host half keeps a mirror of the path lengths -- the host makes every call that changes one -- so that no call reads the device.
-#include "m3pc_internal.h"
+#include "episodes.h"
 
 namespace m3pc {
 namespace {
@@ -121,28 +121,6 @@ int blocks_for(long long total) {
 }  // namespace
 }  // namespace m3pc
 
-// One store.  Device storage is allocated (and zeroed, in stream order) by the first call that enqueues work: m3pc_episodes_create
-// itself makes no HIP call.
-struct m3pc_episodes {
-    int device = 0, S = 0, A = 0, T = 0, n_envs = 0, M = 0;
-    float *obs = nullptr, *act = nullptr, *rew = nullptr;
-    int* len = nullptr;
-    bool ready = false;
-    std::vector<int> mirror;        // path lengths as the calls made so far leave them
-    std::vector<unsigned> seen;     // duplicate check of one call's ids: seen[e] == call
-    unsigned call = 0;
-    // Host data on its way to the device (ids, host observations / actions / rewards / tables): copied into a pinned, device-visible
-    // block the kernel reads directly.  A block is taken again once the event behind its last reader has completed; while none is
-    // free another one is allocated -- the host never waits for the device.
-    struct Stage {
-        void *host = nullptr, *dev = nullptr;
-        size_t bytes = 0;
-        hipEvent_t ev = nullptr;
-    };
-    std::vector<Stage> stages;
-    std::vector<int> held;  // blocks the call being enqueued reads
-};
-
 namespace {
 
 int ep_ensure(m3pc_episodes* ep, hipStream_t st) {
@@ -161,39 +139,10 @@ int ep_ensure(m3pc_episodes* ep, hipStream_t st) {
     return 0;
 }
 
-// `bytes` of host memory -> a device-visible address that stays valid until the work enqueued by this call has run
-int ep_stage(m3pc_episodes* ep, const void* src, size_t bytes, const void** dev) {
-    int pick = -1;
-    for (size_t s = 0; s < ep->stages.size() && pick < 0; ++s) {
-        const auto& g = ep->stages[s];
-        if (g.bytes >= bytes && std::find(ep->held.begin(), ep->held.end(), (int)s) == ep->held.end() && hipEventQuery(g.ev) == hipSuccess)
-            pick = (int)s;
-    }
-    (void)hipGetLastError();  // (hipErrorNotReady of a busy block is not an error of the call)
-    if (pick < 0) {
-        m3pc_episodes::Stage g;
-        g.bytes = 4096;
-        while (g.bytes < bytes) g.bytes *= 2;
-        HIPCHK(hipHostMalloc(&g.host, g.bytes, hipHostMallocMapped));
-        if (hipHostGetDevicePointer(&g.dev, g.host, 0) != hipSuccess || hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) {
-            (void)hipHostFree(g.host);
-            return fail(M3PC_EHIP, "m3pc_episodes: no device view of a %zu-byte staging block", g.bytes);
-        }
-        ep->stages.push_back(g);
-        pick = (int)ep->stages.size() - 1;
-    }
-    memcpy(ep->stages[pick].host, src, bytes);
-    ep->held.push_back(pick);
-    *dev = ep->stages[pick].dev;
-    return 0;
-}
+int ep_stage(m3pc_episodes* ep, const void* src, size_t bytes, const void** dev) { return ep->pool.stage(src, bytes, dev, "m3pc_episodes"); }
 
 // behind the launch that reads them: the call's blocks become free again when `st` has passed this point
-int ep_release(m3pc_episodes* ep, hipStream_t st) {
-    for (int s : ep->held) HIPCHK(hipEventRecord(ep->stages[s].ev, st));
-    ep->held.clear();
-    return 0;
-}
+int ep_release(m3pc_episodes* ep, hipStream_t st) { return ep->pool.release(st); }
 
 // the ids of one call: n in [1, n_envs], every id in [0, n_envs), none twice.  Before any HIP call.
 int ep_check_ids(m3pc_episodes* ep, const int* ids, int n, const char* who) {
@@ -274,15 +223,12 @@ int m3pc_episodes_create(m3pc_handle* h, int n_envs, int max_steps, m3pc_episode
 
 int m3pc_episodes_destroy(m3pc_episodes* ep) {
     if (!ep) return 0;
-    if (ep->ready || !ep->stages.empty()) {
+    if (ep->ready || !ep->pool.stages.empty()) {
         (void)hipSetDevice(ep->device);
         (void)hipDeviceSynchronize();
         for (void* b : {(void*)ep->obs, (void*)ep->act, (void*)ep->rew, (void*)ep->len})
             if (b) (void)hipFree(b);
-        for (auto& g : ep->stages) {
-            (void)hipEventDestroy(g.ev);
-            (void)hipHostFree(g.host);
-        }
+        ep->pool.destroy();
     }
     delete ep;
     return 0;
@@ -299,7 +245,7 @@ int m3pc_episodes_reset(m3pc_episodes* ep, const int* env_ids, int n, const void
     if (!rc && obs_table && !on_device)
         rc = ep_stage(ep, obs_table, (size_t)n * ep->M * ep->S * (table_f64 ? sizeof(double) : sizeof(float)), &tab);
     if (rc) {
-        ep->held.clear();
+        ep->pool.held.clear();
         return rc;
     }
     const int blocks = blocks_for((long long)n * ep->M * (ep->S + ep->A + 1));
@@ -321,7 +267,7 @@ int m3pc_episodes_observe(m3pc_episodes* ep, const int* env_ids, int n, const vo
     const void* src = obs;
     if (!rc && !on_device) rc = ep_stage(ep, obs, (size_t)n * ep->S * (obs_f64 ? sizeof(double) : sizeof(float)), &src);
     if (rc) {
-        ep->held.clear();
+        ep->pool.held.clear();
         return rc;
     }
     const int blocks = blocks_for((long long)n * ep->S);
@@ -344,7 +290,7 @@ int m3pc_episodes_record(m3pc_episodes* ep, const int* env_ids, int n, const flo
     if (!rc && !on_device) rc = ep_stage(ep, actions, (size_t)n * ep->A * sizeof(float), &a);
     if (!rc && !on_device) rc = ep_stage(ep, rewards, (size_t)n * sizeof(float), &r);
     if (rc) {
-        ep->held.clear();
+        ep->pool.held.clear();
         return rc;
     }
     const int per = EP_THREADS / 64;
@@ -366,7 +312,7 @@ int m3pc_episodes_windows(m3pc_episodes* ep, const int* env_ids, int n, int mode
     CHK(ep_ensure(ep, st));
     EpisodesP p;
     if (int rc = ep_params(ep, env_ids, n, &p)) {
-        ep->held.clear();
+        ep->pool.held.clear();
         return rc;
     }
     hipLaunchKernelGGL(ep_windows_kernel, dim3(blocks_for((long long)n * ep->T * (ep->S + ep->A + 1))), dim3(EP_THREADS), 0, st, p, horizon,
@@ -389,7 +335,7 @@ int m3pc_episodes_values(m3pc_episodes* ep, const int* env_ids, int n, double di
     CHK(ep_ensure(ep, st));
     EpisodesP p;
     if (int rc = ep_params(ep, env_ids, n, &p)) {
-        ep->held.clear();
+        ep->pool.held.clear();
         return rc;
     }
     hipLaunchKernelGGL(ep_values_kernel, dim3((n + EP_THREADS - 1) / EP_THREADS), dim3(EP_THREADS), 0, st, p, discount, use_avg ? 1 : 0, values);

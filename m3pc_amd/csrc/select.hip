@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "kernels.h"
+#include "philox.h"
 
 namespace m3pc {
 
@@ -1059,24 +1060,7 @@ void launch_gather_listed(const float* sa, int E, int n_total, int row, const in
 // ---- the variates of a plan step from a counter-based generator (m3pc_draw_variates): a value depends on (seed, step, element
 // index) alone -- not on the launch geometry, the slice asked for or earlier draws -- so a candidate-sharded rank draws its rows
 // of the one-rank array.  Philox4x32-10 (Salmon et al., SC'11): key = (seed lo, seed hi), counter = (block, step lo, step hi,
-// array) with array 0 = eps, 1 = expo; block b gives the flat elements 4b .. 4b+3 of its array.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0;
-    w[1] = c1;
-    w[2] = c2;
-    w[3] = c3;
-}
+// array) with array 0 = eps, 1 = expo; block b gives the flat elements 4b .. 4b+3 of its array.  The generator itself: philox.h.
 // Box-Muller on two words: u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], u2 = (wb >> 8) 2^-24; z = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2).
 // 2 u2 is exact in fp32, so the angle goes through sincospif unrounded; logf / sqrtf / sincospif are the precise library versions.
 __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, float& z1) {

@@ -29,6 +29,11 @@ def new_trajectory(state_dim: int, action_dim: int, max_steps: int = 1000) -> Di
             "total_return": 0, "path_length": 0}
 
 
+def _rtg_at(episode_rtg_ref, t: int, ratio: float) -> float:
+    """episode_rtg_ref[t] * ratio as a float: the reference is (max_steps,) or, as ReplayBuffer.values_up_bound is, (max_steps, 1)."""
+    return float(np.asarray(episode_rtg_ref[t]).reshape(-1)[0] * ratio)
+
+
 class _Episode:
     def __init__(self, env, index, traj):
         self.env, self.index, self.traj = env, index, traj
@@ -89,7 +94,7 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
 
     def issue(ep: _Episode):
         ep.traj["observations"][ep.timestep] = ep.observation
-        rtg = float(episode_rtg_ref[ep.timestep] * ratio) if eval else None
+        rtg = _rtg_at(episode_rtg_ref, ep.timestep, ratio) if eval else None
         ep.ticket = planner.plan_async(ep.traj, percentage=percentage, eval=eval, rtg=rtg)
         flying.append(ep)
 
@@ -125,7 +130,7 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
         live, waiting = waiting, []
         ids = [ep.index for ep in live]
         st.observe(np.stack([np.asarray(ep.observation) for ep in live]), ids)
-        rtgs = [float(episode_rtg_ref[ep.timestep] * ratio) for ep in live] if eval else None
+        rtgs = [_rtg_at(episode_rtg_ref, ep.timestep, ratio) for ep in live] if eval else None
         named = dict(keys=ids) if getattr(planner, "_refine", None) is not None else {}
         acts = planner.action_sample_batch(None, percentage=percentage, eval=eval, rtg=rtgs,
                                            lockstep="native" if lockstep == "native" else True, store=st, env_ids=ids, **named)
@@ -159,7 +164,7 @@ def evaluate_plan(planner, envs: Sequence, episode_rtg_ref: np.ndarray, ratio: f
         live, waiting = waiting, []
         for ep in live:
             ep.traj["observations"][ep.timestep] = ep.observation
-        rtgs = [float(episode_rtg_ref[ep.timestep] * ratio) for ep in live] if eval else None
+        rtgs = [_rtg_at(episode_rtg_ref, ep.timestep, ratio) for ep in live] if eval else None
         # (a planner that plans by refinement keeps a warm start per environment: `live` shrinks as episodes end, so the
         # environments are named by their index, not by their position in this round)
         named = dict(keys=[ep.index for ep in live]) if getattr(planner, "_refine", None) is not None else {}
