@@ -51,7 +51,8 @@ extern "C" {
  * refinement of a lock-step batch of windows, with a shifted warm start); then m3pc_episodes_create / _destroy / _reset / _observe /
  * _record / _windows / _values / _export and the opaque m3pc_episodes (the episode store); then m3pc_replay_create / _destroy / _append /
  * _append_transitions / _push_episodes / _sample_segments / _sample_transitions / _values_up_bound / _counts / _path_lengths and the
- * opaque m3pc_replay (the replay buffer).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * opaque m3pc_replay (the replay buffer); then m3pc_iql_create / _destroy / _load / _export / _set_step / _get_step / _train_step / _train /
+ * _publish_critic / _evaluate, m3pc_iql_args and the opaque m3pc_iql (the IQL trainer).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -934,6 +935,90 @@ int m3pc_replay_values_up_bound(m3pc_replay* rb, double* out, void* stream);
 int m3pc_replay_counts(m3pc_replay* rb, int* trajectories, int* offline, int* online);
 /* path_lengths (replay_buffer.py:133, :288) in logical order: host out, the first `count` of `capacity` entries; no HIP call. */
 int m3pc_replay_path_lengths(m3pc_replay* rb, int* path_lengths, int capacity);
+
+/* THE IQL TRAINER: ImplicitQLearning of finetune_omtm/model.py:194-334 on the device -- the two updates of the fine-tuning loop that
+ * learner.critic_update(buffer.trans_sample()) makes (finetune_omtm/finetune.py:281-310): V (model.py:174-191), the TwinQ with its target
+ * (:146-171, :213) and the Gaussian actor (:107-133), all MLPs [in, hidden, hidden, out] with ReLU, states normalised with (s - obs_mean) /
+ * obs_std -- trained from the transition batches of the replay buffer, and the TwinQ handed to the planner without the host.
+ *   Sizes.  hidden 64, 128 or 256; S + A <= 64, A <= 32 (input features are padded to a multiple of 32); 1 <= batch <= 1024.
+ *   (m3pc_create itself takes state_dim <= 32 today; the trainer's own rule is the wider one.)
+ *   A trainer is created on a handle, from which it takes S, A and the device; it does not refer to the handle afterwards.
+ *   m3pc_iql_create makes no HIP call: storage is allocated, and the Adam moments zeroed, by the first call that enqueues work.  A trainer
+ *   is not re-entrant; its calls are ordered on the device by the caller.  Everything is stream-ordered and no entry point waits for the
+ *   device (m3pc_iql_destroy drains): host tensors given to m3pc_iql_load are consumed before it returns, through pinned staging blocks;
+ *   host tensors m3pc_iql_export writes are complete once the stream has passed the call -- give it pinned (page-locked) memory: a copy
+ *   into pageable host memory is one the runtime may make the calling thread wait for.  The host mirrors the step count.
+ *   ONE STEP is train() (model.py:286-308), in which every forward pass reads pre-step parameters:
+ *     next_v = vf(next_obs);  adv = min(q1_target, q2_target)(obs, act) - vf(obs);  value_loss = mean(|expectile - 1[adv < 0]| adv^2)   (:59-60, :228-240)
+ *     targets = r + (1 - done) discount next_v;  q_loss = (mse(q1, targets) + mse(q2, targets)) / 2                                    (:251-253)
+ *     actor_loss = mean(min(exp(beta adv), 100) * -sum_A log N(act; tanh(net(obs)), exp(clamp(log_std, -20, 2))))                       (:269-279)
+ *     Adam on vf, qf and the actor (torch.optim.Adam defaults; the actor's rate follows CosineAnnealingLR(actor_t_max), :219), then
+ *     q_target <- (1 - tau) q_target + tau qf with the POST-step qf (:22-24, :257-260), each product rounded to fp32, then the sum.
+ *   Seven launches per step; fp32 on v_mfma_f32_32x32x2_f32 (every product an exact fp32 fma); one wavefront owns an output tile and sums
+ *   its K dimension in a fixed order, no atomics: a step is bit-identical from run to run.  m3pc_amd/csrc/iql.h states the order of the
+ *   Adam arithmetic and what of it is fp64.
+ *   Tensors go by the reference's state_dict names, per part (m3pc_named_tensor; any other name in the list is ignored):
+ *     M3PC_IQL_QF, _Q_TARGET, _QF_ADAM_M, _QF_ADAM_V     "q1.net.0.weight" (hidden, S+A) ".0.bias" ".2.weight" ".2.bias" ".4.weight" (1, hidden) ".4.bias", and "q2. ..."
+ *     M3PC_IQL_VF, _VF_ADAM_M, _VF_ADAM_V                "v.net.0.weight" (hidden, S) ... "v.net.4.bias"
+ *     M3PC_IQL_ACTOR, _ACTOR_ADAM_M, _ACTOR_ADAM_V       "net.net.0.weight" (hidden, S) ... "net.net.4.weight" (A, hidden) "net.net.4.bias" (A), "log_std" (A)
+ *   _ADAM_M / _ADAM_V are exp_avg / exp_avg_sq of torch.optim.Adam's state, zero until loaded.
+ * Refused with M3PC_EINVAL before any HIP call: null required pointers; sizes outside the covered set (create); a part or an output that
+ * is none of the macros; a missing or mis-shaped tensor; one of obs_mean / obs_std without the other; total_it < 0; batch outside [1,
+ * 1024]; n_steps < 1; rows < 1; a non-finite or negative rate or discount; expectile outside (0, 1); a non-finite beta; tau outside [0, 1];
+ * actor_t_max < 1; flags != 0; a replay buffer or a handle of other sizes or another device.  Refused with M3PC_ESTATE: training before
+ * qf, q_target, vf, the actor and obs_mean / obs_std are loaded; publishing, evaluating or exporting a network that is not loaded.  The
+ * refusals of m3pc_replay_sample_transitions apply to m3pc_iql_train. */
+typedef struct m3pc_iql m3pc_iql;
+#define M3PC_IQL_QF 0
+#define M3PC_IQL_Q_TARGET 1
+#define M3PC_IQL_VF 2
+#define M3PC_IQL_ACTOR 3
+#define M3PC_IQL_QF_ADAM_M 4
+#define M3PC_IQL_QF_ADAM_V 5
+#define M3PC_IQL_VF_ADAM_M 6
+#define M3PC_IQL_VF_ADAM_V 7
+#define M3PC_IQL_ACTOR_ADAM_M 8
+#define M3PC_IQL_ACTOR_ADAM_V 9
+/* m3pc_iql_evaluate: which output */
+#define M3PC_IQL_Q_MIN 0         /* TwinQ.forward, model.py:170-171 */
+#define M3PC_IQL_Q_TARGET_MIN 1  /* the same of q_target */
+#define M3PC_IQL_V 2             /* ValueFunction.forward, :189-191 */
+#define M3PC_IQL_ACTOR_MEAN 3    /* GaussianPolicy.forward(...).mean, :129-133: what act() returns in evaluation (:135-143) */
+typedef struct m3pc_iql_args {
+    double v_lr, q_lr, actor_lr; /* the three optimizers' rates; the actor's is the base rate of its cosine schedule */
+    double expectile;            /* iql_tau, model.py:204 */
+    double beta;                 /* :205 */
+    double discount;             /* :207 */
+    double tau;                  /* the target's soft-update rate, :208 */
+    long long actor_t_max;       /* max_steps, :206 / :219 */
+    int flags;                   /* must be 0 */
+} m3pc_iql_args;
+int m3pc_iql_create(m3pc_handle* h, int hidden, m3pc_iql** out);
+int m3pc_iql_destroy(m3pc_iql* iql);
+/* load_state_dict (model.py:322-334), one part per call: every tensor of the part must be in the list (its on_device says where it
+ * lives).  obs_mean / obs_std, host (S,), both or neither: the normalisation all networks share.  Loading M3PC_IQL_QF does NOT copy it
+ * into the target (:325 is the caller's second call with M3PC_IQL_Q_TARGET). */
+int m3pc_iql_load(m3pc_iql* iql, int part, const m3pc_named_tensor* tensors, int n, const float* obs_mean, const float* obs_std, void* stream);
+/* state_dict (:310-320), one part per call: every tensor of the part is written to the `data` of the entry of its name (host or device
+ * by its on_device; written although the field is declared const). */
+int m3pc_iql_export(m3pc_iql* iql, int part, const m3pc_named_tensor* tensors, int n, void* stream);
+/* total_it (:225, :334): the number of steps made, which sets Adam's bias corrections and the actor's rate of the next step */
+int m3pc_iql_set_step(m3pc_iql* iql, long long total_it);
+int m3pc_iql_get_step(m3pc_iql* iql, long long* total_it);
+/* train(batch) (:286-308).  state (batch, S), action (batch, A), reward (batch, 1), next_state (batch, S), done (batch, 1): float32 device
+ * arrays, what m3pc_replay_sample_transitions writes.  losses, optional device out (3,): value_loss, q_loss, actor_loss. */
+int m3pc_iql_train_step(m3pc_iql* iql, const m3pc_iql_args* args, int batch, const float* state, const float* action, const float* reward,
+                        const float* next_state, const float* done, float* losses, void* stream);
+/* n_steps steps in one call (finetune.py:288-290, v_iter_per_mtm of them per iteration): step k trains on the batch the buffer draws for
+ * (seed, step + k) with n_online rows from the online ring; losses, optional device out (n_steps, 3).  Per step the bits are those of
+ * m3pc_replay_sample_transitions followed by m3pc_iql_train_step. */
+int m3pc_iql_train(m3pc_iql* iql, const m3pc_iql_args* args, m3pc_replay* rb, int n_steps, int batch, int n_online, unsigned long long seed,
+                   unsigned long long step, float* losses, void* stream);
+/* What m3pc_set_critic does with qf's state_dict, device to device in one launch: q1 / q2 in the operand order of the handle's critic
+ * kernels, obs_mean / obs_std, and the handle's critic counts as set.  The handle was created with critic_hidden == hidden. */
+int m3pc_iql_publish_critic(m3pc_iql* iql, m3pc_handle* h, void* stream);
+/* states (rows, S), actions (rows, A; unused, may be NULL, for M3PC_IQL_V and _ACTOR_MEAN) device -> out (rows,) or (rows, A) device. */
+int m3pc_iql_evaluate(m3pc_iql* iql, int which, const float* states, const float* actions, int rows, float* out, void* stream);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

@@ -55,6 +55,8 @@ EXPORTS = (
     "m3pc_replay_create", "m3pc_replay_destroy", "m3pc_replay_append", "m3pc_replay_append_transitions", "m3pc_replay_push_episodes",
     "m3pc_replay_sample_segments", "m3pc_replay_sample_transitions", "m3pc_replay_values_up_bound", "m3pc_replay_counts",
     "m3pc_replay_path_lengths",
+    "m3pc_iql_create", "m3pc_iql_destroy", "m3pc_iql_load", "m3pc_iql_export", "m3pc_iql_set_step", "m3pc_iql_get_step",
+    "m3pc_iql_train_step", "m3pc_iql_train", "m3pc_iql_publish_critic", "m3pc_iql_evaluate",
 )
 
 
@@ -101,6 +103,12 @@ class RefineArgs(C.Structure):
                 ("step_lo", C.c_uint), ("step_hi", C.c_uint)]
 
 
+class IqlArgs(C.Structure):
+    """m3pc_iql_args: the hyper-parameters of one IQL step (``m3pc_iql_train_step`` / ``m3pc_iql_train``)."""
+    _fields_ = [("v_lr", C.c_double), ("q_lr", C.c_double), ("actor_lr", C.c_double), ("expectile", C.c_double), ("beta", C.c_double),
+                ("discount", C.c_double), ("tau", C.c_double), ("actor_t_max", C.c_longlong), ("flags", C.c_int)]
+
+
 REFINE_CEM, REFINE_MPPI = 0, 1  # M3PC_REFINE_*
 REFINE_MAX_ITER = 16
 REFINE_WEIGHTINGS = {"cem": REFINE_CEM, "mppi": REFINE_MPPI}
@@ -111,6 +119,10 @@ PLAN_INPUTS_READY = 4
 WINDOW_PLAN, WINDOW_GOAL = 0, 1  # M3PC_WINDOW_*: the window rule of m3pc_episodes_windows
 REPLAY_UNIFORM, REPLAY_LENGTH = 0, 1  # M3PC_REPLAY_*: how m3pc_replay_sample_segments draws a trajectory
 REPLAY_OFFLINE, REPLAY_ONLINE = 0, 1  # M3PC_REPLAY_*: the two transition rings
+# M3PC_IQL_*: the parts of m3pc_iql_load / _export, and the outputs of m3pc_iql_evaluate
+(IQL_QF, IQL_Q_TARGET, IQL_VF, IQL_ACTOR, IQL_QF_ADAM_M, IQL_QF_ADAM_V, IQL_VF_ADAM_M, IQL_VF_ADAM_V, IQL_ACTOR_ADAM_M,
+ IQL_ACTOR_ADAM_V) = range(10)
+IQL_Q_MIN, IQL_Q_TARGET_MIN, IQL_V, IQL_ACTOR_MEAN = range(4)
 
 
 class M3pcError(RuntimeError):
@@ -202,6 +214,16 @@ def load_library(path: Optional[str] = None):
         "m3pc_replay_values_up_bound": [vp, vp, vp],
         "m3pc_replay_counts": [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)],
         "m3pc_replay_path_lengths": [vp, C.POINTER(i), i],
+        "m3pc_iql_create": [vp, i, C.POINTER(vp)],
+        "m3pc_iql_destroy": [vp],
+        "m3pc_iql_load": [vp, i, C.POINTER(NamedTensor), i, C.POINTER(f), C.POINTER(f), vp],
+        "m3pc_iql_export": [vp, i, C.POINTER(NamedTensor), i, vp],
+        "m3pc_iql_set_step": [vp, ll],
+        "m3pc_iql_get_step": [vp, C.POINTER(ll)],
+        "m3pc_iql_train_step": [vp, C.POINTER(IqlArgs), i, vp, vp, vp, vp, vp, vp, vp],
+        "m3pc_iql_train": [vp, C.POINTER(IqlArgs), vp, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, vp],
+        "m3pc_iql_publish_critic": [vp, vp, vp],
+        "m3pc_iql_evaluate": [vp, i, vp, vp, i, vp, vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }

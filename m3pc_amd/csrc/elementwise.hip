@@ -764,7 +764,7 @@ void launch_sample(const SampleP& p, hipStream_t st) {
 // the first hidden layer live in LDS and are read as broadcasts.
 #define CR_ROWS 16
 __global__ __launch_bounds__(256) void critic_kernel(CriticP p) {
-    __shared__ float sa[CR_ROWS][32];
+    __shared__ float sa[CR_ROWS][64];  // (S + A <= 64: a handle takes S <= 32 and A <= 32)
     __shared__ float h1[CR_ROWS][256];
     __shared__ float red[CR_ROWS][4];
     const int tid = threadIdx.x;

@@ -284,6 +284,15 @@ struct m3pc_replay {
     m3pc::StagePool pool;
 };
 
+namespace m3pc {
+// (iql.h) what the trainer checks a buffer against
+void replay_sizes(const m3pc_replay* rb, int* S, int* A, int* device) {
+    *S = rb->S;
+    *A = rb->A;
+    *device = rb->device;
+}
+}  // namespace m3pc
+
 namespace {
 
 int rb_ensure(m3pc_replay* rb) {
