@@ -6,7 +6,7 @@
  * Users: tests/test_gemm_kernels_gpu.py, tests/test_gemm_edges_gpu.py, tests/test_bf16x3_gpu.py, tests/test_attention_gpu.py,
  * tests/test_block_fused_gpu.py, tests/test_block_edges_gpu.py, tests/test_block_ref_cpu.py, tests/test_lockstep_kernels_gpu.py,
  * tests/test_block_shared_xb_gpu.py, tests/test_block_shared_xb_cpu.py, tests/test_embed_shared_xb_gpu.py,
- * tools/*.py.
+ * tests/test_elementwise_edges_gpu.py, tests/test_elementwise_ref_cpu.py, tools/*.py.
  */
 #ifndef M3PC_HIP_DEBUG_H
 #define M3PC_HIP_DEBUG_H
@@ -284,12 +284,17 @@ int m3pc_debug_block_split_n(void);
  * own rows of sequence 0, 1, ... -- and this is the row of it that token row r takes as its residual (-1: arguments out of range).
  * Host only, no GPU needed (tests/test_block_shared_xb_cpu.py) */
 int m3pc_debug_block_res_row(int r, int res_L, int res_nshared);
-/* the embedding kernel (launch_embed; d = 256, 512, 768 or 1024: the wave-per-row kernel) on caller tensors: token j of batch element
+/* the embedding kernel (launch_embed; d % 64 == 0, d <= 1024 as a handle takes it: the wave-per-row kernel embed_rows_kernel at d = 256,
+ * 512, 768 or 1024, the block-per-row embed_kernel at every other d) on caller tensors: token j of batch element
  * b is key tokmap[2 j] at step t = tokmap[2 j + 1], its row X[b L + j] = tok[key][b bstride[key] + t feat[key] ..] WT[key] + E[key][t]
  * (WT (feat, d), E (T, d) fp32; no normalisation, no window index), stored as fp32 (X) or bf16 (Xb); with ln_g / ln_b also
  * LayerNorm(row) as bf16 to Hb (n_sh > 0: tokens j < n_sh once to Hb_sh[j], the others to Hb[b (L - n_sh) + j - n_sh]).  The first
  * n_indep tokens do not depend on b; x_first_only: their X rows are stored for b = 0 only; x_compact (with Xb, x_first_only,
- * n_indep > 0): Xb holds those n_indep rows once and behind them the L - n_indep own rows of b = 0, 1, ... (m3pc_debug_block_res_row) */
+ * n_indep > 0): Xb holds those n_indep rows once and behind them the L - n_indep own rows of b = 0, 1, ... (m3pc_debug_block_res_row).
+ * Refused with M3PC_EINVAL before anything is launched: d % 64, d < 64, d > 1024, a token's key outside [0, 3], with feat < 1 (or
+ * above 32 where embed_kernel runs: its LDS row) or without tok / WT / E, a token step outside [0, T), and, where embed_kernel runs, what that kernel does
+ * not implement: Xb, n_sh, n_indep, x_first_only, x_compact.  The checks of d and of embed_kernel's options come first and need no
+ * GPU; tokmap (device memory) is then copied back for the checks of its entries.  The kernel launched: m3pc_debug_elementwise_picked. */
 typedef struct m3pc_debug_embed_args {
     const float* tok[4];
     long long bstride[4];
@@ -308,6 +313,15 @@ typedef struct m3pc_debug_embed_args {
     void* stream;
 } m3pc_debug_embed_args;
 int m3pc_debug_embed(const m3pc_debug_embed_args* a);
+/* the same launch with what EmbedP carries beside it: Hf (optional, with ln_g / ln_b), the LayerNorm rows in fp32 (batch L, d) -- what
+ * holds the fused norm to its fp32 bound and not only through the bf16 rounding of Hb (not with n_sh) -- and picked (1 int, optional).
+ * Both entry points copy tokmap back with a synchronous hipMemcpy on every call: do not time a kernel through them. */
+typedef struct m3pc_debug_embed_ex_args {
+    m3pc_debug_embed_args base;
+    float* Hf;
+    int* picked;
+} m3pc_debug_embed_ex_args;
+int m3pc_debug_embed_ex(const m3pc_debug_embed_ex_args* a);
 /* the fused decoder input (kv_fused_kernel) on caller tensors */
 long long m3pc_debug_kv_stream_bytes(void);
 int m3pc_debug_kv_fused(const void* Z, int n, int Le, int kept0, int off0, int kept1, int off1, const void* We0, const void* We1,
@@ -379,6 +393,177 @@ int m3pc_debug_attention(int dtype, const void* Q, long long q_bstride, int ldq,
                          const void* V2, int ldkv2, int L2, const void* Kp, const void* Vp, int ldp, int Lp, float* pre, void* O,
                          long long o_bstride, int ldo, int batch, int n_head, int hd, float scale, int kernel, int* picked,
                          void* stream);
+/* ---- the streaming and small reduction kernels of csrc/elementwise.hip, each alone on caller tensors, through its production
+ * launcher (launch_layernorm, launch_head_out, ...): the launcher's dispatch decides which kernel runs and the hook reports it.
+ * Every argument structure mirrors the kernel's parameter structure in csrc/kernels.h; a row map is {rpg, gstride, off} as in
+ * m3pc_debug_gemm_ex.  picked (1 int, optional; 0 while nothing was launched): the id of the kernel launched.
+ * Elementwise kernel ids (tests/test_elementwise_edges_gpu.py reaches every id of this list):
+ *   1 embed_kernel;  2 embed_rows_kernel<1>;  3 embed_rows_kernel<2>;  4 embed_rows_kernel<3>;  5 embed_rows_kernel<4>;
+ *   6 gather_rows_kernel;  7 layernorm_kernel;  8 layernorm_vec_kernel;  9 layernorm_rows_kernel<1, 2>;
+ *   10 layernorm_rows_kernel<2, 2>;  11 layernorm_rows_kernel<3, 2>;  12 layernorm_rows_kernel<4, 2>;  13 head_out_kernel;
+ *   14 head_out_mfma_kernel;  15 actor_head_kernel<4>;  16 actor_head_kernel<8>;  17 actor_head_small_kernel;  18 sample_kernel;
+ *   19 critic_kernel;  20 critic_mfma_kernel<2>;  21 critic_mfma_kernel<4>;  22 critic_mfma_kernel<8>;  23 score_kernel;
+ *   24 tokenize_kernel;  25 detokenize_kernel;  26 goal_overlay_kernel;  27 goal_overlay_rows_kernel
+ * (not listed, no id: the A/B-only instances layernorm_rows_kernel<NV, 4> of M3PC_LN_RPW=4, and the weight-load helpers
+ * f32_to_bf16_kernel, fill_kernel, transpose_f32_kernel and embed_table_kernel, which no hook drives)
+ * The id of the elementwise kernel the calling thread launched last, for the entry points without a `picked` argument
+ * (m3pc_debug_embed, m3pc_tokenize, m3pc_detokenize): */
+int m3pc_debug_elementwise_picked(void);
+/* LayerNorm (LnP): Y[r] = LN2?(LN1(X[xmap(r)] (ldx))), r < rows, eps 1e-5, biased variance; Yf fp32 and / or Yb bf16, contiguous
+ * rows of d.  Refused with M3PC_EINVAL before anything is launched: a null X / g1 / b1, neither output, g2 without b2 (or b2 alone),
+ * rows < 1, d % 64, d < 64, d > 1024 (a lane holds at most 16 values), ldx < d, a row map that is neither rpg == 0 nor rpg >= 1
+ * with gstride >= rpg (off >= 0), and, where the 16-byte kernels run (d % 256 == 0 and ldx % 4 == 0), X / g1 / b1 / g2 / b2 / Yf
+ * off 16 bytes or Yb off 8 bytes. */
+typedef struct m3pc_debug_ln_args {
+    const float* X;
+    int ldx;
+    int xmap[3];
+    int rows, d;
+    const float* g1;
+    const float* b1;
+    const float* g2; /* optional */
+    const float* b2;
+    float* Yf; /* optional */
+    void* Yb;  /* optional */
+    void* stream;
+    int* picked;
+} m3pc_debug_ln_args;
+int m3pc_debug_layernorm(const m3pc_debug_ln_args* a);
+/* an output head's last Linear with the de-tokeniser (HeadOutP): Y[ymap(r)] (ldy)[f] = (x[r] . W[f] + b[f]) stdv[f] + mean[f],
+ * f < D (mean null: no de-tokeniser); W (D, d) fp32.  The rows come as fp32 X or bf16 Xb (or both): as the library's callers do,
+ * the hook passes Xb on only where head_out_mfma_covers(rows, d, D) holds (d = 512, D <= 32, rows >= 2048: head_out_mfma_kernel),
+ * and X otherwise.  Refused: no rows the chosen kernel can read (Xb alone where the matrix-core kernel does not cover, X alone is
+ * always fine), null W / b / Y, mean without stdv or stdv alone, rows < 1, d % 64, d < 64, d > 1024, D outside [1, 32], ldx < d,
+ * ldy < D, a bad row map, and for the matrix-core kernel Xb off 16 bytes or ldx % 8. */
+typedef struct m3pc_debug_head_out_args {
+    const float* X; /* optional */
+    const void* Xb; /* optional */
+    int ldx;
+    int rows, d, D;
+    const float* W;
+    const float* b;
+    const float* mean; /* optional */
+    const float* stdv;
+    float* Y;
+    int ymap[3];
+    int ldy;
+    void* stream;
+    int* picked;
+} m3pc_debug_head_out_args;
+int m3pc_debug_head_out(const m3pc_debug_head_out_args* a);
+/* the actor head (ActorP): mu[r] = x . Wmu^T + bmu, sd[r] = exp(-5 + 3.5 (tanh(x . Wls^T + bls) + 1)), x = LN?(X[xmap(r)] (ldx));
+ * Wmu / Wls (A, d), mu / sd (rows, A).  Refused: a null operand, rows < 1, d % 64, d < 64, d > 1024, A outside [1, 32], ldx < d, a
+ * bad row map, ln_g without ln_b (or ln_b alone), ln_g where actor_head_fuses_ln(d, A) is false (actor_head_small_kernel has no
+ * LayerNorm), and, where actor_head_kernel runs (d % 256 == 0, A <= 8), X / Wmu / Wls / ln_g / ln_b off 16 bytes or ldx % 4. */
+typedef struct m3pc_debug_actor_args {
+    const float* X;
+    int ldx;
+    int xmap[3];
+    int rows, d, A;
+    const float* Wmu;
+    const float* bmu;
+    const float* Wls;
+    const float* bls;
+    float* mu;
+    float* sd;
+    const float* ln_g; /* optional */
+    const float* ln_b;
+    void* stream;
+    int* picked;
+} m3pc_debug_actor_args;
+int m3pc_debug_actor_head(const m3pc_debug_actor_args* a);
+/* TwinQ (CriticP): q[r] = min over the two networks of W3 . relu(W2 relu(W1 [(s - om) / os | a] + b1) + b2) + b3.  W1[net]
+ * (hidden, S + A) and W2[net] (hidden, hidden) are HOST arrays in torch Linear layout: the hook transposes them for critic_kernel
+ * and packs them with critic_pack for critic_mfma_kernel inside the call (function-static device buffers, as m3pc_debug_gemm_ex
+ * keeps its split of W); everything else is device memory.  force_scalar: never the matrix-core kernel.  Refused: a null operand,
+ * rows < 1, S or A outside [1, 32] (the scalar kernel's LDS row holds S + A <= 64), hidden outside [1, 256] (one thread per hidden
+ * unit), and, where the matrix-core kernel runs (S + A <= 32, hidden 64 / 128 / 256, not forced), b1 / b2 / W3 off 16 bytes. */
+typedef struct m3pc_debug_critic_args {
+    const float* states;
+    const float* actions;
+    int rows, S, A, hidden;
+    const float* om;
+    const float* os;
+    const float* W1[2]; /* host */
+    const float* b1[2];
+    const float* W2[2]; /* host */
+    const float* b2[2];
+    const float* W3[2];
+    const float* b3[2];
+    float* q;
+    int force_scalar;
+    void* stream;
+    int* picked;
+} m3pc_debug_critic_args;
+int m3pc_debug_critic(const m3pc_debug_critic_args* a);
+/* critic_pack on host arrays (no GPU needed): W1 (hidden, SA), W2 (hidden, hidden) -> w1f (n_w1f floats), w2f (n_w2f floats, its
+ * 1024 floats of read-ahead padding zeroed).  w1f / w2f null: only the sizes are reported.  Refused: SA outside [1, 32], hidden not
+ * 64 / 128 / 256. */
+int m3pc_debug_critic_pack(const float* W1, const float* W2, int SA, int hidden, float* w1f, float* w2f, long long* n_w1f,
+                           long long* n_w2f);
+/* candidate construction (SampleP).  eps_rows: the rows of eps (mode 0: of T A floats, else of h A); hist_windows: the windows of
+ * hist_actions (1 without widx).  index / widx are device arrays whose entries the caller keeps below eps_rows / hist_windows.
+ * Refused: mode outside 0 / 1 / 2, T or A < 1, n_count < 1, idx outside [0, T], h < T - idx (sampled steps would leave their row),
+ * n_begin < 0 or n_begin + n_count > eps_rows without index, a null cand / eps, hist_actions null with idx > 0, loc null in modes
+ * 0 / 1, sd null in mode 0. */
+typedef struct m3pc_debug_sample_args {
+    const float* hist_actions;
+    const float* loc;
+    const float* sd;
+    const float* eps;
+    int mode, T, A, idx, h, n_begin, n_count;
+    const int* widx;  /* optional */
+    const int* index; /* optional */
+    float* cand;
+    float* sample_actions; /* optional */
+    float* loc_out;        /* optional */
+    float* sd_out;         /* optional */
+    long long eps_rows;
+    int hist_windows;
+    void* stream;
+    int* picked;
+} m3pc_debug_sample_args;
+int m3pc_debug_sample(const m3pc_debug_sample_args* a);
+/* TD(lambda) scoring (ScoreP).  Refused: a null rewards / boot / expect_return, n < 1, h < 1, scatter_out without scatter_index. */
+typedef struct m3pc_debug_score_args {
+    const float* rewards;
+    const float* boot;
+    int n, h;
+    float boot_scale, gamma;
+    double lmbda;
+    float* expect_return;
+    float* boot_out;          /* optional */
+    const int* scatter_index; /* optional */
+    float* scatter_out;
+    void* stream;
+    int* picked;
+} m3pc_debug_score_args;
+int m3pc_debug_score(const m3pc_debug_score_args* a);
+/* row gather (GatherP): out[b, i] = Xe[b, rowsrc[i]] (rowsrc[i] >= 0) or table[-rowsrc[i] - 1].  rowsrc is a HOST array: the hook
+ * checks every entry against xe_rows / table_rows and uploads it.  Refused: neither output, batch or rows_per_batch < 1, d % 64,
+ * d < 64, d > 1024, an entry of rowsrc outside its source (or a source that is null), xe_bstride % 4 or below xe_rows d where batch > 1
+ * (the batch elements' rows would alias), Xe / table / out off 16 bytes (outb takes 2-byte stores: any address). */
+typedef struct m3pc_debug_gather_args {
+    const float* Xe;
+    long long xe_bstride;
+    const float* table;
+    const int* rowsrc; /* host */
+    int rows_per_batch, batch, d;
+    float* out; /* optional */
+    void* outb; /* optional */
+    int xe_rows, table_rows;
+    void* stream;
+    int* picked;
+} m3pc_debug_gather_args;
+int m3pc_debug_gather_rows(const m3pc_debug_gather_args* a);
+/* the goal overlays (launch_goal_overlay / launch_goal_overlay_rows): windows of T rows of D floats; pred is de-tokenised in place
+ * (normalize) and written over rows t <= idx and idx + 2 <= t <= T - 2 of states_out, the other rows come from states_in; the rows
+ * form reads the nq overlay rows of each window from pred (windows nq, D) instead.  Refused: a null pointer, windows / T / D < 1,
+ * idx outside [0, T - 1], normalize without mean / stdv, nq below the number of overlay rows. */
+int m3pc_debug_goal_overlay(float* pred, const float* states_in, float* states_out, long long windows, int T, int D, int idx,
+                            const float* mean, const float* stdv, int normalize, void* stream, int* picked);
+int m3pc_debug_goal_overlay_rows(const float* pred, const float* states_in, float* states_out, long long windows, int T, int D, int idx,
+                                 int nq, void* stream, int* picked);
 /* in-kernel phase stamps of workgroup 37 of every fused-tail launch as the step runs: cap > 0 starts a ring of cap entries
  * (64 int64 each), cap == 0 copies it to `out` (host), reports the number of launches logged and stops */
 int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged);

@@ -6,6 +6,10 @@
 
 namespace m3pc {
 
+#ifdef M3PC_LAB
+thread_local int g_ew_picked = 0;
+#endif
+
 __device__ __forceinline__ int map_row(const RowMap& m, int r) {
     if (m.rpg == 0) return r;
     return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
@@ -226,6 +230,7 @@ void launch_embed(const EmbedP& p, hipStream_t st) {
         const int nchunk = (p.batch + CB - 1) / CB;
         const int waves = p.L * nchunk;
         const dim3 grid((waves + 3) / 4), block(256);
+        M3PC_EW_PICK(1 + p.d / 256);
         switch (p.d / 256) {
             case 1: hipLaunchKernelGGL(embed_rows_kernel<1>, grid, block, 0, st, p, CB, nchunk); break;
             case 2: hipLaunchKernelGGL(embed_rows_kernel<2>, grid, block, 0, st, p, CB, nchunk); break;
@@ -234,6 +239,7 @@ void launch_embed(const EmbedP& p, hipStream_t st) {
         }
         return;
     }
+    M3PC_EW_PICK(1);
     hipLaunchKernelGGL(embed_kernel, dim3((unsigned)rows), dim3(p.d < 256 ? p.d : 256), 0, st, p);
 }
 
@@ -258,6 +264,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherP p) {
 void launch_gather_rows(const GatherP& p, hipStream_t st) {
     const long long rows = (long long)p.batch * p.rows_per_batch;
     if (rows <= 0) return;
+    M3PC_EW_PICK(6);
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)rows), dim3(p.d / 4 < 256 ? p.d / 4 : 256), 0, st, p);
 }
 
@@ -475,6 +482,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnP p) {
 template <int RPW>
 static void launch_ln_rows(const LnP& p, hipStream_t st) {
     const dim3 grid((p.rows + 4 * RPW - 1) / (4 * RPW)), block(256);
+    M3PC_EW_PICK(RPW == 2 ? 8 + p.d / 256 : 0);  // (RPW 4: the A/B-only instances have no id)
     switch (p.d / 256) {
         case 1: hipLaunchKernelGGL((layernorm_rows_kernel<1, RPW>), grid, block, 0, st, p); return;
         case 2: hipLaunchKernelGGL((layernorm_rows_kernel<2, RPW>), grid, block, 0, st, p); return;
@@ -490,10 +498,13 @@ void launch_layernorm(const LnP& p, hipStream_t st) {
         if (rpw == 4) return launch_ln_rows<4>(p, st);
         if (rpw == 2) return launch_ln_rows<2>(p, st);
     }
-    if (p.d % 256 == 0 && p.ldx % 4 == 0)
+    if (p.d % 256 == 0 && p.ldx % 4 == 0) {
+        M3PC_EW_PICK(8);
         hipLaunchKernelGGL(layernorm_vec_kernel, dim3((p.rows + 3) / 4), dim3(256), 0, st, p);
-    else
+    } else {
+        M3PC_EW_PICK(7);
         hipLaunchKernelGGL(layernorm_kernel, dim3((p.rows + 3) / 4), dim3(256), 0, st, p);
+    }
 }
 
 // ------------------------------------------------------------------------------------------ head out
@@ -597,9 +608,11 @@ void launch_head_out(const HeadOutP& p, hipStream_t st) {
     if (p.rows <= 0) return;
     if (p.Xb) {  // (the caller asked head_out_mfma_covers first)
         const int n_tiles = (p.rows + 127) / 128;
+        M3PC_EW_PICK(14);
         hipLaunchKernelGGL(head_out_mfma_kernel, dim3(n_tiles < 512 ? n_tiles : 512), dim3(256), 0, st, p, n_tiles);
         return;
     }
+    M3PC_EW_PICK(13);
     hipLaunchKernelGGL(head_out_kernel, dim3((p.rows + 3) / 4), dim3(256), 0, st, p);
 }
 
@@ -711,9 +724,11 @@ void launch_actor_head(const ActorP& p, hipStream_t st) {
     if (p.rows <= 0) return;
     const dim3 grid((p.rows + 3) / 4), block(256);
     if (actor_head_fuses_ln(p.d, p.A)) {
+        M3PC_EW_PICK(p.A <= 4 ? 15 : 16);
         if (p.A <= 4) hipLaunchKernelGGL((actor_head_kernel<4>), grid, block, 0, st, p);
         else hipLaunchKernelGGL((actor_head_kernel<8>), grid, block, 0, st, p);
     } else {
+        M3PC_EW_PICK(17);
         hipLaunchKernelGGL(actor_head_small_kernel, grid, block, 0, st, p);  // (ln_g must be null: callers ask actor_head_fuses_ln)
     }
 }
@@ -756,6 +771,7 @@ void launch_sample(const SampleP& p, hipStream_t st) {
     const long long tot = (long long)p.n_count * p.T * p.A;
     if (tot <= 0) return;
     const int grid = (int)((tot + 255) / 256 < 2048 ? (tot + 255) / 256 : 2048);
+    M3PC_EW_PICK(18);
     hipLaunchKernelGGL(sample_kernel, dim3(grid), dim3(256), 0, st, p);
 }
 
@@ -935,11 +951,13 @@ void launch_critic(const CriticP& p, hipStream_t st) {
     if (p.rows <= 0) return;
     if (p.W1F[0] && critic_mfma_covers(p.S, p.A, p.hidden)) {
         const dim3 grid((p.rows + 127) / 128), block(256);
+        M3PC_EW_PICK(p.hidden == 256 ? 22 : p.hidden == 128 ? 21 : 20);
         if (p.hidden == 256) hipLaunchKernelGGL(critic_mfma_kernel<8>, grid, block, 0, st, p);
         else if (p.hidden == 128) hipLaunchKernelGGL(critic_mfma_kernel<4>, grid, block, 0, st, p);
         else hipLaunchKernelGGL(critic_mfma_kernel<2>, grid, block, 0, st, p);
         return;
     }
+    M3PC_EW_PICK(19);
     hipLaunchKernelGGL(critic_kernel, dim3((p.rows + CR_ROWS - 1) / CR_ROWS), dim3(256), 0, st, p);
 }
 
@@ -977,6 +995,7 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreP p) {
 }
 void launch_score(const ScoreP& p, hipStream_t st) {
     if (p.n <= 0) return;
+    M3PC_EW_PICK(23);
     hipLaunchKernelGGL(score_kernel, dim3((p.n + 255) / 256), dim3(256), 0, st, p);
 }
 
@@ -1013,12 +1032,14 @@ void launch_tokenize(const void* in, int in_f64, float* out, long long rows, int
                      int normalize, hipStream_t st) {
     const long long n = rows * D;
     if (n <= 0) return;
+    M3PC_EW_PICK(24);
     hipLaunchKernelGGL(tokenize_kernel, dim3(grid_for(n)), dim3(256), 0, st, in, in_f64, out, n, D, mean, stdv, normalize);
 }
 void launch_detokenize(const float* in, float* out, long long rows, int D, const float* mean, const float* stdv,
                        int normalize, hipStream_t st) {
     const long long n = rows * D;
     if (n <= 0) return;
+    M3PC_EW_PICK(25);
     hipLaunchKernelGGL(detokenize_kernel, dim3(grid_for(n)), dim3(256), 0, st, in, out, n, D, mean, stdv, normalize);
 }
 
@@ -1038,6 +1059,7 @@ void launch_goal_overlay(float* pred, const float* states_in, float* states_out,
                          const float* mean, const float* stdv, int normalize, hipStream_t st) {
     const long long n = rows * D;
     if (n <= 0) return;
+    M3PC_EW_PICK(26);
     hipLaunchKernelGGL(goal_overlay_kernel, dim3(grid_for(n)), dim3(256), 0, st, pred, states_in, states_out, n, T, D, idx, mean, stdv, normalize);
 }
 
@@ -1059,6 +1081,7 @@ void launch_goal_overlay_rows(const float* pred, const float* states_in, float* 
                               int nq, hipStream_t st) {
     const long long n = windows * T * D;
     if (n <= 0) return;
+    M3PC_EW_PICK(27);
     hipLaunchKernelGGL(goal_overlay_rows_kernel, dim3(grid_for(n)), dim3(256), 0, st, pred, states_in, states_out, n, T, D, idx, nq);
 }
 

@@ -302,6 +302,14 @@ extern thread_local int g_attn_picked;
 #define M3PC_ATTN_PICK(id) ((void)0)
 #endif
 void launch_attention_bf16(const AttnP& p, hipStream_t st);
+// lab build: the id of the elementwise.hip kernel the calling thread launched last (the list is in include/m3pc_hip_debug.h,
+// "Elementwise kernel ids"); the product build records nothing
+#ifdef M3PC_LAB
+extern thread_local int g_ew_picked;
+#define M3PC_EW_PICK(id) (::m3pc::g_ew_picked = (id))
+#else
+#define M3PC_EW_PICK(id) ((void)0)
+#endif
 // lab build: what the GEMM dispatch launched last on the calling thread -- {kernel id, split count S (1: K not split), peel row
 // (0: off), flags: 1 persistent form, 2 the split-K reduce applied the LayerNorm, 4 grouped launch}; the ids are listed in
 // include/m3pc_hip_debug.h (m3pc_debug_gemm_ex).  With g_gemm_dry set the launchers of gemm.hip, gemm_x3.hip, gemm_glds.hip,

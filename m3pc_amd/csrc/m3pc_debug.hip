@@ -2,6 +2,8 @@
 // include/m3pc_hip_debug.h.  The product build does not compile this file.
 #include "m3pc_internal.h"
 
+#include <vector>
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -624,14 +626,30 @@ int m3pc_debug_block_res_row(int r, int res_L, int res_nshared) {
 }
 
 // the embedding kernel (launch_embed) on caller tensors (include/m3pc_hip_debug.h)
-int m3pc_debug_embed(const m3pc_debug_embed_args* a) {
+static int debug_embed_run(const m3pc_debug_embed_args* a, float* Hf) {
     if (!a) return fail(M3PC_EINVAL, "debug_embed: null arguments");
-    if (a->batch < 1 || a->L < 1 || a->d % 256 != 0 || a->d < 256 || a->d > 1024 || !a->tokmap) return fail(M3PC_EINVAL, "debug_embed: batch / L / d / tokmap");
+    g_ew_picked = 0;
+    if (a->batch < 1 || a->L < 1 || a->d % 64 != 0 || a->d < 64 || a->d > 1024 || !a->tokmap) return fail(M3PC_EINVAL, "debug_embed: batch / L / d / tokmap");
+    const bool block_form = a->d % 256 != 0;  // (launch_embed: embed_kernel, one block per row)
+    if (block_form && (a->Xb || a->n_sh || a->n_indep || a->x_first_only || a->x_compact))
+        return fail(M3PC_EINVAL, "debug_embed: d %d runs embed_kernel, which has no Xb / n_sh / n_indep / x_first_only / x_compact", a->d);
+    if (a->T < 1 || (long long)a->batch * a->L > 0x7fffffffLL) return fail(M3PC_EINVAL, "debug_embed: T / batch * L");
     if (a->n_indep < 0 || a->n_indep > a->L || a->n_sh < 0 || a->n_sh > a->n_indep) return fail(M3PC_EINVAL, "debug_embed: n_indep / n_sh");
     if (!a->X == !a->Xb) return fail(M3PC_EINVAL, "debug_embed: exactly one of X / Xb");
     if (a->x_compact && !(a->Xb && a->x_first_only && a->n_indep > 0)) return fail(M3PC_EINVAL, "debug_embed: x_compact needs Xb, x_first_only and n_indep > 0");
-    if ((a->Hb || a->n_sh) && (!a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_embed: Hb without ln_g / ln_b");
+    if ((a->Hb || Hf || a->n_sh) && (!a->ln_g || !a->ln_b)) return fail(M3PC_EINVAL, "debug_embed: Hb / Hf without ln_g / ln_b");
+    if (Hf && (a->n_sh || ((uintptr_t)Hf & 15))) return fail(M3PC_EINVAL, "debug_embed: Hf with n_sh, or off 16 bytes");
     if (a->n_sh > 0 && (!a->Hb || !a->Hb_sh)) return fail(M3PC_EINVAL, "debug_embed: n_sh without Hb / Hb_sh");
+    {  // the entries of tokmap: a key the call carries, a step inside the table E
+        std::vector<int> tm((size_t)a->L * 2);
+        HIPCHK(hipMemcpy(tm.data(), a->tokmap, tm.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int j = 0; j < a->L; ++j) {
+            const int key = tm[2 * j], t = tm[2 * j + 1];
+            if (key < 0 || key > 3 || t < 0 || t >= a->T) return fail(M3PC_EINVAL, "debug_embed: token %d is {key %d, step %d}", j, key, t);
+            if (!a->tok[key] || !a->WT[key] || !a->E[key] || a->feat[key] < 1 || (block_form && a->feat[key] > 32))
+                return fail(M3PC_EINVAL, "debug_embed: key %d of token %d lacks tok / WT / E or has feat %d", key, j, a->feat[key]);
+        }
+    }
     EmbedP e;
     memset(&e, 0, sizeof(e));
     for (int k = 0; k < 4; ++k) {
@@ -650,6 +668,7 @@ int m3pc_debug_embed(const m3pc_debug_embed_args* a) {
     e.Xb = (bf16_t*)a->Xb;
     e.ln_g = a->ln_g;
     e.ln_b = a->ln_b;
+    e.Hf = Hf;
     e.Hb = (bf16_t*)a->Hb;
     e.Hb_sh = (bf16_t*)a->Hb_sh;
     e.n_indep = a->n_indep;
@@ -658,6 +677,343 @@ int m3pc_debug_embed(const m3pc_debug_embed_args* a) {
     e.x_compact = a->x_compact ? 1 : 0;
     launch_embed(e, (hipStream_t)a->stream);
     return check_launch("debug_embed");
+}
+int m3pc_debug_embed(const m3pc_debug_embed_args* a) { return debug_embed_run(a, nullptr); }
+int m3pc_debug_embed_ex(const m3pc_debug_embed_ex_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_embed_ex: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    const int rc = debug_embed_run(&a->base, a->Hf);
+    if (rc == 0 && a->picked) a->picked[0] = g_ew_picked;
+    return rc;
+}
+
+// ---- csrc/elementwise.hip, kernel by kernel (include/m3pc_hip_debug.h, "Elementwise kernel ids"; tests/test_elementwise_edges_gpu.py).
+// Every hook checks first, fills the kernel's parameter structure, goes through the production launcher and reports what that
+// launcher recorded.
+int m3pc_debug_elementwise_picked(void) { return g_ew_picked; }
+static bool ew_bad_map(const int* m) { return m[0] < 0 || m[2] < 0 || (m[0] >= 1 && m[1] < m[0]); }
+static bool ew_bad_d(int d) { return d < 64 || d > 1024 || d % 64 != 0; }
+static int ew_done(int* picked, const char* what) {
+    if (picked) picked[0] = g_ew_picked;
+    return check_launch(what);
+}
+
+int m3pc_debug_layernorm(const m3pc_debug_ln_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_layernorm: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    if (!a->X || !a->g1 || !a->b1) return fail(M3PC_EINVAL, "debug_layernorm: X, g1 and b1 are required");
+    if (!a->Yf && !a->Yb) return fail(M3PC_EINVAL, "debug_layernorm: neither Yf nor Yb");
+    if ((a->g2 != nullptr) != (a->b2 != nullptr)) return fail(M3PC_EINVAL, "debug_layernorm: g2 and b2 go together");
+    if (a->rows < 1) return fail(M3PC_EINVAL, "debug_layernorm: rows %d", a->rows);
+    if (ew_bad_d(a->d)) return fail(M3PC_EINVAL, "debug_layernorm: d %d is not a multiple of 64 in [64, 1024] (a lane holds at most 16 values)", a->d);
+    if (a->ldx < a->d) return fail(M3PC_EINVAL, "debug_layernorm: ldx %d below d %d", a->ldx, a->d);
+    if (ew_bad_map(a->xmap)) return fail(M3PC_EINVAL, "debug_layernorm: row map {%d, %d, %d}", a->xmap[0], a->xmap[1], a->xmap[2]);
+    if (a->d % 256 == 0 && a->ldx % 4 == 0) {  // layernorm_vec_kernel / layernorm_rows_kernel: 16-byte loads, 16- and 8-byte stores
+        const uintptr_t p16 = (uintptr_t)a->X | (uintptr_t)a->g1 | (uintptr_t)a->b1 | (uintptr_t)a->g2 | (uintptr_t)a->b2 | (uintptr_t)a->Yf;
+        if ((p16 & 15) || ((uintptr_t)a->Yb & 7)) return fail(M3PC_EINVAL, "debug_layernorm: the 16-byte kernels need X / g / b / Yf on 16 bytes and Yb on 8");
+    }
+    LnP p;
+    memset(&p, 0, sizeof(p));
+    p.X = a->X;
+    p.ldx = a->ldx;
+    p.xmap = RowMap{a->xmap[0], a->xmap[1], a->xmap[2]};
+    p.rows = a->rows;
+    p.d = a->d;
+    p.g1 = a->g1;
+    p.b1 = a->b1;
+    p.g2 = a->g2;
+    p.b2 = a->b2;
+    p.Yf = a->Yf;
+    p.Yb = (bf16_t*)a->Yb;
+    g_ew_picked = 0;
+    launch_layernorm(p, (hipStream_t)a->stream);
+    return ew_done(a->picked, "debug_layernorm");
+}
+
+int m3pc_debug_head_out(const m3pc_debug_head_out_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_head_out: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    if (!a->W || !a->b || !a->Y) return fail(M3PC_EINVAL, "debug_head_out: W, b and Y are required");
+    if ((a->mean != nullptr) != (a->stdv != nullptr)) return fail(M3PC_EINVAL, "debug_head_out: mean and stdv go together");
+    if (a->rows < 1) return fail(M3PC_EINVAL, "debug_head_out: rows %d", a->rows);
+    if (ew_bad_d(a->d)) return fail(M3PC_EINVAL, "debug_head_out: d %d is not a multiple of 64 in [64, 1024]", a->d);
+    if (a->D < 1 || a->D > 32) return fail(M3PC_EINVAL, "debug_head_out: D %d outside [1, 32]", a->D);
+    if (a->ldx < a->d || a->ldy < a->D) return fail(M3PC_EINVAL, "debug_head_out: ldx %d / ldy %d below d / D", a->ldx, a->ldy);
+    if (ew_bad_map(a->ymap)) return fail(M3PC_EINVAL, "debug_head_out: row map {%d, %d, %d}", a->ymap[0], a->ymap[1], a->ymap[2]);
+    const bool mfma = a->Xb && head_out_mfma_covers(a->rows, a->d, a->D);  // (as the callers ask before they hand over bf16 rows)
+    if (!mfma && !a->X) return fail(M3PC_EINVAL, "debug_head_out: no fp32 rows, and the matrix-core kernel does not cover %d rows of d %d", a->rows, a->d);
+    if (mfma && (((uintptr_t)a->Xb & 15) || a->ldx % 8)) return fail(M3PC_EINVAL, "debug_head_out: the matrix-core kernel reads 16 bytes of a bf16 row at a time (Xb, ldx %% 8)");
+    HeadOutP p;
+    memset(&p, 0, sizeof(p));
+    if (mfma) p.Xb = (const bf16_t*)a->Xb;
+    else p.X = a->X;
+    p.ldx = a->ldx;
+    p.rows = a->rows;
+    p.d = a->d;
+    p.D = a->D;
+    p.W = a->W;
+    p.b = a->b;
+    p.mean = a->mean;
+    p.stdv = a->stdv;
+    p.Y = a->Y;
+    p.ymap = RowMap{a->ymap[0], a->ymap[1], a->ymap[2]};
+    p.ldy = a->ldy;
+    g_ew_picked = 0;
+    launch_head_out(p, (hipStream_t)a->stream);
+    return ew_done(a->picked, "debug_head_out");
+}
+
+int m3pc_debug_actor_head(const m3pc_debug_actor_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_actor_head: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    if (!a->X || !a->Wmu || !a->bmu || !a->Wls || !a->bls || !a->mu || !a->sd) return fail(M3PC_EINVAL, "debug_actor_head: a required pointer is null");
+    if ((a->ln_g != nullptr) != (a->ln_b != nullptr)) return fail(M3PC_EINVAL, "debug_actor_head: ln_g and ln_b go together");
+    if (a->rows < 1) return fail(M3PC_EINVAL, "debug_actor_head: rows %d", a->rows);
+    if (ew_bad_d(a->d)) return fail(M3PC_EINVAL, "debug_actor_head: d %d is not a multiple of 64 in [64, 1024]", a->d);
+    if (a->A < 1 || a->A > 32) return fail(M3PC_EINVAL, "debug_actor_head: A %d outside [1, 32]", a->A);
+    if (a->ldx < a->d) return fail(M3PC_EINVAL, "debug_actor_head: ldx %d below d %d", a->ldx, a->d);
+    if (ew_bad_map(a->xmap)) return fail(M3PC_EINVAL, "debug_actor_head: row map {%d, %d, %d}", a->xmap[0], a->xmap[1], a->xmap[2]);
+    const bool fuses = actor_head_fuses_ln(a->d, a->A);
+    if (a->ln_g && !fuses) return fail(M3PC_EINVAL, "debug_actor_head: ln_g at d %d, A %d (actor_head_small_kernel has no LayerNorm: it would be dropped)", a->d, a->A);
+    if (fuses) {  // actor_head_kernel: 16-byte loads of the row, the weight rows and the norm's vectors
+        const uintptr_t p16 = (uintptr_t)a->X | (uintptr_t)a->Wmu | (uintptr_t)a->Wls | (uintptr_t)a->ln_g | (uintptr_t)a->ln_b;
+        if ((p16 & 15) || a->ldx % 4) return fail(M3PC_EINVAL, "debug_actor_head: actor_head_kernel needs X / Wmu / Wls / ln_g / ln_b on 16 bytes and ldx %% 4 == 0");
+    }
+    ActorP p;
+    memset(&p, 0, sizeof(p));
+    p.X = a->X;
+    p.ldx = a->ldx;
+    p.xmap = RowMap{a->xmap[0], a->xmap[1], a->xmap[2]};
+    p.rows = a->rows;
+    p.d = a->d;
+    p.A = a->A;
+    p.Wmu = a->Wmu;
+    p.bmu = a->bmu;
+    p.Wls = a->Wls;
+    p.bls = a->bls;
+    p.mu = a->mu;
+    p.sd = a->sd;
+    p.ln_g = a->ln_g;
+    p.ln_b = a->ln_b;
+    g_ew_picked = 0;
+    launch_actor_head(p, (hipStream_t)a->stream);
+    return ew_done(a->picked, "debug_actor_head");
+}
+
+int m3pc_debug_critic_pack(const float* W1, const float* W2, int SA, int hidden, float* w1f, float* w2f, long long* n_w1f, long long* n_w2f) {
+    if (SA < 1 || SA > 32 || (hidden != 64 && hidden != 128 && hidden != 256)) return fail(M3PC_EINVAL, "debug_critic_pack: SA %d / hidden %d", SA, hidden);
+    if (n_w1f) *n_w1f = (long long)critic_w1f_floats(hidden);
+    if (n_w2f) *n_w2f = (long long)critic_w2f_floats(hidden);
+    if (!w1f && !w2f) return 0;
+    if (!W1 || !W2 || !w1f || !w2f) return fail(M3PC_EINVAL, "debug_critic_pack: null array");
+    critic_pack(W1, W2, SA, hidden, w1f, w2f);
+    return 0;
+}
+
+int m3pc_debug_critic(const m3pc_debug_critic_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_critic: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    if (!a->states || !a->actions || !a->om || !a->os || !a->q) return fail(M3PC_EINVAL, "debug_critic: a required pointer is null");
+    for (int n = 0; n < 2; ++n)
+        if (!a->W1[n] || !a->b1[n] || !a->W2[n] || !a->b2[n] || !a->W3[n] || !a->b3[n]) return fail(M3PC_EINVAL, "debug_critic: network %d lacks a tensor", n);
+    if (a->rows < 1) return fail(M3PC_EINVAL, "debug_critic: rows %d", a->rows);
+    if (a->S < 1 || a->S > 32 || a->A < 1 || a->A > 32) return fail(M3PC_EINVAL, "debug_critic: S %d / A %d outside [1, 32] (S + A <= 64 floats of LDS per row)", a->S, a->A);
+    if (a->hidden < 1 || a->hidden > 256) return fail(M3PC_EINVAL, "debug_critic: hidden %d outside [1, 256] (one thread per hidden unit)", a->hidden);
+    const int SA = a->S + a->A, Hd = a->hidden;
+    const bool mfma = !a->force_scalar && critic_mfma_covers(a->S, a->A, Hd);
+    if (mfma) {
+        uintptr_t p16 = 0;
+        for (int n = 0; n < 2; ++n) p16 |= (uintptr_t)a->b1[n] | (uintptr_t)a->b2[n] | (uintptr_t)a->W3[n];
+        if (p16 & 15) return fail(M3PC_EINVAL, "debug_critic: critic_mfma_kernel reads b1 / b2 / W3 16 bytes at a time");
+    }
+    // per network: W1T (SA, Hd) | W2T (Hd, Hd) | W1F | W2F.  (A lab hook's shortcut: a function-static buffer that grows and is
+    // never freed; calls from two threads would share it)
+    const size_t n1 = (size_t)SA * Hd, n2 = (size_t)Hd * Hd, nf1 = mfma ? critic_w1f_floats(Hd) : 0, nf2 = mfma ? critic_w2f_floats(Hd) : 0;
+    const size_t per = (n1 + n2 + nf1 + nf2 + 3) & ~(size_t)3;  // (every part a multiple of 4 floats but W1T / W2T at odd sizes)
+    std::vector<float> host(2 * per + 8, 0.f);
+    size_t off[2][4];
+    for (int n = 0; n < 2; ++n) {
+        size_t o = n * per;
+        // the 16-byte parts first, so that they stay on 16 bytes
+        off[n][2] = o; o += nf1;
+        off[n][3] = o; o += nf2;
+        off[n][0] = o; o += n1;
+        off[n][1] = o;
+        float* w1t = host.data() + off[n][0];
+        float* w2t = host.data() + off[n][1];
+        for (int c = 0; c < Hd; ++c)
+            for (int f = 0; f < SA; ++f) w1t[(size_t)f * Hd + c] = a->W1[n][(size_t)c * SA + f];
+        for (int c = 0; c < Hd; ++c)
+            for (int k = 0; k < Hd; ++k) w2t[(size_t)k * Hd + c] = a->W2[n][(size_t)c * Hd + k];
+        if (mfma) critic_pack(a->W1[n], a->W2[n], SA, Hd, host.data() + off[n][2], host.data() + off[n][3]);
+    }
+    static float* dev = nullptr;
+    static size_t cap = 0;
+    hipStream_t st = (hipStream_t)a->stream;
+    HIPCHK(hipStreamSynchronize(st));  // (an earlier call on this stream may still read the buffer)
+    if (host.size() > cap) {
+        if (dev) HIPCHK(hipFree(dev));
+        dev = nullptr;
+        cap = 0;
+        HIPCHK(hipMalloc((void**)&dev, host.size() * sizeof(float)));
+        cap = host.size();
+    }
+    HIPCHK(hipMemcpy(dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    CriticP p;
+    memset(&p, 0, sizeof(p));
+    p.states = a->states;
+    p.actions = a->actions;
+    p.rows = a->rows;
+    p.S = a->S;
+    p.A = a->A;
+    p.hidden = Hd;
+    p.om = a->om;
+    p.os = a->os;
+    for (int n = 0; n < 2; ++n) {
+        p.W1T[n] = dev + off[n][0];
+        p.W2T[n] = dev + off[n][1];
+        p.b1[n] = a->b1[n];
+        p.b2[n] = a->b2[n];
+        p.W3[n] = a->W3[n];
+        p.b3[n] = a->b3[n];
+        p.W1F[n] = mfma ? dev + off[n][2] : nullptr;
+        p.W2F[n] = mfma ? dev + off[n][3] : nullptr;
+    }
+    p.q = a->q;
+    g_ew_picked = 0;
+    launch_critic(p, st);
+    return ew_done(a->picked, "debug_critic");
+}
+
+int m3pc_debug_sample(const m3pc_debug_sample_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_sample: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    if (a->mode < 0 || a->mode > 2) return fail(M3PC_EINVAL, "debug_sample: mode %d", a->mode);
+    if (a->T < 1 || a->A < 1 || a->n_count < 1) return fail(M3PC_EINVAL, "debug_sample: T / A / n_count below 1");
+    if (a->idx < 0 || a->idx > a->T) return fail(M3PC_EINVAL, "debug_sample: idx %d outside [0, T = %d]", a->idx, a->T);
+    if (a->h < a->T - a->idx) return fail(M3PC_EINVAL, "debug_sample: h %d below T - idx = %d (a sampled step would leave its row)", a->h, a->T - a->idx);
+    if (!a->cand || !a->eps) return fail(M3PC_EINVAL, "debug_sample: cand and eps are required");
+    if (a->idx > 0 && !a->hist_actions) return fail(M3PC_EINVAL, "debug_sample: idx > 0 without hist_actions");
+    if ((a->mode <= 1 && !a->loc) || (a->mode == 0 && !a->sd)) return fail(M3PC_EINVAL, "debug_sample: mode %d without loc / sd", a->mode);
+    if (a->eps_rows < 1 || a->hist_windows < 1 || (a->hist_windows > 1 && !a->widx)) return fail(M3PC_EINVAL, "debug_sample: eps_rows / hist_windows");
+    if (!a->index && (a->n_begin < 0 || (long long)a->n_begin + a->n_count > a->eps_rows))
+        return fail(M3PC_EINVAL, "debug_sample: rows [%d, %d + %d) outside the %lld rows of eps", a->n_begin, a->n_begin, a->n_count, a->eps_rows);
+    SampleP p;
+    memset(&p, 0, sizeof(p));
+    p.hist_actions = a->hist_actions;
+    p.loc = a->loc;
+    p.sd = a->sd;
+    p.eps = a->eps;
+    p.mode = a->mode;
+    p.T = a->T;
+    p.A = a->A;
+    p.idx = a->idx;
+    p.h = a->h;
+    p.n_begin = a->n_begin;
+    p.n_count = a->n_count;
+    p.widx = a->widx;
+    p.index = a->index;
+    p.cand = a->cand;
+    p.sample_actions = a->sample_actions;
+    p.loc_out = a->loc_out;
+    p.sd_out = a->sd_out;
+    g_ew_picked = 0;
+    launch_sample(p, (hipStream_t)a->stream);
+    return ew_done(a->picked, "debug_sample");
+}
+
+int m3pc_debug_score(const m3pc_debug_score_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_score: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    if (!a->rewards || !a->boot || !a->expect_return) return fail(M3PC_EINVAL, "debug_score: rewards, boot and expect_return are required");
+    if (a->n < 1 || a->h < 1) return fail(M3PC_EINVAL, "debug_score: n %d / h %d", a->n, a->h);
+    if (a->scatter_out && !a->scatter_index) return fail(M3PC_EINVAL, "debug_score: scatter_out without scatter_index");
+    ScoreP p;
+    memset(&p, 0, sizeof(p));
+    p.rewards = a->rewards;
+    p.boot = a->boot;
+    p.n = a->n;
+    p.h = a->h;
+    p.boot_scale = a->boot_scale;
+    p.gamma = a->gamma;
+    p.lmbda = a->lmbda;
+    p.expect_return = a->expect_return;
+    p.boot_out = a->boot_out;
+    p.scatter_index = a->scatter_index;
+    p.scatter_out = a->scatter_out;
+    g_ew_picked = 0;
+    launch_score(p, (hipStream_t)a->stream);
+    return ew_done(a->picked, "debug_score");
+}
+
+int m3pc_debug_gather_rows(const m3pc_debug_gather_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_gather_rows: null arguments");
+    if (a->picked) a->picked[0] = 0;
+    if (!a->out && !a->outb) return fail(M3PC_EINVAL, "debug_gather_rows: neither out nor outb");
+    if (!a->rowsrc || a->batch < 1 || a->rows_per_batch < 1 || (long long)a->batch * a->rows_per_batch > 0x7fffffffLL)
+        return fail(M3PC_EINVAL, "debug_gather_rows: rowsrc / batch / rows_per_batch");
+    if (ew_bad_d(a->d)) return fail(M3PC_EINVAL, "debug_gather_rows: d %d is not a multiple of 64 in [64, 1024]", a->d);
+    if ((((uintptr_t)a->Xe | (uintptr_t)a->table | (uintptr_t)a->out) & 15) || a->xe_bstride % 4 || a->xe_bstride < 0)
+        return fail(M3PC_EINVAL, "debug_gather_rows: rows move 16 bytes at a time (Xe, table, out, xe_bstride %% 4)");
+    if (a->Xe && a->batch > 1 && a->xe_bstride < (long long)a->xe_rows * a->d)
+        return fail(M3PC_EINVAL, "debug_gather_rows: xe_bstride %lld below xe_rows * d = %lld (the batch elements' rows would alias)", a->xe_bstride, (long long)a->xe_rows * a->d);
+    for (int i = 0; i < a->rows_per_batch; ++i) {
+        const int s = a->rowsrc[i];
+        if (s >= 0 ? (!a->Xe || s >= a->xe_rows) : (!a->table || -(long long)s - 1 >= a->table_rows))
+            return fail(M3PC_EINVAL, "debug_gather_rows: rowsrc[%d] = %d outside its source (%d rows of Xe, %d of the table)", i, s, a->xe_rows, a->table_rows);
+    }
+    static int* dsrc = nullptr;  // (a lab hook's shortcut, as in m3pc_debug_gemm_ex)
+    static int cap = 0;
+    hipStream_t st = (hipStream_t)a->stream;
+    HIPCHK(hipStreamSynchronize(st));
+    if (a->rows_per_batch > cap) {
+        if (dsrc) HIPCHK(hipFree(dsrc));
+        dsrc = nullptr;
+        cap = 0;
+        HIPCHK(hipMalloc((void**)&dsrc, (size_t)a->rows_per_batch * sizeof(int)));
+        cap = a->rows_per_batch;
+    }
+    HIPCHK(hipMemcpy(dsrc, a->rowsrc, (size_t)a->rows_per_batch * sizeof(int), hipMemcpyHostToDevice));
+    GatherP p;
+    memset(&p, 0, sizeof(p));
+    p.Xe = a->Xe;
+    p.xe_bstride = a->xe_bstride;
+    p.table = a->table;
+    p.rowsrc = dsrc;
+    p.rows_per_batch = a->rows_per_batch;
+    p.batch = a->batch;
+    p.d = a->d;
+    p.out = a->out;
+    p.outb = (bf16_t*)a->outb;
+    g_ew_picked = 0;
+    launch_gather_rows(p, st);
+    return ew_done(a->picked, "debug_gather_rows");
+}
+
+static int ew_overlay_check(const char* what, const void* pred, const void* in, const void* out, long long windows, int T, int D, int idx) {
+    if (!pred || !in || !out) return fail(M3PC_EINVAL, "%s: null pointer", what);
+    if (windows < 1 || T < 1 || D < 1 || windows > (1LL << 40) / ((long long)T * D)) return fail(M3PC_EINVAL, "%s: windows / T / D", what);
+    if (idx < 0 || idx > T - 1) return fail(M3PC_EINVAL, "%s: idx %d outside [0, T - 1 = %d]", what, idx, T - 1);
+    return 0;
+}
+int m3pc_debug_goal_overlay(float* pred, const float* states_in, float* states_out, long long windows, int T, int D, int idx,
+                            const float* mean, const float* stdv, int normalize, void* stream, int* picked) {
+    if (picked) picked[0] = 0;
+    CHK(ew_overlay_check("debug_goal_overlay", pred, states_in, states_out, windows, T, D, idx));
+    if (normalize && (!mean || !stdv)) return fail(M3PC_EINVAL, "debug_goal_overlay: normalize without mean / stdv");
+    g_ew_picked = 0;
+    launch_goal_overlay(pred, states_in, states_out, windows * T, T, D, idx, mean, stdv, normalize ? 1 : 0, (hipStream_t)stream);
+    return ew_done(picked, "debug_goal_overlay");
+}
+int m3pc_debug_goal_overlay_rows(const float* pred, const float* states_in, float* states_out, long long windows, int T, int D, int idx,
+                                 int nq, void* stream, int* picked) {
+    if (picked) picked[0] = 0;
+    CHK(ew_overlay_check("debug_goal_overlay_rows", pred, states_in, states_out, windows, T, D, idx));
+    const int n_over = idx + 1 + (T - 1 - (idx + 2) > 0 ? T - 1 - (idx + 2) : 0);  // rows t <= idx, then idx + 2 <= t <= T - 2
+    if (nq < n_over) return fail(M3PC_EINVAL, "debug_goal_overlay_rows: nq %d below the %d overlay rows of a window", nq, n_over);
+    g_ew_picked = 0;
+    launch_goal_overlay_rows(pred, states_in, states_out, windows, T, D, idx, nq, (hipStream_t)stream);
+    return ew_done(picked, "debug_goal_overlay_rows");
 }
 
 // kv_fused_kernel alone (tests/test_block_fused_gpu.py): n candidates of Le rows each in Z (n*Le, 512) bf16; group g holds
