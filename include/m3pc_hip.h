@@ -398,7 +398,8 @@ int m3pc_rescore_merge_race(m3pc_handle* h, const float* scores, const float* ex
                             float* stats, float* host_stats, float seq, void* stream);
 /* m3pc_rescore_merge_race followed by m3pc_select on the merged vector (with the same expo / temperature), in ONE launch: both are
  * one workgroup over the whole vector, and the re-score's tail is a chain of dependent launches.  The certificate's statistics
- * reach host_stats before the select part runs.  Arguments as the two calls. */
+ * reach host_stats before the select part runs.  Arguments as the two calls.
+ * Contract: scores and list_rescored hold no NaN (m3pc_select's contract applies to the merged vector the select part reads). */
 int m3pc_merge_race_select(m3pc_handle* h, const float* scores, const float* expo, float temperature, int n_total, const int* list,
                            int r, int n, const float* list_scores, const float* list_rescored, float delta, float* merged,
                            float* stats, float* host_stats, float seq, const float* a0, long long a0_stride, float* p,
@@ -416,7 +417,9 @@ int m3pc_rescore_listed(m3pc_handle* h, const m3pc_plan_args* args, const float*
  *             q = empty_like(p).exponential_(1) drawn from the caller's generator; passing that q
  *             here reproduces torch's draw without its dozen tiny launches.
  *   p device out (n,), eval_action device out (A,), argmax device out (1,),
- *   sample_idx device out (1,), sample_action device out (A,) -- each optional */
+ *   sample_idx device out (1,), sample_action device out (A,) -- each optional
+ * Contract: expect_return holds no NaN.  A NaN score is never picked by the arg-max or by the race; a vector of NaN alone leaves
+ * 0x7fffffff as the index, and sample_action would be gathered from there.  The caller keeps NaN out; +-inf scores are ordered. */
 int m3pc_select(m3pc_handle* h, const float* expect_return, const float* a0, long long a0_stride, int n,
                 float temperature, const float* expo, float* p, float* eval_action, int* argmax,
                 int* sample_idx, float* sample_action, void* stream);

@@ -6,7 +6,8 @@
  * Users: tests/test_gemm_kernels_gpu.py, tests/test_gemm_edges_gpu.py, tests/test_bf16x3_gpu.py, tests/test_attention_gpu.py,
  * tests/test_block_fused_gpu.py, tests/test_block_edges_gpu.py, tests/test_block_ref_cpu.py, tests/test_lockstep_kernels_gpu.py,
  * tests/test_block_shared_xb_gpu.py, tests/test_block_shared_xb_cpu.py, tests/test_embed_shared_xb_gpu.py,
- * tests/test_elementwise_edges_gpu.py, tests/test_elementwise_ref_cpu.py, tools/*.py.
+ * tests/test_elementwise_edges_gpu.py, tests/test_elementwise_ref_cpu.py, tests/test_select_edges_gpu.py, tests/test_select_ref_cpu.py,
+ * tools/*.py.
  */
 #ifndef M3PC_HIP_DEBUG_H
 #define M3PC_HIP_DEBUG_H
@@ -91,8 +92,75 @@ int m3pc_debug_gemm_group(const m3pc_debug_gemm_args* a, int n);
 /* clock probes of the last probed GEMM workgroup: {shader clocks, 100-MHz ticks} / gemm_big phase timers */
 int m3pc_debug_clock(long long* out2);
 int m3pc_debug_clock_big(long long* out4);
-/* the top-k kernels on their own: indices of the k largest of v (n), descending, ties to the lower index */
+/* the top-k kernels on their own, through launch_topk's dispatch: indices of the k largest of v (n), descending, ties to the lower
+ * index.  Refused with M3PC_EINVAL before anything is launched: a null v / idx_out, n outside [1, 16384], k outside [1, n]. */
 int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream);
+/* ---- the selection and certificate kernels of csrc/select.hip, one by one (tests/test_select_edges_gpu.py reaches every id of this
+ * list; tests/select_ref.py holds the references).  Every launcher of select.hip records the id of the kernel it launches:
+ * Selection kernel ids:
+ *   1 select_kernel;  2 select_batch_kernel;  3 topk_kernel;  4 topk_batch_kernel;  5 topk_select_kernel;
+ *   6 topk_select_batch_kernel;  7 topk_rank_blocks_kernel;  8 topk_rank_blocks_batch_kernel;  9 topk_rank_blocks2_kernel;
+ *   10 topk_rank_blocks2_dyn_kernel;  11 topk_rank_batch_kernel;  12 topk_rank_kernel;  13 window_stats_kernel;
+ *   14 rescore_merge_kernel;  15 merge_select_kernel;  16 merge_select_batch_kernel;  17 deviation_stats_kernel;
+ *   18 eval_bound_kernel;  19 eval_bound_batch_kernel;  20 scatter_kernel;  21 gather_listed_kernel;  22 variates_kernel;
+ *   23 variates_batch_kernel
+ * (end of the selection kernel ids)
+ * Reached through: m3pc_select (1), m3pc_debug_select_batch (2), m3pc_debug_topk_ex (3 .. 10, 12), m3pc_debug_topk_race_batch (11),
+ * m3pc_debug_window_stats (13), m3pc_rescore_merge / m3pc_rescore_merge_race (14), m3pc_merge_race_select (15),
+ * m3pc_debug_merge_select_batch (16), m3pc_debug_calibrate_stats (17), m3pc_eval_bound (18), m3pc_debug_eval_bound_batch (19),
+ * m3pc_debug_scatter (20), m3pc_debug_gather_listed (21), m3pc_draw_variates (22), m3pc_debug_variates_batch (23).
+ * The id of the select.hip kernel the calling thread launched last (0: none), for the entry points without a `picked` argument: */
+int m3pc_debug_select_picked(void);
+/* the set of ids launched by the calling thread since the set was last cleared, bit `id` for kernel id (m3pc_topk_window launches
+ * two kernels); clear != 0 empties the set and the last id */
+unsigned int m3pc_debug_select_picked_set(int clear);
+/* one top-k of n_windows rows of v (n_windows, n): the ranks r < k, descending value, ties to the lower index, -0.0 equal to +0.0;
+ * the element of rank r goes to out[r * out_stride] (window w: out + w k).
+ *   variant 0, no expo: launch_topk (one window) or launch_topk_batch.  out_stride 1.
+ *   variants 1 .. 4: topk_rank_kernel, topk_rank_blocks_kernel, topk_select_kernel, topk_kernel forced, one window, where that kernel
+ *     is legal: n <= 2048;  n <= 2048;  k <= 64 and n <= 16384;  n <= 16384.  With expo (variant 3 only) the value ranked is the race
+ *     key tau v - log expo; out_stride -1 (variant 3 only) writes rank r to out[-r].
+ *   variant 0 with expo: launch_topk_race, one window.  `out` is the list at position rmax: out[-1 - i] = the i-th best by race key,
+ *     i < k <= 64 (out_stride must be -1), out[i] = the i-th best by value, i < kk <= min(1024, n); scores_out (optional, same layout)
+ *     = v[winner].
+ *   variant 5: the same call through launch_topk_race's branch for a device that refuses the LDS opt-in -- launch_topk for the
+ *     values, topk_select_kernel for the race keys -- taken without asking the device to refuse anything.  No scores_out.
+ *   variant 6: launch_topk_batch for every n_windows, one window included (variant 0 sends one window to launch_topk).
+ * Refused with M3PC_EINVAL before anything is launched: a null v / out, n outside [1, 16384], k outside [1, n], n_windows outside
+ * [1, 65535], an out_stride other than 1 / -1, a variant outside [0, 6], a forced kernel outside its shapes (above) or with several
+ * windows, k > 64 on the selection kernel, expo / out_stride -1 / scores_out / kk where the variant has no use for it, kk outside
+ * [1, min(1024, n)] where it has.
+ * picked (2 ints, optional): [0] the kernel launched last, [1] the kernel that ranked the values when two lists were made (variant 0
+ * with expo: the one kernel; variant 5: launch_topk's), else 0. */
+typedef struct m3pc_debug_topk_args {
+    const float* v;
+    const float* expo; /* optional */
+    float tau;
+    int n_windows, n, k;
+    int* out;
+    int out_stride;
+    float* scores_out; /* optional */
+    int kk;            /* with expo and variant 0 / 5, else 0 */
+    int variant;
+    int* picked; /* optional: 2 ints */
+    void* stream;
+} m3pc_debug_topk_args;
+int m3pc_debug_topk_ex(const m3pc_debug_topk_args* a);
+/* window_stats_kernel through launch_window_stats: idx = the kk best entries of v (n_total), best first; stats (device, 4 floats) =
+ * {n = min(clamp(cnt, kmin, kmax), kk), v[idx[0]] - v[idx[n]] (infinity when n == kk), v[idx[0]], cnt = #{i: v[i] >= v[idx[0]] -
+ * window}}; host_stats (optional): 5 floats a kernel can store to, closed by seq in slot 4; top_scores (optional): top_scores[i] =
+ * v[idx[i]] for i in [-rr, kk) -- rr race entries in front of idx.  Refused: a null v / idx / stats, n_total outside [1, 16384], kk
+ * outside [1, n_total], kmin outside [1, kmax], rr outside [0, 64], a window that is not >= 0. */
+int m3pc_debug_window_stats(const float* v, int n_total, const int* idx, int kk, int kmin, int kmax, float window, float* stats,
+                            float* host_stats, float seq, float* top_scores, int rr, void* stream);
+/* scatter_kernel through launch_scatter: dst[index[i]] = src[i], index_copy[i] = index[i] (optional), i < n.  Refused: a null src /
+ * index / dst, n < 1.  The caller keeps the entries of index (device memory) inside dst. */
+int m3pc_debug_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, void* stream);
+/* variates_batch_kernel through launch_variates_batch (the normals of m3pc_refine_plans): out (n_windows, g1 - g0), window w = the
+ * elements [g0, g1) of the standard-normal array of (seed, steps[w]) -- m3pc_draw_variates' eps for that step, flat.  steps is a HOST
+ * array.  Refused: a null steps / out, n_windows outside [1, 65535], g0 < 0, g1 <= g0, g1 > 2^33. */
+int m3pc_debug_variates_batch(unsigned long long seed, const unsigned long long* steps, int n_windows, long long g0, long long g1,
+                              float* out, void* stream);
 /* the statistics kernel of m3pc_calibrate_delta on caller vectors: stats (device, 8 floats) = {lower median c of scores_low - f32,
  * max |scores_low - f32 - c|, max |f32|, 0 ...}; *delta_out (host) = max(factor * stats[1], 1e-6 * stats[2], 1e-30).  n <= 16384.
  * Synchronises the stream. */

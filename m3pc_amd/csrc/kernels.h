@@ -481,6 +481,23 @@ struct SelectP {
     int* sample_idx;
     float* sample_action;  // (A,) = a0[sample_idx]
 };
+// lab build: the id of the select.hip kernel the calling thread launched last, and the set of ids launched since the set was last
+// cleared (bit id; an entry point such as m3pc_topk_window launches two kernels) -- the list is in include/m3pc_hip_debug.h,
+// "Selection kernel ids"; the product build records nothing.  g_sel_force_fallback makes launch_topk_race take the branch of a
+// refused LDS opt-in (m3pc_debug_topk_ex, variant 5); in the product it is the constant false.
+#ifdef M3PC_LAB
+extern thread_local int g_sel_picked;
+extern thread_local unsigned int g_sel_picked_set;
+extern thread_local bool g_sel_force_fallback;
+#define M3PC_SEL_PICK(id) (::m3pc::g_sel_picked = (id), ::m3pc::g_sel_picked_set |= 1u << (id))
+#define M3PC_SEL_FORCE_FALLBACK (::m3pc::g_sel_force_fallback)
+// one top-k launch with the kernel forced (m3pc_debug_topk_ex, variants 1..4: topk_rank_kernel, topk_rank_blocks_kernel,
+// topk_select_kernel, topk_kernel); the caller has checked that the kernel is legal for the shape.  expo / out_stride -1: variant 3 only
+void launch_topk_forced(int variant, const float* v, const float* expo, float tau, int n, int k, int* out, int out_stride, hipStream_t st);
+#else
+#define M3PC_SEL_PICK(id) ((void)0)
+#define M3PC_SEL_FORCE_FALLBACK false
+#endif
 void launch_select(const SelectP& p, hipStream_t st);
 // launch_select for E windows in one launch (workgroup = window, select_body): p describes window 0; window w reads er / expo and
 // writes p at + w row_stride, reads a0 at + w a0_wstride, writes eval_action / sample_action at + w A, argmax / sample_idx at + w

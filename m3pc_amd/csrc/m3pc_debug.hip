@@ -224,7 +224,7 @@ int m3pc_debug_clock(long long* out2) {
     return 0;
 }
 
-// Not part of the public header (tests/test_gemm_kernels_gpu.py): the top-k kernels on their own.
+// Not part of the public header (tests/test_select_edges_gpu.py): the top-k kernels on their own.
 // the statistics kernel of m3pc_calibrate_delta on caller vectors (tests/test_certified_step_gpu.py): stats = {lower median of
 // scores_low - f32, largest deviation from it, largest |f32|, 0 ...} on the device, *delta_out as m3pc_calibrate_delta forms it
 int m3pc_debug_calibrate_stats(const float* scores_low, const float* f32, int n, float factor, float* stats, float* delta_out,
@@ -238,9 +238,109 @@ int m3pc_debug_calibrate_stats(const float* scores_low, const float* f32, int n,
     *delta_out = cert_delta(factor, s8[1], s8[2]);
     return 0;
 }
+// what no top-k kernel may be given: the bitonic kernel's LDS holds 16384 keys, the selection kernel's registers 16 values per thread,
+// and with k > n a rank >= n names no element
+static int debug_topk_check(const void* v, const void* out, int n, int k, const char* who) {
+    if (!v || !out) return fail(M3PC_EINVAL, "%s: null argument", who);
+    if (n < 1 || n > 16384) return fail(M3PC_EINVAL, "%s: n %d outside [1, 16384]", who, n);
+    if (k < 1 || k > n) return fail(M3PC_EINVAL, "%s: k %d outside [1, n = %d]", who, k, n);
+    return 0;
+}
 int m3pc_debug_topk(const float* v, int n, int k, int* idx_out, void* stream) {
+    CHK(debug_topk_check(v, idx_out, n, k, "debug_topk"));
     launch_topk(v, n, k, idx_out, (hipStream_t)stream);
     return check_launch("debug_topk");
+}
+int m3pc_debug_select_picked(void) { return g_sel_picked; }
+unsigned int m3pc_debug_select_picked_set(int clear) {
+    const unsigned int set = g_sel_picked_set;
+    if (clear) {
+        g_sel_picked_set = 0;
+        g_sel_picked = 0;
+    }
+    return set;
+}
+// Every top-k kernel of select.hip on caller arrays (tests/test_select_edges_gpu.py): the dispatch or a forced kernel, a score or a
+// race source.  Nothing is launched before the arguments are known to be inside what the kernel launched can read and write.
+int m3pc_debug_topk_ex(const m3pc_debug_topk_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_topk_ex: null argument");
+    CHK(debug_topk_check(a->v, a->out, a->n, a->k, "debug_topk_ex"));
+    if (a->n_windows < 1 || a->n_windows > 65535) return fail(M3PC_EINVAL, "debug_topk_ex: n_windows %d outside [1, 65535]", a->n_windows);
+    if (a->out_stride != 1 && a->out_stride != -1) return fail(M3PC_EINVAL, "debug_topk_ex: out_stride %d is neither 1 nor -1", a->out_stride);
+    const int v = a->variant;
+    if (v < 0 || v > 6) return fail(M3PC_EINVAL, "debug_topk_ex: variant %d outside [0, 6]", v);
+    const bool race_pair = a->expo && (v == 0 || v == 5);  // launch_topk_race: a score list and a race list
+    if (v == 5 && !a->expo) return fail(M3PC_EINVAL, "debug_topk_ex: variant 5 ranks a race source");
+    if (v != 0 && v != 6 && a->n_windows != 1) return fail(M3PC_EINVAL, "debug_topk_ex: a forced kernel ranks one window");
+    if (race_pair) {
+        if (a->n_windows != 1) return fail(M3PC_EINVAL, "debug_topk_ex: the race lists of several windows are m3pc_debug_topk_race_batch's");
+        if (a->out_stride != -1) return fail(M3PC_EINVAL, "debug_topk_ex: the race list runs backwards (out_stride -1)");
+        if (a->k > 64) return fail(M3PC_EINVAL, "debug_topk_ex: %d racers, the selection kernel lists 64", a->k);
+        if (a->kk < 1 || a->kk > 1024 || a->kk > a->n) return fail(M3PC_EINVAL, "debug_topk_ex: kk %d outside [1, min(1024, n = %d)]", a->kk, a->n);
+        if (v == 5 && a->scores_out) return fail(M3PC_EINVAL, "debug_topk_ex: the selection kernels write no scores");
+    } else {
+        if (a->kk != 0) return fail(M3PC_EINVAL, "debug_topk_ex: kk belongs to the race dispatch (expo with variant 0 or 5)");
+        if (a->scores_out) return fail(M3PC_EINVAL, "debug_topk_ex: scores_out belongs to the race dispatch (expo with variant 0)");
+        if (a->expo && v != 3) return fail(M3PC_EINVAL, "debug_topk_ex: of these kernels only the forced selection kernel ranks a race source");
+        if (a->out_stride != 1 && v != 3) return fail(M3PC_EINVAL, "debug_topk_ex: only the selection kernel writes backwards");
+        if ((v == 1 || v == 2) && a->n > 2048) return fail(M3PC_EINVAL, "debug_topk_ex: the ranking kernels hold 2048 keys, n = %d", a->n);
+        if (v == 3 && a->k > 64) return fail(M3PC_EINVAL, "debug_topk_ex: the selection kernel lists 64, k = %d", a->k);
+    }
+    hipStream_t st = (hipStream_t)a->stream;
+    g_sel_picked = 0;
+    int first = 0;
+    if (race_pair) {
+        // out = the list at position rmax = k: out[-1 - i] the i-th racer, out[i] the i-th best score, scores_out alike
+        g_sel_force_fallback = v == 5;
+        const unsigned int before = g_sel_picked_set;
+        g_sel_picked_set = 0;
+        (void)launch_topk_race(a->v, a->expo, a->tau, a->n, a->kk, a->k, 0, a->out, a->scores_out, st);
+        g_sel_force_fallback = false;
+        for (int id = 1; id < 32; ++id)  // (the fallback launches two kernels: the score list's comes first)
+            if ((g_sel_picked_set >> id & 1u) && id != g_sel_picked) first = id;
+        if (!first) first = g_sel_picked;  // (one kernel ranked both lists, or the selection kernel ranked each)
+        g_sel_picked_set |= before;
+    } else if (v == 0 || v == 6) {
+        if (v == 0 && a->n_windows == 1) launch_topk(a->v, a->n, a->k, a->out, st);
+        else launch_topk_batch(a->v, a->n_windows, a->n, a->k, a->out, st);
+    } else {
+        launch_topk_forced(v, a->v, a->expo, a->tau, a->n, a->k, a->out, a->out_stride, st);
+    }
+    if (a->picked) {
+        a->picked[0] = g_sel_picked;
+        a->picked[1] = first;
+    }
+    return check_launch("debug_topk_ex");
+}
+int m3pc_debug_window_stats(const float* v, int n_total, const int* idx, int kk, int kmin, int kmax, float window, float* stats,
+                            float* host_stats, float seq, float* top_scores, int rr, void* stream) {
+    if (!v || !idx || !stats) return fail(M3PC_EINVAL, "debug_window_stats: null argument");
+    if (n_total < 1 || n_total > 16384) return fail(M3PC_EINVAL, "debug_window_stats: n_total %d outside [1, 16384]", n_total);
+    if (kk < 1 || kk > n_total) return fail(M3PC_EINVAL, "debug_window_stats: kk %d outside [1, n_total = %d]", kk, n_total);
+    if (kmin < 1 || kmin > kmax) return fail(M3PC_EINVAL, "debug_window_stats: kmin %d outside [1, kmax = %d]", kmin, kmax);
+    if (rr < 0 || rr > 64) return fail(M3PC_EINVAL, "debug_window_stats: rr %d outside [0, 64]", rr);
+    if (!(window >= 0.f)) return fail(M3PC_EINVAL, "debug_window_stats: window must be >= 0");
+    g_sel_picked = 0;
+    launch_window_stats(v, n_total, idx, kk, kmin, kmax, window, stats, host_stats, seq, top_scores, (hipStream_t)stream, rr);
+    return check_launch("debug_window_stats");
+}
+// launch_variates_batch (m3pc_refine_plans' normals) on a caller buffer: window w gets the elements [g0, g1) of the (seed, steps[w])
+// normal array, what m3pc_draw_variates gives for that step
+int m3pc_debug_variates_batch(unsigned long long seed, const unsigned long long* steps, int n_windows, long long g0, long long g1,
+                              float* out, void* stream) {
+    if (!steps || !out) return fail(M3PC_EINVAL, "debug_variates_batch: null argument");
+    if (n_windows < 1 || n_windows > 65535) return fail(M3PC_EINVAL, "debug_variates_batch: n_windows %d outside [1, 65535]", n_windows);
+    if (g0 < 0 || g1 <= g0 || g1 > (1LL << 33)) return fail(M3PC_EINVAL, "debug_variates_batch: [g0, g1) outside the generator's range");
+    g_sel_picked = 0;
+    launch_variates_batch(seed, steps, n_windows, g0, g1, out, (hipStream_t)stream);
+    return check_launch("debug_variates_batch");
+}
+int m3pc_debug_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, void* stream) {
+    if (!src || !index || !dst) return fail(M3PC_EINVAL, "debug_scatter: null argument");
+    if (n < 1) return fail(M3PC_EINVAL, "debug_scatter: n %d < 1", n);
+    g_sel_picked = 0;
+    launch_scatter(src, index, n, dst, index_copy, (hipStream_t)stream);
+    return check_launch("debug_scatter");
 }
 
 // Not part of the public header (tests/test_lockstep_kernels_gpu.py): the three kernels of a lock-step batch's tail, each alone on

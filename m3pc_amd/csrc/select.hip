@@ -10,6 +10,12 @@
 
 namespace m3pc {
 
+#ifdef M3PC_LAB
+thread_local int g_sel_picked = 0;
+thread_local unsigned int g_sel_picked_set = 0;
+thread_local bool g_sel_force_fallback = false;
+#endif
+
 __device__ __forceinline__ float wsum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -95,6 +101,7 @@ __global__ __launch_bounds__(1024) void select_kernel(SelectP p) {
 }
 void launch_select(const SelectP& p, hipStream_t st) {
     if (p.n <= 0) return;
+    M3PC_SEL_PICK(1);
     hipLaunchKernelGGL(select_kernel, dim3(1), dim3(1024), 0, st, p);
 }
 // select_kernel for E lock-step windows (the fp32 form of m3pc_plan_steps_certified): workgroup w is window w on its rows of the
@@ -115,6 +122,7 @@ __global__ __launch_bounds__(1024) void select_batch_kernel(SelectP p, long long
 }
 void launch_select_batch(const SelectP& p, int E, long long row_stride, long long a0_wstride, hipStream_t st) {
     if (p.n <= 0 || E <= 0) return;
+    M3PC_SEL_PICK(2);
     hipLaunchKernelGGL(select_batch_kernel, dim3((unsigned)E), dim3(1024), 0, st, p, row_stride, a0_wstride);
 }
 
@@ -178,19 +186,24 @@ __global__ __launch_bounds__(1024) void topk_batch_kernel(const float* v, int n,
 // values with k rounds of (register-local arg-max, 64-lane butterfly) -- no barrier --, then wave 0 does the same over
 // the 16 k survivors.  Same order as the bitonic kernel (descending value, ties to the lower index); ~3x faster
 // at n = 1024 and independent of n up to 16384 (the replicated top-k of an 8-GPU run sorts 8192 scores).
+// A winner leaves the race by its INDEX (0x7fffffff: the index `better` never prefers), not only by its value: a real score of
+// -inf stays a candidate until it has been taken, and is then taken once -- k > #(scores above -inf) lists distinct elements, in
+// index order, as the ranking kernels do.
 __device__ __forceinline__ void topk_select_body(const TopSrc& src, int n, float* cv, int* ci) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int k = src.k;
     float val[16];
+    int idx[16];
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
         const int e = s * 1024 + tid;
         val[s] = e < n ? src_value(src, e) : -INFINITY;
+        idx[s] = e < n ? e : 0x7fffffff;
     }
     for (int r = 0; r < k; ++r) {
         ArgMax a{-INFINITY, 0x7fffffff};
 #pragma unroll
-        for (int s = 0; s < 16; ++s) a = better(a, ArgMax{val[s], s * 1024 + tid});
+        for (int s = 0; s < 16; ++s) a = better(a, ArgMax{val[s], idx[s]});
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) a = better(a, ArgMax{__shfl_xor(a.v, o), __shfl_xor(a.i, o)});
         if (lane == 0) {
@@ -199,7 +212,10 @@ __device__ __forceinline__ void topk_select_body(const TopSrc& src, int n, float
         }
 #pragma unroll
         for (int s = 0; s < 16; ++s)
-            if (s * 1024 + tid == a.i) val[s] = -INFINITY;
+            if (idx[s] == a.i) {
+                val[s] = -INFINITY;
+                idx[s] = 0x7fffffff;
+            }
     }
     __syncthreads();
     if (wid != 0) return;
@@ -220,7 +236,10 @@ __device__ __forceinline__ void topk_select_body(const TopSrc& src, int n, float
         if (lane == 0) src.out[r * src.out_stride] = a.i;
 #pragma unroll
         for (int j = 0; j < 16; ++j)
-            if (mi[j] == a.i) mv[j] = -INFINITY;
+            if (mi[j] == a.i) {
+                mv[j] = -INFINITY;
+                mi[j] = 0x7fffffff;
+            }
     }
 }
 __global__ __launch_bounds__(1024) void topk_select_kernel(TopSrc src, int n) {
@@ -394,11 +413,13 @@ void launch_topk(const float* v, int n, int k, int* idx_out, hipStream_t st) {
     if (n <= 0 || k <= 0) return;
     if (n <= 2048 && k <= n) {
         static const bool one_block = M3PC_ENV("M3PC_TOPK_ONE_BLOCK") != nullptr;  // A/B switch
+        M3PC_SEL_PICK(one_block ? 12 : 7);
         if (one_block) hipLaunchKernelGGL(topk_rank_kernel, dim3(1), dim3(1024), 0, st, v, n, k, idx_out);
         else hipLaunchKernelGGL(topk_rank_blocks_kernel, dim3((n + 63) / 64), dim3(256), 0, st, v, n, k, idx_out);
         return;
     }
     if (k <= 64 && n <= 16384) {
+        M3PC_SEL_PICK(5);
         hipLaunchKernelGGL(topk_select_kernel, dim3(1), dim3(1024), 0, st, TopSrc{v, nullptr, 0.f, k, idx_out, 1, nullptr}, n);
         return;
     }
@@ -411,20 +432,44 @@ void launch_topk(const float* v, int n, int k, int* idx_out, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
         attr[dev] = true;
     }
+    M3PC_SEL_PICK(3);
     hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), (size_t)np * 8, st, v, n, np, k, idx_out);
 }
+
+#ifdef M3PC_LAB
+void launch_topk_forced(int variant, const float* v, const float* expo, float tau, int n, int k, int* out, int out_stride, hipStream_t st) {
+    if (variant == 1) {
+        M3PC_SEL_PICK(12);
+        hipLaunchKernelGGL(topk_rank_kernel, dim3(1), dim3(1024), 0, st, v, n, k, out);
+    } else if (variant == 2) {
+        M3PC_SEL_PICK(7);
+        hipLaunchKernelGGL(topk_rank_blocks_kernel, dim3((n + 63) / 64), dim3(256), 0, st, v, n, k, out);
+    } else if (variant == 3) {
+        M3PC_SEL_PICK(5);
+        hipLaunchKernelGGL(topk_select_kernel, dim3(1), dim3(1024), 0, st, TopSrc{v, expo, tau, k, out, out_stride, nullptr}, n);
+    } else if (variant == 4) {
+        int np = 2;
+        while (np < n) np <<= 1;
+        (void)hipFuncSetAttribute((const void*)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
+        M3PC_SEL_PICK(3);
+        hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), (size_t)np * 8, st, v, n, np, k, out);
+    }
+}
+#endif
 
 // launch_topk for E rows at once (m3pc_refine_plans): the same three regimes with the row as a grid index, so list w is
 // launch_topk's of row w (the keys are integers: the order does not depend on who compares them).  No environment switch.
 void launch_topk_batch(const float* v, int E, int n, int k, int* idx_out, hipStream_t st) {
     if (E <= 0 || n <= 0 || k <= 0) return;
     if (n <= 2048 && k <= n) {
+        M3PC_SEL_PICK(8);
         for (int w0 = 0; w0 < E; w0 += 32768)
             hipLaunchKernelGGL(topk_rank_blocks_batch_kernel, dim3((n + 63) / 64, E - w0 < 32768 ? E - w0 : 32768), dim3(256), 0, st,
                                v + (size_t)w0 * n, n, k, idx_out + (size_t)w0 * k);
         return;
     }
     if (k <= 64 && n <= 16384) {
+        M3PC_SEL_PICK(6);
         hipLaunchKernelGGL(topk_select_batch_kernel, dim3(E), dim3(1024), 0, st, TopSrc{v, nullptr, 0.f, k, idx_out, 1, nullptr}, n);
         return;
     }
@@ -437,6 +482,7 @@ void launch_topk_batch(const float* v, int E, int n, int k, int* idx_out, hipStr
         (void)hipFuncSetAttribute((const void*)topk_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8);
         attr[dev] = true;
     }
+    M3PC_SEL_PICK(4);
     hipLaunchKernelGGL(topk_batch_kernel, dim3(E), dim3(1024), (size_t)np * 8, st, v, n, np, k, idx_out);
 }
 
@@ -463,11 +509,12 @@ bool launch_topk_race(const float* v, const float* expo, float tau, int n, int k
     const bool one = n <= 16384;  // rank by counting: every element knows its value and its rank -- the scores go out with the ids
     const TopSrc s0{v, nullptr, 0.f, kk, list + rmax, 1, one && list_scores ? list_scores + rmax : nullptr};
     const TopSrc s1{v, expo, tau, rr, list + rmax - 1, -1, one && list_scores ? list_scores + rmax - 1 : nullptr};
-    if (n <= 2048) {
+    if (n <= 2048 && !M3PC_SEL_FORCE_FALLBACK) {
+        M3PC_SEL_PICK(9);
         hipLaunchKernelGGL(topk_rank_blocks2_kernel, dim3((n + 63) / 64, rr > 0 ? 2 : 1), dim3(256), 0, st, s0, s1, n);
         return true;  // (list_scores written)
     }
-    if (one) {  // n <= 16384: the keys in dynamic LDS
+    if (one && !M3PC_SEL_FORCE_FALLBACK) {  // n <= 16384: the keys in dynamic LDS
         const int n4 = (((n + 3) / 4) + 1) & ~1;
         const size_t lds = (size_t)4 * n4 * sizeof(unsigned long long);
         // > 64 KiB of dynamic LDS is a per-device opt-in, asked for ONCE per device and only when the launch needs it (n > 8192);
@@ -476,6 +523,7 @@ bool launch_topk_race(const float* v, const float* expo, float tau, int n, int k
         static std::atomic<int> state[64] = {};
         const bool fits = rank_lds_fits((const void*)topk_rank_blocks2_dyn_kernel, state, lds);
         if (fits) {
+            M3PC_SEL_PICK(10);
             hipLaunchKernelGGL(topk_rank_blocks2_dyn_kernel, dim3((n + 63) / 64, rr > 0 ? 2 : 1), dim3(256), lds, st, s0, s1, n, n4);
             return true;
         }
@@ -483,7 +531,10 @@ bool launch_topk_race(const float* v, const float* expo, float tau, int n, int k
     // (the opt-in was refused: the selection kernels, no scores)
     const TopSrc t1{v, expo, tau, rr, list + rmax - 1, -1, nullptr};
     launch_topk(v, n, kk, list + rmax, st);
-    if (rr > 0) hipLaunchKernelGGL(topk_select_kernel, dim3(1), dim3(1024), 0, st, t1, n);  // (rr <= 64, n <= 16384)
+    if (rr > 0) {
+        M3PC_SEL_PICK(5);
+        hipLaunchKernelGGL(topk_select_kernel, dim3(1), dim3(1024), 0, st, t1, n);  // (rr <= 64, n <= 16384)
+    }
     return false;     // (the caller still has to gather list_scores: launch_window_stats)
 }
 
@@ -500,6 +551,7 @@ bool launch_topk_race_batch(const float* v, const float* expo, float tau, int E,
     const size_t lds = (size_t)4 * n4 * sizeof(unsigned long long);
     static std::atomic<int> state[64] = {};
     if (!rank_lds_fits((const void*)topk_rank_batch_kernel, state, lds)) return false;
+    M3PC_SEL_PICK(11);
     hipLaunchKernelGGL(topk_rank_batch_kernel, dim3((n + 63) / 64, rr > 0 ? 2 : 1, E), dim3(256), lds, st, s0, s1, n, n4, v_stride,
                        list_stride);
     return true;
@@ -546,6 +598,7 @@ __global__ __launch_bounds__(256) void window_stats_kernel(const float* v, int n
 }
 void launch_window_stats(const float* v, int n_total, const int* idx, int kk, int kmin, int kmax, float window, float* stats,
                          float* host_stats, float seq, float* top_scores, hipStream_t st, int rr) {
+    M3PC_SEL_PICK(13);
     hipLaunchKernelGGL(window_stats_kernel, dim3(1), dim3(256), 0, st, v, n_total, idx, kk, kmin, kmax, window, stats, host_stats, seq,
                        top_scores, rr);
 }
@@ -676,12 +729,14 @@ __global__ __launch_bounds__(1024) void merge_select_kernel(const float* b, int 
 void launch_rescore_merge(const float* b, int n_total, const int* list, int r, int n, const float* list_scores, const float* f,
                           float delta, const float* expo, float tau, float* out, float* stats, float* host_stats, float seq,
                           hipStream_t st) {
+    M3PC_SEL_PICK(14);
     hipLaunchKernelGGL(rescore_merge_kernel, dim3(1), dim3(1024), 0, st, b, n_total, list, r, n, list_scores, f, delta, expo, tau, out,
                        stats, host_stats, seq, expo ? 8 : 4);
 }
 void launch_merge_select(const float* b, int n_total, const int* list, int r, int n, const float* list_scores, const float* f,
                          float delta, const float* expo, float tau, float* out, float* stats, float* host_stats, float seq,
                          const SelectP& sp, hipStream_t st) {
+    M3PC_SEL_PICK(15);
     hipLaunchKernelGGL(merge_select_kernel, dim3(1), dim3(1024), 0, st, b, n_total, list, r, n, list_scores, f, delta, expo, tau, out,
                        stats, host_stats, seq, expo ? 8 : 4, sp);
 }
@@ -727,6 +782,7 @@ void launch_merge_select_batch(MergeSelectBatchP& P, int E, const int* r, const 
             P.n[i] = n[w0 + i];
             P.delta[i] = delta[w0 + i];
         }
+        M3PC_SEL_PICK(16);
         hipLaunchKernelGGL(merge_select_batch_kernel, dim3(e), dim3(1024), 0, st, P);
     }
 }
@@ -812,6 +868,7 @@ __global__ __launch_bounds__(1024) void deviation_stats_kernel(const float* b, c
 }
 void launch_deviation_stats(const float* b, const float* f, int n, float* stats, float* host_stats, float seq, hipStream_t st) {
     if (n <= 0 || n > 16384) return;
+    M3PC_SEL_PICK(17);
     hipLaunchKernelGGL(deviation_stats_kernel, dim3(1), dim3(1024), 0, st, b, f, n, stats, host_stats, seq);
 }
 
@@ -990,6 +1047,7 @@ __global__ __launch_bounds__(1024) void eval_bound_kernel(const float* m, int n_
 void launch_eval_bound(const float* m, int n_total, const int* list, int r, int n, int n_listed, const float* a0, long long a0_stride,
                        int A, float tau, float delta, float eval_tol, float* stats, float* host_stats, float seq, hipStream_t st) {
     if (n_total <= 0 || n_total > 16384 || r < 0 || n < 0 || n > n_listed || r + n_listed > 1024) return;
+    M3PC_SEL_PICK(18);
     hipLaunchKernelGGL(eval_bound_kernel, dim3(1), dim3(1024), 0, st, m, n_total, list, r, n, n_listed, a0, a0_stride, A, tau, delta,
                        eval_tol, stats, host_stats, seq);
 }
@@ -1021,6 +1079,7 @@ void launch_eval_bound_batch(EvalBoundBatchP& P, int E, const int* r, const int*
             P.n[i] = n[w0 + i];
             P.delta[i] = delta[w0 + i];
         }
+        M3PC_SEL_PICK(19);
         hipLaunchKernelGGL(eval_bound_batch_kernel, dim3(e), dim3(1024), 0, st, P);
     }
 }
@@ -1034,6 +1093,7 @@ __global__ void scatter_kernel(const float* src, const int* index, int n, float*
 }
 void launch_scatter(const float* src, const int* index, int n, float* dst, int* index_copy, hipStream_t st) {
     if (n <= 0) return;
+    M3PC_SEL_PICK(20);
     hipLaunchKernelGGL(scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, index, n, dst, index_copy);
 }
 
@@ -1053,6 +1113,7 @@ __global__ __launch_bounds__(64) void gather_listed_kernel(const float* sa, int 
 void launch_gather_listed(const float* sa, int E, int n_total, int row, const int* list, int list_stride, int lo, int m, float* cand,
                           int* window_index, hipStream_t st) {
     if (E <= 0 || m <= 0 || row <= 0) return;
+    M3PC_SEL_PICK(21);
     hipLaunchKernelGGL(gather_listed_kernel, dim3((unsigned)(E * m)), dim3(64), 0, st, sa, n_total, row, list, list_stride, lo, m, cand,
                        window_index);
 }
@@ -1119,6 +1180,7 @@ void launch_variates(unsigned long long seed, unsigned long long step, int array
     if (g1 <= g0 || !out) return;
     const long long blocks = (g1 + 3) / 4 - g0 / 4;
     const int vec_ok = g0 % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    M3PC_SEL_PICK(22);
     hipLaunchKernelGGL(variates_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, (uint32_t)seed, (uint32_t)(seed >> 32),
                        (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)array, g0, g1, out, vec_ok);
 }
@@ -1137,6 +1199,7 @@ void launch_variates_batch(unsigned long long seed, const unsigned long long* st
             sp.s0[i] = (uint32_t)steps[w0 + i];
             sp.s1[i] = (uint32_t)(steps[w0 + i] >> 32);
         }
+        M3PC_SEL_PICK(23);
         hipLaunchKernelGGL(variates_batch_kernel, dim3((unsigned)((blocks + 255) / 256), m), dim3(256), 0, st, (uint32_t)seed,
                            (uint32_t)(seed >> 32), sp, g0, g1, out + (size_t)w0 * len, vec_ok);
     }
