@@ -40,7 +40,7 @@ def _stale(target: str, deps) -> bool:
 
 def build_library(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, n) for n in ("kernels.h", "gemm_epilogue.h", "gemm_stage_asm.h", "m3pc_internal.h", "cert_resolve.h", "philox.h", "stage.h", "episodes.h", "iql.h", "exports.map")] + \
+    headers = [os.path.join(CSRC, n) for n in ("kernels.h", "device_util.h", "gemm_epilogue.h", "gemm_stage_asm.h", "m3pc_internal.h", "cert_resolve.h", "philox.h", "stage.h", "episodes.h", "iql.h", "exports.map")] + \
               [os.path.join(os.path.dirname(HERE), "include", n) for n in ("m3pc_hip.h", "m3pc_hip_debug.h")]
     objdir = os.path.join(CSRC, "build_lab" if lab else "build")
     os.makedirs(objdir, exist_ok=True)

@@ -13,16 +13,13 @@
 //
 // Arithmetic: operands are staged to LDS as fp32 (bf16 inputs are widened) and multiplied with
 // v_mfma_f32_32x32x2_f32; softmax in fp32.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace m3pc {
 
 #ifdef M3PC_LAB
 thread_local int g_attn_picked = 0;
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <typename T>
 __device__ __forceinline__ f32x4 load4(const T* p);

@@ -10,17 +10,12 @@
 //     no transposing stores.
 #include <cstdio>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace m3pc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 template <int HDT, int NCH>
 __global__ __launch_bounds__(256) void attn_bf16_kernel(AttnP p) {
@@ -424,7 +419,6 @@ __global__ __launch_bounds__(192, 2) void attn_bf16_pipe_kernel(AttnP p, int n_i
     constexpr int NDMA = NP_OWN + 2 * (NP_OWN + NP_SH);          // pieces per item (the loader's): Q, K, V
     static_assert(NDMA <= 63 && Lk <= APIPE_NR && (SH == 0 || (SH == 32 && N1 <= APIPE_NR - 32)), "shapes");
     extern __shared__ __attribute__((aligned(16))) char lds[];  // 2 * APIPE_BUF bytes (dynamic: two workgroups per CU must fit to the byte)
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0, 1: compute; 2: loader
     const int l31 = lane & 31, lh = lane >> 5;
@@ -667,7 +661,6 @@ __global__ __launch_bounds__(192, 1) void attn_bf16_pipe_dec_kernel(AttnP p, int
     constexpr int DBUF = 2 * APIPE_IMG;     // one buffer: V | K
     static_assert(NDMA <= 63 && Lk <= APIPE_NR, "shapes");
     extern __shared__ __attribute__((aligned(16))) char lds[];  // 4 * DBUF bytes: wave w's buffers at (2 w + r % 2) * DBUF
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0, 1: compute; 2: loader
     const int l31 = lane & 31, lh = lane >> 5;
@@ -732,7 +725,7 @@ __global__ __launch_bounds__(192, 1) void attn_bf16_pipe_dec_kernel(AttnP p, int
         for (int s = 0; s < NS; ++s) qf[s] = *(const u32x4*)(qrow + 16 * s);
     }
     float mp = -INFINITY, lp = 0.f;
-    f32x4v po[HDT][4];  // pre_O of this lane's query at the dims it owns: d * 32 + 8 q + 4 lh ..
+    f32x4 po[HDT][4];  // pre_O of this lane's query at the dims it owns: d * 32 + 8 q + 4 lh ..
     if (qi < p.Lq) {
         mp = p.pre_m[head * p.Lq + qi];
         lp = p.pre_l[head * p.Lq + qi];
@@ -742,7 +735,7 @@ __global__ __launch_bounds__(192, 1) void attn_bf16_pipe_dec_kernel(AttnP p, int
 #pragma unroll
         for (int d = 0; d < HDT; ++d)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) po[d][q] = *(const f32x4v*)(prow + d * 32 + 8 * q);
+            for (int q = 0; q < 4; ++q) po[d][q] = *(const f32x4*)(prow + d * 32 + 8 * q);
     }
     const unsigned ooff_base = qi < p.Lq ? 0u : 0x80000000u;
     (void)ooff_base;
@@ -887,7 +880,6 @@ __global__ __launch_bounds__(192, 1) void attn_bf16_pipe_mix_kernel(AttnP p, int
     constexpr int OBUF = 2 * APIPE_IMG + 1024;        // one item buffer: V own | K own | Q own (one piece)
     static_assert(NDMA <= 63 && N1 <= APIPE_NR && NKT <= 4 && N1 >= 32, "shapes");
     extern __shared__ __attribute__((aligned(16))) char lds[];  // 2 * SIMG + 4 * OBUF bytes
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
@@ -1142,7 +1134,6 @@ __global__ __launch_bounds__(((NQ1 + SHQ + 31) / 32 + 1) * 64, 1) void attn_bf16
     // (query rows 100..127 of the second buffer's Q image read up to byte 2 * WPIPE_BUF - WPIPE_IMG + 128 * 256 of the allocation)
     static_assert(2 * WPIPE_BUF - WPIPE_IMG + 128 * 256 <= WPIPE_LDS, "LDS");
     extern __shared__ __attribute__((aligned(16))) char lds[];  // WPIPE_LDS bytes
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0 .. NQT - 1: compute (query rows 32 wid ..); NQT: loader
     const int l31 = lane & 31, lh = lane >> 5;
@@ -1212,7 +1203,7 @@ __global__ __launch_bounds__(((NQ1 + SHQ + 31) / 32 + 1) * 64, 1) void attn_bf16
         for (int s = 0; s < NS; ++s) qf[s] = *(const u32x4*)(qrow + 16 * s);
     }
     float mp = -INFINITY, lp = 0.f;
-    f32x4v po[PRE ? HDT : 1][4];  // (PRE) pre_O of this lane's query at the dims it owns: d * 32 + 8 q + 4 lh ..
+    f32x4 po[PRE ? HDT : 1][4];  // (PRE) pre_O of this lane's query at the dims it owns: d * 32 + 8 q + 4 lh ..
     if constexpr (PRE) {
         if (qrow_i < p.Lq) {
             mp = p.pre_m[head * p.Lq + qrow_i];
@@ -1222,7 +1213,7 @@ __global__ __launch_bounds__(((NQ1 + SHQ + 31) / 32 + 1) * 64, 1) void attn_bf16
 #pragma unroll
         for (int d = 0; d < HDT; ++d)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) po[d][q] = *(const f32x4v*)(prow + d * 32 + 8 * q);
+            for (int q = 0; q < 4; ++q) po[d][q] = *(const f32x4*)(prow + d * 32 + 8 * q);
     }
     const int n_out = PRE ? p.Lq : Lq;  // output rows that exist
     for (int k = 0; k < n_mine; ++k) {

@@ -52,16 +52,9 @@
 #include <type_traits>
 
 #include "gemm_epilogue.h"
-#include "kernels.h"
 
 namespace m3pc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef void __attribute__((address_space(3))) * lptr_t;
 
 namespace {
 constexpr int BD = 512, BFF = 2048;              // model width / FFN width this kernel is built for
@@ -278,8 +271,7 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
     float* const tab = (float*)(smem + TAB_OFF);
     // this lane's view of the tables (+ 4 lh), opaque to the compiler: every table read is then ONE base register + an
     // immediate offset (left to itself it builds a separate address register per read and spills them between the passes)
-    typedef const float __attribute__((address_space(3))) * lds_cf32_t;  // (an LDS pointer: laundered as a generic one the reads become flat loads)
-    lds_cf32_t tabl = (lds_cf32_t)(tab + 4 * lh);
+    lds_cf32_t tabl = (lds_cf32_t)(tab + 4 * lh);  // (an LDS pointer: laundered as a generic one the reads become flat loads)
     asm volatile("" : "+v"(tabl));
 
     // ---- prologue: first stages in flight, parameter tables, accumulators = residual + out-proj bias
@@ -375,8 +367,7 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
     rdma(0);
     rdma(1);
     // this lane's read-back position of chunk 2 q + lh of its row l31: piece l31 >> 3, lane 8 (l31 & 7) + (chunk ^ (l31 & 7))
-    typedef const char __attribute__((address_space(3))) * lds_cc_t;  // (an LDS pointer: laundered as a generic one the reads become flat loads)
-    lds_cc_t rback = (lds_cc_t)(rstage + (l31 >> 3) * 1024 + (l31 & 7) * 128);
+    lds_cc_t rback = (lds_cc_t)(rstage + (l31 >> 3) * 1024 + (l31 & 7) * 128);  // (an LDS pointer: laundered as a generic one the reads become flat loads)
     asm volatile("" : "+v"(rback));
     f32x16 acc[NT];
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -443,7 +434,6 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
     // the accumulator -- so that they ride in the last MFMA slots of phase jn - 1 (round 6; in front of the phase they cost ~0.4 k of
     // its 1.75 k clocks with no MFMA in flight).  The residual of tile jn is in LDS by then: the stage sync of phase jn - 1 lets only
     // the 11 (7) youngest vector-memory operations stay in flight, and tile jn's pieces are older than those.
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     f32x4 ai_x[4], ai_b[4];
     u32x2 ai_v[4];
     (void)ai_x;
@@ -603,7 +593,6 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
         } else {
             gx[j] = DBG == 2 ? gx[j] : gx[j] * gq[j];
             if (j == 1) {
-                typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                 bf16x2 w;
                 w[0] = (bf16_t)gx[0];
                 w[1] = (bf16_t)gx[1];
@@ -734,7 +723,6 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
             if constexpr (XB) xoff[pp] = rr < p.M ? (unsigned)rr * (unsigned)(p.ldx * 2) + (unsigned)((cc ^ r8) << 4) : 0x80000000u;
             else xoff[pp] = rr < p.M ? (unsigned)(((SPLIT ? (size_t)blockIdx.y * p.M : 0) + (size_t)rr) * p.ldx * 4 + ((cc ^ r8) << 4)) : 0x80000000u;
         }
-        typedef char __attribute__((address_space(3))) * lds_c_t;
         lds_c_t xwr = (lds_c_t)(rstage + l31 * 128);
         lds_c_t xrd = (lds_c_t)(rstage + r8 * 128 + cc * 16);
         asm volatile("" : "+v"(xwr), "+v"(xrd));
@@ -752,7 +740,6 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
                 asm volatile("" : "+a"(acc[jn]));
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                     bf16x4 w;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) w[i] = (bf16_t)acc[jn][4 * q + i];
@@ -858,7 +845,6 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
                 srow[pp] = rr < p.M ? (unsigned)rr * (unsigned)(p.ldq * 2) + (unsigned)((cc ^ r8) * 16) : 0x80000000u;
             }
         }
-        typedef char __attribute__((address_space(3))) * lds_c_t;
         lds_c_t const swr = (lds_c_t)(rstage + l31 * 128 + lh * 8);                     // + buffer * 4096 + swizzled chunk * 16
         lds_c_t srd = (lds_c_t)(rstage + (lane >> 3) * 128 + (lane & 7) * 16);          // + buffer * 4096 + pp * 1024
         asm volatile("" : "+v"(srd));
@@ -870,9 +856,7 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
             for (int i = 0; i < 4; ++i) hh[4 * q + i] = bb[i];
         };
         auto stage_q = [&](const f32x16& hh, int t, int q) {  // quarter q of finished tile t -> bf16 -> staging
-            typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            bf16x4v w;
+            bf16x4 w;
 #pragma unroll
             for (int i = 0; i < 4; ++i) w[i] = (bf16_t)hh[4 * q + i];
             const int c = (t & 1) * 4 + q;
@@ -990,7 +974,6 @@ __global__ __launch_bounds__(256, 1) void block_fused_kernel(BlockP p) {
             R[0][k] = frag(0, k);
             R[1][k] = frag(0, 4 + k);
         }
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
         f32x2 hbb[2], hww[2];  // b1 / w2 of the two hidden units a group's gelu slice works on, by group parity
         float dot = 0.f;
         // units of tile tv, group g: registers e = 2 g, 2 g + 1 <-> features 32 tv + 8 (g >> 1) + 4 lh + 2 (g & 1) (+ 1)
@@ -1177,7 +1160,6 @@ __global__ __launch_bounds__(256, 1) void kv_fused_kernel(KvFusedP p) {
     const char* const lbase2 = smem + 2 * RS_B + lane16;
     auto frag = [&](int slot, int f) -> u32x4 { return *(const u32x4*)((slot == 2 ? lbase2 : lbase0 + slot * RS_B) + f * 1024); };
     float* const tab = (float*)(smem + KV_TAB_OFF);
-    typedef const float __attribute__((address_space(3))) * lds_cf32_t;
     lds_cf32_t tabl = (lds_cf32_t)(tab + 4 * lh);
     asm volatile("" : "+v"(tabl));
 
@@ -1227,7 +1209,6 @@ __global__ __launch_bounds__(256, 1) void kv_fused_kernel(KvFusedP p) {
     };
     rdma(0);
     rdma(1);
-    typedef const char __attribute__((address_space(3))) * lds_cc_t;
     lds_cc_t rback = (lds_cc_t)(rstage + (l31 >> 3) * 1024 + (l31 & 7) * 128);
     asm volatile("" : "+v"(rback));
     f32x16 acc[NT];
@@ -1377,7 +1358,6 @@ __global__ __launch_bounds__(256, 1) void kv_fused_kernel(KvFusedP p) {
             srow[pp] = rr < Mg ? (unsigned)(mr * p.ldkv * 2 + ((cc ^ r8) << 4)) : 0x80000000u;
         }
     }
-    typedef char __attribute__((address_space(3))) * lds_c_t;
     lds_c_t const swr = (lds_c_t)(rstage + l31 * 128 + lh * 8);
     lds_c_t srd = (lds_c_t)(rstage + (lane >> 3) * 128 + (lane & 7) * 16);
     asm volatile("" : "+v"(srd));
@@ -1389,9 +1369,7 @@ __global__ __launch_bounds__(256, 1) void kv_fused_kernel(KvFusedP p) {
         for (int i = 0; i < 4; ++i) hh[4 * q + i] = bb[i];
     };
     auto stage_q = [&](const f32x16& hh, int t, int q) {
-        typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        bf16x4v w;
+        bf16x4 w;
 #pragma unroll
         for (int i = 0; i < 4; ++i) w[i] = (bf16_t)hh[4 * q + i];
         const int c = (t & 1) * 4 + q;
@@ -1473,11 +1451,6 @@ __global__ __launch_bounds__(256) void block_split_reduce_kernel(SplitReduceP p)
     }
     if (!p.Hout) return;
     float v[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-    auto wave_sum = [](float t) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-        return t;
-    };
     auto ln = [&](const float* g, const float* b) {
         float s1 = 0.f;
 #pragma unroll

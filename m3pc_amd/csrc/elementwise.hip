@@ -2,29 +2,13 @@
 // output heads, candidate sampling, critic, TD(lambda) scoring and the cross-candidate select.
 // All of them are bandwidth- or latency-bound: one wave (64 lanes) per row, 64-lane shuffles for the
 // reductions, rows laid out so that lanes touch consecutive addresses.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace m3pc {
 
 #ifdef M3PC_LAB
 thread_local int g_ew_picked = 0;
 #endif
-
-__device__ __forceinline__ int map_row(const RowMap& m, int r) {
-    if (m.rpg == 0) return r;
-    return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------ embed
 __global__ __launch_bounds__(256) void embed_kernel(EmbedP p) {
@@ -175,13 +159,12 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(EmbedP p, int CB, int n
                 const long long xrow = p.x_compact ? block_res_row_xb((int)row, p.L, p.n_indep) : row;
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {
-                    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-                    bf16x4_t o;
+                    bf16x4 o;
                     o[0] = (bf16_t)x[i].x;
                     o[1] = (bf16_t)x[i].y;
                     o[2] = (bf16_t)x[i].z;
                     o[3] = (bf16_t)x[i].w;
-                    stream_store(o, (bf16x4_t*)(p.Xb + xrow * d + (i * 64 + lane) * 4));
+                    stream_store(o, (bf16x4*)(p.Xb + xrow * d + (i * 64 + lane) * 4));
                 }
             } else {
 #pragma unroll
@@ -205,13 +188,12 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(EmbedP p, int CB, int n
                 continue;
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
-                typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-                bf16x4_t o;
+                bf16x4 o;
                 o[0] = (bf16_t)y[i].x;
                 o[1] = (bf16_t)y[i].y;
                 o[2] = (bf16_t)y[i].z;
                 o[3] = (bf16_t)y[i].w;
-                stream_store(o, (bf16x4_t*)(dst + (i * 64 + lane) * 4));
+                stream_store(o, (bf16x4*)(dst + (i * 64 + lane) * 4));
             }
         }
     }
@@ -323,20 +305,18 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnP p) {
         }
 }
 // d % 256 == 0: 16-byte loads (lane owns 4 consecutive columns per 256-column slab), 8-byte bf16 stores
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void layernorm_vec_kernel(LnP p) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= p.rows) return;
     const float* x = p.X + (long long)map_row(p.xmap, r) * p.ldx;
     const int n = p.d >> 8;  // slabs of 256 columns (<= 4)
-    f32x4v v[4];
+    f32x4 v[4];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (i < n) {
-            v[i] = *(const f32x4v*)(x + i * 256 + lane * 4);
+            v[i] = *(const f32x4*)(x + i * 256 + lane * 4);
             s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
         }
     const float inv_d = 1.0f / (float)p.d;
@@ -355,8 +335,8 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(LnP p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (i < n) {
-            const f32x4v g = *(const f32x4v*)(p.g1 + i * 256 + lane * 4);
-            const f32x4v b = *(const f32x4v*)(p.b1 + i * 256 + lane * 4);
+            const f32x4 g = *(const f32x4*)(p.g1 + i * 256 + lane * 4);
+            const f32x4 b = *(const f32x4*)(p.b1 + i * 256 + lane * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * g[e] + b[e];
         }
@@ -380,8 +360,8 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(LnP p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (i < n) {
-                const f32x4v g = *(const f32x4v*)(p.g2 + i * 256 + lane * 4);
-                const f32x4v b = *(const f32x4v*)(p.b2 + i * 256 + lane * 4);
+                const f32x4 g = *(const f32x4*)(p.g2 + i * 256 + lane * 4);
+                const f32x4 b = *(const f32x4*)(p.b2 + i * 256 + lane * 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * g[e] + b[e];
             }
@@ -390,12 +370,12 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(LnP p) {
     for (int i = 0; i < 4; ++i)
         if (i < n) {
             const long long o = (long long)r * p.d + i * 256 + lane * 4;
-            if (p.Yf) *(f32x4v*)(p.Yf + o) = v[i];
+            if (p.Yf) *(f32x4*)(p.Yf + o) = v[i];
             if (p.Yb) {
-                bf16x4v w;
+                bf16x4 w;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) w[e] = (bf16_t)v[i][e];
-                *(bf16x4v*)(p.Yb + o) = w;
+                *(bf16x4*)(p.Yb + o) = w;
             }
         }
 }
@@ -407,19 +387,19 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnP p) {
     const int lane = threadIdx.x & 63;
     const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
     if (r0 >= p.rows) return;
-    f32x4v v[RPW][NV];
+    f32x4 v[RPW][NV];
 #pragma unroll
     for (int k = 0; k < RPW; ++k) {
         const int r = r0 + k < p.rows ? r0 + k : p.rows - 1;
         const float* x = p.X + (long long)map_row(p.xmap, r) * p.ldx;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) v[k][i] = *(const f32x4v*)(x + i * 256 + lane * 4);
+        for (int i = 0; i < NV; ++i) v[k][i] = *(const f32x4*)(x + i * 256 + lane * 4);
     }
-    f32x4v g[NV], b[NV];
+    f32x4 g[NV], b[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        g[i] = *(const f32x4v*)(p.g1 + i * 256 + lane * 4);
-        b[i] = *(const f32x4v*)(p.b1 + i * 256 + lane * 4);
+        g[i] = *(const f32x4*)(p.g1 + i * 256 + lane * 4);
+        b[i] = *(const f32x4*)(p.b1 + i * 256 + lane * 4);
     }
     const float inv_d = 1.0f / (float)p.d;
 #pragma unroll
@@ -457,8 +437,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnP p) {
             const float rstd2 = rsqrtf(wave_sum(q2) * inv_d + 1e-5f);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
-                const f32x4v gg = *(const f32x4v*)(p.g2 + i * 256 + lane * 4);
-                const f32x4v bb = *(const f32x4v*)(p.b2 + i * 256 + lane * 4);
+                const f32x4 gg = *(const f32x4*)(p.g2 + i * 256 + lane * 4);
+                const f32x4 bb = *(const f32x4*)(p.b2 + i * 256 + lane * 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[k][i][e] = (v[k][i][e] - mean2) * rstd2 * gg[e] + bb[e];
             }
@@ -467,13 +447,13 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnP p) {
             const long long o = (long long)(r0 + k) * p.d;
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
-                const f32x4v y = v[k][i];
-                if (p.Yf) *(f32x4v*)(p.Yf + o + i * 256 + lane * 4) = y;
+                const f32x4 y = v[k][i];
+                if (p.Yf) *(f32x4*)(p.Yf + o + i * 256 + lane * 4) = y;
                 if (p.Yb) {
-                    bf16x4v w;
+                    bf16x4 w;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) w[e] = (bf16_t)y[e];
-                    *(bf16x4v*)(p.Yb + o + i * 256 + lane * 4) = w;
+                    *(bf16x4*)(p.Yb + o + i * 256 + lane * 4) = w;
                 }
             }
         }
@@ -539,25 +519,22 @@ __global__ __launch_bounds__(256) void head_out_kernel(HeadOutP p) {
 // registers = features: bias and de-tokeniser apply per register, a lane stores its own row's values.  The W2 fragments sit in LDS
 // (2 x 32 KiB, built once per workgroup); workgroups are persistent over 128-row tiles.
 namespace {
-typedef float hf32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned hu32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 hbf16x8 __attribute__((ext_vector_type(8)));
 constexpr int HO_D = 512, HO_KS = HO_D / 16;
 }
 __global__ __launch_bounds__(256) void head_out_mfma_kernel(HeadOutP p, int n_tiles) {
-    __shared__ __attribute__((aligned(16))) hu32x4 wfrag[2][HO_KS][64];  // [hi | lo][k-step][lane]
+    __shared__ __attribute__((aligned(16))) u32x4 wfrag[2][HO_KS][64];  // [hi | lo][k-step][lane]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     for (int i = tid; i < HO_KS * 64; i += 256) {
         const int s = i >> 6, ln = i & 63, f = ln & 31, h = ln >> 5;
-        hbf16x8 hi, lo;
+        bf16x8 hi, lo;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float w = f < p.D ? p.W[(long long)f * HO_D + 16 * s + 8 * h + j] : 0.f;
             hi[j] = (bf16_t)w;
             lo[j] = (bf16_t)(w - (float)hi[j]);
         }
-        wfrag[0][s][ln] = __builtin_bit_cast(hu32x4, hi);
-        wfrag[1][s][ln] = __builtin_bit_cast(hu32x4, lo);
+        wfrag[0][s][ln] = __builtin_bit_cast(u32x4, hi);
+        wfrag[1][s][ln] = __builtin_bit_cast(u32x4, lo);
     }
     __syncthreads();
     // this lane's features: register e <-> feature (e & 3) + 8 (e >> 2) + 4 lh
@@ -574,19 +551,19 @@ __global__ __launch_bounds__(256) void head_out_mfma_kernel(HeadOutP p, int n_ti
         const int r = t * 128 + 32 * wv + l31;
         const int rl = r < p.rows ? r : p.rows - 1;
         const bf16_t* x = p.Xb + (long long)rl * p.ldx + 8 * lh;
-        hf32x16 acc;
+        f32x16 acc;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
         for (int c = 0; c < HO_KS; c += 8) {
-            hu32x4 b[8];
+            u32x4 b[8];
 #pragma unroll
-            for (int s = 0; s < 8; ++s) b[s] = *(const hu32x4*)(x + 16 * (c + s));
+            for (int s = 0; s < 8; ++s) b[s] = *(const u32x4*)(x + 16 * (c + s));
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                const hbf16x8 bv = __builtin_bit_cast(hbf16x8, b[s]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(hbf16x8, wfrag[1][c + s][lane]), bv, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(hbf16x8, wfrag[0][c + s][lane]), bv, acc, 0, 0, 0);
+                const bf16x8 bv = __builtin_bit_cast(bf16x8, b[s]);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wfrag[1][c + s][lane]), bv, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wfrag[0][c + s][lane]), bv, acc, 0, 0, 0);
             }
         }
         if (r < p.rows) {
@@ -628,12 +605,12 @@ __global__ __launch_bounds__(256) void actor_head_kernel(ActorP p) {
     if (r >= p.rows) return;
     const float* x = p.X + (long long)map_row(p.xmap, r) * p.ldx;
     const int n = p.d >> 8;  // slabs of 256 columns (<= 4)
-    f32x4v v[4];
+    f32x4 v[4];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (i < n) {
-            v[i] = *(const f32x4v*)(x + i * 256 + lane * 4);
+            v[i] = *(const f32x4*)(x + i * 256 + lane * 4);
             s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
         }
     if (p.ln_g) {
@@ -652,8 +629,8 @@ __global__ __launch_bounds__(256) void actor_head_kernel(ActorP p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (i < n) {
-                const f32x4v g = *(const f32x4v*)(p.ln_g + i * 256 + lane * 4);
-                const f32x4v b = *(const f32x4v*)(p.ln_b + i * 256 + lane * 4);
+                const f32x4 g = *(const f32x4*)(p.ln_g + i * 256 + lane * 4);
+                const f32x4 b = *(const f32x4*)(p.ln_b + i * 256 + lane * 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - mean) * rstd * g[e] + b[e];
             }
@@ -667,8 +644,8 @@ __global__ __launch_bounds__(256) void actor_head_kernel(ActorP p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if (i < n) {
-                const f32x4v wm = *(const f32x4v*)(p.Wmu + (long long)ff * p.d + i * 256 + lane * 4);
-                const f32x4v wl = *(const f32x4v*)(p.Wls + (long long)ff * p.d + i * 256 + lane * 4);
+                const f32x4 wm = *(const f32x4*)(p.Wmu + (long long)ff * p.d + i * 256 + lane * 4);
+                const f32x4 wl = *(const f32x4*)(p.Wls + (long long)ff * p.d + i * 256 + lane * 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     s1[f] = fmaf(v[i][e], wm[e], s1[f]);
@@ -854,7 +831,6 @@ __global__ __launch_bounds__(256) void critic_kernel(CriticP p) {
 template <int NT>
 __global__ __launch_bounds__(256, 2) void critic_mfma_kernel(CriticP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef float f32x16v __attribute__((ext_vector_type(16)));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
     const int r = (blockIdx.x * 4 + wave) * 32 + l31;
@@ -873,43 +849,43 @@ __global__ __launch_bounds__(256, 2) void critic_mfma_kernel(CriticP p) {
     float qmin = 0.f;
 #pragma unroll
     for (int net = 0; net < 2; ++net) {
-        f32x16v h1[NT];
-        const f32x4v* w1p = (const f32x4v*)p.W1F[net] + lane;
+        f32x16 h1[NT];
+        const f32x4* w1p = (const f32x4*)p.W1F[net] + lane;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const f32x4v b = *(const f32x4v*)(p.b1[net] + 32 * t + 8 * q + 4 * lh);
+                const f32x4 b = *(const f32x4*)(p.b1[net] + 32 * t + 8 * q + 4 * lh);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) h1[t][4 * q + i] = b[i];
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const f32x4v w = w1p[(t * 4 + g) * 64];
+                const f32x4 w = w1p[(t * 4 + g) * 64];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) h1[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], x[4 * g + j], h1[t], 0, 0, 0);
             }
 #pragma unroll
             for (int i = 0; i < 16; ++i) h1[t][i] = fmaxf(h1[t][i], 0.f);
         }
-        const f32x4v* w2p = (const f32x4v*)p.W2F[net] + lane;
-        f32x4v wf[4];
+        const f32x4* w2p = (const f32x4*)p.W2F[net] + lane;
+        f32x4 wf[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) wf[g] = w2p[g * 64];
         float qa = 0.f;
         for (int u = 0; u < NT; ++u) {
-            f32x16v acc;
-            f32x4v w3[4];
+            f32x16 acc;
+            f32x4 w3[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const f32x4v b = *(const f32x4v*)(p.b2[net] + 32 * u + 8 * q + 4 * lh);
-                w3[q] = *(const f32x4v*)(p.W3[net] + 32 * u + 8 * q + 4 * lh);
+                const f32x4 b = *(const f32x4*)(p.b2[net] + 32 * u + 8 * q + 4 * lh);
+                w3[q] = *(const f32x4*)(p.W3[net] + 32 * u + 8 * q + 4 * lh);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) acc[4 * q + i] = b[i];
             }
 #pragma unroll
             for (int g = 0; g < 4 * NT; ++g) {
-                const f32x4v w = wf[g % 4];
+                const f32x4 w = wf[g % 4];
                 wf[g % 4] = w2p[((u * 4 * NT) + g + 4) * 64];  // (runs 4 groups past the end: the buffer is padded)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], h1[g / 4][4 * (g % 4) + j], acc, 0, 0, 0);

@@ -11,7 +11,7 @@
 //
 // Pipeline: two LDS buffers; tile k+1 travels HBM/L2 -> registers while tile k is multiplied, and is
 // written to the other buffer after the MFMAs: one barrier per k-tile.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace m3pc {
 
@@ -20,38 +20,7 @@ thread_local int g_gemm_picked[4] = {0, 0, 0, 0};
 thread_local int g_gemm_dry = 0;
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define LDS_ROW 144
-
-// epilogue flags (template parameter)
-enum { EPI_GELU = 1, EPI_RES = 2, EPI_ROWTAB = 4, EPI_F32OUT = 8, EPI_SPLITK = 16 };
-
-// exact-erf GELU.  fp32 path: libm erff.  bf16 path: Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7 on erf,
-// far below bf16 resolution) -- 2 transcendentals instead of a ~35-instruction erff, which would
-// otherwise make the FFN epilogue VALU-bound beside the matrix pipe.
-__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float gelu_fast(float x) {
-    const float ax = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    float p = fmaf(t, 1.061405429f, -1.453152027f);
-    p = fmaf(t, p, 1.421413741f);
-    p = fmaf(t, p, -0.284496736f);
-    p = fmaf(t, p, 0.254829592f);
-    p *= t;
-    const float e = __builtin_amdgcn_exp2f(-ax * ax * 1.44269504088896340736f);
-    const float erf_abs = fmaf(-p, e, 1.0f);
-    const float hx = 0.5f * x;
-    return fmaf(fabsf(hx), erf_abs, hx);  // 0.5x(1+erf(x/sqrt2)) with erf odd
-}
-
-__device__ __forceinline__ int map_row(const RowMap& m, int r) {
-    if (m.rpg == 0) return r;
-    return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
-}
 
 template <typename T, int BM, int BN, int EPI>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
@@ -81,7 +50,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
     const long long lda_b = (long long)p.lda * sizeof(T), ldw_b = (long long)p.ldw * sizeof(T);
     const int nkt = (int)((long long)p.K * sizeof(T) / 128);
     int kt0 = 0, kt1 = nkt;  // split-K: blockIdx.y owns a contiguous run of k-tiles, raw partials go to p.ws
-    if constexpr (EPI & EPI_SPLITK) {
+    if constexpr (EPI & GE_SPLITK) {
         kt0 = (int)((long long)nkt * blockIdx.y / gridDim.y);
         kt1 = (int)((long long)nkt * (blockIdx.y + 1) / gridDim.y);
     }
@@ -179,7 +148,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
     }
 
     // epilogue.  acc[i][j][reg]: row = (reg&3) + 8*(reg>>2) + 4*(lane>>5), col = lane&31 of the 32x32 tile
-    if constexpr (EPI & EPI_SPLITK) {
+    if constexpr (EPI & GE_SPLITK) {
         float* slab = p.ws + (long long)blockIdx.y * p.M * p.N;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -208,10 +177,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
                 for (int j = 0; j < TN; ++j) {
                     const int c = col0 + wc * (BN / 2) + j * 32 + (lane & 31);
                     float v = acc[i][j][reg] + bj[j];
-                    if constexpr (EPI & EPI_ROWTAB) v += p.rowtab[(long long)(r % p.rt_mod) * p.rt_ld + c];
-                    if constexpr (EPI & EPI_GELU) v = sizeof(T) == 2 ? gelu_fast(v) : gelu_exact(v);
-                    if constexpr (EPI & EPI_RES) v += p.res[pr * p.ldr + c];
-                    if constexpr ((EPI & EPI_F32OUT) || sizeof(T) == 4)
+                    if constexpr (EPI & GE_ROWTAB) v += p.rowtab[(long long)(r % p.rt_mod) * p.rt_ld + c];
+                    if constexpr (EPI & GE_GELU) v = sizeof(T) == 2 ? gelu_fast(v) : gelu_exact(v);
+                    if constexpr (EPI & GE_RES) v += p.res[pr * p.ldr + c];
+                    if constexpr ((EPI & GE_F32OUT) || sizeof(T) == 4)
                         p.Cf[pr * p.ldc + c] = v;
                     else
                         p.Cb[pr * p.ldc + c] = (bf16_t)v;
@@ -241,36 +210,30 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmP p, int S, int 
 // Same reduction, one wave per output row, followed by the LayerNorm that consumes the row (GemmP::ln_*): saves the
 // separate LayerNorm launch of the few-row fp32 passes.  Column layout and summation order are those of
 // layernorm_vec_kernel (elementwise.hip), so fused and unfused paths give identical bits.
-typedef float f32x4r __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float wave_sum_r(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(GemmP p, int S, int exact_gelu) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= p.M) return;
     const long long mn = (long long)p.M * p.N;
     const int n = p.N >> 8;  // slabs of 256 columns (<= 4)
-    f32x4r v[4];
+    f32x4 v[4];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (i < n) {
             const int c = i * 256 + lane * 4;
-            f32x4r a = {0.f, 0.f, 0.f, 0.f};
+            f32x4 a = {0.f, 0.f, 0.f, 0.f};
             const float* src = p.ws + (long long)r * p.N + c;
             int k = 0;
             for (; k + 4 <= S; k += 4) {  // four slabs in flight, added in slab order (the sum order is part of the result)
-                const f32x4r t0 = *(const f32x4r*)(src + (k + 0) * mn), t1 = *(const f32x4r*)(src + (k + 1) * mn);
-                const f32x4r t2 = *(const f32x4r*)(src + (k + 2) * mn), t3 = *(const f32x4r*)(src + (k + 3) * mn);
+                const f32x4 t0 = *(const f32x4*)(src + (k + 0) * mn), t1 = *(const f32x4*)(src + (k + 1) * mn);
+                const f32x4 t2 = *(const f32x4*)(src + (k + 2) * mn), t3 = *(const f32x4*)(src + (k + 3) * mn);
                 a += t0;
                 a += t1;
                 a += t2;
                 a += t3;
             }
-            for (; k < S; ++k) a += *(const f32x4r*)(src + k * mn);
+            for (; k < S; ++k) a += *(const f32x4*)(src + k * mn);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float x = a[e];
@@ -280,12 +243,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(GemmP p, int S, i
                 if (p.res) x += p.res[(long long)r * p.ldr + c + e];
                 a[e] = x;
             }
-            *(f32x4r*)(p.Cf + (long long)r * p.ldc + c) = a;
+            *(f32x4*)(p.Cf + (long long)r * p.ldc + c) = a;
             v[i] = a;
             s += (a[0] + a[1]) + (a[2] + a[3]);
         }
     const float inv_d = 1.0f / (float)p.N;
-    const float mean = wave_sum_r(s) * inv_d;
+    const float mean = wave_sum(s) * inv_d;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -296,17 +259,17 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(GemmP p, int S, i
                 q += c * c;
             }
         }
-    const float rstd = rsqrtf(wave_sum_r(q) * inv_d + 1e-5f);
+    const float rstd = rsqrtf(wave_sum(q) * inv_d + 1e-5f);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (i < n) {
             const int c = i * 256 + lane * 4;
-            const f32x4r g = *(const f32x4r*)(p.ln_g + c);
-            const f32x4r b = *(const f32x4r*)(p.ln_b + c);
-            f32x4r y;
+            const f32x4 g = *(const f32x4*)(p.ln_g + c);
+            const f32x4 b = *(const f32x4*)(p.ln_b + c);
+            f32x4 y;
 #pragma unroll
             for (int e = 0; e < 4; ++e) y[e] = (v[i][e] - mean) * rstd * g[e] + b[e];
-            *(f32x4r*)(p.ln_out + (long long)r * p.N + c) = y;
+            *(f32x4*)(p.ln_out + (long long)r * p.N + c) = y;
         }
 }
 
@@ -351,7 +314,7 @@ static int launch_epi(const GemmP& p, hipStream_t st) {
         }
         M3PC_GEMM_PICK(sizeof(T) == 4 ? 1 : 3, S, 0, 0);
         if (S > 1) {
-            M3PC_GEMM_LAUNCH((gemm_kernel<T, 64, 64, EPI_SPLITK>), dim3((unsigned)tiles, S), dim3(256), 0, st, p);
+            M3PC_GEMM_LAUNCH((gemm_kernel<T, 64, 64, GE_SPLITK>), dim3((unsigned)tiles, S), dim3(256), 0, st, p);
             return launch_splitk_reduce(p, S, (int)(sizeof(T) == 4), st);
         } else {
             launch_cfg<T, 64, 64, EPI>(p, st);
@@ -365,18 +328,17 @@ static int launch_epi(const GemmP& p, hipStream_t st) {
 
 template <typename T>
 static int launch_t(const GemmP& p, hipStream_t st) {
-    const bool f32out = sizeof(T) == 4 || p.Cf != nullptr;
-    const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) |
-                    (f32out && sizeof(T) == 2 ? EPI_F32OUT : 0);
+    int epi = epi_flags(p);
+    if (sizeof(T) == 4) epi &= ~GE_F32OUT;  // the fp32 kernel writes Cf whatever the flag says: one instantiation
     switch (epi) {
         case 0: return launch_epi<T, 0>(p, st);
-        case EPI_F32OUT: return launch_epi<T, EPI_F32OUT>(p, st);
-        case EPI_GELU: return launch_epi<T, EPI_GELU>(p, st);
-        case EPI_GELU | EPI_F32OUT: return launch_epi<T, EPI_GELU | EPI_F32OUT>(p, st);
-        case EPI_RES: return launch_epi<T, EPI_RES>(p, st);
-        case EPI_RES | EPI_F32OUT: return launch_epi<T, EPI_RES | EPI_F32OUT>(p, st);
-        case EPI_ROWTAB: return launch_epi<T, EPI_ROWTAB>(p, st);
-        case EPI_ROWTAB | EPI_F32OUT: return launch_epi<T, EPI_ROWTAB | EPI_F32OUT>(p, st);
+        case GE_F32OUT: return launch_epi<T, GE_F32OUT>(p, st);
+        case GE_GELU: return launch_epi<T, GE_GELU>(p, st);
+        case GE_GELU | GE_F32OUT: return launch_epi<T, GE_GELU | GE_F32OUT>(p, st);
+        case GE_RES: return launch_epi<T, GE_RES>(p, st);
+        case GE_RES | GE_F32OUT: return launch_epi<T, GE_RES | GE_F32OUT>(p, st);
+        case GE_ROWTAB: return launch_epi<T, GE_ROWTAB>(p, st);
+        case GE_ROWTAB | GE_F32OUT: return launch_epi<T, GE_ROWTAB | GE_F32OUT>(p, st);
         default: M3PC_GEMM_PICK(0, 0, 0, 0); return 0;  // no caller combines the remaining flags (the lab hook refuses them: id 0)
     }
 }

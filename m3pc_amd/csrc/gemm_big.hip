@@ -12,14 +12,8 @@
 // LDS rows are 64 B; chunk position c of row r holds logical chunk c ^ ((r >> 2) & 3), applied on the global source
 // address (the DMA writes LDS linearly), which makes the ds_read_b128 groups conflict-free (as in gemm_glds.hip).
 #include "gemm_epilogue.h"
-#include "kernels.h"
 
 namespace m3pc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef void __attribute__((address_space(3))) * lptr_t;
 
 __device__ long long g_big_probe[4];  // wall ticks (100 MHz) of one workgroup: {prologue, K loop, epilogue, shader clocks of the K loop}
 void read_big_probe(long long out[4]) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_big_probe), 4 * sizeof(long long)); }
@@ -54,7 +48,7 @@ __global__ __launch_bounds__(256, 1) void gemm_big_kernel(GemmP p) {
         const int q = (lane & 3) ^ ((r >> 2) & 3);
         int gr = row0 + r;
         if (gr >= p.M) gr = p.M - 1;
-        a_vo[i] = ge_map_row(p.amap, gr) * lda_b + q * 16;
+        a_vo[i] = map_row(p.amap, gr) * lda_b + q * 16;
         w_vo[i] = (col0 + r) * ldw_b + q * 16;
     }
     const int wave_dst = __builtin_amdgcn_readfirstlane(wid) * 1024;
@@ -166,9 +160,9 @@ __global__ __launch_bounds__(256, 1) void gemm_big_kernel(GemmP p) {
     const int wu = __builtin_amdgcn_readfirstlane(wid);
     const int rbase = row0 + (wu >> 1) * 128, cbase = col0 + (wu & 1) * 128;
     const __amdgpu_buffer_rsrc_t crs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.Cf, 0, ge_clamp_bytes((long long)p.M * p.ldc * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)p.Cf, 0, clamp_bytes((long long)p.M * p.ldc * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rrs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, ge_clamp_bytes((long long)p.M * p.ldr * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, clamp_bytes((long long)p.M * p.ldr * 4), 0x00020000);
     const int vo_c = (4 * lh * p.ldc + l31) * 4, vo_r = (4 * lh * p.ldr + l31) * 4;
     float R0[64], R1[64];
     auto load_strip = [&](float (&R)[64], int i) {
@@ -273,8 +267,7 @@ bool launch_gemm_big(const GemmP& p, hipStream_t st) {
     if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15) || (p.lda % 8) || (p.ldw % 8)) return false;
     const long long a_rows = p.amap.rpg ? ((p.M + p.amap.rpg - 1) / p.amap.rpg) * (long long)p.amap.gstride + p.amap.off + p.amap.rpg : p.M;
     if (a_rows * p.lda * 2 >= 0x7ffff000ll || (long long)p.N * p.ldw * 2 >= 0x7ffff000ll) return false;
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? GE_GELU : 0) | (p.res ? GE_RES : 0) | (p.rowtab ? GE_ROWTAB : 0) | (f32out ? GE_F32OUT : 0);
+    const int epi = epi_flags(p);
     const dim3 grid(((p.M + 255) / 256) * (p.N / 256)), block(256);
     M3PC_GEMM_PICK(9, 1, 0, 0);  // (a `default:` below leaves the pick behind: the caller's next launcher overwrites it)
     switch (epi) {

@@ -14,24 +14,9 @@
 // LDS-shared tile, which does not matter at these sizes (<= 200 MB per launch).
 #include <cstdlib>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace m3pc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int map_row_d(const RowMap& m, int r) {
-    if (m.rpg == 0) return r;
-    return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
-}
-__device__ __forceinline__ float gelu_exact_d(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ float wave_sum_d(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // TQ = 32x32 sub-tiles per workgroup tile (4: 64x64 tile, 1: 32x32 tile), KS = K slices; TQ * KS = 16 waves
 template <int TQ, int KS>
@@ -47,7 +32,7 @@ __device__ __forceinline__ void gemm_f32_direct_body(const GemmP& p, int bid, fl
     const int kslice = p.K / KS;
     int gr = tm * BT + rq + l31;
     if (gr >= p.M) gr = p.M - 1;
-    const float* a = (const float*)p.A + (long long)map_row_d(p.amap, gr) * p.lda + ks * kslice + 4 * lh;
+    const float* a = (const float*)p.A + (long long)map_row(p.amap, gr) * p.lda + ks * kslice + 4 * lh;
     const float* w = (const float*)p.W + (long long)(tn * BT + cq + l31) * p.ldw + ks * kslice + 4 * lh;
 
     // optional LayerNorm of the A rows (TQ == 1): wave w computes the statistics of tile rows 2w, 2w+1 exactly as
@@ -60,7 +45,7 @@ __device__ __forceinline__ void gemm_f32_direct_body(const GemmP& p, int bid, fl
         for (int rr = 0; rr < 2; ++rr) {
             int r = tm * BT + 2 * wid + rr;
             if (r >= p.M) r = p.M - 1;
-            const float* x = (const float*)p.A + (long long)map_row_d(p.amap, r) * p.lda;
+            const float* x = (const float*)p.A + (long long)map_row(p.amap, r) * p.lda;
             f32x4 v[8];
             float s = 0.f;
 #pragma unroll
@@ -70,7 +55,7 @@ __device__ __forceinline__ void gemm_f32_direct_body(const GemmP& p, int bid, fl
                     s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
                 }
             const float inv_d = 1.0f / (float)p.K;
-            const float m = wave_sum_d(s) * inv_d;
+            const float m = wave_sum(s) * inv_d;
             float qq = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
@@ -81,7 +66,7 @@ __device__ __forceinline__ void gemm_f32_direct_body(const GemmP& p, int bid, fl
                         qq += c * c;
                     }
                 }
-            const float rs = rsqrtf(wave_sum_d(qq) * inv_d + 1e-5f);
+            const float rs = rsqrtf(wave_sum(qq) * inv_d + 1e-5f);
             if (lane == 0) {
                 lnst[2 * wid + rr][0] = m;
                 lnst[2 * wid + rr][1] = rs;
@@ -141,8 +126,8 @@ __device__ __forceinline__ void gemm_f32_direct_body(const GemmP& p, int bid, fl
         if (r < p.M) {
             if (p.bias) v += p.bias[c];
             if (p.rowtab) v += p.rowtab[(long long)(r % p.rt_mod) * p.rt_ld + c];
-            if (p.gelu) v = gelu_exact_d(v);
-            const long long pr = map_row_d(p.cmap, r);
+            if (p.gelu) v = gelu_exact(v);
+            const long long pr = map_row(p.cmap, r);
             if (p.res) v += p.res[pr * p.ldr + c];
             p.Cf[pr * p.ldc + c] = v;
         }
@@ -223,7 +208,7 @@ __global__ __launch_bounds__(1024) void head_f32_fused_kernel(HeadFusedP hp) {
                     s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
                 }
             const float inv_d = 1.0f / (float)K;
-            const float m1 = wave_sum_d(s) * inv_d;
+            const float m1 = wave_sum(s) * inv_d;
             float qq = 0.f;
 #pragma unroll
             for (int i = 0; i < nsl; ++i)
@@ -232,7 +217,7 @@ __global__ __launch_bounds__(1024) void head_f32_fused_kernel(HeadFusedP hp) {
                         const float c = v[i][e] - m1;
                         qq += c * c;
                     }
-            const float rs1 = rsqrtf(wave_sum_d(qq) * inv_d + 1e-5f);
+            const float rs1 = rsqrtf(wave_sum(qq) * inv_d + 1e-5f);
             float s2 = 0.f;
 #pragma unroll
             for (int i = 0; i < nsl; ++i) {
@@ -241,7 +226,7 @@ __global__ __launch_bounds__(1024) void head_f32_fused_kernel(HeadFusedP hp) {
                     for (int e = 0; e < 4; ++e) v[i][e] = (v[i][e] - m1) * rs1 * g[e] + b[e];
                     s2 += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
                 }
-            const float m2 = wave_sum_d(s2) * inv_d;
+            const float m2 = wave_sum(s2) * inv_d;
             float q2 = 0.f;
 #pragma unroll
             for (int i = 0; i < nsl; ++i)
@@ -250,7 +235,7 @@ __global__ __launch_bounds__(1024) void head_f32_fused_kernel(HeadFusedP hp) {
                         const float c = v[i][e] - m2;
                         q2 += c * c;
                     }
-            const float rs2 = rsqrtf(wave_sum_d(q2) * inv_d + 1e-5f);
+            const float rs2 = rsqrtf(wave_sum(q2) * inv_d + 1e-5f);
             if (lane == 0) {
                 lnst[2 * wid + rr][0] = m1;
                 lnst[2 * wid + rr][1] = rs1;
@@ -294,7 +279,7 @@ __global__ __launch_bounds__(1024) void head_f32_fused_kernel(HeadFusedP hp) {
         for (int k = 0; k < 16; ++k) v += part[k * 1024 + tid];
         const int r = tm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (ln >> 5);
         const int c = tn * 32 + (ln & 31);
-        v = gelu_exact_d(v + hb1[c]) * hw2[c];
+        v = gelu_exact(v + hb1[c]) * hw2[c];
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);  // over the tile's 32 columns (one half wave per row)
         // (agent-scope atomic store: written through to where every XCD sees it -- no fence, hence no L2 write-back, needed)

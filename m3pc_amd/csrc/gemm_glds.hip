@@ -9,40 +9,12 @@
 //   * two LDS buffers, tile k+1 is in flight while tile k is multiplied, one barrier per k-tile;
 //   * residual rows (out-proj / FFN2 epilogues) are prefetched into registers before the K loop, so the
 //     epilogue does not start with a dependent HBM round trip.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace m3pc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-enum { EPI_GELU = 1, EPI_RES = 2, EPI_ROWTAB = 4, EPI_F32OUT = 8 };
-
 __device__ long long g_clock_probe[2];  // {shader clocks, 100-MHz wall ticks} of one workgroup (debug variants only)
 void read_clock_probe(long long out[2]) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_clock_probe), 2 * sizeof(long long)); }
-
-__device__ __forceinline__ float gelu_fast2(float x) {
-    const float ax = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    float p = fmaf(t, 1.061405429f, -1.453152027f);
-    p = fmaf(t, p, 1.421413741f);
-    p = fmaf(t, p, -0.284496736f);
-    p = fmaf(t, p, 0.254829592f);
-    p *= t;
-    const float e = __builtin_amdgcn_exp2f(-ax * ax * 1.44269504088896340736f);
-    const float erf_abs = fmaf(-p, e, 1.0f);
-    const float hx = 0.5f * x;
-    return fmaf(fabsf(hx), erf_abs, hx);
-}
-
-__device__ __forceinline__ int map_row2(const RowMap& m, int r) {
-    if (m.rpg == 0) return r;
-    return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
-}
-
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
 
 // ROWB = bytes of K per LDS row and stage: 128 (64 k, 4 MFMA k-steps per barrier) or 64 (32 k, 2 k-steps, half the
 // LDS => more workgroups per CU, i.e. more tiles in flight against the DMA latency)
@@ -51,15 +23,6 @@ typedef void __attribute__((address_space(3))) * lptr_t;
 // NSLOT = 2: double buffer, one stage in flight, __syncthreads per stage.  NSLOT = 3 (with ROWB = 64): ring of three
 // 32-deep stages, two in flight, counted s_waitcnt vmcnt + raw s_barrier (a __syncthreads would drain the DMA queue),
 // 48 KiB of LDS per 128x128 workgroup => three workgroups per CU.
-template <int N>
-__device__ __forceinline__ void glds_wait_barrier() {
-    static_assert(N == 0 || N == 2 || N == 4 || N == 6 || N == 8, "add the immediate");
-    if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-    if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
-    if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-}
 template <int BM, int BN, int EPI, int WM, int WN, int ROWB, int NSLOT = 2>
 __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int bid, const int ntm, const int row_begin) {
     constexpr int RPI = 1024 / ROWB;   // tile rows per 1-KiB DMA instruction
@@ -94,7 +57,7 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
         const int q = (lane % LPR) ^ (ROWB == 128 ? ((r >> 1) & 7) : ((r >> 2) & 3));
         int gr = row0 + r;
         if (gr >= p.M) gr = p.M - 1;
-        a_src[i] = (const char*)p.A + (long long)map_row2(p.amap, gr) * lda_b + q * 16;
+        a_src[i] = (const char*)p.A + (long long)map_row(p.amap, gr) * lda_b + q * 16;
     }
 #pragma unroll
     for (int i = 0; i < NI_W; ++i) {
@@ -160,7 +123,7 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
     // residual prefetch (same element order as the epilogue)
     // (only for wave tiles up to 64x64: a 128x64 wave tile already holds 128 accumulator registers and loads its
     // residual in the epilogue instead)
-    constexpr bool RES_PREFETCH = (EPI & EPI_RES) != 0 && TM * TN <= 4;
+    constexpr bool RES_PREFETCH = (EPI & GE_RES) != 0 && TM * TN <= 4;
     float rres[RES_PREFETCH ? TM * 16 * TN : 1];
     if constexpr (RES_PREFETCH) {
         if (p.cmap.rpg == 0 && row0 + BM <= p.M) {  // scalar row offsets, one per-lane offset (gemm_epilogue.h)
@@ -187,7 +150,7 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
             for (int reg = 0; reg < 16; ++reg) {
                 int r = row0 + wr * WTM + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
                 if (r >= p.M) r = p.M - 1;
-                const long long pr = map_row2(p.cmap, r);
+                const long long pr = map_row(p.cmap, r);
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
                     rres[(i * 16 + reg) * TN + j] = p.res[pr * p.ldr + col0 + wc * WTN + j * 32 + (lane & 31)];
@@ -209,9 +172,9 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
         if (nkt > 1) issue(1, 1);
         for (int kt = 0; kt < nkt; ++kt) {
             if (kt + 1 < nkt)
-                glds_wait_barrier<PER>();
+                wait_vmcnt_barrier<PER>();
             else
-                glds_wait_barrier<0>();
+                wait_vmcnt_barrier<0>();
             // every wave has finished reading slot (kt-1)%3 = (kt+2)%3 before it passed this barrier
             if (kt + 2 < nkt) issue(kt + 2, (kt + 2) % 3);
             const char* cur = smem + (kt % 3) * BUF;
@@ -426,11 +389,11 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
         if (t == 12345.678f) p.Cf[0] = t;
         return;
     }
-    if (p.cmap.rpg == 0 && row0 + BM <= p.M && !(EPI & EPI_ROWTAB)) {
+    if (p.cmap.rpg == 0 && row0 + BM <= p.M && !(EPI & GE_ROWTAB)) {
         // full tile, identity row map: scalar row offset (buffer soffset) + one per-lane offset (voffset);
         // see gemm_epilogue.h.  The residual comes from the registers prefetched before the K loop.
-        constexpr int ES = (EPI & EPI_F32OUT) ? 4 : 2;
-        void* cptr = (EPI & EPI_F32OUT) ? (void*)p.Cf : (void*)p.Cb;
+        constexpr int ES = (EPI & GE_F32OUT) ? 4 : 2;
+        void* cptr = (EPI & GE_F32OUT) ? (void*)p.Cf : (void*)p.Cb;
         const long long cb = (long long)p.M * p.ldc * ES;
         const __amdgpu_buffer_rsrc_t crs =
             __builtin_amdgcn_make_buffer_rsrc(cptr, 0, cb > 0xfffff000ll ? 0xfffff000u : (unsigned)cb, 0x00020000);
@@ -439,7 +402,7 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
         const int vo_c = (4 * lh * p.ldc + l31) * ES;
         const long long rb2 = (long long)p.M * p.ldr * 4;
         const __amdgpu_buffer_rsrc_t rrs2 = __builtin_amdgcn_make_buffer_rsrc(
-            (EPI & EPI_RES) ? (void*)p.res : cptr, 0, rb2 > 0xfffff000ll ? 0xfffff000u : (unsigned)rb2, 0x00020000);
+            (EPI & GE_RES) ? (void*)p.res : cptr, 0, rb2 > 0xfffff000ll ? 0xfffff000u : (unsigned)rb2, 0x00020000);
         const int vo_r2 = (4 * lh * p.ldr + l31) * 4;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -450,12 +413,12 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     float v = acc[i][j][reg] + bj[j];
-                    if constexpr (EPI & EPI_GELU) v = gelu_fast2(v);
+                    if constexpr (EPI & GE_GELU) v = gelu_fast(v);
                     if constexpr (RES_PREFETCH)
                         v += rres[(i * 16 + reg) * TN + j];
-                    else if constexpr (EPI & EPI_RES)
+                    else if constexpr (EPI & GE_RES)
                         v += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs2, vo_r2 + j * 128, so_r2, 0));
-                    if constexpr (EPI & EPI_F32OUT)
+                    if constexpr (EPI & GE_F32OUT)
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), crs, vo_c + j * 128, so_c, 0);
                     else
                         __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (bf16_t)v), crs, vo_c + j * 64,
@@ -472,8 +435,8 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
     int* rowinfo = (int*)smem;
     for (int rr = tid; rr < BM; rr += NW * 64) {
         const int gr = row0 + rr;
-        rowinfo[2 * rr] = gr < p.M ? map_row2(p.cmap, gr) : -1;
-        rowinfo[2 * rr + 1] = (EPI & EPI_ROWTAB) ? gr % p.rt_mod : 0;
+        rowinfo[2 * rr] = gr < p.M ? map_row(p.cmap, gr) : -1;
+        rowinfo[2 * rr + 1] = (EPI & GE_ROWTAB) ? gr % p.rt_mod : 0;
     }
     __syncthreads();
 #pragma unroll
@@ -488,13 +451,13 @@ __device__ __forceinline__ void gemm_glds_tile(const GemmP& p, char* smem, int b
                 for (int j = 0; j < TN; ++j) {
                     const int c = col0 + wc * WTN + j * 32 + l31;
                     float v = acc[i][j][reg] + bj[j];
-                    if constexpr (EPI & EPI_ROWTAB) v += p.rowtab[tri * p.rt_ld + c];
-                    if constexpr (EPI & EPI_GELU) v = gelu_fast2(v);
+                    if constexpr (EPI & GE_ROWTAB) v += p.rowtab[tri * p.rt_ld + c];
+                    if constexpr (EPI & GE_GELU) v = gelu_fast(v);
                     if constexpr (RES_PREFETCH)
                         v += rres[(i * 16 + reg) * TN + j];
-                    else if constexpr (EPI & EPI_RES)
+                    else if constexpr (EPI & GE_RES)
                         v += p.res[pr * p.ldr + c];
-                    if constexpr (EPI & EPI_F32OUT)
+                    if constexpr (EPI & GE_F32OUT)
                         p.Cf[pr * p.ldc + c] = v;
                     else
                         p.Cb[pr * p.ldc + c] = (bf16_t)v;
@@ -562,30 +525,28 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_ring3w_kernel(GemmP p) {
     gemm_glds_tile<256, 128, EPI, 2, 2, 64, 3>(p, smem, blockIdx.x, (p.M + 255) / 256, 0);
 }
 static bool launch_ring3w(const GemmP& p, hipStream_t st) {
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) | (f32out ? EPI_F32OUT : 0);
+    const int epi = epi_flags(p);
     const dim3 grid(((p.M + 255) / 256) * (p.N / 128)), block(256);
     switch (epi) {
         case 0: M3PC_GEMM_LAUNCH(gemm_glds_ring3w_kernel<0>, grid, block, 0, st, p); return true;
-        case EPI_GELU: M3PC_GEMM_LAUNCH(gemm_glds_ring3w_kernel<EPI_GELU>, grid, block, 0, st, p); return true;
+        case GE_GELU: M3PC_GEMM_LAUNCH(gemm_glds_ring3w_kernel<GE_GELU>, grid, block, 0, st, p); return true;
         default: return false;
     }
 }
 
 static bool launch_ring3(const GemmP& p, hipStream_t st) {
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) | (f32out ? EPI_F32OUT : 0);
+    const int epi = epi_flags(p);
     const int tiles = p.peel > 0 ? (p.peel / 128) * (p.N / 128) + ((p.M - p.peel + 63) / 64) * (p.N / 64)
                                  : ((p.M + 127) / 128) * (p.N / 128);
     const dim3 grid(tiles), block(256);
     M3PC_GEMM_PICK(7, 1, p.peel > 0 ? p.peel : 0, 0);
     switch (epi) {
         case 0: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<0>, grid, block, 0, st, p); return true;
-        case EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_F32OUT>, grid, block, 0, st, p); return true;
-        case EPI_GELU: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_GELU>, grid, block, 0, st, p); return true;
-        case EPI_GELU | EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_GELU | EPI_F32OUT>, grid, block, 0, st, p); return true;
-        case EPI_RES | EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_RES | EPI_F32OUT>, grid, block, 0, st, p); return true;
-        case EPI_ROWTAB | EPI_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<EPI_ROWTAB | EPI_F32OUT>, grid, block, 0, st, p); return true;
+        case GE_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<GE_F32OUT>, grid, block, 0, st, p); return true;
+        case GE_GELU: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<GE_GELU>, grid, block, 0, st, p); return true;
+        case GE_GELU | GE_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<GE_GELU | GE_F32OUT>, grid, block, 0, st, p); return true;
+        case GE_RES | GE_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<GE_RES | GE_F32OUT>, grid, block, 0, st, p); return true;
+        case GE_ROWTAB | GE_F32OUT: M3PC_GEMM_LAUNCH(gemm_glds_ring3_kernel<GE_ROWTAB | GE_F32OUT>, grid, block, 0, st, p); return true;
         default: return false;
     }
 }
@@ -621,16 +582,15 @@ static void launch_cfg(const GemmP& p, hipStream_t st) {
 
 template <int BM, int BN, int WM, int WN, int ROWB = 128>
 static bool launch_tile(const GemmP& p, hipStream_t st) {
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) | (f32out ? EPI_F32OUT : 0);
+    const int epi = epi_flags(p);
     M3PC_GEMM_PICK(BM == 128 && BN == 128 && WM == 2 && WN == 2 ? 8 : 0, 1, BM == 128 && BN == 128 && p.peel > 0 ? p.peel : 0, 0);
     switch (epi) {
         case 0: launch_cfg<BM, BN, 0, WM, WN, ROWB>(p, st); return true;
-        case EPI_F32OUT: launch_cfg<BM, BN, EPI_F32OUT, WM, WN, ROWB>(p, st); return true;
-        case EPI_GELU: launch_cfg<BM, BN, EPI_GELU, WM, WN, ROWB>(p, st); return true;
-        case EPI_GELU | EPI_F32OUT: launch_cfg<BM, BN, EPI_GELU | EPI_F32OUT, WM, WN, ROWB>(p, st); return true;
-        case EPI_RES | EPI_F32OUT: launch_cfg<BM, BN, EPI_RES | EPI_F32OUT, WM, WN, ROWB>(p, st); return true;
-        case EPI_ROWTAB | EPI_F32OUT: launch_cfg<BM, BN, EPI_ROWTAB | EPI_F32OUT, WM, WN, ROWB>(p, st); return true;
+        case GE_F32OUT: launch_cfg<BM, BN, GE_F32OUT, WM, WN, ROWB>(p, st); return true;
+        case GE_GELU: launch_cfg<BM, BN, GE_GELU, WM, WN, ROWB>(p, st); return true;
+        case GE_GELU | GE_F32OUT: launch_cfg<BM, BN, GE_GELU | GE_F32OUT, WM, WN, ROWB>(p, st); return true;
+        case GE_RES | GE_F32OUT: launch_cfg<BM, BN, GE_RES | GE_F32OUT, WM, WN, ROWB>(p, st); return true;
+        case GE_ROWTAB | GE_F32OUT: launch_cfg<BM, BN, GE_ROWTAB | GE_F32OUT, WM, WN, ROWB>(p, st); return true;
         default: return false;
     }
 }

@@ -22,25 +22,8 @@
 #include <type_traits>
 
 #include "gemm_epilogue.h"
-#include "kernels.h"
 
 namespace m3pc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef void __attribute__((address_space(3))) * lptr_t;
-
-template <int PU>
-__device__ __forceinline__ void line_wait_barrier() {
-    static_assert(PU == 4 || PU == 8 || PU == 6 || PU == 12 || PU == 16 || PU == 24, "add the immediate");
-    if constexpr (PU == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (PU == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (PU == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (PU == 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (PU == 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (PU == 24) asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // DBG (timing experiments, tools/gemm_bench.py 45/46): 1 = no DMA pieces, 2 = no MFMA
 template <int BT, int EPI, int DBG = 0>
@@ -90,7 +73,7 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 1) void gemm_line_kernel(GemmP
             } else {
                 int gr = r0 + r;
                 if (gr >= p.M) gr = p.M - 1;
-                a_vo[i] = ge_map_row(p.amap, gr) * lda_b + q * 16;
+                a_vo[i] = map_row(p.amap, gr) * lda_b + q * 16;
                 w_vo[i] = (c0 + r) * ldw_b + q * 16;
             }
         }
@@ -149,7 +132,7 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 1) void gemm_line_kernel(GemmP
     for (int i = 0; i < PU; ++i) piece(2, a_base + 128, false, i);
 #pragma unroll
     for (int i = 0; i < PU / 2; ++i) piece(3, w_base + 128, true, i);
-    line_wait_barrier<PU + PU / 2>();
+    wait_vmcnt_barrier<PU + PU / 2, true>();
 #pragma unroll
     for (int g = 0; g < G; ++g) frag(0, 0, 1, 0, g);
 
@@ -202,7 +185,7 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 1) void gemm_line_kernel(GemmP
         pattern(true);
         // k-step 3: every read of pair u is back and A(u+1), W(u+1) have landed everywhere -> first fragments of pair
         // u+1; first half of W(u+2) into the slot A(u) vacated
-        line_wait_barrier<PU>();
+        wait_vmcnt_barrier<PU, true>();
         mid();
 #pragma unroll
         for (int g = 0; g < G; ++g) {
@@ -232,9 +215,9 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 1) void gemm_line_kernel(GemmP
         const bool fastepi = RESEPI && p.cmap.rpg == 0 && row0 + BT <= p.M;
         const int rbase = row0 + (wu >> 1) * (BT / 2), cbase = col0 + (wu & 1) * (BT / 2);
         const __amdgpu_buffer_rsrc_t crs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)p.Cf, 0, ge_clamp_bytes((long long)p.M * p.ldc * 4), 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc((void*)p.Cf, 0, clamp_bytes((long long)p.M * p.ldc * 4), 0x00020000);
         const __amdgpu_buffer_rsrc_t rrs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, ge_clamp_bytes((long long)p.M * p.ldr * 4), 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, clamp_bytes((long long)p.M * p.ldr * 4), 0x00020000);
         const int vo_c = (4 * lh * p.ldc + l31) * 4, vo_r = (4 * lh * p.ldr + l31) * 4;
         constexpr int RS = 16 * T;  // residual values per lane per strip
         float R0[RS], R1[RS];
@@ -306,13 +289,12 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 1) void gemm_line_kernel(GemmP
         a_base = a_base_n;
         w_base = w_base_n;
     }
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // drain the pieces issued past the last tile
+    wait_vmcnt_barrier<0>();  // drain the pieces issued past the last tile
 }
 
 template <int BT>
 static bool launch_line(const GemmP& p, hipStream_t st) {
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? GE_GELU : 0) | (p.res ? GE_RES : 0) | (f32out ? GE_F32OUT : 0);
+    const int epi = epi_flags(p) & ~GE_ROWTAB;  // (launch_gemm_line refuses a row table)
     const int tiles = ((p.M + BT - 1) / BT) * (p.N / BT), slots = (BT == 128 ? 2 : 1) * 256;  // resident workgroups on 256 CUs
     const bool uniform = p.amap.rpg == 0 && (p.M % BT == 0 || p.a_padded);  // (see the kernel: persistent workgroups need look-alike tiles)
     const dim3 grid(uniform && tiles > slots ? slots : tiles), block(256);

@@ -11,34 +11,8 @@
 // walks its own contiguous range of tiles, so the column tiles of one A row-panel meet in one L2.
 #include "gemm_epilogue.h"
 #include "gemm_stage_asm.h"
-#include "kernels.h"
 
 namespace m3pc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
-
-enum { EPI_GELU = 1, EPI_RES = 2, EPI_ROWTAB = 4, EPI_F32OUT = 8 };
-
-__device__ __forceinline__ float gelu_fast4(float x) {
-    const float ax = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    float p = fmaf(t, 1.061405429f, -1.453152027f);
-    p = fmaf(t, p, 1.421413741f);
-    p = fmaf(t, p, -0.284496736f);
-    p = fmaf(t, p, 0.254829592f);
-    p *= t;
-    const float e = __builtin_amdgcn_exp2f(-ax * ax * 1.44269504088896340736f);
-    const float erf_abs = fmaf(-p, e, 1.0f);
-    const float hx = 0.5f * x;
-    return fmaf(fabsf(hx), erf_abs, hx);
-}
-__device__ __forceinline__ int map_row4(const RowMap& m, int r) {
-    if (m.rpg == 0) return r;
-    return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
-}
 
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_persist_kernel(GemmP p) {
@@ -74,7 +48,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persist_kernel(GemmP p) {
             const int q = (lane & 7) ^ ((r >> 1) & 7);
             int gr = row0 + r;
             if (gr >= p.M) gr = p.M - 1;
-            a_src[i] = (const char*)p.A + (long long)map_row4(p.amap, gr) * lda_b + q * 16;
+            a_src[i] = (const char*)p.A + (long long)map_row(p.amap, gr) * lda_b + q * 16;
             w_src[i] = (const char*)p.W + (long long)(col0 + r) * ldw_b + q * 16;
         }
     };
@@ -182,15 +156,14 @@ bool launch_gemm_persist(const GemmP& p, hipStream_t st) {
         n_cu = prop.multiProcessorCount;
     }
     const int grid = (int)(ntiles < n_cu ? ntiles : n_cu);
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) | (f32out ? EPI_F32OUT : 0);
+    const int epi = epi_flags(p);
     switch (epi) {
         case 0: launch_cfg<0>(p, grid, st); return true;
-        case EPI_F32OUT: launch_cfg<EPI_F32OUT>(p, grid, st); return true;
-        case EPI_GELU: launch_cfg<EPI_GELU>(p, grid, st); return true;
-        case EPI_GELU | EPI_F32OUT: launch_cfg<EPI_GELU | EPI_F32OUT>(p, grid, st); return true;
-        case EPI_RES | EPI_F32OUT: launch_cfg<EPI_RES | EPI_F32OUT>(p, grid, st); return true;
-        case EPI_ROWTAB | EPI_F32OUT: launch_cfg<EPI_ROWTAB | EPI_F32OUT>(p, grid, st); return true;
+        case GE_F32OUT: launch_cfg<GE_F32OUT>(p, grid, st); return true;
+        case GE_GELU: launch_cfg<GE_GELU>(p, grid, st); return true;
+        case GE_GELU | GE_F32OUT: launch_cfg<GE_GELU | GE_F32OUT>(p, grid, st); return true;
+        case GE_RES | GE_F32OUT: launch_cfg<GE_RES | GE_F32OUT>(p, grid, st); return true;
+        case GE_ROWTAB | GE_F32OUT: launch_cfg<GE_ROWTAB | GE_F32OUT>(p, grid, st); return true;
         default: return false;
     }
 }

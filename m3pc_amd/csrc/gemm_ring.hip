@@ -15,46 +15,8 @@
 // LDS rows are 64 B; chunk position c of row r holds logical chunk c ^ ((r >> 2) & 3) (swizzle applied on the
 // global SOURCE address, the DMA writes linearly), which makes the 16-row ds_read_b128 groups conflict-free.
 #include "gemm_epilogue.h"
-#include "kernels.h"
 
 namespace m3pc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
-
-enum { EPI_GELU = 1, EPI_RES = 2, EPI_ROWTAB = 4, EPI_F32OUT = 8 };
-
-__device__ __forceinline__ float gelu_fast3(float x) {
-    const float ax = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    float p = fmaf(t, 1.061405429f, -1.453152027f);
-    p = fmaf(t, p, 1.421413741f);
-    p = fmaf(t, p, -0.284496736f);
-    p = fmaf(t, p, 0.254829592f);
-    p *= t;
-    const float e = __builtin_amdgcn_exp2f(-ax * ax * 1.44269504088896340736f);
-    const float erf_abs = fmaf(-p, e, 1.0f);
-    const float hx = 0.5f * x;
-    return fmaf(fabsf(hx), erf_abs, hx);
-}
-__device__ __forceinline__ int map_row3(const RowMap& m, int r) {
-    if (m.rpg == 0) return r;
-    return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
-}
-
-#define RING_WAIT_BARRIER(N) asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier" ::: "memory")
-template <int N>
-__device__ __forceinline__ void ring_wait_barrier() {
-    static_assert(N == 0 || N == 3 || N == 4 || N == 6 || N == 8, "add the immediate");
-    if constexpr (N == 0) RING_WAIT_BARRIER(0);
-    if constexpr (N == 3) RING_WAIT_BARRIER(3);
-    if constexpr (N == 4) RING_WAIT_BARRIER(4);
-    if constexpr (N == 6) RING_WAIT_BARRIER(6);
-    if constexpr (N == 8) RING_WAIT_BARRIER(8);
-}
 
 // NSLOT = 4: three stages in flight, one block per CU.  NSLOT = 3 (BN = 128 only): two stages in flight, 72 KiB of
 // LDS and <= 128 VGPRs so that two blocks share a CU and one block's epilogue overlaps the other's main loop.
@@ -93,7 +55,7 @@ __global__ __launch_bounds__(512, NSLOT == 3 ? 4 : 2) void gemm_ring_kernel(Gemm
         const int q = (lane & 3) ^ ((r >> 2) & 3);
         int gr = row0 + r;
         if (gr >= p.M) gr = p.M - 1;
-        a_src[i] = (const char*)p.A + (long long)map_row3(p.amap, gr) * lda_b + q * 16;
+        a_src[i] = (const char*)p.A + (long long)map_row(p.amap, gr) * lda_b + q * 16;
     }
 #pragma unroll
     for (int i = 0; i < NI_W; ++i) {
@@ -156,16 +118,16 @@ __global__ __launch_bounds__(512, NSLOT == 3 ? 4 : 2) void gemm_ring_kernel(Gemm
 #pragma unroll
     for (int s = 0; s < F; ++s) issue(s);
     for (int st = 0; st < nst - (F - 1); ++st) {
-        ring_wait_barrier<(F - 1) * PER>();
+        wait_vmcnt_barrier<(F - 1) * PER>();
         if (st + F < nst) issue(st + F);
         compute(st);
     }
     // tail: the last F-1 stages (nothing left to issue)
     if constexpr (F == 3) {
-        ring_wait_barrier<PER>();
+        wait_vmcnt_barrier<PER>();
         compute(nst - 2);
     }
-    ring_wait_barrier<0>();
+    wait_vmcnt_barrier<0>();
     compute(nst - 1);
 
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -183,15 +145,14 @@ static void launch_cfg(const GemmP& p, hipStream_t st) {
 
 template <int BN, int NSLOT>
 static bool launch_bn(const GemmP& p, hipStream_t st) {
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? EPI_GELU : 0) | (p.res ? EPI_RES : 0) | (p.rowtab ? EPI_ROWTAB : 0) | (f32out ? EPI_F32OUT : 0);
+    const int epi = epi_flags(p);
     switch (epi) {
         case 0: launch_cfg<BN, 0, NSLOT>(p, st); return true;
-        case EPI_F32OUT: launch_cfg<BN, EPI_F32OUT, NSLOT>(p, st); return true;
-        case EPI_GELU: launch_cfg<BN, EPI_GELU, NSLOT>(p, st); return true;
-        case EPI_GELU | EPI_F32OUT: launch_cfg<BN, EPI_GELU | EPI_F32OUT, NSLOT>(p, st); return true;
-        case EPI_RES | EPI_F32OUT: launch_cfg<BN, EPI_RES | EPI_F32OUT, NSLOT>(p, st); return true;
-        case EPI_ROWTAB | EPI_F32OUT: launch_cfg<BN, EPI_ROWTAB | EPI_F32OUT, NSLOT>(p, st); return true;
+        case GE_F32OUT: launch_cfg<BN, GE_F32OUT, NSLOT>(p, st); return true;
+        case GE_GELU: launch_cfg<BN, GE_GELU, NSLOT>(p, st); return true;
+        case GE_GELU | GE_F32OUT: launch_cfg<BN, GE_GELU | GE_F32OUT, NSLOT>(p, st); return true;
+        case GE_RES | GE_F32OUT: launch_cfg<BN, GE_RES | GE_F32OUT, NSLOT>(p, st); return true;
+        case GE_ROWTAB | GE_F32OUT: launch_cfg<BN, GE_ROWTAB | GE_F32OUT, NSLOT>(p, st); return true;
         default: return false;
     }
 }

@@ -8,13 +8,8 @@
 //   iteration kt:  barrier (stage kt visible) | issue loads of stage kt+2 -> set (kt&1) | MFMAs of stage kt out of
 //                  slot kt&1 | park stage kt+1 (set (kt+1)&1, loaded during iteration kt-1) in slot (kt+1)&1
 #include "gemm_epilogue.h"
-#include "kernels.h"
 
 namespace m3pc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 template <int EPI>
 __global__ __launch_bounds__(256, 4) void gemm_rs_kernel(GemmP p) {
@@ -43,7 +38,7 @@ __global__ __launch_bounds__(256, 4) void gemm_rs_kernel(GemmP p) {
         const int r = 16 * (wid + 4 * i) + lane / 4, q = lane % 4;
         int gr = row0 + r;
         if (gr >= p.M) gr = p.M - 1;
-        a_vo[i] = ge_map_row(p.amap, gr) * lda_b + q * 16;
+        a_vo[i] = map_row(p.amap, gr) * lda_b + q * 16;
         w_vo[i] = (col0 + r) * ldw_b + q * 16;
         const int sw = (q ^ ((r >> 2) & 3)) * 16;  // LDS-side swizzle: logical chunk q of row r sits at q ^ ((r>>2)&3)
         dstA[i] = r * ROWB + sw;
@@ -126,8 +121,7 @@ bool launch_gemm_rs(const GemmP& p, hipStream_t st) {
     if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15) || (p.lda % 8) || (p.ldw % 8)) return false;
     const long long a_rows = p.amap.rpg ? ((p.M + p.amap.rpg - 1) / p.amap.rpg) * (long long)p.amap.gstride + p.amap.off + p.amap.rpg : p.M;
     if (a_rows * p.lda * 2 >= 0x7ffff000ll || (long long)p.N * p.ldw * 2 >= 0x7ffff000ll) return false;
-    const bool f32out = p.Cf != nullptr;
-    const int epi = (p.gelu ? GE_GELU : 0) | (p.res ? GE_RES : 0) | (p.rowtab ? GE_ROWTAB : 0) | (f32out ? GE_F32OUT : 0);
+    const int epi = epi_flags(p);
     const dim3 grid(((p.M + 127) / 128) * (p.N / 128)), block(256);
     switch (epi) {
         case 0: hipLaunchKernelGGL(gemm_rs_kernel<0>, grid, block, 0, st, p); return true;

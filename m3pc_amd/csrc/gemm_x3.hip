@@ -19,32 +19,19 @@
 
 namespace m3pc {
 
-typedef float x3_f32x16 __attribute__((ext_vector_type(16)));
-typedef float x3_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 x3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 x3_bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int x3_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int x3_u32x2 __attribute__((ext_vector_type(2)));
-
 #define X3_ROW 144
-enum { X3_SPLITK = 1 << 8 };  // template flag beside the GE_* epilogue flags: raw partial sums to p.ws slab blockIdx.y
 
 // hi = bf16_rne(x) (v_cvt_pk_bf16_f32), lo = bf16_rne(x - hi); x - hi is exact in fp32
-__device__ __forceinline__ void x3_split4(x3_u32x4 raw, x3_u32x2& hi, x3_u32x2& lo) {
-    const x3_f32x4 x = __builtin_bit_cast(x3_f32x4, raw);
-    x3_bf16x4 h, l;
+__device__ __forceinline__ void x3_split4(u32x4 raw, u32x2& hi, u32x2& lo) {
+    const f32x4 x = __builtin_bit_cast(f32x4, raw);
+    bf16x4 h, l;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         h[e] = (__bf16)x[e];
         l[e] = (__bf16)(x[e] - (float)h[e]);
     }
-    hi = __builtin_bit_cast(x3_u32x2, h);
-    lo = __builtin_bit_cast(x3_u32x2, l);
-}
-
-__device__ __forceinline__ int x3_map_row(const RowMap& m, int r) {
-    if (m.rpg == 0) return r;
-    return (r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
+    hi = __builtin_bit_cast(u32x2, h);
+    lo = __builtin_bit_cast(u32x2, l);
 }
 
 template <int BM, int BN, int EPI>
@@ -74,7 +61,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmP p) {
     const long long lda_b = (long long)p.lda * 4, ldw_b = (long long)p.ldw * 2, wlo_b = p.w_lo_off * 2;
     const int nkt = p.K / 32;
     int kt0 = 0, kt1 = nkt;
-    if constexpr (EPI & X3_SPLITK) {
+    if constexpr (EPI & GE_SPLITK) {
         kt0 = (int)((long long)nkt * blockIdx.y / gridDim.y);
         kt1 = (int)((long long)nkt * (blockIdx.y + 1) / gridDim.y);
     }
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmP p) {
         const int c = tid + i * 256, r = c >> 3, kc = c & 7;
         int gr = row0 + r;
         if (gr >= p.M) gr = p.M - 1;
-        a_src[i] = Ab + (long long)x3_map_row(p.amap, gr) * lda_b + kc * 16 + (long long)kt0 * 128;
+        a_src[i] = Ab + (long long)map_row(p.amap, gr) * lda_b + kc * 16 + (long long)kt0 * 128;
         a_dst[i] = r * X3_ROW + kc * 8;
     }
     // W: chunk c = row c / 8, piece c % 8: pieces 0..3 the 64 hi bytes, 4..7 the 64 lo bytes of the k-tile
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmP p) {
         w_dst[i] = BM * X3_ROW + r * X3_ROW + kc * 16;
     }
 
-    x3_f32x16 acc[TM][TN];
+    f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -109,23 +96,23 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmP p) {
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     const int nloc = kt1 - kt0;
-    x3_u32x4 ra0[A_CH], rw0[W_CH], ra1[A_CH], rw1[W_CH];
-    auto gload = [&](x3_u32x4* ra, x3_u32x4* rw, int kt) {
+    u32x4 ra0[A_CH], rw0[W_CH], ra1[A_CH], rw1[W_CH];
+    auto gload = [&](u32x4* ra, u32x4* rw, int kt) {
 #pragma unroll
-        for (int i = 0; i < A_CH; ++i) ra[i] = *(const x3_u32x4*)(a_src[i] + (long long)kt * 128);
+        for (int i = 0; i < A_CH; ++i) ra[i] = *(const u32x4*)(a_src[i] + (long long)kt * 128);
 #pragma unroll
-        for (int i = 0; i < W_CH; ++i) rw[i] = *(const x3_u32x4*)(w_src[i] + (long long)kt * 64);
+        for (int i = 0; i < W_CH; ++i) rw[i] = *(const u32x4*)(w_src[i] + (long long)kt * 64);
     };
-    auto lstore = [&](const x3_u32x4* ra, const x3_u32x4* rw, char* buf) {
+    auto lstore = [&](const u32x4* ra, const u32x4* rw, char* buf) {
 #pragma unroll
         for (int i = 0; i < A_CH; ++i) {
-            x3_u32x2 hi, lo;
+            u32x2 hi, lo;
             x3_split4(ra[i], hi, lo);
-            *(x3_u32x2*)(buf + a_dst[i]) = hi;
-            *(x3_u32x2*)(buf + a_dst[i] + 64) = lo;
+            *(u32x2*)(buf + a_dst[i]) = hi;
+            *(u32x2*)(buf + a_dst[i] + 64) = lo;
         }
 #pragma unroll
-        for (int i = 0; i < W_CH; ++i) *(x3_u32x4*)(buf + w_dst[i]) = rw[i];
+        for (int i = 0; i < W_CH; ++i) *(u32x4*)(buf + w_dst[i]) = rw[i];
     };
     gload(ra0, rw0, 0);
     lstore(ra0, rw0, smem);
@@ -139,30 +126,30 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmP p) {
     auto compute = [&](const char* cur) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            x3_u32x4 ah[TM], al[TM], wh[TN], wl[TN];
+            u32x4 ah[TM], al[TM], wh[TN], wl[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                ah[i] = *(const x3_u32x4*)(cur + fragA + i * 32 * X3_ROW + 32 * s);
-                al[i] = *(const x3_u32x4*)(cur + fragA + i * 32 * X3_ROW + 64 + 32 * s);
+                ah[i] = *(const u32x4*)(cur + fragA + i * 32 * X3_ROW + 32 * s);
+                al[i] = *(const u32x4*)(cur + fragA + i * 32 * X3_ROW + 64 + 32 * s);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                wh[j] = *(const x3_u32x4*)(cur + fragW + j * 32 * X3_ROW + 32 * s);
-                wl[j] = *(const x3_u32x4*)(cur + fragW + j * 32 * X3_ROW + 64 + 32 * s);
+                wh[j] = *(const u32x4*)(cur + fragW + j * 32 * X3_ROW + 32 * s);
+                wl[j] = *(const u32x4*)(cur + fragW + j * 32 * X3_ROW + 64 + 32 * s);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    const x3_bf16x8 a_h = __builtin_bit_cast(x3_bf16x8, ah[i]), a_l = __builtin_bit_cast(x3_bf16x8, al[i]);
-                    const x3_bf16x8 w_h = __builtin_bit_cast(x3_bf16x8, wh[j]), w_l = __builtin_bit_cast(x3_bf16x8, wl[j]);
+                    const bf16x8 a_h = __builtin_bit_cast(bf16x8, ah[i]), a_l = __builtin_bit_cast(bf16x8, al[i]);
+                    const bf16x8 w_h = __builtin_bit_cast(bf16x8, wh[j]), w_l = __builtin_bit_cast(bf16x8, wl[j]);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_h, acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, w_l, acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, w_h, acc[i][j], 0, 0, 0);
                 }
         }
     };
-    auto step = [&](x3_u32x4* ra, x3_u32x4* rw, int kt) {
+    auto step = [&](u32x4* ra, u32x4* rw, int kt) {
         compute(smem + (kt & 1) * BUF);
         if (kt + 1 < nloc) lstore(ra, rw, smem + ((kt + 1) & 1) * BUF);
         __syncthreads();
@@ -174,7 +161,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmP p) {
     }
 
     // acc[i][j][reg]: row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), column lane & 31 of the 32x32 tile
-    if constexpr (EPI & X3_SPLITK) {
+    if constexpr (EPI & GE_SPLITK) {
         float* slab = p.ws + (long long)blockIdx.y * p.M * p.N;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -237,7 +224,7 @@ static int x3_launch_epi(const GemmP& p, hipStream_t st) {
     }
     M3PC_GEMM_PICK(12, S, 0, 0);
     if (S > 1) {
-        x3_launch<64, 64, X3_SPLITK>(p, S, st);
+        x3_launch<64, 64, GE_SPLITK>(p, S, st);
         return launch_splitk_reduce(p, S, 1, st);
     }
     x3_launch<64, 64, EPI>(p, 1, st);
@@ -249,8 +236,7 @@ int launch_gemm_x3(const GemmP& p, hipStream_t st) {
     if (p.M <= 0) return 0;
     if (p.K % 32 != 0 || p.N % 64 != 0 || p.w_lo_off <= 0 || p.w_lo_off % 8 != 0 || (p.Cf == nullptr) == (p.Cb == nullptr)) return -1;
     if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15) || p.lda % 4 != 0 || p.ldw % 8 != 0 || p.a_ln_g) return -1;
-    const int epi = (p.gelu ? GE_GELU | GE_GELU_EXACT : 0) | (p.res ? GE_RES : 0) | (p.rowtab ? GE_ROWTAB : 0) |
-                    (p.Cf ? GE_F32OUT : 0);
+    const int epi = epi_flags(p) | (p.gelu ? GE_GELU_EXACT : 0);
     switch (epi) {
         case GE_F32OUT: return x3_launch_epi<GE_F32OUT>(p, st);
         case GE_GELU | GE_GELU_EXACT | GE_F32OUT: return x3_launch_epi<GE_GELU | GE_GELU_EXACT | GE_F32OUT>(p, st);

@@ -15,13 +15,12 @@
 // owns one data row (lane & 31) and accumulator i is output unit 8 (i / 4) + 4 (lane >> 5) + i % 4 of the tile.  Activations live in
 // global memory as (pass, row, unit); rows beyond the batch in the last 32-row tile carry zero inputs and zero deltas, so they add
 // exact zeros to every gradient.  iql.h states the arithmetic (the Adam order, what is fp64).
+#include "device_util.h"
 #include "iql.h"
 
 namespace m3pc {
 namespace {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x16v __attribute__((ext_vector_type(16)));
 constexpr int IQL_MAX_BATCH = 1024, IQL_PASSES = 7, IQL_OUTW = 32, IQL_NETS = 4;
 constexpr int NET_V = 0, NET_Q1 = 1, NET_Q2 = 2, NET_ACTOR = 3, NET_Q1T = 4, NET_Q2T = 5;
 
@@ -83,10 +82,10 @@ __global__ __launch_bounds__(256) void iql_fwd1_kernel(IqlP p) {
     if (f >= p.npass) return;
     const NetP n = p.net[p.pass_net[f]];
     const int row = 32 * rt + l31, m = 32 * ht + l31;
-    f32x16v acc;
+    f32x16 acc;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const f32x4v b = *(const f32x4v*)(n.b1 + 32 * ht + 8 * q + 4 * lh);
+        const f32x4 b = *(const f32x4*)(n.b1 + 32 * ht + 8 * q + 4 * lh);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[4 * q + i] = b[i];
     }
@@ -105,10 +104,10 @@ __global__ __launch_bounds__(256) void iql_fwd1_kernel(IqlP p) {
     float* o = p.h1 + ((size_t)f * p.Bp + row) * p.H + 32 * ht + 4 * lh;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        f32x4v v;
+        f32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(acc[4 * q + i], 0.f);
-        *(f32x4v*)(o + 8 * q) = v;
+        *(f32x4*)(o + 8 * q) = v;
     }
 }
 
@@ -121,21 +120,21 @@ __global__ __launch_bounds__(256) void iql_fwd2_kernel(IqlP p) {
     if (f >= p.npass) return;
     const NetP n = p.net[p.pass_net[f]];
     const int row = 32 * rt + l31, m = 32 * ht + l31, H = p.H;
-    f32x16v acc;
+    f32x16 acc;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const f32x4v b = *(const f32x4v*)(n.b2 + 32 * ht + 8 * q + 4 * lh);
+        const f32x4 b = *(const f32x4*)(n.b2 + 32 * ht + 8 * q + 4 * lh);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[4 * q + i] = b[i];
     }
     const float* ap = n.W2 + (size_t)m * H + 4 * lh;
     const float* bp = p.h1 + ((size_t)f * p.Bp + row) * H + 4 * lh;
     for (int g0 = 0; g0 < H / 8; g0 += 4) {  // (hidden / 8 is a multiple of 4: four groups are loaded ahead of their MFMAs)
-        f32x4v a[4], b[4];
+        f32x4 a[4], b[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            a[u] = *(const f32x4v*)(ap + 8 * (g0 + u));
-            b[u] = *(const f32x4v*)(bp + 8 * (g0 + u));
+            a[u] = *(const f32x4*)(ap + 8 * (g0 + u));
+            b[u] = *(const f32x4*)(bp + 8 * (g0 + u));
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -145,10 +144,10 @@ __global__ __launch_bounds__(256) void iql_fwd2_kernel(IqlP p) {
     float* o = p.h2 + ((size_t)f * p.Bp + row) * H + 32 * ht + 4 * lh;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        f32x4v v;
+        f32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(acc[4 * q + i], 0.f);
-        *(f32x4v*)(o + 8 * q) = v;
+        *(f32x4*)(o + 8 * q) = v;
     }
 }
 
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(256) void iql_fwd3_kernel(IqlP p) {
     const int ni = p.pass_net[f];
     const NetP n = p.net[ni];
     const int row = 32 * rt + l31, H = p.H;
-    f32x16v acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int o = 8 * (i / 4) + 4 * lh + i % 4;
@@ -171,11 +170,11 @@ __global__ __launch_bounds__(256) void iql_fwd3_kernel(IqlP p) {
     const float* ap = n.W3 + (size_t)(on ? l31 : 0) * H + 4 * lh;
     const float* bp = p.h2 + ((size_t)f * p.Bp + row) * H + 4 * lh;
     for (int g0 = 0; g0 < H / 8; g0 += 4) {
-        f32x4v a[4], b[4];
+        f32x4 a[4], b[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            a[u] = *(const f32x4v*)(ap + 8 * (g0 + u));
-            b[u] = *(const f32x4v*)(bp + 8 * (g0 + u));
+            a[u] = *(const f32x4*)(ap + 8 * (g0 + u));
+            b[u] = *(const f32x4*)(bp + 8 * (g0 + u));
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -185,16 +184,16 @@ __global__ __launch_bounds__(256) void iql_fwd3_kernel(IqlP p) {
     float* o = p.out + ((size_t)f * p.Bp + row) * IQL_OUTW + 4 * lh;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        f32x4v v;
+        f32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = ni == NET_ACTOR ? tanhf(acc[4 * q + i]) : acc[4 * q + i];
-        *(f32x4v*)(o + 8 * q) = v;
+        *(f32x4*)(o + 8 * q) = v;
     }
 }
 
 // the sum of one value per thread of a 1024-thread block, by a fixed tree: xor butterflies within a wavefront, then the sixteen
 // wavefront sums left to right.  Every thread returns the same bits.
-__device__ __forceinline__ float block_sum(float v, float* red) {
+__device__ __forceinline__ float iql_block_sum(float v, float* red) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -254,12 +253,12 @@ __global__ __launch_bounds__(IQL_MAX_BATCH) void iql_loss_kernel(IqlP p) {
             gls = inside ? wgt * (1.f - diff * diff * inv_var) : 0.f;
         }
         if (r < Bp) da[a] = dz;
-        const float g = block_sum(gls, red);
+        const float g = iql_block_sum(gls, red);
         if (r == a) my_g = g;
     }
     if (r < Bp)
         for (int a = p.A; a < IQL_OUTW; ++a) da[a] = 0.f;
-    const float sv = block_sum(vl, red), s1 = block_sum(q1l, red), s2 = block_sum(q2l, red), sa = block_sum(on ? ea * bc : 0.f, red);
+    const float sv = iql_block_sum(vl, red), s1 = iql_block_sum(q1l, red), s2 = iql_block_sum(q2l, red), sa = iql_block_sum(on ? ea * bc : 0.f, red);
     if (r == 0 && p.losses) {
         p.losses[0] = sv / (float)p.B;
         p.losses[1] = (s1 / (float)p.B + s2 / (float)p.B) * 0.5f;
@@ -282,11 +281,11 @@ __global__ __launch_bounds__(256) void iql_delta_kernel(IqlP p) {
     const int kmax = L == 2 ? n.out : H;
     const float* W = L == 2 ? n.W3 : n.W2;
     const float* bp = L == 2 ? p.d3 + ((size_t)t * p.Bp + row) * IQL_OUTW + 4 * lh : p.d2 + ((size_t)t * p.Bp + row) * H + 4 * lh;
-    f32x16v acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     for (int g = 0; g < K / 8; ++g) {
-        const f32x4v b = *(const f32x4v*)(bp + 8 * g);
+        const f32x4 b = *(const f32x4*)(bp + 8 * g);
         float a[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -300,11 +299,11 @@ __global__ __launch_bounds__(256) void iql_delta_kernel(IqlP p) {
     float* o = (L == 2 ? p.d2 : p.d1) + ((size_t)t * p.Bp + row) * H + 32 * ht + 4 * lh;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const f32x4v hv = *(const f32x4v*)(act + 8 * q);
-        f32x4v v;
+        const f32x4 hv = *(const f32x4*)(act + 8 * q);
+        f32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = hv[i] > 0.f ? acc[4 * q + i] : 0.f;
-        *(f32x4v*)(o + 8 * q) = v;
+        *(f32x4*)(o + 8 * q) = v;
     }
 }
 
@@ -346,7 +345,7 @@ __global__ __launch_bounds__(256) void iql_grad_kernel(IqlP p) {
     }
     const int col = 32 * nt + l31;
     const float* act = (layer == 2 ? p.h1 : p.h2) + (size_t)f * p.Bp * H;
-    f32x16v acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     const float* dp = delta + 32 * mt + l31;

@@ -3,44 +3,13 @@
 // the two launches below.  Reductions are 64-lane butterflies + one LDS hop summed in a fixed order, no atomics: a result does
 // not change from run to run.  m3pc_refine_plans runs the same steps for E lock-step windows: the *_batch kernels below take the window
 // as a grid index around the one-window device functions, and the batched resample forms the shifted first distribution.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace m3pc {
 namespace {
 
 constexpr int RF_THREADS = 256;  // refit: one workgroup per column
 constexpr int RF_HELD = 4;       // elite values a thread keeps in registers between the passes: all of them while k <= 1024
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float block_sum(float v, float* sv) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    v = wsum(v);
-    __syncthreads();
-    if (lane == 0) sv[wid] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sv[w];
-    return t;
-}
-__device__ __forceinline__ float block_max(float v, float* sv) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    v = wmax(v);
-    __syncthreads();
-    if (lane == 0) sv[wid] = v;
-    __syncthreads();
-    float t = sv[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = fmaxf(t, sv[w]);
-    return t;
-}
 
 // (an id outside [0, n) would read outside cand / scores: it is clamped, the caller's list is wrong either way)
 __device__ __forceinline__ int elite_id(const RefitP& p, int i) {

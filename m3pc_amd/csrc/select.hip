@@ -5,7 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "kernels.h"
+#include "device_util.h"
 #include "philox.h"
 
 namespace m3pc {
@@ -15,12 +15,6 @@ thread_local int g_sel_picked = 0;
 thread_local unsigned int g_sel_picked_set = 0;
 thread_local bool g_sel_force_fallback = false;
 #endif
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 struct ArgMax {
     float v;
@@ -46,17 +40,6 @@ __device__ __forceinline__ ArgMax block_argmax(ArgMax a, float* sv, int* si) {
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = better(r, ArgMax{sv[w], si[w]});
     return r;
 }
-__device__ __forceinline__ float block_sum(float v, float* sv) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    v = wsum(v);
-    __syncthreads();
-    if (lane == 0) sv[wid] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sv[w];
-    return t;
-}
-
 // p = exp(T (E - max E)) / sum;  eval = sum p a0 / sum p;  argmax E;  sample = argmax p / expo
 __device__ __forceinline__ void select_body(const SelectP& p, float* sv, int* si) {
     const int tid = threadIdx.x;
@@ -272,7 +255,6 @@ __device__ __forceinline__ void topk_rank_blocks_body(const float* v, int n, int
     const unsigned long long mine = e < n ? keys[e] : 0ull;
     const int n4 = (((n + 3) / 4) + 1) & ~1;  // keys per quarter, even (keys past n are 0: never greater than a real key)
     int rank = 0;
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     const int j0 = q * n4, j1 = j0 + n4 < 2048 ? j0 + n4 : 2048;
 #pragma unroll 8
     for (int j = j0; j < j1; j += 2) {
@@ -310,7 +292,6 @@ __global__ __launch_bounds__(256) void topk_rank_blocks2_kernel(TopSrc s0, TopSr
     const unsigned long long mine = e < n ? keys[e] : 0ull;
     const int n4 = (((n + 3) / 4) + 1) & ~1;
     int rank = 0;
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     const int j0 = q * n4, j1 = j0 + n4 < 2048 ? j0 + n4 : 2048;
 #pragma unroll 8
     for (int j = j0; j < j1; j += 2) {
@@ -339,7 +320,6 @@ __device__ __forceinline__ void rank_blocks_dyn_body(const TopSrc& s, int n, int
     const int e = blockIdx.x * 64 + lane;
     const unsigned long long mine = e < n ? dkeys[e] : 0ull;
     int rank = 0;
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     const int j0 = q * n4, j1 = j0 + n4;
 #pragma unroll 8
     for (int j = j0; j < j1; j += 2) {
@@ -390,7 +370,6 @@ __global__ __launch_bounds__(1024) void topk_rank_kernel(const float* v, int n, 
     __syncthreads();
     const int n2 = (n + 1) & ~1;  // (keys past n are 0: never greater than a real key)
     int rank0 = 0, rank1 = 0;
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     if (n <= 1024) {
 #pragma unroll 8
         for (int j = 0; j < n2; j += 2) {

@@ -28,7 +28,7 @@ gemm_f32_direct.hip, gemm_epilogue.h); each later term is taken on |reference va
   GELU           E = L E + G(pre) with L = 1.13 >= max |gelu'| (1.1289 at x = sqrt 2) and G the error of the kernel's formula
       fp32 / split-bf16 operands (0.5 x (1 + erff(x / sqrt 2))): G = 12 u |x| -- erff within 16 ulp (the OpenCL bound; <= 16 u on
       |erf| <= 1, times |x| / 2), the rounded argument 0.24 u |x|, the rounding of 1 + erf u |x|, two multiplications 2 u |x|.
-      bf16 operands (gelu_fast / ge_gelu: Abramowitz-Stegun 7.1.26 on v_rcp_f32 and v_exp_f32):
+      bf16 operands (gelu_fast: Abramowitz-Stegun 7.1.26 on v_rcp_f32 and v_exp_f32):
       G = |x| / 2 (AS_ERR + 16 u) + u |gelu(x)| -- AS_ERR = 1.5e-7 is the polynomial's stated error on erf (gelu_fast_f64 over
       gelu_grid(): 1.4e-7 measured, see test_gemm_ref_cpu.py::test_gelu_fast_formula_error), and 16 u is the stated allowance for
       what a CPU cannot measure: 1 ulp each for the hardware rcp and exp2, the rounded exponent argument (<= 0.37 * 3 u on p e)
@@ -99,7 +99,7 @@ def gelu64(x):
 
 
 def gelu_fast_f64(x):
-    """The formula of gelu_fast (gemm.hip) / ge_gelu (gemm_epilogue.h) in float64: what the polynomial alone costs."""
+    """The formula of gelu_fast (device_util.h) in float64: what the polynomial alone costs."""
     ax = x.abs() * 0.70710678118654752440
     t = 1.0 / (0.3275911 * ax + 1.0)
     p = t * 1.061405429 - 1.453152027
