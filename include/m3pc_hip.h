@@ -26,8 +26,8 @@
  * call: replay_buffer.py:204-232, learner.py:645-741) may keep several plan steps in flight: each step
  * owns one of M3PC_SLOTS step slots (m3pc_plan_args::slot: the policy head and returns tokens of its
  * policy pass), and the handle holds three workspaces -- the candidate workspace (m3pc_candidate_pass,
- * m3pc_plan_step_batch's candidate pass, m3pc_forward, m3pc_score_actions of more than max_rescore
- * candidates or in bf16), the policy workspace (m3pc_policy_pass, m3pc_plan_step_batch's policy pass) and
+ * m3pc_plan_step_batch's candidate pass, m3pc_forward, m3pc_mtm_loss and m3pc_mtm_loss_replay (their forward), m3pc_score_actions of
+ * more than max_rescore candidates or in bf16), the policy workspace (m3pc_policy_pass, m3pc_plan_step_batch's policy pass) and
  * the re-score workspace (m3pc_rescore* / fp32 m3pc_score_actions of <= max_rescore candidates).  Calls
  * that use the SAME workspace must be ordered on the device (same stream, or events); calls on different
  * workspaces may run on different streams at
@@ -52,7 +52,8 @@ extern "C" {
  * _record / _windows / _values / _export and the opaque m3pc_episodes (the episode store); then m3pc_replay_create / _destroy / _append /
  * _append_transitions / _push_episodes / _sample_segments / _sample_transitions / _values_up_bound / _counts / _path_lengths and the
  * opaque m3pc_replay (the replay buffer); then m3pc_iql_create / _destroy / _load / _export / _set_step / _get_step / _train_step / _train /
- * _publish_critic / _evaluate, m3pc_iql_args and the opaque m3pc_iql (the IQL trainer).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * _publish_critic / _evaluate, m3pc_iql_args and the opaque m3pc_iql (the IQL trainer); then m3pc_mtm_loss_terms, m3pc_mtm_loss and
+ * m3pc_mtm_loss_replay (the masked-trajectory loss).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -1022,6 +1023,59 @@ int m3pc_iql_train(m3pc_iql* iql, const m3pc_iql_args* args, m3pc_replay* rb, in
 int m3pc_iql_publish_critic(m3pc_iql* iql, m3pc_handle* h, void* stream);
 /* states (rows, S), actions (rows, A; unused, may be NULL, for M3PC_IQL_V and _ACTOR_MEAN) device -> out (rows,) or (rows, A) device. */
 int m3pc_iql_evaluate(m3pc_iql* iql, int which, const float* states, const float* actions, int rows, float* out, void* stream);
+
+/* THE MASKED-TRAJECTORY LOSS: the forward half of Learner.compute_mtm_loss (finetune_omtm/learner.py:419-504; what mtm_update trains on,
+ * :506-538, and what finetune.py:346-370 logs as eval/loss*) and of omtm.forward_loss (omtm/models/mtm_model.py:440-532), for one token
+ * per timestep and modality and continuous heads.  Per call, with m_k the (T,) mask of key k (1 = visible to the encoder), n_vis its
+ * sum, raw = (pred - target)^2 per element:
+ *   targets      the tokenised batch; with M3PC_MTM_NORM_L2 the target row of every key but the actions is divided by its l2 norm
+ *                (mtm_model.py:481-482; for the two scalar keys that is t / |t|: the sign, NaN at 0)
+ *   per key k != actions:   loss_k = mean of raw;  masked_c_loss_k = sum over b, t, d of raw m / n_vis / B;  masked_loss_k = the same with
+ *                1 - m and T - n_vis.  The divisor is the token count alone, as in the reference; a zero count divides as IEEE does.
+ *   actions      loss = mean over (b, t, a) of (tanh(mu) - target)^2 m_t; no masked variants
+ *   likelihood   a = the target actions, clipped to [(float)(-1 + 1e-6), (float)(1 - 1e-6)] with M3PC_MTM_CLIP_ACTIONS (learner.py:490);
+ *                z = 0.5 (log1p(a) - log1p(-a));  lp = Normal(mu, std).log_prob(z) - 2 (log 2 - z - softplus(-2 z));
+ *                log_likelihood = mean of lp over b, the timesteps whose action mask is 0, and a (a MEAN over the action dimension: the
+ *                reference's sum(axis=2) runs over the length-1 token axis); NaN when no timestep is hidden
+ *   entropy      u = mu + std eps;  lq = Normal(mu, std).log_prob(u) - 2 (log 2 - u - softplus(-2 u));  entropy = mean of -lq over the same set
+ *   total        = sum of loss_k over the keys whose bit (1 << M3PC_STATES ...) is set in loss_keys, minus (log_likelihood + entropy_reg entropy)
+ * The two reference forms are two settings: fine-tuning (learner.py:419-504) is flags = M3PC_MTM_CLIP_ACTIONS with loss_keys = the keys up
+ * to and including the first key that is not the actions in the batch's key order -- its lines 488-504 sit INSIDE the key loop, so it
+ * returns after `states` for the order traj_sample produces: loss_keys = 1; pretraining (mtm_model.py:440-532, norm "l2", loss_keys None)
+ * is flags = M3PC_MTM_NORM_L2 with loss_keys = 15.  All twelve per-key numbers are computed either way.
+ *   record       device out, M3PC_MTM_LOSS_FLOATS floats: [3 k] loss_k, [3 k + 1] masked_loss_k, [3 k + 2] masked_c_loss_k for k = M3PC_STATES,
+ *                _ACTIONS, _REWARDS, _RETURNS ([4] and [5], which have no meaning, are 0); [12] entropy; [13] nll = -log_likelihood; [14] total
+ *   masks        host, four (T,) arrays of 0/1 bytes, as m3pc_forward;  eps device (batch, T, A) standard normals;  entropy_reg = exp(log_temperature)
+ * Elementwise terms are fp32 in the reference's operation order; every sum is float64 in a fixed tree (per-row sums to a scratch block, then
+ * one workgroup), no atomics: a call is bit-identical from run to run and does not depend on rows beyond `batch`.  Two launches behind the
+ * forward's (m3pc_amd/csrc/mtm_loss.h).  Stream-ordered; no entry point waits for the device (the first call allocates the scratch).
+ * Refused with M3PC_EINVAL before any HIP call: null required pointers; batch outside [1, max_batch]; a mask byte other than 0 / 1; unknown
+ * flag bits; loss_keys outside [0, 15]; a precision that is none; a replay buffer whose S, A, device or segment_length != T do not fit the
+ * handle; the refusals of m3pc_replay_sample_segments.  Refused with M3PC_ESTATE: weights or tokenizers not loaded (m3pc_mtm_loss, _replay). */
+#define M3PC_MTM_LOSS_FLOATS 15
+#define M3PC_MTM_NORM_L2 1        /* mtm_model.py:481-482 */
+#define M3PC_MTM_CLIP_ACTIONS 2   /* learner.py:490 */
+/* The loss on caller-supplied predictions -- pred_states (batch, T, S), pred_rewards / pred_returns (batch, T, 1), mu / std (batch, T, A):
+ * what m3pc_forward writes -- and tokenised targets[k] (batch, T, D_k), all device.  Needs no weights. */
+int m3pc_mtm_loss_terms(m3pc_handle* h, int batch, const float* pred_states, const float* pred_rewards, const float* pred_returns,
+                        const float* mu, const float* std, const float* const targets[4], const unsigned char* const masks[4],
+                        const float* eps, float entropy_reg, int flags, int loss_keys, float* record, void* stream);
+/* One call on a RAW batch -- states (batch, T, S), actions (batch, T, A), rewards (batch, T, 1) float32, returns (batch, T, 1) float32 or,
+ * with returns_f64, float64: what m3pc_replay_sample_segments writes: m3pc_tokenize of the four, omtm.forward under the masks in
+ * `precision` (m3pc_forward; in the candidate workspace, which it leaves as m3pc_forward does), then the loss on its heads.  out_*,
+ * optional device out: the five head outputs, shaped as m3pc_forward's. */
+int m3pc_mtm_loss(m3pc_handle* h, int batch, const float* states, const float* actions, const float* rewards, const void* returns,
+                  int returns_f64, const unsigned char* const masks[4], const float* eps, float entropy_reg, int flags, int loss_keys,
+                  int precision, float* record, float* out_states, float* out_rewards, float* out_returns, float* out_mu, float* out_std,
+                  void* stream);
+/* The same on the batch the buffer draws at (seed, step, mode), or at the caller's indices: batch ... step, out_traj and out_start are the
+ * arguments of m3pc_replay_sample_segments, with its semantics; the rows are gathered into the handle's scratch (returns float64) and never
+ * cross the host.  eps: device (batch, T, A), or NULL: array 0 of the generator of m3pc_draw_variates at the same (seed, step), elements
+ * [0, batch T A).  rb was created on this handle's sizes with segment_length == T. */
+int m3pc_mtm_loss_replay(m3pc_handle* h, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
+                         int index_on_device, unsigned long long seed, unsigned long long step, const unsigned char* const masks[4],
+                         const float* eps, float entropy_reg, int flags, int loss_keys, int precision, float* record, int* out_traj,
+                         int* out_start, void* stream);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

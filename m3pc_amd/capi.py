@@ -57,6 +57,7 @@ EXPORTS = (
     "m3pc_replay_path_lengths",
     "m3pc_iql_create", "m3pc_iql_destroy", "m3pc_iql_load", "m3pc_iql_export", "m3pc_iql_set_step", "m3pc_iql_get_step",
     "m3pc_iql_train_step", "m3pc_iql_train", "m3pc_iql_publish_critic", "m3pc_iql_evaluate",
+    "m3pc_mtm_loss_terms", "m3pc_mtm_loss", "m3pc_mtm_loss_replay",
 )
 
 
@@ -123,6 +124,10 @@ REPLAY_OFFLINE, REPLAY_ONLINE = 0, 1  # M3PC_REPLAY_*: the two transition rings
 (IQL_QF, IQL_Q_TARGET, IQL_VF, IQL_ACTOR, IQL_QF_ADAM_M, IQL_QF_ADAM_V, IQL_VF_ADAM_M, IQL_VF_ADAM_V, IQL_ACTOR_ADAM_M,
  IQL_ACTOR_ADAM_V) = range(10)
 IQL_Q_MIN, IQL_Q_TARGET_MIN, IQL_V, IQL_ACTOR_MEAN = range(4)
+# the masked-trajectory loss (m3pc_mtm_loss*): the record's length, the flags, and the two reference forms as (flags, loss_keys)
+MTM_LOSS_FLOATS = 15
+MTM_NORM_L2, MTM_CLIP_ACTIONS = 1, 2
+MTM_ENTROPY, MTM_NLL, MTM_TOTAL = 12, 13, 14  # record slots behind the 4 x (loss, masked_loss, masked_c_loss)
 
 
 class M3pcError(RuntimeError):
@@ -224,6 +229,9 @@ def load_library(path: Optional[str] = None):
         "m3pc_iql_train": [vp, C.POINTER(IqlArgs), vp, i, i, i, C.c_ulonglong, C.c_ulonglong, vp, vp],
         "m3pc_iql_publish_critic": [vp, vp, vp],
         "m3pc_iql_evaluate": [vp, i, vp, vp, i, vp, vp],
+        "m3pc_mtm_loss_terms": [vp, i, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, f, i, i, vp, vp],
+        "m3pc_mtm_loss": [vp, i, vp, vp, vp, vp, i, C.POINTER(vp), vp, f, i, i, i, vp, vp, vp, vp, vp, vp, vp],
+        "m3pc_mtm_loss_replay": [vp, vp, i, i, vp, vp, i, C.c_ulonglong, C.c_ulonglong, C.POINTER(vp), vp, f, i, i, i, vp, vp, vp, vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }
@@ -411,6 +419,39 @@ class Handle:
         mb = [bytes(bytearray(int(v != 0) for v in m)) for m in masks]
         mbuf = [C.create_string_buffer(b, len(b)) for b in mb]
         return (C.c_void_p * 4)(*[C.addressof(b) for b in mbuf]), mbuf
+
+    # -- the masked-trajectory loss ------------------------------------------------------------------
+    def mtm_loss_terms(self, preds, targets, masks, eps, entropy_reg: float, flags: int, loss_keys: int, batch: Optional[int] = None,
+                       record: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """m3pc_mtm_loss_terms: preds = (states, rewards, returns, mu, std) and the four tokenised targets, (B,T,D) fp32 cuda; masks:
+        four (T,) 0/1 rows; eps (B,T,A).  Returns the device record (``MTM_LOSS_FLOATS`` floats); nothing is read back."""
+        p = [self._f32(t) for t in preds]
+        tg = [self._f32(t) for t in targets]
+        e = self._f32(eps)
+        B = int(p[0].shape[0] if batch is None else batch)
+        rec = torch.empty(MTM_LOSS_FLOATS, dtype=torch.float32, device=self.device) if record is None else record
+        tp = (C.c_void_p * 4)(*[t.data_ptr() for t in tg])
+        mp, keep = self._mask_ptrs(masks)
+        check(self.lib.m3pc_mtm_loss_terms(self._h, B, *[_ptr(t) for t in p], tp, mp, _ptr(e), float(entropy_reg), int(flags), int(loss_keys),
+                                           _ptr(rec), _stream(self.device)))
+        return rec
+
+    def mtm_loss(self, states, actions, rewards, returns, masks, eps, entropy_reg: float, flags: int, loss_keys: int,
+                 precision: int = PREC_FP32, want_heads: bool = False):
+        """m3pc_mtm_loss on a raw batch (returns float32 or float64): tokenise, forward under the masks, the loss.  Returns the device
+        record, and with ``want_heads`` the five head outputs (states, rewards, returns, mu, std) behind it."""
+        s, a, r = (self._f32(t) for t in (states, actions, rewards))
+        v = returns.contiguous() if returns.dtype == torch.float64 else self._f32(returns)
+        e = self._f32(eps)
+        B = int(s.shape[0])
+        f32 = dict(dtype=torch.float32, device=self.device)
+        rec = torch.empty(MTM_LOSS_FLOATS, **f32)
+        heads = [torch.empty((B, self.T, w), **f32) for w in (self.S, 1, 1, self.A, self.A)] if want_heads else [None] * 5
+        mp, keep = self._mask_ptrs(masks)
+        check(self.lib.m3pc_mtm_loss(self._h, B, _ptr(s), _ptr(a), _ptr(r), _ptr(v), int(v.dtype == torch.float64), mp, _ptr(e),
+                                     float(entropy_reg), int(flags), int(loss_keys), int(precision), _ptr(rec), *[_ptr(t) for t in heads],
+                                     _stream(self.device)))
+        return (rec, heads) if want_heads else rec
 
     def goal_step(self, states, actions, rewards, rtg, masks_pi, masks_fid, idx: int):
         """Both forwards of the zero-shot piid call on raw windows: states (E,T,S), actions (E,T,A), rewards (E,T,1) fp32 cuda,

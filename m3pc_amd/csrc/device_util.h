@@ -45,6 +45,22 @@ __device__ __forceinline__ float block_sum(float v, float* sv) {
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sv[w];
     return t;
 }
+// the same two in float64 (mtm_loss.hip: every sum of a loss term): the same butterfly and the same left-to-right combination
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double block_sum_f64(double v, double* sv) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    v = wave_sum_f64(v);
+    __syncthreads();
+    if (lane == 0) sv[wid] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sv[w];
+    return t;
+}
 __device__ __forceinline__ float block_max(float v, float* sv) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     v = wave_max(v);

@@ -12,6 +12,7 @@
 // depend on the candidate, so only the 2h scored tokens are pushed through out-proj/FFN/heads and only the
 // un-masked tokens through the K/V projection.
 #include "m3pc_internal.h"
+#include "mtm_loss.h"
 
 namespace m3pc {
 thread_local char g_err[512] = "";
@@ -226,6 +227,7 @@ int m3pc_destroy(m3pc_handle* h) {
         hipFree(h->tok_std[k]);
     }
     hipFree(h->mask_tokens);
+    mtm_loss_free(h);
     free_ws(h->base);
     for (int par = 0; par < 2; ++par) {
         free_ws(h->chain[par]);

@@ -291,6 +291,14 @@ struct m3pc_handle {
     bool prof_serial = false;     // m3pc_profile_enable(h, 2): the candidate halves run one after the other on the caller's stream
     std::vector<EventPair> ev;
     size_t ev_used = 0;
+    // m3pc_mtm_loss* (mtm_loss.hip), sized by max_batch and allocated by the first of those calls: the tokenised batch, the five head
+    // outputs (states, rewards, returns, mu, std), the raw batch and the normals of a replay draw, and the per-row partial sums
+    struct MtmLoss {
+        bool ready = false;
+        float *tok[4] = {nullptr, nullptr, nullptr, nullptr}, *head[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        float *raw[3] = {nullptr, nullptr, nullptr}, *eps = nullptr;
+        double *raw_returns = nullptr, *part = nullptr;
+    } ml;
 };
 
 namespace m3pc {

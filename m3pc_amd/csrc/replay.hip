@@ -7,6 +7,7 @@
 // (philox.h), so tests/replay_ref.py restates them bit for bit.  The host half mirrors counts, ring heads and path lengths -- the host
 // makes every call that changes one -- so that no call reads the device.
 #include "episodes.h"
+#include "mtm_loss.h"
 #include "philox.h"
 
 namespace m3pc {
@@ -291,6 +292,27 @@ void replay_sizes(const m3pc_replay* rb, int* S, int* A, int* device) {
     *A = rb->A;
     *device = rb->device;
 }
+// (mtm_loss.h)
+int replay_segment_length(const m3pc_replay* rb) { return rb->L; }
+int replay_check_segments(m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
+                          const char* who) {
+    if ((traj_index == nullptr) != (start_index == nullptr))
+        return fail(M3PC_EINVAL, "%s: traj_index and start_index come together (one of them is null)", who);
+    if (batch < 1) return fail(M3PC_EINVAL, "%s: batch %d < 1", who, batch);
+    if (mode != M3PC_REPLAY_UNIFORM && mode != M3PC_REPLAY_LENGTH)
+        return fail(M3PC_EINVAL, "%s: mode %d is neither M3PC_REPLAY_UNIFORM nor M3PC_REPLAY_LENGTH", who, mode);
+    if (rb->count == 0) return fail(M3PC_ESTATE, "%s: the buffer holds no trajectory", who);
+    if (traj_index && !index_on_device)
+        for (int j = 0; j < batch; ++j) {
+            if (traj_index[j] < 0 || traj_index[j] >= rb->count)
+                return fail(M3PC_EINVAL, "%s: traj_index[%d] = %d outside [0, count=%d)", who, j, traj_index[j], rb->count);
+            const int len = rb->lens[(size_t)((rb->head + traj_index[j]) % rb->C)];
+            if (start_index[j] < 0 || start_index[j] > len - rb->L)
+                return fail(M3PC_EINVAL, "%s: start_index[%d] = %d outside [0, path_length - segment_length = %d]", who, j, start_index[j],
+                            len - rb->L);
+        }
+    return 0;
+}
 }  // namespace m3pc
 
 namespace {
@@ -548,21 +570,7 @@ int m3pc_replay_sample_segments(m3pc_replay* rb, int batch, int mode, const int*
                                 unsigned long long seed, unsigned long long step, float* states, float* actions, float* rewards, void* returns,
                                 int returns_f32, int* out_traj, int* out_start, void* stream) {
     if (!rb || !states || !actions || !rewards || !returns) return fail(M3PC_EINVAL, "null argument");
-    if ((traj_index == nullptr) != (start_index == nullptr))
-        return fail(M3PC_EINVAL, "m3pc_replay_sample_segments: traj_index and start_index come together (one of them is null)");
-    if (batch < 1) return fail(M3PC_EINVAL, "m3pc_replay_sample_segments: batch %d < 1", batch);
-    if (mode != M3PC_REPLAY_UNIFORM && mode != M3PC_REPLAY_LENGTH)
-        return fail(M3PC_EINVAL, "m3pc_replay_sample_segments: mode %d is neither M3PC_REPLAY_UNIFORM nor M3PC_REPLAY_LENGTH", mode);
-    if (rb->count == 0) return fail(M3PC_ESTATE, "m3pc_replay_sample_segments: the buffer holds no trajectory");
-    if (traj_index && !index_on_device)
-        for (int j = 0; j < batch; ++j) {
-            if (traj_index[j] < 0 || traj_index[j] >= rb->count)
-                return fail(M3PC_EINVAL, "m3pc_replay_sample_segments: traj_index[%d] = %d outside [0, count=%d)", j, traj_index[j], rb->count);
-            const int len = rb->lens[(size_t)((rb->head + traj_index[j]) % rb->C)];
-            if (start_index[j] < 0 || start_index[j] > len - rb->L)
-                return fail(M3PC_EINVAL, "m3pc_replay_sample_segments: start_index[%d] = %d outside [0, path_length - segment_length = %d]", j,
-                            start_index[j], len - rb->L);
-        }
+    CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, "m3pc_replay_sample_segments"));
     hipStream_t st = (hipStream_t)stream;
     CHK(rb_ensure(rb));
     const void *ti = traj_index, *si = start_index;

@@ -5,6 +5,7 @@ states, actions, rewards, returns.  The HIP library consumes them as 0/1 byte ro
 """
 from __future__ import annotations
 
+from collections.abc import Sequence
 from typing import Dict
 
 import numpy as np
@@ -61,6 +62,35 @@ def create_gid_mask(traj_length: int, device, idx: int):
 def create_pi_mask(traj_length: int, device, idx: int):
     """Path inference mask; identical rows to gid (zeroshot masks.py:72-91)."""
     return create_gid_mask(traj_length, device, idx)
+
+
+def create_random_autoregressive_mask(data_shapes, mask_ratios, traj_length, p_weights=(0, 0, 0.7, 0.3), rnd=None, device="cpu"):
+    """The training mask of finetune_omtm/masks.py:64-125 (``create_random_autoregressize_mask``): the same NumPy calls in the same
+    order -- ``choice(p=)`` of the mode, ``randint`` of the position, then per key of data_shapes ``choice(mask_ratios)`` (only when
+    mask_ratios is a sequence) and ``shuffle`` -- so that under the same ``np.random.seed`` (or the same ``rnd`` RandomState) the
+    masks are the reference's, bit for bit.  Returns {key: float64 tensor (T, P)} in the order of data_shapes."""
+    r = np.random if rnd is None else rnd
+    modes = ["states", "returns", "actions", "rewards"]
+    mode = r.choice(modes, p=p_weights)
+    position = r.randint(0, traj_length)
+    rows = {}
+    for k, shape in data_shapes.items():
+        P = shape[0]
+        ratio = r.choice(mask_ratios) if isinstance(mask_ratios, Sequence) else mask_ratios
+        n = int(traj_length * P * float(ratio))
+        m = np.concatenate([np.ones(n), np.zeros(traj_length * P - n)])
+        r.shuffle(m)
+        rows[k] = m.reshape(traj_length, P)
+    # nothing of the future: the modes in front of the drawn one keep the token at the position, the drawn one and those behind it do not
+    cut = position + 1
+    for k in modes:
+        if k == mode:
+            cut = position
+        if k in rows:
+            rows[k][cut:, :] = 0
+    if (rows["actions"] == 1).all():
+        rows["actions"][-1] = 0
+    return {k: torch.from_numpy(v).to(device) for k, v in rows.items()}
 
 
 def mask_rows(masks) -> list:

@@ -1,6 +1,7 @@
 """Host-side mirror of the reference model interface (research/omtm/models/mtm_model.py:200-221,
-324-437, 593-607): ``omtmConfig.create(data_shapes, traj_length, discrete_map) -> omtm`` and
-``omtm.forward(trajectories, masks)``.  The transformer itself lives in libm3pc_hip.so.
+324-437, 440-532, 593-607): ``omtmConfig.create(data_shapes, traj_length, discrete_map) -> omtm``,
+``omtm.forward(trajectories, masks)`` and ``omtm.forward_loss(targets, preds, masks, ...)``.  The transformer
+and the loss live in libm3pc_hip.so; the backward pass and the optimizers do not exist here.
 """
 from __future__ import annotations
 
@@ -14,6 +15,67 @@ from .masks import mask_rows
 from .tokenizers import SquashedNormal
 
 KEYS = capi.KEYS
+FORMS = ("finetune", "pretrain")
+
+
+def early_return_keys(order) -> List[str]:
+    """The keys Learner.compute_mtm_loss (finetune_omtm/learner.py:443-504) has in its dicts when it returns: its last lines sit
+    inside the key loop, so it stops behind the first key that is not "actions" (which ``continue``s)."""
+    out = []
+    for k in order:
+        out.append(k)
+        if k != "actions":
+            break
+    return out
+
+
+def key_bits(keys) -> int:
+    """The 4-bit ``loss_keys`` mask of m3pc_mtm_loss*."""
+    return sum(1 << KEYS.index(k) for k in set(keys))
+
+
+def loss_tuple(record: torch.Tensor, dict_keys):
+    """The reference's 5-tuple (loss, losses, masked_losses, masked_c_losses, entropy) out of a device record, as 0-d views of it:
+    ``losses`` holds dict_keys in their order, then "entropy" and "nll"; the masked dicts hold dict_keys without "actions"."""
+    losses, masked, masked_c = {}, {}, {}
+    for k in dict_keys:
+        i = 3 * KEYS.index(k)
+        losses[k] = record[i]
+        if k != "actions":
+            masked[k] = record[i + 1]
+            masked_c[k] = record[i + 2]
+    losses["entropy"] = record[capi.MTM_ENTROPY]
+    losses["nll"] = record[capi.MTM_NLL]
+    return record[capi.MTM_TOTAL], losses, masked, masked_c, record[capi.MTM_ENTROPY]
+
+
+def form_settings(form: str, order):
+    """(flags, loss_keys bits, the keys of the returned dicts) of a reference form for a batch in key order ``order``: "finetune" is
+    Learner.compute_mtm_loss (clip, no norm, the early return), "pretrain" omtm.forward_loss(norm="l2", loss_keys=None)."""
+    if form == "finetune":
+        keys = early_return_keys(order)
+        return capi.MTM_CLIP_ACTIONS, key_bits(keys), keys
+    if form == "pretrain":
+        return capi.MTM_NORM_L2, key_bits(order), list(order)
+    raise ValueError(f"form must be one of {FORMS}, got {form!r}")
+
+
+def raw_batch_loss(handle, batch, masks, entropy_reg, form="finetune", eps=None, precision=capi.PREC_FP32, want_heads=False):
+    """m3pc_mtm_loss on a raw batch dict {key: (B,T,D)} (``traj_sample``'s) under ``masks`` -> the reference's 5-tuple of ``form``
+    (and the five head outputs with want_heads).  eps: (B,T,A) standard normals; None: torch.randn on the handle's device."""
+    order = list(batch.keys())
+    if sorted(order) != sorted(KEYS):
+        raise capi.M3pcError(f"the batch must hold exactly the keys {KEYS}")
+    flags, bits, keys = form_settings(form, order)
+    B = batch["states"].shape[0]
+    if eps is None:
+        eps = torch.randn((B, handle.T, handle.A), dtype=torch.float32, device=handle.device)
+    dev = [batch[k].to(handle.device) for k in KEYS]
+    out = handle.mtm_loss(*[t.reshape(B, handle.T, -1) for t in dev], mask_rows(masks), eps.reshape(B, handle.T, handle.A),
+                          float(entropy_reg), flags, bits, precision=precision, want_heads=want_heads)
+    if want_heads:
+        return loss_tuple(out[0], keys), out[1]
+    return loss_tuple(out, keys)
 
 
 @dataclasses.dataclass
@@ -44,7 +106,7 @@ class omtmConfig:
 
 
 class omtm:
-    """Inference-only masked trajectory model on one MI355X.
+    """Masked trajectory model on one MI355X: the forward pass and the training loss (no backward pass).
 
     ``data_shapes`` = {key: (tokens_per_timestep == 1, feature_dim)} (mtm_model.py:327-331).
     ``handle_kw`` sizes the device workspace: max_candidates, max_batch, critic_hidden, device.
@@ -110,3 +172,37 @@ class omtm:
         return res
 
     __call__ = forward
+
+    @torch.no_grad()
+    def forward_loss(self, targets: Dict[str, torch.Tensor], preds: Dict[str, object], masks, entropy_reg: float,
+                     discrete_map: Dict[str, bool], norm="l2", reduce_use_sum=False, loss_keys: Optional[List[str]] = None,
+                     eps: Optional[torch.Tensor] = None):
+        """mtm_model.py:440-532 on the device (m3pc_mtm_loss_terms): targets[k] (B,T,1,D_k) tokenised, preds as ``forward`` returns
+        them.  Returns the reference's (loss, losses, masked_losses, masked_c_losses, entropy), 0-d device tensors.  ``eps``: the
+        (B,T,A) standard normals of the sampled entropy (None: torch.randn).  norm: "l2", or anything else for none ("mae" changes
+        nothing in the reference either: its normalised target is never used)."""
+        if reduce_use_sum:
+            raise capi.M3pcError("reduce_use_sum is not used by any m3pc config and is not supported")
+        if any(discrete_map.get(k, False) for k in targets):
+            raise capi.M3pcError("discrete heads are not used by any m3pc config and are not supported")
+        order = list(targets.keys())
+        if sorted(order) != sorted(KEYS):
+            raise capi.M3pcError(f"targets must hold exactly the keys {KEYS}")
+        h = self.handle
+        B = targets["states"].shape[0]
+        tg = [targets[k].reshape(B, h.T, -1) for k in KEYS]
+        dist = preds["actions"]
+        pr = [preds["states"], preds["rewards"], preds["returns"], dist.loc, dist.std]
+        if eps is None:
+            eps = torch.randn((B, h.T, h.A), dtype=torch.float32, device=h.device)
+        rec = h.mtm_loss_terms([t.reshape(B, h.T, -1) for t in pr], tg, mask_rows(masks), eps.reshape(B, h.T, h.A), float(entropy_reg),
+                               capi.MTM_NORM_L2 if norm == "l2" else 0, key_bits(order if loss_keys is None else loss_keys))
+        return loss_tuple(rec, order)
+
+    @torch.no_grad()
+    def compute_loss(self, batch: Dict[str, torch.Tensor], masks, entropy_reg: float, form: str = "finetune",
+                     eps: Optional[torch.Tensor] = None):
+        """One call (m3pc_mtm_loss) on a RAW batch {key: (B,T,D_k)}: tokenise, ``forward`` under the masks, the loss of ``form`` --
+        "finetune": Learner.compute_mtm_loss (finetune_omtm/learner.py:419-504), "pretrain": ``forward_loss(norm="l2")``.  Needs the
+        handle's tokenizers (``handle.set_tokenizer``)."""
+        return raw_batch_loss(self.handle, batch, masks, entropy_reg, form, eps, self.precision)

@@ -1290,6 +1290,21 @@ class HipPlanner(GoalMixin, LockstepMixin):
             sample_action, eval_action = self.mtm_sampling(traj, h)
         return eval_action if eval else sample_action
 
+    @torch.no_grad()
+    def compute_mtm_loss(self, batch, data_shapes, discrete_map, entropy_reg, masks=None, eps=None):
+        """learner.py:419-504 in one library call (m3pc_mtm_loss): the raw ``traj_sample`` batch is tokenised, run through the model
+        under ``masks`` (None: drawn as the reference draws them, from NumPy's global generator) and scored.  Returns the
+        reference's (loss, losses, masked_losses, masked_c_losses, entropy) with its dict contents -- "states", "entropy", "nll"
+        for the usual key order (the reference returns from inside its key loop) -- as 0-d device tensors.  eps: the (B,T,A) normals
+        of the sampled entropy (None: torch.randn).  Forward only: there is no backward pass to call on the result."""
+        from .masks import create_random_autoregressive_mask
+        from .mtm import raw_batch_loss
+        if any(discrete_map.get(k, False) for k in batch):
+            raise capi.M3pcError("discrete heads are not used by any m3pc config and are not supported")
+        if masks is None:
+            masks = create_random_autoregressive_mask(data_shapes, self.cfg.mask_ratio, self.cfg.traj_length, self.cfg.p_weights)
+        return raw_batch_loss(self.handle, batch, masks, float(entropy_reg), "finetune", eps, capi.PREC_FP32)
+
 
 # ------------------------------------------------------------------------------------------------------
 def _versions(module):
@@ -1376,7 +1391,8 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
         return types.MethodType(method, learner)
 
     for name in ("action_sample", "rtg_guiding", "critic_lambda_guiding", "noise_adding_lambda", "mtm_sampling",
-                 "action_piid_sample", "action_id_sample", "action_piid_list_sample", "plan_async", "action_sample_batch"):
+                 "action_piid_sample", "action_id_sample", "action_piid_list_sample", "plan_async", "action_sample_batch",
+                 "compute_mtm_loss"):
         setattr(learner, name, _wrap(name))
     learner._hip_planner = planner
     planner.sync = _sync

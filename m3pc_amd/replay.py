@@ -310,6 +310,37 @@ class DeviceReplayBuffer:
         batch = {"states": s, "actions": a, "rewards": r, "returns": v}
         return (batch, oi) if return_indices else batch
 
+    def mtm_loss(self, masks, entropy_reg: float, form: str = "finetune", indices=None, batch_size: Optional[int] = None, eps=None,
+                 precision: int = capi.PREC_FP32, return_indices: bool = False):
+        """The masked-trajectory loss (m3pc_mtm_loss_replay) of the batch ``traj_sample`` would return for the same arguments, without
+        the batch leaving the library: gather, tokenise, forward under ``masks``, loss.  eps: (B,L,A) standard normals, or None: drawn
+        by the library at the same (seed, step).  Returns the reference's 5-tuple of ``form`` (m3pc_amd/mtm.py) as 0-d device tensors;
+        ``step`` advances as in ``traj_sample``."""
+        from .masks import mask_rows
+        from .mtm import form_settings, loss_tuple
+        B = int(self.traj_batch_size if batch_size is None else batch_size)
+        ti = si = pt = ps = None
+        dev = 0
+        if indices is not None:
+            B = int(np.prod(np.shape(indices[0])))
+            ti, pt, dev = self._index(indices[0], B)
+            si, ps, dev2 = self._index(indices[1], B)
+            if dev != dev2:
+                raise ValueError("trajectory indices and starts must both be on the host or both on the device")
+        flags, bits, keys = form_settings(form, capi.KEYS)
+        e = None if eps is None else self._dev(eps, (B, self.sequence_length, self.A))
+        rec = self._new(capi.MTM_LOSS_FLOATS)
+        oi = (self._new(B, dtype=torch.int32), self._new(B, dtype=torch.int32)) if return_indices else (None, None)
+        mp, keep = self.handle._mask_ptrs(mask_rows(masks))
+        capi.check(self.lib.m3pc_mtm_loss_replay(self.handle._h, self._rb, B, _MODES[self._mode], pt, ps, dev, self.seed, self.step, mp,
+                                                 capi._ptr(e), float(entropy_reg), flags, bits, int(precision), capi._ptr(rec),
+                                                 capi._ptr(oi[0]), capi._ptr(oi[1]), self._stream()))
+        if indices is None:
+            self.step += 1
+        del ti, si, keep
+        out = loss_tuple(rec, keys)
+        return (out, oi) if return_indices else out
+
     def split(self, batch_size: Optional[int] = None):
         """(rows of the online ring, rows of the offline ring) of a transition batch: replay_buffer.py:370-381."""
         B = int(self.trans_batch_size if batch_size is None else batch_size)
