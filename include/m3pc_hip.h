@@ -1077,6 +1077,51 @@ int m3pc_mtm_loss_replay(m3pc_handle* h, m3pc_replay* rb, int batch, int mode, c
                          const float* eps, float entropy_reg, int flags, int loss_keys, int precision, float* record, int* out_traj,
                          int* out_start, void* stream);
 
+/* THE GRADIENT OF THE MASKED-TRAJECTORY LOSS: the forward above and loss.backward() of Learner.mtm_update (finetune_omtm/learner.py:506-538)
+ * through the whole model -- loss terms, heads, decoder blocks, decoder embedding and mask tokens, encoder blocks, encoder embedding --
+ * in one call: a raw batch in, one gradient tensor per parameter out, under the reference's state_dict names.  The optimizers stay the
+ * caller's.  The gradient is that of `total`, record[14] as defined above for the given flags and loss_keys, with respect to every tensor
+ * of the model's state_dict except the buffer pos_embed.  Held constant: the tokenised targets (the l2-normalised ones too), the clipped
+ * action and its z, entropy_reg, the masks.  eps is the caller's; u = mu + std eps is differentiated through mu and std (rsample), and std
+ * = exp(-5 + 3.5 (tanh(.) + 1)) through the log_std Linear.
+ *   THE MODEL IS THE EVAL-MODE ONE: NO DROPOUT.  (The shipped configs train with dropout 0.1; drawing keep-masks is not in the library.)
+ *   A key outside loss_keys contributes nothing: with loss_keys = 1 the rewards and returns heads get exact zeros (the reference leaves
+ *   .grad = None there).  Structural zeros are exact zeros: the mask token of a fully visible key; the encoder embedding and the
+ *   encoder_per_dim_encoding of a fully hidden key.  When total is NaN (no hidden action timestep, an l2 norm of 0) the call returns
+ *   M3PC_OK and the gradients are unspecified.
+ *   weights      the object reads the fp32 weights and the tokenizers of the handle it was created on at the time of each call: after
+ *                m3pc_load_weights the next call differentiates the new weights.  The handle must outlive the object.
+ *   workspace    the object never writes to the handle and leaves the candidate workspace alone.  It owns the activations its forward
+ *                saves and one gradient buffer per parameter.  _create makes no HIP call; the first enqueueing call allocates
+ *                max_batch x the bytes per batch element, with L = 4 T, n = n_enc_layer + n_dec_layer, d = embed_dim, ff = 4 d:
+ *                  4 [ n L (8 d + 2 ff + 4 + n_head L) + L (12 d + ff + 4) + T (11 d + 4 S + 8 A + 13) ] + 56 T  bytes
+ *                (rounded up per buffer to 256 bytes), plus once the gradients (the parameters' bytes) and the column-sum partials,
+ *                2 (max_batch L / 64 + 2) max(3 d, ff) doubles.
+ *   precision    fp32 only: the products on v_mfma_f32_32x32x2_f32, one wavefront per 32 x 32 output tile, K in ascending order (the
+ *                weight gradients: four wavefronts per tile, each a fixed quarter of the k blocks, added in a fixed order);
+ *                column sums in float64 in a fixed order.  No floating-point atomics: a call is bit-identical from run to run and does
+ *                not depend on rows beyond `batch` or on what an earlier call left in the workspace (m3pc_amd/csrc/mtm_grad.h).
+ *   record       optional device out, the M3PC_MTM_LOSS_FLOATS floats of m3pc_mtm_loss, from the forward this call runs.
+ *   export       each listed gradient is written in the torch layout of its parameter to the entry's `data` (host or device by its
+ *                on_device; written although the field is declared const).  Gradients are those of the last gradient call.
+ *   replay form  the sampling arguments and semantics of m3pc_mtm_loss_replay; per call the bits of m3pc_replay_sample_segments followed
+ *                by m3pc_mtm_grad.
+ * Stream-ordered; no entry point waits for the device (_destroy drains).  Refused with M3PC_EINVAL before any HIP call: what m3pc_mtm_loss
+ * refuses, with max_batch the object's; max_batch < 1 (create); masks that keep no token (as m3pc_forward); an export name that is not a
+ * parameter (pos_embed included); an export numel that does not fit the parameter.  Refused with M3PC_ESTATE: weights or tokenizers not
+ * loaded; export before any gradient call. */
+struct m3pc_mtm_grad; /* (no typedef: the name is the gradient call's; say `struct m3pc_mtm_grad`) */
+int m3pc_mtm_grad_create(m3pc_handle* h, int max_batch, struct m3pc_mtm_grad** out);
+int m3pc_mtm_grad_destroy(struct m3pc_mtm_grad* g);
+int m3pc_mtm_grad(struct m3pc_mtm_grad* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns,
+                  int returns_f64, const unsigned char* const masks[4], const float* eps, float entropy_reg, int flags, int loss_keys,
+                  float* record, void* stream);
+int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
+                         int index_on_device, unsigned long long seed, unsigned long long step, const unsigned char* const masks[4],
+                         const float* eps, float entropy_reg, int flags, int loss_keys, float* record, int* out_traj, int* out_start,
+                         void* stream);
+int m3pc_mtm_grad_export(struct m3pc_mtm_grad* g, const m3pc_named_tensor* tensors, int n, void* stream);
+
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate
  * halves of a plan step (normally overlapped on two streams) run one after the other on `stream`, so that a

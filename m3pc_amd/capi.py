@@ -58,6 +58,7 @@ EXPORTS = (
     "m3pc_iql_create", "m3pc_iql_destroy", "m3pc_iql_load", "m3pc_iql_export", "m3pc_iql_set_step", "m3pc_iql_get_step",
     "m3pc_iql_train_step", "m3pc_iql_train", "m3pc_iql_publish_critic", "m3pc_iql_evaluate",
     "m3pc_mtm_loss_terms", "m3pc_mtm_loss", "m3pc_mtm_loss_replay",
+    "m3pc_mtm_grad_create", "m3pc_mtm_grad_destroy", "m3pc_mtm_grad", "m3pc_mtm_grad_replay", "m3pc_mtm_grad_export",
 )
 
 
@@ -232,6 +233,11 @@ def load_library(path: Optional[str] = None):
         "m3pc_mtm_loss_terms": [vp, i, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, f, i, i, vp, vp],
         "m3pc_mtm_loss": [vp, i, vp, vp, vp, vp, i, C.POINTER(vp), vp, f, i, i, i, vp, vp, vp, vp, vp, vp, vp],
         "m3pc_mtm_loss_replay": [vp, vp, i, i, vp, vp, i, C.c_ulonglong, C.c_ulonglong, C.POINTER(vp), vp, f, i, i, i, vp, vp, vp, vp],
+        "m3pc_mtm_grad_create": [vp, i, C.POINTER(vp)],
+        "m3pc_mtm_grad_destroy": [vp],
+        "m3pc_mtm_grad": [vp, i, vp, vp, vp, vp, i, C.POINTER(vp), vp, f, i, i, vp, vp],
+        "m3pc_mtm_grad_replay": [vp, vp, i, i, vp, vp, i, C.c_ulonglong, C.c_ulonglong, C.POINTER(vp), vp, f, i, i, vp, vp, vp, vp],
+        "m3pc_mtm_grad_export": [vp, C.POINTER(NamedTensor), i, vp],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }

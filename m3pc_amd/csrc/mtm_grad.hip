@@ -1,0 +1,1192 @@
+// The gradient of the masked-trajectory loss (include/m3pc_hip.h: m3pc_mtm_grad*).  mtm_grad.h states the launches, what the forward
+// keeps, the reduction orders and the bytes.  fp32 only; the eval-mode model (no dropout).
+#include <stdint.h>
+
+#include "device_util.h"
+#include "iql.h"
+#include "mtm_loss.h"
+#include "mtm_grad.h"
+
+namespace m3pc {
+namespace {
+
+typedef unsigned long long u64;
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+#else
+#define MG_MFMA(a, b, c) ((void)(a), (void)(b), (c))
+#endif
+
+// row r of a compact run -> row of the buffer: rpg rows per group, groups gstride rows apart, from row off (rpg == 0: r itself)
+struct RMap {
+    int rpg, gstride, off;
+};
+__host__ __device__ __forceinline__ long long rmap(const RMap& m, int r) {
+    return m.rpg == 0 ? (long long)r : (long long)(r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
+}
+
+// ------------------------------------------------------------------------------------------------ the product
+// C[m][n] = sum_k A(m, k) B(k, n): element (o, k) of an operand is p[row(o) * s_o + k * s_k], or p[o * s_o + row(k) * s_k] with map_k
+struct GOp {
+    const float* p;
+    long long s_o, s_k;
+    RMap map;
+    int map_k;
+    int vec;  // k-contiguous, not row-mapped on k, 16-byte aligned rows: four k per load
+};
+struct GemmG {
+    GOp A, B;
+    float* C;
+    long long ldc;
+    RMap cmap;              // on m
+    int M, N, K;
+    const float *bias, *bias2;  // + bias[n] + bias2[n]
+    const float* pos;       // + pos[(m % pos_T) * N + n]
+    int pos_T;
+    const float* res;       // + res[row(m) * ldc + n]
+    const float* gelu_aux;  // * gelu'(gelu_aux[row(m) * ldc + n])
+    float* gelu_out;        // gelu_out[row(m) * ldc + n] = gelu(C)
+    int accumulate;         // C += instead of C =
+    int splitk;             // the four wavefronts of a workgroup share a tile (mg_gemm_kernel<true>)
+};
+
+__device__ __forceinline__ float gelu_grad_exact(float x) {
+    const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
+    const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
+    return cdf + x * pdf;
+}
+
+// One wavefront per 32 x 32 tile of C.  MFMA operand a: lane holds A(m = lane & 31, k = lane >> 5); b: B(k = lane >> 5, n = lane & 31);
+// accumulator i is row 8 (i / 4) + 4 (lane >> 5) + i % 4, column lane & 31.  K in ascending blocks of 16: step u of a block multiplies
+// k = 8 (u / 4) + u % 4 (lower lane half) and that + 4 (upper half); the operands of the next block are loaded ahead of the eight MFMAs of
+// this one, four consecutive k per 16-byte load where the operand is k-contiguous and aligned (vec).
+// SPLIT (the dW form, K = rows: few tiles, long K): the four wavefronts of a workgroup share ONE tile, wavefront w taking the k
+// blocks w, w + 4, ...; the partial tiles of wavefronts 1, 2, 3 go through LDS and wavefront 0 adds them in that order.
+__device__ __forceinline__ void mg_load8(const GOp& op, const float* base, bool o_ok, int k0, int lh, int K, float* v) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int k = k0 + 8 * h + 4 * lh;
+        if (op.vec && o_ok && k + 3 < K) {
+            const f32x4 x = *(const f32x4*)(base + k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[4 * h + j] = x[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int kk = k + j;
+                const bool ok = o_ok && kk < K;
+                const long long kr = op.map_k && ok ? rmap(op.map, kk) : (long long)kk;
+                v[4 * h + j] = ok ? base[kr * op.s_k] : 0.f;
+            }
+        }
+    }
+}
+
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void mg_gemm_kernel(GemmG p) {
+    __shared__ float red[SPLIT ? 3 * 1024 : 1];
+    const int lane = threadIdx.x & 63, l31 = lane & 31, lh = lane >> 5, wv = threadIdx.x >> 6;
+    const int tiles_n = (p.N + 31) >> 5, tiles_m = (p.M + 31) >> 5;
+    const long long w = SPLIT ? (long long)blockIdx.x : (long long)blockIdx.x * 4 + wv;
+    if (w >= (long long)tiles_m * tiles_n) return;  // (SPLIT: the grid is the tile count, whole workgroups leave)
+    const int tm = (int)(w / tiles_n), tn = (int)(w % tiles_n);
+    const int m = 32 * tm + l31, n = 32 * tn + l31;
+    const bool m_ok = m < p.M, n_ok = n < p.N;
+    const float* pa = p.A.p + (m_ok ? (p.A.map_k ? (long long)m : rmap(p.A.map, m)) * p.A.s_o : 0);
+    const float* pb = p.B.p + (n_ok ? (p.B.map_k ? (long long)n : rmap(p.B.map, n)) * p.B.s_o : 0);
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    const int kstep = SPLIT ? 64 : 16, kbeg = SPLIT ? 16 * wv : 0;
+    float a[8], b[8], a2[8], b2[8];
+    if (kbeg < p.K) {
+        mg_load8(p.A, pa, m_ok, kbeg, lh, p.K, a);
+        mg_load8(p.B, pb, n_ok, kbeg, lh, p.K, b);
+    }
+    for (int k0 = kbeg; k0 < p.K; k0 += kstep) {
+        const bool more = k0 + kstep < p.K;
+        if (more) {
+            mg_load8(p.A, pa, m_ok, k0 + kstep, lh, p.K, a2);
+            mg_load8(p.B, pb, n_ok, k0 + kstep, lh, p.K, b2);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = MG_MFMA(a[u], b[u], acc);
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) a[u] = a2[u], b[u] = b2[u];
+        }
+    }
+    if (SPLIT) {
+        if (wv > 0) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) red[(wv - 1) * 1024 + i * 64 + lane] = acc[i];
+        }
+        __syncthreads();
+        if (wv > 0) return;
+#pragma unroll
+        for (int w2 = 0; w2 < 3; ++w2)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] += red[w2 * 1024 + i * 64 + lane];
+    }
+    if (!n_ok) return;
+    float add = 0.f;
+    if (p.bias) add = p.bias[n];
+    if (p.bias2) add += p.bias2[n];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int mo = 32 * tm + 8 * (i >> 2) + 4 * lh + (i & 3);
+        if (mo >= p.M) continue;
+        const long long at = rmap(p.cmap, mo) * p.ldc + n;
+        float v = acc[i] + add;
+        if (p.pos) v += p.pos[(long long)(mo % p.pos_T) * p.N + n];
+        if (p.res) v += p.res[at];
+        if (p.gelu_aux) v *= gelu_grad_exact(p.gelu_aux[at]);
+        if (p.accumulate) v += p.C[at];
+        p.C[at] = v;
+        if (p.gelu_out) p.gelu_out[at] = gelu_exact(v);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ LayerNorm
+struct LnG {
+    const float* X;   // rows xmap(r), ld d
+    RMap xmap;
+    const float *g, *b;
+    float* Y;         // forward: compact rows
+    float* st;        // (rows, 2): mean, rstd
+    const float* dY;  // backward: compact rows
+    float* dX;        // backward: rows xmap(r)
+    int rows, d, accumulate;
+};
+
+__global__ __launch_bounds__(256) void mg_ln_fwd_kernel(LnG p) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r >= p.rows) return;
+    const float* x = p.X + rmap(p.xmap, r) * p.d;
+    float s = 0.f;
+    for (int c = lane; c < p.d; c += 64) s += x[c];
+    const float mean = wave_sum(s) / (float)p.d;
+    float v = 0.f;
+    for (int c = lane; c < p.d; c += 64) {
+        const float t = x[c] - mean;
+        v += t * t;
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)p.d + 1e-5f);
+    for (int c = lane; c < p.d; c += 64) p.Y[(size_t)r * p.d + c] = (x[c] - mean) * rstd * p.g[c] + p.b[c];
+    if (lane == 0) {
+        p.st[2 * (size_t)r] = mean;
+        p.st[2 * (size_t)r + 1] = rstd;
+    }
+}
+
+// dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma
+__global__ __launch_bounds__(256) void mg_ln_bwd_kernel(LnG p) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (r >= p.rows) return;
+    const long long xr = rmap(p.xmap, r);
+    const float* x = p.X + xr * p.d;
+    const float* dy = p.dY + (size_t)r * p.d;
+    const float mean = p.st[2 * (size_t)r], rstd = p.st[2 * (size_t)r + 1];
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = lane; c < p.d; c += 64) {
+        const float g = dy[c] * p.g[c];
+        s1 += g;
+        s2 += g * ((x[c] - mean) * rstd);
+    }
+    s1 = wave_sum(s1) / (float)p.d;
+    s2 = wave_sum(s2) / (float)p.d;
+    float* dx = p.dX + xr * p.d;
+    for (int c = lane; c < p.d; c += 64) {
+        const float g = dy[c] * p.g[c], xh = (x[c] - mean) * rstd;
+        const float v = rstd * ((g - s1) - xh * s2);
+        dx[c] = p.accumulate ? dx[c] + v : v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ column sums
+// rows (s, j): s < nseq, j < n, bit j of sel set; the buffer row is s L + j0 + j, the compact row s n + j.
+//   out0[c] = sum dY[row][c];  with X: out1[c] = sum dY[row][c] xhat[row][c]  (LayerNorm: bias and weight)
+struct ColG {
+    const float* dY;
+    int dy_compact;
+    long long ldy;
+    const float* X;   // buffer rows, ld C
+    const float* st;  // compact rows
+    int nseq, L, j0, n;
+    u64 sel;
+    int C;
+    double* part;     // (chunks, 2, C)
+    float *out0, *out1;
+    int chunks;
+};
+
+__global__ __launch_bounds__(256) void mg_colsum_kernel(ColG p) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= p.C) return;
+    const long long total = (long long)p.nseq * p.n;
+    const long long q0 = (long long)blockIdx.y * 64, q1 = q0 + 64 < total ? q0 + 64 : total;
+    double a0 = 0.0, a1 = 0.0;
+    for (long long q = q0; q < q1; ++q) {
+        const int s = (int)(q / p.n), j = (int)(q % p.n);
+        if (!((p.sel >> j) & 1ull)) continue;
+        const long long br = (long long)s * p.L + p.j0 + j;
+        const float dy = p.dY[(p.dy_compact ? q : br) * p.ldy + c];
+        a0 += (double)dy;
+        if (p.X) {
+            const float xh = (p.X[br * p.C + c] - p.st[2 * q]) * p.st[2 * q + 1];
+            a1 += (double)(dy * xh);
+        }
+    }
+    p.part[((size_t)blockIdx.y * 2) * p.C + c] = a0;
+    p.part[((size_t)blockIdx.y * 2 + 1) * p.C + c] = a1;
+}
+
+__global__ __launch_bounds__(256) void mg_colsum_fin_kernel(ColG p) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= p.C) return;
+    double a0 = 0.0, a1 = 0.0;
+    for (int k = 0; k < p.chunks; ++k) {
+        a0 += p.part[((size_t)k * 2) * p.C + c];
+        a1 += p.part[((size_t)k * 2 + 1) * p.C + c];
+    }
+    p.out0[c] = (float)a0;
+    if (p.out1) p.out1[c] = (float)a1;
+}
+
+// ------------------------------------------------------------------------------------------------ attention
+struct AttG {
+    const float* QKV;  // (B L, 3 d)
+    float* P;          // (B, nh, L, L): probabilities, then dS
+    float* O;          // forward out (B L, d)
+    const float* dO;   // (B L, d)
+    float* dQKV;       // (B L, 3 d)
+    int B, L, d, nh, hd;
+    float scale;
+};
+
+// one wavefront per (b, head, query i): lane owns the keys lane, lane + 64, ...; L <= 256
+__global__ __launch_bounds__(256) void mg_attn_fwd_kernel(AttG p) {
+    __shared__ float sp[4][256];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + wv;
+    if (w >= (long long)p.B * p.nh * p.L) return;
+    const int i = (int)(w % p.L), hh = (int)((w / p.L) % p.nh), b = (int)(w / ((long long)p.L * p.nh));
+    const size_t ld = 3 * (size_t)p.d;
+    const float* q = p.QKV + ((size_t)b * p.L + i) * ld + (size_t)hh * p.hd;
+    const float* Kb = p.QKV + (size_t)b * p.L * ld + p.d + (size_t)hh * p.hd;
+    const float* Vb = Kb + p.d;
+    float s[4], mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = lane + 64 * c;
+        s[c] = -INFINITY;
+        if (j < p.L) {
+            float a = 0.f;
+            for (int e = 0; e < p.hd; ++e) a += (q[e] * p.scale) * Kb[(size_t)j * ld + e];
+            s[c] = a;
+            mx = fmaxf(mx, a);
+        }
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        s[c] = lane + 64 * c < p.L ? expf(s[c] - mx) : 0.f;
+        sum += s[c];
+    }
+    sum = wave_sum(sum);
+    float* Pr = p.P + (((size_t)b * p.nh + hh) * p.L + i) * p.L;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = lane + 64 * c;
+        if (j < p.L) {
+            const float pr = s[c] / sum;
+            Pr[j] = pr;
+            sp[wv][j] = pr;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    for (int e = lane; e < p.hd; e += 64) {
+        float a = 0.f;
+        for (int j = 0; j < p.L; ++j) a += sp[wv][j] * Vb[(size_t)j * ld + e];
+        p.O[((size_t)b * p.L + i) * p.d + (size_t)hh * p.hd + e] = a;
+    }
+}
+
+// one wavefront per (b, head, key j): out[j][e] = alpha sum_i M[i][j] Z[i][e], queries ascending.  which 0: dV = P^T dO; 1: dK = dS^T Q scale
+__global__ __launch_bounds__(256) void mg_attn_col_kernel(AttG p, int which) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + wv;
+    if (w >= (long long)p.B * p.nh * p.L) return;
+    const int j = (int)(w % p.L), hh = (int)((w / p.L) % p.nh), b = (int)(w / ((long long)p.L * p.nh));
+    const float* Mb = p.P + ((size_t)b * p.nh + hh) * p.L * p.L + j;
+    const size_t ldz = which == 0 ? (size_t)p.d : 3 * (size_t)p.d;
+    const float* Z = (which == 0 ? p.dO : p.QKV) + (size_t)b * p.L * ldz + (size_t)hh * p.hd;
+    const float alpha = which == 0 ? 1.0f : p.scale;
+    float* out = p.dQKV + ((size_t)b * p.L + j) * 3 * p.d + (which == 0 ? 2 * p.d : p.d) + (size_t)hh * p.hd;
+    for (int e = lane; e < p.hd; e += 64) {
+        float a = 0.f;
+        for (int i = 0; i < p.L; ++i) a += Mb[(size_t)i * p.L] * Z[(size_t)i * ldz + e];
+        out[e] = a * alpha;
+    }
+}
+
+// one wavefront per (b, head, query i): dP = dO V^T, dS = P (dP - sum_j dP P) over P in place, dQ = dS K scale (keys ascending)
+__global__ __launch_bounds__(256) void mg_attn_row_kernel(AttG p) {
+    __shared__ float sp[4][256];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + wv;
+    if (w >= (long long)p.B * p.nh * p.L) return;
+    const int i = (int)(w % p.L), hh = (int)((w / p.L) % p.nh), b = (int)(w / ((long long)p.L * p.nh));
+    const size_t ld = 3 * (size_t)p.d;
+    const float* dO = p.dO + ((size_t)b * p.L + i) * p.d + (size_t)hh * p.hd;
+    const float* Kb = p.QKV + (size_t)b * p.L * ld + p.d + (size_t)hh * p.hd;
+    const float* Vb = Kb + p.d;
+    float* Pr = p.P + (((size_t)b * p.nh + hh) * p.L + i) * p.L;
+    float dp[4], pr[4], dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = lane + 64 * c;
+        dp[c] = 0.f;
+        pr[c] = 0.f;
+        if (j < p.L) {
+            float a = 0.f;
+            for (int e = 0; e < p.hd; ++e) a += dO[e] * Vb[(size_t)j * ld + e];
+            dp[c] = a;
+            pr[c] = Pr[j];
+            dot += a * pr[c];
+        }
+    }
+    dot = wave_sum(dot);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = lane + 64 * c;
+        if (j < p.L) {
+            const float ds = pr[c] * (dp[c] - dot);
+            Pr[j] = ds;
+            sp[wv][j] = ds;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    for (int e = lane; e < p.hd; e += 64) {
+        float a = 0.f;
+        for (int j = 0; j < p.L; ++j) a += sp[wv][j] * Kb[(size_t)j * ld + e];
+        p.dQKV[((size_t)b * p.L + i) * ld + (size_t)hh * p.hd + e] = a * p.scale;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ embedding, gather, scatter
+struct EmbG {
+    const float *tok[4], *W[4], *bias[4], *pdim[4], *pos, *mtok[4];
+    u64 bits[4];
+    int kept[4], eoff[4], feat[4];
+    int B, T, d, Le;
+    float* X;          // (B Le, d)  encoder rows (embed: out)
+    const float* src;  // gather: EncN (B Le, d); scatter: dZin (B 4T, d)
+    float* dst;        // gather: Zin (B 4T, d); scatter: dEncN (B Le, d)
+};
+
+// encoder row j -> (key, timestep): the keys in order, the visible timesteps of each ascending
+__device__ __forceinline__ void enc_row_token(const EmbG& p, int j, int* k_out, int* t_out) {
+    int k = 0;
+    while (k < 3 && j >= p.kept[k]) j -= p.kept[k++];
+    u64 m = p.bits[k];
+    for (int i = 0; i < j; ++i) m &= m - 1;
+    *k_out = k;
+    *t_out = __ffsll((long long)m) - 1;
+}
+
+__global__ __launch_bounds__(256) void mg_embed_kernel(EmbG p) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)p.B * p.Le * p.d) return;
+    const int n = (int)(i % p.d), j = (int)((i / p.d) % p.Le), b = (int)(i / ((long long)p.d * p.Le));
+    int k, t;
+    enc_row_token(p, j, &k, &t);
+    const int F = p.feat[k];
+    const float* x = p.tok[k] + ((size_t)b * p.T + t) * F;
+    const float* w = p.W[k] + (size_t)n * F;
+    float a = 0.f;
+    for (int f = 0; f < F; ++f) a += x[f] * w[f];
+    p.X[i] = ((a + p.bias[k][n]) + p.pdim[k][n]) + p.pos[(size_t)t * p.d + n];
+}
+
+// decoder embedding input (b, k, t): the encoder output row of a visible token, the key's mask token of a hidden one
+__global__ __launch_bounds__(256) void mg_gather_kernel(EmbG p) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)p.B * 4 * p.T * p.d) return;
+    const int n = (int)(i % p.d), r = (int)((i / p.d) % (4 * p.T)), b = (int)(i / ((long long)p.d * 4 * p.T));
+    const int k = r / p.T, t = r % p.T;
+    float v;
+    if ((p.bits[k] >> t) & 1ull) {
+        const int j = p.eoff[k] + __popcll(p.bits[k] & ((1ull << t) - 1ull));
+        v = p.src[((size_t)b * p.Le + j) * p.d + n];
+    } else {
+        v = p.mtok[k][n];
+    }
+    p.dst[i] = v;
+}
+
+__global__ __launch_bounds__(256) void mg_scatter_kernel(EmbG p) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)p.B * p.Le * p.d) return;
+    const int n = (int)(i % p.d), j = (int)((i / p.d) % p.Le), b = (int)(i / ((long long)p.d * p.Le));
+    int k, t;
+    enc_row_token(p, j, &k, &t);
+    p.dst[i] = p.src[((size_t)b * 4 * p.T + (size_t)k * p.T + t) * p.d + n];
+}
+
+// the visible token rows of key k, compact: out[b kept + i][f] = tok_k[b, t_i][f] (the B operand of the encoder embedding's dW product)
+__global__ __launch_bounds__(256) void mg_tokv_kernel(EmbG p, int k, float* out) {
+    const int F = p.feat[k], kept = p.kept[k];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)p.B * kept * F) return;
+    const int f = (int)(i % F), ii = (int)((i / F) % kept), b = (int)(i / ((long long)F * kept));
+    u64 m = p.bits[k];
+    for (int q = 0; q < ii; ++q) m &= m - 1;
+    const int t = __ffsll((long long)m) - 1;
+    out[i] = p.tok[k][((size_t)b * p.T + t) * F + f];
+}
+
+// ------------------------------------------------------------------------------------------------ the action head's std, the loss backward
+__global__ __launch_bounds__(256) void mg_std_kernel(const float* ls, float* sd, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) sd[i] = expf(-5.0f + 3.5f * (tanhf(ls[i]) + 1.0f));
+}
+
+struct LossBwdG {
+    const float *pred[3], *mu, *sd, *ls, *tgt[4], *eps;
+    float *dpred[3], *dmu, *dls;
+    u64 mask[4];
+    int batch, T, S, A, flags, loss_keys;
+    float entropy_reg, inv_cnt;  // 1 / (batch * hidden action timesteps * A)
+};
+
+// one thread per (row, feature) of the S + 2 + A head outputs.  The targets, the clipped action and its z are constants.
+//   key k != actions in loss_keys:  dpred = 2 (pred - t') / (B T D)
+//   actions:  dmu  = [bit] 2 (tanh mu - a) m (1 - tanh^2 mu) / (B T A)  -  hid ((z - mu) / var) / cnt  +  hid er 2 tanh(u) / cnt
+//             dstd = - hid ((z - mu)^2 / std^3 - 1 / std) / cnt  +  hid er (2 tanh(u) eps - 1 / std) / cnt      (u = mu + std eps)
+//             d log_std-Linear = dstd std 3.5 (1 - tanh^2(ls))
+__global__ __launch_bounds__(256) void mg_loss_bwd_kernel(LossBwdG p) {
+    const int W = p.S + 2 + p.A;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long rows = (long long)p.batch * p.T;
+    if (i >= rows * W) return;
+    const int c = (int)(i % W);
+    const long long r = i / W;
+    const int t = (int)(r % p.T);
+    if (c < p.S + 2) {
+        const int j = c < p.S ? 0 : c - p.S + 1, k = j == 0 ? M3PC_STATES : j == 1 ? M3PC_REWARDS : M3PC_RETURNS;
+        const int D = j == 0 ? p.S : 1, e = j == 0 ? c : 0;
+        float g = 0.f;
+        if ((p.loss_keys >> k) & 1) {
+            const float* tg = p.tgt[k] + r * D;
+            float tv = tg[e];
+            if (p.flags & M3PC_MTM_NORM_L2) {
+                double n2 = 0.0;
+                for (int q = 0; q < D; ++q) n2 += (double)(tg[q] * tg[q]);
+                tv = tv / sqrtf((float)n2);
+            }
+            g = 2.0f * (p.pred[j][r * D + e] - tv) / (float)((double)rows * D);
+        }
+        p.dpred[j][r * D + e] = g;
+        return;
+    }
+    const int e = c - p.S - 2;
+    const long long at = r * p.A + e;
+    const float mu = p.mu[at], sd = p.sd[at], a = p.tgt[M3PC_ACTIONS][at];
+    const bool vis = (p.mask[M3PC_ACTIONS] >> t) & 1ull;
+    float dmu = 0.f, dsd = 0.f;
+    if (vis) {
+        if ((p.loss_keys >> M3PC_ACTIONS) & 1) {
+            const float th = tanhf(mu);
+            dmu = 2.0f * (th - a) * (1.0f - th * th) / (float)((double)rows * p.A);
+        }
+    } else {
+        const float lo = (float)(-1.0 + 1e-6), hi = (float)(1.0 - 1e-6);
+        float ac = a;
+        if ((p.flags & M3PC_MTM_CLIP_ACTIONS) && a == a) ac = fminf(fmaxf(a, lo), hi);
+        const float z = 0.5f * (log1pf(ac) - log1pf(-ac));
+        const float dz = z - mu, var = sd * sd, eps = p.eps[at];
+        const float th = tanhf(mu + eps * sd);
+        dmu = (p.entropy_reg * 2.0f * th - dz / var) * p.inv_cnt;
+        dsd = (p.entropy_reg * (2.0f * th * eps - 1.0f / sd) - (dz * dz / (var * sd) - 1.0f / sd)) * p.inv_cnt;
+    }
+    const float tl = tanhf(p.ls[at]);
+    p.dmu[at] = dmu;
+    p.dls[at] = dsd * sd * 3.5f * (1.0f - tl * tl);
+}
+
+constexpr size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
+
+}  // namespace
+}  // namespace m3pc
+
+struct m3pc_mtm_grad {
+    m3pc_handle* h = nullptr;
+    int max_batch = 0;
+    bool ready = false, have_grad = false;
+    struct Par {
+        std::string name;
+        long long numel;
+        size_t off;
+    };
+    std::vector<Par> par;
+    std::map<std::string, int> idx;
+    size_t grad_floats = 0;
+    float* arena = nullptr;  // every fp32 buffer below
+    double* arena64 = nullptr;
+    float* grad = nullptr;
+    struct Lay {
+        float *Xin, *Hn1, *QKV, *P, *O, *X1, *Hn2, *Fpre, *Fact, *st1, *st2;
+    };
+    std::vector<Lay> lay;  // encoder layers, then decoder layers
+    float *XencOut, *EncN, *st_enc, *Zin, *XdecOut, *DecN, *st_dec;
+    float *tok[4], *raw[3], *eps;
+    float *Hh[3], *st_h[3], *Hpre[3], *Hact[3], *pred[3], *mu, *ls, *sd;
+    float *dX, *dH, *dQKV, *dF, *dO, *dpred[3], *dmu, *dls, *dh1, *dh2, *rec;
+    double *raw_returns, *part, *colpart;
+};
+
+namespace {
+
+using Obj = struct m3pc_mtm_grad;
+
+// one pass over the buffers: count (base == nullptr) or assign
+size_t mg_layout(Obj* g, float* base) {
+    const m3pc_handle* h = g->h;
+    const size_t B = (size_t)g->max_batch, T = (size_t)h->T, d = (size_t)h->d, ff = (size_t)h->ff, L = 4 * T, R = B * L, RT = B * T;
+    const size_t S = (size_t)h->S, A = (size_t)h->A;
+    size_t at = 0;
+    auto take = [&](float** p, size_t n) {
+        if (base) *p = base + at;
+        at += al64(n);
+    };
+    take(&g->grad, g->grad_floats);
+    const int nl = h->dm.n_enc_layer + h->dm.n_dec_layer;
+    if (base) g->lay.resize(nl);
+    Obj::Lay tmp;
+    for (int l = 0; l < nl; ++l) {
+        Obj::Lay& y = base ? g->lay[l] : tmp;
+        take(&y.Xin, R * d);
+        take(&y.Hn1, R * d);
+        take(&y.QKV, R * 3 * d);
+        take(&y.P, R * h->nh * L);
+        take(&y.O, R * d);
+        take(&y.X1, R * d);
+        take(&y.Hn2, R * d);
+        take(&y.Fpre, R * ff);
+        take(&y.Fact, R * ff);
+        take(&y.st1, R * 2);
+        take(&y.st2, R * 2);
+    }
+    take(&g->XencOut, R * d);
+    take(&g->EncN, R * d);
+    take(&g->st_enc, R * 2);
+    take(&g->Zin, R * d);
+    take(&g->XdecOut, R * d);
+    take(&g->DecN, R * d);
+    take(&g->st_dec, R * 2);
+    for (int k = 0; k < 4; ++k) take(&g->tok[k], RT * h->feat[k]);
+    for (int k = 0; k < 3; ++k) take(&g->raw[k], RT * h->feat[k]);
+    take(&g->eps, RT * A);
+    const size_t hw[3] = {S, 1, 1};
+    for (int j = 0; j < 3; ++j) {
+        take(&g->Hh[j], RT * d);
+        take(&g->st_h[j], RT * 2);
+        take(&g->Hpre[j], RT * d);
+        take(&g->Hact[j], RT * d);
+        take(&g->pred[j], RT * hw[j]);
+        take(&g->dpred[j], RT * hw[j]);
+    }
+    take(&g->mu, RT * A);
+    take(&g->ls, RT * A);
+    take(&g->sd, RT * A);
+    take(&g->dmu, RT * A);
+    take(&g->dls, RT * A);
+    take(&g->dX, R * d);
+    take(&g->dH, R * d);
+    take(&g->dQKV, R * 3 * d);
+    take(&g->dF, R * ff);
+    take(&g->dO, R * d);
+    take(&g->dh1, RT * d);
+    take(&g->dh2, RT * d);
+    take(&g->rec, M3PC_MTM_LOSS_FLOATS);
+    return at;
+}
+
+int mg_ensure(Obj* g) {
+    m3pc_handle* h = g->h;
+    HIPCHK(hipSetDevice(h->device));
+    if (g->ready) return 0;
+    const size_t n = mg_layout(g, nullptr);
+    if (!g->arena) CHK(dmalloc(&g->arena, n));  // (a call that failed at the second allocation left the first: it is kept, not leaked)
+    mg_layout(g, g->arena);
+    const size_t RT = (size_t)g->max_batch * h->T, R = 4 * RT;
+    const size_t C = (size_t)std::max(3 * h->d, h->ff);
+    const size_t n64 = al64(RT) + al64(RT * MTM_LOSS_PART) + (R / 64 + 2) * 2 * C;
+    if (!g->arena64) CHK(dmalloc(&g->arena64, n64));
+    g->raw_returns = g->arena64;
+    g->part = g->raw_returns + al64(RT);
+    g->colpart = g->part + al64(RT * MTM_LOSS_PART);
+    g->ready = true;
+    return 0;
+}
+
+struct Run {
+    Obj* g;
+    m3pc_handle* h;
+    hipStream_t st;
+    int B, T, d, ff, Le;
+    u64 bits[4];
+    int kept[4], eoff[4];
+    float* Wt(const std::string& n) const { return W(h, n).f; }
+    float* Gr(const std::string& n) const { return g->grad + g->par[g->idx.at(n)].off; }
+};
+
+const RMap NOMAP = {0, 0, 0};
+
+void run_gemm(const Run& r, GemmG& p) {
+    const long long tiles = (long long)((p.M + 31) / 32) * ((p.N + 31) / 32);
+    if (tiles <= 0) return;
+    for (GOp* op : {&p.A, &p.B})
+        op->vec = op->s_k == 1 && !op->map_k && op->s_o % 4 == 0 && ((uintptr_t)op->p & 15) == 0 ? 1 : 0;
+    if (p.splitk)
+        hipLaunchKernelGGL(mg_gemm_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, r.st, p);
+    else
+        hipLaunchKernelGGL(mg_gemm_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, r.st, p);
+}
+GemmG gemm_zero() {
+    GemmG p;
+    memset(&p, 0, sizeof(p));
+    return p;
+}
+// C (M, N) = X (M, K) Wt (N, K)^T
+GemmG gemm_fwd(const float* X, long long ldx, RMap xmap, const float* Wt, int M, int N, int K, float* C, long long ldc, RMap cmap, const float* bias) {
+    GemmG p = gemm_zero();
+    p.A = {X, ldx, 1, xmap, 0, 0};
+    p.B = {Wt, (long long)K, 1, NOMAP, 0, 0};
+    p.C = C;
+    p.ldc = ldc;
+    p.cmap = cmap;
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    p.bias = bias;
+    return p;
+}
+// dX (M, N) = dY (M, K) Wt (K, N)
+GemmG gemm_dx(const float* dY, long long ldy, RMap ymap, const float* Wt, int M, int N, int K, float* C, long long ldc, RMap cmap) {
+    GemmG p = gemm_zero();
+    p.A = {dY, ldy, 1, ymap, 0, 0};
+    p.B = {Wt, 1, (long long)N, NOMAP, 0, 0};
+    p.C = C;
+    p.ldc = ldc;
+    p.cmap = cmap;
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    return p;
+}
+// dW (M, N) = dY (rows, M)^T X (rows, N)
+GemmG gemm_dw(const float* dY, long long ldy, RMap ymap, const float* X, long long ldx, RMap xmap, int M, int N, int rows, float* C) {
+    GemmG p = gemm_zero();
+    p.A = {dY, 1, ldy, ymap, 1, 0};
+    p.B = {X, 1, ldx, xmap, 1, 0};
+    p.splitk = 1;
+    p.C = C;
+    p.ldc = N;
+    p.cmap = NOMAP;
+    p.M = M;
+    p.N = N;
+    p.K = rows;
+    return p;
+}
+
+void run_ln_fwd(const Run& r, const float* X, RMap xmap, const std::string& name, float* Y, float* st, int rows) {
+    LnG p;
+    memset(&p, 0, sizeof(p));
+    p.X = X;
+    p.xmap = xmap;
+    p.g = r.Wt(name + ".weight");
+    p.b = r.Wt(name + ".bias");
+    p.Y = Y;
+    p.st = st;
+    p.rows = rows;
+    p.d = r.d;
+    hipLaunchKernelGGL(mg_ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, r.st, p);
+}
+
+// sums over the rows (s, j) (ColG) of dY into out0 and, with X / st, of dY xhat into out1
+void run_colsum(const Run& r, const float* dY, bool dy_compact, long long ldy, const float* X, const float* st, int nseq, int L, int j0, int n,
+                u64 sel, int C, float* out0, float* out1) {
+    const long long total = (long long)nseq * n;
+    if (total <= 0) return;  // (the gradient buffers start as zeros)
+    ColG p;
+    memset(&p, 0, sizeof(p));
+    p.dY = dY;
+    p.dy_compact = dy_compact ? 1 : 0;
+    p.ldy = ldy;
+    p.X = X;
+    p.st = st;
+    p.nseq = nseq;
+    p.L = L;
+    p.j0 = j0;
+    p.n = n;
+    p.sel = sel;
+    p.C = C;
+    p.part = r.g->colpart;
+    p.out0 = out0;
+    p.out1 = out1;
+    p.chunks = (int)((total + 63) / 64);
+    hipLaunchKernelGGL(mg_colsum_kernel, dim3((C + 255) / 256, p.chunks), dim3(256), 0, r.st, p);
+    hipLaunchKernelGGL(mg_colsum_fin_kernel, dim3((C + 255) / 256), dim3(256), 0, r.st, p);
+}
+void run_colsum_rows(const Run& r, const float* dY, int rows, int C, float* out0) {
+    run_colsum(r, dY, false, C, nullptr, nullptr, rows, 1, 0, 1, ~0ull, C, out0, nullptr);
+}
+
+// LayerNorm `name` backward over `rows` compact rows of dY: the weight / bias gradients, and dX (rows xmap(r)) = or += the input's
+void run_ln_bwd(const Run& r, const float* dY, const float* X, RMap xmap, const float* st, const std::string& name, float* dX, int rows,
+                bool accumulate) {
+    if (xmap.rpg == 0)
+        run_colsum(r, dY, false, r.d, X, st, rows, 1, 0, 1, ~0ull, r.d, r.Gr(name + ".bias"), r.Gr(name + ".weight"));
+    else
+        run_colsum(r, dY, true, r.d, X, st, rows / xmap.rpg, xmap.gstride, xmap.off, xmap.rpg, ~0ull, r.d, r.Gr(name + ".bias"),
+                   r.Gr(name + ".weight"));
+    LnG p;
+    memset(&p, 0, sizeof(p));
+    p.X = X;
+    p.xmap = xmap;
+    p.g = r.Wt(name + ".weight");
+    p.st = const_cast<float*>(st);
+    p.dY = dY;
+    p.dX = dX;
+    p.rows = rows;
+    p.d = r.d;
+    p.accumulate = accumulate ? 1 : 0;
+    hipLaunchKernelGGL(mg_ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, r.st, p);
+}
+
+AttG att_params(const Run& r, const Obj::Lay& y, int L) {
+    AttG a;
+    memset(&a, 0, sizeof(a));
+    a.QKV = y.QKV;
+    a.P = y.P;
+    a.O = y.O;
+    a.dO = r.g->dO;
+    a.dQKV = r.g->dQKV;
+    a.B = r.B;
+    a.L = L;
+    a.d = r.d;
+    a.nh = r.h->nh;
+    a.hd = r.h->hd;
+    a.scale = 1.0f / sqrtf((float)r.h->hd);
+    return a;
+}
+
+void block_fwd(const Run& r, const std::string& pfx, const Obj::Lay& y, float* Xout, int L) {
+    const int R = r.B * L, d = r.d, ff = r.ff;
+    run_ln_fwd(r, y.Xin, NOMAP, pfx + ".norm1", y.Hn1, y.st1, R);
+    GemmG p = gemm_fwd(y.Hn1, d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_weight"), R, 3 * d, d, y.QKV, 3 * d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_bias"));
+    run_gemm(r, p);
+    const AttG a = att_params(r, y, L);
+    hipLaunchKernelGGL(mg_attn_fwd_kernel, dim3((unsigned)(((long long)r.B * a.nh * L + 3) / 4)), dim3(256), 0, r.st, a);
+    p = gemm_fwd(y.O, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.weight"), R, d, d, y.X1, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.bias"));
+    p.res = y.Xin;
+    run_gemm(r, p);
+    run_ln_fwd(r, y.X1, NOMAP, pfx + ".norm2", y.Hn2, y.st2, R);
+    p = gemm_fwd(y.Hn2, d, NOMAP, r.Wt(pfx + ".linear1.weight"), R, ff, d, y.Fpre, ff, NOMAP, r.Wt(pfx + ".linear1.bias"));
+    p.gelu_out = y.Fact;
+    run_gemm(r, p);
+    p = gemm_fwd(y.Fact, ff, NOMAP, r.Wt(pfx + ".linear2.weight"), R, d, ff, Xout, d, NOMAP, r.Wt(pfx + ".linear2.bias"));
+    p.res = y.X1;
+    run_gemm(r, p);
+}
+
+// g->dX: in, the gradient of the block's output; out, of its input
+void block_bwd(const Run& r, const std::string& pfx, const Obj::Lay& y, int L) {
+    Obj* g = r.g;
+    const int R = r.B * L, d = r.d, ff = r.ff;
+    GemmG p = gemm_dx(g->dX, d, NOMAP, r.Wt(pfx + ".linear2.weight"), R, ff, d, g->dF, ff, NOMAP);
+    p.gelu_aux = y.Fpre;
+    run_gemm(r, p);
+    p = gemm_dw(g->dX, d, NOMAP, y.Fact, ff, NOMAP, d, ff, R, r.Gr(pfx + ".linear2.weight"));
+    run_gemm(r, p);
+    run_colsum_rows(r, g->dX, R, d, r.Gr(pfx + ".linear2.bias"));
+    p = gemm_dx(g->dF, ff, NOMAP, r.Wt(pfx + ".linear1.weight"), R, d, ff, g->dH, d, NOMAP);
+    run_gemm(r, p);
+    p = gemm_dw(g->dF, ff, NOMAP, y.Hn2, d, NOMAP, ff, d, R, r.Gr(pfx + ".linear1.weight"));
+    run_gemm(r, p);
+    run_colsum_rows(r, g->dF, R, ff, r.Gr(pfx + ".linear1.bias"));
+    run_ln_bwd(r, g->dH, y.X1, NOMAP, y.st2, pfx + ".norm2", g->dX, R, true);
+    p = gemm_dx(g->dX, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.weight"), R, d, d, g->dO, d, NOMAP);
+    run_gemm(r, p);
+    p = gemm_dw(g->dX, d, NOMAP, y.O, d, NOMAP, d, d, R, r.Gr(pfx + ".self_attn.out_proj.weight"));
+    run_gemm(r, p);
+    run_colsum_rows(r, g->dX, R, d, r.Gr(pfx + ".self_attn.out_proj.bias"));
+    const AttG a = att_params(r, y, L);
+    const dim3 ag((unsigned)(((long long)r.B * a.nh * L + 3) / 4));
+    hipLaunchKernelGGL(mg_attn_col_kernel, ag, dim3(256), 0, r.st, a, 0);
+    hipLaunchKernelGGL(mg_attn_row_kernel, ag, dim3(256), 0, r.st, a);
+    hipLaunchKernelGGL(mg_attn_col_kernel, ag, dim3(256), 0, r.st, a, 1);
+    p = gemm_dx(g->dQKV, 3 * d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_weight"), R, d, 3 * d, g->dH, d, NOMAP);
+    run_gemm(r, p);
+    p = gemm_dw(g->dQKV, 3 * d, NOMAP, y.Hn1, d, NOMAP, 3 * d, d, R, r.Gr(pfx + ".self_attn.in_proj_weight"));
+    run_gemm(r, p);
+    run_colsum_rows(r, g->dQKV, R, 3 * d, r.Gr(pfx + ".self_attn.in_proj_bias"));
+    run_ln_bwd(r, g->dH, y.Xin, NOMAP, y.st1, pfx + ".norm1", g->dX, R, true);
+}
+
+EmbG emb_params(const Run& r) {
+    EmbG e;
+    memset(&e, 0, sizeof(e));
+    for (int k = 0; k < 4; ++k) {
+        const std::string kn = KEYN[k];
+        e.tok[k] = r.g->tok[k];
+        e.W[k] = r.Wt("encoder_embed_dict." + kn + ".weight");
+        e.bias[k] = r.Wt("encoder_embed_dict." + kn + ".bias");
+        e.pdim[k] = r.Wt("encoder_per_dim_encoding." + kn);
+        e.mtok[k] = r.Wt("mask_token_dict." + kn);
+        e.bits[k] = r.bits[k];
+        e.kept[k] = r.kept[k];
+        e.eoff[k] = r.eoff[k];
+        e.feat[k] = r.h->feat[k];
+    }
+    e.pos = r.Wt("pos_embed");
+    e.B = r.B;
+    e.T = r.T;
+    e.d = r.d;
+    e.Le = r.Le;
+    return e;
+}
+
+unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
+
+// everything behind the refusals: the batch is in g->tok-able form (raw rows), the masks are bits
+int mg_run(Obj* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
+           const u64 bits[4], const float* eps, float entropy_reg, int flags, int loss_keys, float* record, hipStream_t st) {
+    m3pc_handle* h = g->h;
+    Run r;
+    r.g = g;
+    r.h = h;
+    r.st = st;
+    r.B = batch;
+    r.T = h->T;
+    r.d = h->d;
+    r.ff = h->ff;
+    r.Le = 0;
+    for (int k = 0; k < 4; ++k) {
+        r.bits[k] = bits[k];
+        r.kept[k] = __builtin_popcountll(bits[k]);
+        r.eoff[k] = r.Le;
+        r.Le += r.kept[k];
+    }
+    const int T = r.T, d = r.d, S = h->S, A = h->A, L4 = 4 * T, RT = batch * T, Rd = batch * L4, Re = batch * r.Le;
+    const int nE = h->dm.n_enc_layer, nD = h->dm.n_dec_layer;
+    const int HK[3] = {M3PC_STATES, M3PC_REWARDS, M3PC_RETURNS};
+    HIPCHK(hipMemsetAsync(g->grad, 0, g->grad_floats * sizeof(float), st));
+
+    // ---------------- forward
+    const void* raw[4] = {states, actions, rewards, returns};
+    for (int k = 0; k < 4; ++k)
+        launch_tokenize(raw[k], k == M3PC_RETURNS ? (returns_f64 ? 1 : 0) : 0, g->tok[k], RT, h->feat[k], h->tok_mean[k], h->tok_std[k],
+                        h->tok_norm[k], st);
+    EmbG e = emb_params(r);
+    float* enc0 = nE ? g->lay[0].Xin : g->XencOut;
+    e.X = enc0;
+    hipLaunchKernelGGL(mg_embed_kernel, dim3(blocks256((long long)Re * d)), dim3(256), 0, st, e);
+    for (int l = 0; l < nE; ++l)
+        block_fwd(r, "encoder.layers." + std::to_string(l), g->lay[l], l + 1 < nE ? g->lay[l + 1].Xin : g->XencOut, r.Le);
+    run_ln_fwd(r, g->XencOut, NOMAP, "encoder.norm", g->EncN, g->st_enc, Re);
+    e.src = g->EncN;
+    e.dst = g->Zin;
+    hipLaunchKernelGGL(mg_gather_kernel, dim3(blocks256((long long)Rd * d)), dim3(256), 0, st, e);
+    float* dec0 = nD ? g->lay[nE].Xin : g->XdecOut;
+    for (int k = 0; k < 4; ++k) {
+        const std::string kn = KEYN[k];
+        const RMap km = {T, L4, k * T};
+        GemmG p = gemm_fwd(g->Zin, d, km, r.Wt("decoder_embed_dict." + kn + ".weight"), RT, d, d, dec0, d, km, r.Wt("decoder_embed_dict." + kn + ".bias"));
+        p.bias2 = r.Wt("decoder_per_dim_encoding." + kn);
+        p.pos = r.Wt("pos_embed");
+        p.pos_T = T;
+        run_gemm(r, p);
+    }
+    for (int l = 0; l < nD; ++l)
+        block_fwd(r, "decoder.layers." + std::to_string(l), g->lay[nE + l], l + 1 < nD ? g->lay[nE + l + 1].Xin : g->XdecOut, L4);
+    run_ln_fwd(r, g->XdecOut, NOMAP, "decoder.norm", g->DecN, g->st_dec, Rd);
+    for (int j = 0; j < 3; ++j) {
+        const int k = HK[j], F = h->feat[k];
+        const std::string hn = std::string("output_head_dict.") + KEYN[k];
+        const RMap km = {T, L4, k * T};
+        run_ln_fwd(r, g->DecN, km, hn + ".0", g->Hh[j], g->st_h[j], RT);
+        GemmG p = gemm_fwd(g->Hh[j], d, NOMAP, r.Wt(hn + ".1.weight"), RT, d, d, g->Hpre[j], d, NOMAP, r.Wt(hn + ".1.bias"));
+        p.gelu_out = g->Hact[j];
+        run_gemm(r, p);
+        p = gemm_fwd(g->Hact[j], d, NOMAP, r.Wt(hn + ".3.weight"), RT, F, d, g->pred[j], F, NOMAP, r.Wt(hn + ".3.bias"));
+        run_gemm(r, p);
+    }
+    const RMap am = {T, L4, M3PC_ACTIONS * T};
+    {
+        GemmG p = gemm_fwd(g->DecN, d, am, r.Wt("output_head_dict.actions.mu.weight"), RT, A, d, g->mu, A, NOMAP, r.Wt("output_head_dict.actions.mu.bias"));
+        run_gemm(r, p);
+        p = gemm_fwd(g->DecN, d, am, r.Wt("output_head_dict.actions.log_std.weight"), RT, A, d, g->ls, A, NOMAP, r.Wt("output_head_dict.actions.log_std.bias"));
+        run_gemm(r, p);
+        hipLaunchKernelGGL(mg_std_kernel, dim3(blocks256((long long)RT * A)), dim3(256), 0, st, g->ls, g->sd, (long long)RT * A);
+    }
+    {
+        MtmLossP p;
+        memset(&p, 0, sizeof(p));
+        for (int j = 0; j < 3; ++j) p.pred[j] = g->pred[j];
+        p.mu = g->mu;
+        p.sd = g->sd;
+        for (int k = 0; k < 4; ++k) {
+            p.tgt[k] = g->tok[k];
+            p.mask[k] = bits[k];
+        }
+        p.eps = eps;
+        p.batch = batch;
+        p.T = T;
+        p.S = S;
+        p.A = A;
+        p.flags = flags;
+        p.loss_keys = loss_keys;
+        p.entropy_reg = entropy_reg;
+        p.part = g->part;
+        p.record = record ? record : g->rec;
+        launch_mtm_loss(p, st);
+    }
+    CHK(check_launch("mtm_grad forward"));
+
+    // ---------------- backward
+    {
+        LossBwdG p;
+        memset(&p, 0, sizeof(p));
+        for (int j = 0; j < 3; ++j) {
+            p.pred[j] = g->pred[j];
+            p.dpred[j] = g->dpred[j];
+        }
+        p.mu = g->mu;
+        p.sd = g->sd;
+        p.ls = g->ls;
+        p.eps = eps;
+        p.dmu = g->dmu;
+        p.dls = g->dls;
+        for (int k = 0; k < 4; ++k) {
+            p.tgt[k] = g->tok[k];
+            p.mask[k] = bits[k];
+        }
+        p.batch = batch;
+        p.T = T;
+        p.S = S;
+        p.A = A;
+        p.flags = flags;
+        p.loss_keys = loss_keys;
+        p.entropy_reg = entropy_reg;
+        p.inv_cnt = (float)(1.0 / ((double)batch * (double)(T - r.kept[M3PC_ACTIONS]) * (double)A));
+        hipLaunchKernelGGL(mg_loss_bwd_kernel, dim3(blocks256((long long)RT * (S + 2 + A))), dim3(256), 0, st, p);
+    }
+    float* dDecN = g->dO;
+    HIPCHK(hipMemsetAsync(dDecN, 0, (size_t)Rd * d * sizeof(float), st));
+    for (int j = 0; j < 3; ++j) {
+        const int k = HK[j], F = h->feat[k];
+        if (!((loss_keys >> k) & 1)) continue;  // (a key outside loss_keys: its head's gradients stay the zeros they start as)
+        const std::string hn = std::string("output_head_dict.") + KEYN[k];
+        const RMap km = {T, L4, k * T};
+        GemmG p = gemm_dx(g->dpred[j], F, NOMAP, r.Wt(hn + ".3.weight"), RT, d, F, g->dh1, d, NOMAP);
+        p.gelu_aux = g->Hpre[j];
+        run_gemm(r, p);
+        p = gemm_dw(g->dpred[j], F, NOMAP, g->Hact[j], d, NOMAP, F, d, RT, r.Gr(hn + ".3.weight"));
+        run_gemm(r, p);
+        run_colsum_rows(r, g->dpred[j], RT, F, r.Gr(hn + ".3.bias"));
+        p = gemm_dx(g->dh1, d, NOMAP, r.Wt(hn + ".1.weight"), RT, d, d, g->dh2, d, NOMAP);
+        run_gemm(r, p);
+        p = gemm_dw(g->dh1, d, NOMAP, g->Hh[j], d, NOMAP, d, d, RT, r.Gr(hn + ".1.weight"));
+        run_gemm(r, p);
+        run_colsum_rows(r, g->dh1, RT, d, r.Gr(hn + ".1.bias"));
+        run_ln_bwd(r, g->dh2, g->DecN, km, g->st_h[j], hn + ".0", dDecN, RT, false);
+    }
+    {
+        const std::string hm = "output_head_dict.actions.mu", hl = "output_head_dict.actions.log_std";
+        GemmG p = gemm_dx(g->dmu, A, NOMAP, r.Wt(hm + ".weight"), RT, d, A, dDecN, d, am);
+        run_gemm(r, p);
+        p = gemm_dx(g->dls, A, NOMAP, r.Wt(hl + ".weight"), RT, d, A, dDecN, d, am);
+        p.accumulate = 1;
+        run_gemm(r, p);
+        p = gemm_dw(g->dmu, A, NOMAP, g->DecN, d, am, A, d, RT, r.Gr(hm + ".weight"));
+        run_gemm(r, p);
+        p = gemm_dw(g->dls, A, NOMAP, g->DecN, d, am, A, d, RT, r.Gr(hl + ".weight"));
+        run_gemm(r, p);
+        run_colsum_rows(r, g->dmu, RT, A, r.Gr(hm + ".bias"));
+        run_colsum_rows(r, g->dls, RT, A, r.Gr(hl + ".bias"));
+    }
+    run_ln_bwd(r, dDecN, g->XdecOut, NOMAP, g->st_dec, "decoder.norm", g->dX, Rd, false);
+    for (int l = nD - 1; l >= 0; --l) block_bwd(r, "decoder.layers." + std::to_string(l), g->lay[nE + l], L4);
+    for (int k = 0; k < 4; ++k) {  // the decoder embedding: g->dX is the gradient of its output, g->dH becomes that of its input
+        const std::string kn = KEYN[k];
+        const RMap km = {T, L4, k * T};
+        float* gb = r.Gr("decoder_embed_dict." + kn + ".bias");
+        run_colsum(r, g->dX, false, d, nullptr, nullptr, batch, L4, k * T, T, ~0ull, d, gb, nullptr);
+        HIPCHK(hipMemcpyAsync(r.Gr("decoder_per_dim_encoding." + kn), gb, (size_t)d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        GemmG p = gemm_dx(g->dX, d, km, r.Wt("decoder_embed_dict." + kn + ".weight"), RT, d, d, g->dH, d, km);
+        run_gemm(r, p);
+        p = gemm_dw(g->dX, d, km, g->Zin, d, km, d, d, RT, r.Gr("decoder_embed_dict." + kn + ".weight"));
+        run_gemm(r, p);
+        const u64 all = T == 64 ? ~0ull : (1ull << T) - 1ull, hidden = ~bits[k] & all;
+        if (hidden) run_colsum(r, g->dH, false, d, nullptr, nullptr, batch, L4, k * T, T, hidden, d, r.Gr("mask_token_dict." + kn), nullptr);
+    }
+    float* dEncN = g->dO;
+    e.src = g->dH;
+    e.dst = dEncN;
+    hipLaunchKernelGGL(mg_scatter_kernel, dim3(blocks256((long long)Re * d)), dim3(256), 0, st, e);
+    run_ln_bwd(r, dEncN, g->XencOut, NOMAP, g->st_enc, "encoder.norm", g->dX, Re, false);
+    for (int l = nE - 1; l >= 0; --l) block_bwd(r, "encoder.layers." + std::to_string(l), g->lay[l], r.Le);
+    for (int k = 0; k < 4; ++k) {
+        if (!r.kept[k]) continue;  // (a fully hidden key: exact zeros)
+        const std::string kn = KEYN[k];
+        float* gb = r.Gr("encoder_embed_dict." + kn + ".bias");
+        run_colsum(r, g->dX, false, d, nullptr, nullptr, batch, r.Le, r.eoff[k], r.kept[k], ~0ull, d, gb, nullptr);
+        HIPCHK(hipMemcpyAsync(r.Gr("encoder_per_dim_encoding." + kn), gb, (size_t)d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        float* tokv = g->dF;  // (scratch: the layers are done with it)
+        hipLaunchKernelGGL(mg_tokv_kernel, dim3(blocks256((long long)batch * r.kept[k] * h->feat[k])), dim3(256), 0, st, e, k, tokv);
+        const RMap em = {r.kept[k], r.Le, r.eoff[k]};
+        GemmG p = gemm_dw(g->dX, d, em, tokv, h->feat[k], NOMAP, d, h->feat[k], batch * r.kept[k], r.Gr("encoder_embed_dict." + kn + ".weight"));
+        run_gemm(r, p);
+    }
+    CHK(check_launch("mtm_grad backward"));
+    g->have_grad = true;
+    return 0;
+}
+
+// what the calls refuse alike, before any HIP call; bits[k]: the mask of key k, bit t = token t visible
+int mg_check(const Obj* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who, u64 bits[4]) {
+    const m3pc_handle* h = g->h;
+    if (batch < 1 || batch > g->max_batch) return fail(M3PC_EINVAL, "%s: batch %d outside [1, max_batch=%d]", who, batch, g->max_batch);
+    if (flags & ~(M3PC_MTM_NORM_L2 | M3PC_MTM_CLIP_ACTIONS)) return fail(M3PC_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
+    if (loss_keys < 0 || loss_keys > 15) return fail(M3PC_EINVAL, "%s: loss_keys %d outside [0, 15]", who, loss_keys);
+    const int T = h->dm.traj_length;
+    if (T < 1 || T > 64) return fail(M3PC_EINVAL, "%s: traj_length %d outside [1, 64]", who, T);
+    int kept = 0;
+    for (int k = 0; k < 4; ++k) {
+        if (!masks[k]) return fail(M3PC_EINVAL, "%s: null mask of '%s'", who, KEYN[k]);
+        bits[k] = 0;
+        for (int t = 0; t < T; ++t) {
+            if (masks[k][t] > 1) return fail(M3PC_EINVAL, "%s: mask byte %d of '%s' is %d, not 0 or 1", who, t, KEYN[k], (int)masks[k][t]);
+            bits[k] |= (u64)masks[k][t] << t;
+            kept += masks[k][t];
+        }
+    }
+    if (kept == 0) return fail(M3PC_EINVAL, "%s: mask keeps no token", who);
+    return 0;
+}
+
+int mg_state(const Obj* g, const char* who) {
+    if (!g->h->weights_loaded) return fail(M3PC_ESTATE, "%s: weights not loaded", who);
+    for (int k = 0; k < 4; ++k)
+        if (!g->h->tok_set[k]) return fail(M3PC_ESTATE, "%s: tokenizer '%s' not set", who, KEYN[k]);
+    return 0;
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int m3pc_mtm_grad_create(m3pc_handle* h, int max_batch, struct m3pc_mtm_grad** out) {
+    if (!h || !out) return fail(M3PC_EINVAL, "m3pc_mtm_grad_create: null argument");
+    if (max_batch < 1) return fail(M3PC_EINVAL, "m3pc_mtm_grad_create: max_batch %d < 1", max_batch);
+    if (h->T < 1 || h->T > 64 || h->hd < 1) return fail(M3PC_EINVAL, "m3pc_mtm_grad_create: traj_length %d outside [1, 64]", h->T);
+    if ((long long)max_batch * 4 * h->T * std::max(3 * h->d, h->ff) > 0x7fffffffll)
+        return fail(M3PC_EINVAL, "m3pc_mtm_grad_create: max_batch %d is too large for these sizes", max_batch);
+    Obj* g = new Obj();
+    g->h = h;
+    g->max_batch = max_batch;
+    size_t at = 0;
+    for (auto& kv : h->w) {
+        if (kv.first == "pos_embed") continue;
+        g->idx[kv.first] = (int)g->par.size();
+        g->par.push_back({kv.first, kv.second.numel, at});
+        at += al64((size_t)kv.second.numel);
+    }
+    g->grad_floats = at;
+    *out = g;
+    return 0;
+}
+
+int m3pc_mtm_grad_destroy(struct m3pc_mtm_grad* g) {
+    if (!g) return 0;
+    if (g->arena || g->arena64) {
+        (void)hipSetDevice(g->h->device);
+        (void)hipDeviceSynchronize();
+        if (g->arena) (void)hipFree(g->arena);
+        if (g->arena64) (void)hipFree(g->arena64);
+    }
+    delete g;
+    return 0;
+}
+
+int m3pc_mtm_grad(struct m3pc_mtm_grad* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns,
+                  int returns_f64, const unsigned char* const masks[4], const float* eps, float entropy_reg, int flags, int loss_keys,
+                  float* record, void* stream) {
+    if (!g || !states || !actions || !rewards || !returns || !masks || !eps) return fail(M3PC_EINVAL, "m3pc_mtm_grad: null argument");
+    u64 bits[4];
+    CHK(mg_check(g, batch, masks, flags, loss_keys, "m3pc_mtm_grad", bits));
+    CHK(mg_state(g, "m3pc_mtm_grad"));
+    CHK(mg_ensure(g));
+    return mg_run(g, batch, states, actions, rewards, returns, returns_f64, bits, eps, entropy_reg, flags, loss_keys, record, (hipStream_t)stream);
+}
+
+int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
+                         int index_on_device, unsigned long long seed, unsigned long long step, const unsigned char* const masks[4],
+                         const float* eps, float entropy_reg, int flags, int loss_keys, float* record, int* out_traj, int* out_start,
+                         void* stream) {
+    if (!g || !rb || !masks) return fail(M3PC_EINVAL, "m3pc_mtm_grad_replay: null argument");
+    u64 bits[4];
+    CHK(mg_check(g, batch, masks, flags, loss_keys, "m3pc_mtm_grad_replay", bits));
+    m3pc_handle* h = g->h;
+    int S = 0, A = 0, dev = 0;
+    replay_sizes(rb, &S, &A, &dev);
+    const int L = replay_segment_length(rb);
+    if (S != h->dm.state_dim || A != h->dm.action_dim || dev != h->device || L != h->dm.traj_length)
+        return fail(M3PC_EINVAL, "m3pc_mtm_grad_replay: the buffer (S %d, A %d, segment_length %d, device %d) does not fit the handle (%d, %d, T %d, %d)",
+                    S, A, L, dev, h->dm.state_dim, h->dm.action_dim, h->dm.traj_length, h->device);
+    CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, "m3pc_mtm_grad_replay"));
+    CHK(mg_state(g, "m3pc_mtm_grad_replay"));
+    CHK(mg_ensure(g));
+    hipStream_t st = (hipStream_t)stream;
+    CHK(m3pc_replay_sample_segments(rb, batch, mode, traj_index, start_index, index_on_device, seed, step, g->raw[0], g->raw[1], g->raw[2],
+                                    g->raw_returns, 0, out_traj, out_start, stream));
+    if (!eps) {  // array 0 of the generator of m3pc_draw_variates at (seed, step): batch * T rows of A normals
+        launch_variates(seed, step, 0, 0, (long long)batch * h->T * h->A, g->eps, st);
+        CHK(check_launch("mtm_grad variates"));
+        eps = g->eps;
+    }
+    return mg_run(g, batch, g->raw[0], g->raw[1], g->raw[2], g->raw_returns, 1, bits, eps, entropy_reg, flags, loss_keys, record, st);
+}
+
+int m3pc_mtm_grad_export(struct m3pc_mtm_grad* g, const m3pc_named_tensor* tensors, int n, void* stream) {
+    if (!g || !tensors || n < 0) return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: null argument");
+    for (int i = 0; i < n; ++i) {
+        const m3pc_named_tensor& t = tensors[i];
+        if (!t.name || !t.data) return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: entry %d has no name or no data", i);
+        auto it = g->idx.find(t.name);
+        if (it == g->idx.end()) return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: '%s' is not a parameter", t.name);
+        if (t.numel != g->par[it->second].numel)
+            return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: '%s' has %lld elements, expected %lld", t.name, t.numel, g->par[it->second].numel);
+    }
+    if (!g->have_grad) return fail(M3PC_ESTATE, "m3pc_mtm_grad_export: no gradient call was made");
+    HIPCHK(hipSetDevice(g->h->device));
+    hipStream_t st = (hipStream_t)stream;
+    for (int i = 0; i < n; ++i) {
+        const m3pc_named_tensor& t = tensors[i];
+        const Obj::Par& p = g->par[g->idx.at(t.name)];
+        HIPCHK(hipMemcpyAsync(const_cast<float*>(t.data), g->grad + p.off, (size_t)p.numel * sizeof(float),
+                              t.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    }
+    return 0;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

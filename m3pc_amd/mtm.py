@@ -1,7 +1,7 @@
 """Host-side mirror of the reference model interface (research/omtm/models/mtm_model.py:200-221,
 324-437, 440-532, 593-607): ``omtmConfig.create(data_shapes, traj_length, discrete_map) -> omtm``,
 ``omtm.forward(trajectories, masks)`` and ``omtm.forward_loss(targets, preds, masks, ...)``.  The transformer
-and the loss live in libm3pc_hip.so; the backward pass and the optimizers do not exist here.
+and the loss live in libm3pc_hip.so; the backward pass is m3pc_amd/mtm_grad.py (``DeviceMTMGrad``), the optimizers stay torch's.
 """
 from __future__ import annotations
 

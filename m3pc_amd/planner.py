@@ -1296,7 +1296,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
         under ``masks`` (None: drawn as the reference draws them, from NumPy's global generator) and scored.  Returns the
         reference's (loss, losses, masked_losses, masked_c_losses, entropy) with its dict contents -- "states", "entropy", "nll"
         for the usual key order (the reference returns from inside its key loop) -- as 0-d device tensors.  eps: the (B,T,A) normals
-        of the sampled entropy (None: torch.randn).  Forward only: there is no backward pass to call on the result."""
+        of the sampled entropy (None: torch.randn).  Forward only: ``mtm_update`` is the call that also differentiates."""
         from .masks import create_random_autoregressive_mask
         from .mtm import raw_batch_loss
         if any(discrete_map.get(k, False) for k in batch):
@@ -1304,6 +1304,61 @@ class HipPlanner(GoalMixin, LockstepMixin):
         if masks is None:
             masks = create_random_autoregressive_mask(data_shapes, self.cfg.mask_ratio, self.cfg.traj_length, self.cfg.p_weights)
         return raw_batch_loss(self.handle, batch, masks, float(entropy_reg), "finetune", eps, capi.PREC_FP32)
+
+    def mtm_update(self, batch, data_shapes, discrete_map, model, optimizer, scheduler, temp_optimizer, masks=None, eps=None,
+                   dropout=None, sync=True):
+        """Learner.mtm_update (finetune_omtm/learner.py:506-538) with its forward and ``loss.backward()`` in one library call
+        (m3pc_mtm_grad): the gradients of ``model``'s parameters come from the device (``DeviceMTMGrad.backward_into``), then
+        ``optimizer.step()``, ``scheduler.step()`` and the temperature step on ``temperature * (entropy - target_entropy)`` with the
+        device's entropy as a constant -- the optimizers are torch's.  Returns the reference's ``log_dict`` (same keys).
+        ``model``: the torch module being trained (``temperature()``, ``target_entropy``, ``state_dict(keep_vars=True)``); with
+        ``sync`` (the default) the WHOLE state_dict is uploaded to the handle before every step -- a full ``m3pc_load_weights``, its stream
+        synchronise included; a caller that steps often should follow the tensors itself and pass ``sync=False``, as ``attach`` does
+        (its ``_sync`` sends only what the last optimizer step moved).
+        THE GRADIENT IS THE EVAL-MODE MODEL'S: NO DROPOUT.  A model in training mode whose config has ``dropout > 0`` is refused
+        unless ``dropout="eval"`` says that a step without dropout is what the caller wants."""
+        from .masks import create_random_autoregressive_mask
+        from .mtm import form_settings, loss_tuple
+        from .mtm_grad import DeviceMTMGrad
+        p_drop = float(_cfg_get(getattr(model, "config", None), "dropout", 0) or 0)
+        if getattr(model, "training", False) and p_drop > 0 and dropout != "eval":
+            raise capi.M3pcError(f"mtm_update differentiates the eval-mode model (no dropout) but the model trains with dropout={p_drop}: "
+                                 "pass dropout=\"eval\" to take the step without dropout, or keep loss.backward() in torch")
+        if any(discrete_map.get(k, False) for k in batch):
+            raise capi.M3pcError("discrete heads are not used by any m3pc config and are not supported")
+        if masks is None:
+            masks = create_random_autoregressive_mask(data_shapes, self.cfg.mask_ratio, self.cfg.traj_length, self.cfg.p_weights)
+        if sync:
+            self.load_state_dict({k: v.detach() for k, v in model.state_dict().items()})
+        B = int(batch["states"].shape[0])
+        g = getattr(self, "_mtm_grad", None)
+        if g is None or g.max_batch < B:
+            if g is not None:
+                g.close()
+            g = self._mtm_grad = DeviceMTMGrad(self, B)
+        entropy_reg = float(model.temperature().detach())
+        model.zero_grad(set_to_none=True)
+        rec = g.backward_into(model, batch, masks, entropy_reg, "finetune", eps, unused="none")  # (.grad = None where the reference leaves it)
+        loss, losses, masked_losses, masked_c_losses, entropy = loss_tuple(rec, form_settings("finetune", list(batch.keys()))[2])
+        log_dict = {}
+        for k, l in losses.items():
+            log_dict[f"train/loss_{k}"] = l
+            if k in masked_losses:
+                log_dict[f"train/masked_loss_{k}"] = masked_losses[k]
+            if k in masked_c_losses:
+                log_dict[f"train/masked_c_loss_{k}"] = masked_c_losses[k]
+        log_dict["train/loss"] = loss.item()
+        log_dict["train/lr"] = scheduler.get_last_lr()[0]
+        optimizer.step()
+        scheduler.step()
+        temp_optimizer.zero_grad()
+        temperature = model.temperature()
+        temperature_loss = temperature * (entropy.detach().to(temperature.device, temperature.dtype) - model.target_entropy)
+        temperature_loss.backward()
+        temp_optimizer.step()
+        log_dict["train/temperature"] = model.temperature().item()
+        log_dict["train/entropy"] = entropy.item()
+        return log_dict
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1320,7 +1375,7 @@ def _versions(module):
 
 
 def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None, generator: Optional[torch.Generator] = None,
-           native_step: bool = False, eval_tol: Optional[float] = None, **planner_kw):
+           native_step: bool = False, eval_tol: Optional[float] = None, mtm_update: bool = False, **planner_kw):
     """Rebind the plan path of a reference-style ``Learner`` onto the HIP library.
 
     precision: "bf16" (default since round 6: the configuration the headline is measured on) -- the bf16 candidate pass with the
@@ -1340,6 +1395,10 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     it evaluation rollouts (eval=True) stay within eval_tol of the fp32 step under the certificate's delta model.
     ``group`` + ``generator``: shard the candidates over the ranks of a process group (every rank attaches its own
     learner replica and passes a generator seeded identically); further keywords go to ``HipPlanner``.
+    mtm_update: True rebinds ``learner.mtm_update(batch, data_shapes, discrete_map)`` too, onto ``HipPlanner.mtm_update`` with the
+    learner's own ``mtm``, ``mtm_optimizer``, ``mtm_scheduler`` and ``temp_optimizer`` (further keywords -- masks, eps, dropout -- pass
+    through).  The device gradient is the eval-mode model's (no dropout): with a model in training mode whose config has dropout > 0
+    the rebound method raises unless called with ``dropout="eval"``.  The default (False) leaves ``mtm_update`` alone.
     Weights are followed per tensor: before each call the version counters of ``mtm`` / ``iql.qf`` are compared with the
     ones uploaded last, and only the tensors that changed are sent (m3pc_load_weights re-packs what depends on them)."""
     capi.precision_code(precision)  # (an unknown name fails here, before anything is built)
@@ -1394,6 +1453,13 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
                  "action_piid_sample", "action_id_sample", "action_piid_list_sample", "plan_async", "action_sample_batch",
                  "compute_mtm_loss"):
         setattr(learner, name, _wrap(name))
+    if mtm_update:
+        def _mtm_update(self, batch, data_shapes, discrete_map, **kw):
+            _sync()
+            return planner.mtm_update(batch, data_shapes, discrete_map, self.mtm, self.mtm_optimizer, self.mtm_scheduler,
+                                      self.temp_optimizer, sync=False, **kw)
+
+        learner.mtm_update = types.MethodType(_mtm_update, learner)
     learner._hip_planner = planner
     planner.sync = _sync
     return planner

@@ -341,6 +341,38 @@ class DeviceReplayBuffer:
         out = loss_tuple(rec, keys)
         return (out, oi) if return_indices else out
 
+    def mtm_grad(self, grad, masks, entropy_reg: float, form: str = "finetune", indices=None, batch_size: Optional[int] = None, eps=None,
+                 return_indices: bool = False):
+        """The gradient of that loss (m3pc_mtm_grad_replay) into ``grad``, a ``DeviceMTMGrad`` on this buffer's handle, for the batch
+        ``traj_sample`` would return for the same arguments: per call the bits of ``traj_sample`` followed by ``grad.grad_record``.
+        Returns the device record (15 floats; ``grad.export()`` hands out the gradients); ``step`` advances as in ``traj_sample``.
+        Eval-mode model: no dropout."""
+        from .masks import mask_rows
+        from .mtm import form_settings
+        if grad.handle is not self.handle:  # (the library compares sizes and device only: another handle's weights would be differentiated)
+            raise capi.M3pcError("mtm_grad: the DeviceMTMGrad object was created on another handle than this buffer's")
+        B = int(self.traj_batch_size if batch_size is None else batch_size)
+        ti = si = pt = ps = None
+        dev = 0
+        if indices is not None:
+            B = int(np.prod(np.shape(indices[0])))
+            ti, pt, dev = self._index(indices[0], B)
+            si, ps, dev2 = self._index(indices[1], B)
+            if dev != dev2:
+                raise ValueError("trajectory indices and starts must both be on the host or both on the device")
+        flags, bits, _ = form_settings(form, capi.KEYS)
+        e = None if eps is None else self._dev(eps, (B, self.sequence_length, self.A))
+        rec = self._new(capi.MTM_LOSS_FLOATS)
+        oi = (self._new(B, dtype=torch.int32), self._new(B, dtype=torch.int32)) if return_indices else (None, None)
+        mp, keep = self.handle._mask_ptrs(mask_rows(masks))
+        capi.check(self.lib.m3pc_mtm_grad_replay(grad._g, self._rb, B, _MODES[self._mode], pt, ps, dev, self.seed, self.step, mp,
+                                                 capi._ptr(e), float(entropy_reg), flags, bits, capi._ptr(rec), capi._ptr(oi[0]),
+                                                 capi._ptr(oi[1]), self._stream()))
+        if indices is None:
+            self.step += 1
+        del ti, si, keep
+        return (rec, oi) if return_indices else rec
+
     def split(self, batch_size: Optional[int] = None):
         """(rows of the online ring, rows of the offline ring) of a transition batch: replay_buffer.py:370-381."""
         B = int(self.trans_batch_size if batch_size is None else batch_size)
