@@ -632,6 +632,154 @@ int m3pc_debug_goal_overlay(float* pred, const float* states_in, float* states_o
                             const float* mean, const float* stdv, int normalize, void* stream, int* picked);
 int m3pc_debug_goal_overlay_rows(const float* pred, const float* states_in, float* states_out, long long windows, int T, int D, int idx,
                                  int nq, void* stream, int* picked);
+/* ---- the kernels of csrc/mtm_grad.hip (the gradient of the masked-trajectory loss), each alone on caller tensors, through the
+ * launchers m3pc_mtm_grad itself uses (csrc/mtm_grad.h: mg_launch_*): grid geometry, the `vec` decision of the product and the chunk
+ * count of the column sums are the production ones.  Every argument structure mirrors the kernel's parameter structure in
+ * csrc/mtm_grad.h; a row map is {rpg, gstride, off}.  picked (2 ints, optional; 0 while nothing was launched): [0] the id of the
+ * kernel launched last, [1] the set of ids the call launched (bit id).  Every refusal is M3PC_EINVAL and comes before any HIP call.
+ * MTM-gradient kernel ids (tests/test_mtm_grad_kernel_edges_gpu.py reaches every id of this list):
+ *   1 mg_gemm_kernel<false>;  2 mg_gemm_kernel<true>;  3 mg_ln_fwd_kernel;  4 mg_ln_bwd_kernel;  5 mg_colsum_kernel;
+ *   6 mg_colsum_fin_kernel;  7 mg_attn_fwd_kernel;  8 mg_attn_col_kernel;  9 mg_attn_row_kernel;  10 mg_embed_kernel;
+ *   11 mg_gather_kernel;  12 mg_scatter_kernel;  13 mg_tokv_kernel;  14 mg_std_kernel;  15 mg_loss_bwd_kernel
+ * (end of the MTM-gradient kernel ids) */
+/* one operand of the product (GOp): element (o, k) is p[row(o) s_o + k s_k], or p[o s_o + row(k) s_k] with map_k; len: the floats
+ * behind p (the hook refuses a product that would read beyond them) */
+typedef struct m3pc_debug_mg_op {
+    const float* p;
+    long long s_o, s_k;
+    int map[3];
+    int map_k;
+    long long len;
+} m3pc_debug_mg_op;
+/* the product (GemmG): C[cmap(m) ldc + n] (+)= epilogue(sum_k A(m, k) B(k, n)), epilogue = ((acc + (bias[n] + bias2[n])) +
+ * pos[(m % pos_T) N + n]) + res[at], times gelu'(gelu_aux[at]); gelu_out[at] = gelu(C).  res, gelu_aux, gelu_out share C's layout
+ * and c_len floats.  splitk: mg_gemm_kernel<true>.  Refused: a null A.p / B.p / C, M / N / K < 1, negative strides, a bad row map
+ * (rpg < 0, off < 0, gstride < rpg), bias2 without bias, pos with pos_T < 1, ldc < N, an operand or C index beyond len / c_len or
+ * beyond int. */
+typedef struct m3pc_debug_mg_gemm_args {
+    m3pc_debug_mg_op A, B;
+    float* C;
+    long long ldc, c_len;
+    int cmap[3];
+    int M, N, K;
+    const float* bias;
+    const float* bias2;
+    const float* pos;
+    int pos_T;
+    const float* res;
+    const float* gelu_aux;
+    float* gelu_out;
+    int accumulate, splitk;
+    void* stream;
+    int* picked;
+} m3pc_debug_mg_gemm_args;
+int m3pc_debug_mg_gemm(const m3pc_debug_mg_gemm_args* a);
+/* LayerNorm (LnG), eps 1e-5, biased variance.  backward 0: Y[r] = LN(X[xmap(r)]) g + b and st[r] = (mean, rstd), r < rows;
+ * backward 1: dX[xmap(r)] (+)= rstd (g' - mean(g') - xhat mean(g' xhat)), g' = dY[r] g, from the st given.  x_rows: the rows of X
+ * (and of dX).  Refused: rows / d < 1, rows d beyond int, a bad row map, xmap(rows - 1) >= x_rows, a null X / g / st, forward
+ * without b / Y, backward without dY / dX. */
+typedef struct m3pc_debug_mg_ln_args {
+    int backward;
+    const float* X;
+    int xmap[3];
+    long long x_rows;
+    const float* g;
+    const float* b;
+    float* Y;
+    float* st;
+    const float* dY;
+    float* dX;
+    int rows, d, accumulate;
+    void* stream;
+    int* picked;
+} m3pc_debug_mg_ln_args;
+int m3pc_debug_mg_layernorm(const m3pc_debug_mg_ln_args* a);
+/* column sums, both stages (ColG): out0[c] = sum over the rows (s, j), s < nseq, j < n, bit j of sel, of dY[row][c]; with X / st
+ * out1[c] = the same sum of dY xhat.  The buffer row is s L + j0 + j, the compact row s n + j (dY: the compact row with dy_compact;
+ * st: always).  part: part_doubles doubles of scratch; buf_rows: the rows of X, and of dY unless compact.  Refused: a null dY / out0 /
+ * part, X without st or st without X, out1 without X, nseq < 1, n outside [1, 64], j0 < 0, j0 + n > L, C < 1, ldy < C, buf_rows
+ * below (nseq - 1) L + j0 + n, part_doubles below chunks 2 C (chunks = ceil(nseq n / 64)), counts beyond int. */
+typedef struct m3pc_debug_mg_colsum_args {
+    const float* dY;
+    int dy_compact;
+    long long ldy;
+    const float* X;
+    const float* st;
+    int nseq, L, j0, n;
+    unsigned long long sel;
+    int C;
+    double* part;
+    long long part_doubles, buf_rows;
+    float* out0;
+    float* out1;
+    void* stream;
+    int* picked;
+} m3pc_debug_mg_colsum_args;
+int m3pc_debug_mg_colsum(const m3pc_debug_mg_colsum_args* a);
+/* the four attention kernels (AttG).  which 0: mg_attn_fwd_kernel (QKV -> P, O); 1: mg_attn_col_kernel dV = P^T dO; 2:
+ * mg_attn_row_kernel (P, dO, QKV -> dS over P, dQ); 3: mg_attn_col_kernel dK = dS^T Q scale.  QKV, dQKV (B L, 3 d); O, dO (B L, d);
+ * P (B, nh, L, L).  Refused: which outside [0, 3], B < 1, L outside [1, 256], nh / hd < 1, nh hd != d, B nh L L or B L 3 d beyond
+ * int, a null pointer the kernel uses. */
+typedef struct m3pc_debug_mg_attn_args {
+    int which;
+    const float* QKV;
+    float* P;
+    float* O;
+    const float* dO;
+    float* dQKV;
+    int B, L, d, nh, hd;
+    float scale;
+    void* stream;
+    int* picked;
+} m3pc_debug_mg_attn_args;
+int m3pc_debug_mg_attention(const m3pc_debug_mg_attn_args* a);
+/* the token-layout kernels (EmbG).  which 0: mg_embed_kernel (tok, W, bias, pdim, pos -> X); 1: mg_gather_kernel (src, mtok -> dst);
+ * 2: mg_scatter_kernel (src -> dst); 3: mg_tokv_kernel (tok[key] -> out).  Refused: which outside [0, 3], B < 1, T outside [1, 64],
+ * d < 1, a bit of bits[k] at or above T, kept[k] != popcount(bits[k]), eoff[k] != kept[0] + .. + kept[k - 1], Le != their sum or
+ * < 1, B 4 T d beyond int, a null pointer the kernel uses (embed: tok / W / bias / pdim of every key with kept > 0 and feat >= 1
+ * there; gather: mtok of every key), tokv with key outside [0, 3], kept[key] < 1 or feat[key] < 1. */
+typedef struct m3pc_debug_mg_tokens_args {
+    int which;
+    const float* tok[4];
+    const float* W[4];
+    const float* bias[4];
+    const float* pdim[4];
+    const float* pos;
+    const float* mtok[4];
+    unsigned long long bits[4];
+    int kept[4], eoff[4], feat[4];
+    int B, T, d, Le;
+    float* X;
+    const float* src;
+    float* dst;
+    int key;
+    float* out;
+    void* stream;
+    int* picked;
+} m3pc_debug_mg_tokens_args;
+int m3pc_debug_mg_tokens(const m3pc_debug_mg_tokens_args* a);
+/* sd[i] = exp(-5 + 3.5 (tanh(ls[i]) + 1)), i < n.  Refused: a null pointer, n < 1. */
+int m3pc_debug_mg_std(const float* ls, float* sd, long long n, void* stream, int* picked);
+/* the loss backward (LossBwdG): dpred of the three scalar heads, dmu and d log_std of the action head.  Refused: a null pointer,
+ * batch / S / A < 1, T outside [1, 64], a mask bit at or above T, unknown flag bits, loss_keys outside [0, 15], batch T (S + 2 + A)
+ * beyond int. */
+typedef struct m3pc_debug_mg_loss_bwd_args {
+    const float* pred[3];
+    const float* mu;
+    const float* sd;
+    const float* ls;
+    const float* tgt[4];
+    const float* eps;
+    float* dpred[3];
+    float* dmu;
+    float* dls;
+    unsigned long long mask[4];
+    int batch, T, S, A, flags, loss_keys;
+    float entropy_reg, inv_cnt;
+    void* stream;
+    int* picked;
+} m3pc_debug_mg_loss_bwd_args;
+int m3pc_debug_mg_loss_bwd(const m3pc_debug_mg_loss_bwd_args* a);
 /* in-kernel phase stamps of workgroup 37 of every fused-tail launch as the step runs: cap > 0 starts a ring of cap entries
  * (64 int64 each), cap == 0 copies it to `out` (host), reports the number of launches logged and stops */
 int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged);

@@ -498,6 +498,15 @@ void launch_topk_forced(int variant, const float* v, const float* expo, float ta
 #define M3PC_SEL_PICK(id) ((void)0)
 #define M3PC_SEL_FORCE_FALLBACK false
 #endif
+// lab build: the id of the mtm_grad.hip kernel the calling thread launched last and the set of ids launched since the set was last
+// cleared (a column sum is two kernels) -- include/m3pc_hip_debug.h, "MTM-gradient kernel ids"; the product build records nothing
+#ifdef M3PC_LAB
+extern thread_local int g_mg_picked;
+extern thread_local unsigned int g_mg_picked_set;
+#define M3PC_MG_PICK(id) (::m3pc::g_mg_picked = (id), ::m3pc::g_mg_picked_set |= 1u << (id))
+#else
+#define M3PC_MG_PICK(id) ((void)0)
+#endif
 void launch_select(const SelectP& p, hipStream_t st);
 // launch_select for E windows in one launch (workgroup = window, select_body): p describes window 0; window w reads er / expo and
 // writes p at + w row_stride, reads a0 at + w a0_wstride, writes eval_action / sample_action at + w A, argmax / sample_idx at + w

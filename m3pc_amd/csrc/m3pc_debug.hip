@@ -1,6 +1,7 @@
 // libm3pc_hip_lab.so only (m3pc_amd/build.py: LAB_SOURCES): the kernel-level test / bench hooks declared in
 // include/m3pc_hip_debug.h.  The product build does not compile this file.
 #include "m3pc_internal.h"
+#include "mtm_grad.h"
 
 #include <vector>
 
@@ -1114,6 +1115,284 @@ int m3pc_debug_goal_overlay_rows(const float* pred, const float* states_in, floa
     g_ew_picked = 0;
     launch_goal_overlay_rows(pred, states_in, states_out, windows, T, D, idx, nq, (hipStream_t)stream);
     return ew_done(picked, "debug_goal_overlay_rows");
+}
+
+// ---- csrc/mtm_grad.hip, kernel by kernel (include/m3pc_hip_debug.h, "MTM-gradient kernel ids"; tests/test_mtm_grad_kernel_edges_gpu.py).
+// Every hook checks first (no HIP call before a refusal), fills the kernel's parameter structure, goes through the launcher
+// m3pc_mtm_grad uses and reports what that launcher recorded.
+static const long long MG_INT_MAX = 0x7fffffffLL;
+static void mg_begin(int* picked) {
+    if (picked) picked[0] = picked[1] = 0;
+    g_mg_picked = 0;
+    g_mg_picked_set = 0;
+}
+static int mg_done(int* picked, const char* what) {
+    if (picked) {
+        picked[0] = g_mg_picked;
+        picked[1] = (int)g_mg_picked_set;
+    }
+    return check_launch(what);
+}
+static RMap mg_map(const int* m) { return RMap{m[0], m[1], m[2]}; }
+// the largest index of an operand with `outer` rows or columns, -1 if its description is bad
+static long long mg_op_last(const m3pc_debug_mg_op& o, int outer, int K) {
+    if (!o.p || o.s_o < 0 || o.s_k < 0 || ew_bad_map(o.map) || o.len < 1) return -1;
+    const RMap m = mg_map(o.map);
+    const long long ro = o.map_k ? outer - 1 : rmap(m, outer - 1), rk = o.map_k ? rmap(m, K - 1) : K - 1;
+    if (ro > MG_INT_MAX || rk > MG_INT_MAX || (o.s_o && ro > MG_INT_MAX / o.s_o) || (o.s_k && rk > MG_INT_MAX / o.s_k)) return -1;
+    return ro * o.s_o + rk * o.s_k;
+}
+
+int m3pc_debug_mg_gemm(const m3pc_debug_mg_gemm_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_gemm: null arguments");
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (!a->A.p || !a->B.p || !a->C) return fail(M3PC_EINVAL, "debug_mg_gemm: A, B and C are required");
+    if (a->M < 1 || a->N < 1 || a->K < 1) return fail(M3PC_EINVAL, "debug_mg_gemm: M %d, N %d, K %d: each must be >= 1", a->M, a->N, a->K);
+    const long long la = mg_op_last(a->A, a->M, a->K), lb = mg_op_last(a->B, a->N, a->K);
+    if (la < 0 || la >= a->A.len || la > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_gemm: operand A (strides, row map or an index beyond its %lld floats)", a->A.len);
+    if (lb < 0 || lb >= a->B.len || lb > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_gemm: operand B (strides, row map or an index beyond its %lld floats)", a->B.len);
+    if (ew_bad_map(a->cmap) || a->ldc < a->N || a->ldc > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_gemm: cmap / ldc %lld below N %d", a->ldc, a->N);
+    const long long rc = rmap(mg_map(a->cmap), a->M - 1);
+    if (rc > MG_INT_MAX / a->ldc || rc * a->ldc + a->N - 1 >= a->c_len)
+        return fail(M3PC_EINVAL, "debug_mg_gemm: row %lld of C lies beyond its %lld floats", rc, a->c_len);
+    if (a->bias2 && !a->bias) return fail(M3PC_EINVAL, "debug_mg_gemm: bias2 without bias");
+    if (a->pos && a->pos_T < 1) return fail(M3PC_EINVAL, "debug_mg_gemm: pos with pos_T %d < 1", a->pos_T);
+    GemmG p;
+    memset(&p, 0, sizeof(p));
+    p.A = GOp{a->A.p, a->A.s_o, a->A.s_k, mg_map(a->A.map), a->A.map_k ? 1 : 0, 0};
+    p.B = GOp{a->B.p, a->B.s_o, a->B.s_k, mg_map(a->B.map), a->B.map_k ? 1 : 0, 0};
+    p.C = a->C;
+    p.ldc = a->ldc;
+    p.cmap = mg_map(a->cmap);
+    p.M = a->M;
+    p.N = a->N;
+    p.K = a->K;
+    p.bias = a->bias;
+    p.bias2 = a->bias2;
+    p.pos = a->pos;
+    p.pos_T = a->pos ? a->pos_T : 1;
+    p.res = a->res;
+    p.gelu_aux = a->gelu_aux;
+    p.gelu_out = a->gelu_out;
+    p.accumulate = a->accumulate ? 1 : 0;
+    p.splitk = a->splitk ? 1 : 0;
+    mg_begin(a->picked);
+    mg_launch_gemm(p, (hipStream_t)a->stream);
+    return mg_done(a->picked, "debug_mg_gemm");
+}
+
+int m3pc_debug_mg_layernorm(const m3pc_debug_mg_ln_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_layernorm: null arguments");
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (!a->X || !a->g || !a->st) return fail(M3PC_EINVAL, "debug_mg_layernorm: X, g and st are required");
+    if (a->backward ? (!a->dY || !a->dX) : (!a->b || !a->Y)) return fail(M3PC_EINVAL, "debug_mg_layernorm: %s", a->backward ? "backward needs dY and dX" : "forward needs b and Y");
+    if (a->rows < 1 || a->d < 1 || (long long)a->rows * a->d > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_layernorm: rows %d, d %d", a->rows, a->d);
+    if (ew_bad_map(a->xmap)) return fail(M3PC_EINVAL, "debug_mg_layernorm: row map");
+    const long long last = rmap(mg_map(a->xmap), a->rows - 1);
+    if (last >= a->x_rows || a->x_rows > MG_INT_MAX / a->d) return fail(M3PC_EINVAL, "debug_mg_layernorm: row %lld of X beyond its x_rows %lld", last, a->x_rows);
+    LnG p;
+    memset(&p, 0, sizeof(p));
+    p.X = a->X;
+    p.xmap = mg_map(a->xmap);
+    p.g = a->g;
+    p.b = a->b;
+    p.Y = a->Y;
+    p.st = a->st;
+    p.dY = a->dY;
+    p.dX = a->dX;
+    p.rows = a->rows;
+    p.d = a->d;
+    p.accumulate = a->accumulate ? 1 : 0;
+    mg_begin(a->picked);
+    if (a->backward)
+        mg_launch_ln_bwd(p, (hipStream_t)a->stream);
+    else
+        mg_launch_ln_fwd(p, (hipStream_t)a->stream);
+    return mg_done(a->picked, "debug_mg_layernorm");
+}
+
+int m3pc_debug_mg_colsum(const m3pc_debug_mg_colsum_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_colsum: null arguments");
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (!a->dY || !a->out0 || !a->part) return fail(M3PC_EINVAL, "debug_mg_colsum: dY, out0 and part are required");
+    if ((a->X == nullptr) != (a->st == nullptr) || (a->out1 && !a->X)) return fail(M3PC_EINVAL, "debug_mg_colsum: X and st come together, out1 needs them");
+    if (a->nseq < 1 || a->n < 1 || a->n > 64) return fail(M3PC_EINVAL, "debug_mg_colsum: nseq %d < 1 or n %d outside [1, 64]", a->nseq, a->n);
+    if (a->j0 < 0 || a->L < 1 || (long long)a->j0 + a->n > a->L) return fail(M3PC_EINVAL, "debug_mg_colsum: j0 %d + n %d beyond L %d", a->j0, a->n, a->L);
+    if (a->C < 1 || a->ldy < a->C) return fail(M3PC_EINVAL, "debug_mg_colsum: C %d < 1 or ldy %lld below it", a->C, a->ldy);
+    const long long total = (long long)a->nseq * a->n, need_rows = (long long)(a->nseq - 1) * a->L + a->j0 + a->n;
+    if (total > MG_INT_MAX || need_rows > MG_INT_MAX / a->ldy || a->buf_rows < need_rows)
+        return fail(M3PC_EINVAL, "debug_mg_colsum: the rows reach buffer row %lld, buf_rows is %lld", need_rows - 1, a->buf_rows);
+    const size_t need = mg_colsum_doubles(total, a->C);
+    if (a->part_doubles < 0 || (size_t)a->part_doubles < need)
+        return fail(M3PC_EINVAL, "debug_mg_colsum: part holds %lld doubles, %d chunks of 2 C need %zu", a->part_doubles, mg_colsum_chunks(total), need);
+    ColG p;
+    memset(&p, 0, sizeof(p));
+    p.dY = a->dY;
+    p.dy_compact = a->dy_compact ? 1 : 0;
+    p.ldy = a->ldy;
+    p.X = a->X;
+    p.st = a->st;
+    p.nseq = a->nseq;
+    p.L = a->L;
+    p.j0 = a->j0;
+    p.n = a->n;
+    p.sel = a->sel;
+    p.C = a->C;
+    p.out0 = a->out0;
+    p.out1 = a->out1;
+    mg_begin(a->picked);
+    mg_launch_colsum(p, a->part, (hipStream_t)a->stream);
+    return mg_done(a->picked, "debug_mg_colsum");
+}
+
+int m3pc_debug_mg_attention(const m3pc_debug_mg_attn_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_attention: null arguments");
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (a->which < 0 || a->which > 3) return fail(M3PC_EINVAL, "debug_mg_attention: which %d outside [0, 3]", a->which);
+    if (a->L < 1 || a->L > MG_ATT_MAX_L) return fail(M3PC_EINVAL, "debug_mg_attention: L %d outside [1, %d] (a row of P is held in LDS)", a->L, MG_ATT_MAX_L);
+    if (a->B < 1 || a->nh < 1 || a->hd < 1 || a->d < 1 || (long long)a->nh * a->hd != a->d)
+        return fail(M3PC_EINVAL, "debug_mg_attention: B %d, n_head %d x head dim %d against d %d", a->B, a->nh, a->hd, a->d);
+    if ((long long)a->B * a->nh * a->L * a->L > MG_INT_MAX || (long long)a->B * a->L * 3 * a->d > MG_INT_MAX)
+        return fail(M3PC_EINVAL, "debug_mg_attention: the element counts exceed int");
+    const bool need_qkv = a->which != 1, need_o = a->which == 0, need_do = a->which == 1 || a->which == 2, need_dqkv = a->which != 0;
+    if (!a->P || (need_qkv && !a->QKV) || (need_o && !a->O) || (need_do && !a->dO) || (need_dqkv && !a->dQKV))
+        return fail(M3PC_EINVAL, "debug_mg_attention: a pointer kernel %d uses is null", a->which);
+    AttG p;
+    memset(&p, 0, sizeof(p));
+    p.QKV = a->QKV;
+    p.P = a->P;
+    p.O = a->O;
+    p.dO = a->dO;
+    p.dQKV = a->dQKV;
+    p.B = a->B;
+    p.L = a->L;
+    p.d = a->d;
+    p.nh = a->nh;
+    p.hd = a->hd;
+    p.scale = a->scale;
+    hipStream_t st = (hipStream_t)a->stream;
+    mg_begin(a->picked);
+    if (a->which == 0)
+        mg_launch_attn_fwd(p, st);
+    else if (a->which == 2)
+        mg_launch_attn_row(p, st);
+    else
+        mg_launch_attn_col(p, a->which == 1 ? 0 : 1, st);
+    return mg_done(a->picked, "debug_mg_attention");
+}
+
+int m3pc_debug_mg_tokens(const m3pc_debug_mg_tokens_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_tokens: null arguments");
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (a->which < 0 || a->which > 3) return fail(M3PC_EINVAL, "debug_mg_tokens: which %d outside [0, 3]", a->which);
+    if (a->B < 1 || a->T < 1 || a->T > 64 || a->d < 1) return fail(M3PC_EINVAL, "debug_mg_tokens: B %d, d %d, T %d outside [1, 64]", a->B, a->d, a->T);
+    int Le = 0;
+    for (int k = 0; k < 4; ++k) {
+        if (a->T < 64 && (a->bits[k] >> a->T)) return fail(M3PC_EINVAL, "debug_mg_tokens: bits[%d] has a bit at or above T %d", k, a->T);
+        if (a->kept[k] != __builtin_popcountll(a->bits[k]) || a->eoff[k] != Le)
+            return fail(M3PC_EINVAL, "debug_mg_tokens: kept[%d] %d / eoff[%d] %d inconsistent with bits", k, a->kept[k], k, a->eoff[k]);
+        Le += a->kept[k];
+    }
+    if (a->Le != Le || Le < 1) return fail(M3PC_EINVAL, "debug_mg_tokens: Le %d, the masks keep %d tokens", a->Le, Le);
+    if ((long long)a->B * 4 * a->T * a->d > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_tokens: B 4 T d exceeds int");
+    if (a->which == 0) {
+        if (!a->X || !a->pos) return fail(M3PC_EINVAL, "debug_mg_tokens: embed needs X and pos");
+        for (int k = 0; k < 4; ++k)
+            if (a->kept[k] && (!a->tok[k] || !a->W[k] || !a->bias[k] || !a->pdim[k] || a->feat[k] < 1))
+                return fail(M3PC_EINVAL, "debug_mg_tokens: embed needs tok / W / bias / pdim and feat >= 1 of key %d", k);
+    } else if (a->which == 1) {
+        if (!a->src || !a->dst) return fail(M3PC_EINVAL, "debug_mg_tokens: gather needs src and dst");
+        for (int k = 0; k < 4; ++k)
+            if (!a->mtok[k]) return fail(M3PC_EINVAL, "debug_mg_tokens: gather needs mtok of key %d", k);
+    } else if (a->which == 2) {
+        if (!a->src || !a->dst) return fail(M3PC_EINVAL, "debug_mg_tokens: scatter needs src and dst");
+    } else {
+        if (a->key < 0 || a->key > 3 || a->kept[a->key] < 1 || a->feat[a->key] < 1 || !a->tok[a->key] || !a->out)
+            return fail(M3PC_EINVAL, "debug_mg_tokens: tokv needs a key in [0, 3] with kept >= 1, feat >= 1, its tok and out");
+        if ((long long)a->B * a->T * a->feat[a->key] > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_tokens: B T feat exceeds int");
+    }
+    EmbG p;
+    memset(&p, 0, sizeof(p));
+    for (int k = 0; k < 4; ++k) {
+        p.tok[k] = a->tok[k];
+        p.W[k] = a->W[k];
+        p.bias[k] = a->bias[k];
+        p.pdim[k] = a->pdim[k];
+        p.mtok[k] = a->mtok[k];
+        p.bits[k] = a->bits[k];
+        p.kept[k] = a->kept[k];
+        p.eoff[k] = a->eoff[k];
+        p.feat[k] = a->feat[k];
+    }
+    p.pos = a->pos;
+    p.B = a->B;
+    p.T = a->T;
+    p.d = a->d;
+    p.Le = a->Le;
+    p.X = a->X;
+    p.src = a->src;
+    p.dst = a->dst;
+    hipStream_t st = (hipStream_t)a->stream;
+    mg_begin(a->picked);
+    if (a->which == 0)
+        mg_launch_embed(p, st);
+    else if (a->which == 1)
+        mg_launch_gather(p, st);
+    else if (a->which == 2)
+        mg_launch_scatter(p, st);
+    else
+        mg_launch_tokv(p, a->key, a->out, st);
+    return mg_done(a->picked, "debug_mg_tokens");
+}
+
+int m3pc_debug_mg_std(const float* ls, float* sd, long long n, void* stream, int* picked) {
+    if (picked) picked[0] = picked[1] = 0;
+    if (!ls || !sd || n < 1) return fail(M3PC_EINVAL, "debug_mg_std: null pointer or n %lld < 1", n);
+    mg_begin(picked);
+    mg_launch_std(ls, sd, n, (hipStream_t)stream);
+    return mg_done(picked, "debug_mg_std");
+}
+
+int m3pc_debug_mg_loss_bwd(const m3pc_debug_mg_loss_bwd_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_loss_bwd: null arguments");
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    bool null = !a->mu || !a->sd || !a->ls || !a->eps || !a->dmu || !a->dls;
+    for (int j = 0; j < 3; ++j) null = null || !a->pred[j] || !a->dpred[j];
+    for (int k = 0; k < 4; ++k) null = null || !a->tgt[k];
+    if (null) return fail(M3PC_EINVAL, "debug_mg_loss_bwd: null pointer");
+    if (a->batch < 1 || a->S < 1 || a->A < 1 || a->T < 1 || a->T > 64) return fail(M3PC_EINVAL, "debug_mg_loss_bwd: batch %d, S %d, A %d, T %d outside [1, 64]", a->batch, a->S, a->A, a->T);
+    for (int k = 0; k < 4; ++k)
+        if (a->T < 64 && (a->mask[k] >> a->T)) return fail(M3PC_EINVAL, "debug_mg_loss_bwd: mask[%d] has a bit at or above T %d", k, a->T);
+    if (a->flags & ~(M3PC_MTM_NORM_L2 | M3PC_MTM_CLIP_ACTIONS)) return fail(M3PC_EINVAL, "debug_mg_loss_bwd: unknown flag bits 0x%x", a->flags);
+    if (a->loss_keys < 0 || a->loss_keys > 15) return fail(M3PC_EINVAL, "debug_mg_loss_bwd: loss_keys %d outside [0, 15]", a->loss_keys);
+    if ((long long)a->batch * a->T * ((long long)a->S + 2 + a->A) > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_loss_bwd: batch T (S + 2 + A) exceeds int");
+    LossBwdG p;
+    memset(&p, 0, sizeof(p));
+    for (int j = 0; j < 3; ++j) {
+        p.pred[j] = a->pred[j];
+        p.dpred[j] = a->dpred[j];
+    }
+    for (int k = 0; k < 4; ++k) {
+        p.tgt[k] = a->tgt[k];
+        p.mask[k] = a->mask[k];
+    }
+    p.mu = a->mu;
+    p.sd = a->sd;
+    p.ls = a->ls;
+    p.eps = a->eps;
+    p.dmu = a->dmu;
+    p.dls = a->dls;
+    p.batch = a->batch;
+    p.T = a->T;
+    p.S = a->S;
+    p.A = a->A;
+    p.flags = a->flags;
+    p.loss_keys = a->loss_keys;
+    p.entropy_reg = a->entropy_reg;
+    p.inv_cnt = a->inv_cnt;
+    mg_begin(a->picked);
+    mg_launch_loss_bwd(p, (hipStream_t)a->stream);
+    return mg_done(a->picked, "debug_mg_loss_bwd");
 }
 
 // kv_fused_kernel alone (tests/test_block_fused_gpu.py): n candidates of Le rows each in Z (n*Le, 512) bf16; group g holds

@@ -32,11 +32,123 @@
 //   backward   L (7 d + ff)  +  T (2 d + S + 2 + 2 A)
 //   float64    7 T doubles (the returns of a replay draw, the six row sums of the record)
 // in all 4 [n L (8 d + 2 ff + 4 + n_head L) + L (12 d + ff + 4) + T (11 d + 4 S + 8 A + 13)] + 56 T bytes, each buffer rounded up to 256
-// bytes; and, once per object, the gradient of every parameter and the column-sum partials (2 (max_batch L / 64 + 2) max(3 d, ff) doubles).
+// bytes; and, once per object, the gradient of every parameter and the column-sum partials (2 ceil(max_batch L / 64) max(3 d, ff) doubles).
 #pragma once
 #include "m3pc_internal.h"
 
 struct m3pc_replay;
 namespace m3pc {
 int replay_segment_length(const m3pc_replay* rb);
+
+// ------------------------------------------------------------------------------------------------ parameter structures
+// (mtm_grad.hip holds the kernels; mg_run and the lab hooks of m3pc_debug.hip fill these and go through the launchers below)
+// row r of a compact run -> row of the buffer: rpg rows per group, groups gstride rows apart, from row off (rpg == 0: r itself)
+struct RMap {
+    int rpg, gstride, off;
+};
+__host__ __device__ __forceinline__ long long rmap(const RMap& m, int r) {
+    return m.rpg == 0 ? (long long)r : (long long)(r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
+}
+
+// C[m][n] = sum_k A(m, k) B(k, n): element (o, k) of an operand is p[row(o) * s_o + k * s_k], or p[o * s_o + row(k) * s_k] with map_k
+struct GOp {
+    const float* p;
+    long long s_o, s_k;
+    RMap map;
+    int map_k;
+    int vec;  // k-contiguous, not row-mapped on k, 16-byte aligned rows: four k per load (mg_launch_gemm decides it)
+};
+struct GemmG {
+    GOp A, B;
+    float* C;
+    long long ldc;
+    RMap cmap;              // on m
+    int M, N, K;
+    const float *bias, *bias2;  // + bias[n] + bias2[n]
+    const float* pos;       // + pos[(m % pos_T) * N + n]
+    int pos_T;
+    const float* res;       // + res[row(m) * ldc + n]
+    const float* gelu_aux;  // * gelu'(gelu_aux[row(m) * ldc + n])
+    float* gelu_out;        // gelu_out[row(m) * ldc + n] = gelu(C)
+    int accumulate;         // C += instead of C =
+    int splitk;             // the four wavefronts of a workgroup share a tile (mg_gemm_kernel<true>)
+};
+
+struct LnG {
+    const float* X;   // rows xmap(r), ld d
+    RMap xmap;
+    const float *g, *b;
+    float* Y;         // forward: compact rows
+    float* st;        // (rows, 2): mean, rstd
+    const float* dY;  // backward: compact rows
+    float* dX;        // backward: rows xmap(r)
+    int rows, d, accumulate;
+};
+
+// rows (s, j): s < nseq, j < n, bit j of sel set; the buffer row is s L + j0 + j, the compact row s n + j.
+//   out0[c] = sum dY[row][c];  with X: out1[c] = sum dY[row][c] xhat[row][c]  (LayerNorm: bias and weight)
+struct ColG {
+    const float* dY;
+    int dy_compact;
+    long long ldy;
+    const float* X;   // buffer rows, ld C
+    const float* st;  // compact rows
+    int nseq, L, j0, n;
+    unsigned long long sel;
+    int C;
+    double* part;     // (chunks, 2, C)
+    float *out0, *out1;
+    int chunks;
+};
+
+struct AttG {
+    const float* QKV;  // (B L, 3 d)
+    float* P;          // (B, nh, L, L): probabilities, then dS
+    float* O;          // forward out (B L, d)
+    const float* dO;   // (B L, d)
+    float* dQKV;       // (B L, 3 d)
+    int B, L, d, nh, hd;
+    float scale;
+};
+
+struct EmbG {
+    const float *tok[4], *W[4], *bias[4], *pdim[4], *pos, *mtok[4];
+    unsigned long long bits[4];
+    int kept[4], eoff[4], feat[4];
+    int B, T, d, Le;
+    float* X;          // (B Le, d)  encoder rows (embed: out)
+    const float* src;  // gather: EncN (B Le, d); scatter: dZin (B 4T, d)
+    float* dst;        // gather: Zin (B 4T, d); scatter: dEncN (B Le, d)
+};
+
+struct LossBwdG {
+    const float *pred[3], *mu, *sd, *ls, *tgt[4], *eps;
+    float *dpred[3], *dmu, *dls;
+    unsigned long long mask[4];
+    int batch, T, S, A, flags, loss_keys;
+    float entropy_reg, inv_cnt;  // 1 / (batch * hidden action timesteps * A)
+};
+
+// ------------------------------------------------------------------------------------------------ launchers
+// The grid geometry, the `vec` decision of the product, the chunk count of the column sums and their scratch size exist here once.
+// The longest attention row the kernels hold in LDS (sp[4][MG_ATT_MAX_L]).
+constexpr int MG_ATT_MAX_L = 256;
+// decides A.vec / B.vec; no launch when M or N is 0
+void mg_launch_gemm(GemmG& p, hipStream_t st);
+void mg_launch_ln_fwd(const LnG& p, hipStream_t st);
+void mg_launch_ln_bwd(const LnG& p, hipStream_t st);
+// blocks of 64 rows (s, j) of a column sum, and the doubles of scratch its two stages need
+inline int mg_colsum_chunks(long long total) { return (int)((total + 63) / 64); }
+inline size_t mg_colsum_doubles(long long total, int C) { return (size_t)mg_colsum_chunks(total) * 2 * (size_t)C; }
+// sets p.part = scratch (mg_colsum_doubles(nseq n, C) doubles) and p.chunks; both stages.  No launch when nseq n is 0.
+void mg_launch_colsum(ColG& p, double* scratch, hipStream_t st);
+void mg_launch_attn_fwd(const AttG& p, hipStream_t st);
+void mg_launch_attn_col(const AttG& p, int which, hipStream_t st);
+void mg_launch_attn_row(const AttG& p, hipStream_t st);
+void mg_launch_embed(const EmbG& p, hipStream_t st);
+void mg_launch_gather(const EmbG& p, hipStream_t st);
+void mg_launch_scatter(const EmbG& p, hipStream_t st);
+void mg_launch_tokv(const EmbG& p, int k, float* out, hipStream_t st);
+void mg_launch_std(const float* ls, float* sd, long long n, hipStream_t st);
+void mg_launch_loss_bwd(const LossBwdG& p, hipStream_t st);
 }  // namespace m3pc

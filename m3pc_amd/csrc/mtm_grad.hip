@@ -18,39 +18,8 @@ typedef unsigned long long u64;
 #define MG_MFMA(a, b, c) ((void)(a), (void)(b), (c))
 #endif
 
-// row r of a compact run -> row of the buffer: rpg rows per group, groups gstride rows apart, from row off (rpg == 0: r itself)
-struct RMap {
-    int rpg, gstride, off;
-};
-__host__ __device__ __forceinline__ long long rmap(const RMap& m, int r) {
-    return m.rpg == 0 ? (long long)r : (long long)(r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
-}
-
 // ------------------------------------------------------------------------------------------------ the product
-// C[m][n] = sum_k A(m, k) B(k, n): element (o, k) of an operand is p[row(o) * s_o + k * s_k], or p[o * s_o + row(k) * s_k] with map_k
-struct GOp {
-    const float* p;
-    long long s_o, s_k;
-    RMap map;
-    int map_k;
-    int vec;  // k-contiguous, not row-mapped on k, 16-byte aligned rows: four k per load
-};
-struct GemmG {
-    GOp A, B;
-    float* C;
-    long long ldc;
-    RMap cmap;              // on m
-    int M, N, K;
-    const float *bias, *bias2;  // + bias[n] + bias2[n]
-    const float* pos;       // + pos[(m % pos_T) * N + n]
-    int pos_T;
-    const float* res;       // + res[row(m) * ldc + n]
-    const float* gelu_aux;  // * gelu'(gelu_aux[row(m) * ldc + n])
-    float* gelu_out;        // gelu_out[row(m) * ldc + n] = gelu(C)
-    int accumulate;         // C += instead of C =
-    int splitk;             // the four wavefronts of a workgroup share a tile (mg_gemm_kernel<true>)
-};
-
+// C[m][n] = sum_k A(m, k) B(k, n) (GemmG, mtm_grad.h)
 __device__ __forceinline__ float gelu_grad_exact(float x) {
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
     const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
@@ -149,17 +118,6 @@ __global__ __launch_bounds__(256) void mg_gemm_kernel(GemmG p) {
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
-struct LnG {
-    const float* X;   // rows xmap(r), ld d
-    RMap xmap;
-    const float *g, *b;
-    float* Y;         // forward: compact rows
-    float* st;        // (rows, 2): mean, rstd
-    const float* dY;  // backward: compact rows
-    float* dX;        // backward: rows xmap(r)
-    int rows, d, accumulate;
-};
-
 __global__ __launch_bounds__(256) void mg_ln_fwd_kernel(LnG p) {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= p.rows) return;
@@ -205,22 +163,7 @@ __global__ __launch_bounds__(256) void mg_ln_bwd_kernel(LnG p) {
 }
 
 // ------------------------------------------------------------------------------------------------ column sums
-// rows (s, j): s < nseq, j < n, bit j of sel set; the buffer row is s L + j0 + j, the compact row s n + j.
-//   out0[c] = sum dY[row][c];  with X: out1[c] = sum dY[row][c] xhat[row][c]  (LayerNorm: bias and weight)
-struct ColG {
-    const float* dY;
-    int dy_compact;
-    long long ldy;
-    const float* X;   // buffer rows, ld C
-    const float* st;  // compact rows
-    int nseq, L, j0, n;
-    u64 sel;
-    int C;
-    double* part;     // (chunks, 2, C)
-    float *out0, *out1;
-    int chunks;
-};
-
+// the rows (s, j) and the two sums: ColG (mtm_grad.h).  One thread per column and chunk of 64 rows, then one per column over the chunks.
 __global__ __launch_bounds__(256) void mg_colsum_kernel(ColG p) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= p.C) return;
@@ -255,19 +198,9 @@ __global__ __launch_bounds__(256) void mg_colsum_fin_kernel(ColG p) {
 }
 
 // ------------------------------------------------------------------------------------------------ attention
-struct AttG {
-    const float* QKV;  // (B L, 3 d)
-    float* P;          // (B, nh, L, L): probabilities, then dS
-    float* O;          // forward out (B L, d)
-    const float* dO;   // (B L, d)
-    float* dQKV;       // (B L, 3 d)
-    int B, L, d, nh, hd;
-    float scale;
-};
-
 // one wavefront per (b, head, query i): lane owns the keys lane, lane + 64, ...; L <= 256
 __global__ __launch_bounds__(256) void mg_attn_fwd_kernel(AttG p) {
-    __shared__ float sp[4][256];
+    __shared__ float sp[4][MG_ATT_MAX_L];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * 4 + wv;
     if (w >= (long long)p.B * p.nh * p.L) return;
@@ -335,7 +268,7 @@ __global__ __launch_bounds__(256) void mg_attn_col_kernel(AttG p, int which) {
 
 // one wavefront per (b, head, query i): dP = dO V^T, dS = P (dP - sum_j dP P) over P in place, dQ = dS K scale (keys ascending)
 __global__ __launch_bounds__(256) void mg_attn_row_kernel(AttG p) {
-    __shared__ float sp[4][256];
+    __shared__ float sp[4][MG_ATT_MAX_L];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * 4 + wv;
     if (w >= (long long)p.B * p.nh * p.L) return;
@@ -379,16 +312,6 @@ __global__ __launch_bounds__(256) void mg_attn_row_kernel(AttG p) {
 }
 
 // ------------------------------------------------------------------------------------------------ embedding, gather, scatter
-struct EmbG {
-    const float *tok[4], *W[4], *bias[4], *pdim[4], *pos, *mtok[4];
-    u64 bits[4];
-    int kept[4], eoff[4], feat[4];
-    int B, T, d, Le;
-    float* X;          // (B Le, d)  encoder rows (embed: out)
-    const float* src;  // gather: EncN (B Le, d); scatter: dZin (B 4T, d)
-    float* dst;        // gather: Zin (B 4T, d); scatter: dEncN (B Le, d)
-};
-
 // encoder row j -> (key, timestep): the keys in order, the visible timesteps of each ascending
 __device__ __forceinline__ void enc_row_token(const EmbG& p, int j, int* k_out, int* t_out) {
     int k = 0;
@@ -456,14 +379,6 @@ __global__ __launch_bounds__(256) void mg_std_kernel(const float* ls, float* sd,
     if (i < n) sd[i] = expf(-5.0f + 3.5f * (tanhf(ls[i]) + 1.0f));
 }
 
-struct LossBwdG {
-    const float *pred[3], *mu, *sd, *ls, *tgt[4], *eps;
-    float *dpred[3], *dmu, *dls;
-    u64 mask[4];
-    int batch, T, S, A, flags, loss_keys;
-    float entropy_reg, inv_cnt;  // 1 / (batch * hidden action timesteps * A)
-};
-
 // one thread per (row, feature) of the S + 2 + A head outputs.  The targets, the clipped action and its z are constants.
 //   key k != actions in loss_keys:  dpred = 2 (pred - t') / (B T D)
 //   actions:  dmu  = [bit] 2 (tanh mu - a) m (1 - tanh^2 mu) / (B T A)  -  hid ((z - mu) / var) / cnt  +  hid er 2 tanh(u) / cnt
@@ -521,7 +436,91 @@ __global__ __launch_bounds__(256) void mg_loss_bwd_kernel(LossBwdG p) {
 
 constexpr size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
 
+unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
+// one wavefront per item, four to a workgroup
+unsigned blocks4(long long n) { return (unsigned)((n + 3) / 4); }
+
 }  // namespace
+
+#ifdef M3PC_LAB
+thread_local int g_mg_picked = 0;
+thread_local unsigned int g_mg_picked_set = 0;
+#endif
+
+// ------------------------------------------------------------------------------------------------ the launchers (mtm_grad.h)
+void mg_launch_gemm(GemmG& p, hipStream_t st) {
+    const long long tiles = (long long)((p.M + 31) / 32) * ((p.N + 31) / 32);
+    if (tiles <= 0) return;
+    for (GOp* op : {&p.A, &p.B})
+        op->vec = op->s_k == 1 && !op->map_k && op->s_o % 4 == 0 && ((uintptr_t)op->p & 15) == 0 ? 1 : 0;
+    if (p.splitk) {
+        M3PC_MG_PICK(2);
+        hipLaunchKernelGGL(mg_gemm_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, p);
+    } else {
+        M3PC_MG_PICK(1);
+        hipLaunchKernelGGL(mg_gemm_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, st, p);
+    }
+}
+
+void mg_launch_ln_fwd(const LnG& p, hipStream_t st) {
+    M3PC_MG_PICK(3);
+    hipLaunchKernelGGL(mg_ln_fwd_kernel, dim3(blocks4(p.rows)), dim3(256), 0, st, p);
+}
+void mg_launch_ln_bwd(const LnG& p, hipStream_t st) {
+    M3PC_MG_PICK(4);
+    hipLaunchKernelGGL(mg_ln_bwd_kernel, dim3(blocks4(p.rows)), dim3(256), 0, st, p);
+}
+
+void mg_launch_colsum(ColG& p, double* scratch, hipStream_t st) {
+    const long long total = (long long)p.nseq * p.n;
+    if (total <= 0) return;  // (the gradient buffers start as zeros)
+    p.part = scratch;
+    p.chunks = mg_colsum_chunks(total);
+    M3PC_MG_PICK(5);
+    hipLaunchKernelGGL(mg_colsum_kernel, dim3((p.C + 255) / 256, p.chunks), dim3(256), 0, st, p);
+    M3PC_MG_PICK(6);
+    hipLaunchKernelGGL(mg_colsum_fin_kernel, dim3((p.C + 255) / 256), dim3(256), 0, st, p);
+}
+
+void mg_launch_attn_fwd(const AttG& p, hipStream_t st) {
+    M3PC_MG_PICK(7);
+    hipLaunchKernelGGL(mg_attn_fwd_kernel, dim3(blocks4((long long)p.B * p.nh * p.L)), dim3(256), 0, st, p);
+}
+void mg_launch_attn_col(const AttG& p, int which, hipStream_t st) {
+    M3PC_MG_PICK(8);
+    hipLaunchKernelGGL(mg_attn_col_kernel, dim3(blocks4((long long)p.B * p.nh * p.L)), dim3(256), 0, st, p, which);
+}
+void mg_launch_attn_row(const AttG& p, hipStream_t st) {
+    M3PC_MG_PICK(9);
+    hipLaunchKernelGGL(mg_attn_row_kernel, dim3(blocks4((long long)p.B * p.nh * p.L)), dim3(256), 0, st, p);
+}
+
+void mg_launch_embed(const EmbG& p, hipStream_t st) {
+    M3PC_MG_PICK(10);
+    hipLaunchKernelGGL(mg_embed_kernel, dim3(blocks256((long long)p.B * p.Le * p.d)), dim3(256), 0, st, p);
+}
+void mg_launch_gather(const EmbG& p, hipStream_t st) {
+    M3PC_MG_PICK(11);
+    hipLaunchKernelGGL(mg_gather_kernel, dim3(blocks256((long long)p.B * 4 * p.T * p.d)), dim3(256), 0, st, p);
+}
+void mg_launch_scatter(const EmbG& p, hipStream_t st) {
+    M3PC_MG_PICK(12);
+    hipLaunchKernelGGL(mg_scatter_kernel, dim3(blocks256((long long)p.B * p.Le * p.d)), dim3(256), 0, st, p);
+}
+void mg_launch_tokv(const EmbG& p, int k, float* out, hipStream_t st) {
+    M3PC_MG_PICK(13);
+    hipLaunchKernelGGL(mg_tokv_kernel, dim3(blocks256((long long)p.B * p.kept[k] * p.feat[k])), dim3(256), 0, st, p, k, out);
+}
+
+void mg_launch_std(const float* ls, float* sd, long long n, hipStream_t st) {
+    M3PC_MG_PICK(14);
+    hipLaunchKernelGGL(mg_std_kernel, dim3(blocks256(n)), dim3(256), 0, st, ls, sd, n);
+}
+void mg_launch_loss_bwd(const LossBwdG& p, hipStream_t st) {
+    M3PC_MG_PICK(15);
+    hipLaunchKernelGGL(mg_loss_bwd_kernel, dim3(blocks256((long long)p.batch * p.T * (p.S + 2 + p.A))), dim3(256), 0, st, p);
+}
+
 }  // namespace m3pc
 
 struct m3pc_mtm_grad {
@@ -626,7 +625,7 @@ int mg_ensure(Obj* g) {
     mg_layout(g, g->arena);
     const size_t RT = (size_t)g->max_batch * h->T, R = 4 * RT;
     const size_t C = (size_t)std::max(3 * h->d, h->ff);
-    const size_t n64 = al64(RT) + al64(RT * MTM_LOSS_PART) + (R / 64 + 2) * 2 * C;
+    const size_t n64 = al64(RT) + al64(RT * MTM_LOSS_PART) + mg_colsum_doubles((long long)R, (int)C);  // (no column sum has more rows than R)
     if (!g->arena64) CHK(dmalloc(&g->arena64, n64));
     g->raw_returns = g->arena64;
     g->part = g->raw_returns + al64(RT);
@@ -648,16 +647,7 @@ struct Run {
 
 const RMap NOMAP = {0, 0, 0};
 
-void run_gemm(const Run& r, GemmG& p) {
-    const long long tiles = (long long)((p.M + 31) / 32) * ((p.N + 31) / 32);
-    if (tiles <= 0) return;
-    for (GOp* op : {&p.A, &p.B})
-        op->vec = op->s_k == 1 && !op->map_k && op->s_o % 4 == 0 && ((uintptr_t)op->p & 15) == 0 ? 1 : 0;
-    if (p.splitk)
-        hipLaunchKernelGGL(mg_gemm_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, r.st, p);
-    else
-        hipLaunchKernelGGL(mg_gemm_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, r.st, p);
-}
+void run_gemm(const Run& r, GemmG& p) { mg_launch_gemm(p, r.st); }
 GemmG gemm_zero() {
     GemmG p;
     memset(&p, 0, sizeof(p));
@@ -716,14 +706,12 @@ void run_ln_fwd(const Run& r, const float* X, RMap xmap, const std::string& name
     p.st = st;
     p.rows = rows;
     p.d = r.d;
-    hipLaunchKernelGGL(mg_ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, r.st, p);
+    mg_launch_ln_fwd(p, r.st);
 }
 
 // sums over the rows (s, j) (ColG) of dY into out0 and, with X / st, of dY xhat into out1
 void run_colsum(const Run& r, const float* dY, bool dy_compact, long long ldy, const float* X, const float* st, int nseq, int L, int j0, int n,
                 u64 sel, int C, float* out0, float* out1) {
-    const long long total = (long long)nseq * n;
-    if (total <= 0) return;  // (the gradient buffers start as zeros)
     ColG p;
     memset(&p, 0, sizeof(p));
     p.dY = dY;
@@ -737,12 +725,9 @@ void run_colsum(const Run& r, const float* dY, bool dy_compact, long long ldy, c
     p.n = n;
     p.sel = sel;
     p.C = C;
-    p.part = r.g->colpart;
     p.out0 = out0;
     p.out1 = out1;
-    p.chunks = (int)((total + 63) / 64);
-    hipLaunchKernelGGL(mg_colsum_kernel, dim3((C + 255) / 256, p.chunks), dim3(256), 0, r.st, p);
-    hipLaunchKernelGGL(mg_colsum_fin_kernel, dim3((C + 255) / 256), dim3(256), 0, r.st, p);
+    mg_launch_colsum(p, r.g->colpart, r.st);
 }
 void run_colsum_rows(const Run& r, const float* dY, int rows, int C, float* out0) {
     run_colsum(r, dY, false, C, nullptr, nullptr, rows, 1, 0, 1, ~0ull, C, out0, nullptr);
@@ -767,7 +752,7 @@ void run_ln_bwd(const Run& r, const float* dY, const float* X, RMap xmap, const 
     p.rows = rows;
     p.d = r.d;
     p.accumulate = accumulate ? 1 : 0;
-    hipLaunchKernelGGL(mg_ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, r.st, p);
+    mg_launch_ln_bwd(p, r.st);
 }
 
 AttG att_params(const Run& r, const Obj::Lay& y, int L) {
@@ -793,7 +778,7 @@ void block_fwd(const Run& r, const std::string& pfx, const Obj::Lay& y, float* X
     GemmG p = gemm_fwd(y.Hn1, d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_weight"), R, 3 * d, d, y.QKV, 3 * d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_bias"));
     run_gemm(r, p);
     const AttG a = att_params(r, y, L);
-    hipLaunchKernelGGL(mg_attn_fwd_kernel, dim3((unsigned)(((long long)r.B * a.nh * L + 3) / 4)), dim3(256), 0, r.st, a);
+    mg_launch_attn_fwd(a, r.st);
     p = gemm_fwd(y.O, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.weight"), R, d, d, y.X1, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.bias"));
     p.res = y.Xin;
     run_gemm(r, p);
@@ -828,10 +813,9 @@ void block_bwd(const Run& r, const std::string& pfx, const Obj::Lay& y, int L) {
     run_gemm(r, p);
     run_colsum_rows(r, g->dX, R, d, r.Gr(pfx + ".self_attn.out_proj.bias"));
     const AttG a = att_params(r, y, L);
-    const dim3 ag((unsigned)(((long long)r.B * a.nh * L + 3) / 4));
-    hipLaunchKernelGGL(mg_attn_col_kernel, ag, dim3(256), 0, r.st, a, 0);
-    hipLaunchKernelGGL(mg_attn_row_kernel, ag, dim3(256), 0, r.st, a);
-    hipLaunchKernelGGL(mg_attn_col_kernel, ag, dim3(256), 0, r.st, a, 1);
+    mg_launch_attn_col(a, 0, r.st);
+    mg_launch_attn_row(a, r.st);
+    mg_launch_attn_col(a, 1, r.st);
     p = gemm_dx(g->dQKV, 3 * d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_weight"), R, d, 3 * d, g->dH, d, NOMAP);
     run_gemm(r, p);
     p = gemm_dw(g->dQKV, 3 * d, NOMAP, y.Hn1, d, NOMAP, 3 * d, d, R, r.Gr(pfx + ".self_attn.in_proj_weight"));
@@ -862,8 +846,6 @@ EmbG emb_params(const Run& r) {
     e.Le = r.Le;
     return e;
 }
-
-unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
 
 // everything behind the refusals: the batch is in g->tok-able form (raw rows), the masks are bits
 int mg_run(Obj* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
@@ -897,13 +879,13 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     EmbG e = emb_params(r);
     float* enc0 = nE ? g->lay[0].Xin : g->XencOut;
     e.X = enc0;
-    hipLaunchKernelGGL(mg_embed_kernel, dim3(blocks256((long long)Re * d)), dim3(256), 0, st, e);
+    mg_launch_embed(e, st);
     for (int l = 0; l < nE; ++l)
         block_fwd(r, "encoder.layers." + std::to_string(l), g->lay[l], l + 1 < nE ? g->lay[l + 1].Xin : g->XencOut, r.Le);
     run_ln_fwd(r, g->XencOut, NOMAP, "encoder.norm", g->EncN, g->st_enc, Re);
     e.src = g->EncN;
     e.dst = g->Zin;
-    hipLaunchKernelGGL(mg_gather_kernel, dim3(blocks256((long long)Rd * d)), dim3(256), 0, st, e);
+    mg_launch_gather(e, st);
     float* dec0 = nD ? g->lay[nE].Xin : g->XdecOut;
     for (int k = 0; k < 4; ++k) {
         const std::string kn = KEYN[k];
@@ -934,7 +916,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         run_gemm(r, p);
         p = gemm_fwd(g->DecN, d, am, r.Wt("output_head_dict.actions.log_std.weight"), RT, A, d, g->ls, A, NOMAP, r.Wt("output_head_dict.actions.log_std.bias"));
         run_gemm(r, p);
-        hipLaunchKernelGGL(mg_std_kernel, dim3(blocks256((long long)RT * A)), dim3(256), 0, st, g->ls, g->sd, (long long)RT * A);
+        mg_launch_std(g->ls, g->sd, (long long)RT * A, st);
     }
     {
         MtmLossP p;
@@ -986,7 +968,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         p.loss_keys = loss_keys;
         p.entropy_reg = entropy_reg;
         p.inv_cnt = (float)(1.0 / ((double)batch * (double)(T - r.kept[M3PC_ACTIONS]) * (double)A));
-        hipLaunchKernelGGL(mg_loss_bwd_kernel, dim3(blocks256((long long)RT * (S + 2 + A))), dim3(256), 0, st, p);
+        mg_launch_loss_bwd(p, st);
     }
     float* dDecN = g->dO;
     HIPCHK(hipMemsetAsync(dDecN, 0, (size_t)Rd * d * sizeof(float), st));
@@ -1040,7 +1022,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     float* dEncN = g->dO;
     e.src = g->dH;
     e.dst = dEncN;
-    hipLaunchKernelGGL(mg_scatter_kernel, dim3(blocks256((long long)Re * d)), dim3(256), 0, st, e);
+    mg_launch_scatter(e, st);
     run_ln_bwd(r, dEncN, g->XencOut, NOMAP, g->st_enc, "encoder.norm", g->dX, Re, false);
     for (int l = nE - 1; l >= 0; --l) block_bwd(r, "encoder.layers." + std::to_string(l), g->lay[l], r.Le);
     for (int k = 0; k < 4; ++k) {
@@ -1050,7 +1032,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         run_colsum(r, g->dX, false, d, nullptr, nullptr, batch, r.Le, r.eoff[k], r.kept[k], ~0ull, d, gb, nullptr);
         HIPCHK(hipMemcpyAsync(r.Gr("encoder_per_dim_encoding." + kn), gb, (size_t)d * sizeof(float), hipMemcpyDeviceToDevice, st));
         float* tokv = g->dF;  // (scratch: the layers are done with it)
-        hipLaunchKernelGGL(mg_tokv_kernel, dim3(blocks256((long long)batch * r.kept[k] * h->feat[k])), dim3(256), 0, st, e, k, tokv);
+        mg_launch_tokv(e, k, tokv, st);
         const RMap em = {r.kept[k], r.Le, r.eoff[k]};
         GemmG p = gemm_dw(g->dX, d, em, tokv, h->feat[k], NOMAP, d, h->feat[k], batch * r.kept[k], r.Gr("encoder_embed_dict." + kn + ".weight"));
         run_gemm(r, p);

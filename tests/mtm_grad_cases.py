@@ -47,6 +47,8 @@ def mask_sets(T):
         "full_and_empty": rows(T, states="all", actions=[0, 1], rewards="none", returns=[0]),  # one key fully visible, another fully hidden
         "one_token": rows(T, states=[0]),                                                      # the smallest encoder the forward accepts
         "all_but_one_action": rows(T, states="all", actions=[t for t in range(T) if t != T // 2], rewards="all", returns="all"),
+        "states_hidden": rows(T, actions=[0], returns="all"),                                  # no states token: encoder row 0 is an action's
+        "middle_key_hidden": rows(T, states="all", rewards="all", returns=[T - 1]),            # a hidden key between two visible ones
     }
 
 

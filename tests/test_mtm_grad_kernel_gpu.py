@@ -1,6 +1,8 @@
 """The kernels of m3pc_mtm_grad at their edges, against the float64 restatement (tests/mtm_grad_ref.py): row counts that are no
-multiple of the 32-row tile and cross 128 (odd), the shipped widths with hd = 128 and K = 2048 products (wide), L = 256 (long), the
-mask sets with structural zeros, and run-to-run determinism.  Bound per tensor: 16 x max(dev32[tensor], median dev32 of the case),
+multiple of the 32-row tile and cross 128 (odd), the shipped widths with hd = 128 and K = 2048 products (wide), L = 256 (long),
+hd = 64 with feature widths that are multiples of 4 and dW products of 3 and 6 rows (hd64), traj_length 1 (one), the
+mask sets with structural zeros, without a states token and with a hidden key between visible ones, and run-to-run determinism.
+(The kernels one by one: tests/test_mtm_grad_kernel_edges_gpu.py.)  Bound per tensor: 16 x max(dev32[tensor], median dev32 of the case),
 dev32 the float32 restatement's own deviation (tests/mtm_grad_cases.py)."""
 import numpy as np
 import pytest
@@ -17,6 +19,8 @@ REG = 0.1
 ODD = synth.Dims(17, 6, 5, n_embd=128, n_head=4)
 WIDE = synth.Dims(11, 3, 8, n_embd=512, n_head=4)
 LONG = synth.Dims(11, 3, 64, n_embd=64, n_head=2)
+HD64 = synth.Dims(12, 8, 3, n_embd=64, n_head=1)   # head_dim 64, feature widths that are multiples of 4, dW products of 3 and 6 rows
+ONE = synth.Dims(17, 6, 1, n_embd=64, n_head=2)    # traj_length 1: L = 4, one row per row-map group
 
 
 def _setup(dims, max_batch):
@@ -56,7 +60,7 @@ def test_odd_rows(odd, B, form):
     MC.compare(got, g64, dev32, f"odd B={B} {form}")
 
 
-@pytest.mark.parametrize("name", ["full_and_empty", "one_token", "all_but_one_action"])
+@pytest.mark.parametrize("name", ["full_and_empty", "one_token", "all_but_one_action", "states_hidden", "middle_key_hidden"])
 def test_odd_mask_sets(odd, name):
     h, sd, ostats, obj = odd
     B = 3
@@ -73,6 +77,41 @@ def test_odd_mask_sets(odd, name):
             for n, g in got.items():
                 if n.startswith("output_head_dict.rewards") or n.startswith("output_head_dict.returns"):
                     assert not g.any(), n
+
+
+@pytest.mark.parametrize("form", ["finetune", "pretrain"])
+@pytest.mark.parametrize("B", [1, 2])
+def test_head_dim_64_and_feature_widths_that_are_multiples_of_four(B, form):
+    h, sd, ostats, obj = _setup(HD64, 2)
+    try:
+        batch, eps, masks = MC.make_batch(HD64, B, 81 + B), MC.make_eps(HD64, B, 82 + B), MC.random_masks(HD64.traj_length, 83 + B)
+        rec, got = MC.device_grads(obj, batch, masks, eps, REG, form)
+        t64, g64, dev32 = MC.reference(sd, ostats, batch, masks, eps, REG, form, HD64.n_head)
+        assert np.isfinite(t64) and abs(rec[R.TOTAL] - t64) <= 1e-4 * max(1.0, abs(t64))
+        _check_record(rec, h, batch, masks, eps, form)
+        MC.compare(got, g64, dev32, f"hd64 B={B} {form}")
+    finally:
+        torch.cuda.synchronize()
+        obj.close()
+        h.close()
+
+
+def test_traj_length_one():
+    """L = 4: the states token visible, the action hidden."""
+    h, sd, ostats, obj = _setup(ONE, 3)
+    try:
+        B = 3
+        batch, eps, masks = MC.make_batch(ONE, B, 91), MC.make_eps(ONE, B, 92), MC.rows(1, states="all", rewards="all")
+        for form in ("finetune", "pretrain"):
+            rec, got = MC.device_grads(obj, batch, masks, eps, REG, form)
+            t64, g64, dev32 = MC.reference(sd, ostats, batch, masks, eps, REG, form, ONE.n_head)
+            assert np.isfinite(t64) and abs(rec[R.TOTAL] - t64) <= 1e-4 * max(1.0, abs(t64))
+            _check_record(rec, h, batch, masks, eps, form)
+            MC.compare(got, g64, dev32, f"traj_length 1 {form}")
+    finally:
+        torch.cuda.synchronize()
+        obj.close()
+        h.close()
 
 
 def test_wide():
