@@ -780,6 +780,103 @@ typedef struct m3pc_debug_mg_loss_bwd_args {
     int* picked;
 } m3pc_debug_mg_loss_bwd_args;
 int m3pc_debug_mg_loss_bwd(const m3pc_debug_mg_loss_bwd_args* a);
+/* ---- the kernels of csrc/iql.hip (the IQL trainer), each alone on caller tensors, through the launchers m3pc_iql_train_step,
+ * _evaluate, _load, _export and _publish_critic themselves use (csrc/iql.h: iql_launch_*): grid geometry, the tile count of the
+ * gradient grid and the block count of the copies are the production ones.  The caller owns every buffer; no hook creates a trainer.
+ * picked (2 ints, optional; 0 while nothing was launched): [0] the id of the kernel launched last, [1] the set of ids the call
+ * launched (bit id).  Every refusal is M3PC_EINVAL and comes before any HIP call.
+ * IQL-trainer kernel ids (tests/test_iql_kernel_edges_gpu.py reaches every id of this list):
+ *   1 iql_fwd1_kernel;  2 iql_fwd2_kernel;  3 iql_fwd3_kernel;  4 iql_loss_kernel;  5 iql_delta_kernel<2>;  6 iql_delta_kernel<1>;
+ *   7 iql_grad_kernel;  8 iql_eval_out_kernel;  9 iql_copy_kernel;  10 iql_publish_kernel
+ * (end of the IQL-trainer kernel ids) */
+/* one network (NetP), torch layout: W1 (H, in), b1 (H), W2 (H, H), b2 (H), W3 (out, H), b3 (out) */
+typedef struct m3pc_debug_iql_net {
+    float* W1;
+    float* b1;
+    float* W2;
+    float* b2;
+    float* W3;
+    float* b3;
+    int in, out;
+} m3pc_debug_iql_net;
+/* IqlP, flat.  net[0..3] = V, Q1, Q2, actor (the trained networks, in that order in d3 / d2 / d1), net[4..5] = the targets of Q1 / Q2;
+ * am / av their Adam moments.  Bp = B rounded up to 32.  h1, h2 (pass, Bp, H); out (pass, Bp, 32); d3 (4, Bp, 32); d2, d1 (4, Bp, H).
+ * The backward of trained network t reads forward pass 1, 4, 5, 6 for t = 0, 1, 2, 3.  Feature k of layer 1 is (s[k] - om[k]) / os[k]
+ * for k < S and action[k - S] beyond; s is next_state where pass_next is set.  Adam (csrc/iql.h): omb1 = 1 - beta1, b2 = beta2,
+ * omb2 = 1 - beta2 in fp32; step_size[t] = lr / (1 - beta1^t), sqrt_bc2 = sqrt(1 - beta2^t) and eps in fp64; omt = 1 - tau.
+ * Common refusals: a null structure, hidden not 64 / 128 / 256, B outside [1, 1024], A outside [1, 32], S outside [1, 64]. */
+typedef struct m3pc_debug_iql_args {
+    m3pc_debug_iql_net net[6];
+    m3pc_debug_iql_net am[4];
+    m3pc_debug_iql_net av[4];
+    float* log_std;
+    float* ls_m;
+    float* ls_v;
+    const float* om;
+    const float* os;
+    const float* state;
+    const float* action;
+    const float* reward;
+    const float* next_state;
+    const float* done;
+    float* h1;
+    float* h2;
+    float* out;
+    float* d3;
+    float* d2;
+    float* d1;
+    float* losses; /* optional */
+    int B, H, S, A;
+    int npass, pass_net[7], pass_next[7];
+    float expectile, beta, gamma, omt, tau, omb1, b2, omb2;
+    double step_size[4], sqrt_bc2, eps;
+    int which; /* forward: the layer 1, 2, 3; delta: L = 2, 1 */
+    void* stream;
+    int* picked;
+} m3pc_debug_iql_args;
+/* layer `which` of passes [0, npass) (network pass_net[f]).  1: state / next_state / action, om, os -> h1; 2: h1 -> h2; 3: h2 -> out
+ * (tanh where pass_net[f] is 3).  Refused: which outside [1, 3], npass outside [1, 7], pass_net[f] outside [0, 5], a null pointer the
+ * layer uses (layer 1: action only where a network is wider than S), in outside [1, 64] or above S + A (layer 1), out outside [1, 32]
+ * (layer 3), b1 / h1 (layer 1), W2 / b2 / h1 / h2 (layer 2), W3 / h2 / out (layer 3) off 16 bytes. */
+int m3pc_debug_iql_forward(const m3pc_debug_iql_args* a);
+/* out (7 passes: next_v, v, q1t, q2t, q1, q2, mu), reward, done, action, log_std -> d3 (all four networks, rows < Bp, 32 columns),
+ * losses (optional), and the Adam step of log_std / ls_m / ls_v with step_size[3].  Refused: a null pointer but losses. */
+int m3pc_debug_iql_loss(const m3pc_debug_iql_args* a);
+/* which 2: d2 = (W3^T d3) relu'(h2); which 1: d1 = (W2^T d2) relu'(h1); of the four trained networks.  Refused: which not 1 or 2, a null
+ * W3 (W2) of net[0..3], out outside [1, 32], a null or 16-byte-unaligned d3 / h2 / d2 (d2 / h1 / d1). */
+int m3pc_debug_iql_delta(const m3pc_debug_iql_args* a);
+/* the gradients of the four trained networks from d1 / d2 / d3, h1 / h2 and the layer-1 features, Adam on every element, and the soft
+ * update of net[4] / net[5].  Refused: a null tensor of net[0..5], am[0..3] or av[0..3], in outside [1, 64] or above S + A, out outside
+ * [1, 32], a null d1 / d2 / d3 / h1 / h2 / om / os / state (next_state where pass_next of a backward's pass is set; action where a
+ * network is wider than S). */
+int m3pc_debug_iql_grad(const m3pc_debug_iql_args* a);
+/* dst[r width + c] = out[r 32 + c], or with twin the smaller of that and out[(Bp + r) 32 + c].  Refused: a null pointer, rows outside
+ * [1, 1024], Bp below rows or no multiple of 32, width outside [1, 32]. */
+int m3pc_debug_iql_eval_out(const float* out, int Bp, int rows, int twin, int width, float* dst, void* stream, int* picked);
+/* dst[i] = src[i], i < n.  Refused: a null pointer, n < 1. */
+int m3pc_debug_iql_copy(float* dst, const float* src, long long n, void* stream, int* picked);
+/* PublishP: q[0] / q[1] (in = SA, out = 1) -> W1T (SA, H), b1, W2T (H, H), b2, W3 (H), b3 (1) of each, om / os (S) -> c_om / c_os, and with
+ * streams the operand streams W1F / W2F of critic_pack (m3pc_debug_critic_pack gives their lengths).  Refused: a null pointer (W1F / W2F
+ * only with streams), hidden not 64 / 128 / 256, S < 1, SA <= S, SA > 64, in != SA, out != 1, streams with SA > 32. */
+typedef struct m3pc_debug_iql_publish_args {
+    m3pc_debug_iql_net q[2];
+    float* W1T[2];
+    float* b1[2];
+    float* W2T[2];
+    float* b2[2];
+    float* W3[2];
+    float* b3[2];
+    float* W1F[2];
+    float* W2F[2];
+    const float* om;
+    const float* os;
+    float* c_om;
+    float* c_os;
+    int S, SA, H, streams;
+    void* stream;
+    int* picked;
+} m3pc_debug_iql_publish_args;
+int m3pc_debug_iql_publish(const m3pc_debug_iql_publish_args* a);
 /* in-kernel phase stamps of workgroup 37 of every fused-tail launch as the step runs: cap > 0 starts a ring of cap entries
  * (64 int64 each), cap == 0 copies it to `out` (host), reports the number of launches logged and stops */
 int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged);

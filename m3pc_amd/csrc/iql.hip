@@ -14,37 +14,13 @@
 // seven launches, no host wait.  The layout is critic_mfma_kernel's: weights are the A operand, data rows the B operand, so a lane
 // owns one data row (lane & 31) and accumulator i is output unit 8 (i / 4) + 4 (lane >> 5) + i % 4 of the tile.  Activations live in
 // global memory as (pass, row, unit); rows beyond the batch in the last 32-row tile carry zero inputs and zero deltas, so they add
-// exact zeros to every gradient.  iql.h states the arithmetic (the Adam order, what is fp64).
+// exact zeros to every gradient.  iql.h states the arithmetic (the Adam order, what is fp64) and holds the parameter structures and the
+// launchers every entry point goes through.
 #include "device_util.h"
 #include "iql.h"
 
 namespace m3pc {
 namespace {
-
-constexpr int IQL_MAX_BATCH = 1024, IQL_PASSES = 7, IQL_OUTW = 32, IQL_NETS = 4;
-constexpr int NET_V = 0, NET_Q1 = 1, NET_Q2 = 2, NET_ACTOR = 3, NET_Q1T = 4, NET_Q2T = 5;
-
-struct NetP {
-    float *W1, *b1, *W2, *b2, *W3, *b3;  // torch layout: (H, in) (H) (H, H) (H) (out, H) (out)
-    int in, out;
-};
-
-struct IqlP {
-    NetP net[6];                // NET_*: parameters
-    NetP am[IQL_NETS], av[IQL_NETS];  // Adam moments of the four trained networks
-    float *log_std, *ls_m, *ls_v;
-    const float *om, *os;       // obs_mean, obs_std (S)
-    const float *state, *action, *reward, *next_state, *done;
-    float *h1, *h2;             // (pass, Bp, H) activations after ReLU
-    float* out;                 // (pass, Bp, 32) network outputs
-    float *d3, *d2, *d1;        // (net, Bp, 32) (net, Bp, H) (net, Bp, H) deltas of the trained networks
-    float* losses;              // optional: value_loss, q_loss, actor_loss
-    int B, Bp, RT, H, NT, S, A;
-    int npass, pass_net[IQL_PASSES], pass_next[IQL_PASSES];  // a forward pass: its network; 1 = it reads next_state
-    float expectile, beta, gamma, omt, tau;
-    float omb1, b2, omb2;       // Adam: 1 - beta1, beta2, 1 - beta2 (iql.h)
-    double step_size[IQL_NETS], sqrt_bc2, eps;
-};
 
 __device__ __forceinline__ int train_pass(int t) { return t == 0 ? 1 : t + 3; }  // the forward pass a trained network's backward reads
 
@@ -403,16 +379,6 @@ __global__ __launch_bounds__(256) void iql_copy_kernel(float* dst, const float* 
     for (long long x = (long long)blockIdx.x * 256 + threadIdx.x; x < n; x += (long long)gridDim.x * 256) dst[x] = src[x];
 }
 
-// m3pc_iql_publish_critic: q1 / q2 into the planner's critic buffers -- the transposed copies and plain vectors the scalar critic
-// kernel reads, and (w1f != null) the MFMA operand streams of critic_pack (elementwise.hip), index for index.
-struct PublishP {
-    NetP q[2];
-    float *W1T[2], *b1[2], *W2T[2], *b2[2], *W3[2], *b3[2], *W1F[2], *W2F[2];
-    const float *om, *os;
-    float *c_om, *c_os;
-    int S, SA, H;
-    long long n_w1f, n_w2f;  // critic_w1f_floats / critic_w2f_floats, or 0
-};
 __global__ __launch_bounds__(256) void iql_publish_kernel(PublishP p) {
     const int H = p.H, SA = p.SA, NT = H / 32, NG = H / 8;
     const long long s0 = (long long)SA * H, s1 = s0 + H, s2 = s1 + (long long)H * H, s3 = s2 + H, s4 = s3 + H, s5 = s4 + 1,
@@ -458,6 +424,55 @@ __global__ __launch_bounds__(256) void iql_publish_kernel(PublishP p) {
 }
 
 }  // namespace
+
+#ifdef M3PC_LAB
+thread_local int g_iql_picked = 0;
+thread_local unsigned int g_iql_picked_set = 0;
+#endif
+
+void iql_launch_fwd(const IqlP& p, int layer, hipStream_t st) {
+    const dim3 blk(256);
+    if (layer == 1) {
+        M3PC_IQL_PICK(1);
+        hipLaunchKernelGGL(iql_fwd1_kernel, dim3((p.npass * p.RT * p.NT + 3) / 4), blk, 0, st, p);
+    } else if (layer == 2) {
+        M3PC_IQL_PICK(2);
+        hipLaunchKernelGGL(iql_fwd2_kernel, dim3((p.npass * p.RT * p.NT + 3) / 4), blk, 0, st, p);
+    } else {
+        M3PC_IQL_PICK(3);
+        hipLaunchKernelGGL(iql_fwd3_kernel, dim3((p.npass * p.RT + 3) / 4), blk, 0, st, p);
+    }
+}
+void iql_launch_loss(const IqlP& p, hipStream_t st) {
+    M3PC_IQL_PICK(4);
+    hipLaunchKernelGGL(iql_loss_kernel, dim3(1), dim3(IQL_MAX_BATCH), 0, st, p);
+}
+void iql_launch_delta(const IqlP& p, int L, hipStream_t st) {
+    const dim3 grid((IQL_NETS * p.RT * p.NT + 3) / 4), blk(256);
+    if (L == 2) {
+        M3PC_IQL_PICK(5);
+        hipLaunchKernelGGL(iql_delta_kernel<2>, grid, blk, 0, st, p);
+    } else {
+        M3PC_IQL_PICK(6);
+        hipLaunchKernelGGL(iql_delta_kernel<1>, grid, blk, 0, st, p);
+    }
+}
+void iql_launch_grad(const IqlP& p, hipStream_t st) {
+    M3PC_IQL_PICK(7);
+    hipLaunchKernelGGL(iql_grad_kernel, dim3((iql_grad_tiles(p) + 3) / 4), dim3(256), 0, st, p);
+}
+void iql_launch_eval_out(const float* out, int Bp, int rows, int twin, int width, float* dst, hipStream_t st) {
+    M3PC_IQL_PICK(8);
+    hipLaunchKernelGGL(iql_eval_out_kernel, dim3((rows * width + 255) / 256), dim3(256), 0, st, out, Bp, rows, twin, width, dst);
+}
+void iql_launch_copy(float* dst, const float* src, long long n, hipStream_t st) {
+    M3PC_IQL_PICK(9);
+    hipLaunchKernelGGL(iql_copy_kernel, dim3(iql_copy_blocks(n)), dim3(256), 0, st, dst, src, n);
+}
+void iql_launch_publish(const PublishP& p, hipStream_t st) {
+    M3PC_IQL_PICK(10);
+    hipLaunchKernelGGL(iql_publish_kernel, dim3(iql_copy_blocks(iql_publish_total(p))), dim3(256), 0, st, p);
+}
 }  // namespace m3pc
 
 // One trainer.  Device storage is allocated (and the Adam moments zeroed, in stream order) by the first call that enqueues work:
@@ -551,12 +566,6 @@ IqlP iql_params(const m3pc_iql* q) {
     return p;
 }
 
-void set_rows(IqlP& p, int rows) {
-    p.B = rows;
-    p.Bp = (rows + 31) & ~31;
-    p.RT = p.Bp / 32;
-}
-
 // the tensors of a part, by their state_dict names (model.py:146-191, :107-133): the bank (3 = the target) and the offset within it
 struct Entry {
     std::string name;
@@ -603,8 +612,6 @@ int find_named(const m3pc_named_tensor* list, int n, const std::string& name) {
     return -1;
 }
 
-int copy_blocks(long long n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
-
 bool finite_nonneg(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }
 
 int check_args(const m3pc_iql_args* a, const char* who) {
@@ -631,7 +638,7 @@ int check_trainable(const m3pc_iql* q, const char* who) {
 int iql_step(m3pc_iql* q, const m3pc_iql_args* a, int batch, const float* state, const float* action, const float* reward,
              const float* next_state, const float* done, float* losses, hipStream_t st) {
     IqlP p = iql_params(q);
-    set_rows(p, batch);
+    iql_set_rows(p, batch);
     p.state = state;
     p.action = action;
     p.reward = reward;
@@ -657,17 +664,11 @@ int iql_step(m3pc_iql* q, const m3pc_iql_args* a, int batch, const float* state,
     p.step_size[NET_ACTOR] = actor_lr / bc1;
     p.sqrt_bc2 = sqrt(bc2);
     p.eps = 1e-8;
-    const int NT = p.NT, RT = p.RT;
-    const dim3 blk(256);
-    hipLaunchKernelGGL(iql_fwd1_kernel, dim3((IQL_PASSES * RT * NT + 3) / 4), blk, 0, st, p);
-    hipLaunchKernelGGL(iql_fwd2_kernel, dim3((IQL_PASSES * RT * NT + 3) / 4), blk, 0, st, p);
-    hipLaunchKernelGGL(iql_fwd3_kernel, dim3((IQL_PASSES * RT + 3) / 4), blk, 0, st, p);
-    hipLaunchKernelGGL(iql_loss_kernel, dim3(1), dim3(IQL_MAX_BATCH), 0, st, p);
-    hipLaunchKernelGGL(iql_delta_kernel<2>, dim3((IQL_NETS * RT * NT + 3) / 4), blk, 0, st, p);
-    hipLaunchKernelGGL(iql_delta_kernel<1>, dim3((IQL_NETS * RT * NT + 3) / 4), blk, 0, st, p);
-    int tiles = 0;
-    for (int t2 = 0; t2 < IQL_NETS; ++t2) tiles += NT * ((q->off[t2].in + 31) / 32 + 1) + NT * (NT + 1) + NT + 1;
-    hipLaunchKernelGGL(iql_grad_kernel, dim3((tiles + 3) / 4), blk, 0, st, p);
+    for (int layer = 1; layer <= 3; ++layer) iql_launch_fwd(p, layer, st);
+    iql_launch_loss(p, st);
+    iql_launch_delta(p, 2, st);
+    iql_launch_delta(p, 1, st);
+    iql_launch_grad(p, st);
     CHK(check_launch("iql_train_step"));
     q->total_it += 1;
     return 0;
@@ -749,15 +750,15 @@ int m3pc_iql_load(m3pc_iql* q, int part, const m3pc_named_tensor* tensors, int n
         const void* src = t.data;
         if (!t.on_device)
             if (int rc = q->pool.stage(t.data, (size_t)t.numel * sizeof(float), &src, "m3pc_iql")) return abandon(rc);
-        hipLaunchKernelGGL(iql_copy_kernel, dim3(copy_blocks(t.numel)), dim3(256), 0, st, entry_dev(q, ent[i]), (const float*)src, t.numel);
+        iql_launch_copy(entry_dev(q, ent[i]), (const float*)src, t.numel, st);
     }
     if (obs_mean) {
         const void *m = nullptr, *s = nullptr;
         int rc = q->pool.stage(obs_mean, (size_t)q->S * sizeof(float), &m, "m3pc_iql");
         if (!rc) rc = q->pool.stage(obs_std, (size_t)q->S * sizeof(float), &s, "m3pc_iql");
         if (rc) return abandon(rc);
-        hipLaunchKernelGGL(iql_copy_kernel, dim3(1), dim3(256), 0, st, q->om, (const float*)m, (long long)q->S);
-        hipLaunchKernelGGL(iql_copy_kernel, dim3(1), dim3(256), 0, st, q->os, (const float*)s, (long long)q->S);
+        iql_launch_copy(q->om, (const float*)m, (long long)q->S, st);
+        iql_launch_copy(q->os, (const float*)s, (long long)q->S, st);
         q->norm_set = true;
     }
     const int rc = check_launch("iql_load");
@@ -786,7 +787,7 @@ int m3pc_iql_export(m3pc_iql* q, int part, const m3pc_named_tensor* tensors, int
     for (size_t i = 0; i < ent.size(); ++i) {
         const m3pc_named_tensor& t = tensors[at[i]];
         float* dst = const_cast<float*>(t.data);
-        if (t.on_device) hipLaunchKernelGGL(iql_copy_kernel, dim3(copy_blocks(t.numel)), dim3(256), 0, st, dst, (const float*)entry_dev(q, ent[i]), t.numel);
+        if (t.on_device) iql_launch_copy(dst, (const float*)entry_dev(q, ent[i]), t.numel, st);
         else HIPCHK(hipMemcpyAsync(dst, entry_dev(q, ent[i]), (size_t)t.numel * sizeof(float), hipMemcpyDeviceToHost, st));
     }
     return check_launch("iql_export");
@@ -879,8 +880,7 @@ int m3pc_iql_publish_critic(m3pc_iql* q, m3pc_handle* h, void* stream) {
     const bool packed = h->cW1F[0] != nullptr;
     p.n_w1f = packed ? (long long)critic_w1f_floats(q->H) : 0;
     p.n_w2f = packed ? (long long)critic_w2f_floats(q->H) : 0;
-    const long long total = 2 * ((long long)p.SA * q->H + (long long)q->H * q->H + 3 * q->H + 1 + p.n_w1f + p.n_w2f + q->S);
-    hipLaunchKernelGGL(iql_publish_kernel, dim3(copy_blocks(total)), dim3(256), 0, st, p);
+    iql_launch_publish(p, st);
     CHK(check_launch("iql_publish_critic"));
     h->critic_set = true;
     return 0;
@@ -904,15 +904,11 @@ int m3pc_iql_evaluate(m3pc_iql* q, int which, const float* states, const float* 
     const int width = which == M3PC_IQL_ACTOR_MEAN ? q->A : 1;
     for (int r0 = 0; r0 < rows; r0 += IQL_MAX_BATCH) {
         const int nr = rows - r0 < IQL_MAX_BATCH ? rows - r0 : IQL_MAX_BATCH;
-        set_rows(p, nr);
+        iql_set_rows(p, nr);
         p.state = states + (size_t)r0 * q->S;
         p.action = actions ? actions + (size_t)r0 * q->A : nullptr;
-        const dim3 blk(256);
-        hipLaunchKernelGGL(iql_fwd1_kernel, dim3((p.npass * p.RT * p.NT + 3) / 4), blk, 0, st, p);
-        hipLaunchKernelGGL(iql_fwd2_kernel, dim3((p.npass * p.RT * p.NT + 3) / 4), blk, 0, st, p);
-        hipLaunchKernelGGL(iql_fwd3_kernel, dim3((p.npass * p.RT + 3) / 4), blk, 0, st, p);
-        hipLaunchKernelGGL(iql_eval_out_kernel, dim3((nr * width + 255) / 256), blk, 0, st, (const float*)p.out, p.Bp, nr, twin ? 1 : 0, width,
-                           out + (size_t)r0 * width);
+        for (int layer = 1; layer <= 3; ++layer) iql_launch_fwd(p, layer, st);
+        iql_launch_eval_out(p.out, p.Bp, nr, twin ? 1 : 0, width, out + (size_t)r0 * width, st);
     }
     return check_launch("iql_evaluate");
 }

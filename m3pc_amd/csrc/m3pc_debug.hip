@@ -2,6 +2,7 @@
 // include/m3pc_hip_debug.h.  The product build does not compile this file.
 #include "m3pc_internal.h"
 #include "mtm_grad.h"
+#include "iql.h"
 
 #include <vector>
 
@@ -1393,6 +1394,179 @@ int m3pc_debug_mg_loss_bwd(const m3pc_debug_mg_loss_bwd_args* a) {
     mg_begin(a->picked);
     mg_launch_loss_bwd(p, (hipStream_t)a->stream);
     return mg_done(a->picked, "debug_mg_loss_bwd");
+}
+
+// ---- csrc/iql.hip, kernel by kernel (include/m3pc_hip_debug.h, "IQL-trainer kernel ids"; tests/test_iql_kernel_edges_gpu.py).
+// Every hook checks first (no HIP call before a refusal), fills the kernel's parameter structure, goes through the launcher
+// the trainer uses and reports what that launcher recorded.
+static void iql_begin(int* picked) {
+    if (picked) picked[0] = picked[1] = 0;
+    g_iql_picked = 0;
+    g_iql_picked_set = 0;
+}
+static int iql_done(int* picked, const char* what) {
+    if (picked) {
+        picked[0] = g_iql_picked;
+        picked[1] = (int)g_iql_picked_set;
+    }
+    return check_launch(what);
+}
+static bool iql_off16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+static NetP iql_net(const m3pc_debug_iql_net& n) { return NetP{n.W1, n.b1, n.W2, n.b2, n.W3, n.b3, n.in, n.out}; }
+static bool iql_net_null(const m3pc_debug_iql_net& n) { return !n.W1 || !n.b1 || !n.W2 || !n.b2 || !n.W3 || !n.b3; }
+static int iql_common(const m3pc_debug_iql_args* a, const char* who) {
+    if (!a) return fail(M3PC_EINVAL, "%s: null arguments", who);
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (a->H != 64 && a->H != 128 && a->H != 256) return fail(M3PC_EINVAL, "%s: hidden %d is none of 64, 128, 256", who, a->H);
+    if (a->B < 1 || a->B > IQL_MAX_BATCH) return fail(M3PC_EINVAL, "%s: B %d outside [1, %d]", who, a->B, IQL_MAX_BATCH);
+    if (a->A < 1 || a->A > 32) return fail(M3PC_EINVAL, "%s: A %d outside [1, 32]", who, a->A);
+    if (a->S < 1 || a->S > 64) return fail(M3PC_EINVAL, "%s: S %d outside [1, 64]", who, a->S);
+    return 0;
+}
+static int iql_bad_in(const m3pc_debug_iql_args* a, const m3pc_debug_iql_net& n, const char* who) {
+    if (n.in < 1 || n.in > 64 || n.in > a->S + a->A) return fail(M3PC_EINVAL, "%s: in %d outside [1, 64] or above S + A = %d", who, n.in, a->S + a->A);
+    if (n.in > a->S && !a->action) return fail(M3PC_EINVAL, "%s: a network is wider than S and action is null", who);
+    return 0;
+}
+static IqlP iql_fill(const m3pc_debug_iql_args* a) {
+    IqlP p;
+    memset(&p, 0, sizeof(p));
+    for (int t = 0; t < 6; ++t) p.net[t] = iql_net(a->net[t]);
+    for (int t = 0; t < IQL_NETS; ++t) p.am[t] = iql_net(a->am[t]), p.av[t] = iql_net(a->av[t]);
+    p.log_std = a->log_std, p.ls_m = a->ls_m, p.ls_v = a->ls_v;
+    p.om = a->om, p.os = a->os;
+    p.state = a->state, p.action = a->action, p.reward = a->reward, p.next_state = a->next_state, p.done = a->done;
+    p.h1 = a->h1, p.h2 = a->h2, p.out = a->out, p.d3 = a->d3, p.d2 = a->d2, p.d1 = a->d1, p.losses = a->losses;
+    iql_set_rows(p, a->B);
+    p.H = a->H, p.NT = a->H / 32, p.S = a->S, p.A = a->A;
+    p.npass = a->npass;
+    for (int f = 0; f < IQL_PASSES; ++f) p.pass_net[f] = a->pass_net[f], p.pass_next[f] = a->pass_next[f] ? 1 : 0;
+    p.expectile = a->expectile, p.beta = a->beta, p.gamma = a->gamma, p.omt = a->omt, p.tau = a->tau;
+    p.omb1 = a->omb1, p.b2 = a->b2, p.omb2 = a->omb2;
+    for (int t = 0; t < IQL_NETS; ++t) p.step_size[t] = a->step_size[t];
+    p.sqrt_bc2 = a->sqrt_bc2, p.eps = a->eps;
+    return p;
+}
+
+int m3pc_debug_iql_forward(const m3pc_debug_iql_args* a) {
+    const char* who = "debug_iql_forward";
+    CHK(iql_common(a, who));
+    if (a->which < 1 || a->which > 3) return fail(M3PC_EINVAL, "%s: layer %d outside [1, 3]", who, a->which);
+    if (a->npass < 1 || a->npass > IQL_PASSES) return fail(M3PC_EINVAL, "%s: npass %d outside [1, %d]", who, a->npass, IQL_PASSES);
+    for (int f = 0; f < a->npass; ++f) {
+        if (a->pass_net[f] < 0 || a->pass_net[f] > 5) return fail(M3PC_EINVAL, "%s: pass_net[%d] %d outside [0, 5]", who, f, a->pass_net[f]);
+        const m3pc_debug_iql_net& n = a->net[a->pass_net[f]];
+        if (a->which == 1) {
+            if (!n.W1 || !n.b1 || !a->om || !a->os || !a->h1 || !(a->pass_next[f] ? a->next_state : a->state)) return fail(M3PC_EINVAL, "%s: null pointer", who);
+            CHK(iql_bad_in(a, n, who));
+            if (iql_off16(n.b1) || iql_off16(a->h1)) return fail(M3PC_EINVAL, "%s: b1 / h1 off 16 bytes", who);
+        } else if (a->which == 2) {
+            if (!n.W2 || !n.b2 || !a->h1 || !a->h2) return fail(M3PC_EINVAL, "%s: null pointer", who);
+            if (iql_off16(n.W2) || iql_off16(n.b2) || iql_off16(a->h1) || iql_off16(a->h2)) return fail(M3PC_EINVAL, "%s: W2 / b2 / h1 / h2 off 16 bytes", who);
+        } else {
+            if (!n.W3 || !n.b3 || !a->h2 || !a->out) return fail(M3PC_EINVAL, "%s: null pointer", who);
+            if (n.out < 1 || n.out > IQL_OUTW) return fail(M3PC_EINVAL, "%s: out %d outside [1, %d]", who, n.out, IQL_OUTW);
+            if (iql_off16(n.W3) || iql_off16(a->h2) || iql_off16(a->out)) return fail(M3PC_EINVAL, "%s: W3 / h2 / out off 16 bytes", who);
+        }
+    }
+    const IqlP p = iql_fill(a);
+    iql_begin(a->picked);
+    iql_launch_fwd(p, a->which, (hipStream_t)a->stream);
+    return iql_done(a->picked, who);
+}
+
+int m3pc_debug_iql_loss(const m3pc_debug_iql_args* a) {
+    const char* who = "debug_iql_loss";
+    CHK(iql_common(a, who));
+    if (!a->out || !a->reward || !a->done || !a->action || !a->log_std || !a->ls_m || !a->ls_v || !a->d3) return fail(M3PC_EINVAL, "%s: null pointer", who);
+    const IqlP p = iql_fill(a);
+    iql_begin(a->picked);
+    iql_launch_loss(p, (hipStream_t)a->stream);
+    return iql_done(a->picked, who);
+}
+
+int m3pc_debug_iql_delta(const m3pc_debug_iql_args* a) {
+    const char* who = "debug_iql_delta";
+    CHK(iql_common(a, who));
+    if (a->which != 1 && a->which != 2) return fail(M3PC_EINVAL, "%s: L %d is neither 1 nor 2", who, a->which);
+    for (int t = 0; t < IQL_NETS; ++t) {
+        if (!(a->which == 2 ? a->net[t].W3 : a->net[t].W2)) return fail(M3PC_EINVAL, "%s: null pointer", who);
+        if (a->which == 2 && (a->net[t].out < 1 || a->net[t].out > IQL_OUTW)) return fail(M3PC_EINVAL, "%s: out %d outside [1, %d]", who, a->net[t].out, IQL_OUTW);
+    }
+    const float *in = a->which == 2 ? a->d3 : a->d2, *act = a->which == 2 ? a->h2 : a->h1, *o = a->which == 2 ? a->d2 : a->d1;
+    if (!in || !act || !o) return fail(M3PC_EINVAL, "%s: null pointer", who);
+    if (iql_off16(in) || iql_off16(act) || iql_off16(o)) return fail(M3PC_EINVAL, "%s: a delta or activation buffer off 16 bytes", who);
+    const IqlP p = iql_fill(a);
+    iql_begin(a->picked);
+    iql_launch_delta(p, a->which, (hipStream_t)a->stream);
+    return iql_done(a->picked, who);
+}
+
+int m3pc_debug_iql_grad(const m3pc_debug_iql_args* a) {
+    const char* who = "debug_iql_grad";
+    CHK(iql_common(a, who));
+    for (int t = 0; t < 6; ++t)
+        if (iql_net_null(a->net[t]) || (t < IQL_NETS && (iql_net_null(a->am[t]) || iql_net_null(a->av[t])))) return fail(M3PC_EINVAL, "%s: null pointer", who);
+    if (!a->d1 || !a->d2 || !a->d3 || !a->h1 || !a->h2 || !a->om || !a->os) return fail(M3PC_EINVAL, "%s: null pointer", who);
+    for (int t = 0; t < IQL_NETS; ++t) {
+        CHK(iql_bad_in(a, a->net[t], who));
+        if (a->net[t].out < 1 || a->net[t].out > IQL_OUTW) return fail(M3PC_EINVAL, "%s: out %d outside [1, %d]", who, a->net[t].out, IQL_OUTW);
+        const int f = t == 0 ? 1 : t + 3;
+        if (!(a->pass_next[f] ? a->next_state : a->state)) return fail(M3PC_EINVAL, "%s: null pointer", who);
+    }
+    const IqlP p = iql_fill(a);
+    iql_begin(a->picked);
+    iql_launch_grad(p, (hipStream_t)a->stream);
+    return iql_done(a->picked, who);
+}
+
+int m3pc_debug_iql_eval_out(const float* out, int Bp, int rows, int twin, int width, float* dst, void* stream, int* picked) {
+    if (picked) picked[0] = picked[1] = 0;
+    if (!out || !dst) return fail(M3PC_EINVAL, "debug_iql_eval_out: null pointer");
+    if (rows < 1 || rows > IQL_MAX_BATCH || Bp < rows || Bp % 32 || width < 1 || width > IQL_OUTW)
+        return fail(M3PC_EINVAL, "debug_iql_eval_out: rows %d outside [1, %d], Bp %d below it or no multiple of 32, or width %d outside [1, %d]", rows, IQL_MAX_BATCH, Bp, width, IQL_OUTW);
+    iql_begin(picked);
+    iql_launch_eval_out(out, Bp, rows, twin ? 1 : 0, width, dst, (hipStream_t)stream);
+    return iql_done(picked, "debug_iql_eval_out");
+}
+
+int m3pc_debug_iql_copy(float* dst, const float* src, long long n, void* stream, int* picked) {
+    if (picked) picked[0] = picked[1] = 0;
+    if (!dst || !src || n < 1) return fail(M3PC_EINVAL, "debug_iql_copy: null pointer or n %lld < 1", n);
+    iql_begin(picked);
+    iql_launch_copy(dst, src, n, (hipStream_t)stream);
+    return iql_done(picked, "debug_iql_copy");
+}
+
+int m3pc_debug_iql_publish(const m3pc_debug_iql_publish_args* a) {
+    const char* who = "debug_iql_publish";
+    if (!a) return fail(M3PC_EINVAL, "%s: null arguments", who);
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (a->H != 64 && a->H != 128 && a->H != 256) return fail(M3PC_EINVAL, "%s: hidden %d is none of 64, 128, 256", who, a->H);
+    if (a->S < 1 || a->SA <= a->S || a->SA > 64) return fail(M3PC_EINVAL, "%s: S %d < 1, or S + A = %d not above it or above 64", who, a->S, a->SA);
+    if (a->streams && a->SA > 32) return fail(M3PC_EINVAL, "%s: the operand streams cover S + A <= 32, not %d", who, a->SA);
+    bool null = !a->om || !a->os || !a->c_om || !a->c_os;
+    for (int i = 0; i < 2; ++i) {
+        null = null || iql_net_null(a->q[i]) || !a->W1T[i] || !a->b1[i] || !a->W2T[i] || !a->b2[i] || !a->W3[i] || !a->b3[i];
+        if (a->streams) null = null || !a->W1F[i] || !a->W2F[i];
+    }
+    if (null) return fail(M3PC_EINVAL, "%s: null pointer", who);
+    for (int i = 0; i < 2; ++i)
+        if (a->q[i].in != a->SA || a->q[i].out != 1) return fail(M3PC_EINVAL, "%s: q[%d] has in %d / out %d, a critic has %d / 1", who, i, a->q[i].in, a->q[i].out, a->SA);
+    PublishP p;
+    memset(&p, 0, sizeof(p));
+    for (int i = 0; i < 2; ++i) {
+        p.q[i] = iql_net(a->q[i]);
+        p.W1T[i] = a->W1T[i], p.b1[i] = a->b1[i], p.W2T[i] = a->W2T[i], p.b2[i] = a->b2[i], p.W3[i] = a->W3[i], p.b3[i] = a->b3[i];
+        p.W1F[i] = a->streams ? a->W1F[i] : nullptr, p.W2F[i] = a->streams ? a->W2F[i] : nullptr;
+    }
+    p.om = a->om, p.os = a->os, p.c_om = a->c_om, p.c_os = a->c_os;
+    p.S = a->S, p.SA = a->SA, p.H = a->H;
+    p.n_w1f = a->streams ? (long long)critic_w1f_floats(a->H) : 0;
+    p.n_w2f = a->streams ? (long long)critic_w2f_floats(a->H) : 0;
+    iql_begin(a->picked);
+    iql_launch_publish(p, (hipStream_t)a->stream);
+    return iql_done(a->picked, who);
 }
 
 // kv_fused_kernel alone (tests/test_block_fused_gpu.py): n candidates of Le rows each in Z (n*Le, 512) bf16; group g holds

@@ -13,15 +13,19 @@ Per case of iql_ref.CASES the capture holds
   ref32_grad_dev   per tensor, max|g32 - g64| / max|g64| of the first step's gradient, g = exp_avg / (1 - beta1) in both runs;
   ref32_loss_dev   per loss, the largest relative deviation of the float32 run over the 20 steps;
   ref32_param_dev  per tensor, max|p32 - p64| after the 20 steps; ref32_traj_dev, its largest over the tensors of the case
-(what the float32 arithmetic of the reference itself loses: the GPU tests allow the device 16 times that), and for the hidden-64 case
+(what the float32 arithmetic of the reference itself loses: the GPU tests allow the device 16 times that), and for the case h64
 the first batch, the first step's exp_avg / exp_avg_sq and the final parameters of both runs (exp_avg_sq of the float32 run only).
 
-Not stored, although a capture could hold them: the initial state and the batches after the first, even for the hidden-64 case.
+Not stored, although a capture could hold them: the initial state and the batches after the first, even for h64 (and for the other
+hidden-64 cases, a32 and b1024, not the first batch, moments and final parameters either: the file stays below the size a committed
+file may have).
 Both are functions of a seed (tests/iql_ref.py), so the capture and the tests build the same arrays; what ties the recipes to this
 capture is the equality of the first batch and, for every case, the 20 float64 losses at 1e-10, which no other weights or batches
 reproduce (tests/test_iql_cpu.py).
 
-Usage:  python tests/golden/make_iql_golden.py /path/to/reference
+Usage:  python tests/golden/make_iql_golden.py /path/to/reference [--add]
+--add keeps what the file already holds and captures only the cases of iql_ref.CASES it lacks: the float32 run of a case depends on
+the BLAS of the machine that made it, and the tolerances of the GPU tests are scaled from it, so a new case does not move the old ones.
 """
 import os
 import sys
@@ -34,7 +38,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-REFERENCE = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("M3PC_REFERENCE")
+ADD = "--add" in sys.argv
+ARGS = [x for x in sys.argv[1:] if x != "--add"]
+REFERENCE = ARGS[0] if ARGS else os.environ.get("M3PC_REFERENCE")
 if not REFERENCE or not os.path.isdir(os.path.join(REFERENCE, "research")):
     sys.exit("usage: make_iql_golden.py /path/to/reference  (the checkout that holds research/finetune_omtm/model.py)")
 sys.modules.setdefault("gym", types.ModuleType("gym"))
@@ -91,8 +97,16 @@ def run(case, dtype):
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(1)
-    out = {"cases": np.array(list(R.CASES)), "n_steps": np.int64(R.N_STEPS)}
+    path = os.path.join(HERE, "g7_iql.npz")
+    out, have = {}, set()
+    if ADD and os.path.exists(path):
+        with np.load(path) as old:
+            out = {k: old[k] for k in old.files}
+        have = {str(c) for c in out["cases"]}
+    out["cases"], out["n_steps"] = np.array(list(R.CASES)), np.int64(R.N_STEPS)
     for case in R.CASES:
+        if case in have:
+            continue
         l32, m32, v32, p32 = run(case, torch.float32)
         l64, m64, v64, p64 = run(case, torch.float64)
         ref, lref, _ = R.run(case)
@@ -114,7 +128,7 @@ def main():
         print(case, "grad dev %.2e  loss dev %.2e  param dev %.2e  | restatement vs float64 reference: losses %.1e" % (
             max(gdev), out[case + "/ref32_loss_dev"].max(), out[case + "/ref32_param_dev"].max(), (np.abs(lref - l64) / np.abs(l64)).max()),
             "| conditions", out[case + "/conditions"])
-        if R.CASES[case][2] == 64:
+        if case == "h64":
             for j, key in enumerate(("state", "action", "reward", "next_state", "done")):
                 out[case + "/batch0/" + key] = R.make_batches(case, 1)[0][j]
             for n in gnames:
@@ -124,7 +138,6 @@ def main():
             for n in pnames:
                 part, name = n.split("/")
                 out[case + "/final32/" + n], out[case + "/final64/" + n] = p32[part][name], p64[part][name]
-    path = os.path.join(HERE, "g7_iql.npz")
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), "bytes")
 

@@ -9,12 +9,15 @@ import numpy as np
 
 # (S, A, hidden, batch): a partial 32-row tile; S + A = 35 (a second feature tile) and one row past a tile; a single row; the
 # reference's own batch; S = 40, a second feature tile in V and the actor as well (the widest states the trainer's size rule covers
-# are S = 63: wider than a planner handle's, so the GPU tests make this trainer on a stand-in for a handle)
-CASES = {"h64": (11, 3, 64, 37), "h128": (27, 8, 128, 33), "h256_1": (11, 3, 256, 1), "h256": (17, 6, 256, 256), "s40": (40, 6, 128, 33)}
+# are S = 63: wider than a planner handle's, so the GPU tests make this trainer on a stand-in for a handle); S = A = 32, both input
+# widths whole feature tiles, the widest actor and a batch of whole row tiles; the largest batch a step takes
+CASES = {"h64": (11, 3, 64, 37), "h128": (27, 8, 128, 33), "h256_1": (11, 3, 256, 1), "h256": (17, 6, 256, 256), "s40": (40, 6, 128, 33),
+         "a32": (32, 32, 64, 64), "b1024": (11, 3, 64, 1024)}
 # picked so that the fixture conditions of test_iql_cpu.py hold and, among those, so that the reference's own float32 gradient of a
 # single-number tensor (the bias of an output unit) is at least 2^-27 of it away from the exact one: a smaller deviation (1e-9 was
 # seen) is chance, and 16 x it is less than the spacing of float32 there, no tolerance for any float32 evaluation
-SEEDS = {"h64": 41, "h128": 71, "h256_1": 38, "h256": 515, "s40": 1}
+SEEDS = {"h64": 41, "h128": 71, "h256_1": 38, "h256": 515, "s40": 1, "a32": 2, "b1024": 1}
+LOG_STD_BELOW = ("a32",)   # cases whose log_std also has a component below the lower clamp
 HP = dict(v_lr=3e-4, q_lr=3e-4, actor_lr=3e-4, expectile=0.7, beta=3.0, discount=0.99, tau=0.005, max_steps=1000)
 N_STEPS = 20
 PARTS = ("qf", "q_target", "vf", "actor")
@@ -44,8 +47,8 @@ def part_shapes(part, S, A, H):
 def make_state(case, seed=None):
     """{part: {name: float32 array}}, obs_mean, obs_std.  Linear layers as nn.Linear draws them (uniform within 1 / sqrt(fan_in)), the
     output layers of V and Q four times as wide, so that advantages reach both signs and the clamp of exp(beta adv); q_target is a draw
-    of its own (not a copy of qf: the soft update then has something to move); log_std has one component above the clamp, which
-    gets no gradient, and the others inside it."""
+    of its own (not a copy of qf: the soft update then has something to move); log_std has one component above the clamp (and in the
+    cases of LOG_STD_BELOW one below it), which gets no gradient, and the others inside it."""
     S, A, H, _ = CASES[case]
     rng = np.random.RandomState(1000 + (SEEDS[case] if seed is None else seed))
     state = {}
@@ -56,6 +59,8 @@ def make_state(case, seed=None):
                 v = rng.uniform(-1.0, 0.5, size=shape)
                 v[0] = 2.5
                 v[1] = -0.5
+                if case in LOG_STD_BELOW:
+                    v[2] = -20.5
             else:
                 fan_in = shape[1] if len(shape) == 2 else (H if ".0." not in name else (S + A if part in ("qf", "q_target") else S))
                 gain = 4.0 if (".4." in name and part != "actor") else 1.0

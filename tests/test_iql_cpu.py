@@ -208,13 +208,13 @@ def test_every_bad_argument_is_refused_without_a_gpu(lib):
 
 @pytest.mark.parametrize("case", list(R.CASES))
 def test_the_restatement_is_the_reference_in_float64(golden, runs, case):
-    """tests/iql_ref.py against the .double() run of the real ImplicitQLearning: the 20 losses of every case, and for the hidden-64
-    case the first step's exp_avg and the final parameters, at 1e-10."""
+    """tests/iql_ref.py against the .double() run of the real ImplicitQLearning: the 20 losses of every case, and for the case
+    h64 the first step's exp_avg and the final parameters, at 1e-10."""
     ref, losses, g1 = runs[case]
     want = golden[case + "/losses64"]
     assert losses.shape == want.shape == (R.N_STEPS, 3)
     assert np.abs(losses - want).max() <= 1e-10 * np.abs(want).max(), np.abs(losses / want - 1).max()
-    if R.CASES[case][2] != 64:
+    if case != "h64":
         return
     for j, key in enumerate(("state", "action", "reward", "next_state", "done")):   # the recipe is the captured one
         assert np.array_equal(R.make_batches(case, 1)[0][j], golden[case + "/batch0/" + key]), key

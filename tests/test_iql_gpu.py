@@ -11,7 +11,9 @@ Parameters after an Adam step are NOT compared elementwise with the float64 run:
       step on the same batch with all rates 0 repeats the gradient bits), the soft update bit for bit.
   (c) the trajectory: 20 steps; losses relatively and final parameters absolutely within 16 x the float32 reference's deviation.
 Cases (S, A, hidden, batch): (11, 3, 64, 37) a partial 32-row tile; (27, 8, 128, 33) S + A = 35, a second feature tile, one row past a
-tile; (11, 3, 256, 1) a single row; (17, 6, 256, 256) the reference's own batch; (40, 6, 128, 33) states wider than one feature tile."""
+tile; (11, 3, 256, 1) a single row; (17, 6, 256, 256) the reference's own batch; (40, 6, 128, 33) states wider than one feature tile;
+(32, 32, 64, 64) both input widths and the batch whole tiles, the widest actor, a log_std component below the lower clamp as well;
+(11, 3, 64, 1024) the largest batch."""
 import ctypes as C
 import math
 import os
@@ -145,8 +147,11 @@ def test_a_first_step_gradients(golden, case):
         print("  grad %-24s device %.2e  reference float32 %.2e" % (n, dev, t / 16.0))
         assert dev <= t, (n, dev, t)
     print("  %s: largest gradient deviation %.2e" % (case, worst))
-    # the clamped component of log_std gets no gradient at all
-    assert run.after1["m/actor/log_std"][0] == 0.0 and run.after1["v/actor/log_std"][0] == 0.0 and (run.after1["m/actor/log_std"][1:] != 0).all()
+    # a clamped component of log_std gets no gradient at all (component 0, above the clamp, in every case; component 2, below it, in a32)
+    ls = run.before["p/actor/log_std"]
+    out = (ls > R.LOG_STD_MAX) | (ls < R.LOG_STD_MIN)
+    assert out[0] and out.sum() == (2 if case in R.LOG_STD_BELOW else 1) and (not out[2:].any() or ls[2] < R.LOG_STD_MIN)
+    assert (run.after1["m/actor/log_std"][out] == 0.0).all() and (run.after1["v/actor/log_std"][out] == 0.0).all() and (run.after1["m/actor/log_std"][~out] != 0).all()
 
 
 @pytest.mark.parametrize("case", list(R.CASES))
@@ -220,23 +225,32 @@ def test_two_runs_give_the_same_bits(case):
     assert np.isfinite(run.traj[0]).all()
 
 
+EVAL_ROWS = {"h64": (1024, 1025, 2049), "h256": (1030,)}   # (the other cases: their own batch)
+
+
 @pytest.mark.parametrize("case", ["h64", "h128", "h256", "s40"])
 def test_evaluate_against_the_restatement(case):
-    """Q_MIN, Q_TARGET_MIN, V and ACTOR_MEAN at the loaded weights, on more rows than one pass takes (1024).  Tolerance: three layers of
-    fp32 sums of at most 256 terms, each off by at most K 2^-24 of the sum of its terms' magnitudes -- 2e-5 of the largest output."""
+    """Q_MIN, Q_TARGET_MIN, V and ACTOR_MEAN at the loaded weights; at hidden 64 on exactly one pass of rows (1024), one row more and
+    two passes and a row (2049), at hidden 256 on 1030 rows (the second pass takes 6).  Tolerance: three layers of fp32 sums of at most
+    256 terms, each off by at most K 2^-24 of the sum of its terms' magnitudes -- 2e-5 of the largest output."""
     S, A, H, B = R.CASES[case]
     q = _trainer(case)
     state, om, os_ = R.make_state(case)
     ref = R.RefIQL(state, om, os_)
-    rows = 1030 if case == "h64" else B
-    bs = R.make_batches(case, (rows + B - 1) // B)
-    s, a = np.concatenate([b[0] for b in bs])[:rows], np.concatenate([b[1] for b in bs])[:rows]
-    s64, a64 = s.astype(np.float64), a.astype(np.float64)
-    for which, want in ((capi.IQL_Q_MIN, ref.q_min("qf", s64, a64)), (capi.IQL_Q_TARGET_MIN, ref.q_min("q_target", s64, a64)),
-                        (capi.IQL_V, ref.value(s64)), (capi.IQL_ACTOR_MEAN, ref.actor_mean(s64))):
-        got = q.evaluate(which, torch.from_numpy(s), None if which in (capi.IQL_V, capi.IQL_ACTOR_MEAN) else torch.from_numpy(a)).cpu().numpy()
-        assert got.shape == want.shape and np.abs(got - want).max() <= 2e-5 * max(1.0, np.abs(want).max()), (which, np.abs(got - want).max())
-    assert np.allclose(q.act(s[0]), np.clip(ref.actor_mean(s64[:1])[0], -1, 1), atol=2e-5)
+    most = max(EVAL_ROWS.get(case, (B,)))
+    bs = R.make_batches(case, 1)
+    rng = np.random.RandomState(17)
+    reps = (most + B - 1) // B    # the recipe's rows, jittered: every row its own
+    s_all = (np.concatenate([bs[0][0]] * reps) + rng.normal(size=(reps * B, S)) * 0.1).astype(np.float32)
+    a_all = np.clip(np.concatenate([bs[0][1]] * reps) + rng.normal(size=(reps * B, A)) * 0.05, -1, 1).astype(np.float32)
+    for rows in EVAL_ROWS.get(case, (B,)):
+        s, a = s_all[:rows], a_all[:rows]
+        s64, a64 = s.astype(np.float64), a.astype(np.float64)
+        for which, want in ((capi.IQL_Q_MIN, ref.q_min("qf", s64, a64)), (capi.IQL_Q_TARGET_MIN, ref.q_min("q_target", s64, a64)),
+                            (capi.IQL_V, ref.value(s64)), (capi.IQL_ACTOR_MEAN, ref.actor_mean(s64))):
+            got = q.evaluate(which, torch.from_numpy(s), None if which in (capi.IQL_V, capi.IQL_ACTOR_MEAN) else torch.from_numpy(a)).cpu().numpy()
+            assert got.shape == want.shape and np.abs(got - want).max() <= 2e-5 * max(1.0, np.abs(want).max()), (rows, which, np.abs(got - want).max())
+    assert np.allclose(q.act(s_all[0]), np.clip(ref.actor_mean(s_all[:1].astype(np.float64))[0], -1, 1), atol=2e-5)
     q.close()
 
 
@@ -255,12 +269,13 @@ def _planner(case, max_batch=1, max_windows=1, **cfg_over):
     return p, dims
 
 
-@pytest.mark.parametrize("case", ["h64", "h128"])
+@pytest.mark.parametrize("case", ["h64", "h128", "h256_1"])
 def test_publish_is_the_host_route(case):
     """A critic-guided fp32 plan step after m3pc_iql_publish_critic, and after m3pc_set_critic with the exported qf: every output bit
     for bit (pred_boot is min(q1, q2) itself).  hidden 64 with S + A = 14: the MFMA critic, so the packed operand streams are compared
     through their only reader; hidden 128 with S + A = 35, which critic_mfma_covers does not cover: the scalar critic kernel, the only
-    reader of the transposed copies."""
+    reader of the transposed copies; hidden 256 with S + A = 14: the MFMA critic again, with streams long enough (289308 elements
+    in all) that the grid-stride loop of iql_publish_kernel runs."""
     S, A, H, _ = R.CASES[case]
     p, dims = _planner(case)
     q = _trainer(case, p.handle)
@@ -287,6 +302,64 @@ def test_publish_is_the_host_route(case):
     assert np.isfinite(published["expect_return"]).all()
     q.close()
     p.handle.close()
+
+
+@pytest.mark.parametrize("k", [500, 1000, 1500])
+def test_adam_from_loaded_moments_at_a_late_step(k):
+    """The ADAM_M / ADAM_V parts loaded, set_step(k) with actor_t_max = 1000, one step: the moments move by the recurrences, every
+    parameter is the formula in float64 from the exported moments (2 ulp of the larger of |p| and |p'|, as in
+    test_b_adam_from_the_devices_own_moments) with bias corrections of step k + 1 and, for the actor, the cosine rate at k -- half the
+    rate at 500, EXACTLY 0 at 1000 (cos(pi) = -1 in double: the actor's parameters keep their bits, its moments move), and the rate on
+    the way back up at 1500."""
+    case = "h64"
+    q = _trainer(case)
+    hp = R.HP
+    assert q.max_steps == 1000 == hp["max_steps"]
+    rng = np.random.RandomState(100 + k)
+    loaded = {}
+    for part, (cp, cm, cv) in PART_CODES.items():
+        shapes = q.shapes(part)
+        m = {n: (rng.normal(size=sh) * 0.05).astype(np.float32) for n, sh in shapes.items()}
+        v = {n: (rng.uniform(size=sh) * 0.01).astype(np.float32) for n, sh in shapes.items()}
+        q.load_part(cm, m)
+        q.load_part(cv, v)
+        loaded[part] = (m, v)
+    q.total_it = k
+    before = _export(q)
+    zero1 = _device_run(case).zero1      # exp_avg = (1 - b1) g of the same weights and batch, from zero moments
+    for part, (m, v) in loaded.items():
+        for n in m:
+            assert _bits(before["m/%s/%s" % (part, n)], m[n]) and _bits(before["v/%s/%s" % (part, n)], v[n]), (part, n)
+    q.train(R.make_batches(case, 1)[0])
+    after = _export(q)
+    assert q.total_it == k + 1
+    t = k + 1
+    bc1, bc2 = 1.0 - R.BETA1 ** t, 1.0 - R.BETA2 ** t
+    alr = R.actor_lr(hp["actor_lr"], k, 1000)
+    assert (alr == 0.0) == (k == 1000) and (k != 500 or abs(alr - hp["actor_lr"] / 2) < 1e-18) and (k != 1500 or abs(alr - hp["actor_lr"] / 2) < 1e-18)
+    lr = dict(vf=hp["v_lr"], qf=hp["q_lr"], actor=alr)
+    for key in [x for x in before if x.startswith("p/") and not x.startswith("p/q_target")]:
+        part, name = key.split("/")[1:]
+        p, p1 = before[key].astype(np.float64), after[key]
+        m0, v0 = before["m/%s/%s" % (part, name)], before["v/%s/%s" % (part, name)]
+        m1, v1 = after["m/%s/%s" % (part, name)], after["v/%s/%s" % (part, name)]
+        assert not _bits(m0, m1) and not _bits(v0, v1), key
+        # the recurrences from the loaded moments: the gradient is the one of the first step from zero moments (the same weights and
+        # batch), g = exp_avg / (1 - b1) to one rounding.  Three fp32 roundings each, of operands no larger than `mag`, and g's own
+        m064, v064 = m0.astype(np.float64), v0.astype(np.float64)
+        g = zero1["m/%s/%s" % (part, name)].astype(np.float64) / OMB1
+        want_m, want_v = m064 + OMB1 * (g - m064), B2 * v064 + OMB2 * g * g
+        mag = np.abs(m064) + OMB1 * (np.abs(g) + np.abs(m064))
+        assert (np.abs(m1 - want_m) <= 4.0 * R.ulp(mag)).all(), (key, (np.abs(m1 - want_m) / R.ulp(mag)).max())
+        assert (np.abs(v1 - want_v) <= 4.0 * R.ulp(want_v)).all(), (key, (np.abs(v1 - want_v) / R.ulp(want_v)).max())
+        want = p - (lr[part] / bc1) * m1.astype(np.float64) / (np.sqrt(v1.astype(np.float64)) / math.sqrt(bc2) + R.EPS)
+        ulp = np.maximum(R.ulp(p), R.ulp(p1))
+        assert (np.abs(p1.astype(np.float64) - want) <= 2.0 * ulp).all(), (key, (np.abs(p1 - want) / ulp).max())
+        if part == "actor" and k == 1000:
+            assert _bits(p1, before[key]), key
+        elif name != "log_std":
+            assert not _bits(p1, before[key]), key
+    q.close()
 
 
 @pytest.mark.parametrize("threshold", [1000, 4])
