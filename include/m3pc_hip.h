@@ -53,7 +53,10 @@ extern "C" {
  * _append_transitions / _push_episodes / _sample_segments / _sample_transitions / _values_up_bound / _counts / _path_lengths and the
  * opaque m3pc_replay (the replay buffer); then m3pc_iql_create / _destroy / _load / _export / _set_step / _get_step / _train_step / _train /
  * _publish_critic / _evaluate, m3pc_iql_args and the opaque m3pc_iql (the IQL trainer); then m3pc_mtm_loss_terms, m3pc_mtm_loss and
- * m3pc_mtm_loss_replay (the masked-trajectory loss).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
+ * m3pc_mtm_loss_replay (the masked-trajectory loss); then m3pc_mtm_grad_create / _destroy / m3pc_mtm_grad / _replay / _export and
+ * the opaque struct m3pc_mtm_grad (its gradient); then m3pc_mtm_opt_create / _destroy / _decays / _step / _export / _load / _get_state /
+ * _set_state, m3pc_mtm_lr, m3pc_mtm_train_step, m3pc_mtm_train, m3pc_mtm_weights_export, m3pc_mtm_opt_args, m3pc_mtm_opt_state and
+ * the opaque struct m3pc_mtm_opt (its optimizers).  v7: M3PC_PREC_BF16X3, a third precision of the candidate pass, accepted wherever a precision is taken
  * (m3pc_forward, m3pc_candidate_pass, m3pc_plan_step[_batch], m3pc_score_actions, m3pc_goal_step_batch, m3pc_profile_read); no new
  * entry point and no structure change.  v6 (round 6): no new entry point and no structure change; m3pc_rescore_merge now writes all 8 floats of its
  * host_stats block (slots 5..7 as zeros: a reader of the 8-float layout never sees an earlier race merge's values), so a caller
@@ -1080,7 +1083,7 @@ int m3pc_mtm_loss_replay(m3pc_handle* h, m3pc_replay* rb, int batch, int mode, c
 /* THE GRADIENT OF THE MASKED-TRAJECTORY LOSS: the forward above and loss.backward() of Learner.mtm_update (finetune_omtm/learner.py:506-538)
  * through the whole model -- loss terms, heads, decoder blocks, decoder embedding and mask tokens, encoder blocks, encoder embedding --
  * in one call: a raw batch in, one gradient tensor per parameter out, under the reference's state_dict names.  The optimizers stay the
- * caller's.  The gradient is that of `total`, record[14] as defined above for the given flags and loss_keys, with respect to every tensor
+ * caller's, or the library's (m3pc_mtm_opt_* below).  The gradient is that of `total`, record[14] as defined above for the given flags and loss_keys, with respect to every tensor
  * of the model's state_dict except the buffer pos_embed.  Held constant: the tokenised targets (the l2-normalised ones too), the clipped
  * action and its z, entropy_reg, the masks.  eps is the caller's; u = mu + std eps is differentiated through mu and std (rsample), and std
  * = exp(-5 + 3.5 (tanh(.) + 1)) through the log_std Linear.
@@ -1121,6 +1124,64 @@ int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, in
                          const float* eps, float entropy_reg, int flags, int loss_keys, float* record, int* out_traj, int* out_start,
                          void* stream);
 int m3pc_mtm_grad_export(struct m3pc_mtm_grad* g, const m3pc_named_tensor* tensors, int n, void* stream);
+
+/* THE OPTIMIZERS OF THE MASKED-TRAJECTORY MODEL: what Learner.mtm_update (finetune_omtm/learner.py:506-538) does behind loss.backward(),
+ * on the device and on the HANDLE'S OWN WEIGHTS -- AdamW over every parameter in the two groups of omtm.configure_optimizers
+ * (mtm_model.py:779-841), the LambdaLR schedule, and the Adam step of the float64 log_temperature on exp(log_t) (entropy - target_entropy)
+ * with the gradient call's entropy.  A step moves the fp32 weights of the handle the gradient object was created on and re-derives
+ * every form the passes read (what m3pc_load_weights derives) behind it: the next plan step runs on the trained weights, and nothing
+ * crosses the host.  Arithmetic order, launches and determinism: m3pc_amd/csrc/mtm_opt.h.
+ *   inactive     the output-head tensors of a key outside loss_keys have no gradient in the reference and torch's AdamW skips them: their
+ *                weights, moments, bf16 copies and step counts keep their bits.  Step counts are per tensor.  An all-zero gradient IS stepped.
+ *   schedule     the step made at scheduler count s uses lr = learning_rate * lambda(s) (m3pc_mtm_lr: what scheduler.get_last_lr()[0]
+ *                shows before the step); warmup_steps == 0: 0.5 (1 + cos(s / num_train_steps * pi)); warmup_steps > 0: s / warmup_steps
+ *                below it, then 0.5 (1 + cos((s - warmup_steps) / (num_train_steps - warmup_steps) * pi)).
+ *   _step        applies the gradients and the entropy of g's last gradient call under that call's loss_keys, once.
+ *   _train_step  m3pc_mtm_grad with entropy_reg read from the device temperature, then _step.  record: optional device out, the
+ *                M3PC_MTM_LOSS_FLOATS floats; train_record: optional DEVICE out, 3 doubles {lr used, temperature after, log_temperature after}.
+ *   _train       n_steps such steps on the segments rb draws at (seed, step0 + i) as m3pc_mtm_grad_replay draws them, eps library-drawn;
+ *                masks: 4 n_steps host rows (step i: masks[4 i + key]); records (n_steps, 15) floats and train_records (n_steps, 3) doubles,
+ *                optional device out.  The bf16 copies and the derived forms are written behind the last step only; weights, moments
+ *                and records are bit-identical to n_steps single calls.
+ *   _export/_load  which = 1: exp_avg, 2: exp_avg_sq, in the torch layout of the parameter (host or device by on_device); steps: optional
+ *                HOST array, one count per listed tensor (a call that passes it waits for the stream).  m3pc_mtm_weights_export: the handle's fp32 weights.
+ *   _get/_set_state  synchronous (they wait for the device).  temperature: out only, the float the next gradient call reads.
+ * _create makes no HIP call; the first enqueueing call allocates two moment arenas of the parameters' size (zeroed) and the tables.  The
+ * gradient object must outlive the optimizer.  The stepping entries wait for nothing and copy nothing from host memory per step; they
+ * order themselves behind deferred candidate parts as m3pc_load_weights does, and invalidate what it invalidates.
+ * Refused with M3PC_EINVAL before any HIP call, the argument named in m3pc_last_error: a null argument; hyper-parameters out of range
+ * (negative or non-finite rates, betas outside [0, 1), eps <= 0, num_train_steps < 1, warmup_steps outside [0, num_train_steps)); what
+ * m3pc_mtm_grad / m3pc_mtm_grad_replay refuse; n_steps < 1; a name that is not a parameter, a numel that does not fit, `which` not 1 or 2.
+ * Refused with M3PC_ESTATE: _step without a gradient call or twice on one; a stepping entry while a pipelined certified step is between
+ * _begin and _end on the handle; weights or tokenizers not loaded. */
+typedef struct m3pc_mtm_opt_args {
+    double learning_rate, weight_decay, beta1, beta2, eps; /* AdamW: the reference uses betas (0.9, 0.999), eps 1e-8 */
+    long long num_train_steps, warmup_steps;
+    double temp_learning_rate, temp_beta1, temp_beta2, temp_eps; /* the reference: 1e-4, 0.9, 0.999, 1e-8 */
+    double target_entropy;
+    double init_log_temperature;
+} m3pc_mtm_opt_args;
+typedef struct m3pc_mtm_opt_state {
+    long long sched_step, temp_step;
+    double log_temperature, temp_exp_avg, temp_exp_avg_sq;
+    double temperature;
+} m3pc_mtm_opt_state;
+struct m3pc_mtm_opt;
+int m3pc_mtm_opt_create(struct m3pc_mtm_grad* g, const m3pc_mtm_opt_args* args, struct m3pc_mtm_opt** out);
+int m3pc_mtm_opt_destroy(struct m3pc_mtm_opt* opt);
+int m3pc_mtm_lr(const m3pc_mtm_opt_args* args, long long sched_step, double* lr);
+int m3pc_mtm_opt_decays(struct m3pc_mtm_opt* opt, const char* name, int* decays);
+int m3pc_mtm_opt_step(struct m3pc_mtm_opt* opt, void* stream);
+int m3pc_mtm_train_step(struct m3pc_mtm_opt* opt, int batch, const float* states, const float* actions, const float* rewards, const void* returns,
+                        int returns_f64, const unsigned char* const masks[4], const float* eps, int flags, int loss_keys, float* record,
+                        double* train_record, void* stream);
+int m3pc_mtm_train(struct m3pc_mtm_opt* opt, m3pc_replay* rb, int n_steps, int batch, int mode, unsigned long long seed, unsigned long long step0,
+                   const unsigned char* const* masks, int flags, int loss_keys, float* records, double* train_records, void* stream);
+int m3pc_mtm_opt_export(struct m3pc_mtm_opt* opt, int which, const m3pc_named_tensor* tensors, int n, long long* steps, void* stream);
+int m3pc_mtm_opt_load(struct m3pc_mtm_opt* opt, int which, const m3pc_named_tensor* tensors, int n, const long long* steps, void* stream);
+int m3pc_mtm_weights_export(m3pc_handle* h, const m3pc_named_tensor* tensors, int n, void* stream);
+int m3pc_mtm_opt_get_state(struct m3pc_mtm_opt* opt, m3pc_mtm_opt_state* out);
+int m3pc_mtm_opt_set_state(struct m3pc_mtm_opt* opt, const m3pc_mtm_opt_state* in);
 
 /* kernel-level timing of the last plan_step for bench.py / profiling: when enabled the library
  * brackets the MFMA launches with hipEvents on the stream they run on.  enable = 2: in addition the two candidate

@@ -877,6 +877,35 @@ typedef struct m3pc_debug_iql_publish_args {
     int* picked;
 } m3pc_debug_iql_publish_args;
 int m3pc_debug_iql_publish(const m3pc_debug_iql_publish_args* a);
+/* ---- csrc/mtm_opt.hip: mo_adamw_kernel (the AdamW launch of m3pc_mtm_opt_step) alone, on caller-given device arrays and a caller-given
+ * segment table, through the launcher the trainer uses (csrc/mtm_opt.h: arithmetic order, block table, step-count arrays).  Segment i:
+ * weight p[i] (device, numel[i] floats), gradient at grad + g_off[i], moments at exp_avg / exp_avg_sq + s_off[i], b[i] (optional; device,
+ * 2 numel[i] bf16: hi | lo) written when write_bf16.  p, b, g_off, s_off, numel, decay, active are HOST arrays of n; steps_in / steps_out
+ * DEVICE arrays of n int64 (distinct).  An inactive segment (active[i] == 0) keeps every bit and its step count.  n_blocks (optional out):
+ * the workgroups launched.  The call waits for the launch.  Refused (M3PC_EINVAL, before any HIP call): a null pointer (b, n_blocks
+ * and stream excepted), n outside [1, 4096], numel outside [1, 2^30], an offset + numel beyond grad_floats / state_floats, steps_in == steps_out. */
+typedef struct m3pc_debug_mtm_adamw_args {
+    int n;
+    float* const* p;
+    void* const* b;
+    const long long* g_off;
+    const long long* s_off;
+    const long long* numel;
+    const int* decay;
+    const int* active;
+    const float* grad;
+    long long grad_floats;
+    float* exp_avg;
+    float* exp_avg_sq;
+    long long state_floats;
+    const long long* steps_in;
+    long long* steps_out;
+    int write_bf16;
+    double lr_t, weight_decay, beta1, beta2, eps;
+    void* stream;
+    int* n_blocks;
+} m3pc_debug_mtm_adamw_args;
+int m3pc_debug_mtm_adamw(const m3pc_debug_mtm_adamw_args* a);
 /* in-kernel phase stamps of workgroup 37 of every fused-tail launch as the step runs: cap > 0 starts a ring of cap entries
  * (64 int64 each), cap == 0 copies it to `out` (host), reports the number of launches logged and stops */
 int m3pc_debug_stamp_log(m3pc_handle* h, int cap, long long* out, int* n_logged);

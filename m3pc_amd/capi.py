@@ -59,6 +59,9 @@ EXPORTS = (
     "m3pc_iql_train_step", "m3pc_iql_train", "m3pc_iql_publish_critic", "m3pc_iql_evaluate",
     "m3pc_mtm_loss_terms", "m3pc_mtm_loss", "m3pc_mtm_loss_replay",
     "m3pc_mtm_grad_create", "m3pc_mtm_grad_destroy", "m3pc_mtm_grad", "m3pc_mtm_grad_replay", "m3pc_mtm_grad_export",
+    "m3pc_mtm_opt_create", "m3pc_mtm_opt_destroy", "m3pc_mtm_lr", "m3pc_mtm_opt_decays", "m3pc_mtm_opt_step", "m3pc_mtm_train_step",
+    "m3pc_mtm_train", "m3pc_mtm_opt_export", "m3pc_mtm_opt_load", "m3pc_mtm_weights_export", "m3pc_mtm_opt_get_state",
+    "m3pc_mtm_opt_set_state",
 )
 
 
@@ -70,6 +73,26 @@ class Dims(C.Structure):
 
 class NamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_longlong), ("on_device", C.c_int)]
+
+
+class MtmOptArgs(C.Structure):
+    """m3pc_mtm_opt_args; the defaults are the reference's (learner.py:42-58; torch's AdamW / Adam eps)."""
+    _fields_ = [("learning_rate", C.c_double), ("weight_decay", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("num_train_steps", C.c_longlong), ("warmup_steps", C.c_longlong), ("temp_learning_rate", C.c_double),
+                ("temp_beta1", C.c_double), ("temp_beta2", C.c_double), ("temp_eps", C.c_double), ("target_entropy", C.c_double),
+                ("init_log_temperature", C.c_double)]
+
+    @classmethod
+    def make(cls, learning_rate, weight_decay, num_train_steps, target_entropy, init_log_temperature, beta1=0.9, beta2=0.999, eps=1e-8,
+             warmup_steps=0, temp_learning_rate=1e-4, temp_beta1=0.9, temp_beta2=0.999, temp_eps=1e-8):
+        return cls(float(learning_rate), float(weight_decay), float(beta1), float(beta2), float(eps), int(num_train_steps), int(warmup_steps),
+                   float(temp_learning_rate), float(temp_beta1), float(temp_beta2), float(temp_eps), float(target_entropy),
+                   float(init_log_temperature))
+
+
+class MtmOptState(C.Structure):
+    _fields_ = [("sched_step", C.c_longlong), ("temp_step", C.c_longlong), ("log_temperature", C.c_double), ("temp_exp_avg", C.c_double),
+                ("temp_exp_avg_sq", C.c_double), ("temperature", C.c_double)]
 
 
 class PlanArgs(C.Structure):
@@ -238,6 +261,18 @@ def load_library(path: Optional[str] = None):
         "m3pc_mtm_grad": [vp, i, vp, vp, vp, vp, i, C.POINTER(vp), vp, f, i, i, vp, vp],
         "m3pc_mtm_grad_replay": [vp, vp, i, i, vp, vp, i, C.c_ulonglong, C.c_ulonglong, C.POINTER(vp), vp, f, i, i, vp, vp, vp, vp],
         "m3pc_mtm_grad_export": [vp, C.POINTER(NamedTensor), i, vp],
+        "m3pc_mtm_opt_create": [vp, C.POINTER(MtmOptArgs), C.POINTER(vp)],
+        "m3pc_mtm_opt_destroy": [vp],
+        "m3pc_mtm_lr": [C.POINTER(MtmOptArgs), ll, C.POINTER(d)],
+        "m3pc_mtm_opt_decays": [vp, C.c_char_p, C.POINTER(i)],
+        "m3pc_mtm_opt_step": [vp, vp],
+        "m3pc_mtm_train_step": [vp, i, vp, vp, vp, vp, i, C.POINTER(vp), vp, i, i, vp, vp, vp],
+        "m3pc_mtm_train": [vp, vp, i, i, i, C.c_ulonglong, C.c_ulonglong, C.POINTER(vp), i, i, vp, vp, vp],
+        "m3pc_mtm_opt_export": [vp, i, C.POINTER(NamedTensor), i, C.POINTER(ll), vp],
+        "m3pc_mtm_opt_load": [vp, i, C.POINTER(NamedTensor), i, C.POINTER(ll), vp],
+        "m3pc_mtm_weights_export": [vp, C.POINTER(NamedTensor), i, vp],
+        "m3pc_mtm_opt_get_state": [vp, C.POINTER(MtmOptState)],
+        "m3pc_mtm_opt_set_state": [vp, C.POINTER(MtmOptState)],
         "m3pc_profile_enable": [vp, i],
         "m3pc_profile_read": [vp, i, C.POINTER(ll), C.POINTER(d), C.POINTER(d), i],
     }

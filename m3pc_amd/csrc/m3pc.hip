@@ -40,6 +40,96 @@ int find_tensor(const m3pc_named_tensor* list, int n, const std::string& name) {
 // =====================================================================================================
 static int fill_rtok(m3pc_handle* h, const double* rtg, int n_windows, hipStream_t st);
 
+namespace m3pc {
+// The derive half of m3pc_load_weights: every form the passes read beside the fp32 tensors, re-made on `st` for the tensors named in
+// `dirty` (map order) -- hi / lo bf16 copies (unless skip_bf16_split: the writer of the fp32 values wrote them too), the fragment
+// streams of the fused layer tails, the K|V streams, WT / Eenc / Edec, the mask tokens; the cached decoder tables and the slots'
+// policy state are invalidated.  Fills h->load_stats.  No stream synchronise.
+int derive_weights(m3pc_handle* h, const std::vector<std::string>& dirty, bool skip_bf16_split, hipStream_t st) {
+    if (!skip_bf16_split)
+        for (const std::string& nme : dirty) {
+            Tensor& t = h->w.at(nme);
+            if (t.gemm) launch_f32_split_bf16(t.f, t.b, t.b + t.numel, t.numel, st);
+        }
+    auto is_dirty = [&](const std::string& name) {
+        for (const std::string& d : dirty)
+            if (d == name) return true;
+        return false;
+    };
+    long long* ls = h->load_stats;
+    ls[0] = (long long)dirty.size();
+    ls[1] = ls[2] = ls[3] = 0;
+    if (block_fused_supported(h->d, h->ff)) {  // fragment streams of the fused layer tails (block_fused.hip)
+        // nxt: the layer whose Q|K|V projection rides behind this layer's tail (the next encoder layer), or ""
+        auto pack = [&](const std::string& pfx, const std::string& nxt) -> int {
+            const bool own = is_dirty(pfx + ".self_attn.out_proj.weight") || is_dirty(pfx + ".linear1.weight") || is_dirty(pfx + ".linear2.weight");
+            const bool qkv = !nxt.empty() && is_dirty(nxt + ".self_attn.in_proj_weight");
+            if (!own && !qkv) return 0;
+            bf16_t*& ws = h->wstream[pfx];
+            if (!ws) CHK(dmalloc((char**)&ws, block_stream_bytes()));
+            if (own)
+                launch_pack_block_stream(W(h, pfx + ".self_attn.out_proj.weight").b, W(h, pfx + ".linear1.weight").b,
+                                         W(h, pfx + ".linear2.weight").b, ws, st);
+            if (qkv) launch_pack_block_qkv(W(h, nxt + ".self_attn.in_proj_weight").b, ws, st);
+            ++ls[1];
+            return 0;
+        };
+        for (int i = 0; i < h->dm.n_enc_layer; ++i)
+            CHK(pack("encoder.layers." + std::to_string(i), i + 1 < h->dm.n_enc_layer ? "encoder.layers." + std::to_string(i + 1) : ""));
+        for (int i = 0; i < h->dm.n_dec_layer; ++i) CHK(pack("decoder.layers." + std::to_string(i), ""));
+        // behind the decoder layer's own fragments: the first Linear of the two scalar output heads rtg_guiding scores
+        // (rewards, returns: learner.py:294-305), consumed by the fused tail's head phases
+        if (h->dm.n_dec_layer >= 1 && h->wstream.count("decoder.layers.0")) {
+            const std::string w0 = std::string("output_head_dict.") + KEYN[M3PC_REWARDS] + ".1.weight";
+            const std::string w1 = std::string("output_head_dict.") + KEYN[M3PC_RETURNS] + ".1.weight";
+            if (is_dirty(w0) || is_dirty(w1)) {
+                launch_pack_block_heads(W(h, w0).b, W(h, w1).b, h->wstream["decoder.layers.0"], st);
+                ++ls[1];
+            }
+        }
+        if (h->dm.n_dec_layer >= 1)
+            for (int k = 0; k < 4; ++k) {
+                const std::string we = std::string("decoder_embed_dict.") + KEYN[k] + ".weight";
+                if (!(is_dirty(we) || is_dirty("decoder.layers.0.self_attn.in_proj_weight"))) continue;
+                if (!h->kvstream[k]) CHK(dmalloc((char**)&h->kvstream[k], kv_stream_bytes()));
+                launch_pack_kv_stream(W(h, we).b, W(h, "decoder.layers.0.self_attn.in_proj_weight").b + (size_t)h->d * h->d,
+                                      h->kvstream[k], st);
+                ++ls[2];
+            }
+    }
+    // small derived tables, on the device: transposed encoder-embed weights, E_enc / E_dec = (bias + per-dim) + pos, mask tokens
+    const int d = h->d, T = h->T;
+    const bool pos_dirty = is_dirty("pos_embed");
+    for (int k = 0; k < 4; ++k) {
+        const std::string kn = KEYN[k];
+        if (is_dirty("encoder_embed_dict." + kn + ".weight"))
+            launch_transpose_f32(W(h, "encoder_embed_dict." + kn + ".weight").f, h->WT[k], d, h->feat[k], st);
+        for (int pass = 0; pass < 2; ++pass) {
+            const std::string side = pass == 0 ? "encoder" : "decoder";
+            if (pos_dirty || is_dirty(side + "_embed_dict." + kn + ".bias") || is_dirty(side + "_per_dim_encoding." + kn))
+                launch_embed_table(W(h, side + "_embed_dict." + kn + ".bias").f, W(h, side + "_per_dim_encoding." + kn).f,
+                                   W(h, "pos_embed").f, pass == 0 ? h->Eenc[k] : h->Edec[k], T, d, st);
+        }
+        if (is_dirty("mask_token_dict." + kn))
+            HIPCHK(hipMemcpyAsync(h->mask_tokens + (size_t)k * d, W(h, "mask_token_dict." + kn).f, d * sizeof(float),
+                                  hipMemcpyDeviceToDevice, st));
+    }
+    // the candidate-independent decoder tables of every cached plan hang on the decoder side of the model
+    bool dec_dirty = pos_dirty;
+    for (const std::string& nme : dirty)
+        if (nme.rfind("decoder", 0) == 0 || nme.rfind("mask_token_dict", 0) == 0) dec_dirty = true;
+    if (dec_dirty) {
+        invalidate_tables(h);
+        ls[3] = 1;
+    }
+    for (int sl = 0; sl < M3PC_SLOTS; ++sl) {
+        h->slot[sl].policy_valid = false;
+        h->slot[sl].n_windows = 0;
+    }
+    return 0;
+}
+}  // namespace m3pc
+
 // the library is built with -fvisibility=hidden: the C ABI below (include/m3pc_hip.h, and in the lab build m3pc_hip_debug.h) is
 // everything it exports
 #pragma GCC visibility push(default)
@@ -323,89 +413,15 @@ int m3pc_load_weights(m3pc_handle* h, const m3pc_named_tensor* tensors, int n, v
             return fail(M3PC_EINVAL, "'%s' has %lld elements, expected %lld", kv.first.c_str(), tensors[i].numel, kv.second.numel);
         HIPCHK(hipMemcpyAsync(kv.second.f, tensors[i].data, (size_t)kv.second.numel * sizeof(float),
                               tensors[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        if (kv.second.gemm) launch_f32_split_bf16(kv.second.f, kv.second.b, kv.second.b + kv.second.numel, kv.second.numel, st);
         kv.second.loaded = true;
         dirty.push_back(kv.first);
     }
-    auto is_dirty = [&](const std::string& name) {
-        for (const std::string& d : dirty)
-            if (d == name) return true;
-        return false;
-    };
-    long long* ls = h->load_stats;
-    ls[0] = (long long)dirty.size();
-    ls[1] = ls[2] = ls[3] = 0;
-    if (block_fused_supported(h->d, h->ff)) {  // fragment streams of the fused layer tails (block_fused.hip)
-        // nxt: the layer whose Q|K|V projection rides behind this layer's tail (the next encoder layer), or ""
-        auto pack = [&](const std::string& pfx, const std::string& nxt) -> int {
-            const bool own = is_dirty(pfx + ".self_attn.out_proj.weight") || is_dirty(pfx + ".linear1.weight") || is_dirty(pfx + ".linear2.weight");
-            const bool qkv = !nxt.empty() && is_dirty(nxt + ".self_attn.in_proj_weight");
-            if (!own && !qkv) return 0;
-            bf16_t*& ws = h->wstream[pfx];
-            if (!ws) CHK(dmalloc((char**)&ws, block_stream_bytes()));
-            if (own)
-                launch_pack_block_stream(W(h, pfx + ".self_attn.out_proj.weight").b, W(h, pfx + ".linear1.weight").b,
-                                         W(h, pfx + ".linear2.weight").b, ws, st);
-            if (qkv) launch_pack_block_qkv(W(h, nxt + ".self_attn.in_proj_weight").b, ws, st);
-            ++ls[1];
-            return 0;
-        };
-        for (int i = 0; i < h->dm.n_enc_layer; ++i)
-            CHK(pack("encoder.layers." + std::to_string(i), i + 1 < h->dm.n_enc_layer ? "encoder.layers." + std::to_string(i + 1) : ""));
-        for (int i = 0; i < h->dm.n_dec_layer; ++i) CHK(pack("decoder.layers." + std::to_string(i), ""));
-        // behind the decoder layer's own fragments: the first Linear of the two scalar output heads rtg_guiding scores
-        // (rewards, returns: learner.py:294-305), consumed by the fused tail's head phases
-        if (h->dm.n_dec_layer >= 1 && h->wstream.count("decoder.layers.0")) {
-            const std::string w0 = std::string("output_head_dict.") + KEYN[M3PC_REWARDS] + ".1.weight";
-            const std::string w1 = std::string("output_head_dict.") + KEYN[M3PC_RETURNS] + ".1.weight";
-            if (is_dirty(w0) || is_dirty(w1)) {
-                launch_pack_block_heads(W(h, w0).b, W(h, w1).b, h->wstream["decoder.layers.0"], st);
-                ++ls[1];
-            }
-        }
-        if (h->dm.n_dec_layer >= 1)
-            for (int k = 0; k < 4; ++k) {
-                const std::string we = std::string("decoder_embed_dict.") + KEYN[k] + ".weight";
-                if (!(is_dirty(we) || is_dirty("decoder.layers.0.self_attn.in_proj_weight"))) continue;
-                if (!h->kvstream[k]) CHK(dmalloc((char**)&h->kvstream[k], kv_stream_bytes()));
-                launch_pack_kv_stream(W(h, we).b, W(h, "decoder.layers.0.self_attn.in_proj_weight").b + (size_t)h->d * h->d,
-                                      h->kvstream[k], st);
-                ++ls[2];
-            }
-    }
-    // small derived tables, on the device: transposed encoder-embed weights, E_enc / E_dec = (bias + per-dim) + pos, mask tokens
-    const int d = h->d, T = h->T;
-    const bool pos_dirty = is_dirty("pos_embed");
-    for (int k = 0; k < 4; ++k) {
-        const std::string kn = KEYN[k];
-        if (is_dirty("encoder_embed_dict." + kn + ".weight"))
-            launch_transpose_f32(W(h, "encoder_embed_dict." + kn + ".weight").f, h->WT[k], d, h->feat[k], st);
-        for (int pass = 0; pass < 2; ++pass) {
-            const std::string side = pass == 0 ? "encoder" : "decoder";
-            if (pos_dirty || is_dirty(side + "_embed_dict." + kn + ".bias") || is_dirty(side + "_per_dim_encoding." + kn))
-                launch_embed_table(W(h, side + "_embed_dict." + kn + ".bias").f, W(h, side + "_per_dim_encoding." + kn).f,
-                                   W(h, "pos_embed").f, pass == 0 ? h->Eenc[k] : h->Edec[k], T, d, st);
-        }
-        if (is_dirty("mask_token_dict." + kn))
-            HIPCHK(hipMemcpyAsync(h->mask_tokens + (size_t)k * d, W(h, "mask_token_dict." + kn).f, d * sizeof(float),
-                                  hipMemcpyDeviceToDevice, st));
-    }
-    // the candidate-independent decoder tables of every cached plan hang on the decoder side of the model
-    bool dec_dirty = pos_dirty;
-    for (const std::string& nme : dirty)
-        if (nme.rfind("decoder", 0) == 0 || nme.rfind("mask_token_dict", 0) == 0) dec_dirty = true;
-    if (dec_dirty) {
-        invalidate_tables(h);
-        ls[3] = 1;
-    }
-    for (int sl = 0; sl < M3PC_SLOTS; ++sl) {
-        h->slot[sl].policy_valid = false;
-        h->slot[sl].n_windows = 0;
-    }
+    CHK(derive_weights(h, dirty, false, st));
     HIPCHK(hipStreamSynchronize(st));  // the caller's tensors may go away when the call returns
     h->weights_loaded = true;
     return check_launch("load_weights");
 }
+
 
 int m3pc_load_stats(m3pc_handle* h, long long* out4) {
     if (!h || !out4) return fail(M3PC_EINVAL, "null argument");

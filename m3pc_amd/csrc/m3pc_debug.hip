@@ -3,6 +3,7 @@
 #include "m3pc_internal.h"
 #include "mtm_grad.h"
 #include "iql.h"
+#include "mtm_opt.h"
 
 #include <vector>
 
@@ -1857,6 +1858,77 @@ int m3pc_debug_clock_big(long long* out4) {
     HIPCHK(hipDeviceSynchronize());
     read_big_probe(out4);
     return 0;
+}
+
+
+// ---- csrc/mtm_opt.hip: mo_adamw_kernel alone on caller arrays and a caller segment table, through the launcher the trainer uses
+// (tests/test_mtm_opt_kernel_edges_gpu.py).  The tables are uploaded here and freed when the launch has finished: the call waits.
+int m3pc_debug_mtm_adamw(const m3pc_debug_mtm_adamw_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mtm_adamw: null arguments");
+    if (a->n < 1 || a->n > 4096) return fail(M3PC_EINVAL, "debug_mtm_adamw: n %d outside [1, 4096]", a->n);
+    if (!a->p || !a->g_off || !a->s_off || !a->numel || !a->decay || !a->active || !a->grad || !a->exp_avg || !a->exp_avg_sq || !a->steps_in ||
+        !a->steps_out)
+        return fail(M3PC_EINVAL, "debug_mtm_adamw: null pointer");
+    if (a->steps_in == a->steps_out) return fail(M3PC_EINVAL, "debug_mtm_adamw: steps_in and steps_out are one array");
+    std::vector<MoSeg> seg((size_t)a->n);
+    for (int i = 0; i < a->n; ++i) {
+        if (!a->p[i]) return fail(M3PC_EINVAL, "debug_mtm_adamw: p[%d] is null", i);
+        if (a->numel[i] < 1 || a->numel[i] > (1ll << 30)) return fail(M3PC_EINVAL, "debug_mtm_adamw: numel[%d] = %lld outside [1, 2^30]", i, a->numel[i]);
+        if (a->g_off[i] < 0 || a->g_off[i] + a->numel[i] > a->grad_floats)
+            return fail(M3PC_EINVAL, "debug_mtm_adamw: g_off[%d] + numel leaves the %lld floats of grad", i, a->grad_floats);
+        if (a->s_off[i] < 0 || a->s_off[i] + a->numel[i] > a->state_floats)
+            return fail(M3PC_EINVAL, "debug_mtm_adamw: s_off[%d] + numel leaves the %lld floats of the moments", i, a->state_floats);
+        seg[i].p = a->p[i];
+        seg[i].b = a->b ? (bf16_t*)a->b[i] : nullptr;
+        seg[i].g_off = a->g_off[i];
+        seg[i].s_off = a->s_off[i];
+        seg[i].numel = a->numel[i];
+        seg[i].decay = a->decay[i] ? 1 : 0;
+        seg[i].head_key = a->active[i] ? -1 : 0;  // (with loss_keys 0 below: key 0 is outside)
+    }
+    std::vector<int2> blk;
+    mo_block_table(a->numel, a->n, blk);
+    MoSeg* d_seg = nullptr;
+    int2* d_blk = nullptr;
+    hipStream_t st = (hipStream_t)a->stream;
+    CHK(dmalloc((char**)&d_seg, seg.size() * sizeof(MoSeg)));
+    if (int rc = dmalloc((char**)&d_blk, blk.size() * sizeof(int2))) {
+        (void)hipFree(d_seg);
+        return rc;
+    }
+    hipError_t e = hipMemcpy(d_seg, seg.data(), seg.size() * sizeof(MoSeg), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_blk, blk.data(), blk.size() * sizeof(int2), hipMemcpyHostToDevice);
+    int rc = 0;
+    if (e == hipSuccess) {
+        MoAdamP p;
+        memset(&p, 0, sizeof(p));
+        p.seg = d_seg;
+        p.blk = d_blk;
+        p.n_blocks = (int)blk.size();
+        p.grad = a->grad;
+        p.exp_avg = a->exp_avg;
+        p.exp_avg_sq = a->exp_avg_sq;
+        p.steps_in = a->steps_in;
+        p.steps_out = a->steps_out;
+        p.loss_keys = 0;
+        p.write_bf16 = a->write_bf16;
+        p.lr_t = a->lr_t;
+        p.wd = a->weight_decay;
+        p.beta1 = a->beta1;
+        p.beta2 = a->beta2;
+        p.eps = a->eps;
+        p.omb1 = (float)(1.0 - a->beta1);
+        p.b2 = (float)a->beta2;
+        p.omb2 = (float)(1.0 - a->beta2);
+        mo_launch_adamw(p, st);
+        rc = check_launch("debug_mtm_adamw");
+        e = hipStreamSynchronize(st);
+    }
+    (void)hipFree(d_seg);
+    (void)hipFree(d_blk);
+    if (e != hipSuccess) return fail(M3PC_EHIP, "debug_mtm_adamw: %s", hipGetErrorString(e));
+    if (a->n_blocks) *a->n_blocks = (int)blk.size();
+    return rc;
 }
 
 

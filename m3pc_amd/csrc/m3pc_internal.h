@@ -714,6 +714,8 @@ void invalidate_tables(m3pc_handle* h);
 int build_query_list(m3pc_handle* h, Plan* pl, int qi, int hh, const std::vector<int>& toks, int n_groups, int key0, int key1);
 int build_query(m3pc_handle* h, Plan* pl, int qi, int hh);
 int build_tables(m3pc_handle* h, Plan* pl, int qi, int dt, hipStream_t st);
+// m3pc.hip: the derive half of m3pc_load_weights (also behind the last AdamW launch of the trainer, mtm_opt.hip)
+int derive_weights(m3pc_handle* h, const std::vector<std::string>& dirty, bool skip_bf16_split, hipStream_t st);
 // m3pc_certified.hip
 int cert_check_args(const m3pc_plan_args* a, const char* who);  // one rank, every candidate, a valid precision and slot
 bool cert_any_begun(const m3pc_handle* h);                      // a pipelined certified step is between _begin and _end

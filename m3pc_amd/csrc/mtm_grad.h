@@ -127,6 +127,7 @@ struct LossBwdG {
     unsigned long long mask[4];
     int batch, T, S, A, flags, loss_keys;
     float entropy_reg, inv_cnt;  // 1 / (batch * hidden action timesteps * A)
+    const float* entropy_reg_p;  // optional device scalar read in place of entropy_reg (the trainer's temperature, mtm_opt.h)
 };
 
 // ------------------------------------------------------------------------------------------------ launchers
@@ -151,4 +152,50 @@ void mg_launch_scatter(const EmbG& p, hipStream_t st);
 void mg_launch_tokv(const EmbG& p, int k, float* out, hipStream_t st);
 void mg_launch_std(const float* ls, float* sd, long long n, hipStream_t st);
 void mg_launch_loss_bwd(const LossBwdG& p, hipStream_t st);
+}  // namespace m3pc
+
+// ------------------------------------------------------------------------------------------------ the object
+// (mtm_grad.hip fills it; mtm_opt.hip reads the parameter list, the gradient arena and the record of the last call)
+struct m3pc_mtm_grad {
+    m3pc_handle* h = nullptr;
+    int max_batch = 0;
+    bool ready = false, have_grad = false;
+    bool consumed = false;       // the optimizer of mtm_opt.h has applied the gradients of the last call
+    int last_loss_keys = 0;      // loss_keys of the last gradient call
+    struct Par {
+        std::string name;
+        long long numel;
+        size_t off;
+    };
+    std::vector<Par> par;
+    std::map<std::string, int> idx;
+    size_t grad_floats = 0;
+    float* arena = nullptr;  // every fp32 buffer below
+    double* arena64 = nullptr;
+    float* grad = nullptr;
+    struct Lay {
+        float *Xin, *Hn1, *QKV, *P, *O, *X1, *Hn2, *Fpre, *Fact, *st1, *st2;
+    };
+    std::vector<Lay> lay;  // encoder layers, then decoder layers
+    float *XencOut, *EncN, *st_enc, *Zin, *XdecOut, *DecN, *st_dec;
+    float *tok[4], *raw[3], *eps;
+    float *Hh[3], *st_h[3], *Hpre[3], *Hact[3], *pred[3], *mu, *ls, *sd;
+    float *dX, *dH, *dQKV, *dF, *dO, *dpred[3], *dmu, *dls, *dh1, *dh2, *rec;
+    double *raw_returns, *part, *colpart;
+};
+
+namespace m3pc {
+// m3pc_mtm_grad / m3pc_mtm_grad_replay behind their null checks, under the caller's name `who`: the refusals, the allocation and the
+// launches.  entropy_reg_p: optional device scalar read in place of entropy_reg.  The record lands in g->rec, and in `record` too when given.
+// the refusals of those calls that need no HIP call, alone (the trainer makes them before it allocates)
+int mg_precheck(const struct m3pc_mtm_grad* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who);
+int mg_precheck_replay(const struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const unsigned char* const masks[4], int flags, int loss_keys,
+                       const char* who);
+int mg_call(struct m3pc_mtm_grad* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
+            const unsigned char* const masks[4], const float* eps, float entropy_reg, const float* entropy_reg_p, int flags, int loss_keys,
+            float* record, hipStream_t st, const char* who);
+int mg_call_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
+                   unsigned long long seed, unsigned long long step, const unsigned char* const masks[4], const float* eps, float entropy_reg,
+                   const float* entropy_reg_p, int flags, int loss_keys, float* record, int* out_traj, int* out_start, hipStream_t st,
+                   const char* who);
 }  // namespace m3pc

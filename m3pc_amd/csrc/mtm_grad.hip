@@ -425,9 +425,9 @@ __global__ __launch_bounds__(256) void mg_loss_bwd_kernel(LossBwdG p) {
         if ((p.flags & M3PC_MTM_CLIP_ACTIONS) && a == a) ac = fminf(fmaxf(a, lo), hi);
         const float z = 0.5f * (log1pf(ac) - log1pf(-ac));
         const float dz = z - mu, var = sd * sd, eps = p.eps[at];
-        const float th = tanhf(mu + eps * sd);
-        dmu = (p.entropy_reg * 2.0f * th - dz / var) * p.inv_cnt;
-        dsd = (p.entropy_reg * (2.0f * th * eps - 1.0f / sd) - (dz * dz / (var * sd) - 1.0f / sd)) * p.inv_cnt;
+        const float th = tanhf(mu + eps * sd), er = p.entropy_reg_p ? *p.entropy_reg_p : p.entropy_reg;
+        dmu = (er * 2.0f * th - dz / var) * p.inv_cnt;
+        dsd = (er * (2.0f * th * eps - 1.0f / sd) - (dz * dz / (var * sd) - 1.0f / sd)) * p.inv_cnt;
     }
     const float tl = tanhf(p.ls[at]);
     p.dmu[at] = dmu;
@@ -523,32 +523,7 @@ void mg_launch_loss_bwd(const LossBwdG& p, hipStream_t st) {
 
 }  // namespace m3pc
 
-struct m3pc_mtm_grad {
-    m3pc_handle* h = nullptr;
-    int max_batch = 0;
-    bool ready = false, have_grad = false;
-    struct Par {
-        std::string name;
-        long long numel;
-        size_t off;
-    };
-    std::vector<Par> par;
-    std::map<std::string, int> idx;
-    size_t grad_floats = 0;
-    float* arena = nullptr;  // every fp32 buffer below
-    double* arena64 = nullptr;
-    float* grad = nullptr;
-    struct Lay {
-        float *Xin, *Hn1, *QKV, *P, *O, *X1, *Hn2, *Fpre, *Fact, *st1, *st2;
-    };
-    std::vector<Lay> lay;  // encoder layers, then decoder layers
-    float *XencOut, *EncN, *st_enc, *Zin, *XdecOut, *DecN, *st_dec;
-    float *tok[4], *raw[3], *eps;
-    float *Hh[3], *st_h[3], *Hpre[3], *Hact[3], *pred[3], *mu, *ls, *sd;
-    float *dX, *dH, *dQKV, *dF, *dO, *dpred[3], *dmu, *dls, *dh1, *dh2, *rec;
-    double *raw_returns, *part, *colpart;
-};
-
+namespace m3pc {
 namespace {
 
 using Obj = struct m3pc_mtm_grad;
@@ -849,7 +824,7 @@ EmbG emb_params(const Run& r) {
 
 // everything behind the refusals: the batch is in g->tok-able form (raw rows), the masks are bits
 int mg_run(Obj* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
-           const u64 bits[4], const float* eps, float entropy_reg, int flags, int loss_keys, float* record, hipStream_t st) {
+           const u64 bits[4], const float* eps, float entropy_reg, const float* entropy_reg_p, int flags, int loss_keys, float* record, hipStream_t st) {
     m3pc_handle* h = g->h;
     Run r;
     r.g = g;
@@ -936,9 +911,11 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         p.flags = flags;
         p.loss_keys = loss_keys;
         p.entropy_reg = entropy_reg;
+        p.entropy_reg_p = entropy_reg_p;
         p.part = g->part;
-        p.record = record ? record : g->rec;
+        p.record = g->rec;  // (the optimizer reads the entropy here: a caller's buffer may be gone by then)
         launch_mtm_loss(p, st);
+        if (record) HIPCHK(hipMemcpyAsync(record, g->rec, M3PC_MTM_LOSS_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     CHK(check_launch("mtm_grad forward"));
 
@@ -967,6 +944,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         p.flags = flags;
         p.loss_keys = loss_keys;
         p.entropy_reg = entropy_reg;
+        p.entropy_reg_p = entropy_reg_p;
         p.inv_cnt = (float)(1.0 / ((double)batch * (double)(T - r.kept[M3PC_ACTIONS]) * (double)A));
         mg_launch_loss_bwd(p, st);
     }
@@ -1039,6 +1017,8 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     }
     CHK(check_launch("mtm_grad backward"));
     g->have_grad = true;
+    g->consumed = false;
+    g->last_loss_keys = loss_keys;
     return 0;
 }
 
@@ -1072,6 +1052,63 @@ int mg_state(const Obj* g, const char* who) {
 }
 
 }  // namespace
+
+int mg_precheck(const struct m3pc_mtm_grad* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who) {
+    u64 bits[4];
+    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
+    return mg_state(g, who);
+}
+int mg_precheck_replay(const struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const unsigned char* const masks[4], int flags, int loss_keys,
+                       const char* who) {
+    u64 bits[4];
+    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
+    const m3pc_handle* h = g->h;
+    int S = 0, A = 0, dev = 0;
+    replay_sizes(rb, &S, &A, &dev);
+    const int L = replay_segment_length(rb);
+    if (S != h->dm.state_dim || A != h->dm.action_dim || dev != h->device || L != h->dm.traj_length)
+        return fail(M3PC_EINVAL, "%s: the buffer (S %d, A %d, segment_length %d, device %d) does not fit the handle (%d, %d, T %d, %d)", who,
+                    S, A, L, dev, h->dm.state_dim, h->dm.action_dim, h->dm.traj_length, h->device);
+    CHK(replay_check_segments(rb, batch, mode, nullptr, nullptr, 0, who));
+    return mg_state(g, who);
+}
+
+int mg_call(struct m3pc_mtm_grad* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
+            const unsigned char* const masks[4], const float* eps, float entropy_reg, const float* entropy_reg_p, int flags, int loss_keys,
+            float* record, hipStream_t st, const char* who) {
+    u64 bits[4];
+    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
+    CHK(mg_state(g, who));
+    CHK(mg_ensure(g));
+    return mg_run(g, batch, states, actions, rewards, returns, returns_f64, bits, eps, entropy_reg, entropy_reg_p, flags, loss_keys, record, st);
+}
+
+int mg_call_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
+                   unsigned long long seed, unsigned long long step, const unsigned char* const masks[4], const float* eps, float entropy_reg,
+                   const float* entropy_reg_p, int flags, int loss_keys, float* record, int* out_traj, int* out_start, hipStream_t st,
+                   const char* who) {
+    u64 bits[4];
+    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
+    m3pc_handle* h = g->h;
+    int S = 0, A = 0, dev = 0;
+    replay_sizes(rb, &S, &A, &dev);
+    const int L = replay_segment_length(rb);
+    if (S != h->dm.state_dim || A != h->dm.action_dim || dev != h->device || L != h->dm.traj_length)
+        return fail(M3PC_EINVAL, "%s: the buffer (S %d, A %d, segment_length %d, device %d) does not fit the handle (%d, %d, T %d, %d)", who,
+                    S, A, L, dev, h->dm.state_dim, h->dm.action_dim, h->dm.traj_length, h->device);
+    CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, who));
+    CHK(mg_state(g, who));
+    CHK(mg_ensure(g));
+    CHK(m3pc_replay_sample_segments(rb, batch, mode, traj_index, start_index, index_on_device, seed, step, g->raw[0], g->raw[1], g->raw[2],
+                                    g->raw_returns, 0, out_traj, out_start, (void*)st));
+    if (!eps) {  // array 0 of the generator of m3pc_draw_variates at (seed, step): batch * T rows of A normals
+        launch_variates(seed, step, 0, 0, (long long)batch * h->T * h->A, g->eps, st);
+        CHK(check_launch("mtm_grad variates"));
+        eps = g->eps;
+    }
+    return mg_run(g, batch, g->raw[0], g->raw[1], g->raw[2], g->raw_returns, 1, bits, eps, entropy_reg, entropy_reg_p, flags, loss_keys, record, st);
+}
+}  // namespace m3pc
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -1113,11 +1150,8 @@ int m3pc_mtm_grad(struct m3pc_mtm_grad* g, int batch, const float* states, const
                   int returns_f64, const unsigned char* const masks[4], const float* eps, float entropy_reg, int flags, int loss_keys,
                   float* record, void* stream) {
     if (!g || !states || !actions || !rewards || !returns || !masks || !eps) return fail(M3PC_EINVAL, "m3pc_mtm_grad: null argument");
-    u64 bits[4];
-    CHK(mg_check(g, batch, masks, flags, loss_keys, "m3pc_mtm_grad", bits));
-    CHK(mg_state(g, "m3pc_mtm_grad"));
-    CHK(mg_ensure(g));
-    return mg_run(g, batch, states, actions, rewards, returns, returns_f64, bits, eps, entropy_reg, flags, loss_keys, record, (hipStream_t)stream);
+    return mg_call(g, batch, states, actions, rewards, returns, returns_f64, masks, eps, entropy_reg, nullptr, flags, loss_keys, record,
+                   (hipStream_t)stream, "m3pc_mtm_grad");
 }
 
 int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
@@ -1125,27 +1159,8 @@ int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, in
                          const float* eps, float entropy_reg, int flags, int loss_keys, float* record, int* out_traj, int* out_start,
                          void* stream) {
     if (!g || !rb || !masks) return fail(M3PC_EINVAL, "m3pc_mtm_grad_replay: null argument");
-    u64 bits[4];
-    CHK(mg_check(g, batch, masks, flags, loss_keys, "m3pc_mtm_grad_replay", bits));
-    m3pc_handle* h = g->h;
-    int S = 0, A = 0, dev = 0;
-    replay_sizes(rb, &S, &A, &dev);
-    const int L = replay_segment_length(rb);
-    if (S != h->dm.state_dim || A != h->dm.action_dim || dev != h->device || L != h->dm.traj_length)
-        return fail(M3PC_EINVAL, "m3pc_mtm_grad_replay: the buffer (S %d, A %d, segment_length %d, device %d) does not fit the handle (%d, %d, T %d, %d)",
-                    S, A, L, dev, h->dm.state_dim, h->dm.action_dim, h->dm.traj_length, h->device);
-    CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, "m3pc_mtm_grad_replay"));
-    CHK(mg_state(g, "m3pc_mtm_grad_replay"));
-    CHK(mg_ensure(g));
-    hipStream_t st = (hipStream_t)stream;
-    CHK(m3pc_replay_sample_segments(rb, batch, mode, traj_index, start_index, index_on_device, seed, step, g->raw[0], g->raw[1], g->raw[2],
-                                    g->raw_returns, 0, out_traj, out_start, stream));
-    if (!eps) {  // array 0 of the generator of m3pc_draw_variates at (seed, step): batch * T rows of A normals
-        launch_variates(seed, step, 0, 0, (long long)batch * h->T * h->A, g->eps, st);
-        CHK(check_launch("mtm_grad variates"));
-        eps = g->eps;
-    }
-    return mg_run(g, batch, g->raw[0], g->raw[1], g->raw[2], g->raw_returns, 1, bits, eps, entropy_reg, flags, loss_keys, record, st);
+    return mg_call_replay(g, rb, batch, mode, traj_index, start_index, index_on_device, seed, step, masks, eps, entropy_reg, nullptr, flags,
+                          loss_keys, record, out_traj, out_start, (hipStream_t)stream, "m3pc_mtm_grad_replay");
 }
 
 int m3pc_mtm_grad_export(struct m3pc_mtm_grad* g, const m3pc_named_tensor* tensors, int n, void* stream) {

@@ -41,6 +41,7 @@ struct MtmLossP {
     unsigned long long mask[4];  // bit t of mask[k]: token t of key k is visible
     int batch, T, S, A, flags, loss_keys;
     float entropy_reg;
+    const float* entropy_reg_p;  // optional device scalar read in place of entropy_reg (the trainer's temperature, mtm_opt.h)
     double* part;           // (rows, MTM_LOSS_PART)
     float* record;
 };

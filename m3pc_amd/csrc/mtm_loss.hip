@@ -128,7 +128,7 @@ __global__ __launch_bounds__(ML_THREADS) void mtm_loss_reduce_kernel(MtmLossP p)
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if ((p.loss_keys >> k) & 1) total += loss[k];
-    total -= ll + (double)p.entropy_reg * entropy;
+    total -= ll + (double)(p.entropy_reg_p ? *p.entropy_reg_p : p.entropy_reg) * entropy;
     rec[12] = (float)entropy;
     rec[13] = (float)(-ll);
     rec[14] = (float)total;

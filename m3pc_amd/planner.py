@@ -1306,7 +1306,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
         return raw_batch_loss(self.handle, batch, masks, float(entropy_reg), "finetune", eps, capi.PREC_FP32)
 
     def mtm_update(self, batch, data_shapes, discrete_map, model, optimizer, scheduler, temp_optimizer, masks=None, eps=None,
-                   dropout=None, sync=True):
+                   dropout=None, sync=True, native=False):
         """Learner.mtm_update (finetune_omtm/learner.py:506-538) with its forward and ``loss.backward()`` in one library call
         (m3pc_mtm_grad): the gradients of ``model``'s parameters come from the device (``DeviceMTMGrad.backward_into``), then
         ``optimizer.step()``, ``scheduler.step()`` and the temperature step on ``temperature * (entropy - target_entropy)`` with the
@@ -1316,7 +1316,11 @@ class HipPlanner(GoalMixin, LockstepMixin):
         synchronise included; a caller that steps often should follow the tensors itself and pass ``sync=False``, as ``attach`` does
         (its ``_sync`` sends only what the last optimizer step moved).
         THE GRADIENT IS THE EVAL-MODE MODEL'S: NO DROPOUT.  A model in training mode whose config has ``dropout > 0`` is refused
-        unless ``dropout="eval"`` says that a step without dropout is what the caller wants."""
+        unless ``dropout="eval"`` says that a step without dropout is what the caller wants.
+        native: the whole step as one library call (m3pc_mtm_train_step, ``DeviceMTMTrainer``) on the planner's OWN weights: the
+        first native call imports the state of ``optimizer`` / ``scheduler`` / ``temp_optimizer`` (a shim with ``mtm``,
+        ``mtm_optimizer``, ``mtm_scheduler``, ``temp_optimizer``, ``cfg``; ``sync`` uploads the module's weights for it, once), later
+        calls leave ``model`` and the torch optimizers alone -- ``planner._mtm_trainer.to_learner(learner)`` writes them back."""
         from .masks import create_random_autoregressive_mask
         from .mtm import form_settings, loss_tuple
         from .mtm_grad import DeviceMTMGrad
@@ -1328,9 +1332,22 @@ class HipPlanner(GoalMixin, LockstepMixin):
             raise capi.M3pcError("discrete heads are not used by any m3pc config and are not supported")
         if masks is None:
             masks = create_random_autoregressive_mask(data_shapes, self.cfg.mask_ratio, self.cfg.traj_length, self.cfg.p_weights)
+        B = int(batch["states"].shape[0])
+        if native:
+            from .mtm_train import DeviceMTMTrainer
+            tr = getattr(self, "_mtm_trainer", None)
+            if tr is None or tr.max_batch < B:
+                if tr is not None:
+                    tr.to_learner(tr._shim)
+                    tr.close()
+                if sync:
+                    self.load_state_dict({k: v.detach() for k, v in model.state_dict().items()})
+                shim = types.SimpleNamespace(cfg=self.cfg, mtm=model, mtm_optimizer=optimizer, mtm_scheduler=scheduler, temp_optimizer=temp_optimizer)
+                tr = self._mtm_trainer = DeviceMTMTrainer.from_learner(shim, planner=self, max_batch=B)
+                tr._shim = shim
+            return tr.train_step(batch, masks, eps, "finetune")
         if sync:
             self.load_state_dict({k: v.detach() for k, v in model.state_dict().items()})
-        B = int(batch["states"].shape[0])
         g = getattr(self, "_mtm_grad", None)
         if g is None or g.max_batch < B:
             if g is not None:
@@ -1398,7 +1415,9 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     mtm_update: True rebinds ``learner.mtm_update(batch, data_shapes, discrete_map)`` too, onto ``HipPlanner.mtm_update`` with the
     learner's own ``mtm``, ``mtm_optimizer``, ``mtm_scheduler`` and ``temp_optimizer`` (further keywords -- masks, eps, dropout -- pass
     through).  The device gradient is the eval-mode model's (no dropout): with a model in training mode whose config has dropout > 0
-    the rebound method raises unless called with ``dropout="eval"``.  The default (False) leaves ``mtm_update`` alone.
+    the rebound method raises unless called with ``dropout="eval"``.  "native": the same rebinding with the optimizers on the
+    device too (``HipPlanner.mtm_update(native=True)``: the planner's own weights move; ``learner._hip_planner._mtm_trainer.to_learner(learner)``
+    writes weights and optimizer state back to torch).  The default (False) leaves ``mtm_update`` alone.
     Weights are followed per tensor: before each call the version counters of ``mtm`` / ``iql.qf`` are compared with the
     ones uploaded last, and only the tensors that changed are sent (m3pc_load_weights re-packs what depends on them)."""
     capi.precision_code(precision)  # (an unknown name fails here, before anything is built)
@@ -1453,11 +1472,13 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
                  "action_piid_sample", "action_id_sample", "action_piid_list_sample", "plan_async", "action_sample_batch",
                  "compute_mtm_loss"):
         setattr(learner, name, _wrap(name))
+    if mtm_update not in (False, True, "native"):
+        raise ValueError('mtm_update must be False, True or "native"')
     if mtm_update:
         def _mtm_update(self, batch, data_shapes, discrete_map, **kw):
             _sync()
             return planner.mtm_update(batch, data_shapes, discrete_map, self.mtm, self.mtm_optimizer, self.mtm_scheduler,
-                                      self.temp_optimizer, sync=False, **kw)
+                                      self.temp_optimizer, sync=False, native=mtm_update == "native", **kw)
 
         learner.mtm_update = types.MethodType(_mtm_update, learner)
     learner._hip_planner = planner

@@ -373,6 +373,12 @@ class DeviceReplayBuffer:
         del ti, si, keep
         return (rec, oi) if return_indices else rec
 
+    def mtm_train(self, trainer, n_steps: int, masks, batch_size: Optional[int] = None, form: str = "finetune"):
+        """``n_steps`` whole training steps of the model (m3pc_mtm_train) on the batches ``traj_sample`` would draw at this ``step``,
+        ``step + 1``, ...: ``trainer`` is a ``DeviceMTMTrainer`` on this buffer's handle (``trainer.train_from``).  Returns (records
+        (n_steps, 15), train_records (n_steps, 3)) on the device; ``step`` advances by n_steps.  Eval-mode model: no dropout."""
+        return trainer.train_from(self, n_steps, batch_size, masks, form)
+
     def split(self, batch_size: Optional[int] = None):
         """(rows of the online ring, rows of the offline ring) of a transition batch: replay_buffer.py:370-381."""
         B = int(self.trans_batch_size if batch_size is None else batch_size)
