@@ -21,6 +21,7 @@
 #endif
 #include "cert_resolve.h"
 #include "kernels.h"
+#include "mtm_batch.h"
 
 using namespace m3pc;
 
@@ -295,9 +296,8 @@ struct m3pc_handle {
     // outputs (states, rewards, returns, mu, std), the raw batch and the normals of a replay draw, and the per-row partial sums
     struct MtmLoss {
         bool ready = false;
-        float *tok[4] = {nullptr, nullptr, nullptr, nullptr}, *head[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        float *raw[3] = {nullptr, nullptr, nullptr}, *eps = nullptr;
-        double *raw_returns = nullptr, *part = nullptr;
+        MtmStage s;
+        float* head[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     } ml;
 };
 

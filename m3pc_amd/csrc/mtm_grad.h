@@ -36,10 +36,7 @@
 #pragma once
 #include "m3pc_internal.h"
 
-struct m3pc_replay;
 namespace m3pc {
-int replay_segment_length(const m3pc_replay* rb);
-
 // ------------------------------------------------------------------------------------------------ parameter structures
 // (mtm_grad.hip holds the kernels; mg_run and the lab hooks of m3pc_debug.hip fill these and go through the launchers below)
 // row r of a compact run -> row of the buffer: rpg rows per group, groups gstride rows apart, from row off (rpg == 0: r itself)
@@ -178,24 +175,33 @@ struct m3pc_mtm_grad {
     };
     std::vector<Lay> lay;  // encoder layers, then decoder layers
     float *XencOut, *EncN, *st_enc, *Zin, *XdecOut, *DecN, *st_dec;
-    float *tok[4], *raw[3], *eps;
+    m3pc::MtmStage s;  // tok, raw, eps out of arena; raw_returns, part out of arena64
     float *Hh[3], *st_h[3], *Hpre[3], *Hact[3], *pred[3], *mu, *ls, *sd;
     float *dX, *dH, *dQKV, *dF, *dO, *dpred[3], *dmu, *dls, *dh1, *dh2, *rec;
-    double *raw_returns, *part, *colpart;
+    double* colpart;
 };
 
 namespace m3pc {
-// m3pc_mtm_grad / m3pc_mtm_grad_replay behind their null checks, under the caller's name `who`: the refusals, the allocation and the
-// launches.  entropy_reg_p: optional device scalar read in place of entropy_reg.  The record lands in g->rec, and in `record` too when given.
-// the refusals of those calls that need no HIP call, alone (the trainer makes them before it allocates)
-int mg_precheck(const struct m3pc_mtm_grad* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who);
-int mg_precheck_replay(const struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const unsigned char* const masks[4], int flags, int loss_keys,
-                       const char* who);
-int mg_call(struct m3pc_mtm_grad* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
-            const unsigned char* const masks[4], const float* eps, float entropy_reg, const float* entropy_reg_p, int flags, int loss_keys,
-            float* record, hipStream_t st, const char* who);
-int mg_call_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
-                   unsigned long long seed, unsigned long long step, const unsigned char* const masks[4], const float* eps, float entropy_reg,
-                   const float* entropy_reg_p, int flags, int loss_keys, float* record, int* out_traj, int* out_start, hipStream_t st,
-                   const char* who);
+// m3pc_mtm_grad / m3pc_mtm_grad_replay behind their null checks, under the caller's name `who`, in the three parts every entry makes in
+// this order (the trainer of mtm_opt.hip: the first for all its steps, the second once, the third per step).
+// 1. Every refusal of the call and bits[k], the mask of key k.  No HIP call, and a pure function of the arguments and of host state that
+//    neither a gradient call, a replay draw nor an optimizer step writes (the handle's m3pc_dims, weights_loaded and tok_set; the
+//    buffer's sizes, count and path lengths): what holds before the first of a run of steps holds before each of them.
+int mg_precheck(const struct m3pc_mtm_grad* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who,
+                unsigned long long bits[4]);
+int mg_precheck_replay(const struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
+                       int index_on_device, const unsigned char* const masks[4], int flags, int loss_keys, const char* who,
+                       unsigned long long bits[4]);
+// 2. The object's arenas, at the first call.
+int mg_ensure(struct m3pc_mtm_grad* g);
+// 3. The launches.  entropy_reg_p: optional device scalar read in place of entropy_reg.  The record lands in g->rec, and in `record`
+//    too when given.  mg_run_replay draws the batch (and, with eps null, the normals) into the object's staging rows first.
+int mg_run(struct m3pc_mtm_grad* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
+           const unsigned long long bits[4], const float* eps, float entropy_reg, const float* entropy_reg_p, int flags, int loss_keys,
+           float* record, hipStream_t st);
+int mg_run_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
+                  unsigned long long seed, unsigned long long step, const unsigned long long bits[4], const float* eps, float entropy_reg,
+                  const float* entropy_reg_p, int flags, int loss_keys, float* record, int* out_traj, int* out_start, hipStream_t st,
+                  const char* who);
 }  // namespace m3pc
+

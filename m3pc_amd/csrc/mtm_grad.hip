@@ -563,9 +563,9 @@ size_t mg_layout(Obj* g, float* base) {
     take(&g->XdecOut, R * d);
     take(&g->DecN, R * d);
     take(&g->st_dec, R * 2);
-    for (int k = 0; k < 4; ++k) take(&g->tok[k], RT * h->feat[k]);
-    for (int k = 0; k < 3; ++k) take(&g->raw[k], RT * h->feat[k]);
-    take(&g->eps, RT * A);
+    for (int k = 0; k < 4; ++k) take(&g->s.tok[k], RT * h->feat[k]);
+    for (int k = 0; k < 3; ++k) take(&g->s.raw[k], RT * h->feat[k]);
+    take(&g->s.eps, RT * A);
     const size_t hw[3] = {S, 1, 1};
     for (int j = 0; j < 3; ++j) {
         take(&g->Hh[j], RT * d);
@@ -591,6 +591,8 @@ size_t mg_layout(Obj* g, float* base) {
     return at;
 }
 
+}  // namespace
+
 int mg_ensure(Obj* g) {
     m3pc_handle* h = g->h;
     HIPCHK(hipSetDevice(h->device));
@@ -602,12 +604,14 @@ int mg_ensure(Obj* g) {
     const size_t C = (size_t)std::max(3 * h->d, h->ff);
     const size_t n64 = al64(RT) + al64(RT * MTM_LOSS_PART) + mg_colsum_doubles((long long)R, (int)C);  // (no column sum has more rows than R)
     if (!g->arena64) CHK(dmalloc(&g->arena64, n64));
-    g->raw_returns = g->arena64;
-    g->part = g->raw_returns + al64(RT);
-    g->colpart = g->part + al64(RT * MTM_LOSS_PART);
+    g->s.raw_returns = g->arena64;
+    g->s.part = g->s.raw_returns + al64(RT);
+    g->colpart = g->s.part + al64(RT * MTM_LOSS_PART);
     g->ready = true;
     return 0;
 }
+
+namespace {
 
 struct Run {
     Obj* g;
@@ -804,7 +808,7 @@ EmbG emb_params(const Run& r) {
     memset(&e, 0, sizeof(e));
     for (int k = 0; k < 4; ++k) {
         const std::string kn = KEYN[k];
-        e.tok[k] = r.g->tok[k];
+        e.tok[k] = r.g->s.tok[k];
         e.W[k] = r.Wt("encoder_embed_dict." + kn + ".weight");
         e.bias[k] = r.Wt("encoder_embed_dict." + kn + ".bias");
         e.pdim[k] = r.Wt("encoder_per_dim_encoding." + kn);
@@ -822,7 +826,9 @@ EmbG emb_params(const Run& r) {
     return e;
 }
 
-// everything behind the refusals: the batch is in g->tok-able form (raw rows), the masks are bits
+}  // namespace
+
+// everything behind the refusals: the batch is in raw rows, the masks are bits
 int mg_run(Obj* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
            const u64 bits[4], const float* eps, float entropy_reg, const float* entropy_reg_p, int flags, int loss_keys, float* record, hipStream_t st) {
     m3pc_handle* h = g->h;
@@ -847,10 +853,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     HIPCHK(hipMemsetAsync(g->grad, 0, g->grad_floats * sizeof(float), st));
 
     // ---------------- forward
-    const void* raw[4] = {states, actions, rewards, returns};
-    for (int k = 0; k < 4; ++k)
-        launch_tokenize(raw[k], k == M3PC_RETURNS ? (returns_f64 ? 1 : 0) : 0, g->tok[k], RT, h->feat[k], h->tok_mean[k], h->tok_std[k],
-                        h->tok_norm[k], st);
+    mb_tokenize(h, g->s, batch, states, actions, rewards, returns, returns_f64, st);
     EmbG e = emb_params(r);
     float* enc0 = nE ? g->lay[0].Xin : g->XencOut;
     e.X = enc0;
@@ -893,30 +896,10 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         run_gemm(r, p);
         mg_launch_std(g->ls, g->sd, (long long)RT * A, st);
     }
-    {
-        MtmLossP p;
-        memset(&p, 0, sizeof(p));
-        for (int j = 0; j < 3; ++j) p.pred[j] = g->pred[j];
-        p.mu = g->mu;
-        p.sd = g->sd;
-        for (int k = 0; k < 4; ++k) {
-            p.tgt[k] = g->tok[k];
-            p.mask[k] = bits[k];
-        }
-        p.eps = eps;
-        p.batch = batch;
-        p.T = T;
-        p.S = S;
-        p.A = A;
-        p.flags = flags;
-        p.loss_keys = loss_keys;
-        p.entropy_reg = entropy_reg;
-        p.entropy_reg_p = entropy_reg_p;
-        p.part = g->part;
-        p.record = g->rec;  // (the optimizer reads the entropy here: a caller's buffer may be gone by then)
-        launch_mtm_loss(p, st);
-        if (record) HIPCHK(hipMemcpyAsync(record, g->rec, M3PC_MTM_LOSS_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
+    const float* const pred[5] = {g->pred[0], g->pred[1], g->pred[2], g->mu, g->sd};
+    // (the optimizer reads the entropy in g->rec: a caller's buffer may be gone by then)
+    mb_loss(h, g->s, batch, pred, g->s.tok, bits, eps, entropy_reg, entropy_reg_p, flags, loss_keys, g->rec, st);
+    if (record) HIPCHK(hipMemcpyAsync(record, g->rec, M3PC_MTM_LOSS_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, st));
     CHK(check_launch("mtm_grad forward"));
 
     // ---------------- backward
@@ -934,7 +917,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         p.dmu = g->dmu;
         p.dls = g->dls;
         for (int k = 0; k < 4; ++k) {
-            p.tgt[k] = g->tok[k];
+            p.tgt[k] = g->s.tok[k];
             p.mask[k] = bits[k];
         }
         p.batch = batch;
@@ -1022,91 +1005,26 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     return 0;
 }
 
-// what the calls refuse alike, before any HIP call; bits[k]: the mask of key k, bit t = token t visible
-int mg_check(const Obj* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who, u64 bits[4]) {
-    const m3pc_handle* h = g->h;
-    if (batch < 1 || batch > g->max_batch) return fail(M3PC_EINVAL, "%s: batch %d outside [1, max_batch=%d]", who, batch, g->max_batch);
-    if (flags & ~(M3PC_MTM_NORM_L2 | M3PC_MTM_CLIP_ACTIONS)) return fail(M3PC_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (loss_keys < 0 || loss_keys > 15) return fail(M3PC_EINVAL, "%s: loss_keys %d outside [0, 15]", who, loss_keys);
-    const int T = h->dm.traj_length;
-    if (T < 1 || T > 64) return fail(M3PC_EINVAL, "%s: traj_length %d outside [1, 64]", who, T);
-    int kept = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (!masks[k]) return fail(M3PC_EINVAL, "%s: null mask of '%s'", who, KEYN[k]);
-        bits[k] = 0;
-        for (int t = 0; t < T; ++t) {
-            if (masks[k][t] > 1) return fail(M3PC_EINVAL, "%s: mask byte %d of '%s' is %d, not 0 or 1", who, t, KEYN[k], (int)masks[k][t]);
-            bits[k] |= (u64)masks[k][t] << t;
-            kept += masks[k][t];
-        }
-    }
-    if (kept == 0) return fail(M3PC_EINVAL, "%s: mask keeps no token", who);
-    return 0;
+int mg_precheck(const struct m3pc_mtm_grad* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who,
+                u64 bits[4]) {
+    CHK(mb_check(g->h->dm, g->max_batch, batch, masks, flags, loss_keys, who, true, bits));
+    return mb_state(g->h, who);
 }
-
-int mg_state(const Obj* g, const char* who) {
-    if (!g->h->weights_loaded) return fail(M3PC_ESTATE, "%s: weights not loaded", who);
-    for (int k = 0; k < 4; ++k)
-        if (!g->h->tok_set[k]) return fail(M3PC_ESTATE, "%s: tokenizer '%s' not set", who, KEYN[k]);
-    return 0;
-}
-
-}  // namespace
-
-int mg_precheck(const struct m3pc_mtm_grad* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who) {
-    u64 bits[4];
-    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
-    return mg_state(g, who);
-}
-int mg_precheck_replay(const struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const unsigned char* const masks[4], int flags, int loss_keys,
-                       const char* who) {
-    u64 bits[4];
-    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
-    const m3pc_handle* h = g->h;
-    int S = 0, A = 0, dev = 0;
-    replay_sizes(rb, &S, &A, &dev);
-    const int L = replay_segment_length(rb);
-    if (S != h->dm.state_dim || A != h->dm.action_dim || dev != h->device || L != h->dm.traj_length)
-        return fail(M3PC_EINVAL, "%s: the buffer (S %d, A %d, segment_length %d, device %d) does not fit the handle (%d, %d, T %d, %d)", who,
-                    S, A, L, dev, h->dm.state_dim, h->dm.action_dim, h->dm.traj_length, h->device);
-    CHK(replay_check_segments(rb, batch, mode, nullptr, nullptr, 0, who));
-    return mg_state(g, who);
-}
-
-int mg_call(struct m3pc_mtm_grad* g, int batch, const float* states, const float* actions, const float* rewards, const void* returns, int returns_f64,
-            const unsigned char* const masks[4], const float* eps, float entropy_reg, const float* entropy_reg_p, int flags, int loss_keys,
-            float* record, hipStream_t st, const char* who) {
-    u64 bits[4];
-    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
-    CHK(mg_state(g, who));
-    CHK(mg_ensure(g));
-    return mg_run(g, batch, states, actions, rewards, returns, returns_f64, bits, eps, entropy_reg, entropy_reg_p, flags, loss_keys, record, st);
-}
-
-int mg_call_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
-                   unsigned long long seed, unsigned long long step, const unsigned char* const masks[4], const float* eps, float entropy_reg,
-                   const float* entropy_reg_p, int flags, int loss_keys, float* record, int* out_traj, int* out_start, hipStream_t st,
-                   const char* who) {
-    u64 bits[4];
-    CHK(mg_check(g, batch, masks, flags, loss_keys, who, bits));
-    m3pc_handle* h = g->h;
-    int S = 0, A = 0, dev = 0;
-    replay_sizes(rb, &S, &A, &dev);
-    const int L = replay_segment_length(rb);
-    if (S != h->dm.state_dim || A != h->dm.action_dim || dev != h->device || L != h->dm.traj_length)
-        return fail(M3PC_EINVAL, "%s: the buffer (S %d, A %d, segment_length %d, device %d) does not fit the handle (%d, %d, T %d, %d)", who,
-                    S, A, L, dev, h->dm.state_dim, h->dm.action_dim, h->dm.traj_length, h->device);
+int mg_precheck_replay(const struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
+                       int index_on_device, const unsigned char* const masks[4], int flags, int loss_keys, const char* who, u64 bits[4]) {
+    CHK(mb_check(g->h->dm, g->max_batch, batch, masks, flags, loss_keys, who, true, bits));
+    CHK(mb_fits(g->h, rb, who));
     CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, who));
-    CHK(mg_state(g, who));
-    CHK(mg_ensure(g));
-    CHK(m3pc_replay_sample_segments(rb, batch, mode, traj_index, start_index, index_on_device, seed, step, g->raw[0], g->raw[1], g->raw[2],
-                                    g->raw_returns, 0, out_traj, out_start, (void*)st));
-    if (!eps) {  // array 0 of the generator of m3pc_draw_variates at (seed, step): batch * T rows of A normals
-        launch_variates(seed, step, 0, 0, (long long)batch * h->T * h->A, g->eps, st);
-        CHK(check_launch("mtm_grad variates"));
-        eps = g->eps;
-    }
-    return mg_run(g, batch, g->raw[0], g->raw[1], g->raw[2], g->raw_returns, 1, bits, eps, entropy_reg, entropy_reg_p, flags, loss_keys, record, st);
+    return mb_state(g->h, who);
+}
+
+int mg_run_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index, int index_on_device,
+                  unsigned long long seed, unsigned long long step, const u64 bits[4], const float* eps, float entropy_reg,
+                  const float* entropy_reg_p, int flags, int loss_keys, float* record, int* out_traj, int* out_start, hipStream_t st,
+                  const char* who) {
+    const MtmStage& s = g->s;
+    CHK(mb_draw(g->h, s, rb, batch, mode, traj_index, start_index, index_on_device, seed, step, &eps, out_traj, out_start, st, who));
+    return mg_run(g, batch, s.raw[0], s.raw[1], s.raw[2], s.raw_returns, 1, bits, eps, entropy_reg, entropy_reg_p, flags, loss_keys, record, st);
 }
 }  // namespace m3pc
 
@@ -1150,8 +1068,11 @@ int m3pc_mtm_grad(struct m3pc_mtm_grad* g, int batch, const float* states, const
                   int returns_f64, const unsigned char* const masks[4], const float* eps, float entropy_reg, int flags, int loss_keys,
                   float* record, void* stream) {
     if (!g || !states || !actions || !rewards || !returns || !masks || !eps) return fail(M3PC_EINVAL, "m3pc_mtm_grad: null argument");
-    return mg_call(g, batch, states, actions, rewards, returns, returns_f64, masks, eps, entropy_reg, nullptr, flags, loss_keys, record,
-                   (hipStream_t)stream, "m3pc_mtm_grad");
+    u64 bits[4];
+    CHK(mg_precheck(g, batch, masks, flags, loss_keys, "m3pc_mtm_grad", bits));
+    CHK(mg_ensure(g));
+    return mg_run(g, batch, states, actions, rewards, returns, returns_f64, bits, eps, entropy_reg, nullptr, flags, loss_keys, record,
+                  (hipStream_t)stream);
 }
 
 int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
@@ -1159,30 +1080,24 @@ int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, in
                          const float* eps, float entropy_reg, int flags, int loss_keys, float* record, int* out_traj, int* out_start,
                          void* stream) {
     if (!g || !rb || !masks) return fail(M3PC_EINVAL, "m3pc_mtm_grad_replay: null argument");
-    return mg_call_replay(g, rb, batch, mode, traj_index, start_index, index_on_device, seed, step, masks, eps, entropy_reg, nullptr, flags,
-                          loss_keys, record, out_traj, out_start, (hipStream_t)stream, "m3pc_mtm_grad_replay");
+    const char* who = "m3pc_mtm_grad_replay";
+    u64 bits[4];
+    CHK(mg_precheck_replay(g, rb, batch, mode, traj_index, start_index, index_on_device, masks, flags, loss_keys, who, bits));
+    CHK(mg_ensure(g));
+    return mg_run_replay(g, rb, batch, mode, traj_index, start_index, index_on_device, seed, step, bits, eps, entropy_reg, nullptr, flags,
+                         loss_keys, record, out_traj, out_start, (hipStream_t)stream, who);
 }
 
 int m3pc_mtm_grad_export(struct m3pc_mtm_grad* g, const m3pc_named_tensor* tensors, int n, void* stream) {
     if (!g || !tensors || n < 0) return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: null argument");
-    for (int i = 0; i < n; ++i) {
-        const m3pc_named_tensor& t = tensors[i];
-        if (!t.name || !t.data) return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: entry %d has no name or no data", i);
-        auto it = g->idx.find(t.name);
-        if (it == g->idx.end()) return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: '%s' is not a parameter", t.name);
-        if (t.numel != g->par[it->second].numel)
-            return fail(M3PC_EINVAL, "m3pc_mtm_grad_export: '%s' has %lld elements, expected %lld", t.name, t.numel, g->par[it->second].numel);
-    }
+    auto par = [g](const char* name) {
+        auto it = g->idx.find(name);
+        return it == g->idx.end() ? nullptr : &g->par[it->second];
+    };
+    CHK(nt_check(tensors, n, [&](const char* name) { return par(name) ? par(name)->numel : -1ll; }, "m3pc_mtm_grad_export", "parameter"));
     if (!g->have_grad) return fail(M3PC_ESTATE, "m3pc_mtm_grad_export: no gradient call was made");
     HIPCHK(hipSetDevice(g->h->device));
-    hipStream_t st = (hipStream_t)stream;
-    for (int i = 0; i < n; ++i) {
-        const m3pc_named_tensor& t = tensors[i];
-        const Obj::Par& p = g->par[g->idx.at(t.name)];
-        HIPCHK(hipMemcpyAsync(const_cast<float*>(t.data), g->grad + p.off, (size_t)p.numel * sizeof(float),
-                              t.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    }
-    return 0;
+    return nt_copy(tensors, n, true, [&](const char* name) { return g->grad + par(name)->off; }, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,6 @@
 // The masked-trajectory loss (include/m3pc_hip.h: m3pc_mtm_loss_terms, m3pc_mtm_loss, m3pc_mtm_loss_replay).  mtm_loss.h states the
 // arithmetic, the reduction order and the record.  Two launches behind the forward's.
 #include "device_util.h"
-#include "iql.h"
 #include "mtm_loss.h"
 
 namespace m3pc {
@@ -144,9 +143,9 @@ void launch_mtm_loss(const MtmLossP& p, hipStream_t st) {
 
 void mtm_loss_free(m3pc_handle* h) {
     auto& m = h->ml;
-    for (void* b : {(void*)m.tok[0], (void*)m.tok[1], (void*)m.tok[2], (void*)m.tok[3], (void*)m.head[0], (void*)m.head[1], (void*)m.head[2],
-                    (void*)m.head[3], (void*)m.head[4], (void*)m.raw[0], (void*)m.raw[1], (void*)m.raw[2], (void*)m.eps, (void*)m.raw_returns,
-                    (void*)m.part})
+    for (void* b : {(void*)m.s.tok[0], (void*)m.s.tok[1], (void*)m.s.tok[2], (void*)m.s.tok[3], (void*)m.head[0], (void*)m.head[1],
+                    (void*)m.head[2], (void*)m.head[3], (void*)m.head[4], (void*)m.s.raw[0], (void*)m.s.raw[1], (void*)m.s.raw[2], (void*)m.s.eps,
+                    (void*)m.s.raw_returns, (void*)m.s.part})
         if (b) (void)hipFree(b);
     m = m3pc_handle::MtmLoss();
 }
@@ -161,60 +160,15 @@ int ml_ensure(m3pc_handle* h) {
     auto& m = h->ml;
     if (m.ready) return 0;
     const size_t rows = (size_t)h->dm.max_batch * h->T;
-    for (int k = 0; k < 4; ++k) CHK(dmalloc(&m.tok[k], rows * h->feat[k]));
+    for (int k = 0; k < 4; ++k) CHK(dmalloc(&m.s.tok[k], rows * h->feat[k]));
     const int hw[5] = {h->S, 1, 1, h->A, h->A};
     for (int j = 0; j < 5; ++j) CHK(dmalloc(&m.head[j], rows * hw[j]));
-    for (int k = 0; k < 3; ++k) CHK(dmalloc(&m.raw[k], rows * h->feat[k]));
-    CHK(dmalloc(&m.eps, rows * h->A));
-    CHK(dmalloc(&m.raw_returns, rows));
-    CHK(dmalloc(&m.part, rows * MTM_LOSS_PART));
+    for (int k = 0; k < 3; ++k) CHK(dmalloc(&m.s.raw[k], rows * h->feat[k]));
+    CHK(dmalloc(&m.s.eps, rows * h->A));
+    CHK(dmalloc(&m.s.raw_returns, rows));
+    CHK(dmalloc(&m.s.part, rows * MTM_LOSS_PART));
     m.ready = true;
     return 0;
-}
-
-// what the three calls refuse alike, from the sizes a handle starts with (no HIP call, nothing behind the m3pc_dims is read);
-// bits[k]: the mask of key k, bit t = token t visible
-int ml_check(const m3pc_handle* h, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who,
-             unsigned long long bits[4]) {
-    if (batch < 1 || batch > h->dm.max_batch) return fail(M3PC_EINVAL, "%s: batch %d outside [1, max_batch=%d]", who, batch, h->dm.max_batch);
-    if (flags & ~(M3PC_MTM_NORM_L2 | M3PC_MTM_CLIP_ACTIONS)) return fail(M3PC_EINVAL, "%s: unknown flag bits 0x%x", who, flags);
-    if (loss_keys < 0 || loss_keys > 15) return fail(M3PC_EINVAL, "%s: loss_keys %d outside [0, 15]", who, loss_keys);
-    const int T = h->dm.traj_length;
-    if (T < 1 || T > 64) return fail(M3PC_EINVAL, "%s: traj_length %d outside [1, 64]", who, T);
-    for (int k = 0; k < 4; ++k) {
-        if (!masks[k]) return fail(M3PC_EINVAL, "%s: null mask of '%s'", who, KEYN[k]);
-        bits[k] = 0;
-        for (int t = 0; t < T; ++t) {
-            if (masks[k][t] > 1) return fail(M3PC_EINVAL, "%s: mask byte %d of '%s' is %d, not 0 or 1", who, t, KEYN[k], (int)masks[k][t]);
-            bits[k] |= (unsigned long long)masks[k][t] << t;
-        }
-    }
-    return 0;
-}
-
-int ml_terms(m3pc_handle* h, int batch, const float* const pred[5], const float* const tgt[4], const unsigned long long bits[4],
-             const float* eps, float entropy_reg, int flags, int loss_keys, float* record, hipStream_t st) {
-    MtmLossP p;
-    memset(&p, 0, sizeof(p));
-    for (int j = 0; j < 3; ++j) p.pred[j] = pred[j];
-    p.mu = pred[3];
-    p.sd = pred[4];
-    for (int k = 0; k < 4; ++k) {
-        p.tgt[k] = tgt[k];
-        p.mask[k] = bits[k];
-    }
-    p.eps = eps;
-    p.batch = batch;
-    p.T = h->T;
-    p.S = h->S;
-    p.A = h->A;
-    p.flags = flags;
-    p.loss_keys = loss_keys;
-    p.entropy_reg = entropy_reg;
-    p.part = h->ml.part;
-    p.record = record;
-    launch_mtm_loss(p, st);
-    return check_launch("mtm_loss");
 }
 
 // tokenise the raw batch, omtm.forward under the masks, the loss: everything behind the refusals
@@ -222,18 +176,14 @@ int ml_run(m3pc_handle* h, int batch, const float* states, const float* actions,
            const unsigned char* const masks[4], const unsigned long long bits[4], const float* eps, float entropy_reg, int flags,
            int loss_keys, int precision, float* record, float* const outs[5], hipStream_t st) {
     auto& m = h->ml;
-    const long long rows = (long long)batch * h->T;
-    const void* raw[4] = {states, actions, rewards, returns};
-    for (int k = 0; k < 4; ++k)
-        launch_tokenize(raw[k], k == M3PC_RETURNS ? (returns_f64 ? 1 : 0) : 0, m.tok[k], rows, h->feat[k], h->tok_mean[k], h->tok_std[k],
-                        h->tok_norm[k], st);
+    mb_tokenize(h, m.s, batch, states, actions, rewards, returns, returns_f64, st);
     CHK(check_launch("mtm_loss tokenize"));
     Plan* pl = nullptr;
     CHK(get_plan(h, masks, &pl));
     TokIn in;
     memset(&in, 0, sizeof(in));
     for (int k = 0; k < 4; ++k) {
-        in.ptr[k] = m.tok[k];
+        in.ptr[k] = m.s.tok[k];
         in.bstride[k] = (long long)h->T * h->feat[k];
     }
     float* head[5];
@@ -244,7 +194,8 @@ int ml_run(m3pc_handle* h, int batch, const float* states, const float* actions,
         X3Scope x3(h, precision == M3PC_PREC_BF16X3);
         CHK(forward_impl(h, pl, in, batch, head[0], head[1], head[2], head[3], head[4], pass_dt(precision), st));
     }
-    return ml_terms(h, batch, head, m.tok, bits, eps, entropy_reg, flags, loss_keys, record, st);
+    mb_loss(h, m.s, batch, head, m.s.tok, bits, eps, entropy_reg, nullptr, flags, loss_keys, record, st);
+    return check_launch("mtm_loss");
 }
 
 }  // namespace
@@ -260,23 +211,23 @@ int m3pc_mtm_loss_terms(m3pc_handle* h, int batch, const float* pred_states, con
     for (int k = 0; k < 4; ++k)
         if (!targets[k]) return fail(M3PC_EINVAL, "m3pc_mtm_loss_terms: null targets of '%s'", KEYN[k]);
     unsigned long long bits[4];
-    CHK(ml_check(h, batch, masks, flags, loss_keys, "m3pc_mtm_loss_terms", bits));
+    CHK(mb_check(h->dm, h->dm.max_batch, batch, masks, flags, loss_keys, "m3pc_mtm_loss_terms", false, bits));
     CHK(ml_ensure(h));
     const float* pred[5] = {pred_states, pred_rewards, pred_returns, mu, std_};
-    return ml_terms(h, batch, pred, targets, bits, eps, entropy_reg, flags, loss_keys, record, (hipStream_t)stream);
+    mb_loss(h, h->ml.s, batch, pred, targets, bits, eps, entropy_reg, nullptr, flags, loss_keys, record, (hipStream_t)stream);
+    return check_launch("mtm_loss");
 }
 
 int m3pc_mtm_loss(m3pc_handle* h, int batch, const float* states, const float* actions, const float* rewards, const void* returns,
                   int returns_f64, const unsigned char* const masks[4], const float* eps, float entropy_reg, int flags, int loss_keys,
                   int precision, float* record, float* out_states, float* out_rewards, float* out_returns, float* out_mu, float* out_std,
                   void* stream) {
-    if (!h || !states || !actions || !rewards || !returns || !masks || !eps || !record) return fail(M3PC_EINVAL, "m3pc_mtm_loss: null argument");
+    const char* who = "m3pc_mtm_loss";
+    if (!h || !states || !actions || !rewards || !returns || !masks || !eps || !record) return fail(M3PC_EINVAL, "%s: null argument", who);
     unsigned long long bits[4];
-    CHK(ml_check(h, batch, masks, flags, loss_keys, "m3pc_mtm_loss", bits));
-    if (!precision_ok(precision)) return fail(M3PC_EINVAL, "m3pc_mtm_loss: bad precision %d", precision);
-    if (!h->weights_loaded) return fail(M3PC_ESTATE, "m3pc_mtm_loss: weights not loaded");
-    for (int k = 0; k < 4; ++k)
-        if (!h->tok_set[k]) return fail(M3PC_ESTATE, "m3pc_mtm_loss: tokenizer '%s' not set", KEYN[k]);
+    CHK(mb_check(h->dm, h->dm.max_batch, batch, masks, flags, loss_keys, who, false, bits));
+    if (!precision_ok(precision)) return fail(M3PC_EINVAL, "%s: bad precision %d", who, precision);
+    CHK(mb_state(h, who));
     CHK(ml_ensure(h));
     float* const outs[5] = {out_states, out_rewards, out_returns, out_mu, out_std};
     return ml_run(h, batch, states, actions, rewards, returns, returns_f64, masks, bits, eps, entropy_reg, flags, loss_keys, precision, record,
@@ -287,34 +238,23 @@ int m3pc_mtm_loss_replay(m3pc_handle* h, m3pc_replay* rb, int batch, int mode, c
                          int index_on_device, unsigned long long seed, unsigned long long step, const unsigned char* const masks[4],
                          const float* eps, float entropy_reg, int flags, int loss_keys, int precision, float* record, int* out_traj,
                          int* out_start, void* stream) {
-    if (!h || !rb || !masks || !record) return fail(M3PC_EINVAL, "m3pc_mtm_loss_replay: null argument");
+    const char* who = "m3pc_mtm_loss_replay";
+    if (!h || !rb || !masks || !record) return fail(M3PC_EINVAL, "%s: null argument", who);
     unsigned long long bits[4];
-    CHK(ml_check(h, batch, masks, flags, loss_keys, "m3pc_mtm_loss_replay", bits));
-    if (!precision_ok(precision)) return fail(M3PC_EINVAL, "m3pc_mtm_loss_replay: bad precision %d", precision);
-    int S = 0, A = 0, dev = 0;
-    replay_sizes(rb, &S, &A, &dev);
-    const int L = replay_segment_length(rb);
-    if (S != h->dm.state_dim || A != h->dm.action_dim || dev != h->device || L != h->dm.traj_length)
-        return fail(M3PC_EINVAL, "m3pc_mtm_loss_replay: the buffer (S %d, A %d, segment_length %d, device %d) does not fit the handle (%d, %d, T %d, %d)",
-                    S, A, L, dev, h->dm.state_dim, h->dm.action_dim, h->dm.traj_length, h->device);
-    CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, "m3pc_mtm_loss_replay"));
-    if (!h->weights_loaded) return fail(M3PC_ESTATE, "m3pc_mtm_loss_replay: weights not loaded");
-    for (int k = 0; k < 4; ++k)
-        if (!h->tok_set[k]) return fail(M3PC_ESTATE, "m3pc_mtm_loss_replay: tokenizer '%s' not set", KEYN[k]);
+    CHK(mb_check(h->dm, h->dm.max_batch, batch, masks, flags, loss_keys, who, false, bits));
+    if (!precision_ok(precision)) return fail(M3PC_EINVAL, "%s: bad precision %d", who, precision);
+    CHK(mb_fits(h, rb, who));
+    CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, who));
+    CHK(mb_state(h, who));
     CHK(ml_ensure(h));
-    auto& m = h->ml;
+    const MtmStage& s = h->ml.s;
     hipStream_t st = (hipStream_t)stream;
-    CHK(m3pc_replay_sample_segments(rb, batch, mode, traj_index, start_index, index_on_device, seed, step, m.raw[0], m.raw[1], m.raw[2],
-                                    m.raw_returns, 0, out_traj, out_start, stream));
-    if (!eps) {  // array 0 of the generator of m3pc_draw_variates at (seed, step): batch * T rows of A normals
-        launch_variates(seed, step, 0, 0, (long long)batch * h->T * h->A, m.eps, st);
-        CHK(check_launch("mtm_loss variates"));
-        eps = m.eps;
-    }
+    CHK(mb_draw(h, s, rb, batch, mode, traj_index, start_index, index_on_device, seed, step, &eps, out_traj, out_start, st, who));
     float* const outs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    return ml_run(h, batch, m.raw[0], m.raw[1], m.raw[2], m.raw_returns, 1, masks, bits, eps, entropy_reg, flags, loss_keys, precision, record,
+    return ml_run(h, batch, s.raw[0], s.raw[1], s.raw[2], s.raw_returns, 1, masks, bits, eps, entropy_reg, flags, loss_keys, precision, record,
                   outs, st);
 }
 
 }  // extern "C"
 #pragma GCC visibility pop
+

@@ -205,7 +205,7 @@ double mo_lr(const m3pc_mtm_opt_args& a, long long s) {
     return a.learning_rate * lam;
 }
 
-int mo_ensure(Opt* o, hipStream_t st) {
+int mo_ensure(Opt* o) {
     m3pc_handle* h = o->g->h;
     HIPCHK(hipSetDevice(h->device));
     if (o->ready) return 0;
@@ -231,7 +231,6 @@ int mo_ensure(Opt* o, hipStream_t st) {
     HIPCHK(hipMemcpy(o->d_temp, t4, sizeof(t4), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(o->d_temp_f, &tf, sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipDeviceSynchronize());
-    (void)st;
     o->cur = 0;
     o->ready = true;
     return 0;
@@ -297,16 +296,18 @@ int mo_step(Opt* o, bool last, double* train_record, hipStream_t st, const char*
     return 0;
 }
 
+// the parameter `name` in the gradient object's list, or null
+const m3pc_mtm_grad::Par* mo_par(const Opt* o, const char* name) {
+    auto it = o->g->idx.find(name);
+    return it == o->g->idx.end() ? nullptr : &o->g->par[it->second];
+}
 int mo_find(const Opt* o, const m3pc_named_tensor* tensors, int n, const char* who) {
-    for (int i = 0; i < n; ++i) {
-        const m3pc_named_tensor& t = tensors[i];
-        if (!t.name || !t.data) return fail(M3PC_EINVAL, "%s: entry %d has no name or no data", who, i);
-        auto it = o->g->idx.find(t.name);
-        if (it == o->g->idx.end()) return fail(M3PC_EINVAL, "%s: '%s' is not a parameter", who, t.name);
-        if (t.numel != o->g->par[it->second].numel)
-            return fail(M3PC_EINVAL, "%s: '%s' has %lld elements, expected %lld", who, t.name, t.numel, o->g->par[it->second].numel);
-    }
-    return 0;
+    return nt_check(tensors, n, [o](const char* name) { return mo_par(o, name) ? mo_par(o, name)->numel : -1ll; }, who, "parameter");
+}
+// exp_avg (which = 1) or exp_avg_sq (2) of the listed parameters, to the caller's tensors or from them
+int mo_copy(Opt* o, int which, const m3pc_named_tensor* tensors, int n, bool to_caller, hipStream_t st) {
+    float* base = o->arena + (which == 2 ? o->g->grad_floats : 0);
+    return nt_copy(tensors, n, to_caller, [&](const char* name) { return base + mo_par(o, name)->off; }, st);
 }
 
 }  // namespace
@@ -379,7 +380,7 @@ int m3pc_mtm_opt_step(struct m3pc_mtm_opt* o, void* stream) {
     if (o->g->consumed) return fail(M3PC_ESTATE, "m3pc_mtm_opt_step: the gradients of the last gradient call were already applied");
     CHK(mo_step_state(o, "m3pc_mtm_opt_step"));
     hipStream_t st = (hipStream_t)stream;
-    CHK(mo_ensure(o, st));
+    CHK(mo_ensure(o));
     CHK(ws_sync(o->g->h, st));  // (deferred candidate parts still read the weights this call is about to move)
     return mo_step(o, true, nullptr, st, "m3pc_mtm_opt_step");
 }
@@ -390,13 +391,14 @@ int m3pc_mtm_train_step(struct m3pc_mtm_opt* o, int batch, const float* states, 
     if (!o) return fail(M3PC_EINVAL, "m3pc_mtm_train_step: null opt");
     if (!states || !actions || !rewards || !returns || !masks || !eps)
         return fail(M3PC_EINVAL, "m3pc_mtm_train_step: null argument (states, actions, rewards, returns, masks or eps)");
-    CHK(mg_precheck(o->g, batch, masks, flags, loss_keys, "m3pc_mtm_train_step"));
+    unsigned long long bits[4];
+    CHK(mg_precheck(o->g, batch, masks, flags, loss_keys, "m3pc_mtm_train_step", bits));
     CHK(mo_step_state(o, "m3pc_mtm_train_step"));
     hipStream_t st = (hipStream_t)stream;
-    CHK(mo_ensure(o, st));
+    CHK(mo_ensure(o));
     CHK(ws_sync(o->g->h, st));
-    CHK(mg_call(o->g, batch, states, actions, rewards, returns, returns_f64, masks, eps, 0.f, o->d_temp_f, flags, loss_keys, record, st,
-                "m3pc_mtm_train_step"));
+    CHK(mg_ensure(o->g));
+    CHK(mg_run(o->g, batch, states, actions, rewards, returns, returns_f64, bits, eps, 0.f, o->d_temp_f, flags, loss_keys, record, st));
     return mo_step(o, true, train_record, st, "m3pc_mtm_train_step");
 }
 
@@ -405,16 +407,18 @@ int m3pc_mtm_train(struct m3pc_mtm_opt* o, m3pc_replay* rb, int n_steps, int bat
     if (!o) return fail(M3PC_EINVAL, "m3pc_mtm_train: null opt");
     if (!rb || !masks) return fail(M3PC_EINVAL, "m3pc_mtm_train: null argument (rb or masks)");
     if (n_steps < 1) return fail(M3PC_EINVAL, "m3pc_mtm_train: n_steps %d < 1", n_steps);
+    std::vector<unsigned long long> bits(4 * (size_t)n_steps);  // (every step is refused or accepted before the first one runs: mtm_grad.h)
     for (int i = 0; i < n_steps; ++i)
-        CHK(mg_precheck_replay(o->g, rb, batch, mode, masks + 4 * (size_t)i, flags, loss_keys, "m3pc_mtm_train"));
+        CHK(mg_precheck_replay(o->g, rb, batch, mode, nullptr, nullptr, 0, masks + 4 * (size_t)i, flags, loss_keys, "m3pc_mtm_train", &bits[4 * (size_t)i]));
     CHK(mo_step_state(o, "m3pc_mtm_train"));
     hipStream_t st = (hipStream_t)stream;
-    CHK(mo_ensure(o, st));
+    CHK(mo_ensure(o));
     CHK(ws_sync(o->g->h, st));
+    CHK(mg_ensure(o->g));
     for (int i = 0; i < n_steps; ++i) {
-        CHK(mg_call_replay(o->g, rb, batch, mode, nullptr, nullptr, 0, seed, step0 + (unsigned long long)i, masks + 4 * (size_t)i, nullptr, 0.f,
-                           o->d_temp_f, flags, loss_keys, records ? records + (size_t)i * M3PC_MTM_LOSS_FLOATS : nullptr, nullptr, nullptr, st,
-                           "m3pc_mtm_train"));
+        CHK(mg_run_replay(o->g, rb, batch, mode, nullptr, nullptr, 0, seed, step0 + (unsigned long long)i, &bits[4 * (size_t)i], nullptr, 0.f,
+                          o->d_temp_f, flags, loss_keys, records ? records + (size_t)i * M3PC_MTM_LOSS_FLOATS : nullptr, nullptr, nullptr, st,
+                          "m3pc_mtm_train"));
         CHK(mo_step(o, i + 1 == n_steps, train_records ? train_records + 3 * (size_t)i : nullptr, st, "m3pc_mtm_train"));
     }
     return 0;
@@ -425,13 +429,8 @@ int m3pc_mtm_opt_export(struct m3pc_mtm_opt* o, int which, const m3pc_named_tens
     if (which != 1 && which != 2) return fail(M3PC_EINVAL, "m3pc_mtm_opt_export: which %d is not 1 (exp_avg) or 2 (exp_avg_sq)", which);
     CHK(mo_find(o, tensors, n, "m3pc_mtm_opt_export"));
     hipStream_t st = (hipStream_t)stream;
-    CHK(mo_ensure(o, st));
-    const float* base = o->arena + (which == 2 ? o->g->grad_floats : 0);
-    for (int i = 0; i < n; ++i) {
-        const auto& par = o->g->par[o->g->idx.at(tensors[i].name)];
-        HIPCHK(hipMemcpyAsync(const_cast<float*>(tensors[i].data), base + par.off, (size_t)par.numel * sizeof(float),
-                              tensors[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    }
+    CHK(mo_ensure(o));
+    CHK(mo_copy(o, which, tensors, n, true, st));
     if (steps) {  // (host out: waits for the stream)
         const size_t ns = o->seg.size();
         std::vector<long long> all(ns);
@@ -450,13 +449,8 @@ int m3pc_mtm_opt_load(struct m3pc_mtm_opt* o, int which, const m3pc_named_tensor
         for (int i = 0; i < n; ++i)
             if (steps[i] < 0) return fail(M3PC_EINVAL, "m3pc_mtm_opt_load: steps[%d] = %lld < 0", i, steps[i]);
     hipStream_t st = (hipStream_t)stream;
-    CHK(mo_ensure(o, st));
-    float* base = o->arena + (which == 2 ? o->g->grad_floats : 0);
-    for (int i = 0; i < n; ++i) {
-        const auto& par = o->g->par[o->g->idx.at(tensors[i].name)];
-        HIPCHK(hipMemcpyAsync(base + par.off, tensors[i].data, (size_t)par.numel * sizeof(float),
-                              tensors[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    }
+    CHK(mo_ensure(o));
+    CHK(mo_copy(o, which, tensors, n, false, st));
     HIPCHK(hipStreamSynchronize(st));  // the caller's tensors may go away when the call returns
     if (steps) {
         const size_t ns = o->seg.size();
@@ -471,23 +465,14 @@ int m3pc_mtm_opt_load(struct m3pc_mtm_opt* o, int which, const m3pc_named_tensor
 
 int m3pc_mtm_weights_export(m3pc_handle* h, const m3pc_named_tensor* tensors, int n, void* stream) {
     if (!h || !tensors || n < 0) return fail(M3PC_EINVAL, "m3pc_mtm_weights_export: null argument (h or tensors) or n < 0");
-    for (int i = 0; i < n; ++i) {
-        const m3pc_named_tensor& t = tensors[i];
-        if (!t.name || !t.data) return fail(M3PC_EINVAL, "m3pc_mtm_weights_export: entry %d has no name or no data", i);
-        auto it = h->w.find(t.name);
-        if (it == h->w.end()) return fail(M3PC_EINVAL, "m3pc_mtm_weights_export: '%s' is not a tensor of the model", t.name);
-        if (t.numel != it->second.numel)
-            return fail(M3PC_EINVAL, "m3pc_mtm_weights_export: '%s' has %lld elements, expected %lld", t.name, t.numel, it->second.numel);
-    }
+    auto numel_of = [h](const char* name) {
+        auto it = h->w.find(name);
+        return it == h->w.end() ? -1ll : it->second.numel;
+    };
+    CHK(nt_check(tensors, n, numel_of, "m3pc_mtm_weights_export", "tensor of the model"));
     if (!h->weights_loaded) return fail(M3PC_ESTATE, "m3pc_mtm_weights_export: weights not loaded");
     HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    for (int i = 0; i < n; ++i) {
-        const Tensor& w = h->w.at(tensors[i].name);
-        HIPCHK(hipMemcpyAsync(const_cast<float*>(tensors[i].data), w.f, (size_t)w.numel * sizeof(float),
-                              tensors[i].on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    }
-    return 0;
+    return nt_copy(tensors, n, true, [h](const char* name) { return h->w.at(name).f; }, (hipStream_t)stream);
 }
 
 int m3pc_mtm_opt_get_state(struct m3pc_mtm_opt* o, m3pc_mtm_opt_state* out) {

@@ -60,6 +60,43 @@ def form_settings(form: str, order):
     raise ValueError(f"form must be one of {FORMS}, got {form!r}")
 
 
+def device_batch(handle, batch, eps=None, form: str = "finetune", flags=None, loss_keys=None):
+    """A raw batch {key: (B,T,D_k)} as m3pc_mtm_grad / m3pc_mtm_train_step take it: -> (B, states, actions, rewards, returns, eps,
+    returns_f64, flags, loss_keys): the tensors contiguous on the handle's device, float32 except returns that came as float64.  eps:
+    (B,T,A) standard normals; None: torch.randn on the handle's device.  flags / loss_keys override those of ``form``."""
+    order = list(batch.keys())
+    if sorted(order) != sorted(KEYS):
+        raise capi.M3pcError(f"the batch must hold exactly the keys {KEYS}")
+    f, bits, _ = form_settings(form, order)
+    f = f if flags is None else int(flags)
+    bits = bits if loss_keys is None else int(loss_keys)
+    h, dev = handle, handle.device
+    B = int(batch["states"].shape[0])
+    s, a, r = (h._f32(batch[k].to(dev)).reshape(B, h.T, -1) for k in ("states", "actions", "rewards"))
+    v = batch["returns"].to(dev)
+    v = v.contiguous() if v.dtype == torch.float64 else h._f32(v)
+    if eps is None:
+        eps = torch.randn((B, h.T, h.A), dtype=torch.float32, device=dev)
+    e = h._f32(eps.to(dev)).reshape(B, h.T, h.A)
+    return B, s, a, r, v, e, int(v.dtype == torch.float64), f, bits
+
+
+def named_strict(tensors: Dict[str, torch.Tensor], device, what: str = ""):
+    """{name: tensor} -> (NamedTensor array, keep-alives) for the calls that write to or read the caller's own storage: every tensor
+    must be contiguous float32, on the host or on ``device`` (``capi._named`` converts instead).  what: prefix of the messages."""
+    arr = (capi.NamedTensor * len(tensors))()
+    keep = []
+    for j, (k, t) in enumerate(tensors.items()):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise capi.M3pcError(f"{what}'{k}' must be a contiguous float32 tensor")
+        if t.is_cuda and t.device != device:
+            raise capi.M3pcError(f"{what}'{k}' lives on {t.device}, not on {device} or the host")
+        nb = k.encode()
+        keep.append(nb)
+        arr[j] = capi.NamedTensor(nb, t.data_ptr(), t.numel(), 1 if t.is_cuda else 0)
+    return arr, keep
+
+
 def raw_batch_loss(handle, batch, masks, entropy_reg, form="finetune", eps=None, precision=capi.PREC_FP32, want_heads=False):
     """m3pc_mtm_loss on a raw batch dict {key: (B,T,D)} (``traj_sample``'s) under ``masks`` -> the reference's 5-tuple of ``form``
     (and the five head outputs with want_heads).  eps: (B,T,A) standard normals; None: torch.randn on the handle's device."""

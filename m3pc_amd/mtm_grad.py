@@ -14,7 +14,7 @@ import torch
 
 from . import capi
 from .masks import mask_rows
-from .mtm import form_settings, loss_tuple
+from .mtm import device_batch, form_settings, loss_tuple, named_strict
 
 KEYS = capi.KEYS
 
@@ -95,24 +95,11 @@ class DeviceMTMGrad:
     def grad_record(self, batch, masks, entropy_reg: float, form: str = "finetune", eps=None, flags=None, loss_keys=None) -> torch.Tensor:
         """m3pc_mtm_grad on a raw batch {key: (B,T,D_k)} (returns float32 or float64) under ``masks``; the gradients stay in the
         object (``export``).  flags / loss_keys override those of ``form``.  Returns the device record (15 floats)."""
-        order = list(batch.keys())
-        if sorted(order) != sorted(KEYS):
-            raise capi.M3pcError(f"the batch must hold exactly the keys {KEYS}")
-        f, bits, _ = form_settings(form, order)
-        f = f if flags is None else int(flags)
-        bits = bits if loss_keys is None else int(loss_keys)
-        h = self.handle
-        B = int(batch["states"].shape[0])
-        s, a, r = (h._f32(batch[k].to(self.device)).reshape(B, h.T, -1) for k in ("states", "actions", "rewards"))
-        v = batch["returns"].to(self.device)
-        v = v.contiguous() if v.dtype == torch.float64 else h._f32(v)
-        if eps is None:
-            eps = torch.randn((B, h.T, h.A), dtype=torch.float32, device=self.device)
-        e = h._f32(eps.to(self.device)).reshape(B, h.T, h.A)
+        B, s, a, r, v, e, f64, f, bits = device_batch(self.handle, batch, eps, form, flags, loss_keys)
         rec = torch.empty(capi.MTM_LOSS_FLOATS, dtype=torch.float32, device=self.device)
-        mp, keep = h._mask_ptrs(mask_rows(masks))
+        mp, keep = self.handle._mask_ptrs(mask_rows(masks))
         with torch.cuda.device(self.device):
-            capi.check(self.lib.m3pc_mtm_grad(self._g, B, capi._ptr(s), capi._ptr(a), capi._ptr(r), capi._ptr(v), int(v.dtype == torch.float64),
+            capi.check(self.lib.m3pc_mtm_grad(self._g, B, capi._ptr(s), capi._ptr(a), capi._ptr(r), capi._ptr(v), f64,
                                               mp, capi._ptr(e), float(entropy_reg), f, bits, capi._ptr(rec), self._stream()))
         del keep
         return rec
@@ -122,16 +109,7 @@ class DeviceMTMGrad:
         on the library's GPU} to write to (any subset of the parameters); None: new device tensors for every parameter."""
         if into is None:
             into = {k: torch.empty(s, dtype=torch.float32, device=self.device) for k, s in self.shapes.items()}
-        arr = (capi.NamedTensor * len(into))()
-        keep = []
-        for j, (k, t) in enumerate(into.items()):
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise capi.M3pcError(f"export target '{k}' must be a contiguous float32 tensor")
-            if t.is_cuda and t.device != self.device:
-                raise capi.M3pcError(f"export target '{k}' lives on {t.device}, not on {self.device} or the host")
-            nb = k.encode()
-            keep.append(nb)
-            arr[j] = capi.NamedTensor(nb, t.data_ptr(), t.numel(), 1 if t.is_cuda else 0)
+        arr, keep = named_strict(into, self.device, "export target ")
         with torch.cuda.device(self.device):
             capi.check(self.lib.m3pc_mtm_grad_export(self._g, arr, len(into), self._stream()))
             if any(not t.is_cuda for t in into.values()):

@@ -17,7 +17,7 @@ import torch
 
 from . import capi
 from .masks import mask_rows
-from .mtm import form_settings, loss_tuple
+from .mtm import device_batch, form_settings, loss_tuple, named_strict
 from .mtm_grad import DeviceMTMGrad
 
 KEYS = capi.KEYS
@@ -119,25 +119,12 @@ class DeviceMTMTrainer:
     def train_step_record(self, batch, masks, eps=None, form: str = "finetune", flags=None, loss_keys=None):
         """m3pc_mtm_train_step on a raw batch {key: (B,T,D_k)} -> (record: 15 device floats, train_record: 3 device doubles
         {lr used, temperature after, log_temperature after}).  No host wait."""
-        order = list(batch.keys())
-        if sorted(order) != sorted(KEYS):
-            raise capi.M3pcError(f"the batch must hold exactly the keys {KEYS}")
-        f, bits, _ = form_settings(form, order)
-        f = f if flags is None else int(flags)
-        bits = bits if loss_keys is None else int(loss_keys)
-        h = self.handle
-        B = int(batch["states"].shape[0])
-        s, a, r = (h._f32(batch[k].to(self.device)).reshape(B, h.T, -1) for k in ("states", "actions", "rewards"))
-        v = batch["returns"].to(self.device)
-        v = v.contiguous() if v.dtype == torch.float64 else h._f32(v)
-        if eps is None:
-            eps = torch.randn((B, h.T, h.A), dtype=torch.float32, device=self.device)
-        e = h._f32(eps.to(self.device)).reshape(B, h.T, h.A)
+        B, s, a, r, v, e, f64, f, bits = device_batch(self.handle, batch, eps, form, flags, loss_keys)
         rec = torch.empty(capi.MTM_LOSS_FLOATS, dtype=torch.float32, device=self.device)
         trec = torch.empty(3, dtype=torch.float64, device=self.device)
-        mp, keep = h._mask_ptrs(mask_rows(masks))
+        mp, keep = self.handle._mask_ptrs(mask_rows(masks))
         with torch.cuda.device(self.device):
-            capi.check(self.lib.m3pc_mtm_train_step(self._o, B, capi._ptr(s), capi._ptr(a), capi._ptr(r), capi._ptr(v), int(v.dtype == torch.float64),
+            capi.check(self.lib.m3pc_mtm_train_step(self._o, B, capi._ptr(s), capi._ptr(a), capi._ptr(r), capi._ptr(v), f64,
                                                     mp, capi._ptr(e), f, bits, capi._ptr(rec), capi._ptr(trec), self._stream()))
         del keep
         self._moved()
@@ -199,26 +186,13 @@ class DeviceMTMTrainer:
         return recs, trecs
 
     # -- state in and out ---------------------------------------------------------------------------
-    def _named(self, tensors: Dict[str, torch.Tensor]):
-        arr = (capi.NamedTensor * len(tensors))()
-        keep = []
-        for j, (k, t) in enumerate(tensors.items()):
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise capi.M3pcError(f"'{k}' must be a contiguous float32 tensor")
-            if t.is_cuda and t.device != self.device:
-                raise capi.M3pcError(f"'{k}' lives on {t.device}, not on {self.device} or the host")
-            nb = k.encode()
-            keep.append(nb)
-            arr[j] = capi.NamedTensor(nb, t.data_ptr(), t.numel(), 1 if t.is_cuda else 0)
-        return arr, keep
-
     def _new(self, names=None):
         return {k: torch.empty(s, dtype=torch.float32, device=self.device) for k, s in self.shapes.items() if names is None or k in names}
 
     def export_weights(self, into: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """m3pc_mtm_weights_export: the handle's fp32 weights, each in the torch layout of its parameter."""
         into = self._new() if into is None else into
-        arr, keep = self._named(into)
+        arr, keep = named_strict(into, self.device)
         with torch.cuda.device(self.device):
             capi.check(self.lib.m3pc_mtm_weights_export(self.handle._h, arr, len(into), self._stream()))
             if any(not t.is_cuda for t in into.values()):
@@ -229,7 +203,7 @@ class DeviceMTMTrainer:
     def export_moments(self, which: int, into: Optional[Dict[str, torch.Tensor]] = None, steps: bool = False):
         """m3pc_mtm_opt_export: exp_avg (which = 1) or exp_avg_sq (2); with ``steps`` -> (tensors, {name: step count}) (waits)."""
         into = self._new() if into is None else into
-        arr, keep = self._named(into)
+        arr, keep = named_strict(into, self.device)
         st = (C.c_longlong * max(1, len(into)))() if steps else None
         with torch.cuda.device(self.device):
             capi.check(self.lib.m3pc_mtm_opt_export(self._o, int(which), arr, len(into), st, self._stream()))
@@ -240,7 +214,7 @@ class DeviceMTMTrainer:
 
     def load_moments(self, which: int, tensors: Dict[str, torch.Tensor], steps: Optional[Dict[str, int]] = None):
         """m3pc_mtm_opt_load; steps: {name: count} for the listed tensors, or None to leave the counts."""
-        arr, keep = self._named(tensors)
+        arr, keep = named_strict(tensors, self.device)
         st = None if steps is None else (C.c_longlong * max(1, len(tensors)))(*[int(steps[k]) for k in tensors])
         with torch.cuda.device(self.device):
             capi.check(self.lib.m3pc_mtm_opt_load(self._o, int(which), arr, len(tensors), st, self._stream()))

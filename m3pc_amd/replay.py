@@ -286,17 +286,21 @@ class DeviceReplayBuffer:
         return self._ub
 
     # ------------------------------------------------------------------------------------------ sampling
+    def _segment_indices(self, indices, batch_size):
+        """(indices, batch_size) of the segment calls -> (B, traj_index pointer, start_index pointer, index_on_device, keep-alives);
+        indices None: the pointers are None and the library draws."""
+        if indices is None:
+            return int(self.traj_batch_size if batch_size is None else batch_size), None, None, 0, None
+        B = int(np.prod(np.shape(indices[0])))
+        ti, pt, dev = self._index(indices[0], B)
+        si, ps, dev2 = self._index(indices[1], B)
+        if dev != dev2:
+            raise ValueError("trajectory indices and starts must both be on the host or both on the device")
+        return B, pt, ps, dev, (ti, si)
+
     def traj_sample(self, indices=None, batch_size: Optional[int] = None, returns_f32: bool = False, return_indices: bool = False):
         """replay_buffer.py:312-366.  indices: (trajectory indices, starts), each (B,), host or device; None: drawn by the library."""
-        B = int(self.traj_batch_size if batch_size is None else batch_size)
-        ti = si = pt = ps = None
-        dev = 0
-        if indices is not None:
-            B = int(np.prod(np.shape(indices[0])))
-            ti, pt, dev = self._index(indices[0], B)
-            si, ps, dev2 = self._index(indices[1], B)
-            if dev != dev2:
-                raise ValueError("trajectory indices and starts must both be on the host or both on the device")
+        B, pt, ps, dev, keep_i = self._segment_indices(indices, batch_size)
         L = self.sequence_length
         s, a, r = self._new(B, L, self.S), self._new(B, L, self.A), self._new(B, L, 1)
         v = self._new(B, L, 1, dtype=torch.float32 if returns_f32 else torch.float64)
@@ -306,7 +310,7 @@ class DeviceReplayBuffer:
                                                         capi._ptr(oi[1]), self._stream()))
         if indices is None:
             self.step += 1
-        del ti, si
+        del keep_i
         batch = {"states": s, "actions": a, "rewards": r, "returns": v}
         return (batch, oi) if return_indices else batch
 
@@ -318,15 +322,7 @@ class DeviceReplayBuffer:
         ``step`` advances as in ``traj_sample``."""
         from .masks import mask_rows
         from .mtm import form_settings, loss_tuple
-        B = int(self.traj_batch_size if batch_size is None else batch_size)
-        ti = si = pt = ps = None
-        dev = 0
-        if indices is not None:
-            B = int(np.prod(np.shape(indices[0])))
-            ti, pt, dev = self._index(indices[0], B)
-            si, ps, dev2 = self._index(indices[1], B)
-            if dev != dev2:
-                raise ValueError("trajectory indices and starts must both be on the host or both on the device")
+        B, pt, ps, dev, keep_i = self._segment_indices(indices, batch_size)
         flags, bits, keys = form_settings(form, capi.KEYS)
         e = None if eps is None else self._dev(eps, (B, self.sequence_length, self.A))
         rec = self._new(capi.MTM_LOSS_FLOATS)
@@ -337,7 +333,7 @@ class DeviceReplayBuffer:
                                                  capi._ptr(oi[0]), capi._ptr(oi[1]), self._stream()))
         if indices is None:
             self.step += 1
-        del ti, si, keep
+        del keep_i, keep
         out = loss_tuple(rec, keys)
         return (out, oi) if return_indices else out
 
@@ -351,15 +347,7 @@ class DeviceReplayBuffer:
         from .mtm import form_settings
         if grad.handle is not self.handle:  # (the library compares sizes and device only: another handle's weights would be differentiated)
             raise capi.M3pcError("mtm_grad: the DeviceMTMGrad object was created on another handle than this buffer's")
-        B = int(self.traj_batch_size if batch_size is None else batch_size)
-        ti = si = pt = ps = None
-        dev = 0
-        if indices is not None:
-            B = int(np.prod(np.shape(indices[0])))
-            ti, pt, dev = self._index(indices[0], B)
-            si, ps, dev2 = self._index(indices[1], B)
-            if dev != dev2:
-                raise ValueError("trajectory indices and starts must both be on the host or both on the device")
+        B, pt, ps, dev, keep_i = self._segment_indices(indices, batch_size)
         flags, bits, _ = form_settings(form, capi.KEYS)
         e = None if eps is None else self._dev(eps, (B, self.sequence_length, self.A))
         rec = self._new(capi.MTM_LOSS_FLOATS)
@@ -370,7 +358,7 @@ class DeviceReplayBuffer:
                                                  capi._ptr(oi[1]), self._stream()))
         if indices is None:
             self.step += 1
-        del ti, si, keep
+        del keep_i, keep
         return (rec, oi) if return_indices else rec
 
     def mtm_train(self, trainer, n_steps: int, masks, batch_size: Optional[int] = None, form: str = "finetune"):

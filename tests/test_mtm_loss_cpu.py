@@ -233,6 +233,14 @@ def test_every_bad_argument_is_refused_without_a_gpu(lib):
     assert replay(mode=2) == -1 and b"mode" in err()
     assert replay(ti=p) == -1 and b"come together" in err()
     assert replay() == -2 and b"holds no trajectory" in err()  # (M3PC_ESTATE: nothing stored, still no HIP call)
+    # what the raw and the replay entry refuse alike: the same code and, behind the entry's name, the same text
+    null_row = (C.c_void_p * 4)(p, p, None, p)
+    for kw in (dict(b=0), dict(b=5), dict(mk=bad), dict(mk=null_row), dict(flags=4), dict(flags=-1), dict(keys=16)):
+        rc_l, text_l = loss(**kw), err()
+        rc_r, text_r = replay(**kw), err()
+        assert rc_l == rc_r == -1, kw
+        assert text_l.startswith(b"m3pc_mtm_loss: ") and text_r.startswith(b"m3pc_mtm_loss_replay: "), (kw, text_l, text_r)
+        assert text_l[len(b"m3pc_mtm_loss: "):] == text_r[len(b"m3pc_mtm_loss_replay: "):] != b"", (kw, text_l, text_r)
     for r in (rb, other, short):
         assert lib.m3pc_replay_destroy(r) == 0
 

@@ -455,6 +455,132 @@ def test_refusals(golden, planner, fresh):
     assert lib.m3pc_mtm_opt_set_state(tr._o, C.byref(st)) == EINVAL and b"sched_step" in lib.m3pc_last_error()
 
 
+ENTRIES = ("m3pc_mtm_loss", "m3pc_mtm_loss_replay", "m3pc_mtm_grad", "m3pc_mtm_grad_replay", "m3pc_mtm_train_step", "m3pc_mtm_train")
+REPLAY_ENTRIES = tuple(e for e in ENTRIES if e.endswith("replay") or e == "m3pc_mtm_train")
+
+
+def _six_entries(lib, handle, tr, dims_T=T):
+    """-> call(entry, rb, b, mk, flags, keys): the same call through one of the six batch entries of the handle / of the trainer ``tr`` on
+    it, on zero-filled device rows, under the mask rows ``mk`` ((C.c_void_p * 4) of host bytes), eps given (raw) or library-drawn."""
+    dev, stream = handle.device, capi._stream(handle.device)
+    z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=dev)
+    n = 5  # (rows for max_batch + 1: a refused call reads none of them, a call that runs has batch <= 4)
+    s, a, r, v, e = z(n, dims_T, S), z(n, dims_T, A), z(n, dims_T, 1), z(n, dims_T, 1, dtype=torch.float64), z(n, dims_T, A)
+    rec, trec = z(capi.MTM_LOSS_FLOATS), z(3, dtype=torch.float64)
+    ptr = capi._ptr
+
+    def call(entry, rb=None, b=2, mk=None, flags=0, keys=FINETUNE_BITS):
+        if entry == "m3pc_mtm_loss":
+            return lib.m3pc_mtm_loss(handle._h, b, ptr(s), ptr(a), ptr(r), ptr(v), 1, mk, ptr(e), 0.1, flags, keys, capi.PREC_FP32, ptr(rec),
+                                     None, None, None, None, None, stream)
+        if entry == "m3pc_mtm_loss_replay":
+            return lib.m3pc_mtm_loss_replay(handle._h, rb, b, 0, None, None, 0, 5, 0, mk, None, 0.1, flags, keys, capi.PREC_FP32, ptr(rec),
+                                            None, None, stream)
+        if entry == "m3pc_mtm_grad":
+            return lib.m3pc_mtm_grad(tr.grad._g, b, ptr(s), ptr(a), ptr(r), ptr(v), 1, mk, ptr(e), 0.1, flags, keys, ptr(rec), stream)
+        if entry == "m3pc_mtm_grad_replay":
+            return lib.m3pc_mtm_grad_replay(tr.grad._g, rb, b, 0, None, None, 0, 5, 0, mk, None, 0.1, flags, keys, ptr(rec), None, None, stream)
+        if entry == "m3pc_mtm_train_step":
+            return lib.m3pc_mtm_train_step(tr._o, b, ptr(s), ptr(a), ptr(r), ptr(v), 1, mk, ptr(e), flags, keys, ptr(rec), ptr(trec), stream)
+        assert entry == "m3pc_mtm_train"
+        return lib.m3pc_mtm_train(tr._o, rb, 1, b, 0, 5, 0, mk, flags, keys, ptr(rec), ptr(trec), stream)
+
+    call.keep = (s, a, r, v, e, rec, trec)
+    return call
+
+
+def _mask_ptrs(*rows):
+    bufs = [None if row is None else C.create_string_buffer(bytes(bytearray(row)), len(row)) for row in rows]
+    return (C.c_void_p * 4)(*[None if b is None else C.addressof(b) for b in bufs]), bufs
+
+
+def test_the_six_batch_entries_refuse_alike(golden, planner, sd, fresh):
+    """One faulty call through m3pc_mtm_loss, _loss_replay, _grad, _grad_replay, _train_step and _train: the same code and, behind the
+    entry's name, the same text; the first of two faults is reported; a refusal leaves the gradient object's have_grad / consumed
+    state (probed with m3pc_mtm_opt_step, which refuses in both states used here) and ``replay.step`` where they were.  An all-hidden
+    mask set is refused by name in the four gradient and trainer entries, accepted by m3pc_mtm_loss_terms, and refused without the
+    entry's name by the two loss entries that run the forward (the plan lookup behind their tokenise launches refuses it)."""
+    tr = fresh(max_batch=4)  # (the handle's max_batch is 4 too: "max_batch=4" in every entry's text)
+    lib, err = tr.lib, tr.lib.m3pc_last_error
+    stream = capi._stream(tr.device)
+    call = _six_entries(lib, planner.handle, tr)
+    good, k0 = _mask_ptrs(*[[1, 0] * (T // 2)] * 4)
+    byte2, k1 = _mask_ptrs([1, 0] * (T // 2), [1, 0, 2, 0, 0, 0, 0, 0], [0] * T, [1] * T)
+    hidden, k2 = _mask_ptrs(*[[0] * T] * 4)
+    buf, _ = _filled_buffer(planner)
+    short, empty = C.c_void_p(), C.c_void_p()
+    assert lib.m3pc_replay_create(planner.handle._h, 4, 40, T - 1, 0, 0, C.byref(short)) == 0
+    assert lib.m3pc_replay_create(planner.handle._h, 4, 40, T, 0, 0, C.byref(empty)) == 0
+
+    def alike(entries, code, text, **kw):
+        for entry in entries:
+            kw.setdefault("rb", buf._rb)
+            kw.setdefault("mk", good)
+            rc, msg = call(entry, **kw), err()
+            assert rc == code and msg.startswith(entry.encode() + b": "), (entry, kw, rc, msg)
+            assert msg[len(entry) + 2:] == text, (entry, kw, msg)
+
+    def every_refusal(probe):
+        """Each shared refusal through the entries that can meet it; after each, m3pc_mtm_opt_step still answers ``probe``."""
+        for kw, code, text, entries in (
+                (dict(b=0), EINVAL, b"batch 0 outside [1, max_batch=4]", ENTRIES),
+                (dict(b=5), EINVAL, b"batch 5 outside [1, max_batch=4]", ENTRIES),
+                (dict(mk=byte2), EINVAL, b"mask byte 2 of 'actions' is 2, not 0 or 1", ENTRIES),
+                (dict(flags=4), EINVAL, b"unknown flag bits 0x4", ENTRIES),
+                (dict(keys=16), EINVAL, b"loss_keys 16 outside [0, 15]", ENTRIES),
+                (dict(b=0, flags=4), EINVAL, b"batch 0 outside [1, max_batch=4]", ENTRIES),  # two faults: the batch is reported
+                (dict(rb=short), EINVAL, b"the buffer (S 11, A 3, segment_length 7, device 0) does not fit the handle (11, 3, T 8, 0)", REPLAY_ENTRIES),
+                (dict(rb=empty), ESTATE, b"the buffer holds no trajectory", REPLAY_ENTRIES),
+                (dict(mk=hidden), EINVAL, b"mask keeps no token", ENTRIES[2:])):
+            alike(entries, code, text, **kw)
+            assert lib.m3pc_mtm_opt_step(tr._o, stream) == ESTATE and probe in err(), (kw, err())
+
+    try:
+        every_refusal(b"no gradient call was made")  # have_grad stays false
+        for entry in ENTRIES[:2]:  # as observed on the parent commit: M3PC_EINVAL from the plan lookup, no entry name in front
+            assert call(entry, rb=buf._rb, mk=hidden) == EINVAL and err() == b"mask keeps no token", (entry, err())
+        c = call.keep
+        four = (C.c_void_p * 4)(*[capi._ptr(t) for t in (c[0], c[1], c[2], c[2])])
+        one = torch.ones_like(c[4])
+        assert lib.m3pc_mtm_loss_terms(planner.handle._h, 2, capi._ptr(c[0]), capi._ptr(c[2]), capi._ptr(c[2]), capi._ptr(c[4]), capi._ptr(one),
+                                       four, hidden, capi._ptr(c[4]), 0.1, 0, FINETUNE_BITS, capi._ptr(c[5]), stream) == 0, err()
+        step0 = buf.step
+        for wrapper in (lambda: buf.mtm_loss(_g8(golden)[1], 0.1, batch_size=5), lambda: buf.mtm_grad(tr.grad, _g8(golden)[1], 0.1, batch_size=5),
+                        lambda: buf.mtm_train(tr, 2, _g8(golden)[1], batch_size=5)):
+            with pytest.raises(capi.M3pcError, match="batch 5 outside"):
+                wrapper()
+            assert buf.step == step0
+        batch, masks, eps = _g8(golden)
+        tr.grad.grad_record({k: v[:2] for k, v in batch.items()}, masks, 0.1, "finetune", eps[:2])
+        tr.opt_step()
+        every_refusal(b"already applied")  # consumed stays true
+
+        # a bare handle: the state refusals, behind every argument refusal
+        bare = capi.Handle(S, A, T, 64, 2, 2, 1, max_candidates=64, max_batch=4)
+        tr2 = buf2 = None
+        try:
+            tr2 = DeviceMTMTrainer(bare, 4, **HYPER)
+            buf2 = type(buf)(bare, planner.cfg, 4, 40, discount=0.99, seed=5)
+            buf2.append(np.zeros((1, 40, S), np.float32), np.zeros((1, 40, A), np.float32), np.zeros((1, 40), np.float32), np.zeros((1, 40)), [20])
+            call2 = _six_entries(lib, bare, tr2)
+            for entry in ENTRIES:
+                assert call2(entry, rb=buf2._rb, mk=good) == ESTATE and err() == entry.encode() + b": weights not loaded", (entry, err())
+            bare.load_weights(sd)
+            for entry in ENTRIES:
+                assert call2(entry, rb=buf2._rb, mk=good) == ESTATE and err() == entry.encode() + b": tokenizer 'states' not set", (entry, err())
+        finally:
+            torch.cuda.synchronize()
+            for x in (buf2, tr2, bare):
+                if x is not None:
+                    x.close()
+    finally:
+        torch.cuda.synchronize()
+        buf.close()
+        for rb in (short, empty):
+            assert lib.m3pc_replay_destroy(rb) == 0
+    del k0, k1, k2
+
+
 # ------------------------------------------------------------------------------------------------ the C example
 def test_mtm_train_example(planner, golden, fresh, tmp_path):
     """examples/mtm_train.c compiled with gcc -Wall -Werror against include/m3pc_hip.h, linked to the built library and run on a handle
