@@ -5,7 +5,8 @@
  * through the whole model; m3pc_mtm_grad_export then hands out the gradients the caller names, in the torch layout of their
  * parameters.  The batch never leaves the device.  The optimizer is the caller's.
  *
- * The model differentiated is the eval-mode one: no dropout (include/m3pc_hip.h).
+ * The model differentiated here is the eval-mode one; m3pc_mtm_grad_set_dropout(g, p, seed, draw) before the call would switch on the
+ * training-mode model's dropout under the library's own keep-mask stream (include/m3pc_hip.h; examples/mtm_train.c sets it).
  *
  *   gcc -O2 -Wall -Werror -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include -c examples/mtm_grad.c
  *   (link with -L<dir of libm3pc_hip.so> -l:libm3pc_hip.so -lamdhip64 -lm)

@@ -5,7 +5,9 @@
  * temperature, steps AdamW over every parameter under the cosine schedule and steps the float64 log_temperature -- and leaves the
  * handle's weights, and every form the plan step reads, moved.  Nothing crosses the host until the records are read back.
  *
- * The model trained is the eval-mode one: no dropout (include/m3pc_hip.h).
+ * mtm_train_example trains the eval-mode model; mtm_train_example_dropout(..., p, dropout_seed) the training-mode one, with
+ * dropout p at the four sites of every transformer layer under the library's own keep-mask stream (include/m3pc_hip.h: not
+ * torch's generator): step i of the call drops under draw i.
  *
  *   gcc -O2 -Wall -Werror -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include -c examples/mtm_train.c
  *   (link with -L<dir of libm3pc_hip.so> -l:libm3pc_hip.so -lamdhip64 -lm)
@@ -50,8 +52,8 @@ typedef struct mtm_train_io {
     long long weight_numel;
 } mtm_train_io;
 
-/* -> 0, or a negative code (the message on stderr) */
-int mtm_train_example(mtm_train_io* io, int device, void* stream) {
+/* -> 0, or a negative code (the message on stderr).  dropout_p 0: the eval-mode model. */
+int mtm_train_example_dropout(mtm_train_io* io, int device, void* stream, double dropout_p, unsigned long long dropout_seed) {
     m3pc_handle* h = 0;
     m3pc_replay* rb = 0;
     struct m3pc_mtm_grad* g = 0;
@@ -82,6 +84,8 @@ int mtm_train_example(mtm_train_io* io, int device, void* stream) {
     if (rc == 0) rc = m3pc_replay_append(rb, io->n_traj, io->obs, io->act, io->rew, io->val, io->lens, 0, stream);
     if (rc == 0) rc = m3pc_mtm_grad_create(h, io->batch, &g);
     if (rc == 0) rc = m3pc_mtm_opt_create(g, &a, &opt);
+    /* host state of the gradient object: every gradient call from here on uses the current draw (0, 1, 2 below) and advances it */
+    if (rc == 0 && dropout_p > 0.0) rc = m3pc_mtm_grad_set_dropout(g, dropout_p, dropout_seed, 0);
     /* the fine-tuning form: the clip, no l2 norm, loss_keys = states alone (the rewards / returns heads are left alone, as torch's
      * AdamW leaves parameters without a gradient) */
     if (rc == 0)
@@ -118,3 +122,5 @@ int mtm_train_example(mtm_train_io* io, int device, void* stream) {
     m3pc_destroy(h);
     return rc;
 }
+
+int mtm_train_example(mtm_train_io* io, int device, void* stream) { return mtm_train_example_dropout(io, device, stream, 0.0, 0); }

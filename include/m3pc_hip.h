@@ -1087,7 +1087,21 @@ int m3pc_mtm_loss_replay(m3pc_handle* h, m3pc_replay* rb, int batch, int mode, c
  * of the model's state_dict except the buffer pos_embed.  Held constant: the tokenised targets (the l2-normalised ones too), the clipped
  * action and its z, entropy_reg, the masks.  eps is the caller's; u = mu + std eps is differentiated through mu and std (rsample), and std
  * = exp(-5 + 3.5 (tanh(.) + 1)) through the log_std Linear.
- *   THE MODEL IS THE EVAL-MODE ONE: NO DROPOUT.  (The shipped configs train with dropout 0.1; drawing keep-masks is not in the library.)
+ *   dropout      the model is the eval-mode one until m3pc_mtm_grad_set_dropout(g, p, seed, draw) with p > 0 switches on the four dropout
+ *                sites of every nn.TransformerEncoderLayer(norm_first=True) of the training-mode model (the shipped configs train with
+ *                dropout 0.1): the attention probabilities, dropout1 behind out_proj, the feed-forward's dropout behind the GELU and
+ *                dropout2 behind linear2; the embeddings and the output heads have none.  An element is kept iff its word of the
+ *                library's Philox4x32-10 stream is >= floor(p 2^32), and a kept element is multiplied by (float)(1 / (1 - p)); the stream
+ *                is a pure function of (seed, draw, site, element) -- THE LIBRARY'S OWN, NOT TORCH'S (counter layout, sites and the
+ *                arithmetic order: m3pc_amd/csrc/mtm_grad.h).  Every gradient call -- m3pc_mtm_grad, m3pc_mtm_grad_replay,
+ *                m3pc_mtm_train_step and each step of m3pc_mtm_train -- uses the object's current draw and then advances it by one; a
+ *                refused call does not.  n steps of one m3pc_mtm_train use the draws d .. d + n - 1 and equal n single calls bit for
+ *                bit.  The record, and the entropy the temperature step reads, come from the dropped forward (the reference's
+ *                train/loss).  m3pc_mtm_loss* stays the eval-mode loss.  p == 0 switches dropout off: no launch differs from an object
+ *                that never had it set; a p below 2^-32 has threshold 0 and is treated the same (nothing drops, the draw does not
+ *                advance).  _set / _get_dropout are host-only: no HIP call, no wait; the outputs of _get are optional.
+ *                Refused with M3PC_EINVAL: a null g; p not finite or outside [0, 1); and, by the gradient calls while p > 0, a model of
+ *                more than 64 layers or a batch whose largest site has more than 2^32 groups of four elements.
  *   A key outside loss_keys contributes nothing: with loss_keys = 1 the rewards and returns heads get exact zeros (the reference leaves
  *   .grad = None there).  Structural zeros are exact zeros: the mask token of a fully visible key; the encoder embedding and the
  *   encoder_per_dim_encoding of a fully hidden key.  When total is NaN (no hidden action timestep, an l2 norm of 0) the call returns
@@ -1124,6 +1138,8 @@ int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, in
                          const float* eps, float entropy_reg, int flags, int loss_keys, float* record, int* out_traj, int* out_start,
                          void* stream);
 int m3pc_mtm_grad_export(struct m3pc_mtm_grad* g, const m3pc_named_tensor* tensors, int n, void* stream);
+int m3pc_mtm_grad_set_dropout(struct m3pc_mtm_grad* g, double p, unsigned long long seed, unsigned long long draw);
+int m3pc_mtm_grad_get_dropout(struct m3pc_mtm_grad* g, double* p, unsigned long long* seed, unsigned long long* next_draw);
 
 /* THE OPTIMIZERS OF THE MASKED-TRAJECTORY MODEL: what Learner.mtm_update (finetune_omtm/learner.py:506-538) does behind loss.backward(),
  * on the device and on the HANDLE'S OWN WEIGHTS -- AdamW over every parameter in the two groups of omtm.configure_optimizers

@@ -780,6 +780,46 @@ typedef struct m3pc_debug_mg_loss_bwd_args {
     int* picked;
 } m3pc_debug_mg_loss_bwd_args;
 int m3pc_debug_mg_loss_bwd(const m3pc_debug_mg_loss_bwd_args* a);
+/* ---- the kernels of csrc/mtm_dropout.hip: the product and the attention kernels above with the keep masks of a dropout site, dY = dX k
+ * over rows, and the mask itself (csrc/mtm_grad.h, DROPOUT: sites, counter layout, arithmetic order).  The hooks go through the same
+ * launchers: with p == 0 (or p < 2^-32, which drops nothing) the launch is the one without dropout and reports its id.
+ * MTM-dropout kernel ids (tests/test_mtm_dropout_kernel_edges_gpu.py reaches every id of this list):
+ *   16 mg_gemm_drop_kernel;  17 mg_attn_fwd_drop_kernel;  18 mg_attn_col_drop_kernel;  19 mg_attn_row_drop_kernel;
+ *   20 mg_drop_rows_kernel;  21 mg_keep_kernel
+ * (end of the MTM-dropout kernel ids) */
+/* a site: an element is kept iff its Philox word of (seed, draw, site) is >= floor(p 2^32); kept elements are multiplied by
+ * (float)(1 / (1 - p)).  Refused by every hook: p not finite or outside [0, 1), site outside [0, 255], more than 2^32 quads. */
+typedef struct m3pc_debug_mg_drop {
+    double p;
+    unsigned long long seed, draw;
+    int site;
+} m3pc_debug_mg_drop;
+/* the product with the mask of a matrix site of extent (M, N) on element (m, n): ((acc + bias + bias2) + pos) k + res; with gelu_out
+ * C stays unmasked and gelu_out = gelu(C) k; with gelu_aux (acc k) gelu'(aux).  Refused too: splitk with p >= 2^-32. */
+typedef struct m3pc_debug_mg_gemm_drop_args {
+    m3pc_debug_mg_gemm_args g;
+    m3pc_debug_mg_drop drop;
+} m3pc_debug_mg_gemm_drop_args;
+int m3pc_debug_mg_gemm_drop(const m3pc_debug_mg_gemm_drop_args* a);
+/* the attention kernels with site 0 of a layer.  which 0: P keeps the undropped probability and carries "dropped" in its sign bit, O =
+ * (P k) V; 1: dV = (|P| k)^T dO; 2: dP = (dO V^T) k, dS = |P| (dP - sum dP |P|) over P, dQ; 3: dK, the launch without dropout. */
+typedef struct m3pc_debug_mg_attn_drop_args {
+    m3pc_debug_mg_attn_args a;
+    m3pc_debug_mg_drop drop;
+} m3pc_debug_mg_attn_drop_args;
+int m3pc_debug_mg_attention_drop(const m3pc_debug_mg_attn_drop_args* a);
+/* dY[r][c] = dX[r][c] k(r, c) over (R, C) compact rows (dY may be dX).  Refused too: a null dX / dY, R / C < 1, R C beyond int, p < 2^-32. */
+typedef struct m3pc_debug_mg_drop_rows_args {
+    const float* dX;
+    float* dY;
+    int R, C;
+    m3pc_debug_mg_drop drop;
+    void* stream;
+    int* picked;
+} m3pc_debug_mg_drop_rows_args;
+int m3pc_debug_mg_drop_rows(const m3pc_debug_mg_drop_rows_args* a);
+/* keep[r C + c] = 0 / 1 (device bytes): attention 0, the matrix site of extent (R, C); 1, R = B n_head L attention rows of C = L keys */
+int m3pc_debug_mtm_keep(const m3pc_debug_mg_drop* d, int attention, long long R, int C, unsigned char* keep, void* stream, int* picked);
 /* ---- the kernels of csrc/iql.hip (the IQL trainer), each alone on caller tensors, through the launchers m3pc_iql_train_step,
  * _evaluate, _load, _export and _publish_critic themselves use (csrc/iql.h: iql_launch_*): grid geometry, the tile count of the
  * gradient grid and the block count of the copies are the production ones.  The caller owns every buffer; no hook creates a trainer.

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libm3pc_hip.so")
 SOURCES = ["gemm.hip", "gemm_x3.hip", "gemm_glds.hip", "gemm_big.hip", "gemm_line.hip", "gemm_f32_direct.hip", "block_fused.hip", "attn.hip",
            "attn_bf16.hip", "elementwise.hip", "select.hip", "refine.hip", "m3pc_plans.hip", "m3pc_passes.hip", "m3pc.hip", "m3pc_certified.hip",
-           "episodes.hip", "replay.hip", "iql.hip", "mtm_batch.hip", "mtm_loss.hip", "mtm_grad.hip", "mtm_opt.hip"]
+           "episodes.hip", "replay.hip", "iql.hip", "mtm_batch.hip", "mtm_loss.hip", "mtm_grad.hip", "mtm_dropout.hip", "mtm_opt.hip"]
 # the lab build (libm3pc_hip_lab.so, `python -m m3pc_amd.build --lab`, used by tools/ with M3PC_LIB=...): adds the experimental
 # GEMM tilings, the timing variants of block_fused.hip, the M3PC_GEMM_VARIANT environment override (-DM3PC_LAB) and the kernel-level
 # hooks of include/m3pc_hip_debug.h (m3pc_debug.hip)
@@ -40,7 +40,7 @@ def _stale(target: str, deps) -> bool:
 
 def build_library(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, n) for n in ("kernels.h", "device_util.h", "gemm_epilogue.h", "gemm_stage_asm.h", "m3pc_internal.h", "cert_resolve.h", "philox.h", "stage.h", "episodes.h", "iql.h", "mtm_batch.h", "mtm_loss.h", "mtm_grad.h", "mtm_opt.h", "exports.map")] + \
+    headers = [os.path.join(CSRC, n) for n in ("kernels.h", "device_util.h", "gemm_epilogue.h", "gemm_stage_asm.h", "m3pc_internal.h", "cert_resolve.h", "philox.h", "stage.h", "episodes.h", "iql.h", "mtm_batch.h", "mtm_loss.h", "mtm_grad.h", "mtm_grad_body.h", "mtm_opt.h", "exports.map")] + \
               [os.path.join(os.path.dirname(HERE), "include", n) for n in ("m3pc_hip.h", "m3pc_hip_debug.h")]
     objdir = os.path.join(CSRC, "build_lab" if lab else "build")
     os.makedirs(objdir, exist_ok=True)

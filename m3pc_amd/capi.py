@@ -59,6 +59,7 @@ EXPORTS = (
     "m3pc_iql_train_step", "m3pc_iql_train", "m3pc_iql_publish_critic", "m3pc_iql_evaluate",
     "m3pc_mtm_loss_terms", "m3pc_mtm_loss", "m3pc_mtm_loss_replay",
     "m3pc_mtm_grad_create", "m3pc_mtm_grad_destroy", "m3pc_mtm_grad", "m3pc_mtm_grad_replay", "m3pc_mtm_grad_export",
+    "m3pc_mtm_grad_set_dropout", "m3pc_mtm_grad_get_dropout",
     "m3pc_mtm_opt_create", "m3pc_mtm_opt_destroy", "m3pc_mtm_lr", "m3pc_mtm_opt_decays", "m3pc_mtm_opt_step", "m3pc_mtm_train_step",
     "m3pc_mtm_train", "m3pc_mtm_opt_export", "m3pc_mtm_opt_load", "m3pc_mtm_weights_export", "m3pc_mtm_opt_get_state",
     "m3pc_mtm_opt_set_state",
@@ -261,6 +262,8 @@ def load_library(path: Optional[str] = None):
         "m3pc_mtm_grad": [vp, i, vp, vp, vp, vp, i, C.POINTER(vp), vp, f, i, i, vp, vp],
         "m3pc_mtm_grad_replay": [vp, vp, i, i, vp, vp, i, C.c_ulonglong, C.c_ulonglong, C.POINTER(vp), vp, f, i, i, vp, vp, vp, vp],
         "m3pc_mtm_grad_export": [vp, C.POINTER(NamedTensor), i, vp],
+        "m3pc_mtm_grad_set_dropout": [vp, C.c_double, C.c_ulonglong, C.c_ulonglong],
+        "m3pc_mtm_grad_get_dropout": [vp, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)],
         "m3pc_mtm_opt_create": [vp, C.POINTER(MtmOptArgs), C.POINTER(vp)],
         "m3pc_mtm_opt_destroy": [vp],
         "m3pc_mtm_lr": [C.POINTER(MtmOptArgs), ll, C.POINTER(d)],

@@ -1145,7 +1145,17 @@ static long long mg_op_last(const m3pc_debug_mg_op& o, int outer, int K) {
     return ro * o.s_o + rk * o.s_k;
 }
 
-int m3pc_debug_mg_gemm(const m3pc_debug_mg_gemm_args* a) {
+// a site of the hooks with keep masks (m3pc_debug_mg_drop): refused, or the launch's DropG (thr == 0: off)
+static int mg_drop_fill(const m3pc_debug_mg_drop& d, unsigned int array, unsigned long long quads, const char* who, DropG* out) {
+    if (!std::isfinite(d.p) || d.p < 0.0 || d.p >= 1.0) return fail(M3PC_EINVAL, "%s: dropout p %g is not a finite number in [0, 1)", who, d.p);
+    if (d.site < 0 || d.site > 255) return fail(M3PC_EINVAL, "%s: dropout site %d outside [0, 255]", who, d.site);
+    if (quads > (1ull << 32)) return fail(M3PC_EINVAL, "%s: the site has more than 2^32 quads (%llu)", who, quads);
+    *out = mg_drop_make(d.p, d.seed, d.draw);
+    out->c3 = array | (unsigned int)d.site << 8;
+    return 0;
+}
+
+static int mg_gemm_hook(const m3pc_debug_mg_gemm_args* a, const m3pc_debug_mg_drop* drop) {
     if (!a) return fail(M3PC_EINVAL, "debug_mg_gemm: null arguments");
     if (a->picked) a->picked[0] = a->picked[1] = 0;
     if (!a->A.p || !a->B.p || !a->C) return fail(M3PC_EINVAL, "debug_mg_gemm: A, B and C are required");
@@ -1178,9 +1188,18 @@ int m3pc_debug_mg_gemm(const m3pc_debug_mg_gemm_args* a) {
     p.gelu_out = a->gelu_out;
     p.accumulate = a->accumulate ? 1 : 0;
     p.splitk = a->splitk ? 1 : 0;
+    if (drop) {
+        CHK(mg_drop_fill(*drop, MG_DROP_MATRIX, (unsigned long long)((a->M + 3) / 4) * a->N, "debug_mg_gemm_drop", &p.drop));
+        if (p.drop.thr && a->splitk) return fail(M3PC_EINVAL, "debug_mg_gemm_drop: no dropout form of the split-k product");
+    }
     mg_begin(a->picked);
     mg_launch_gemm(p, (hipStream_t)a->stream);
     return mg_done(a->picked, "debug_mg_gemm");
+}
+int m3pc_debug_mg_gemm(const m3pc_debug_mg_gemm_args* a) { return mg_gemm_hook(a, nullptr); }
+int m3pc_debug_mg_gemm_drop(const m3pc_debug_mg_gemm_drop_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_gemm_drop: null arguments");
+    return mg_gemm_hook(&a->g, &a->drop);
 }
 
 int m3pc_debug_mg_layernorm(const m3pc_debug_mg_ln_args* a) {
@@ -1247,7 +1266,7 @@ int m3pc_debug_mg_colsum(const m3pc_debug_mg_colsum_args* a) {
     return mg_done(a->picked, "debug_mg_colsum");
 }
 
-int m3pc_debug_mg_attention(const m3pc_debug_mg_attn_args* a) {
+static int mg_attention_hook(const m3pc_debug_mg_attn_args* a, const m3pc_debug_mg_drop* drop) {
     if (!a) return fail(M3PC_EINVAL, "debug_mg_attention: null arguments");
     if (a->picked) a->picked[0] = a->picked[1] = 0;
     if (a->which < 0 || a->which > 3) return fail(M3PC_EINVAL, "debug_mg_attention: which %d outside [0, 3]", a->which);
@@ -1272,6 +1291,8 @@ int m3pc_debug_mg_attention(const m3pc_debug_mg_attn_args* a) {
     p.nh = a->nh;
     p.hd = a->hd;
     p.scale = a->scale;
+    if (drop)
+        CHK(mg_drop_fill(*drop, MG_DROP_ATTN, (unsigned long long)a->B * a->nh * a->L * ((a->L + 3) / 4), "debug_mg_attention_drop", &p.drop));
     hipStream_t st = (hipStream_t)a->stream;
     mg_begin(a->picked);
     if (a->which == 0)
@@ -1281,6 +1302,37 @@ int m3pc_debug_mg_attention(const m3pc_debug_mg_attn_args* a) {
     else
         mg_launch_attn_col(p, a->which == 1 ? 0 : 1, st);
     return mg_done(a->picked, "debug_mg_attention");
+}
+int m3pc_debug_mg_attention(const m3pc_debug_mg_attn_args* a) { return mg_attention_hook(a, nullptr); }
+int m3pc_debug_mg_attention_drop(const m3pc_debug_mg_attn_drop_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_attention_drop: null arguments");
+    return mg_attention_hook(&a->a, &a->drop);
+}
+
+int m3pc_debug_mg_drop_rows(const m3pc_debug_mg_drop_rows_args* a) {
+    if (!a) return fail(M3PC_EINVAL, "debug_mg_drop_rows: null arguments");
+    if (a->picked) a->picked[0] = a->picked[1] = 0;
+    if (!a->dX || !a->dY) return fail(M3PC_EINVAL, "debug_mg_drop_rows: dX and dY are required");
+    if (a->R < 1 || a->C < 1 || (long long)a->R * a->C > MG_INT_MAX) return fail(M3PC_EINVAL, "debug_mg_drop_rows: R %d, C %d", a->R, a->C);
+    DropRowsG p = {a->dX, a->dY, a->R, a->C, {}};
+    CHK(mg_drop_fill(a->drop, MG_DROP_MATRIX, (unsigned long long)((a->R + 3) / 4) * a->C, "debug_mg_drop_rows", &p.drop));
+    if (!p.drop.thr) return fail(M3PC_EINVAL, "debug_mg_drop_rows: p %g drops nothing: m3pc_mtm_grad makes no such launch", a->drop.p);
+    mg_begin(a->picked);
+    mg_launch_drop_rows(p, (hipStream_t)a->stream);
+    return mg_done(a->picked, "debug_mg_drop_rows");
+}
+
+int m3pc_debug_mtm_keep(const m3pc_debug_mg_drop* d, int attention, long long R, int C, unsigned char* keep, void* stream, int* picked) {
+    if (picked) picked[0] = picked[1] = 0;
+    if (!d || !keep) return fail(M3PC_EINVAL, "debug_mtm_keep: null argument");
+    if (R < 1 || C < 1 || R > (1ll << 40)) return fail(M3PC_EINVAL, "debug_mtm_keep: R %lld, C %d", R, C);
+    DropG g;
+    const unsigned long long quads = attention ? (unsigned long long)R * ((C + 3) / 4) : (unsigned long long)((R + 3) / 4) * C;
+    CHK(mg_drop_fill(*d, attention ? MG_DROP_ATTN : MG_DROP_MATRIX, quads, "debug_mtm_keep", &g));
+    if (R > MG_INT_MAX / C) return fail(M3PC_EINVAL, "debug_mtm_keep: R %lld x C %d bytes beyond int", R, C);
+    mg_begin(picked);
+    mg_launch_keep(g, R, C, keep, (hipStream_t)stream);
+    return mg_done(picked, "debug_mtm_keep");
 }
 
 int m3pc_debug_mg_tokens(const m3pc_debug_mg_tokens_args* a) {

@@ -1,5 +1,6 @@
 // The gradient of the masked-trajectory loss (include/m3pc_hip.h: m3pc_mtm_grad*): Learner.compute_mtm_loss / omtm.forward_loss and
-// loss.backward() through the whole model on the device, one gradient tensor per parameter.  Eval-mode model: no dropout.
+// loss.backward() through the whole model on the device, one gradient tensor per parameter.  Eval-mode model unless
+// m3pc_mtm_grad_set_dropout switched the training-mode one on: DROPOUT, below.
 //
 // LAUNCHES of one call (n = layers of a stack; a "product" is one mg_gemm_kernel launch):
 //   forward   tokenize x4; mg_embed_kernel (encoder rows); per layer: LayerNorm, Q|K|V product, mg_attn_fwd_kernel (keeps the
@@ -33,6 +34,31 @@
 //   float64    7 T doubles (the returns of a replay draw, the six row sums of the record)
 // in all 4 [n L (8 d + 2 ff + 4 + n_head L) + L (12 d + ff + 4) + T (11 d + 4 S + 8 A + 13)] + 56 T bytes, each buffer rounded up to 256
 // bytes; and, once per object, the gradient of every parameter and the column-sum partials (2 ceil(max_batch L / 64) max(3 d, ff) doubles).
+//
+// DROPOUT (m3pc_mtm_grad_set_dropout, p > 0; kernels in mtm_dropout.hip, device bodies in mtm_grad_body.h).  The four sites of a
+// training-mode nn.TransformerEncoderLayer(norm_first=True), site id 4 layer + s, layers counted encoder first as `lay` is:
+//   s 0  attention probabilities (B, nh, L, L)   O = (P * k) V;  dV = (P * k)^T dO;  dP = (dO V^T) * k, softmax backward on the undropped P
+//   s 1  dropout1, out_proj output (R, d)        X1 = Xin + (O Wo^T + b) * k;  dY = dX * k feeds the dX and dW products and the bias sum
+//   s 2  the FFN's dropout (R, ff)               Fact = gelu(Fpre) * k (stored dropped);  dF = ((dX W2) * k) gelu'(Fpre)
+//   s 3  dropout2, linear2 output (R, d)         Xout = X1 + (Fact W2^T + b) * k;  backward as s 1
+// k is scale = (float)(1.0 / (1.0 - p)) where the element is kept, 0 where it is dropped; kept iff its Philox word >= thr,
+// thr = (uint32) floor(p 2^32), both computed on the host in double.  The keep-mask stream is a pure function of (seed, draw, site,
+// logical element) (philox.h: key = seed, counter = (quad, draw lo, draw hi, array | site << 8)):
+//   matrix sites (array 5)   quad = (row >> 2) C + col, word = row & 3; row: the row of the site's (R, C) activation
+//   attention (array 6)      quad = ((b nh + h) L + i) ceil(L / 4) + (j >> 2), word = j & 3
+// so nothing depends on batch, max_batch, the tiling or the workspace.  ARITHMETIC ORDER, exactly:
+//   product, forward form      v = ((acc + (bias + bias2)) + pos);  v = kept ? __fmul_rn(v, scale) : 0;  v = v + res
+//   product with gelu_out      C = v unmasked;  gelu_out = kept ? __fmul_rn(gelu(v), scale) : 0
+//   product with gelu_aux      v = kept ? __fmul_rn(acc, scale) : 0;  v = v * gelu'(gelu_aux)
+//   mg_drop_rows_kernel        dY = kept ? __fmul_rn(dX, scale) : 0
+//   attention forward          the stored P keeps the undropped probability and carries "dropped" in its sign bit (P >= 0, so the bit
+//                              is free); O sums (kept ? __fmul_rn(P, scale) : 0) V, keys ascending
+//   attention backward         dV sums (kept ? __fmul_rn(|P|, scale) : 0) dO, queries ascending;  dP = kept ? __fmul_rn(dO . V_j, scale) : 0,
+//                              then dS = |P| (dP - sum_j dP |P|) over P as without dropout; the dK launch is the one without dropout
+// One Philox call serves the four accumulators a lane holds of one column (rows 4 q .. 4 q + 3), and four keys of one attention row:
+// lane q of the row's wavefront draws quad q once and leaves the four bits in LDS.  No new buffer: dY of dropout2 goes to dO (free
+// until the out_proj dX product writes it) and dY of dropout1 to dH (free between the LayerNorm backward that read it and the Q|K|V dX
+// product).  Refused before any HIP call: more than 64 layers, a site of more than 2^32 quads.  With p == 0 no launch differs.
 #pragma once
 #include "m3pc_internal.h"
 
@@ -46,6 +72,16 @@ struct RMap {
 __host__ __device__ __forceinline__ long long rmap(const RMap& m, int r) {
     return m.rpg == 0 ? (long long)r : (long long)(r / m.rpg) * m.gstride + (r % m.rpg) + m.off;
 }
+
+// a dropout site of one launch (DROPOUT above); thr == 0: off
+struct DropG {
+    unsigned int thr;
+    float scale;
+    unsigned int k0, k1;  // seed lo, hi
+    unsigned int d0, d1;  // draw lo, hi
+    unsigned int c3;      // array | site << 8
+};
+constexpr unsigned int MG_DROP_MATRIX = 5, MG_DROP_ATTN = 6;  // (philox.h: the arrays)
 
 // C[m][n] = sum_k A(m, k) B(k, n): element (o, k) of an operand is p[row(o) * s_o + k * s_k], or p[o * s_o + row(k) * s_k] with map_k
 struct GOp {
@@ -69,6 +105,7 @@ struct GemmG {
     float* gelu_out;        // gelu_out[row(m) * ldc + n] = gelu(C)
     int accumulate;         // C += instead of C =
     int splitk;             // the four wavefronts of a workgroup share a tile (mg_gemm_kernel<true>)
+    DropG drop;             // the site's keep mask on element (m, n) of an (M, N) activation (never with splitk)
 };
 
 struct LnG {
@@ -106,6 +143,15 @@ struct AttG {
     float* dQKV;       // (B L, 3 d)
     int B, L, d, nh, hd;
     float scale;
+    DropG drop;        // site 0 of the layer: forward, dV and the row kernel
+};
+
+// dY[r][c] = dX[r][c] * k(r, c) over (R, C) compact rows
+struct DropRowsG {
+    const float* dX;
+    float* dY;
+    int R, C;
+    DropG drop;
 };
 
 struct EmbG {
@@ -149,6 +195,17 @@ void mg_launch_scatter(const EmbG& p, hipStream_t st);
 void mg_launch_tokv(const EmbG& p, int k, float* out, hipStream_t st);
 void mg_launch_std(const float* ls, float* sd, long long n, hipStream_t st);
 void mg_launch_loss_bwd(const LossBwdG& p, hipStream_t st);
+// mtm_dropout.hip: what the launchers above call when p.drop.thr != 0, and the two kernels without a counterpart
+void mg_launch_gemm_drop(const GemmG& p, hipStream_t st);
+void mg_launch_attn_fwd_drop(const AttG& p, hipStream_t st);
+void mg_launch_attn_col_drop(const AttG& p, hipStream_t st);  // (dV only)
+void mg_launch_attn_row_drop(const AttG& p, hipStream_t st);
+void mg_launch_drop_rows(const DropRowsG& p, hipStream_t st);
+// keep[r * C + c] = 0 / 1 of a matrix site (array 5: extent (R, C)) or of attention (array 6: R = B nh L rows of C = L keys)
+void mg_launch_keep(const DropG& d, long long R, int C, unsigned char* keep, hipStream_t st);
+// thr, scale and the key / draw words of (p, seed, draw); c3 is left 0 for the caller to set per site.  (The limits of a gradient
+// call -- layers, quads -- are checked by mg_precheck[_replay], in mtm_grad.hip.)
+DropG mg_drop_make(double p, unsigned long long seed, unsigned long long draw);
 }  // namespace m3pc
 
 // ------------------------------------------------------------------------------------------------ the object
@@ -179,6 +236,9 @@ struct m3pc_mtm_grad {
     float *Hh[3], *st_h[3], *Hpre[3], *Hact[3], *pred[3], *mu, *ls, *sd;
     float *dX, *dH, *dQKV, *dF, *dO, *dpred[3], *dmu, *dls, *dh1, *dh2, *rec;
     double* colpart;
+    // dropout (host state; DROPOUT above): every gradient call with drop_p > 0 uses drop_draw and advances it by one
+    double drop_p = 0.0;
+    unsigned long long drop_seed = 0, drop_draw = 0;
 };
 
 namespace m3pc {

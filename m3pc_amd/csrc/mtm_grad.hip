@@ -1,120 +1,23 @@
 // The gradient of the masked-trajectory loss (include/m3pc_hip.h: m3pc_mtm_grad*).  mtm_grad.h states the launches, what the forward
-// keeps, the reduction orders and the bytes.  fp32 only; the eval-mode model (no dropout).
+// keeps, the reduction orders, the bytes and the dropout sites.  fp32 only.  The kernels with keep masks: mtm_dropout.hip.
 #include <stdint.h>
 
 #include "device_util.h"
 #include "iql.h"
 #include "mtm_loss.h"
 #include "mtm_grad.h"
+#include "mtm_grad_body.h"
 
 namespace m3pc {
 namespace {
 
 typedef unsigned long long u64;
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MG_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#else
-#define MG_MFMA(a, b, c) ((void)(a), (void)(b), (c))
-#endif
-
 // ------------------------------------------------------------------------------------------------ the product
-// C[m][n] = sum_k A(m, k) B(k, n) (GemmG, mtm_grad.h)
-__device__ __forceinline__ float gelu_grad_exact(float x) {
-    const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-    const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
-    return cdf + x * pdf;
-}
-
-// One wavefront per 32 x 32 tile of C.  MFMA operand a: lane holds A(m = lane & 31, k = lane >> 5); b: B(k = lane >> 5, n = lane & 31);
-// accumulator i is row 8 (i / 4) + 4 (lane >> 5) + i % 4, column lane & 31.  K in ascending blocks of 16: step u of a block multiplies
-// k = 8 (u / 4) + u % 4 (lower lane half) and that + 4 (upper half); the operands of the next block are loaded ahead of the eight MFMAs of
-// this one, four consecutive k per 16-byte load where the operand is k-contiguous and aligned (vec).
-// SPLIT (the dW form, K = rows: few tiles, long K): the four wavefronts of a workgroup share ONE tile, wavefront w taking the k
-// blocks w, w + 4, ...; the partial tiles of wavefronts 1, 2, 3 go through LDS and wavefront 0 adds them in that order.
-__device__ __forceinline__ void mg_load8(const GOp& op, const float* base, bool o_ok, int k0, int lh, int K, float* v) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int k = k0 + 8 * h + 4 * lh;
-        if (op.vec && o_ok && k + 3 < K) {
-            const f32x4 x = *(const f32x4*)(base + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[4 * h + j] = x[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int kk = k + j;
-                const bool ok = o_ok && kk < K;
-                const long long kr = op.map_k && ok ? rmap(op.map, kk) : (long long)kk;
-                v[4 * h + j] = ok ? base[kr * op.s_k] : 0.f;
-            }
-        }
-    }
-}
-
+// C[m][n] = sum_k A(m, k) B(k, n) (GemmG, mtm_grad.h); the body, with its tiling and its k order: mtm_grad_body.h
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void mg_gemm_kernel(GemmG p) {
-    __shared__ float red[SPLIT ? 3 * 1024 : 1];
-    const int lane = threadIdx.x & 63, l31 = lane & 31, lh = lane >> 5, wv = threadIdx.x >> 6;
-    const int tiles_n = (p.N + 31) >> 5, tiles_m = (p.M + 31) >> 5;
-    const long long w = SPLIT ? (long long)blockIdx.x : (long long)blockIdx.x * 4 + wv;
-    if (w >= (long long)tiles_m * tiles_n) return;  // (SPLIT: the grid is the tile count, whole workgroups leave)
-    const int tm = (int)(w / tiles_n), tn = (int)(w % tiles_n);
-    const int m = 32 * tm + l31, n = 32 * tn + l31;
-    const bool m_ok = m < p.M, n_ok = n < p.N;
-    const float* pa = p.A.p + (m_ok ? (p.A.map_k ? (long long)m : rmap(p.A.map, m)) * p.A.s_o : 0);
-    const float* pb = p.B.p + (n_ok ? (p.B.map_k ? (long long)n : rmap(p.B.map, n)) * p.B.s_o : 0);
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    const int kstep = SPLIT ? 64 : 16, kbeg = SPLIT ? 16 * wv : 0;
-    float a[8], b[8], a2[8], b2[8];
-    if (kbeg < p.K) {
-        mg_load8(p.A, pa, m_ok, kbeg, lh, p.K, a);
-        mg_load8(p.B, pb, n_ok, kbeg, lh, p.K, b);
-    }
-    for (int k0 = kbeg; k0 < p.K; k0 += kstep) {
-        const bool more = k0 + kstep < p.K;
-        if (more) {
-            mg_load8(p.A, pa, m_ok, k0 + kstep, lh, p.K, a2);
-            mg_load8(p.B, pb, n_ok, k0 + kstep, lh, p.K, b2);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc = MG_MFMA(a[u], b[u], acc);
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a[u] = a2[u], b[u] = b2[u];
-        }
-    }
-    if (SPLIT) {
-        if (wv > 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) red[(wv - 1) * 1024 + i * 64 + lane] = acc[i];
-        }
-        __syncthreads();
-        if (wv > 0) return;
-#pragma unroll
-        for (int w2 = 0; w2 < 3; ++w2)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] += red[w2 * 1024 + i * 64 + lane];
-    }
-    if (!n_ok) return;
-    float add = 0.f;
-    if (p.bias) add = p.bias[n];
-    if (p.bias2) add += p.bias2[n];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int mo = 32 * tm + 8 * (i >> 2) + 4 * lh + (i & 3);
-        if (mo >= p.M) continue;
-        const long long at = rmap(p.cmap, mo) * p.ldc + n;
-        float v = acc[i] + add;
-        if (p.pos) v += p.pos[(long long)(mo % p.pos_T) * p.N + n];
-        if (p.res) v += p.res[at];
-        if (p.gelu_aux) v *= gelu_grad_exact(p.gelu_aux[at]);
-        if (p.accumulate) v += p.C[at];
-        p.C[at] = v;
-        if (p.gelu_out) p.gelu_out[at] = gelu_exact(v);
-    }
+    mg_gemm_body<SPLIT, false>(p);
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
@@ -198,118 +101,15 @@ __global__ __launch_bounds__(256) void mg_colsum_fin_kernel(ColG p) {
 }
 
 // ------------------------------------------------------------------------------------------------ attention
+// (the bodies: mtm_grad_body.h)
 // one wavefront per (b, head, query i): lane owns the keys lane, lane + 64, ...; L <= 256
-__global__ __launch_bounds__(256) void mg_attn_fwd_kernel(AttG p) {
-    __shared__ float sp[4][MG_ATT_MAX_L];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * 4 + wv;
-    if (w >= (long long)p.B * p.nh * p.L) return;
-    const int i = (int)(w % p.L), hh = (int)((w / p.L) % p.nh), b = (int)(w / ((long long)p.L * p.nh));
-    const size_t ld = 3 * (size_t)p.d;
-    const float* q = p.QKV + ((size_t)b * p.L + i) * ld + (size_t)hh * p.hd;
-    const float* Kb = p.QKV + (size_t)b * p.L * ld + p.d + (size_t)hh * p.hd;
-    const float* Vb = Kb + p.d;
-    float s[4], mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int j = lane + 64 * c;
-        s[c] = -INFINITY;
-        if (j < p.L) {
-            float a = 0.f;
-            for (int e = 0; e < p.hd; ++e) a += (q[e] * p.scale) * Kb[(size_t)j * ld + e];
-            s[c] = a;
-            mx = fmaxf(mx, a);
-        }
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        s[c] = lane + 64 * c < p.L ? expf(s[c] - mx) : 0.f;
-        sum += s[c];
-    }
-    sum = wave_sum(sum);
-    float* Pr = p.P + (((size_t)b * p.nh + hh) * p.L + i) * p.L;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int j = lane + 64 * c;
-        if (j < p.L) {
-            const float pr = s[c] / sum;
-            Pr[j] = pr;
-            sp[wv][j] = pr;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    for (int e = lane; e < p.hd; e += 64) {
-        float a = 0.f;
-        for (int j = 0; j < p.L; ++j) a += sp[wv][j] * Vb[(size_t)j * ld + e];
-        p.O[((size_t)b * p.L + i) * p.d + (size_t)hh * p.hd + e] = a;
-    }
-}
+__global__ __launch_bounds__(256) void mg_attn_fwd_kernel(AttG p) { mg_attn_fwd_body<false>(p); }
 
 // one wavefront per (b, head, key j): out[j][e] = alpha sum_i M[i][j] Z[i][e], queries ascending.  which 0: dV = P^T dO; 1: dK = dS^T Q scale
-__global__ __launch_bounds__(256) void mg_attn_col_kernel(AttG p, int which) {
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * 4 + wv;
-    if (w >= (long long)p.B * p.nh * p.L) return;
-    const int j = (int)(w % p.L), hh = (int)((w / p.L) % p.nh), b = (int)(w / ((long long)p.L * p.nh));
-    const float* Mb = p.P + ((size_t)b * p.nh + hh) * p.L * p.L + j;
-    const size_t ldz = which == 0 ? (size_t)p.d : 3 * (size_t)p.d;
-    const float* Z = (which == 0 ? p.dO : p.QKV) + (size_t)b * p.L * ldz + (size_t)hh * p.hd;
-    const float alpha = which == 0 ? 1.0f : p.scale;
-    float* out = p.dQKV + ((size_t)b * p.L + j) * 3 * p.d + (which == 0 ? 2 * p.d : p.d) + (size_t)hh * p.hd;
-    for (int e = lane; e < p.hd; e += 64) {
-        float a = 0.f;
-        for (int i = 0; i < p.L; ++i) a += Mb[(size_t)i * p.L] * Z[(size_t)i * ldz + e];
-        out[e] = a * alpha;
-    }
-}
+__global__ __launch_bounds__(256) void mg_attn_col_kernel(AttG p, int which) { mg_attn_col_body<false>(p, which); }
 
 // one wavefront per (b, head, query i): dP = dO V^T, dS = P (dP - sum_j dP P) over P in place, dQ = dS K scale (keys ascending)
-__global__ __launch_bounds__(256) void mg_attn_row_kernel(AttG p) {
-    __shared__ float sp[4][MG_ATT_MAX_L];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * 4 + wv;
-    if (w >= (long long)p.B * p.nh * p.L) return;
-    const int i = (int)(w % p.L), hh = (int)((w / p.L) % p.nh), b = (int)(w / ((long long)p.L * p.nh));
-    const size_t ld = 3 * (size_t)p.d;
-    const float* dO = p.dO + ((size_t)b * p.L + i) * p.d + (size_t)hh * p.hd;
-    const float* Kb = p.QKV + (size_t)b * p.L * ld + p.d + (size_t)hh * p.hd;
-    const float* Vb = Kb + p.d;
-    float* Pr = p.P + (((size_t)b * p.nh + hh) * p.L + i) * p.L;
-    float dp[4], pr[4], dot = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int j = lane + 64 * c;
-        dp[c] = 0.f;
-        pr[c] = 0.f;
-        if (j < p.L) {
-            float a = 0.f;
-            for (int e = 0; e < p.hd; ++e) a += dO[e] * Vb[(size_t)j * ld + e];
-            dp[c] = a;
-            pr[c] = Pr[j];
-            dot += a * pr[c];
-        }
-    }
-    dot = wave_sum(dot);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int j = lane + 64 * c;
-        if (j < p.L) {
-            const float ds = pr[c] * (dp[c] - dot);
-            Pr[j] = ds;
-            sp[wv][j] = ds;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    for (int e = lane; e < p.hd; e += 64) {
-        float a = 0.f;
-        for (int j = 0; j < p.L; ++j) a += sp[wv][j] * Kb[(size_t)j * ld + e];
-        p.dQKV[((size_t)b * p.L + i) * ld + (size_t)hh * p.hd + e] = a * p.scale;
-    }
-}
+__global__ __launch_bounds__(256) void mg_attn_row_kernel(AttG p) { mg_attn_row_body<false>(p); }
 
 // ------------------------------------------------------------------------------------------------ embedding, gather, scatter
 // encoder row j -> (key, timestep): the keys in order, the visible timesteps of each ascending
@@ -453,6 +253,7 @@ void mg_launch_gemm(GemmG& p, hipStream_t st) {
     if (tiles <= 0) return;
     for (GOp* op : {&p.A, &p.B})
         op->vec = op->s_k == 1 && !op->map_k && op->s_o % 4 == 0 && ((uintptr_t)op->p & 15) == 0 ? 1 : 0;
+    if (p.drop.thr) return mg_launch_gemm_drop(p, st);  // (mtm_dropout.hip; never with splitk)
     if (p.splitk) {
         M3PC_MG_PICK(2);
         hipLaunchKernelGGL(mg_gemm_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, p);
@@ -483,14 +284,17 @@ void mg_launch_colsum(ColG& p, double* scratch, hipStream_t st) {
 }
 
 void mg_launch_attn_fwd(const AttG& p, hipStream_t st) {
+    if (p.drop.thr) return mg_launch_attn_fwd_drop(p, st);
     M3PC_MG_PICK(7);
     hipLaunchKernelGGL(mg_attn_fwd_kernel, dim3(blocks4((long long)p.B * p.nh * p.L)), dim3(256), 0, st, p);
 }
 void mg_launch_attn_col(const AttG& p, int which, hipStream_t st) {
+    if (p.drop.thr && which == 0) return mg_launch_attn_col_drop(p, st);  // (dK reads dS: the launch without dropout)
     M3PC_MG_PICK(8);
     hipLaunchKernelGGL(mg_attn_col_kernel, dim3(blocks4((long long)p.B * p.nh * p.L)), dim3(256), 0, st, p, which);
 }
 void mg_launch_attn_row(const AttG& p, hipStream_t st) {
+    if (p.drop.thr) return mg_launch_attn_row_drop(p, st);
     M3PC_MG_PICK(9);
     hipLaunchKernelGGL(mg_attn_row_kernel, dim3(blocks4((long long)p.B * p.nh * p.L)), dim3(256), 0, st, p);
 }
@@ -620,6 +424,13 @@ struct Run {
     int B, T, d, ff, Le;
     u64 bits[4];
     int kept[4], eoff[4];
+    DropG drop;  // this call's draw (thr == 0: no dropout); c3 is set per site
+    // site s of layer li on an (R, C) matrix (s 1, 2, 3) or on the attention probabilities (s 0)
+    DropG site(int li, int s) const {
+        DropG x = drop;
+        x.c3 = (s == 0 ? MG_DROP_ATTN : MG_DROP_MATRIX) | (unsigned int)(4 * li + s) << 8;
+        return x;
+    }
     float* Wt(const std::string& n) const { return W(h, n).f; }
     float* Gr(const std::string& n) const { return g->grad + g->par[g->idx.at(n)].off; }
 };
@@ -734,7 +545,7 @@ void run_ln_bwd(const Run& r, const float* dY, const float* X, RMap xmap, const 
     mg_launch_ln_bwd(p, r.st);
 }
 
-AttG att_params(const Run& r, const Obj::Lay& y, int L) {
+AttG att_params(const Run& r, const Obj::Lay& y, int L, int li) {
     AttG a;
     memset(&a, 0, sizeof(a));
     a.QKV = y.QKV;
@@ -748,50 +559,66 @@ AttG att_params(const Run& r, const Obj::Lay& y, int L) {
     a.nh = r.h->nh;
     a.hd = r.h->hd;
     a.scale = 1.0f / sqrtf((float)r.h->hd);
+    a.drop = r.site(li, 0);
     return a;
 }
 
-void block_fwd(const Run& r, const std::string& pfx, const Obj::Lay& y, float* Xout, int L) {
+// li: the layer's index in g->lay (the dropout sites 4 li + s; mtm_grad.h, DROPOUT)
+void block_fwd(const Run& r, const std::string& pfx, const Obj::Lay& y, float* Xout, int L, int li) {
     const int R = r.B * L, d = r.d, ff = r.ff;
     run_ln_fwd(r, y.Xin, NOMAP, pfx + ".norm1", y.Hn1, y.st1, R);
     GemmG p = gemm_fwd(y.Hn1, d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_weight"), R, 3 * d, d, y.QKV, 3 * d, NOMAP, r.Wt(pfx + ".self_attn.in_proj_bias"));
     run_gemm(r, p);
-    const AttG a = att_params(r, y, L);
+    const AttG a = att_params(r, y, L, li);
     mg_launch_attn_fwd(a, r.st);
     p = gemm_fwd(y.O, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.weight"), R, d, d, y.X1, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.bias"));
     p.res = y.Xin;
+    p.drop = r.site(li, 1);
     run_gemm(r, p);
     run_ln_fwd(r, y.X1, NOMAP, pfx + ".norm2", y.Hn2, y.st2, R);
     p = gemm_fwd(y.Hn2, d, NOMAP, r.Wt(pfx + ".linear1.weight"), R, ff, d, y.Fpre, ff, NOMAP, r.Wt(pfx + ".linear1.bias"));
     p.gelu_out = y.Fact;
+    p.drop = r.site(li, 2);
     run_gemm(r, p);
     p = gemm_fwd(y.Fact, ff, NOMAP, r.Wt(pfx + ".linear2.weight"), R, d, ff, Xout, d, NOMAP, r.Wt(pfx + ".linear2.bias"));
     p.res = y.X1;
+    p.drop = r.site(li, 3);
     run_gemm(r, p);
 }
 
+// dY = dX * k of site (li, s) over (R, d) rows into `into`; without dropout dX itself
+const float* drop_rows(const Run& r, int li, int s, int R, float* into) {
+    if (!r.drop.thr) return r.g->dX;
+    const DropRowsG p = {r.g->dX, into, R, r.d, r.site(li, s)};
+    mg_launch_drop_rows(p, r.st);
+    return into;
+}
+
 // g->dX: in, the gradient of the block's output; out, of its input
-void block_bwd(const Run& r, const std::string& pfx, const Obj::Lay& y, int L) {
+void block_bwd(const Run& r, const std::string& pfx, const Obj::Lay& y, int L, int li) {
     Obj* g = r.g;
     const int R = r.B * L, d = r.d, ff = r.ff;
-    GemmG p = gemm_dx(g->dX, d, NOMAP, r.Wt(pfx + ".linear2.weight"), R, ff, d, g->dF, ff, NOMAP);
+    const float* dY = drop_rows(r, li, 3, R, g->dO);  // (dO is free until the out_proj dX product below)
+    GemmG p = gemm_dx(dY, d, NOMAP, r.Wt(pfx + ".linear2.weight"), R, ff, d, g->dF, ff, NOMAP);
     p.gelu_aux = y.Fpre;
+    p.drop = r.site(li, 2);
     run_gemm(r, p);
-    p = gemm_dw(g->dX, d, NOMAP, y.Fact, ff, NOMAP, d, ff, R, r.Gr(pfx + ".linear2.weight"));
+    p = gemm_dw(dY, d, NOMAP, y.Fact, ff, NOMAP, d, ff, R, r.Gr(pfx + ".linear2.weight"));
     run_gemm(r, p);
-    run_colsum_rows(r, g->dX, R, d, r.Gr(pfx + ".linear2.bias"));
+    run_colsum_rows(r, dY, R, d, r.Gr(pfx + ".linear2.bias"));
     p = gemm_dx(g->dF, ff, NOMAP, r.Wt(pfx + ".linear1.weight"), R, d, ff, g->dH, d, NOMAP);
     run_gemm(r, p);
     p = gemm_dw(g->dF, ff, NOMAP, y.Hn2, d, NOMAP, ff, d, R, r.Gr(pfx + ".linear1.weight"));
     run_gemm(r, p);
     run_colsum_rows(r, g->dF, R, ff, r.Gr(pfx + ".linear1.bias"));
     run_ln_bwd(r, g->dH, y.X1, NOMAP, y.st2, pfx + ".norm2", g->dX, R, true);
-    p = gemm_dx(g->dX, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.weight"), R, d, d, g->dO, d, NOMAP);
+    dY = drop_rows(r, li, 1, R, g->dH);  // (dH is free from the LayerNorm backward above to the Q|K|V dX product below)
+    p = gemm_dx(dY, d, NOMAP, r.Wt(pfx + ".self_attn.out_proj.weight"), R, d, d, g->dO, d, NOMAP);
     run_gemm(r, p);
-    p = gemm_dw(g->dX, d, NOMAP, y.O, d, NOMAP, d, d, R, r.Gr(pfx + ".self_attn.out_proj.weight"));
+    p = gemm_dw(dY, d, NOMAP, y.O, d, NOMAP, d, d, R, r.Gr(pfx + ".self_attn.out_proj.weight"));
     run_gemm(r, p);
-    run_colsum_rows(r, g->dX, R, d, r.Gr(pfx + ".self_attn.out_proj.bias"));
-    const AttG a = att_params(r, y, L);
+    run_colsum_rows(r, dY, R, d, r.Gr(pfx + ".self_attn.out_proj.bias"));
+    const AttG a = att_params(r, y, L, li);
     mg_launch_attn_col(a, 0, r.st);
     mg_launch_attn_row(a, r.st);
     mg_launch_attn_col(a, 1, r.st);
@@ -841,6 +668,14 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     r.d = h->d;
     r.ff = h->ff;
     r.Le = 0;
+    memset(&r.drop, 0, sizeof(r.drop));
+    if (g->drop_p > 0.0) {  // (every refusal lies before this call)
+        const DropG dg = mg_drop_make(g->drop_p, g->drop_seed, g->drop_draw);
+        if (dg.thr) {  // (p below 2^-32 drops nothing: no launch differs and the draw stays)
+            r.drop = dg;
+            ++g->drop_draw;
+        }
+    }
     for (int k = 0; k < 4; ++k) {
         r.bits[k] = bits[k];
         r.kept[k] = __builtin_popcountll(bits[k]);
@@ -859,7 +694,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     e.X = enc0;
     mg_launch_embed(e, st);
     for (int l = 0; l < nE; ++l)
-        block_fwd(r, "encoder.layers." + std::to_string(l), g->lay[l], l + 1 < nE ? g->lay[l + 1].Xin : g->XencOut, r.Le);
+        block_fwd(r, "encoder.layers." + std::to_string(l), g->lay[l], l + 1 < nE ? g->lay[l + 1].Xin : g->XencOut, r.Le, l);
     run_ln_fwd(r, g->XencOut, NOMAP, "encoder.norm", g->EncN, g->st_enc, Re);
     e.src = g->EncN;
     e.dst = g->Zin;
@@ -875,7 +710,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         run_gemm(r, p);
     }
     for (int l = 0; l < nD; ++l)
-        block_fwd(r, "decoder.layers." + std::to_string(l), g->lay[nE + l], l + 1 < nD ? g->lay[nE + l + 1].Xin : g->XdecOut, L4);
+        block_fwd(r, "decoder.layers." + std::to_string(l), g->lay[nE + l], l + 1 < nD ? g->lay[nE + l + 1].Xin : g->XdecOut, L4, nE + l);
     run_ln_fwd(r, g->XdecOut, NOMAP, "decoder.norm", g->DecN, g->st_dec, Rd);
     for (int j = 0; j < 3; ++j) {
         const int k = HK[j], F = h->feat[k];
@@ -966,7 +801,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
         run_colsum_rows(r, g->dls, RT, A, r.Gr(hl + ".bias"));
     }
     run_ln_bwd(r, dDecN, g->XdecOut, NOMAP, g->st_dec, "decoder.norm", g->dX, Rd, false);
-    for (int l = nD - 1; l >= 0; --l) block_bwd(r, "decoder.layers." + std::to_string(l), g->lay[nE + l], L4);
+    for (int l = nD - 1; l >= 0; --l) block_bwd(r, "decoder.layers." + std::to_string(l), g->lay[nE + l], L4, nE + l);
     for (int k = 0; k < 4; ++k) {  // the decoder embedding: g->dX is the gradient of its output, g->dH becomes that of its input
         const std::string kn = KEYN[k];
         const RMap km = {T, L4, k * T};
@@ -985,7 +820,7 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     e.dst = dEncN;
     mg_launch_scatter(e, st);
     run_ln_bwd(r, dEncN, g->XencOut, NOMAP, g->st_enc, "encoder.norm", g->dX, Re, false);
-    for (int l = nE - 1; l >= 0; --l) block_bwd(r, "encoder.layers." + std::to_string(l), g->lay[l], r.Le);
+    for (int l = nE - 1; l >= 0; --l) block_bwd(r, "encoder.layers." + std::to_string(l), g->lay[l], r.Le, l);
     for (int k = 0; k < 4; ++k) {
         if (!r.kept[k]) continue;  // (a fully hidden key: exact zeros)
         const std::string kn = KEYN[k];
@@ -1005,14 +840,30 @@ int mg_run(Obj* g, int batch, const float* states, const float* actions, const f
     return 0;
 }
 
+// the limits of the keep-mask counters (mtm_grad.h, DROPOUT); nothing to check without dropout.  (With the sizes
+// m3pc_mtm_grad_create accepts -- max_batch 4 T max(3 d, ff) <= 2^31, head dim >= 32, L <= 256 -- no site reaches 2^32 quads: the
+// second refusal is there for the day those limits move.)
+static int mg_drop_check(const struct m3pc_mtm_grad* g, int batch, const char* who) {
+    if (!(g->drop_p > 0.0)) return 0;
+    const m3pc_handle* h = g->h;
+    const int nl = h->dm.n_enc_layer + h->dm.n_dec_layer;
+    if (nl > 64) return fail(M3PC_EINVAL, "%s: dropout numbers its sites 4 layer + s in 8 bits, the model has %d layers (> 64)", who, nl);
+    const unsigned long long L = 4ull * h->T, R = (unsigned long long)batch * L, lim = 1ull << 32;
+    const unsigned long long mq = ((R + 3) / 4) * (unsigned long long)std::max(h->d, h->ff), aq = R * h->nh * ((L + 3) / 4);
+    if (mq > lim || aq > lim) return fail(M3PC_EINVAL, "%s: a dropout site of batch %d has more than 2^32 quads (%llu)", who, batch, std::max(mq, aq));
+    return 0;
+}
+
 int mg_precheck(const struct m3pc_mtm_grad* g, int batch, const unsigned char* const masks[4], int flags, int loss_keys, const char* who,
                 u64 bits[4]) {
     CHK(mb_check(g->h->dm, g->max_batch, batch, masks, flags, loss_keys, who, true, bits));
+    CHK(mg_drop_check(g, batch, who));
     return mb_state(g->h, who);
 }
 int mg_precheck_replay(const struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, int mode, const int* traj_index, const int* start_index,
                        int index_on_device, const unsigned char* const masks[4], int flags, int loss_keys, const char* who, u64 bits[4]) {
     CHK(mb_check(g->h->dm, g->max_batch, batch, masks, flags, loss_keys, who, true, bits));
+    CHK(mg_drop_check(g, batch, who));
     CHK(mb_fits(g->h, rb, who));
     CHK(replay_check_segments(rb, batch, mode, traj_index, start_index, index_on_device, who));
     return mb_state(g->h, who);
@@ -1086,6 +937,23 @@ int m3pc_mtm_grad_replay(struct m3pc_mtm_grad* g, m3pc_replay* rb, int batch, in
     CHK(mg_ensure(g));
     return mg_run_replay(g, rb, batch, mode, traj_index, start_index, index_on_device, seed, step, bits, eps, entropy_reg, nullptr, flags,
                          loss_keys, record, out_traj, out_start, (hipStream_t)stream, who);
+}
+
+int m3pc_mtm_grad_set_dropout(struct m3pc_mtm_grad* g, double p, unsigned long long seed, unsigned long long draw) {
+    if (!std::isfinite(p) || p < 0.0 || p >= 1.0) return fail(M3PC_EINVAL, "m3pc_mtm_grad_set_dropout: p %g is not a finite number in [0, 1)", p);
+    if (!g) return fail(M3PC_EINVAL, "m3pc_mtm_grad_set_dropout: null g");
+    g->drop_p = p;
+    g->drop_seed = seed;
+    g->drop_draw = draw;
+    return 0;
+}
+
+int m3pc_mtm_grad_get_dropout(struct m3pc_mtm_grad* g, double* p, unsigned long long* seed, unsigned long long* next_draw) {
+    if (!g) return fail(M3PC_EINVAL, "m3pc_mtm_grad_get_dropout: null g");
+    if (p) *p = g->drop_p;
+    if (seed) *seed = g->drop_seed;
+    if (next_draw) *next_draw = g->drop_draw;
+    return 0;
 }
 
 int m3pc_mtm_grad_export(struct m3pc_mtm_grad* g, const m3pc_named_tensor* tensors, int n, void* stream) {

@@ -1,6 +1,8 @@
 // Philox4x32-10 (Salmon et al., SC'11), the library's one counter-based generator: key = (seed lo, seed hi), counter = (block, step lo,
 // step hi, array).  The arrays: 0 = eps and 1 = expo of m3pc_draw_variates (select.hip), 2 = the segment draws, 3 / 4 = the round keys
-// of the online / offline transition permutation of the replay buffer (replay.hip).
+// of the online / offline transition permutation of the replay buffer (replay.hip); 5 / 6 = the dropout keep masks of a matrix site /
+// of the attention probabilities (mtm_grad.h, DROPOUT), where block = the group of four elements, step = the draw and the array word
+// also carries the site: array | site << 8.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -2,8 +2,10 @@
 ``omtm.forward_loss`` and ``loss.backward()`` through the whole model in one library call -- a raw batch in, one gradient tensor per
 parameter out, under the reference's ``state_dict`` names.  The optimizers stay torch's.
 
-The model differentiated is the EVAL-MODE one: no dropout.  The shipped configs train with ``dropout: 0.1``; drawing keep-masks is
-not in the library, so a step made from these gradients is the step of a model whose dropout is switched off.
+The model differentiated is the eval-mode one until ``set_dropout(p, seed)`` switches on the four dropout sites of every transformer
+layer of the training-mode model (the shipped configs train with ``dropout: 0.1``).  The keep-masks are the library's own
+counter-based stream -- a pure function of (seed, draw, site, element), NOT torch's generator: a step is reproducible from
+(seed, draw), not comparable mask for mask with ``model.train()`` under ``torch.manual_seed``.
 """
 from __future__ import annotations
 
@@ -64,7 +66,8 @@ def param_shapes(S: int, A: int, d: int, n_enc_layer: int, n_dec_layer: int) -> 
 
 class DeviceMTMGrad:
     """One m3pc_mtm_grad object on a planner's (or a bare ``capi.Handle``'s) device.  It reads the handle's fp32 weights and tokenizers
-    at the time of each call and owns its workspace; the handle must outlive it.  Eval-mode model: no dropout (module docstring)."""
+    at the time of each call and owns its workspace; the handle must outlive it.  Eval-mode model unless ``set_dropout`` says
+    otherwise (module docstring)."""
 
     def __init__(self, planner_or_handle, max_batch: int):
         self.handle = getattr(planner_or_handle, "handle", planner_or_handle)
@@ -90,6 +93,18 @@ class DeviceMTMGrad:
 
     def _stream(self):
         return capi._stream(self.device)
+
+    # -- dropout (host state: no device call) ---------------------------------------------------------
+    def set_dropout(self, p: float, seed: int, draw: int = 0):
+        """m3pc_mtm_grad_set_dropout: every later gradient call (this object's, and a trainer's on it) drops with probability ``p``
+        under the keep-masks of (seed, draw) and advances ``draw`` by one.  p = 0 switches dropout off."""
+        capi.check(self.lib.m3pc_mtm_grad_set_dropout(self._g, float(p), int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1)))
+
+    def get_dropout(self):
+        """-> (p, seed, next_draw): what the next gradient call will use."""
+        p, seed, draw = C.c_double(), C.c_ulonglong(), C.c_ulonglong()
+        capi.check(self.lib.m3pc_mtm_grad_get_dropout(self._g, C.byref(p), C.byref(seed), C.byref(draw)))
+        return p.value, seed.value, draw.value
 
     # -- the calls ---------------------------------------------------------------------------------
     def grad_record(self, batch, masks, entropy_reg: float, form: str = "finetune", eps=None, flags=None, loss_keys=None) -> torch.Tensor:
@@ -119,7 +134,8 @@ class DeviceMTMGrad:
 
     def grad(self, batch, masks, entropy_reg: float, form: str = "finetune", eps=None):
         """-> (record, {name: device tensor}): the 15 floats of m3pc_mtm_loss and the gradient of its ``total`` with respect to every
-        parameter ("finetune": Learner.compute_mtm_loss, "pretrain": omtm.forward_loss(norm="l2")).  Eval-mode model: no dropout."""
+        parameter ("finetune": Learner.compute_mtm_loss, "pretrain": omtm.forward_loss(norm="l2")).  With ``set_dropout``: of the
+        dropped forward under the current draw."""
         rec = self.grad_record(batch, masks, entropy_reg, form, eps)
         return rec, self.export()
 

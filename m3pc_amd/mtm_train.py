@@ -4,7 +4,9 @@ the two groups of ``omtm.configure_optimizers``, the LambdaLR schedule and the f
 OWN weights, with every derived weight form refreshed behind it.  Nothing crosses the host; the next plan step runs on the trained
 weights.  Arithmetic order: m3pc_amd/csrc/mtm_opt.h.
 
-The model trained is the EVAL-MODE one: no dropout (m3pc_amd/mtm_grad.py).
+The model trained is the eval-mode one unless the trainer is created with ``dropout=p``: then every step drops with the library's own
+keep-mask stream (m3pc_amd/mtm_grad.py), step i of the trainer's life under draw i, and ``get_state`` / ``set_state`` carry (p, seed,
+next draw) so that a resumed run continues the stream.
 """
 from __future__ import annotations
 
@@ -48,9 +50,10 @@ class DeviceMTMTrainer:
     """One m3pc_mtm_opt object (and the m3pc_mtm_grad object it steps) on a planner's handle.
 
     opt_args: learning_rate, weight_decay, num_train_steps, target_entropy, init_log_temperature and optionally beta1, beta2, eps,
-    warmup_steps, temp_learning_rate, temp_beta1, temp_beta2, temp_eps (``capi.MtmOptArgs.make``)."""
+    warmup_steps, temp_learning_rate, temp_beta1, temp_beta2, temp_eps (``capi.MtmOptArgs.make``).
+    dropout, dropout_seed: ``self.grad.set_dropout(dropout, dropout_seed)`` (0: the eval-mode model)."""
 
-    def __init__(self, planner, max_batch: int, **opt_args):
+    def __init__(self, planner, max_batch: int, dropout: float = 0.0, dropout_seed: int = 0, **opt_args):
         self.planner = planner if hasattr(planner, "handle") else None
         self.handle = getattr(planner, "handle", planner)
         self.lib = self.handle.lib
@@ -61,6 +64,8 @@ class DeviceMTMTrainer:
         self.shapes = self.grad.shapes
         self._o = C.c_void_p()
         try:
+            if dropout:
+                self.grad.set_dropout(dropout, dropout_seed)
             capi.check(self.lib.m3pc_mtm_opt_create(self.grad._g, C.byref(self.args), C.byref(self._o)))
         except Exception:
             self.grad.close()
@@ -102,12 +107,19 @@ class DeviceMTMTrainer:
         st = capi.MtmOptState()
         with torch.cuda.device(self.device):
             capi.check(self.lib.m3pc_mtm_opt_get_state(self._o, C.byref(st)))
-        return {n: getattr(st, n) for n, _ in capi.MtmOptState._fields_}
+        out = {n: getattr(st, n) for n, _ in capi.MtmOptState._fields_}
+        out["dropout"], out["dropout_seed"], out["dropout_next_draw"] = self.grad.get_dropout()
+        return out
 
-    def set_state(self, sched_step: int, temp_step: int, log_temperature: float, temp_exp_avg: float = 0.0, temp_exp_avg_sq: float = 0.0):
+    def set_state(self, sched_step: int, temp_step: int, log_temperature: float, temp_exp_avg: float = 0.0, temp_exp_avg_sq: float = 0.0,
+                  temperature=None, dropout=None, dropout_seed: int = 0, dropout_next_draw: int = 0):
+        """What ``get_state`` returned (``set_state(**get_state())``).  temperature is derived, not set; dropout None leaves the
+        keep-mask stream where it stands."""
         st = capi.MtmOptState(int(sched_step), int(temp_step), float(log_temperature), float(temp_exp_avg), float(temp_exp_avg_sq), 0.0)
         with torch.cuda.device(self.device):
             capi.check(self.lib.m3pc_mtm_opt_set_state(self._o, C.byref(st)))
+        if dropout is not None:
+            self.grad.set_dropout(dropout, dropout_seed, dropout_next_draw)
 
     # -- the steps ----------------------------------------------------------------------------------
     def opt_step(self):
@@ -223,12 +235,13 @@ class DeviceMTMTrainer:
     # -- a torch learner in and out -----------------------------------------------------------------
     @classmethod
     def from_learner(cls, learner, planner=None, max_batch: Optional[int] = None, num_train_steps: Optional[int] = None,
-                     warmup_steps: Optional[int] = None):
+                     warmup_steps: Optional[int] = None, dropout=None, dropout_seed: int = 0):
         """A trainer that continues where ``learner``'s torch optimizers stand: hyper-parameters from ``learner.cfg`` and the
         optimizers' groups, AdamW state by parameter identity (``learner.mtm.state_dict(keep_vars=True)``), ``mtm_scheduler.last_epoch``,
         the temperature optimizer's state and ``log_temperature``.  The planner (default ``learner._hip_planner``, as ``attach`` leaves
         it) must already hold the model's weights.  num_train_steps / warmup_steps: default ``learner.cfg``'s (the schedule is the library's
-        closed form, not the scheduler's lambda)."""
+        closed form, not the scheduler's lambda).  dropout: None / "eval": the eval-mode model; "device": ``learner.mtm.config.dropout``
+        on the library's keep-mask stream of ``dropout_seed``; a number: that probability."""
         planner = getattr(learner, "_hip_planner", None) if planner is None else planner
         if planner is None:
             raise capi.M3pcError("from_learner: no planner (attach(learner) first, or pass planner=)")
@@ -244,7 +257,13 @@ class DeviceMTMTrainer:
                 raise capi.M3pcError("from_learner: learner.cfg has no num_train_steps; pass num_train_steps=")
         if warmup_steps is None:
             warmup_steps = getattr(cfg, "warmup_steps", 0) or 0
-        self = cls(planner, int(max_batch if max_batch is not None else getattr(cfg, "traj_batch_size", 1)), learning_rate=base_lr, weight_decay=wd,
+        if dropout == "device":
+            mc = getattr(model, "config", None)
+            p_drop = float((mc.get("dropout", 0) if isinstance(mc, dict) else getattr(mc, "dropout", 0)) or 0)
+        else:
+            p_drop = 0.0 if dropout in (None, "eval") else float(dropout)
+        self = cls(planner, int(max_batch if max_batch is not None else getattr(cfg, "traj_batch_size", 1)), dropout=p_drop,
+                   dropout_seed=dropout_seed, learning_rate=base_lr, weight_decay=wd,
                    num_train_steps=int(num_train_steps), warmup_steps=int(warmup_steps),
                    beta1=g0["betas"][0], beta2=g0["betas"][1], eps=g0["eps"], temp_learning_rate=tg["lr"], temp_beta1=tg["betas"][0],
                    temp_beta2=tg["betas"][1], temp_eps=tg["eps"], target_entropy=float(model.target_entropy),

@@ -1306,7 +1306,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
         return raw_batch_loss(self.handle, batch, masks, float(entropy_reg), "finetune", eps, capi.PREC_FP32)
 
     def mtm_update(self, batch, data_shapes, discrete_map, model, optimizer, scheduler, temp_optimizer, masks=None, eps=None,
-                   dropout=None, sync=True, native=False):
+                   dropout=None, sync=True, native=False, dropout_seed=0):
         """Learner.mtm_update (finetune_omtm/learner.py:506-538) with its forward and ``loss.backward()`` in one library call
         (m3pc_mtm_grad): the gradients of ``model``'s parameters come from the device (``DeviceMTMGrad.backward_into``), then
         ``optimizer.step()``, ``scheduler.step()`` and the temperature step on ``temperature * (entropy - target_entropy)`` with the
@@ -1315,8 +1315,12 @@ class HipPlanner(GoalMixin, LockstepMixin):
         ``sync`` (the default) the WHOLE state_dict is uploaded to the handle before every step -- a full ``m3pc_load_weights``, its stream
         synchronise included; a caller that steps often should follow the tensors itself and pass ``sync=False``, as ``attach`` does
         (its ``_sync`` sends only what the last optimizer step moved).
-        THE GRADIENT IS THE EVAL-MODE MODEL'S: NO DROPOUT.  A model in training mode whose config has ``dropout > 0`` is refused
-        unless ``dropout="eval"`` says that a step without dropout is what the caller wants.
+        dropout: the gradient is the eval-mode model's unless told otherwise, so a model in training mode whose config has
+        ``dropout > 0`` is refused unless the caller says which step it wants: ``dropout="device"`` drops on the device at the four
+        sites of every transformer layer with ``config.dropout``, under the library's own keep-mask stream of ``dropout_seed`` (not
+        torch's generator; call i with dropout on the gradient object or trainer uses draw i -- a call with ``dropout="eval"`` in between
+        neither uses nor resets the draw, only another ``dropout_seed`` restarts the stream at draw 0); ``dropout="eval"`` takes the
+        step without dropout.
         native: the whole step as one library call (m3pc_mtm_train_step, ``DeviceMTMTrainer``) on the planner's OWN weights: the
         first native call imports the state of ``optimizer`` / ``scheduler`` / ``temp_optimizer`` (a shim with ``mtm``,
         ``mtm_optimizer``, ``mtm_scheduler``, ``temp_optimizer``, ``cfg``; ``sync`` uploads the module's weights for it, once), later
@@ -1325,9 +1329,21 @@ class HipPlanner(GoalMixin, LockstepMixin):
         from .mtm import form_settings, loss_tuple
         from .mtm_grad import DeviceMTMGrad
         p_drop = float(_cfg_get(getattr(model, "config", None), "dropout", 0) or 0)
-        if getattr(model, "training", False) and p_drop > 0 and dropout != "eval":
+        if dropout not in (None, "eval", "device"):
+            raise ValueError('dropout must be None, "eval" or "device"')
+        if getattr(model, "training", False) and p_drop > 0 and dropout not in ("eval", "device"):
             raise capi.M3pcError(f"mtm_update differentiates the eval-mode model (no dropout) but the model trains with dropout={p_drop}: "
-                                 "pass dropout=\"eval\" to take the step without dropout, or keep loss.backward() in torch")
+                                 "pass dropout=\"device\" to drop on the device with the library's own keep-masks, dropout=\"eval\" to take "
+                                 "the step without dropout, or keep loss.backward() in torch")
+        want = (p_drop if dropout == "device" and getattr(model, "training", False) else 0.0, int(dropout_seed))
+
+        def _set_dropout(gobj):  # (only another seed restarts the stream at draw 0: "eval" switches p off and keeps seed and draw)
+            p0, seed0, draw0 = gobj.get_dropout()
+            if want[0] > 0 and (p0 != want[0] or seed0 != want[1]):
+                gobj.set_dropout(want[0], want[1], draw0 if seed0 == want[1] else 0)
+            elif want[0] == 0 and p0 != 0:
+                gobj.set_dropout(0.0, seed0, draw0)
+
         if any(discrete_map.get(k, False) for k in batch):
             raise capi.M3pcError("discrete heads are not used by any m3pc config and are not supported")
         if masks is None:
@@ -1345,6 +1361,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
                 shim = types.SimpleNamespace(cfg=self.cfg, mtm=model, mtm_optimizer=optimizer, mtm_scheduler=scheduler, temp_optimizer=temp_optimizer)
                 tr = self._mtm_trainer = DeviceMTMTrainer.from_learner(shim, planner=self, max_batch=B)
                 tr._shim = shim
+            _set_dropout(tr.grad)
             return tr.train_step(batch, masks, eps, "finetune")
         if sync:
             self.load_state_dict({k: v.detach() for k, v in model.state_dict().items()})
@@ -1353,6 +1370,7 @@ class HipPlanner(GoalMixin, LockstepMixin):
             if g is not None:
                 g.close()
             g = self._mtm_grad = DeviceMTMGrad(self, B)
+        _set_dropout(g)
         entropy_reg = float(model.temperature().detach())
         model.zero_grad(set_to_none=True)
         rec = g.backward_into(model, batch, masks, entropy_reg, "finetune", eps, unused="none")  # (.grad = None where the reference leaves it)
@@ -1392,7 +1410,8 @@ def _versions(module):
 
 
 def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None, generator: Optional[torch.Generator] = None,
-           native_step: bool = False, eval_tol: Optional[float] = None, mtm_update: bool = False, **planner_kw):
+           native_step: bool = False, eval_tol: Optional[float] = None, mtm_update: bool = False, dropout: Optional[str] = None,
+           dropout_seed: int = 0, **planner_kw):
     """Rebind the plan path of a reference-style ``Learner`` onto the HIP library.
 
     precision: "bf16" (default since round 6: the configuration the headline is measured on) -- the bf16 candidate pass with the
@@ -1414,8 +1433,9 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     learner replica and passes a generator seeded identically); further keywords go to ``HipPlanner``.
     mtm_update: True rebinds ``learner.mtm_update(batch, data_shapes, discrete_map)`` too, onto ``HipPlanner.mtm_update`` with the
     learner's own ``mtm``, ``mtm_optimizer``, ``mtm_scheduler`` and ``temp_optimizer`` (further keywords -- masks, eps, dropout -- pass
-    through).  The device gradient is the eval-mode model's (no dropout): with a model in training mode whose config has dropout > 0
-    the rebound method raises unless called with ``dropout="eval"``.  "native": the same rebinding with the optimizers on the
+    through).  The device gradient is the eval-mode model's unless ``dropout="device"`` (here, or per call) switches on the library's own
+    keep-masks of ``dropout_seed``: with a model in training mode whose config has dropout > 0 the rebound method raises unless
+    ``dropout`` is "device" or "eval" (``HipPlanner.mtm_update``).  "native": the same rebinding with the optimizers on the
     device too (``HipPlanner.mtm_update(native=True)``: the planner's own weights move; ``learner._hip_planner._mtm_trainer.to_learner(learner)``
     writes weights and optimizer state back to torch).  The default (False) leaves ``mtm_update`` alone.
     Weights are followed per tensor: before each call the version counters of ``mtm`` / ``iql.qf`` are compared with the
@@ -1477,6 +1497,8 @@ def attach(learner, precision: str = "bf16", rescore_topk: int = 16, group=None,
     if mtm_update:
         def _mtm_update(self, batch, data_shapes, discrete_map, **kw):
             _sync()
+            kw.setdefault("dropout", dropout)
+            kw.setdefault("dropout_seed", dropout_seed)
             return planner.mtm_update(batch, data_shapes, discrete_map, self.mtm, self.mtm_optimizer, self.mtm_scheduler,
                                       self.temp_optimizer, sync=False, native=mtm_update == "native", **kw)
 

@@ -342,7 +342,7 @@ class DeviceReplayBuffer:
         """The gradient of that loss (m3pc_mtm_grad_replay) into ``grad``, a ``DeviceMTMGrad`` on this buffer's handle, for the batch
         ``traj_sample`` would return for the same arguments: per call the bits of ``traj_sample`` followed by ``grad.grad_record``.
         Returns the device record (15 floats; ``grad.export()`` hands out the gradients); ``step`` advances as in ``traj_sample``.
-        Eval-mode model: no dropout."""
+        Dropout is ``grad``'s: after ``grad.set_dropout(p, seed)`` the call drops under ``grad``'s current draw and advances it."""
         from .masks import mask_rows
         from .mtm import form_settings
         if grad.handle is not self.handle:  # (the library compares sizes and device only: another handle's weights would be differentiated)
@@ -364,7 +364,8 @@ class DeviceReplayBuffer:
     def mtm_train(self, trainer, n_steps: int, masks, batch_size: Optional[int] = None, form: str = "finetune"):
         """``n_steps`` whole training steps of the model (m3pc_mtm_train) on the batches ``traj_sample`` would draw at this ``step``,
         ``step + 1``, ...: ``trainer`` is a ``DeviceMTMTrainer`` on this buffer's handle (``trainer.train_from``).  Returns (records
-        (n_steps, 15), train_records (n_steps, 3)) on the device; ``step`` advances by n_steps.  Eval-mode model: no dropout."""
+        (n_steps, 15), train_records (n_steps, 3)) on the device; ``step`` advances by n_steps.  Dropout is ``trainer``'s
+        (``DeviceMTMTrainer(dropout=, dropout_seed=)``): step i of the call drops under the trainer's draw + i."""
         return trainer.train_from(self, n_steps, batch_size, masks, form)
 
     def split(self, batch_size: Optional[int] = None):

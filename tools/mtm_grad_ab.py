@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of the device gradient of the masked-trajectory loss (m3pc_mtm_grad) against what a user of the library does without it, in ONE
 process on one box: forward + ``loss.backward()`` of one traj_sample batch (finetune_omtm/learner.py:506-538 without the optimizer
-steps) from an idle device until the device is idle again, fp32, eval-mode model (no dropout on either side), on the headline
+steps) from an idle device until the device is idle again, fp32, eval-mode model (no dropout on either side; `--dropout P` below), on the headline
 dimensions (hopper: S = 11, A = 3; n_embd 512, 4 heads, 2 encoder layers, 1 decoder layer) at two shapes: batch 64 / T = 32 and
 batch 512 / T = 8 (the shipped traj_batch_size).
 
@@ -12,7 +12,11 @@ batch 512 / T = 8 (the shipped traj_batch_size).
 Both legs read the same raw batch, masks and eps, and are checked against each other before anything is timed.  The legs alternate
 call by call; a call is timed by the host clock from an idle device until the device is idle again.  There is no bar: the table is
 recorded, whichever side wins.  `--out FILE` also writes the lines to a file (profiles/mtm_grad_ab.txt).  `--leg one` runs the library
-leg alone at one shape (for a kernel trace of its launches)."""
+leg alone at one shape (for a kernel trace of its launches).
+
+`--dropout P` measures something else: the library leg alone, twice -- one object without dropout, one after set_dropout(P, seed) (the
+library's own keep-mask stream) -- alternating call by call; what is recorded is the cost of the masks, with no bar.  In this mode
+`--out FILE` APPENDS (profiles/mtm_dropout_ab.txt, shared with tools/mtm_train_ab.py --dropout)."""
 import argparse
 import os
 import sys
@@ -68,6 +72,38 @@ def torch_leg(dims, ostats, batch, eps, masks, params, reg):
     return total.detach(), dict(zip(names, torch.autograd.grad(total, [params[k] for k in names], allow_unused=True)))
 
 
+def dropout_ab(a):
+    lines = [f"MTM gradient, dropout {a.dropout} against none: one m3pc_mtm_grad from an idle device until it is idle again, two objects on one "
+             f"handle, alternating call by call; S {S}, A {A}, n_embd 512, 4 heads, 2 + 1 layers, fp32; {a.calls} calls per leg after "
+             f"{a.warmup} warm-up calls; ms per call; {torch.cuda.get_device_name(0)}"]
+    for si, (B, T) in enumerate(SHAPES):
+        if a.shape >= 0 and si != a.shape:
+            continue
+        dims, hd, ostats, batch, eps, masks, params = setup(B, T)
+        objs = {"p = 0": DeviceMTMGrad(hd, B), f"p = {a.dropout}": DeviceMTMGrad(hd, B)}
+        objs[f"p = {a.dropout}"].set_dropout(a.dropout, 1)
+        per = {k: [] for k in objs}
+        for i in range(a.warmup + a.calls):
+            for k, obj in objs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = obj.grad_record(batch, masks, 0.1, "finetune", eps)
+                torch.cuda.synchronize()
+                if i >= a.warmup:
+                    per[k].append(1e3 * (time.perf_counter() - t0))
+                del out
+        lines.append(f"B {B:4d}, T {T:3d}  {'leg':10s} {'median':>9s} {'p10':>9s} {'p90':>9s}")
+        for k, v in per.items():
+            lines.append(f"                 {k:10s} {q(v, 0.5):9.4f} {q(v, 0.1):9.4f} {q(v, 0.9):9.4f}")
+        m0, m1 = (q(v, 0.5) for v in per.values())
+        lines.append(f"                 dropout costs {m1 - m0:+.4f} ms per call ({100 * (m1 / m0 - 1):+.2f} %; recorded, no bar)")
+        torch.cuda.synchronize()
+        for obj in objs.values():
+            obj.close()
+        hd.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=40, help="timed calls per leg (after warm-up)")
@@ -75,7 +111,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--leg", default="both", choices=("both", "one"))
     ap.add_argument("--shape", type=int, default=-1, help="index into the two shapes; -1: both")
+    ap.add_argument("--dropout", type=float, default=0.0, help="P > 0: the library leg with dropout P against without (module docstring)")
     a = ap.parse_args()
+    if a.dropout > 0:
+        lines = dropout_ab(a)
+        print("\n".join(lines))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     reg = 0.1
     lines = [f"MTM gradient A/B: forward + backward of one batch from an idle device until it is idle again, torch-eager autograd through the "
              f"restatement [torch] against m3pc_mtm_grad [one call]; S {S}, A {A}, n_embd 512, 4 heads, 2 + 1 layers, fp32, no dropout; "

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of one whole training step of the masked-trajectory model, in ONE process on one box, from an idle device until the device is
-idle again, fp32, eval-mode model (no dropout), on the headline dimensions (hopper: S = 11, A = 3; n_embd 512, 4 heads, 2 encoder
+idle again, fp32, eval-mode model (no dropout; `--dropout P` below), on the headline dimensions (hopper: S = 11, A = 3; n_embd 512, 4 heads, 2 encoder
 layers, 1 decoder layer) at batch 64 / T = 32 and batch 512 / T = 8:
 
   route A   HipPlanner.mtm_update(sync=False) with torch's AdamW (two groups), LambdaLR and temperature Adam on a torch module that
@@ -11,7 +11,11 @@ layers, 1 decoder layer) at batch 64 / T = 32 and batch 512 / T = 8:
 The routes alternate call by call on two planners that start from the same weights.  Then the split: the gradient call alone
 (DeviceMTMGrad.grad_record) and the optimizer half of route B alone (m3pc_mtm_opt_step: the AdamW launch, the temperature kernel and
 the re-derivation), each from idle to idle.  The condition recorded: route B is not slower than route A.  `--out FILE` also writes
-the lines to a file (profiles/mtm_train_ab.txt).  `--leg one` runs route B alone at one shape (for a kernel trace of its launches)."""
+the lines to a file (profiles/mtm_train_ab.txt).  `--leg one` runs route B alone at one shape (for a kernel trace of its launches).
+
+`--dropout P` measures something else: route B alone, twice -- one trainer without dropout, one with dropout P on the library's own
+keep-mask stream (DeviceMTMTrainer(dropout=P)) -- alternating call by call from the same weights; what is recorded is the cost of the
+masks, with no bar.  In this mode `--out FILE` APPENDS (profiles/mtm_dropout_ab.txt, shared with tools/mtm_grad_ab.py --dropout)."""
 import argparse
 import math
 import os
@@ -86,6 +90,38 @@ def timed(fn):
     return dt
 
 
+def dropout_ab(a):
+    """Route B without dropout against route B with dropout a.dropout: -> the lines."""
+    lines = [f"MTM training step, dropout {a.dropout} against none: one m3pc_mtm_train_step from an idle device until it is idle again, two trainers "
+             f"from the same weights, alternating call by call; S {S}, A {A}, n_embd 512, 4 heads, 2 + 1 layers, fp32; {a.calls} calls per leg "
+             f"after {a.warmup} warm-up calls; ms per call; {torch.cuda.get_device_name(0)}"]
+    for si, (B, T) in enumerate(SHAPES):
+        if a.shape >= 0 and si != a.shape:
+            continue
+        dims, sd, mk, batch, eps, masks = setup(B, T)
+        legs, per = {}, {}
+        for name, p in (("p = 0", 0.0), (f"p = {a.dropout}", a.dropout)):
+            pl = mk()
+            tr = DeviceMTMTrainer(pl, B, dropout=p, dropout_seed=1, target_entropy=-float(A), init_log_temperature=math.log(0.1), **HYPER)
+            legs[name], per[name] = (pl, tr), []
+        for i in range(a.warmup + a.calls):
+            for name, (pl, tr) in legs.items():
+                dt = timed(lambda: tr.train_step_record(batch, masks, eps))
+                if i >= a.warmup:
+                    per[name].append(dt)
+        lines.append(f"B {B:4d}, T {T:3d}  {'leg':26s} {'median':>9s} {'p10':>9s} {'p90':>9s}")
+        for name, v in per.items():
+            lines.append(f"                 {name:26s} {q(v, 0.5):9.4f} {q(v, 0.1):9.4f} {q(v, 0.9):9.4f}")
+        m0, m1 = (q(v, 0.5) for v in per.values())
+        lines.append(f"                 dropout costs {m1 - m0:+.4f} ms per step ({100 * (m1 / m0 - 1):+.2f} %; recorded, no bar); draws used: "
+                     f"{legs[f'p = {a.dropout}'][1].grad.get_dropout()[2]}")
+        torch.cuda.synchronize()
+        for pl, tr in legs.values():
+            tr.close()
+            pl.handle.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30, help="timed calls per route (after warm-up)")
@@ -93,7 +129,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--leg", default="both", choices=("both", "one"))
     ap.add_argument("--shape", type=int, default=-1, help="index into the two shapes; -1: both")
+    ap.add_argument("--dropout", type=float, default=0.0, help="P > 0: route B with dropout P against route B without (module docstring)")
     a = ap.parse_args()
+    if a.dropout > 0:
+        lines = dropout_ab(a)
+        print("\n".join(lines))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     lines = [f"MTM training-step A/B: one whole step from an idle device until it is idle again; route A = HipPlanner.mtm_update (device gradient, "
              f"torch AdamW + LambdaLR + temperature Adam) + the upload of the moved tensors (m3pc_load_weights), route B = one m3pc_mtm_train_step; "
              f"S {S}, A {A}, n_embd 512, 4 heads, 2 + 1 layers, fp32, no dropout; {a.calls} interleaved calls per route after {a.warmup} warm-up calls; "
